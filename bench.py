@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- ms per 2^20-point BLS12-377 G1 MSM on N MI355X (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps 50 --warmup 10
+    python bench.py --gpus 1 --steps 50 --warmup 10 [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -156,6 +156,18 @@ def seeded_scalars(seed, n):
     return bytes(out)
 
 
+def dump_outputs(dump_dir, results, coord_bytes):
+    """--dump-outputs: the affine result(s) the timed path returned in its last step, as DIR/result.npy.  Each
+    coordinate is split into little-endian 32-bit words, which float64 holds exactly: shape (results, 2 (x, y), words)."""
+    import numpy as np
+
+    if not results or any(r is None for r in results):
+        raise SystemExit("--dump-outputs: no step ran (pass --steps 1 or more)")
+    words = np.frombuffer(b"".join(results), dtype="<u4").astype(np.float64)
+    os.makedirs(dump_dir, exist_ok=True)
+    np.save(os.path.join(dump_dir, "result.npy"), words.reshape(len(results), 2, coord_bytes // 4))
+
+
 def fixed64_scalar_sets(torch, scalars_host, n, batch):
     """`batch` scalar sets on the device: the seeded set rotated by b entries (distinct MSMs, no 2 GB of host bignum work)."""
     d_one = torch.frombuffer(bytearray(scalars_host), dtype=torch.uint8).cuda().view(n, 32)
@@ -239,6 +251,7 @@ def side_workload(args, torch, msm, n):
                     "dtype": "u32 (29-bit limbs, 64-bit accumulate)",
                     "config": {"workload": "64 x 2^%d fixed-base G1 MSMs over one HBM-resident converted base set, host tail overlapped" % args.log_n}})
         alg = 32 * n + NUM_WINDOWS * 96 * n + 2 * NUM_WINDOWS * NUM_BUCKETS * 144 + 96
+    res = None
     for _ in range(args.warmup):
         res = step()
     torch.cuda.synchronize()
@@ -248,6 +261,8 @@ def side_workload(args, torch, msm, n):
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) * 1e3 / max(1, args.steps) / per_step
     out.update({"value": round(ms, 4), "ms_per_step": round(ms * per_step, 4), "whole_job_hbm_GBps": round(alg / (ms * 1e-3) / 1e9, 2)})
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res if args.workload == "fixed64" else [res], 32 if args.workload == "ed" else 48)
     if args.workload == "fixed64" and verify_fixed:
         # Every one of the 64 results against a closed form (after the timed region; the oracle is the checker).
         exp = fixed64_expected(n, batch, scalars_host)
@@ -291,6 +306,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--log-n", type=int, default=LOG_N, help="log2 of the point count (default 20: the metric's workload)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the affine result(s) of the last one to DIR/result.npy (rank 0; float64 32-bit words)")
     ap.add_argument(
         "--workload",
         choices=["g1", "ed", "fixed64"],
@@ -448,6 +465,8 @@ def main():
     stages["accumulate_kernel"] = acc_sum / max(1, args.steps)  # the timed region's own average
 
     out = None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, [result], 48)
     if rank == 0:
         glv_path = glv_single or (world > 1 and use_glv)
         te_path = te_single or (world > 1 and not use_glv and os.environ.get("MSM377_G1_FORM", "1") != "0")

@@ -27,8 +27,8 @@ def run_bench(extra, env_extra=None):
     return json.loads(lines[0])
 
 
-def test_single_gpu_line_and_two_rank_rehearsal():
-    one = run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--log-n", "16"])
+def test_single_gpu_line_and_two_rank_rehearsal(tmp_path):
+    one = run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--log-n", "16", "--dump-outputs", str(tmp_path)])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in one, key
     assert one["n_gpus"] == 1 and one["higher_is_better"] is False and one["vs_baseline"] is None
@@ -37,6 +37,12 @@ def test_single_gpu_line_and_two_rank_rehearsal():
     sec = roof["secondary"]
     assert sec["bound"] == "int32-mad" and 0 < sec["frac"] < 1 and abs(sec["frac"] - sec["achieved"] / sec["peak"]) < 1e-3
     assert one["cpu_baseline"]["kind"] == "port" and one["cpu_baseline"]["cores"] >= 1
+    # --dump-outputs: the last timed step's affine result, x and y as 32-bit words
+    import numpy as np
+
+    dumped = np.load(tmp_path / "result.npy")
+    assert dumped.shape == (1, 2, 12)
+    assert int.from_bytes(dumped[0, 0].astype("<u4").tobytes(), "little") == int(one["result_x"], 16)
     # plain `python bench.py --gpus 2`: the parent starts both ranks itself
     two = run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--log-n", "16"],
                     {"MSM377_BENCH_SINGLE_DEVICE": "1", "MSM377_BENCH_BACKEND": "gloo"})

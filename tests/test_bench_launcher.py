@@ -53,3 +53,21 @@ def test_roofline_traffic_comes_from_the_newest_profile():
     assert abs(nbytes - (2 * fetch_kb + write_kb) * 1024) <= 0.01 * nbytes
     assert tag in source
     assert bench.pmc_traffic_bytes(16) == (None, None)  # taken at 2^20 only
+
+
+def test_dump_outputs_holds_every_result_word_exactly(tmp_path):
+    """--dump-outputs: each result's x and y as little-endian 32-bit words in float64 (exact), one row per result."""
+    import random
+
+    import numpy as np
+
+    rnd = random.Random(20)
+    results = [b"\xff" * 96, bytes(96)] + [bytes(rnd.randrange(256) for _ in range(96)) for _ in range(3)]
+    bench.dump_outputs(str(tmp_path / "out"), results, 48)
+    a = np.load(tmp_path / "out" / "result.npy")
+    assert a.dtype == np.float64 and a.shape == (5, 2, 12)
+    assert a.astype("<u4").tobytes() == b"".join(results)
+    bench.dump_outputs(str(tmp_path / "ed"), [results[2][:64]], 32)
+    assert np.load(tmp_path / "ed" / "result.npy").shape == (1, 2, 8)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "none"), [None], 48)
