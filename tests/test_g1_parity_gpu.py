@@ -6,6 +6,7 @@ Bar: bit-exact (integer work).  Shapes follow the reference's own checks: end-to
 (src/ui/Benchmark.tsx:41-48) and the per-stage debug read-backs (src/submission/submission.ts:466-520,
 613-641, 724-798).
 """
+import contextlib
 import ctypes
 import random
 
@@ -36,9 +37,10 @@ def seeded_inputs(oracle, n, seed):
 
 
 def test_golden_vectors(engine, golden):
-    for name, case in golden.items():
-        if name.startswith("g1_"):
-            assert engine.msm(case["points"], case["scalars"]) == case["expected"], name
+    with util.edwards_only(engine):  # every golden G1 point lies in the prime-order subgroup
+        for name, case in golden.items():
+            if name.startswith("g1_"):
+                assert engine.msm(case["points"], case["scalars"]) == case["expected"], name
 
 
 def test_compute_msm_entry_point(golden):
@@ -64,9 +66,10 @@ def test_ragged_sizes_against_oracle(engine, oracle, n, windows):
     engine.set_narrow_max(1 << 16 if windows == "narrow" else 0)
     try:
         exp = util.oracle_msm(oracle, pts, ks)
-        assert engine.msm(pts, ks) == exp
-        d_p, d_s = dev(pts), dev(ks)
-        assert engine.msm_device(d_p.data_ptr(), d_s.data_ptr(), n) == exp
+        with util.edwards_only(engine):
+            assert engine.msm(pts, ks) == exp
+            d_p, d_s = dev(pts), dev(ks)
+            assert engine.msm_device(d_p.data_ptr(), d_s.data_ptr(), n) == exp
     finally:
         engine.set_narrow_max()
 
@@ -139,6 +142,29 @@ def test_narrow_windows_edge_cases(engine, oracle, golden):
         engine.set_narrow_max()
 
 
+def even_edge_scalars():
+    """Scalars at the edges of the even geometry (see test_even_window_geometry_edge_cases)."""
+    s15 = 0x7FFF
+    edge = [
+        s15 << 208, s15 << 223, s15 << 238,                      # the largest digit of each short window
+        (s15 << 208) + (0x8000 << 192),                          # a carry into window 13 wraps it to 0, carry on
+        (s15 << 208) + (s15 << 223) + (0x8000 << 192),           # ... through window 14 into the top window
+        (s15 << 208) + (s15 << 223) + (s15 << 238) + (0x8000 << 192),  # ... and out of it: does not fit (< 2^253)
+        (s15 << 238) + (s15 << 223) + (s15 << 208) + 0x7FFF,     # largest scalar that fits with no carry at all
+        (1 << 253) - 1, 1 << 253, (1 << 254) + 5,                # from 2^253 on: never fits
+        (1 << 208) - 1, 1 << 208, (1 << 223) - 1, 1 << 223, (1 << 238) - 1, 1 << 238,
+        0x8000 << 192, 0x7FFF << 192, R.R_ORDER - 1, R.R_ORDER - 2, 0, 1,
+    ]
+    assert [even_window_fits(k) for k in edge[3:10]] == [True, True, False, True, False, False, False]
+    return edge
+
+
+def even_window_fits(k):
+    """Whether scalar k fits the even geometry's top window (otherwise the call reruns on sixteen equal windows)."""
+    s15 = 0x7FFF
+    return k < (1 << 253) and not (k >> 238 == s15 and (k >> 223) & s15 == s15 and (k >> 208) & s15 == s15 and (k >> 207) & 1)
+
+
 def test_even_window_geometry_edge_cases(engine, oracle, golden):
     """Whole MSMs on the main path recode scalars into thirteen signed 16-bit windows and three UNSIGNED 15-bit ones
     (bit offsets 208, 223, 238; kernels/decompose.hpp k_decompose `even`): every golden vector forced onto that path,
@@ -154,19 +180,7 @@ def test_even_window_geometry_edge_cases(engine, oracle, golden):
         pts, ks = seeded_inputs(oracle, n, 4242)
         pl = R.decode_points(pts)
         kl = R.decode_scalars(ks)
-        s15 = 0x7FFF
-        edge = [
-            s15 << 208, s15 << 223, s15 << 238,                      # the largest digit of each short window
-            (s15 << 208) + (0x8000 << 192),                          # a carry into window 13 wraps it to 0, carry on
-            (s15 << 208) + (s15 << 223) + (0x8000 << 192),           # ... through window 14 into the top window
-            (s15 << 208) + (s15 << 223) + (s15 << 238) + (0x8000 << 192),  # ... and out of it: does not fit (< 2^253)
-            (s15 << 238) + (s15 << 223) + (s15 << 208) + 0x7FFF,     # largest scalar that fits with no carry at all
-            (1 << 253) - 1, 1 << 253, (1 << 254) + 5,                # from 2^253 on: never fits
-            (1 << 208) - 1, 1 << 208, (1 << 223) - 1, 1 << 223, (1 << 238) - 1, 1 << 238,
-            0x8000 << 192, 0x7FFF << 192, R.R_ORDER - 1, R.R_ORDER - 2, 0, 1,
-        ]
-        fits = lambda k: k < (1 << 253) and not (k >> 238 == s15 and (k >> 223) & s15 == s15 and (k >> 208) & s15 == s15 and (k >> 207) & 1)  # noqa: E731
-        assert [fits(k) for k in edge[3:10]] == [True, True, False, True, False, False, False]
+        edge = even_edge_scalars()
         base = R.decode_result(util.oracle_msm(oracle, pts, ks))
         for i, k in enumerate(edge):  # one edge scalar at a time, so that those that fit stay on the even windows
             kk = list(kl)
@@ -200,9 +214,10 @@ def test_2_16_against_reference_sized_oracle(engine, oracle):
     n = 1 << 16
     pts, ks = seeded_inputs(oracle, n, 16)
     exp = util.oracle_msm(oracle, pts, ks)
-    assert engine.msm(pts, ks) == exp
-    d_p, d_s = dev(pts), dev(ks)
-    assert engine.msm_device(d_p.data_ptr(), d_s.data_ptr(), n) == exp
+    with util.edwards_only(engine):
+        assert engine.msm(pts, ks) == exp
+        d_p, d_s = dev(pts), dev(ks)
+        assert engine.msm_device(d_p.data_ptr(), d_s.data_ptr(), n) == exp
 
 
 def test_stage_parity(engine, oracle):
@@ -287,6 +302,10 @@ def test_stage_parity_edwards_form(engine, oracle):
 
 
 def test_every_check_of_the_edwards_law_fires(engine):
+    check_edwards_law_placements(engine)
+
+
+def check_edwards_law_placements(engine):
     """the exceptional pairs of the a = -1 law are P, P + T' with T' = (-omega, 0) (util.t_prime) -- NOT the
     2-torsion point (-1, 0) the older tests used, whose Edwards image is an ordinary point.  One case per place the
     pair can meet: a bucket chain in k_accumulate, the merge of a split row, a thread-level and a quad-level step of
@@ -324,9 +343,12 @@ def test_every_check_of_the_edwards_law_fires(engine):
         assert engine.msm(pb, sb) == exp, name
         count, mask = engine.fallback_info()
         assert count == before + 1 and mask & where, (name, count - before, mask)
-        # device entry point, resident table (projective or affine records), batch
+        # device entry point (per-call affine records on a context with a small MSM377_AFFINE_MIN), resident table
+        # (projective or affine records), batch
         d_p, d_s = dev(pb), dev(sb + sb)
         assert engine.msm_device(d_p.data_ptr(), d_s.data_ptr(), n) == exp, name
+        count, mask = engine.fallback_info()
+        assert count == before + 2 and mask & where, (name, count - before, mask)
         engine.set_bases(pb)
         before, _ = engine.fallback_info()
         assert engine.msm_fixed_base(sb) == exp, name
@@ -479,7 +501,8 @@ def test_all_same_scalar(engine, oracle, n, path):
     ks = R.encode_scalars([k] * n)
     select_path(engine, path)
     try:
-        assert engine.msm(pts, ks) == util.oracle_msm(oracle, pts, ks)
+        with util.edwards_only(engine):
+            assert engine.msm(pts, ks) == util.oracle_msm(oracle, pts, ks)
     finally:
         default_path(engine)
 
@@ -667,6 +690,14 @@ def test_fixed_base_batch_pipeline(engine, oracle, path):
     select_path(engine, path)
     engine.set_bases(pts)
     default_path(engine)  # the resident table remembers how it was built
+    # the Edwards table: no element of any batch below (a scalar outside the GLV range, an out-of-range scalar) may
+    # rerun on the Weierstrass path
+    guard = util.edwards_only(engine) if path == "edwards" else contextlib.nullcontext()
+    with guard:
+        fixed_base_batch_pipeline_body(engine, oracle, pts, sets, n, batch)
+
+
+def fixed_base_batch_pipeline_body(engine, oracle, pts, sets, n, batch):
     d_s = dev(b"".join(sets))
     got = engine.msm_fixed_base_batch_device(d_s.data_ptr(), n, batch)
     assert got == [util.oracle_msm(oracle, pts, s) for s in sets]
@@ -770,19 +801,20 @@ def test_alternative_settings_of_the_default_path(oracle, monkeypatch, knobs):
         monkeypatch.setenv(k, v)
     eng = msm.MsmEngine(1 << 17)
     try:
-        for n in (1, 7, 300, 4099, 40000, 100003):
-            pts, ks = seeded_inputs(oracle, n, 900 + n)
-            exp = util.oracle_msm(oracle, pts, ks)
-            d_p, d_s = dev(pts), dev(ks)
-            for timing in (False, 2, True):
-                eng.set_timing(timing)
-                assert eng.msm_device(d_p.data_ptr(), d_s.data_ptr(), n) == exp, (n, timing)
-                st = eng.stage_ms()
-                if timing:
-                    assert st["accumulate_kernel"] > 0.0
-                    assert (st["reduce"] > 0.0) == (timing is True)
-            eng.set_timing(False)
-            assert eng.msm(pts, ks) == exp, n
+        with util.edwards_only(eng):  # the seeded points lie in the prime-order subgroup
+            for n in (1, 7, 300, 4099, 40000, 100003):
+                pts, ks = seeded_inputs(oracle, n, 900 + n)
+                exp = util.oracle_msm(oracle, pts, ks)
+                d_p, d_s = dev(pts), dev(ks)
+                for timing in (False, 2, True):
+                    eng.set_timing(timing)
+                    assert eng.msm_device(d_p.data_ptr(), d_s.data_ptr(), n) == exp, (n, timing)
+                    st = eng.stage_ms()
+                    if timing:
+                        assert st["accumulate_kernel"] > 0.0
+                        assert (st["reduce"] > 0.0) == (timing is True)
+                eng.set_timing(False)
+                assert eng.msm(pts, ks) == exp, n
     finally:
         eng.close()
 
@@ -930,7 +962,8 @@ def test_heavily_skewed_scalars_at_scale(engine, oracle):
     gen = ctypes.create_string_buffer(96)
     oracle.oracle_g1_generator(ctypes.addressof(gen))
     assert oracle.oracle_g1_scalar_mul(gen.raw, total.to_bytes(32, "little"), 32, ctypes.addressof(exp)) == 0
-    assert engine.msm(pts, R.encode_scalars(ks_int)) == exp.raw
+    with util.edwards_only(engine):
+        assert engine.msm(pts, R.encode_scalars(ks_int)) == exp.raw
 
 
 def test_generate_bases(engine):
@@ -961,17 +994,19 @@ def test_full_size_2_20_closed_form(engine, oracle):
     d_p, d_s = dev(pts), dev(ks)
     engine.set_timing(True)
     try:
-        got = engine.msm_device(d_p.data_ptr(), d_s.data_ptr(), n)
+        with util.edwards_only(engine, products=7):  # the per-call affine records (n >= MSM377_AFFINE_MIN), no rerun
+            got = engine.msm_device(d_p.data_ptr(), d_s.data_ptr(), n)
         print("stage ms:", engine.stage_ms())
     finally:
         engine.set_timing(False)
     assert got == exp.raw
     # linearity on the same resident inputs: MSM(P, 2k) == 2 MSM(P, k) via the fixed-base path
-    engine.set_bases_device(d_p.data_ptr(), n)
     ks2 = R.encode_scalars([(2 * k) % R.R_ORDER for k in ks_int])
     exp2 = ctypes.create_string_buffer(96)
     assert oracle.oracle_g1_scalar_mul(gen.raw, ((2 * total) % R.R_ORDER).to_bytes(32, "little"), 32, ctypes.addressof(exp2)) == 0
-    assert engine.msm_fixed_base(ks2) == exp2.raw
+    with util.edwards_only(engine):
+        engine.set_bases_device(d_p.data_ptr(), n)
+        assert engine.msm_fixed_base(ks2) == exp2.raw
 
 
 def test_2_22_closed_form(oracle):
@@ -992,11 +1027,13 @@ def test_2_22_closed_form(oracle):
     with msm.MsmEngine(n) as eng:
         d_p, d_s = dev(pts), dev(ks)
         eng.set_timing(True)
-        got = eng.msm_device(d_p.data_ptr(), d_s.data_ptr(), n)
+        with util.edwards_only(eng, products=7):
+            got = eng.msm_device(d_p.data_ptr(), d_s.data_ptr(), n)
         print("2^22 stage ms:", eng.stage_ms())
         assert got == exp.raw
         # the same problem as 8 window shards
-        parts = [eng.window_partials_device(d_p.data_ptr(), d_s.data_ptr(), n, *msm.windows_for_rank(r, 8)) for r in range(8)]
+        with util.edwards_only(eng):
+            parts = [eng.window_partials_device(d_p.data_ptr(), d_s.data_ptr(), n, *msm.windows_for_rank(r, 8)) for r in range(8)]
         assert msm.combine_partials(b"".join(parts)) == exp.raw
 
 
@@ -1014,14 +1051,15 @@ def test_config5_full_batch_of_64_at_2_20(engine, table):
     scalars_host = bench.seeded_scalars(0x5CA1A5, n)
     d_points = torch.empty(96 * n, dtype=torch.uint8, device="cuda")
     engine.generate_bases_device(0x377, n, d_points.data_ptr())
-    if table == "wide":
-        engine.set_precompute_window(20)
-        engine.set_bases_precomputed_device(d_points.data_ptr(), n)
-    else:
-        engine.set_bases_device(d_points.data_ptr(), n)
-    d_scalars = bench.fixed64_scalar_sets(torch, scalars_host, n, batch)
-    torch.cuda.synchronize()
-    got = engine.msm_fixed_base_batch_device(d_scalars.data_ptr(), n, batch)
+    with util.edwards_only(engine):  # P_i = [a_i]G
+        if table == "wide":
+            engine.set_precompute_window(20)
+            engine.set_bases_precomputed_device(d_points.data_ptr(), n)
+        else:
+            engine.set_bases_device(d_points.data_ptr(), n)
+        d_scalars = bench.fixed64_scalar_sets(torch, scalars_host, n, batch)
+        torch.cuda.synchronize()
+        got = engine.msm_fixed_base_batch_device(d_scalars.data_ptr(), n, batch)
     assert got == bench.fixed64_expected(n, batch, scalars_host)
     engine.set_precompute_window(16)
     engine.set_bases_device(d_points.data_ptr(), 1)  # drops the 2.2 GB table

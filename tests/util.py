@@ -1,5 +1,6 @@
 """Shared helpers for the tests (TEST INFRASTRUCTURE): oracle loading, golden loading,
 device-format encoders."""
+import contextlib
 import ctypes
 import json
 import os
@@ -91,6 +92,32 @@ def oracle_ed_gen_points(lib, n, a0, delta) -> bytes:
     rc = lib.oracle_ed_gen_points_arith(n, R.ed_encode_points([R.ED_G]), int(a0).to_bytes(32, "little"), int(delta).to_bytes(32, "little"), ctypes.addressof(out))
     assert rc == 0, rc
     return out.raw
+
+
+@contextlib.contextmanager
+def edwards_only(engine, products=None):
+    """Guard around G1 calls whose points all lie in the prime-order subgroup: the twisted Edwards form must carry them
+    through without a rerun on the Weierstrass path (include/msm377.h: the fallback count stays at zero for such inputs).
+    A false exceptional flag would leave every result exact and only cost time, so the count is checked on exit;
+    ``products`` also pins the field products per bucket addition of the last accumulation launch (7 = affine records,
+    8 = projective Edwards records)."""
+    before, _ = engine.fallback_info()
+    yield
+    count, mask = engine.fallback_info()
+    assert count == before, "%d silent rerun(s) on the Weierstrass path, last mask 0x%x" % (count - before, mask)
+    if products is not None:
+        got = engine.accumulate_products()
+        assert got == products, "%d field products per bucket addition, expected %d" % (got, products)
+
+
+def closed_form(lib, total) -> bytes:
+    """[total]G in the wire format, by one oracle scalar multiplication: the closed form of sum k_i P_i over points
+    P_i = [a0 + i d]G (oracle_gen_points) is total = sum k_i (a0 + i d) mod r."""
+    exp = ctypes.create_string_buffer(96)
+    gen = ctypes.create_string_buffer(96)
+    lib.oracle_g1_generator(ctypes.addressof(gen))
+    assert lib.oracle_g1_scalar_mul(gen.raw, (total % R.R_ORDER).to_bytes(32, "little"), 32, ctypes.addressof(exp)) == 0
+    return exp.raw
 
 
 def load_golden():

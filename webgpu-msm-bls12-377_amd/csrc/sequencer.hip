@@ -1531,7 +1531,7 @@ int window_partials(msm377_ctx* ctx, const void* d_points, const void* d_scalars
     // Affine base records (7-product additions, batched inversion) once a point takes part in enough additions to pay for
     // its ~9 extra conversion products: windows x points >= 2^24 -- e.g. the 8 windows a rank of a 2-GPU run owns at 2^21
     // points and more, the 2 of an 8-GPU run at 2^23 (msm377_g1_msm_device: 16 windows, n >= 2^20).
-    const bool affine = ctx->te_affine_msm && n >= (1ull << 18) && (uint64_t)win_count * n >= (1ull << 24);
+    const bool affine = ctx->te_affine_msm && n >= ctx->affine_min_points / 4 && (uint64_t)win_count * n >= 16 * ctx->affine_min_points;
     if (affine) {
       rc = affine_convert_begin(ctx, (const uint32_t*)d_points, n);
       if (rc) return rc;
