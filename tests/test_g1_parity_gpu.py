@@ -78,7 +78,7 @@ def test_narrow_windows_edge_cases(engine, oracle, golden):
     """The small-input path (eleven signed 12-bit windows + eleven unsigned 11-bit ones, the last from bit 242; 2^11
     buckets each; kernels/decompose.hpp k_decompose_geom) on the inputs that stress a recode: every golden vector (edge
     scalars, cancellations, repeated points), digits at the window boundaries of this geometry and of the one before it
-    (22 signed 11-bit windows + an unsigned top one, still there as MSM377_NARROW_EVEN=0), scalars of 2^253 and more
+    (22 signed 11-bit windows + an unsigned top one), scalars of 2^253 and more
     (their top digit does not fit: the call must rerun on the 16-bit path), one repeated base point, a skewed set that
     splits rows, and the scalar-overflow error, which must fire exactly as on the main path."""
     engine.set_narrow_max(1 << 15)
@@ -782,13 +782,13 @@ def test_point_sharding_on_one_gpu(engine, oracle, world):
 @pytest.mark.parametrize(
     "knobs",
     [
-        {"MSM377_NARROW_QUAD_ACC": "0"},  # narrow path with a thread per work item (k_accumulate), not a lane quad
+        {"MSM377_NARROW_QUAD_ITEMS": "0"},  # narrow path with a thread per work item (k_accumulate), not a lane quad
         {"MSM377_ZERO_COPY_OUT": "0"},  # D2H copies + event instead of zero-copy stores and a polled sequence number
         {"MSM377_TAIL_THREADS": "1"},
         {"MSM377_TAIL_THREADS": "8", "MSM377_TAIL_SPIN_US": "0", "MSM377_TAIL_NUMA": "0"},
         {"MSM377_TAIL_THREADS": "3"},
         {"MSM377_EVEN_WINDOWS": "0", "MSM377_TWIN_BATCH": "0"},  # sixteen equal windows everywhere; batches on one context
-        {"MSM377_NARROW_EVEN": "0", "MSM377_TAIL_LDS": "0"},  # small inputs: 22 signed 11-bit windows + an unsigned top one; reduction tail in global memory
+        {"MSM377_TAIL_LDS": "0"},  # reduction tail in global memory
         {"MSM377_NARROW_TAIL_FROM": "7", "MSM377_COOP_THREADS": "65536", "MSM377_NARROW_SEG": "32"},
         {"MSM377_NARROW_TAIL_FROM": "1", "MSM377_COOP_THREADS": "100000000"},  # every level on lane quads, everything behind level 0 in one launch
     ],
@@ -819,16 +819,13 @@ def test_alternative_settings_of_the_default_path(oracle, monkeypatch, knobs):
         eng.close()
 
 
-@pytest.mark.parametrize("schedule", ["front end per chunk", "sorted once", "sorted once, 7 chunks"])
+@pytest.mark.parametrize("schedule", ["front end per chunk", "front end per chunk, 7 chunks"])
 def test_host_buffers_upload_in_chunks(oracle, monkeypatch, schedule):
     """msm377_g1_msm with large host buffers uploads and accumulates in chunks of points (later chunks on top of the
-    earlier ones' buckets, one reduction): forced here at small sizes through MSM377_UPLOAD_CHUNK_MIN; both schedules
-    (the default: every chunk its own decompose / sort; MSM377_UPLOAD_SORT_ONCE: scalars first, one sort with the rows
-    filed by chunk, every chunk its own sub-rows), both coordinate forms, ragged sizes, skew, and an exceptional point
-    in a later chunk (whole call reruns on the Weierstrass path)."""
+    earlier ones' buckets, one reduction; every chunk its own decompose / sort): forced here at small sizes through
+    MSM377_UPLOAD_CHUNK_MIN; two chunk geometries (the default, and 7 chunks with a 9 % first one), both coordinate
+    forms, ragged sizes, skew, and an exceptional point in a later chunk (whole call reruns on the Weierstrass path)."""
     monkeypatch.setenv("MSM377_UPLOAD_CHUNK_MIN", "100")
-    if schedule != "front end per chunk":
-        monkeypatch.setenv("MSM377_UPLOAD_SORT_ONCE", "1")
     if schedule.endswith("7 chunks"):
         monkeypatch.setenv("MSM377_UPLOAD_CHUNKS", "7")
         monkeypatch.setenv("MSM377_UPLOAD_SPLIT", "9")

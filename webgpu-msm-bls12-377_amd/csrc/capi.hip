@@ -50,11 +50,8 @@ int msm377_ctx_create(int device, uint64_t max_points, msm377_ctx** out) {
   ctx->cap = max_points;
   if (const char* e = getenv("MSM377_GLV")) ctx->glv_mode = atoi(e);
   if (const char* e = getenv("MSM377_G1_FORM")) ctx->g1_form = atoi(e) != 0;
-  if (const char* e = getenv("MSM377_UPLOAD_SORT_ONCE")) ctx->upload_sort_once = atoi(e) != 0;
   if (const char* e = getenv("MSM377_CONV_WAVE_PRIO")) ctx->conv_wave_prio = atoi(e) != 0;
-  if (const char* e = getenv("MSM377_FRONT_WAVE_PRIO")) ctx->front_wave_prio = atoi(e) != 0;
   if (const char* e = getenv("MSM377_AFF_PREWAKE_US")) ctx->aff_prewake_us = atoll(e);
-  if (const char* e = getenv("MSM377_UPLOAD_TRACE")) ctx->upload_trace_on = atoi(e) != 0;
   if (const char* e = getenv("MSM377_UPLOAD_CHUNKS")) ctx->upload_chunks = (uint32_t)std::min(std::max(atoi(e), 2), 7);
   if (const char* e = getenv("MSM377_UPLOAD_SPLIT")) ctx->upload_split_pct = (uint32_t)std::min(std::max(atoi(e), 5), 90);
   if (const char* e = getenv("MSM377_UPLOAD_CHUNK_MIN")) ctx->upload_chunk_min = strtoull(e, nullptr, 10);
@@ -72,11 +69,9 @@ int msm377_ctx_create(int device, uint64_t max_points, msm377_ctx** out) {
   if (const char* e = getenv("MSM377_ZERO_COPY_OUT")) ctx->zc_out = atoi(e);
   if (const char* e = getenv("MSM377_NARROW_SEG")) ctx->narrow_seg = (uint32_t)std::min(std::max(atoi(e), (int)NARROW_SEG), (int)SEG_BINS - 1);
   if (const char* e = getenv("MSM377_NARROW_QUAD_ITEMS")) ctx->narrow_quad_items = strtoull(e, nullptr, 10);
-  if (const char* e = getenv("MSM377_NARROW_QUAD_ACC")) ctx->narrow_quad_acc = atoi(e);
   if (const char* e = getenv("MSM377_COOP_THREADS")) ctx->coop_threads = (uint32_t)atoi(e);
   if (const char* e = getenv("MSM377_NARROW_TAIL_FROM")) ctx->narrow_tail_from = (uint32_t)std::min(std::max(atoi(e), 1), (int)TREE_LEVELS);
   if (const char* e = getenv("MSM377_TAIL_LDS")) ctx->tail_lds = atoi(e) != 0;
-  if (const char* e = getenv("MSM377_NARROW_EVEN")) ctx->narrow_even = atoi(e) != 0;
   if (const char* e = getenv("MSM377_EVEN_WINDOWS")) ctx->even_windows = atoi(e) != 0;
   if (const char* e = getenv("MSM377_TWIN_BATCH")) ctx->twin_batches = atoi(e) != 0;
   if (const char* e = getenv("MSM377_TAIL_FROM")) ctx->tail_from = (uint32_t)std::min(std::max(atoi(e), 1), (int)TREE_LEVELS);
@@ -96,9 +91,9 @@ int msm377_ctx_create(int device, uint64_t max_points, msm377_ctx** out) {
   dalloc((void**)&ctx->d_raw_points, cap * 96);
   dalloc((void**)&ctx->d_raw_scalars, cap * 32);
   dalloc((void**)&ctx->d_bases, 2 * cap * G1_REC_WORDS * 4);  // 128-byte records of P_i and phi(P_i) (GLV front end), or 256-byte twisted Edwards records of P_i
-  // (window, point) entries the window-indexed buffers hold: 16 windows of `cap` points, or the 23 windows of the
+  // (window, point) entries the window-indexed buffers hold: 16 windows of `cap` points, or the 22 windows of the
   // narrow path over a small input when that is more (small contexts)
-  const uint64_t wcap = std::max<uint64_t>((uint64_t)MSM377_NUM_WINDOWS * cap, (uint64_t)NARROW_WINDOWS * std::min<uint64_t>(cap, SMALL_SORT_MAX));
+  const uint64_t wcap = std::max<uint64_t>((uint64_t)MSM377_NUM_WINDOWS * cap, (uint64_t)NARROW_EVEN_WINDOWS * std::min<uint64_t>(cap, SMALL_SORT_MAX));
   dalloc((void**)&ctx->d_digits, wcap * 2);
   dalloc((void**)&ctx->d_range_counts, (size_t)NRANGE * MAX_SORT_BLOCKS * 4);  // chunks * wc <= MAX_SORT_BLOCKS
   dalloc((void**)&ctx->d_region_base, (size_t)MSM377_NUM_WINDOWS * (NRANGE + 1) * 4);
@@ -108,9 +103,9 @@ int msm377_ctx_create(int device, uint64_t max_points, msm377_ctx** out) {
   dalloc((void**)&ctx->d_buckets, (size_t)MSM377_NUM_WINDOWS * BKT_WORDS * NB * 4);
   dalloc((void**)&ctx->d_partials, (size_t)2 * SLOT_WORDS * 4);
   // extra work items / overflow slots beyond one per row: entries / SEG_MIN on the main path, entries / NARROW_SEG on the narrow one
-  const uint64_t extra_items = std::max<uint64_t>((uint64_t)MSM377_NUM_WINDOWS * cap / SEG_MIN, (uint64_t)NARROW_WINDOWS * std::min<uint64_t>(cap, SMALL_SORT_MAX) / NARROW_SEG) + 2;
+  const uint64_t extra_items = std::max<uint64_t>((uint64_t)MSM377_NUM_WINDOWS * cap / SEG_MIN, (uint64_t)NARROW_EVEN_WINDOWS * std::min<uint64_t>(cap, SMALL_SORT_MAX) / NARROW_SEG) + 2;
   dalloc((void**)&ctx->d_work, ((size_t)MSM377_NUM_WINDOWS * NB + extra_items) * sizeof(WorkItem));
-  dalloc((void**)&ctx->d_work_meta, (size_t)2 * META_BLOCK_WORDS * 4);  // one block per pipeline part
+  dalloc((void**)&ctx->d_work_meta, (size_t)META_BLOCK_WORDS * 4);
   dalloc((void**)&ctx->d_row_ovf_base, (size_t)MSM377_NUM_WINDOWS * NB * 4);
   dalloc((void**)&ctx->d_split_rows, (size_t)MSM377_NUM_WINDOWS * NB * 4);
   dalloc((void**)&ctx->d_ovf, (size_t)extra_items * BKT_WORDS * 4);
@@ -128,7 +123,7 @@ int msm377_ctx_create(int device, uint64_t max_points, msm377_ctx** out) {
        hipHostGetDevicePointer((void**)&ctx->dm_aff_flag, ctx->h_aff_flag, 0) == hipSuccess &&
        hipEventCreateWithFlags(&ctx->aff_up_done, hipEventDisableTiming) == hipSuccess;
   if (ok) ctx->aff_scratch.resize(aff_blocks);
-  dalloc((void**)&ctx->d_err, 4 * sizeof(int));  // [0], [1]: the two pipeline slots; [2]: base conversion (lives with the table)
+  dalloc((void**)&ctx->d_err, 4 * sizeof(int));  // [0], [1]: the two double-buffer slots; [2]: base conversion (lives with the table)
   ok = ok && hipHostMalloc((void**)&ctx->h_partials, (size_t)2 * SLOT_WORDS * 4, host_flags) == hipSuccess &&
        hipHostGetDevicePointer((void**)&ctx->dm_partials, ctx->h_partials, 0) == hipSuccess &&
        hipHostMalloc((void**)&ctx->h_out_flag, 64, host_flags) == hipSuccess &&
@@ -139,7 +134,7 @@ int msm377_ctx_create(int device, uint64_t max_points, msm377_ctx** out) {
   ok = ok && hipHostMalloc((void**)&ctx->h_err, 2 * sizeof(int)) == hipSuccess;
   for (int k = 0; ok && k < 2; k++) ok = ok && hipEventCreateWithFlags(&ctx->done_ev[k], hipEventDisableTiming) == hipSuccess;
   for (int s = 0; ok && s < MSM377_NUM_STAGES; s++)
-    for (int k = 0; k < 4; k++) ok = ok && hipEventCreate(&ctx->ev[k >> 1][s][k & 1]) == hipSuccess;
+    for (int k = 0; k < 2; k++) ok = ok && hipEventCreate(&ctx->ev[s][k]) == hipSuccess;
   if (!ok) {
     msm377_ctx_destroy(ctx);
     return MSM377_ENOMEM;
@@ -160,7 +155,7 @@ void msm377_ctx_destroy(msm377_ctx* ctx) {
     ctx->twin = nullptr;
   }
   void* bufs[] = {ctx->d_raw_points, ctx->d_raw_scalars, ctx->d_bases, ctx->d_digits, ctx->d_range_counts, ctx->d_region_base, ctx->d_sort_temp,
-                  ctx->d_row_ptr, ctx->d_val_idx, ctx->d_buckets, ctx->d_buckets_snap, ctx->d_partials, ctx->d_work, ctx->d_work_meta, ctx->d_row_ovf_base, ctx->d_split_rows, ctx->d_ovf, ctx->d_err, ctx->d_aff_stash, ctx->d_aff_trees, ctx->d_aff_count, ctx->d_out_count, ctx->d_table, ctx->d_wide_digits, ctx->d_wide_counts, ctx->d_wide_temp, ctx->d_row_ptr_chunks};
+                  ctx->d_row_ptr, ctx->d_val_idx, ctx->d_buckets, ctx->d_buckets_snap, ctx->d_partials, ctx->d_work, ctx->d_work_meta, ctx->d_row_ovf_base, ctx->d_split_rows, ctx->d_ovf, ctx->d_err, ctx->d_aff_stash, ctx->d_aff_trees, ctx->d_aff_count, ctx->d_out_count, ctx->d_table, ctx->d_wide_digits, ctx->d_wide_counts, ctx->d_wide_temp};
   for (void* p : bufs)
     if (p) (void)hipFree(p);
   if (ctx->h_partials) (void)hipHostFree(ctx->h_partials);
@@ -177,8 +172,7 @@ void msm377_ctx_destroy(msm377_ctx* ctx) {
     if (ctx->done_ev[k]) (void)hipEventDestroy(ctx->done_ev[k]);
   for (int s = 0; s < MSM377_NUM_STAGES; s++)
     for (int k = 0; k < 2; k++)
-      for (int p = 0; p < 2; p++)
-        if (ctx->ev[p][s][k]) (void)hipEventDestroy(ctx->ev[p][s][k]);
+      if (ctx->ev[s][k]) (void)hipEventDestroy(ctx->ev[s][k]);
   if (ctx->bases_ready) (void)hipEventDestroy(ctx->bases_ready);
   if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);

@@ -24,15 +24,13 @@ constexpr uint32_t SEG_BINS = SEG_MAX + 1; // work items are counting-sorted by 
 constexpr int ERR_SCALAR = 1, ERR_GLV_RANGE = 2, ERR_NARROW_RANGE = 128;  // 128: a scalar's top digit does not fit the narrow-window path
 constexpr int ERR_TE_EXCEPTIONAL = MSM377_FB_ACCUMULATE, ERR_TE_MERGE = MSM377_FB_MERGE, ERR_TE_TREE = MSM377_FB_TREE, ERR_TE_CONVERT = MSM377_FB_CONVERT;
 constexpr int ERR_TE_ANY = ERR_TE_EXCEPTIONAL | ERR_TE_MERGE | ERR_TE_TREE | ERR_TE_CONVERT;
-constexpr uint32_t NARROW_BITS = 11;       // digit width of the small-input path ...
-constexpr uint32_t NARROW_LOG = 11;        // ... whose windows have 2^11 buckets (the unsigned top digit needs the room: k_decompose_narrow)
+// The small-input path (kernels/decompose.hpp k_decompose_geom): eleven signed 12-bit windows, then eleven unsigned 11-bit
+// ones, 11 x 12 + 11 x 11 = 253 bits, 2^11 buckets each.
+constexpr uint32_t NARROW_LOG = 11;        // 2^11 buckets per window
 constexpr uint32_t NARROW_SEG = 8;         // entries per accumulation work item on that path
-constexpr uint32_t NARROW_WINDOWS = 23;    // 22 signed 11-bit windows + the top window from bit 242 on
-// The same path in the even geometry (kernels/decompose.hpp k_decompose_geom; the default, MSM377_NARROW_EVEN): eleven signed
-// 12-bit windows, then eleven unsigned 11-bit ones, 11 x 12 + 11 x 11 = 253 bits, 2^11 buckets each.
 constexpr uint32_t NARROW_EVEN_WINDOWS = 22, NARROW_EVEN_SIGNED = 11, NARROW_EVEN_BITS = NARROW_LOG + 1;
 static_assert(NARROW_EVEN_SIGNED * NARROW_EVEN_BITS + (NARROW_EVEN_WINDOWS - NARROW_EVEN_SIGNED) * NARROW_LOG == 253, "the windows cover a 253-bit scalar");
-constexpr uint32_t MAX_WINDOW_SLOTS = NARROW_WINDOWS > MSM377_NUM_WINDOWS ? NARROW_WINDOWS : MSM377_NUM_WINDOWS;  // partial-record slots
+constexpr uint32_t MAX_WINDOW_SLOTS = NARROW_EVEN_WINDOWS > MSM377_NUM_WINDOWS ? NARROW_EVEN_WINDOWS : MSM377_NUM_WINDOWS;  // partial-record slots
 
 // ---- sort geometry (kernels/sort.hpp) ----
 // Sort keys: |d| in 0..32768 with the sign carried separately; coarse range = key / 128
@@ -52,19 +50,7 @@ struct WorkItem {
   uint32_t row;  // ws * NB + t   (bucket index t <-> key t + 1)
   uint32_t seg;  // entries [seg * seglen, seg * seglen + seglen) of the row, see row_split
 };
-// The CSR rows of a call whose points arrive in K chunks (host-buffer entry point, sequencer.hip run_sorted_upload): the
-// sort files every key's entries by chunk, row_ptr holds K sub-row bounds per key -- entry (key, c) at index key K + c of
-// a window's ((2^L + 1) K + 1) offsets -- and a launch walks ONE chunk's sub-rows.  K = 1, c = 0: the plain layout
-// (2^L + 2 offsets per window, row t = key t + 1 at [t + 1, t + 2)).
-struct RowView {
-  uint32_t k = 1, c = 0;
-};
-constexpr uint32_t MAX_UPLOAD_CHUNKS = 8;
-struct ChunkCuts {  // chunk j of the points = indices [cut[j], cut[j + 1]); cut[0] = 0, entries from k on = n
-  uint32_t k = 1;
-  uint32_t cut[MAX_UPLOAD_CHUNKS + 1] = {};
-};
-constexpr uint32_t META_BLOCK_WORDS = 2 * SEG_BINS + 4 + MSM377_NUM_WINDOWS;  // per pipeline part: work-list counters + key_max words
+constexpr uint32_t META_BLOCK_WORDS = 2 * SEG_BINS + 4 + MSM377_NUM_WINDOWS;  // work-list counters + key_max words of a call
 constexpr size_t SLOT_WORDS = (size_t)MAX_WINDOW_SLOTS * MSM377_G1_PARTIAL_POINTS * MSM377_G1_POINT_WORDS;  // per double-buffer slot of partial records
 
 // ---- batched affine conversion (kernels/convert.hpp) ----

@@ -22,14 +22,13 @@ namespace {
 // skewed scalars -- the load balancing the reference left out, README.md:543-547).
 
 
-// [0], [1]: begin and end of bucket t's row in window slot ws -- of its sub-row rv.c when the rows are filed by upload
-// chunk (common.hpp RowView).
-__device__ __forceinline__ const uint32_t* row_bounds(const uint32_t* __restrict__ row_ptr, uint32_t L, uint32_t ws, uint32_t t, RowView rv) {
-  return row_ptr + (size_t)ws * (((1u << L) + 1) * rv.k + 1) + (size_t)(t + 1) * rv.k + rv.c;
+// [0], [1]: begin and end of bucket t's row in window slot ws (2^L + 2 offsets per window, row t = key t + 1).
+__device__ __forceinline__ const uint32_t* row_bounds(const uint32_t* __restrict__ row_ptr, uint32_t L, uint32_t ws, uint32_t t) {
+  return row_ptr + (size_t)ws * ((1u << L) + 2) + t + 1;
 }
-__device__ __forceinline__ uint32_t row_len(const uint32_t* __restrict__ row_ptr, uint32_t L, uint32_t row, RowView rv) {
-  const uint32_t* b = row_bounds(row_ptr, L, row >> L, row & ((1u << L) - 1), rv);
-  return b[1] - b[0];
+__device__ __forceinline__ uint32_t row_len(const uint32_t* __restrict__ row_ptr, uint32_t L, uint32_t row) {
+  const int at = (int)(row + 2 * (row >> L) + 1);  // row_bounds of row = ws 2^L + t: ws (2^L + 2) + t + 1 (< 2^20)
+  return row_ptr[at + 1] - row_ptr[at];
 }
 
 // A row of `len` entries becomes `nseg` work items of `seglen` entries (the last one `lastlen`): equal parts of at
@@ -55,8 +54,7 @@ __device__ __forceinline__ RowSplit row_split(uint32_t len, uint32_t SEG) {
 // atomic per bin and block -- the ~60 hot counters serialise, hence the large blocks); rows with more than one item reserve overflow slots and join the split-row list.
 __global__ void __launch_bounds__(1024) k_work_hist(const uint32_t* __restrict__ row_ptr, uint32_t L, uint32_t rows, uint32_t SEG, uint32_t* __restrict__ work_hist,
                                                    uint32_t* __restrict__ row_ovf_base, uint32_t* __restrict__ counters /* [0]=split rows, [1]=overflow slots */,
-                                                   uint32_t* __restrict__ split_rows, RowView rv, uint32_t prio) {
-  if (prio) __builtin_amdgcn_s_setprio(3);  // sequencer.hip: front-end kernels outrank the conversion beside them
+                                                   uint32_t* __restrict__ split_rows) {
   __shared__ uint32_t lh[SEG_BINS];
   __shared__ uint32_t blk[4];  // split rows, overflow slots of this block; then their bases in the global lists
   const uint32_t tid = threadIdx.x, row = blockIdx.x * 1024 + tid;
@@ -66,7 +64,7 @@ __global__ void __launch_bounds__(1024) k_work_hist(const uint32_t* __restrict__
   RowSplit sp = {1, 0, 0};
   uint32_t my_split = 0, my_ovf = 0;
   if (row < rows) {
-    sp = row_split(row_len(row_ptr, L, row, rv), SEG);
+    sp = row_split(row_len(row_ptr, L, row), SEG);
     atomicAdd(&lh[sp.lastlen], 1u);
     if (sp.nseg > 1) {
       atomicAdd(&lh[sp.seglen], sp.nseg - 1);
@@ -95,8 +93,7 @@ __global__ void __launch_bounds__(1024) k_work_hist(const uint32_t* __restrict__
 // cursor[b] (zero at the start: the meta block's clear) counts the slots of that length handed out so far.
 __global__ void __launch_bounds__(1024) k_work_scatter(const uint32_t* __restrict__ row_ptr, uint32_t L, uint32_t rows, uint32_t SEG,
                                                       const uint32_t* __restrict__ work_hist, uint32_t* __restrict__ cursor, uint32_t* __restrict__ total,
-                                                      WorkItem* __restrict__ work, RowView rv, uint32_t prio) {
-  if (prio) __builtin_amdgcn_s_setprio(3);  // sequencer.hip: front-end kernels outrank the conversion beside them
+                                                      WorkItem* __restrict__ work) {
   __shared__ uint32_t lh[SEG_BINS];
   __shared__ uint32_t lbase[SEG_BINS];
   __shared__ uint32_t gh[SEG_BINS];
@@ -114,7 +111,7 @@ __global__ void __launch_bounds__(1024) k_work_scatter(const uint32_t* __restric
   RowSplit sp = {0, 0, 0};
   uint32_t rank_full = 0, rank_last = 0;
   if (row < rows) {
-    sp = row_split(row_len(row_ptr, L, row, rv), SEG);
+    sp = row_split(row_len(row_ptr, L, row), SEG);
     if (sp.nseg > 1) rank_full = atomicAdd(&lh[sp.seglen], sp.nseg - 1);
     rank_last = atomicAdd(&lh[sp.lastlen], 1u);
   }
@@ -133,13 +130,13 @@ __global__ void __launch_bounds__(256, OCC) k_accumulate(const uint32_t* __restr
                                                        const uint32_t* __restrict__ bases, uint32_t* __restrict__ buckets, uint64_t n,
                                                        const WorkItem* __restrict__ work, const uint32_t* __restrict__ work_total,
                                                        const uint32_t* __restrict__ row_ovf_base, uint32_t* __restrict__ ovf, uint32_t SEG,
-                                                       int* __restrict__ err, const int* __restrict__ conv_err, uint32_t into, uint64_t table_stride, uint32_t L, RowView rv) {
+                                                       int* __restrict__ err, const int* __restrict__ conv_err, uint32_t into, uint64_t table_stride, uint32_t L) {
   const uint32_t v = blockIdx.x * 256 + threadIdx.x;
   if (v == 0 && *conv_err) atomicOr(err, *conv_err);  // the table holds a point its coordinate system cannot represent
   if (v >= *work_total) return;
   const WorkItem it = work[v];
   const uint32_t ws = it.row >> L, t = it.row & ((1u << L) - 1);
-  const uint32_t* rb = row_bounds(row_ptr, L, ws, t, rv);
+  const uint32_t* rb = row_bounds(row_ptr, L, ws, t);
   const uint32_t* vi = val_idx + (size_t)ws * n;
   bases += (size_t)ws * table_stride * BP::REC_WORDS;  // precomputed-window tables: window slot ws gathers from its own copy, [2^(16 ws)] P_i
   const uint32_t row_beg = rb[0], row_end = rb[1];
@@ -240,7 +237,7 @@ __global__ void __launch_bounds__(256, 2) k_accumulate_quad(const uint32_t* __re
   if (v >= *work_total) return;  // whole quads leave together
   const WorkItem it = work[v];
   const uint32_t ws = it.row >> L, t = it.row & ((1u << L) - 1);
-  const uint32_t* rb = row_bounds(row_ptr, L, ws, t, RowView{});
+  const uint32_t* rb = row_bounds(row_ptr, L, ws, t);
   const uint32_t* vi = val_idx + (size_t)ws * n;
   const uint32_t row_beg = rb[0], row_end = rb[1];
   const uint32_t seglen = row_split(row_end - row_beg, SEG).seglen;
@@ -298,7 +295,7 @@ template <class CV>
 __global__ void __launch_bounds__(256, 2) k_merge_split_rows_quad(const uint32_t* __restrict__ row_ptr, uint32_t* __restrict__ buckets,
                                                                   const uint32_t* __restrict__ counters, const uint32_t* __restrict__ split_rows,
                                                                   const uint32_t* __restrict__ row_ovf_base, const uint32_t* __restrict__ ovf, uint32_t SEG,
-                                                                  int* __restrict__ err, uint32_t L, RowView rv, uint32_t* __restrict__ host_flag, uint32_t seq) {
+                                                                  int* __restrict__ err, uint32_t L, uint32_t* __restrict__ host_flag, uint32_t seq) {
   // The first launch behind the accumulation kernel tells the host that it is through (sequencer.hip TailArm: the
   // tail's helper threads start polling for their jobs now).  An event record between the two kernels did the same and
   // cost a ~6 us bubble in the stream.
@@ -307,7 +304,7 @@ __global__ void __launch_bounds__(256, 2) k_merge_split_rows_quad(const uint32_t
   const uint32_t q = threadIdx.x & 3;
   for (uint32_t i = (blockIdx.x * 256 + threadIdx.x) >> 2; i < count; i += gridDim.x * 64) {
     const uint32_t row = split_rows[i];
-    const uint32_t len = row_len(row_ptr, L, row, rv);
+    const uint32_t len = row_len(row_ptr, L, row);
     const uint32_t nseg = row_split(len, SEG).nseg;
     const uint32_t ws = row >> L, t = row & ((1u << L) - 1);
     typename CV::Pt acc = load_bucket_quad<CV>(buckets, L, ws, t, q);  // (all four lanes of a quad share i: they are all here)

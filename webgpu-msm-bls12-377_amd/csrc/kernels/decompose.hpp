@@ -1,4 +1,4 @@
-// Stage 1: scalars -> signed window digits (k_decompose, k_decompose_narrow, k_decompose_glv).  Replaces
+// Stage 1: scalars -> signed window digits (k_decompose, k_decompose_geom, k_decompose_glv).  Replaces
 // wgsl/cuzk/convert_point_coords_and_decompose_scalars.template.wgsl:100-141; model cuzk/utils.ts:66-109.
 // Device code; included by sequencer.hip only.
 #pragma once
@@ -41,9 +41,7 @@ __device__ __forceinline__ uint32_t key_range(uint32_t key, uint32_t s) {
 // window (win_shift).  A scalar of 2^253 - 2^238 and more, whose top digit does not fit, raises ERR_NARROW_RANGE and
 // the call reruns with the sixteen equal windows; the ERROR condition stays the one of the 16-bit recode.
 __global__ void __launch_bounds__(256) k_decompose(const uint32_t* __restrict__ scalars, uint16_t* __restrict__ digits, uint64_t n,
-                                                   uint32_t wb, uint32_t wc, int* __restrict__ err, uint32_t* __restrict__ top_key_max, uint32_t prio,
-                                                   uint32_t even) {
-  if (prio) __builtin_amdgcn_s_setprio(3);  // sequencer.hip: front-end kernels outrank the conversion beside them
+                                                   uint32_t wb, uint32_t wc, int* __restrict__ err, uint32_t* __restrict__ top_key_max, uint32_t even) {
   // top_key_max (may be null): largest key of window 15, the one window that scalars below a 253-bit modulus leave
   // mostly empty; see win_shift.  One LDS atomic per thread at worst, one global atomic per block.
   __shared__ uint32_t wmax;
@@ -101,64 +99,26 @@ __global__ void __launch_bounds__(256) k_decompose(const uint32_t* __restrict__ 
 // ---- narrow windows for small inputs (the reference switches to 4-bit windows below
 //      65 536 points, src/submission/submission.ts:97,173-186) ----
 // Below ~2^15 points the 16 x 32 768 buckets of the main path are mostly empty and their reduction -- 15 levels, the
-// first ones streaming 134 MB of identity records -- is most of the call.  With 11-bit windows (23 windows of 2 048
-// buckets) the bucket array shrinks 11-fold and the reduction loses four levels (0.28 -> 0.115 ms); the additions grow
-// from 16 n to 23 n, which a small input does not notice.  Everything behind the sort runs the same kernels with
-// L = 11 as their run-time bucket geometry; decomposition and sort have their own small kernels here.
-
-// One thread per scalar: W windows of c bits.  Windows 0 .. W-2 are signed digits with a carry (|d| <= 2^(c-1)); the TOP
-// window takes everything that is left WITHOUT a carry out, as an unsigned digit: a signed top window would push
-// its carry into one more window whose only digits are 0 and 1 -- a single row holding a seventh of all points,
-// which no segmenting saves on a small input (measured: the merge of that row alone took 2.6 ms at 2^14).  With
-// c = 11 the top window starts at bit 242, so scalars below r (253 bits) leave it digits below 1 195 < 2^L = 2 048;
-// a larger top digit (scalars >= 2^253) raises ERR_NARROW_RANGE and the call reruns on the 16-bit path.  All digits
-// are stored biased by 2^L: d + 2^L in [0, 2^(L+1)).
+// first ones streaming 134 MB of identity records -- is most of the call.  With windows of 2 048 buckets the bucket
+// array shrinks 11-fold and the reduction loses four levels; the additions grow from 16 n to 22 n, which a small input
+// does not notice.  Everything behind the sort runs the same kernels with L = 11 as their run-time bucket geometry;
+// decomposition and sort have their own small kernels (k_decompose_geom, k_small_sort).
 // The error condition is the one of the 16-bit recode for every input size (cuzk/utils.ts:95-98 throws when the recode
 // ends with a carry; with 16-bit windows that is k >= 2^255 - 2^239), whichever window width runs here.  The reference
 // itself switches to 4-bit windows below 65 536 points (submission.ts:97), where the same check fires for every
 // k > 0x7777...7 -- a set that differs only in NON-canonical scalars (every k < r passes both): deliberately not
 // reproduced, one error condition for all sizes (tests/test_g1_parity_gpu.py::test_narrow_windows_edge_cases).
-__global__ void __launch_bounds__(256) k_decompose_narrow(const uint32_t* __restrict__ scalars, uint16_t* __restrict__ digits, uint64_t n, uint32_t c,
-                                                          uint32_t L, uint32_t W, int* __restrict__ err) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  uint32_t w[8];
-  load_words16(scalars + i * 8, w, 2);
-  const uint32_t half = 1u << (c - 1), mask = (1u << c) - 1u, bias = 1u << L;
-  uint32_t carry = 0;
-  for (uint32_t win = 0; win + 1 < W; win++) {
-    const uint32_t bit = win * c, word = bit >> 5, off = bit & 31;
-    uint32_t v = w[word] >> off;
-    if (off + c > 32 && word + 1 < 8) v |= w[word + 1] << (32 - off);
-    v = (v & mask) + carry;
-    carry = v >= half ? 1u : 0u;
-    const int d = (int)v - (int)(carry << c);  // in [-2^(c-1), 2^(c-1))
-    digits[(size_t)win * n + i] = (uint16_t)(d + (int)bias);
-  }
-  {  // the top window: bits (W - 1) c .. 255, unsigned, no carry out (at most 32 bits wide for the widths in use)
-    const uint32_t bit = (W - 1) * c, word = bit >> 5, off = bit & 31;
-    uint64_t v = w[word] >> off;
-    for (uint32_t k = word + 1, sh = 32 - off; k < 8; k++, sh += 32) v |= (uint64_t)w[k] << sh;
-    v += carry;
-    if (v >= bias) atomicOr(err, ERR_NARROW_RANGE);
-    digits[(size_t)(W - 1) * n + i] = (uint16_t)((uint32_t)(v < bias ? v : 0) + bias);
-  }
-  uint32_t carry16 = 0;
-#pragma unroll
-  for (uint32_t win = 0; win < 16; win++) carry16 = (((w[win >> 1] >> (16 * (win & 1))) & 0xffffu) + carry16) >= 32768u ? 1u : 0u;
-  if (carry16) atomicOr(err, ERR_SCALAR);
-}
 
 // The even geometry in general (k_decompose's `even` mode is the instance L = 15, a = 13, W = 16 with its fields at fixed
 // places): W windows of 2^L buckets over the 253 bits of a scalar below r -- the first `a` windows are SIGNED digits of
 // L + 1 bits (|d| <= 2^L, carry into the next window), the other W - a are UNSIGNED digits of L bits with a carry chain
 // of their own (limb + carry = 2^L -> digit 0, carry 1), and a (L + 1) + (W - a) L = 253, so that every window fills
 // its 2^L buckets with rows of n / 2^L entries.  The small-input path runs it with L = 11, a = 11, W = 22 (common.hpp
-// NARROW_EVEN_*): against k_decompose_narrow's 22 signed 11-bit windows + an unsigned top one, whose signed digits reach
-// only half of a window's 2048 buckets, that is one window less and rows half as long -- fewer rows cut into several
-// work items, a shorter merge.  Digits are stored biased by `bias` (2^L for k_small_sort).  A scalar whose top digit does
-// not fit -- everything from 2^253 on and the few below that carry out of the top window -- raises ERR_NARROW_RANGE and
-// the call reruns with sixteen 16-bit windows; the ERROR condition stays the 16-bit recode's (cuzk/utils.ts:95-98).
+// NARROW_EVEN_*).  (Its first geometry, 22 signed 11-bit windows + an unsigned top one, reached only half of a window's
+// 2048 buckets with its signed digits; retired in favour of this one, HISTORY.md.)  Digits are stored biased by `bias`
+// (2^L for k_small_sort).  A scalar whose top digit does not fit -- everything from 2^253 on and the few below that
+// carry out of the top window -- raises ERR_NARROW_RANGE and the call reruns with sixteen 16-bit windows; the ERROR
+// condition stays the 16-bit recode's.
 __global__ void __launch_bounds__(256) k_decompose_geom(const uint32_t* __restrict__ scalars, uint16_t* __restrict__ digits, uint64_t n, uint32_t L,
                                                         uint32_t a, uint32_t W, uint32_t bias, int* __restrict__ err) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;

@@ -45,8 +45,7 @@ __device__ __forceinline__ void for_each_digit(const uint16_t* __restrict__ dg, 
 }
 
 __global__ void __launch_bounds__(1024) k_range_count(const uint16_t* __restrict__ digits, uint32_t* __restrict__ counts /* [ws][r][c] */,
-                                                      uint64_t n, uint32_t chunks, uint64_t per_chunk, const uint32_t* __restrict__ key_max, uint32_t prio) {
-  if (prio) __builtin_amdgcn_s_setprio(3);  // sequencer.hip: front-end kernels outrank the conversion beside them
+                                                      uint64_t n, uint32_t chunks, uint64_t per_chunk, const uint32_t* __restrict__ key_max) {
   __shared__ uint32_t cnt[NRANGE];
   const uint32_t c = blockIdx.x, ws = blockIdx.y, tid = threadIdx.x;
   const uint32_t shift = win_shift(key_max[ws]);
@@ -65,8 +64,7 @@ __global__ void __launch_bounds__(1024) k_range_count(const uint16_t* __restrict
 
 // Block per window slot, thread per range: region_base[r] = elements in smaller ranges;
 // counts[ws][r][c] becomes the write offset of chunk c inside region r (absolute).
-__global__ void __launch_bounds__(NRANGE) k_range_scan(uint32_t* __restrict__ counts, uint32_t* __restrict__ region_base, uint32_t chunks, uint32_t prio) {
-  if (prio) __builtin_amdgcn_s_setprio(3);  // sequencer.hip: front-end kernels outrank the conversion beside them
+__global__ void __launch_bounds__(NRANGE) k_range_scan(uint32_t* __restrict__ counts, uint32_t* __restrict__ region_base, uint32_t chunks) {
   __shared__ uint32_t part[NRANGE];
   const uint32_t ws = blockIdx.x, r = threadIdx.x;
   uint32_t* cr = counts + ((size_t)ws * NRANGE + r) * chunks;
@@ -101,8 +99,7 @@ __global__ void __launch_bounds__(NRANGE) k_range_scan(uint32_t* __restrict__ co
 constexpr uint32_t PT_TILE = 8192;  // 8 digits (one 16-byte load) per thread; 64 KB of staging: two workgroups per CU
 __global__ void __launch_bounds__(1024) k_partition_staged(const uint16_t* __restrict__ digits, const uint32_t* __restrict__ counts,
                                                            SortElem* __restrict__ temp, uint64_t n, uint32_t chunks, uint64_t per_chunk,
-                                                           const uint32_t* __restrict__ key_max, uint32_t prio) {
-  if (prio) __builtin_amdgcn_s_setprio(3);  // sequencer.hip: front-end kernels outrank the conversion beside them
+                                                           const uint32_t* __restrict__ key_max) {
   __shared__ uint32_t cur[NRANGE];     // this workgroup's write cursor in every range's region
   __shared__ uint32_t cnt[NRANGE];     // elements of the tile per range
   __shared__ uint32_t toff[NRANGE];    // first slot of the range in the staged tile
@@ -197,43 +194,28 @@ __global__ void __launch_bounds__(1024) k_partition_staged(const uint16_t* __res
 // A/B at 2^20: sort stage 0.344 -> 0.296 ms, whole MSM 2.60 -> 2.55).  Longer regions (skewed scalars) are streamed twice.
 constexpr uint32_t LS_CACHE = 6144;           // region length (n / 256 = 4096 on average at n = 2^20) the register / LDS path holds
 constexpr uint32_t LS_REG = LS_CACHE / 256;  // elements per thread
-// CH: the rows are filed by upload chunk as well (common.hpp RowView / ChunkCuts; the host-buffer entry point): bin
-// (key, chunk of the point index) instead of key, K sub-row bounds per key in row_ptr.  CH = false compiles to the
-// plain layout.
-template <bool CH>
 __global__ void __launch_bounds__(256) k_local_sort_lds(const SortElem* __restrict__ temp, const uint32_t* __restrict__ region_base,
                                                         uint32_t* __restrict__ row_ptr, uint32_t* __restrict__ val_idx, uint64_t n,
-                                                        const uint32_t* __restrict__ key_max, uint32_t NR, uint32_t NBK, ChunkCuts cuts, uint32_t prio) {
-  if (prio) __builtin_amdgcn_s_setprio(3);  // sequencer.hip: front-end kernels outrank the conversion beside them
+                                                        const uint32_t* __restrict__ key_max, uint32_t NR, uint32_t NBK) {
   // NR ranges per window over keys 0 .. NBK (256 x 2^15 on the main path; 4096 x 2^19, one window, no key_max, for the
   // wide windows of kernels/wide.hpp); the last range also owns key NBK.
-  constexpr uint32_t MAXK = CH ? MAX_UPLOAD_CHUNKS : 1;
-  constexpr uint32_t NBINS = (KRANGE + 1) * MAXK, PER = (NBINS + 255) / 256;  // bins a thread owns in the scan
+  constexpr uint32_t NBINS = KRANGE + 1;  // keys of a range, bin = key - lo; a thread owns one in the scan
+  static_assert(NBINS <= 256, "one bin per thread");
   __shared__ uint32_t bins[NBINS];
   __shared__ uint32_t part[256];
   __shared__ uint32_t sorted[LS_CACHE];
-  const uint32_t K = CH ? cuts.k : 1u;
-  const uint32_t RPW = (NBK + 1) * K + 1;  // row_ptr entries per window
+  const uint32_t RPW = NBK + 2;  // row_ptr entries per window
   const uint32_t r = blockIdx.x, ws = blockIdx.y, tid = threadIdx.x;
   const uint32_t shift = key_max ? win_shift(key_max[ws]) : 0u;
   const uint32_t KR = KRANGE >> shift;  // keys per range in this window
   const uint32_t lo = r * KR;
   const bool last = shift == 0 && r == NR - 1;  // only the full-width layout reaches key NBK
-  const uint32_t nb = (KR + (last ? 1u : 0u)) * K;  // bins in use: (key - lo, chunk)
+  const uint32_t nb = KR + (last ? 1u : 0u);  // bins in use
   const uint32_t rbeg = region_base[ws * (NR + 1) + r], rend = region_base[ws * (NR + 1) + r + 1];
   const uint32_t len = rend - rbeg;
   const bool cached = len <= LS_CACHE;
   const SortElem* in = temp + (size_t)ws * n + rbeg;
-  auto bin_of = [&](const SortElem& e) {
-    uint32_t b = (e.key - lo) * K;
-    if (CH) {
-      const uint32_t idx = e.idx_sign & 0x7fffffffu;
-#pragma unroll
-      for (uint32_t j = 1; j < MAXK; j++) b += (j < K && idx >= cuts.cut[j]) ? 1u : 0u;
-    }
-    return b;
-  };
-  for (uint32_t b = tid; b < NBINS; b += 256) bins[b] = 0;
+  if (tid < NBINS) bins[tid] = 0;
   __syncthreads();
   SortElem e[LS_REG];
   if (cached) {
@@ -246,7 +228,7 @@ __global__ void __launch_bounds__(256) k_local_sort_lds(const SortElem* __restri
     }
 #pragma unroll
     for (uint32_t u = 0; u < LS_REG; u++)
-      if (u * 256 + tid < len) atomicAdd(&bins[bin_of(e[u])], 1u);
+      if (u * 256 + tid < len) atomicAdd(&bins[e[u].key - lo], 1u);
   } else {
     for (uint32_t i0 = 0; i0 < len; i0 += 2048) {
       SortElem f[8];
@@ -259,19 +241,13 @@ __global__ void __launch_bounds__(256) k_local_sort_lds(const SortElem* __restri
       }
 #pragma unroll
       for (int u = 0; u < 8; u++)
-        if (i0 + u * 256 + tid < len) atomicAdd(&bins[bin_of(f[u])], 1u);
+        if (i0 + u * 256 + tid < len) atomicAdd(&bins[f[u].key - lo], 1u);
     }
   }
   __syncthreads();
-  // exclusive scan over the bins in use: a thread owns PER consecutive bins
-  uint32_t own[PER], sum = 0;
-#pragma unroll
-  for (uint32_t k = 0; k < PER; k++) {
-    const uint32_t b = tid * PER + k;
-    own[k] = b < nb ? bins[b] : 0u;
-    sum += own[k];
-  }
-  part[tid] = sum;
+  // exclusive scan over the bins in use
+  const uint32_t own = tid < nb ? bins[tid] : 0u;
+  part[tid] = own;
   __syncthreads();
   for (uint32_t off = 1; off < 256; off <<= 1) {
     const uint32_t v = tid >= off ? part[tid - off] : 0u;
@@ -279,21 +255,16 @@ __global__ void __launch_bounds__(256) k_local_sort_lds(const SortElem* __restri
     part[tid] += v;
     __syncthreads();
   }
-  uint32_t* rp = row_ptr + (size_t)ws * RPW + (size_t)lo * K;  // bin b of this range is offset lo K + b of the window
-  uint32_t start = rbeg + part[tid] - sum;
+  uint32_t* rp = row_ptr + (size_t)ws * RPW + lo;  // bin b of this range is offset lo + b of the window
+  const uint32_t start = rbeg + part[tid] - own;
   __syncthreads();
-#pragma unroll
-  for (uint32_t k = 0; k < PER; k++) {
-    const uint32_t b = tid * PER + k;
-    if (b < nb) {
-      bins[b] = start;  // becomes the write cursor of the bin
-      rp[b] = start;
-      start += own[k];
-    }
+  if (tid < nb) {
+    bins[tid] = start;  // becomes the write cursor of the bin
+    rp[tid] = start;
   }
   if (tid == 0 && last) rp[nb] = rend;  // the end sentinel behind key NBK
   if (shift) {  // narrowed ranges cover keys below NR * KR only: every row above is empty and starts at the end
-    const uint32_t covered = NR * KR * K, total = region_base[ws * (NR + 1) + NR];
+    const uint32_t covered = NR * KR, total = region_base[ws * (NR + 1) + NR];
     const uint32_t per_block = (RPW - covered + NR - 1) / NR;
     uint32_t* rp_w = row_ptr + (size_t)ws * RPW;
     for (uint32_t j = tid; j < per_block; j += 256) {
@@ -306,7 +277,7 @@ __global__ void __launch_bounds__(256) k_local_sort_lds(const SortElem* __restri
   if (cached) {
 #pragma unroll
     for (uint32_t u = 0; u < LS_REG; u++)
-      if (u * 256 + tid < len) sorted[atomicAdd(&bins[bin_of(e[u])], 1u) - rbeg] = e[u].idx_sign;
+      if (u * 256 + tid < len) sorted[atomicAdd(&bins[e[u].key - lo], 1u) - rbeg] = e[u].idx_sign;
     __syncthreads();
     for (uint32_t i = tid; i < len; i += 256) vi[rbeg + i] = sorted[i];
   } else {
@@ -322,7 +293,7 @@ __global__ void __launch_bounds__(256) k_local_sort_lds(const SortElem* __restri
 #pragma unroll
       for (int u = 0; u < 8; u++) {
         const uint32_t i = i0 + u * 256 + tid;
-        if (i < len) vi[atomicAdd(&bins[bin_of(f[u])], 1u)] = f[u].idx_sign;
+        if (i < len) vi[atomicAdd(&bins[f[u].key - lo], 1u)] = f[u].idx_sign;
       }
     }
   }

@@ -6,7 +6,7 @@
 // Pipeline (each stage names the reference code it replaces; paths relative to /root/reference/src/submission/):
 //   kernels/convert.hpp     k_affine_up / host inversion / k_affine_down (n >= 2^20, resident tables), k_convert_bases (otherwise)
 //                           wire x||y -> Montgomery records            wgsl/cuzk/convert_point_coords_and_decompose_scalars.template.wgsl:41-99 + barrett.template.wgsl:60-82
-//   kernels/decompose.hpp   k_decompose (16 windows), k_decompose_geom / k_decompose_narrow (inputs <= 2^16 points: 22 / 23 windows of 2^11 buckets, submission.ts:97)
+//   kernels/decompose.hpp   k_decompose (16 windows), k_decompose_geom (inputs <= 2^16 points: 22 windows of 2^11 buckets, submission.ts:97)
 //                           scalars -> signed digits                   same file :100-141; model cuzk/utils.ts:66-109
 //   kernels/sort.hpp        k_range_count / k_range_scan / k_partition / k_local_sort (k_small_sort on the narrow path)
 //                           per-window counting sort -> CSR            wgsl/cuzk/transpose_serial.wgsl:34-76 (16 serial threads there); model cuzk/transpose.ts:14-62
@@ -121,17 +121,16 @@ void identity_wire(uint8_t out[96]) {
   out[48] = 1;
 }
 
-struct StageTimer {  // HIP events around one stage of one part, on the part's own stream
+struct StageTimer {  // HIP events around one stage of a call, on its stream
   msm377_ctx* c;
   int s;
   hipStream_t st;
-  uint32_t part;
   bool on() const { return c->timing == 1 || (c->timing == 2 && s == MSM377_STAGE_ACC_KERNEL); }
-  StageTimer(msm377_ctx* ctx, int stage, hipStream_t stream, uint32_t part_) : c(ctx), s(stage), st(stream), part(part_) {
-    if (on()) (void)hipEventRecord(c->ev[part][s][0], st);
+  StageTimer(msm377_ctx* ctx, int stage, hipStream_t stream) : c(ctx), s(stage), st(stream) {
+    if (on()) (void)hipEventRecord(c->ev[s][0], st);
   }
   ~StageTimer() {
-    if (on()) (void)hipEventRecord(c->ev[part][s][1], st);
+    if (on()) (void)hipEventRecord(c->ev[s][1], st);
   }
 };
 
@@ -144,12 +143,12 @@ int convert_bases(msm377_ctx* ctx, const uint32_t* d_raw, uint64_t n, uint64_t f
   // gather kernel publishes, and that kernel is the LAST launch of a call and reads the buckets only (the invariant
   // is spelled out at publish_to_host, kernels/reduce.hpp).
   if (n == 0) return MSM377_OK;
-  if (ctx->timing == 1) (void)hipEventRecord(ctx->ev[0][MSM377_STAGE_CONVERT][0], ctx->stream2);
+  if (ctx->timing == 1) (void)hipEventRecord(ctx->ev[MSM377_STAGE_CONVERT][0], ctx->stream2);
   if (clear_err) hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(256), 0, ctx->stream2, (uint32_t*)(ctx->d_err + 2), 1u, (uint32_t*)nullptr, 0u);
   hipLaunchKernelGGL(k_convert_bases<CV>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream2, d_raw, ctx->d_bases + first * CV::REC_WORDS, n,
                      ctx->d_err + 2);
   HIP_TRY(ctx, hipGetLastError());
-  if (ctx->timing == 1) (void)hipEventRecord(ctx->ev[0][MSM377_STAGE_CONVERT][1], ctx->stream2);
+  if (ctx->timing == 1) (void)hipEventRecord(ctx->ev[MSM377_STAGE_CONVERT][1], ctx->stream2);
   HIP_TRY(ctx, hipEventRecord(ctx->bases_ready, ctx->stream2));
   return MSM377_OK;
 }
@@ -162,7 +161,7 @@ int convert_bases(msm377_ctx* ctx, const uint32_t* d_raw, uint64_t n, uint64_t f
 int affine_convert_begin(msm377_ctx* ctx, const uint32_t* d_raw, uint64_t n, const uint32_t* prev_window_records = nullptr, bool clear_err = true) {
   if (n == 0) return MSM377_OK;
   const uint32_t nblk = affine_blocks(n);
-  if (ctx->timing == 1) (void)hipEventRecord(ctx->ev[0][MSM377_STAGE_CONVERT][0], ctx->stream2);
+  if (ctx->timing == 1) (void)hipEventRecord(ctx->ev[MSM377_STAGE_CONVERT][0], ctx->stream2);
   __atomic_store_n(ctx->h_aff_flag, 0u, __ATOMIC_RELEASE);
   if (clear_err) hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(256), 0, ctx->stream2, (uint32_t*)(ctx->d_err + 2), 1u, (uint32_t*)nullptr, 0u);
   if (prev_window_records)
@@ -205,7 +204,7 @@ int affine_convert_finish(msm377_ctx* ctx, uint32_t* d_records_out, uint64_t n, 
   // it wait for the sort was measured both ways in round 2: 2^20 2.62 -> 2.59 ms, 2^22 10.39 -> 10.21 without the wait).
   hipLaunchKernelGGL(k_affine_down, dim3(nblk), dim3(AFF_THREADS), 0, ctx->stream2, n, ctx->d_aff_stash, ctx->d_aff_trees, ctx->dm_aff_inv, d_records_out, ctx->conv_wave_prio);
   HIP_TRY(ctx, hipGetLastError());
-  if (ctx->timing == 1) (void)hipEventRecord(ctx->ev[0][MSM377_STAGE_CONVERT][1], ctx->stream2);
+  if (ctx->timing == 1) (void)hipEventRecord(ctx->ev[MSM377_STAGE_CONVERT][1], ctx->stream2);
   HIP_TRY(ctx, hipEventRecord(ctx->bases_ready, ctx->stream2));
   return MSM377_OK;
 }
@@ -225,12 +224,6 @@ uint32_t auto_seg(const msm377_ctx* ctx, uint64_t entries, bool glv) {
 }
 
 
-
-// Enqueue stages decompose .. gather for windows [wb, wb + wc) against ctx->d_bases, the D2H of
-// the partial records into slot `slot` of ctx->h_partials and that slot's completion event.
-// Nothing here waits for the GPU.
-// One part of a call's windows: window slots [ws0, ws0 + wc) of every window-indexed buffer, windows
-// [wb, wb + wc) of the scalars, on its own stream.
 // Which stages of a call to enqueue (all of them, except for the chunked host-buffer entry point).
 struct Phase {
   bool clear_err = true;   // first chunk of a call
@@ -244,9 +237,9 @@ struct Phase {
   // before the reduction: one window's reduction, one window's partial record, a 16-step host tail.
   const uint32_t* table = nullptr;
   uint64_t table_stride = 0;
-  // Window width of the call: 16 (the main path: 16 windows x 2^15 buckets, the two-level sort) or NARROW_BITS (small
-  // inputs: k_decompose_narrow + k_small_sort, 22 windows x 2^11 buckets); everything behind the sort takes
-  // L = cbits - 1 as a run-time argument.
+  // Window width of the call: 16 (the main path: 16 windows x 2^15 buckets, the two-level sort) or NARROW_EVEN_BITS
+  // (small inputs: k_decompose_geom + k_small_sort, 22 windows x 2^11 buckets); everything behind the sort takes
+  // L = bucket_log as a run-time argument.
   uint32_t cbits = MSM377_WINDOW_BITS;
   uint32_t bucket_log = MSM377_WINDOW_BITS - 1;  // L: 2^L buckets per window (NARROW_LOG on the small-input path)
   // Wide windows over a precomputed table (kernels/wide.hpp): `table` holds [2^(20 w)] P_i for 13 windows, the call has
@@ -254,188 +247,180 @@ struct Phase {
   bool wide = false;
   bool even = false;  // whole MSMs on 16 windows: the top three windows 15 bits wide (kernels/decompose.hpp k_decompose); the tail gets short_from = EVEN_FROM
   const uint32_t* bases_override = nullptr;  // base records of the call if not ctx->d_bases (the wide table's window 0 = the plain affine records)
-  // Points that arrive in chunks (run_sorted_upload): ONE decomposition and sort of all scalars files every row's entries
-  // by chunk (`cuts`), then each chunk's accumulation phase walks its own sub-rows (`chunk`) once its points are on the
-  // device.  sort / accumulate select which half of the front phase a call enqueues.
-  bool sort = true;        // decompose + sort
-  bool accumulate = true;  // work list, accumulation, merge of split rows
-  ChunkCuts cuts;          // cuts.k > 1: rows filed by chunk
-  uint32_t chunk = 0;      // the chunk this phase accumulates
-  uint64_t chunk_points = 0;  // its points (work-item length), 0 = all n
 };
 
-struct PartView {
-  hipStream_t st;
-  uint32_t part, ws0, wb, wc;
-  size_t work_off, ovf_off;  // first work item / overflow slot of this part
-};
-
-template <class CV, class BP>
-int enqueue_part(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scalars, uint64_t n, const PartView& pv, int* d_err, uint32_t* d_partials, bool glv,
-                 uint32_t sort_blocks, const Phase& ph) {
-  hipStream_t st = pv.st;
-  const uint32_t wc = pv.wc, part = pv.part;
+// Enqueue stages decompose .. gather for windows [wb, wb + wc) against ctx->d_bases on the main stream, the D2H of
+// the partial records into slot `slot` of ctx->h_partials and that slot's completion event.
+// Nothing here waits for the GPU.
+//
+// (Rounds 1 and 2 could run a large call as TWO parts of half the windows on two streams, so that one part's sort and
+// reduction hid under the other's accumulation: 3.19 vs 3.17 ms at 2^20, then 2.72 -> 2.89 on round 2's kernels -- the
+// accumulation kernel owns every VGPR of the chip, kernels of another stream do not become co-resident.  Removed in
+// round 3.)
+template <class CV, class BP = CV>
+int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scalars, uint32_t wb, uint32_t wc, int slot, bool glv = false,
+                    const Phase& ph = Phase()) {
+  // GLV front end: n_scalars scalars become 2 n_scalars (point, half-scalar) columns over 8 windows.
+  const uint64_t n = glv ? 2 * n_scalars : n_scalars;
+  hipStream_t st = ctx->stream;
+  int* d_err = ctx->d_err + slot;
+  uint32_t* d_partials = ctx->d_partials + (size_t)slot * SLOT_WORDS;
+  // the error word is cleared by the call's first kernel together with its counters -- unless there is no such kernel
+  // (back phase only)
+  if (ph.clear_err && !ph.front) hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(256), 0, st, (uint32_t*)d_err, 1u, (uint32_t*)nullptr, 0u);
+  ctx->zc_active = ph.zc_out && ph.back && ctx->zc_out && slot == 0 && !ph.table;
+  if (ctx->zc_active) ctx->out_seq++;
   const uint32_t L = ph.bucket_log, NB = 1u << L;  // this call's bucket geometry (shadows the main path's constant)
-  const RowView rv{ph.cuts.k, ph.chunk};
-  const uint32_t wprio = ctx->front_wave_prio;  // s_setprio in the decompose / sort / work-list kernels
-  const uint32_t RP = (NB + 1) * rv.k + 1;  // row_ptr entries per window slot (NB + 2 for plain rows)
   const bool wide = ph.wide;
   const bool narrow = !wide && ph.cbits != MSM377_WINDOW_BITS;
-  const uint64_t entries = wide ? (uint64_t)WIDE_WINDOWS * n : (uint64_t)wc * (ph.chunk_points ? ph.chunk_points : n);  // (window, point) pairs this phase accumulates
-  static_assert((uint64_t)NARROW_WINDOWS * SMALL_SORT_MAX / NARROW_SEG + NARROW_WINDOWS * (1u << NARROW_LOG) <= (uint64_t)MSM377_NUM_WINDOWS * 32768, "narrow work items fit the work-item buffer");
-  // per launch: each part must fill the GPU on its own.  Narrow windows: a small input is all latency -- a work item is
+  const uint64_t entries = (wide ? (uint64_t)WIDE_WINDOWS : (uint64_t)wc) * n;  // (window, point) pairs this call accumulates
+  static_assert((uint64_t)NARROW_EVEN_WINDOWS * SMALL_SORT_MAX / NARROW_SEG + NARROW_EVEN_WINDOWS * (1u << NARROW_LOG) <= (uint64_t)MSM377_NUM_WINDOWS * 32768,
+                "narrow work items fit the work-item buffer");
+  // Each launch must fill the GPU on its own.  Narrow windows: a small input is all latency -- a work item is
   // a serial chain of ~10 us additions -- so its chains are cut at 8 entries (the buffers, sized for 16 windows of
-  // 2^15 rows plus entries / SEG_MIN items, hold the 23 x 2^11 rows and 23 n / 8 items of an input this small easily).
+  // 2^15 rows plus entries / SEG_MIN items, hold the 22 x 2^11 rows and 22 n / 8 items of an input this small easily).
   // (With the even geometry and quad-cooperative record loads in the merge, 16 entries win from 2^14 points on and 12
   // at 2^13 -- accumulate + merge 0.288 / 0.277 / 0.284 / 0.270 ms for 8 / 10 / 12 / 16 at 2^16, 0.077 / 0.077 / 0.074 /
   // 0.085 at 2^13, profiles/r03_final/sweep_narrow_seg_even.txt; below that a row has two entries on average.)
   const uint32_t SEG = (narrow && !ctx->seg_plain) ? (ctx->narrow_seg ? ctx->narrow_seg : (n > 8192 ? 16u : 12u)) : auto_seg(ctx, entries, glv);
-  uint16_t* digits = ctx->d_digits + (size_t)pv.ws0 * n;
-  uint32_t* range_counts = ctx->d_range_counts + (size_t)part * NRANGE * (MAX_SORT_BLOCKS / 2);
-  uint32_t* region_base = ctx->d_region_base + (size_t)pv.ws0 * (NRANGE + 1);
-  SortElem* sort_temp = ctx->d_sort_temp + (size_t)pv.ws0 * n;
-  uint32_t* row_ptr = (rv.k > 1 ? ctx->d_row_ptr_chunks : ctx->d_row_ptr) + (size_t)pv.ws0 * RP;
-  uint32_t* val_idx = ctx->d_val_idx + (size_t)pv.ws0 * n;
-  uint32_t* buckets = ctx->d_buckets + (size_t)pv.ws0 * CV::BKT_WORDS * NB;
-  uint32_t* row_ovf_base = ctx->d_row_ovf_base + (size_t)pv.ws0 * NB;
-  uint32_t* split_rows = ctx->d_split_rows + (size_t)pv.ws0 * NB;
-  WorkItem* work = ctx->d_work + pv.work_off;
-  uint32_t* ovf = ctx->d_ovf + pv.ovf_off * CV::BKT_WORDS;
+  uint16_t* digits = ctx->d_digits;
+  uint32_t* range_counts = ctx->d_range_counts;
+  uint32_t* region_base = ctx->d_region_base;
+  SortElem* sort_temp = ctx->d_sort_temp;
+  uint32_t* row_ptr = ctx->d_row_ptr;
+  uint32_t* val_idx = ctx->d_val_idx;
+  uint32_t* buckets = ctx->d_buckets;
+  uint32_t* row_ovf_base = ctx->d_row_ovf_base;
+  uint32_t* split_rows = ctx->d_split_rows;
+  WorkItem* work = ctx->d_work;
+  uint32_t* ovf = ctx->d_ovf;
   const uint32_t* bases = ph.table ? ph.table : ph.bases_override ? ph.bases_override : ctx->d_bases + ph.base_first * BP::REC_WORDS;
-  uint32_t* meta_block = ctx->d_work_meta + (size_t)part * META_BLOCK_WORDS;  // [work-list counters | key_max[16]]
+  uint32_t* meta_block = ctx->d_work_meta;  // [work-list counters | key_max[16]]
   uint32_t* key_max = meta_block + (2 * SEG_BINS + 4);
   if (ph.front) {
-  // One memset clears this part's work-list counters AND its key_max words (0 = full-width ranges); k_decompose
-  // then measures window 15 of the plain front end.
-  hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(256), 0, st, meta_block, META_BLOCK_WORDS, (uint32_t*)d_err, (ph.clear_err && part == 0) ? 1u : 0u);
-  uint32_t* top_key_max = (!glv && !ph.even && pv.wb + wc == MSM377_NUM_WINDOWS) ? key_max + (wc - 1) : nullptr;
-  const uint64_t max_items = (uint64_t)wc * NB + entries / SEG;  // every row has an item; extra ones are full segments
-  // a lane quad per work item while the launch is one chain's latency (up to 2^14 points: ~94 k items); beyond that
-  // the quads are VALU-bound like threads and only add their exchange instructions (kernel at 2^16: 0.216 / 0.183 ms)
-  const bool quad_acc = std::is_same<BP, CV>::value && std::is_same<CV, TeDev>::value && narrow && ctx->narrow_quad_acc && !ph.table && max_items <= ctx->narrow_quad_items;
-  // (One launch for the whole front end of such a call -- each window's workgroup recoding, sorting and listing its
-  // work items itself, one global atomic per list and workgroup -- was built and dropped: 0.271 -> 0.293 ms at 2^12,
-  // 0.342 -> 0.373 at 2^14.  Saving four dispatch latencies did not pay for a work list that is sorted by length
-  // only within each window: the accumulation kernel went from 0.038 to 0.054 ms at 2^12.)
-  if (ph.sort) {
-  {
-    StageTimer t(ctx, MSM377_STAGE_DECOMPOSE, st, part);
-    if (wide)
-      hipLaunchKernelGGL(k_decompose_wide, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, ctx->d_wide_digits, n, d_err);
-    else if (narrow && ph.even)
-      hipLaunchKernelGGL(k_decompose_geom, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, digits, n, L, NARROW_EVEN_SIGNED, wc, 1u << L, d_err);
-    else if (narrow)
-      hipLaunchKernelGGL(k_decompose_narrow, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, digits, n, ph.cbits, L, wc, d_err);
-    else if (glv)
-      hipLaunchKernelGGL(k_decompose_glv, dim3((unsigned)((n_scalars + 255) / 256)), dim3(256), 0, st, d_scalars, digits, n_scalars, pv.wb, wc, d_err);
-    else
-      hipLaunchKernelGGL(k_decompose, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, digits, n, pv.wb, wc, d_err, top_key_max, wprio, ph.even ? 1u : 0u);
-    HIP_TRY(ctx, hipGetLastError());
-  }
-
-  if (wide) {  // the 13 n entries into 4096 fine ranges: two staged partition passes per window (kernels/wide.hpp), then k_local_sort_lds
-    StageTimer t(ctx, MSM377_STAGE_SORT, st, part);
-    uint32_t* wc = ctx->d_wide_counts;
-    hipLaunchKernelGGL(k_wide_count, dim3(WS_CHUNKS, WIDE_WINDOWS), dim3(1024), 0, st, (const uint32_t*)ctx->d_wide_digits, wc, n);
-    hipLaunchKernelGGL(k_wide_sums, dim3(WIDE_NRANGE / 256, WIDE_WINDOWS), dim3(256), 0, st, wc);
-    hipLaunchKernelGGL(k_wide_scan, dim3(1), dim3(1024), 0, st, wc, region_base);
-    hipLaunchKernelGGL(k_wide_offsets1, dim3(WIDE_WINDOWS), dim3(WS_COARSE), 0, st, wc, n);
-    hipLaunchKernelGGL(k_wide_part1, dim3(WS_CHUNKS, WIDE_WINDOWS), dim3(1024), 0, st, (const uint32_t*)ctx->d_wide_digits, (const uint32_t*)wc, sort_temp, n, (uint32_t)ph.table_stride);
-    hipLaunchKernelGGL(k_wide_part2, dim3(WS_COARSE, WIDE_WINDOWS), dim3(1024), 0, st, (const SortElem*)sort_temp, (const uint32_t*)wc, ctx->d_wide_temp);
-    hipLaunchKernelGGL(k_local_sort_lds<false>, dim3(WIDE_NRANGE, 1), dim3(256), 0, st, (const SortElem*)ctx->d_wide_temp, region_base, row_ptr, val_idx, entries,
-                       (const uint32_t*)nullptr, WIDE_NRANGE, NB, ChunkCuts{}, wprio);
-    HIP_TRY(ctx, hipGetLastError());
-  } else if (narrow) {
-    StageTimer t(ctx, MSM377_STAGE_SORT, st, part);
-    hipLaunchKernelGGL(k_small_sort, dim3(wc), dim3(1024), 0, st, digits, row_ptr, val_idx, (uint32_t)n, L);
-    HIP_TRY(ctx, hipGetLastError());
-  } else {
-    StageTimer t(ctx, MSM377_STAGE_SORT, st, part);
-    uint32_t chunks = sort_blocks / wc;
-    const uint64_t want = (n + 4095) / 4096;  // at least ~4096 elements per block
-    if (chunks > want) chunks = (uint32_t)(want ? want : 1);
-    const uint64_t per_chunk = (n + chunks - 1) / chunks;
-    hipLaunchKernelGGL(k_range_count, dim3(chunks, wc), dim3(1024), 0, st, digits, range_counts, n, chunks, per_chunk, key_max, wprio);
-    HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_range_scan, dim3(wc), dim3(NRANGE), 0, st, range_counts, region_base, chunks, wprio);
-    HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_partition_staged, dim3(chunks, wc), dim3(1024), 0, st, digits, range_counts, sort_temp, n, chunks, per_chunk, key_max, wprio);
-    HIP_TRY(ctx, hipGetLastError());
-    if (rv.k > 1)  // rows filed by upload chunk: K sub-row bounds per key
-      hipLaunchKernelGGL(k_local_sort_lds<true>, dim3(NRANGE, wc), dim3(256), 0, st, sort_temp, region_base, row_ptr, val_idx, n, key_max, NRANGE, NB, ph.cuts, wprio);
-    else
-      hipLaunchKernelGGL(k_local_sort_lds<false>, dim3(NRANGE, wc), dim3(256), 0, st, sort_temp, region_base, row_ptr, val_idx, n, key_max, NRANGE, NB, ChunkCuts{}, wprio);
-    HIP_TRY(ctx, hipGetLastError());
-  }
-  }  // ph.sort
-  if (ph.accumulate) {
-    StageTimer t(ctx, MSM377_STAGE_ACCUMULATE, st, part);
-    const uint32_t rows = wc * NB;
-    uint32_t* meta = meta_block;
-    uint32_t* work_hist = meta;
-    uint32_t* cursor = meta + SEG_BINS;
-    uint32_t* total = meta + 2 * SEG_BINS;
-    uint32_t* counters = meta + 2 * SEG_BINS + 1;  // [0] split rows, [1] overflow slots
-    hipLaunchKernelGGL(k_work_hist, dim3((rows + 1023) / 1024), dim3(1024), 0, st, row_ptr, L, rows, SEG, work_hist, row_ovf_base, counters, split_rows, rv, wprio);
-    HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_work_scatter, dim3((rows + 1023) / 1024), dim3(1024), 0, st, row_ptr, L, rows, SEG, (const uint32_t*)work_hist, cursor, total, work, rv, wprio);
-    HIP_TRY(ctx, hipGetLastError());
-    if (ctx->before_accumulate) {  // must run before the wait below is queued: the wait binds to the event's latest record
-      std::function<int()> f;
-      f.swap(ctx->before_accumulate);
-      const int hook_rc = f();
-      if (hook_rc) return hook_rc;
-    }
-    HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->bases_ready, 0));
-    ctx->last_products = BP::MADD_PRODUCTS;
+    // One memset clears the call's work-list counters AND its key_max words (0 = full-width ranges); k_decompose
+    // then measures window 15 of the plain front end.
+    hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(256), 0, st, meta_block, META_BLOCK_WORDS, (uint32_t*)d_err, ph.clear_err ? 1u : 0u);
+    uint32_t* top_key_max = (!glv && !ph.even && wb + wc == MSM377_NUM_WINDOWS) ? key_max + (wc - 1) : nullptr;
+    const uint64_t max_items = (uint64_t)wc * NB + entries / SEG;  // every row has an item; extra ones are full segments
+    // a lane quad per work item while the launch is one chain's latency (up to 2^14 points: ~94 k items); beyond that
+    // the quads are VALU-bound like threads and only add their exchange instructions (kernel at 2^16: 0.216 / 0.183 ms)
+    const bool quad_acc = std::is_same<BP, CV>::value && std::is_same<CV, TeDev>::value && narrow && !ph.table && max_items <= ctx->narrow_quad_items;
+    // (One launch for the whole front end of such a call -- each window's workgroup recoding, sorting and listing its
+    // work items itself, one global atomic per list and workgroup -- was built and dropped: 0.271 -> 0.293 ms at 2^12,
+    // 0.342 -> 0.373 at 2^14.  Saving four dispatch latencies did not pay for a work list that is sorted by length
+    // only within each window: the accumulation kernel went from 0.038 to 0.054 ms at 2^12.)
     {
-      StageTimer tk(ctx, MSM377_STAGE_ACC_KERNEL, st, part);
-      const dim3 grid((unsigned)((max_items + 255) / 256));
-      bool launched = false;
-      if constexpr (std::is_same<BP, CV>::value && std::is_same<CV, TeDev>::value) {
-        if (quad_acc) {
-          hipLaunchKernelGGL(k_accumulate_quad<CV>, dim3((unsigned)((4 * max_items + 255) / 256)), dim3(256), 0, st, row_ptr, val_idx, bases, buckets, n, work, total,
-                             row_ovf_base, ovf, SEG, d_err, ctx->d_err + 2, ph.into ? 1u : 0u, L);
-          launched = true;
-        }
-      }
-      if (launched) {
-      } else if constexpr (!std::is_same<BP, CV>::value)
-        hipLaunchKernelGGL((k_accumulate<CV, 2, BP>), grid, dim3(256), 0, st, row_ptr, val_idx, bases, buckets, n, work, total, row_ovf_base, ovf, SEG, d_err,
-                           ctx->d_err + 2, ph.into ? 1u : 0u, ph.table_stride, L, rv);
+      StageTimer t(ctx, MSM377_STAGE_DECOMPOSE, st);
+      if (wide)
+        hipLaunchKernelGGL(k_decompose_wide, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, ctx->d_wide_digits, n, d_err);
+      else if (narrow)
+        hipLaunchKernelGGL(k_decompose_geom, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, digits, n, L, NARROW_EVEN_SIGNED, wc, 1u << L, d_err);
+      else if (glv)
+        hipLaunchKernelGGL(k_decompose_glv, dim3((unsigned)((n_scalars + 255) / 256)), dim3(256), 0, st, d_scalars, digits, n_scalars, wb, wc, d_err);
       else
-        hipLaunchKernelGGL((k_accumulate<CV, 2>), grid, dim3(256), 0, st, row_ptr, val_idx, bases, buckets, n, work, total, row_ovf_base, ovf, SEG, d_err,
-                           ctx->d_err + 2, ph.into ? 1u : 0u, ph.table_stride, L, rv);
+        hipLaunchKernelGGL(k_decompose, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, digits, n, wb, wc, d_err, top_key_max, ph.even ? 1u : 0u);
+      HIP_TRY(ctx, hipGetLastError());
     }
-    HIP_TRY(ctx, hipGetLastError());
-    if (part == 0) ctx->acc_seq++;
-    static_assert(CV::HAS_QUAD, "every curve policy has the quad-cooperative addition");
-    // (grid-stride over the split-row list: with the even windows few rows split, and 8192 workgroups that only read the
-    // count cost 11 us at 2^20)
-    hipLaunchKernelGGL(k_merge_split_rows_quad<CV>, dim3(std::min<uint32_t>((rows + 63) / 64, 1024u)), dim3(256), 0, st, row_ptr, buckets, counters, split_rows, row_ovf_base, ovf, SEG, d_err, L, rv,
-                       part == 0 ? ctx->dm_out_flag + ACC_FLAG_WORD : (uint32_t*)nullptr, ctx->acc_seq);
-    HIP_TRY(ctx, hipGetLastError());
-  }  // ph.accumulate
+
+    if (wide) {  // the 13 n entries into 4096 fine ranges: two staged partition passes per window (kernels/wide.hpp), then k_local_sort_lds
+      StageTimer t(ctx, MSM377_STAGE_SORT, st);
+      uint32_t* wc = ctx->d_wide_counts;
+      hipLaunchKernelGGL(k_wide_count, dim3(WS_CHUNKS, WIDE_WINDOWS), dim3(1024), 0, st, (const uint32_t*)ctx->d_wide_digits, wc, n);
+      hipLaunchKernelGGL(k_wide_sums, dim3(WIDE_NRANGE / 256, WIDE_WINDOWS), dim3(256), 0, st, wc);
+      hipLaunchKernelGGL(k_wide_scan, dim3(1), dim3(1024), 0, st, wc, region_base);
+      hipLaunchKernelGGL(k_wide_offsets1, dim3(WIDE_WINDOWS), dim3(WS_COARSE), 0, st, wc, n);
+      hipLaunchKernelGGL(k_wide_part1, dim3(WS_CHUNKS, WIDE_WINDOWS), dim3(1024), 0, st, (const uint32_t*)ctx->d_wide_digits, (const uint32_t*)wc, sort_temp, n, (uint32_t)ph.table_stride);
+      hipLaunchKernelGGL(k_wide_part2, dim3(WS_COARSE, WIDE_WINDOWS), dim3(1024), 0, st, (const SortElem*)sort_temp, (const uint32_t*)wc, ctx->d_wide_temp);
+      hipLaunchKernelGGL(k_local_sort_lds, dim3(WIDE_NRANGE, 1), dim3(256), 0, st, (const SortElem*)ctx->d_wide_temp, region_base, row_ptr, val_idx, entries,
+                         (const uint32_t*)nullptr, WIDE_NRANGE, NB);
+      HIP_TRY(ctx, hipGetLastError());
+    } else if (narrow) {
+      StageTimer t(ctx, MSM377_STAGE_SORT, st);
+      hipLaunchKernelGGL(k_small_sort, dim3(wc), dim3(1024), 0, st, digits, row_ptr, val_idx, (uint32_t)n, L);
+      HIP_TRY(ctx, hipGetLastError());
+    } else {
+      StageTimer t(ctx, MSM377_STAGE_SORT, st);
+      uint32_t chunks = MAX_SORT_BLOCKS / wc;
+      const uint64_t want = (n + 4095) / 4096;  // at least ~4096 elements per block
+      if (chunks > want) chunks = (uint32_t)(want ? want : 1);
+      const uint64_t per_chunk = (n + chunks - 1) / chunks;
+      hipLaunchKernelGGL(k_range_count, dim3(chunks, wc), dim3(1024), 0, st, digits, range_counts, n, chunks, per_chunk, key_max);
+      HIP_TRY(ctx, hipGetLastError());
+      hipLaunchKernelGGL(k_range_scan, dim3(wc), dim3(NRANGE), 0, st, range_counts, region_base, chunks);
+      HIP_TRY(ctx, hipGetLastError());
+      hipLaunchKernelGGL(k_partition_staged, dim3(chunks, wc), dim3(1024), 0, st, digits, range_counts, sort_temp, n, chunks, per_chunk, key_max);
+      HIP_TRY(ctx, hipGetLastError());
+      hipLaunchKernelGGL(k_local_sort_lds, dim3(NRANGE, wc), dim3(256), 0, st, sort_temp, region_base, row_ptr, val_idx, n, key_max, NRANGE, NB);
+      HIP_TRY(ctx, hipGetLastError());
+    }
+
+    {  // work list, accumulation, merge of split rows
+      StageTimer t(ctx, MSM377_STAGE_ACCUMULATE, st);
+      const uint32_t rows = wc * NB;
+      uint32_t* meta = meta_block;
+      uint32_t* work_hist = meta;
+      uint32_t* cursor = meta + SEG_BINS;
+      uint32_t* total = meta + 2 * SEG_BINS;
+      uint32_t* counters = meta + 2 * SEG_BINS + 1;  // [0] split rows, [1] overflow slots
+      hipLaunchKernelGGL(k_work_hist, dim3((rows + 1023) / 1024), dim3(1024), 0, st, row_ptr, L, rows, SEG, work_hist, row_ovf_base, counters, split_rows);
+      HIP_TRY(ctx, hipGetLastError());
+      hipLaunchKernelGGL(k_work_scatter, dim3((rows + 1023) / 1024), dim3(1024), 0, st, row_ptr, L, rows, SEG, (const uint32_t*)work_hist, cursor, total, work);
+      HIP_TRY(ctx, hipGetLastError());
+      if (ctx->before_accumulate) {  // must run before the wait below is queued: the wait binds to the event's latest record
+        std::function<int()> f;
+        f.swap(ctx->before_accumulate);
+        const int hook_rc = f();
+        if (hook_rc) return hook_rc;
+      }
+      HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->bases_ready, 0));
+      ctx->last_products = BP::MADD_PRODUCTS;
+      {
+        StageTimer tk(ctx, MSM377_STAGE_ACC_KERNEL, st);
+        const dim3 grid((unsigned)((max_items + 255) / 256));
+        bool launched = false;
+        if constexpr (std::is_same<BP, CV>::value && std::is_same<CV, TeDev>::value) {
+          if (quad_acc) {
+            hipLaunchKernelGGL(k_accumulate_quad<CV>, dim3((unsigned)((4 * max_items + 255) / 256)), dim3(256), 0, st, row_ptr, val_idx, bases, buckets, n, work, total,
+                               row_ovf_base, ovf, SEG, d_err, ctx->d_err + 2, ph.into ? 1u : 0u, L);
+            launched = true;
+          }
+        }
+        if (launched) {
+        } else if constexpr (!std::is_same<BP, CV>::value)
+          hipLaunchKernelGGL((k_accumulate<CV, 2, BP>), grid, dim3(256), 0, st, row_ptr, val_idx, bases, buckets, n, work, total, row_ovf_base, ovf, SEG, d_err,
+                             ctx->d_err + 2, ph.into ? 1u : 0u, ph.table_stride, L);
+        else
+          hipLaunchKernelGGL((k_accumulate<CV, 2>), grid, dim3(256), 0, st, row_ptr, val_idx, bases, buckets, n, work, total, row_ovf_base, ovf, SEG, d_err,
+                             ctx->d_err + 2, ph.into ? 1u : 0u, ph.table_stride, L);
+      }
+      HIP_TRY(ctx, hipGetLastError());
+      ctx->acc_seq++;
+      static_assert(CV::HAS_QUAD, "every curve policy has the quad-cooperative addition");
+      // (grid-stride over the split-row list: with the even windows few rows split, and 8192 workgroups that only read the
+      // count cost 11 us at 2^20)
+      hipLaunchKernelGGL(k_merge_split_rows_quad<CV>, dim3(std::min<uint32_t>((rows + 63) / 64, 1024u)), dim3(256), 0, st, row_ptr, buckets, counters, split_rows, row_ovf_base, ovf, SEG, d_err, L,
+                         ctx->dm_out_flag + ACC_FLAG_WORD, ctx->acc_seq);
+      HIP_TRY(ctx, hipGetLastError());
+    }
   }  // ph.front
   if (!ph.back) return MSM377_OK;
   if (ctx->capture) {
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_buckets_snap, buckets, (size_t)wc * CV::BKT_WORDS * NB * 4, hipMemcpyDeviceToDevice, st));
   }
+  const uint32_t wc_out = ph.table ? 1u : wc;  // precomputed-window tables fold the windows on the GPU
+  const uint32_t pp = wide ? WIDE_POINTS : (uint32_t)MSM377_G1_PARTIAL_POINTS;  // points per window record
   {
-    StageTimer t(ctx, MSM377_STAGE_REDUCE, st, part);
-    const uint32_t wc_acc = wc;  // window slots the accumulation filled
-    uint32_t wc = wc_acc;        // window slots left to reduce (shadows the parameter copy on purpose)
+    StageTimer t(ctx, MSM377_STAGE_REDUCE, st);
     if (ph.table) {
-      for (uint32_t half = wc_acc / 2; half >= 1; half /= 2) {  // wc_acc = 16: a power of two
+      for (uint32_t half = wc / 2; half >= 1; half /= 2) {  // wc = 16: a power of two
         hipLaunchKernelGGL(k_fold_windows<CV>, dim3(half * NB / 256), dim3(256), 0, st, buckets, L, half, d_err);
         HIP_TRY(ctx, hipGetLastError());
       }
-      wc = 1;
     }
     const uint32_t levels = L;  // log2 of the buckets per window
-    const uint32_t first_level = 0;
     uint32_t coop_from = 0;
-    for (coop_from = 0; coop_from < levels && 4ull * (coop_from + 1) * (NB >> (coop_from + 1)) * wc > ctx->coop_threads; coop_from++) {
+    for (coop_from = 0; coop_from < levels && 4ull * (coop_from + 1) * (NB >> (coop_from + 1)) * wc_out > ctx->coop_threads; coop_from++) {
       }
     // Levels [0, coop_from): one thread per addition (VALU-bound: 2^18 additions per level at first); [coop_from,
     // tail_from): one lane quad per addition, one launch per level; [tail_from, levels): k_reduce_tail, one launch.
@@ -448,16 +433,16 @@ int enqueue_part(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scalars,
     // per launch; a thread with four serial additions only lengthens that.)
     // More waves do not help either: k_tree_step at 3 / 4 waves per SIMD (132 VGPRs, no scratch) reduces in 0.300 /
     // 0.32 ms against 0.298 at 2; lane quads for levels 0-4 (MSM377_COOP_THREADS up to 2^20 threads) in 0.36.
-    for (uint32_t r = first_level; r < tail_from; r++) {
+    for (uint32_t r = 0; r < tail_from; r++) {
       const uint32_t ops = (r + 1) * (NB >> (r + 1));
       bool done = false;
       if constexpr (CV::HAS_QUAD) {
         if (r >= coop_from) {
-          hipLaunchKernelGGL(k_tree_step_quad<CV>, dim3((4 * ops + 255) / 256, wc), dim3(256), 0, st, buckets, L, r, ops, d_err);
+          hipLaunchKernelGGL(k_tree_step_quad<CV>, dim3((4 * ops + 255) / 256, wc_out), dim3(256), 0, st, buckets, L, r, ops, d_err);
           done = true;
         }
       }
-      if (!done) hipLaunchKernelGGL(k_tree_step<CV>, dim3((ops + 255) / 256, wc), dim3(256), 0, st, buckets, L, r, ops, d_err);
+      if (!done) hipLaunchKernelGGL(k_tree_step<CV>, dim3((ops + 255) / 256, wc_out), dim3(256), 0, st, buckets, L, r, ops, d_err);
       HIP_TRY(ctx, hipGetLastError());
     }
     if constexpr (CV::HAS_QUAD) {
@@ -466,59 +451,22 @@ int enqueue_part(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scalars,
         if (ctx->tail_lds && lds_bytes > 64 * 1024 && lds_bytes <= TAIL_LDS_BYTES_MAX)  // (only with MSM377_TAIL_FROM below its default; per device, so every time)
           HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_reduce_tail_lds<CV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TAIL_LDS_BYTES_MAX));
         if (ctx->tail_lds && lds_bytes <= TAIL_LDS_BYTES_MAX)
-          hipLaunchKernelGGL(k_reduce_tail_lds<CV>, dim3(tail_from + 1, wc), dim3(TAIL_THREADS), lds_bytes, st, buckets, L, tail_from, d_err);
+          hipLaunchKernelGGL(k_reduce_tail_lds<CV>, dim3(tail_from + 1, wc_out), dim3(TAIL_THREADS), lds_bytes, st, buckets, L, tail_from, d_err);
         else
-          hipLaunchKernelGGL(k_reduce_tail<CV>, dim3(tail_from + 1, wc), dim3(TAIL_THREADS), 0, st, buckets, L, tail_from, d_err);
+          hipLaunchKernelGGL(k_reduce_tail<CV>, dim3(tail_from + 1, wc_out), dim3(TAIL_THREADS), 0, st, buckets, L, tail_from, d_err);
         HIP_TRY(ctx, hipGetLastError());
       }
     }
-    const uint32_t pp = wide ? WIDE_POINTS : (uint32_t)MSM377_G1_PARTIAL_POINTS;  // points per window record
-    if (ctx->zc_active)  // set by enqueue_windows for this call: one part, slot 0
-      hipLaunchKernelGGL(k_gather_partials<CV>, dim3((wc * pp * 4 + 63) / 64), dim3(64), 0, st, buckets, d_partials, wc, L, ctx->dm_partials,
+    if (ctx->zc_active)
+      hipLaunchKernelGGL(k_gather_partials<CV>, dim3((wc_out * pp * 4 + 63) / 64), dim3(64), 0, st, buckets, d_partials, wc_out, L, ctx->dm_partials,
                          ctx->dm_out_flag, ctx->d_out_count, (const int*)d_err, ctx->out_seq, pp);
     else
-      hipLaunchKernelGGL(k_gather_partials<CV>, dim3((wc * pp * 4 + 63) / 64), dim3(64), 0, st, buckets,
-                         d_partials + (size_t)pv.ws0 * MSM377_G1_PARTIAL_POINTS * CV::OUT_WORDS, wc, L, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                         (const int*)nullptr, 0u, pp);
+      hipLaunchKernelGGL(k_gather_partials<CV>, dim3((wc_out * pp * 4 + 63) / 64), dim3(64), 0, st, buckets, d_partials, wc_out, L, (uint32_t*)nullptr,
+                         (uint32_t*)nullptr, (uint32_t*)nullptr, (const int*)nullptr, 0u, pp);
     HIP_TRY(ctx, hipGetLastError());
   }
-  return MSM377_OK;
-}
-
-// Enqueue stages decompose .. gather for windows [wb, wb + wc) against ctx->d_bases, the D2H of
-// the partial records into slot `slot` of ctx->h_partials and that slot's completion event.
-// Nothing here waits for the GPU.
-//
-// (Rounds 1 and 2 could run a large call as TWO parts of half the windows on two streams, so that one part's sort and
-// reduction hid under the other's accumulation: 3.19 vs 3.17 ms at 2^20, then 2.72 -> 2.89 on round 2's kernels -- the
-// accumulation kernel owns every VGPR of the chip, kernels of another stream do not become co-resident.  Removed in
-// round 3; PartView keeps the stream and the window slots of a call together.)
-template <class CV, class BP = CV>
-int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scalars, uint32_t wb, uint32_t wc, int slot, bool glv = false,
-                    const Phase& ph = Phase()) {
-  // GLV front end: n_scalars scalars become 2 n_scalars (point, half-scalar) columns over 8 windows.
-  const uint64_t n = glv ? 2 * n_scalars : n_scalars;
-  hipStream_t st = ctx->stream;
-  int* d_err = ctx->d_err + slot;
-  uint32_t* d_partials = ctx->d_partials + (size_t)slot * SLOT_WORDS;
-  // the error word is cleared by the call's first kernel together with its counters -- unless there is no such kernel
-  // (back phase only)
-  const bool clear_here = ph.clear_err && !ph.front;
-  if (clear_here) hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(256), 0, st, (uint32_t*)d_err, 1u, (uint32_t*)nullptr, 0u);
-  Phase part_phase = ph;
-  part_phase.clear_err = ph.clear_err && !clear_here;
-  const PartView pv{st, 0, 0, wb, wc, 0, 0};
-  ctx->zc_active = ph.zc_out && ph.back && ctx->zc_out && slot == 0 && !ph.table;
-  if (ctx->zc_active) ctx->out_seq++;
-  {
-    const int rc = enqueue_part<CV, BP>(ctx, d_scalars, n_scalars, n, pv, d_err, d_partials, glv, MAX_SORT_BLOCKS, part_phase);
-    if (rc) return rc;
-  }
-  if (!ph.back) return MSM377_OK;
-  const uint32_t wc_out = ph.table ? 1u : wc;  // precomputed-window tables fold the windows on the GPU
-  const uint32_t pp_out = ph.wide ? WIDE_POINTS : (uint32_t)MSM377_G1_PARTIAL_POINTS;
   if (!ctx->zc_active) {
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_partials + (size_t)slot * SLOT_WORDS, d_partials, (size_t)wc_out * pp_out * CV::OUT_WORDS * 4,
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_partials + (size_t)slot * SLOT_WORDS, d_partials, (size_t)wc_out * pp * CV::OUT_WORDS * 4,
                                  hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->h_err + slot, d_err, sizeof(int), hipMemcpyDeviceToHost, st));
   }
@@ -566,12 +514,8 @@ int finish_windows(msm377_ctx* ctx, int slot) {
         ctx->stage_ms[s] = 0.0;
         continue;
       }
-      double sum = 0.0;  // a pipelined call reports the sum over its two parts (they overlap each other in wall time)
-      for (uint32_t p = 0; p < 1u; p++) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, ctx->ev[p][s][0], ctx->ev[p][s][1]) == hipSuccess) sum += ms;
-      }
-      ctx->stage_ms[s] = sum;
+      float ms = 0.f;
+      ctx->stage_ms[s] = hipEventElapsedTime(&ms, ctx->ev[s][0], ctx->ev[s][1]) == hipSuccess ? ms : 0.0;
     }
     (void)hipGetLastError();  // a stage that did not run in this call must not leave its error for the next launch check
   }
@@ -595,11 +539,11 @@ inline bool use_glv(const msm377_ctx* ctx, uint64_t) { return ctx->glv_mode == 1
 int convert_bases_g1(msm377_ctx* ctx, const uint32_t* d_raw, uint64_t n, bool glv) {
   if (!glv) return convert_bases<G1Dev>(ctx, d_raw, n);
   if (n == 0) return MSM377_OK;
-  if (ctx->timing == 1) (void)hipEventRecord(ctx->ev[0][MSM377_STAGE_CONVERT][0], ctx->stream2);
+  if (ctx->timing == 1) (void)hipEventRecord(ctx->ev[MSM377_STAGE_CONVERT][0], ctx->stream2);
   hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(256), 0, ctx->stream2, (uint32_t*)(ctx->d_err + 2), 1u, (uint32_t*)nullptr, 0u);
   hipLaunchKernelGGL(k_convert_bases_glv, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream2, d_raw, ctx->d_bases, n);
   HIP_TRY(ctx, hipGetLastError());
-  if (ctx->timing == 1) (void)hipEventRecord(ctx->ev[0][MSM377_STAGE_CONVERT][1], ctx->stream2);
+  if (ctx->timing == 1) (void)hipEventRecord(ctx->ev[MSM377_STAGE_CONVERT][1], ctx->stream2);
   HIP_TRY(ctx, hipEventRecord(ctx->bases_ready, ctx->stream2));
   return MSM377_OK;
 }
@@ -673,7 +617,7 @@ int g1_table_msm(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n, int for
       ph.table = ctx->d_table;
       ph.table_stride = ctx->bases_n;
     }
-    // Small inputs: narrow windows (k_decompose_narrow); the window-indexed buffers are sized for them too
+    // Small inputs: narrow windows (k_decompose_geom); the window-indexed buffers are sized for them too
     // (msm377_ctx_create: wcap).  Stage read-backs describe the 16-bit geometry.
     bool narrow = form != TABLE_TE_PRECOMP && n <= ctx->narrow_max_points && n <= SMALL_SORT_MAX && !ctx->capture;
     bool wide = form == TABLE_TE_PRECOMP && ctx->table_window_bits == WIDE_BITS;
@@ -691,21 +635,15 @@ int g1_table_msm(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n, int for
         windows = 1;
         cbits = WIDE_BITS;
         planes = WIDE_LOG;
-      } else if (narrow && even && ctx->narrow_even) {  // eleven signed 12-bit + eleven unsigned 11-bit windows
+      } else if (narrow) {  // eleven signed 12-bit + eleven unsigned 11-bit windows (whatever MSM377_EVEN_WINDOWS says)
         ph.cbits = NARROW_EVEN_BITS;
         ph.bucket_log = NARROW_LOG;
         windows = NARROW_EVEN_WINDOWS;
         cbits = NARROW_EVEN_BITS;
         planes = NARROW_LOG;
         short_from = NARROW_EVEN_SIGNED;
-      } else if (narrow) {  // 22 signed 11-bit windows + an unsigned top one
-        ph.cbits = NARROW_BITS;
-        ph.bucket_log = NARROW_LOG;
-        windows = NARROW_WINDOWS;
-        cbits = NARROW_BITS;
-        planes = NARROW_LOG;
       }
-      ph.even = even && !wide && !table0 && (!narrow || ctx->narrow_even);
+      ph.even = even && !wide && !table0;
       if (ph.even && !narrow) short_from = EVEN_FROM;
       ph.zc_out = true;
       int rc = form == TABLE_TE ? enqueue_windows<TeDev>(ctx, d_scalars, n, 0, windows, 0, false, ph)
@@ -786,22 +724,10 @@ int resident_table_to_weierstrass(msm377_ctx* ctx) {
 // Host-buffer entry points with large inputs: the upload (3.0-3.6 ms for the 128 MB of a 2^20-point G1 input from
 // pageable memory, box to box) is longer than the whole computation, so the two overlap: the MSM runs as K chunks of
 // points, later chunks accumulate on top of the buckets the earlier ones left (Phase::into), reduction, gather and D2H
-// are queued once, with the last chunk.  Two schedules:
-//
-// run_chunked_upload (DEFAULT): a chunk's scalars AND points go up together and the chunk runs the whole front end --
-// decompose .. accumulate .. merge -- while the next one is on its way.
-//
-// run_sorted_upload (MSM377_UPLOAD_SORT_ONCE=1): all scalars first, ONE decomposition and sort with
-// the rows filed by chunk of the point index (k_local_sort_lds<true>: K sub-row bounds per key, common.hpp RowView), then
-// per chunk of points only its base conversion, a work list over ITS sub-rows, the accumulation and the merge.  Built,
-// parity-green and NOT faster: same box, interleaved (profiles/r03_final/ab_upload.txt) 4.44 / 4.45 / 4.72 ms for the
-// per-chunk front ends against 4.67 / 4.67 / 4.74 sorted once.  The trace (MSM377_UPLOAD_TRACE=1,
-// profiles/r03_final/upload_trace.txt) says why: the call is bound by the GPU, not by the upload -- the chunks'
-// accumulations with projective records cost ~2.7 ms per 2^20 points (0.65 ms per 24 % chunk: short rows, a bucket
-// load and store per item and chunk, work list + merge per chunk) plus reduction and tail, and that work cannot start
-// before the first points are on the device; the per-chunk sorts the new schedule saves (~0.1 ms each) were hidden
-// behind the upload anyway, while its scalars-first head (0.78 ms of upload + 0.18 ms of sort before the first
-// accumulation) is not.
+// are queued once, with the last chunk.  A chunk's scalars AND points go up together and the chunk runs the whole front
+// end -- decompose .. accumulate .. merge -- while the next one is on its way.  (Sorting all scalars once and
+// accumulating each chunk through its own sub-rows was built, passed and measured slower: HISTORY.md, "Sort-once
+// schedule".)
 // The chunks' decompositions use the even window geometry in the Edwards forms (g1_msm / ed_msm hand EVEN_FROM to the
 // tail and rerun in one piece when a scalar does not fit).
 template <class CV>
@@ -856,92 +782,6 @@ int run_chunked_upload(msm377_ctx* ctx, const uint8_t* points, const uint8_t* sc
     ph.even = upload_even<CV>(ctx);
     rc = convert_bases<CV>(ctx, ctx->d_raw_points + first * CV::RAW_WORDS, cnt, first, c == 0);
     if (rc == MSM377_OK) rc = enqueue_windows<CV>(ctx, ctx->d_raw_scalars + first * 8, cnt, 0, MSM377_NUM_WINDOWS, 0, false, ph);
-  }
-  upload.join();
-  if (rc) (void)hipStreamSynchronize(ctx->stream);
-  return rc;
-}
-
-template <class CV>
-int run_sorted_upload(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n) {
-  constexpr size_t PB = CV::RAW_WORDS * 4;  // bytes per wire point
-  // chunk c = points [cut[c], cut[c + 1]): the first one upload_split_pct of n (it should land when the sort is through),
-  // the last one half a share (only ITS accumulation trails the upload), the rest even; multiples of 64 points
-  ChunkCuts cuts;
-  {
-    const uint32_t want = std::min<uint32_t>(ctx->upload_chunks + 1, MAX_UPLOAD_CHUNKS);  // one chunk more than the default schedule: its last one is half a share
-    const uint64_t first_end = std::max<uint64_t>(64, (n * (ctx->upload_split_pct * 5 / 9) / 100) & ~63ull);  // 30 % -> 16 %: the first chunk should land when the sort is through
-    const double rest = (double)(n - std::min(n, first_end)), shares = want > 2 ? (double)(want - 2) + 0.5 : 1.0;
-    uint32_t K = 0;
-    cuts.cut[0] = 0;
-    double at = (double)first_end;
-    for (uint32_t c = 1; c < want; c++) {
-      const uint64_t bnd = c == 1 ? first_end : ((uint64_t)at) & ~63ull;
-      if (bnd > cuts.cut[K] && bnd < n) cuts.cut[++K] = (uint32_t)bnd;  // no empty chunks (small n)
-      at += rest / shares;
-    }
-    cuts.k = K + 1;
-    for (uint32_t j = cuts.k; j <= MAX_UPLOAD_CHUNKS; j++) cuts.cut[j] = (uint32_t)n;
-  }
-  const uint32_t K = cuts.k;
-  if (K > 1 && !ctx->d_row_ptr_chunks) {  // K sub-row bounds per key: allocated the first time a call needs them
-    if (hipMalloc((void**)&ctx->d_row_ptr_chunks, (size_t)MSM377_NUM_WINDOWS * ((size_t)(NB + 1) * MAX_UPLOAD_CHUNKS + 1) * 4) != hipSuccess) {
-      ctx->d_row_ptr_chunks = nullptr;
-      (void)hipGetLastError();
-      ctx->err = "chunked upload: out of device memory for the row bounds";
-      return MSM377_ENOMEM;
-    }
-  }
-  // MSM377_UPLOAD_TRACE=1: host timestamps (us after the call) of the upload and enqueue steps and GPU timestamps of the
-  // phases' ends (HIP events on the main stream), printed by upload_trace_report once the call is through.
-  UploadTrace& tr = ctx->upload_trace;
-  tr.begin(ctx->upload_trace_on, K);
-  int rc = h2d_staged(ctx, ctx->d_raw_scalars, scalars, n * 32, (size_t)ctx->cap * 96);
-  if (rc) return rc;
-  tr.host("scalars up");
-  int up_rc = MSM377_OK;
-  std::atomic<uint32_t> uploaded{0};  // chunks of points on the device so far
-  std::atomic<bool> upload_done{false};
-  std::thread upload([&] {
-    if (hipSetDevice(ctx->device) != hipSuccess) up_rc = MSM377_EHIP;
-    for (uint32_t c = 0; c < K && up_rc == MSM377_OK; c++) {
-      const uint64_t first = cuts.cut[c], cnt = cuts.cut[c + 1] - first;
-      up_rc = h2d_staged(ctx, (uint8_t*)ctx->d_raw_points + first * PB, points + first * PB, cnt * PB, first * PB);
-      tr.chunk_up(c);
-      if (up_rc == MSM377_OK) uploaded.store(c + 1, std::memory_order_release);
-    }
-    upload_done.store(true, std::memory_order_release);
-  });
-  {  // phase 1: decompose + sort, once
-    Phase ph;
-    ph.accumulate = false;
-    ph.back = false;
-    ph.cuts = cuts;
-    ph.even = upload_even<CV>(ctx);
-    tr.gpu(ctx->stream, 0);
-    rc = enqueue_windows<CV>(ctx, ctx->d_raw_scalars, n, 0, MSM377_NUM_WINDOWS, 0, false, ph);
-    tr.gpu(ctx->stream, 1);
-    tr.host("sort enqueued");
-  }
-  for (uint32_t c = 0; c < K && rc == MSM377_OK; c++) {
-    while (uploaded.load(std::memory_order_acquire) <= c && !upload_done.load(std::memory_order_acquire)) std::this_thread::yield();
-    if (uploaded.load(std::memory_order_acquire) <= c) {  // the upload thread stopped on an error
-      rc = up_rc ? up_rc : MSM377_EHIP;
-      break;
-    }
-    const uint64_t first = cuts.cut[c], cnt = cuts.cut[c + 1] - first;
-    Phase ph;
-    ph.clear_err = false;
-    ph.sort = false;
-    ph.into = c > 0;
-    ph.back = c + 1 == K;
-    ph.cuts = cuts;
-    ph.chunk = c;
-    ph.chunk_points = cnt;
-    rc = convert_bases<CV>(ctx, ctx->d_raw_points + first * CV::RAW_WORDS, cnt, first, c == 0);
-    if (rc == MSM377_OK) rc = enqueue_windows<CV>(ctx, ctx->d_raw_scalars, n, 0, MSM377_NUM_WINDOWS, 0, false, ph);
-    tr.gpu(ctx->stream, 2 + c);
-    tr.chunk_enqueued(c);
   }
   upload.join();
   if (rc) (void)hipStreamSynchronize(ctx->stream);
@@ -1041,13 +881,9 @@ int g1_msm(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint6
   int rc;
   if (n >= ctx->upload_chunk_min && form != TABLE_XYZZ_GLV && !ctx->capture) {  // (stage read-backs describe the plain row layout)
     const bool te = form == TABLE_TE;
-    if (ctx->upload_sort_once)
-      rc = te ? run_sorted_upload<TeDev>(ctx, points, scalars, n) : run_sorted_upload<G1Dev>(ctx, points, scalars, n);
-    else
-      rc = te ? run_chunked_upload<TeDev>(ctx, points, scalars, n) : run_chunked_upload<G1Dev>(ctx, points, scalars, n);
+    rc = te ? run_chunked_upload<TeDev>(ctx, points, scalars, n) : run_chunked_upload<G1Dev>(ctx, points, scalars, n);
     if (rc) return rc;
     HIP_TRY(ctx, hipEventSynchronize(ctx->done_ev[0]));
-    ctx->upload_trace.report();
     const bool even = te && upload_even<TeDev>(ctx);
     if (even && (ctx->h_err[0] & ERR_NARROW_RANGE) && !(ctx->h_err[0] & (ERR_SCALAR | ERR_TE_ANY))) {
       // a scalar of 2^253 and more: everything is on the device by now, rerun in one piece (g1_table_msm falls back to
@@ -1149,7 +985,7 @@ int ed_msm(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint6
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (n >= ctx->upload_chunk_min) {  // chunks of points, like g1_msm: a chunk computes while the next one uploads
     ctx->bases_n = 0;
-    int rc = ctx->upload_sort_once ? run_sorted_upload<EdDev>(ctx, points, scalars, n) : run_chunked_upload<EdDev>(ctx, points, scalars, n);
+    int rc = run_chunked_upload<EdDev>(ctx, points, scalars, n);
     if (rc) return rc;
     HIP_TRY(ctx, hipEventSynchronize(ctx->done_ev[0]));
     const bool even = upload_even<EdDev>(ctx);
@@ -1293,8 +1129,8 @@ int g1_msm_fixed_base_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n,
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (ctx->timing == 1) {  // no conversion in this mode
-    (void)hipEventRecord(ctx->ev[0][MSM377_STAGE_CONVERT][0], ctx->stream);
-    (void)hipEventRecord(ctx->ev[0][MSM377_STAGE_CONVERT][1], ctx->stream);
+    (void)hipEventRecord(ctx->ev[MSM377_STAGE_CONVERT][0], ctx->stream);
+    (void)hipEventRecord(ctx->ev[MSM377_STAGE_CONVERT][1], ctx->stream);
   }
   rc = g1_table_msm(ctx, (const uint32_t*)d_scalars, n, resident_form(ctx, n), out_xy);
   if (rc != RC_TE_FALLBACK) return rc;
