@@ -84,7 +84,12 @@ int msm377_ctx_reserve_host_staging(msm377_ctx* ctx);
  * by bench.py ("inputs resident in HBM"). */
 int msm377_g1_msm_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint8_t out_xy[96]);
 
-/* Fixed-base batches (BASELINE.json config 5): convert and keep a base set in HBM once ... */
+/* Fixed-base batches (BASELINE.json config 5): convert and keep a base set in HBM once ...
+ * The resident bases are valid only after a msm377_g1_set_bases* call has returned MSM377_OK, and only until a call
+ * that writes the context's base records, its raw point copy or its table -- any other G1 or Edwards-BLS12 MSM, the
+ * window-partials calls, the next set-bases call.  Every set-bases call drops the resident bases first, before it
+ * checks its arguments, and installs the new ones as its last step: after one that fails for whatever reason the
+ * fixed-base calls return MSM377_ESTATE. */
 int msm377_g1_set_bases(msm377_ctx* ctx, const uint8_t* points, uint64_t n);
 int msm377_g1_set_bases_device(msm377_ctx* ctx, const void* d_points, uint64_t n);
 /* The same with precomputed window multiples (BASELINE.json config 5, "precomputed-point reuse"; the reference lists

@@ -2,7 +2,9 @@
 // -fsanitize=thread when the toolchain has it): many rounds of "post shares to the idle helpers, run the caller's own
 // share, finish the others in order", with helpers that are randomly stalled BEFORE they look at their job -- the
 // failure this mechanism exists for.  Every share must run exactly once per round, whoever runs it; a stalled helper's
-// late look at an old job must touch nothing; no round may wait for a stalled helper that had not started.
+// late look at an old job must touch nothing; no round may wait for a stalled helper that had not started.  First, one
+// case of its own: a caller's wait for a share that a stalled helper is still running times out, and shutdown() must
+// return only after that share has finished (the context frees what such a share touches right after it).
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -15,7 +17,35 @@
 
 using msm377::TailPool;
 
+static int shutdown_waits_for_a_timed_out_share() {
+  TailPool pool;
+  pool.numa_local = false;
+  pool.wait_limit_ns = 1000000;  // 1 ms
+  pool.start();
+  auto shares = std::make_shared<TailPool::Shares>();
+  auto result = std::make_shared<int>(0);  // plain memory: only the join in shutdown() orders its write before the read
+  std::atomic<bool> entered{false};
+  pool.post_share(0, shares, 0, [result, &entered] {
+    entered.store(true);
+    std::this_thread::sleep_for(std::chrono::milliseconds(50));  // stalled inside the share it has claimed
+    *result = 42;
+  });
+  while (!entered.load()) std::this_thread::yield();
+  if (pool.finish_share(shares, 0, [] {})) {
+    printf("FAIL: finish_share did not time out on a share that runs for 50 ms\n");
+    return 1;
+  }
+  pool.shutdown();
+  if (*result != 42 || shares->state[0].load() != 2) {
+    printf("FAIL: shutdown() returned before the running share had finished\n");
+    return 1;
+  }
+  pool.shutdown();  // idempotent (the destructor calls it once more)
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (shutdown_waits_for_a_timed_out_share()) return 1;
   const int rounds = argc > 1 ? atoi(argv[1]) : 20000;
   const int stall_every = argc > 2 ? atoi(argv[2]) : 97;  // one posted job in this many sleeps 2 ms before its claim
   TailPool pool;

@@ -631,6 +631,56 @@ def test_fixed_base_with_precomputed_window_multiples(engine, oracle, window_bit
     assert e.value.code == -1
 
 
+@pytest.mark.parametrize("kind", ["set_bases", "precomputed16", "precomputed20"])
+def test_failed_set_bases_leaves_no_resident_table(oracle, kind):
+    """A set-bases call that fails for any reason -- here on its arguments, with the table lent to the twin context by a
+    batch just before -- leaves no resident bases (include/msm377.h): the fixed-base calls answer MSM377_ESTATE
+    instead of reading the old table, and the next successful set-bases call of another kind and size is exact again."""
+    n, n2 = 3000, 2000
+    pts, _ = seeded_inputs(oracle, n, 61)
+    sets = [R.encode_scalars(R.rand_scalars(610 + b, n)) for b in range(4)]
+    want = [util.oracle_msm(oracle, pts, k) for k in sets]
+    d_s, d_p = dev(b"".join(sets)), dev(pts)
+    with msm.MsmEngine(1 << 12) as eng:  # n > capacity is cheap to ask for, and so is the twin
+
+        def build(kind, points):
+            if kind == "set_bases":
+                eng.set_bases(points)
+            else:
+                eng.set_precompute_window(16 if kind == "precomputed16" else 20)
+                eng.set_bases_precomputed(points)
+
+        over = eng.max_points + 1
+        failing = {
+            "host, n > capacity": lambda: eng.set_bases(pts[:96] * over),
+            "host precomputed, n > capacity": lambda: eng.set_bases_precomputed(pts[:96] * over),
+            "device, misaligned": lambda: eng.set_bases_device(d_p.data_ptr() + 4, n),
+            "device, n > capacity": lambda: eng.set_bases_device(d_p.data_ptr(), over),
+            "device precomputed, misaligned": lambda: eng.set_bases_precomputed_device(d_p.data_ptr() + 4, n),
+            "device precomputed, n > capacity": lambda: eng.set_bases_precomputed_device(d_p.data_ptr(), over),
+        }
+        for name, fail in failing.items():
+            build(kind, pts)
+            assert eng.msm_fixed_base_batch_device(d_s.data_ptr(), n, 4) == want, name  # the twin has borrowed the table
+            with pytest.raises(msm.MsmError) as e:
+                fail()
+            assert e.value.code == -1, name
+            with pytest.raises(msm.MsmError) as e:
+                eng.msm_fixed_base(sets[0][: 32 * 100])
+            assert e.value.code == -5, name
+            with pytest.raises(msm.MsmError) as e:
+                eng.msm_fixed_base_batch_device(d_s.data_ptr(), n, 4)
+            assert e.value.code == -5, name
+        other = {"set_bases": "precomputed20", "precomputed16": "set_bases", "precomputed20": "precomputed16"}[kind]
+        pts2 = pts[: 96 * n2]
+        build(other, pts2)
+        sets2 = [k[: 32 * n2] for k in sets]
+        want2 = [util.oracle_msm(oracle, pts2, k) for k in sets2]
+        assert eng.msm_fixed_base(sets2[0]) == want2[0]
+        d_s2 = dev(b"".join(sets2))
+        assert eng.msm_fixed_base_batch_device(d_s2.data_ptr(), n2, 4) == want2
+
+
 def test_wide_windows_on_skewed_and_larger_inputs(engine, oracle):
     """The 20-bit-window table at a size where both partition passes of its sort run over several tiles, and with
     heavily repeated scalars (rows far longer than a work item, merged from their overflow records; sort regions

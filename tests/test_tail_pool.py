@@ -1,7 +1,8 @@
 """csrc/tail_pool.hpp, host-only: the claimed shares that keep a call from waiting for a helper thread which has lost its
 CPU.  tests/native/tail_pool_stress.cpp posts shares to the idle helpers, stalls some of them for 2 ms BEFORE they look at
-their job, and checks that every share runs exactly once, that no round waits for such a helper, and (with
--fsanitize=thread, when the toolchain links it) that the hand-over has no data race.  CPU only."""
+their job, and checks that every share runs exactly once, that no round waits for such a helper, that shutdown() returns
+only after a share whose wait timed out has finished, and (with -fsanitize=thread, when the toolchain links it) that the
+hand-over has no data race.  CPU only."""
 import os
 import platform
 import shutil

@@ -145,19 +145,20 @@ int msm377_ctx_create(int device, uint64_t max_points, msm377_ctx** out) {
 
 void msm377_ctx_destroy(msm377_ctx* ctx) {
   if (!ctx) return;
+  ctx->tail_pool.shutdown();  // first: a share left running by a timed-out tail wait may still use the buffers below
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
-  if (ctx->twin) {  // it owns everything but the table it borrows during a batch call
-    ctx->twin->d_bases = nullptr;
-    ctx->twin->d_table = nullptr;
+  if (ctx->twin) {  // it owns everything but the resident bases it borrows during a batch call
+    eng::twin_return(ctx);
     msm377_ctx_destroy(ctx->twin);
     ctx->twin = nullptr;
   }
   void* bufs[] = {ctx->d_raw_points, ctx->d_raw_scalars, ctx->d_bases, ctx->d_digits, ctx->d_range_counts, ctx->d_region_base, ctx->d_sort_temp,
-                  ctx->d_row_ptr, ctx->d_val_idx, ctx->d_buckets, ctx->d_buckets_snap, ctx->d_partials, ctx->d_work, ctx->d_work_meta, ctx->d_row_ovf_base, ctx->d_split_rows, ctx->d_ovf, ctx->d_err, ctx->d_aff_stash, ctx->d_aff_trees, ctx->d_aff_count, ctx->d_out_count, ctx->d_table, ctx->d_wide_digits, ctx->d_wide_counts, ctx->d_wide_temp};
+                  ctx->d_row_ptr, ctx->d_val_idx, ctx->d_buckets, ctx->d_buckets_snap, ctx->d_partials, ctx->d_work, ctx->d_work_meta, ctx->d_row_ovf_base, ctx->d_split_rows, ctx->d_ovf, ctx->d_err, ctx->d_aff_stash, ctx->d_aff_trees, ctx->d_aff_count, ctx->d_out_count, ctx->resident.table};
   for (void* p : bufs)
     if (p) (void)hipFree(p);
+  ctx->wide.release();
   if (ctx->h_partials) (void)hipHostFree(ctx->h_partials);
   if (ctx->h_err) (void)hipHostFree(ctx->h_err);
   if (ctx->h_out_flag) (void)hipHostFree(ctx->h_out_flag);

@@ -18,6 +18,36 @@ using msm377::Fp64;
 using msm377::MAX_WINDOW_SLOTS;
 using msm377::NARROW_SEG;
 
+// The resident base table of the fixed-base entry points.  Valid only from the successful end of a msm377_g1_set_bases*
+// call until a call writes d_bases, d_raw_points or the table: every writer clear()s it first and a successful build
+// sets it as its last step.  The twin of a context borrows the whole value for the length of a batch call.
+struct ResidentBases {
+  uint64_t n = 0;              // resident base count (0: none)
+  int form = 0;                // TableForm (sequencer.hip) of the records
+  uint32_t* bases = nullptr;   // the base records: the owner's d_bases
+  // The precomputed-window table: `windows` x cap affine records, [2^(c w)] P_i at record w * n + i.  The allocation
+  // outlives clear(); free_table (sequencer.hip) gives it back.
+  uint32_t* table = nullptr;
+  uint64_t cap = 0;
+  uint32_t windows = 0;        // 16 (c = 16), or WIDE_WINDOWS (c = 20: six 20-bit + seven 19-bit windows)
+  bool valid() const { return n != 0; }
+  void clear() { n = 0; }
+  void set(uint32_t* records, uint64_t count, int table_form) { bases = records; n = count; form = table_form; }
+};
+
+// Work buffers of the 20-bit-window sort (kernels/wide.hpp) for up to `cap` points.
+struct WideBuffers {
+  uint32_t* digits = nullptr;  // 13 x n u32 biased 20-bit digits, the flat list the sort reads
+  SortElem* temp = nullptr;    // output of the second partition pass (the first one writes d_sort_temp)
+  uint32_t* counts = nullptr;  // the sort's counters and offsets (kernels/wide.hpp WC_*)
+  uint64_t cap = 0;
+  bool ensure(uint64_t n);     // sequencer.hip; false: out of device memory (nothing allocated)
+  void release() {
+    for (void* p : {(void*)digits, (void*)temp, (void*)counts}) (void)hipFree(p);  // (no-op on nullptr)
+    *this = WideBuffers();
+  }
+};
+
 struct msm377_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -43,13 +73,9 @@ struct msm377_ctx {
   uint32_t* d_row_ovf_base = nullptr; // 16 x NB
   uint32_t* d_split_rows = nullptr;   // 16 x NB
   uint32_t* d_ovf = nullptr;          // overflow partial points, 52 words each (<= 16 cap / SEG)
-  uint32_t* d_table = nullptr;        // precomputed-window table: 16 x table_cap affine records, [2^(16 w)] P_i at record w * bases_n + i
-  uint64_t table_cap = 0;
-  uint32_t table_windows = 0;         // windows the allocated table holds (16, or WIDE_WINDOWS)
+  ResidentBases resident;             // fixed-base mode: the bases of the last successful msm377_g1_set_bases* call
+  WideBuffers wide;                   // the 20-bit-window sort's buffers (allocated with such a table; the twin's own set)
   int precomp_bits = MSM377_WINDOW_BITS;  // window width msm377_g1_set_bases_precomputed builds its next table for: 16 or 20 (msm377_ctx_set_precompute_window, MSM377_PRECOMP_BITS)
-  uint32_t* d_wide_digits = nullptr;  // wide windows: 13 x n u32 biased 20-bit digits, the flat list the sort reads
-  SortElem* d_wide_temp = nullptr;    // wide windows: output of the second partition pass (the first one writes d_sort_temp)
-  uint32_t* d_wide_counts = nullptr;  // wide windows: the sort's counters and offsets (kernels/wide.hpp WC_*)
   uint32_t* d_aff_stash = nullptr;    // cap x 52 words: N1, N2, Z, running product per point (k_affine_up -> k_affine_down)
   uint32_t* d_aff_trees = nullptr;    // one product tree (2 x 256 nodes x 13 words) per AFF_BLOCK_POINTS points
   uint32_t* h_aff_prod = nullptr;     // pinned + coherent host memory the kernels access in place (dm_* = its device address)
@@ -58,8 +84,6 @@ struct msm377_ctx {
   uint32_t *dm_aff_prod = nullptr, *dm_aff_inv = nullptr, *dm_aff_flag = nullptr;
   uint32_t* d_aff_count = nullptr;    // workgroups of k_affine_up that have delivered (device memory; the last one resets it)
   hipEvent_t aff_up_done = nullptr;
-  uint32_t table_window_bits = MSM377_WINDOW_BITS;  // window width of the resident precomputed table: 16, or WIDE_BITS (six 20-bit + seven 19-bit windows)
-  uint32_t table_doublings = MSM377_WINDOW_BITS;    // doublings from the previous window's multiple to the one being built (AffDoublingSource)
   std::vector<Fp64::El> aff_scratch;  // prefix products of the host's share of Montgomery's trick
   bool te_affine_msm = true;          // MSM377_TE_AFFINE_MSM=0: msm377_g1_msm_device keeps projective records (A/B knob)
   // Below this the batched conversion does not pay: it costs ~9 more products per point than the projective record and
@@ -76,7 +100,6 @@ struct msm377_ctx {
   uint8_t* h_stage = nullptr;  // cap x 128 bytes
   hipStream_t copy_stream[8] = {};
   // state
-  uint64_t bases_n = 0;  // resident base count (fixed-base mode)
   uint64_t last_n = 0;
   uint32_t last_wc = 0;
   int last_form = -1;  // MSM377_STAGE_FORM_* of the buckets the last call left (stage read-backs)
@@ -108,7 +131,6 @@ struct msm377_ctx {
   // Interleaved A/B on one MI355X (tools/ab_knobs.py), Weierstrass plain vs GLV ms per MSM: 2^18 1.39 / 1.24,
   // 2^19 2.08 / 2.00, 2^20 3.56 / 3.51, 2^22 12.56 / 12.39 (halved bucket reduction and host tail).
   int glv_mode = 0;
-  int bases_form = 0;      // TableForm of the resident base table (fixed-base mode)
   int g1_form = 1;         // G1 full-MSM entry points: 1 = twisted Edwards form (te377.hpp, default), 0 = Weierstrass XYZZ (MSM377_G1_FORM)
   bool last_glv = false;
   uint32_t seg_plain = 0, seg_glv = 0;  // MSM377_SEG_PLAIN / MSM377_SEG_GLV: force the work-item length (SEG_MIN..SEG_MAX), 0 = auto_seg()
@@ -144,10 +166,9 @@ struct msm377_ctx {
   bool even_windows = true;     // MSM377_EVEN_WINDOWS=0: sixteen 16-bit windows on the 16-window paths (kernels/decompose.hpp k_decompose); the narrow path keeps its geometry
   bool ed_equal_windows_once = false;  // ed_msm -> ed_msm_device: this call reruns a chunked upload whose scalars did not fit
   uint32_t acc_seq = 0;  // calls' accumulation kernels so far; h_out_flag[ACC_FLAG_WORD] follows it (k_merge_split_rows_quad)
-  msm377_ctx* twin = nullptr;   // owned; borrows d_bases / d_table for the length of a batch call
+  msm377_ctx* twin = nullptr;   // owned; borrows `resident` for the length of a batch call
   bool twin_batches = true;     // MSM377_TWIN_BATCH=0: batches run on this context alone
   bool twin_failed = false;
-  uint64_t wide_cap = 0;        // points the twin's wide-window buffers hold
   uint64_t fallback_count = 0;  // reruns on the Weierstrass path after an exceptional case of the Edwards law
   uint32_t fallback_mask = 0;   // MSM377_FB_* bits of the last one
 };

@@ -43,6 +43,20 @@
 #include "kernels/sort.hpp"
 #include "kernels/wide.hpp"
 
+bool WideBuffers::ensure(uint64_t n) {
+  using namespace msm377;
+  if (cap >= n) return true;
+  release();
+  if (hipMalloc((void**)&digits, (size_t)WIDE_WINDOWS * n * 4) == hipSuccess && hipMalloc((void**)&temp, (size_t)WIDE_WINDOWS * n * sizeof(SortElem)) == hipSuccess &&
+      hipMalloc((void**)&counts, WC_WORDS * 4) == hipSuccess) {
+    cap = n;
+    return true;
+  }
+  release();
+  (void)hipGetLastError();
+  return false;
+}
+
 namespace msm377 {
 namespace eng {
 
@@ -68,19 +82,37 @@ void note_fallback(msm377_ctx* ctx, uint32_t mask) {
 // into it and queue the DMA of each piece on their own stream, so the CPU copy of one piece
 // overlaps the DMA of the others.  Measured on the MI355X box for 160 MB: 4.2 ms, against 28 ms
 // for a first hipMemcpy from fresh pageable pages (4.4 ms once the runtime has pinned them) and
-// 3.3 + 2.9 ms for hipHostRegister + copy.  Returns when the data is on the device.
-int h2d_staged(msm377_ctx* ctx, void* d_dst, const uint8_t* src, size_t bytes, size_t stage_off) {
+// 3.3 + 2.9 ms for hipHostRegister + copy.  Returns when the data is on the device.  An upload thread passes `fail`: a
+// HIP error and the call that failed go there, and the thread that joins it records them (only that one writes ctx->err).
+struct HipFail {
+  hipError_t e = hipSuccess;
+  const char* what = "";
+  int record(msm377_ctx* ctx, int rc) const {  // (no-op when nothing failed)
+    hip_ok(ctx, e, what);
+    return rc;
+  }
+};
+int h2d_staged(msm377_ctx* ctx, void* d_dst, const uint8_t* src, size_t bytes, size_t stage_off, HipFail* fail = nullptr) {
   using msm377::eng::reserve_host_staging;
+#define H2D_TRY(call)                \
+  do {                               \
+    const hipError_t e_ = (call);    \
+    if (e_ != hipSuccess) {          \
+      if (fail) *fail = {e_, #call}; \
+      else hip_ok(ctx, e_, #call);   \
+      return MSM377_EHIP;            \
+    }                                \
+  } while (0)
   constexpr int NT_MAX = 8;
   constexpr int NT = 4;  // copy workers: 2, 4, 6 or 8 all moved 128 MB in 2.9-3.0 ms (round 2) -- the DMA sets the pace
   constexpr size_t SMALL = 8u << 20, PIECE = 4u << 20;
   if (bytes < SMALL) {  // not worth four threads
-    HIP_TRY(ctx, hipMemcpy(d_dst, src, bytes, hipMemcpyHostToDevice));
+    H2D_TRY(hipMemcpy(d_dst, src, bytes, hipMemcpyHostToDevice));
     return MSM377_OK;
   }
   if (!ctx->h_stage && reserve_host_staging(ctx) != MSM377_OK) {
     (void)hipGetLastError();
-    HIP_TRY(ctx, hipMemcpy(d_dst, src, bytes, hipMemcpyHostToDevice));  // fall back to the runtime's pageable path
+    H2D_TRY(hipMemcpy(d_dst, src, bytes, hipMemcpyHostToDevice));  // fall back to the runtime's pageable path
     return MSM377_OK;
   }
   // Pieces of about 4 MB, their number a multiple of the worker count (with fixed 8 MB pieces a 48 MB upload took as
@@ -112,8 +144,9 @@ int h2d_staged(msm377_ctx* ctx, void* d_dst, const uint8_t* src, size_t bytes, s
   for (int t = 0; t < NT; t++) workers[t] = std::thread([&copy_pieces, t] { copy_pieces(t); });
   copy_pieces(NT);  // the caller takes pieces too (its own stream)
   for (int t = 0; t < NT; t++) workers[t].join();
-  for (int t = 0; t <= NT; t++) HIP_TRY(ctx, errs[t]);
+  for (int t = 0; t <= NT; t++) H2D_TRY(errs[t]);
   return MSM377_OK;
+#undef H2D_TRY
 }
 
 void identity_wire(uint8_t out[96]) {
@@ -158,14 +191,16 @@ int convert_bases(msm377_ctx* ctx, const uint32_t* d_raw, uint64_t n, uint64_t f
 // first half's products while the second half is still on its way up and the ~50 us round trip idles nothing: slower,
 // 2.60 -> 2.72 ms at 2^20.  The conversion is latency-bound at two workgroups per CU -- a half-size launch is one
 // workgroup per CU and takes 104 us where the full one takes 171 -- so the chain grew from 171 + 50 + 170 to 4 x ~110 us.)
-int affine_convert_begin(msm377_ctx* ctx, const uint32_t* d_raw, uint64_t n, const uint32_t* prev_window_records = nullptr, bool clear_err = true) {
+// prev_window_records: build a window of a precomputed table instead, `doublings` doublings above the previous one's.
+int affine_convert_begin(msm377_ctx* ctx, const uint32_t* d_raw, uint64_t n, const uint32_t* prev_window_records = nullptr, uint32_t doublings = 0,
+                         bool clear_err = true) {
   if (n == 0) return MSM377_OK;
   const uint32_t nblk = affine_blocks(n);
   if (ctx->timing == 1) (void)hipEventRecord(ctx->ev[MSM377_STAGE_CONVERT][0], ctx->stream2);
   __atomic_store_n(ctx->h_aff_flag, 0u, __ATOMIC_RELEASE);
   if (clear_err) hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(256), 0, ctx->stream2, (uint32_t*)(ctx->d_err + 2), 1u, (uint32_t*)nullptr, 0u);
   if (prev_window_records)
-    hipLaunchKernelGGL(k_affine_up<AffDoublingSource>, dim3(nblk), dim3(AFF_THREADS), 0, ctx->stream2, AffDoublingSource{prev_window_records, ctx->table_doublings}, n,
+    hipLaunchKernelGGL(k_affine_up<AffDoublingSource>, dim3(nblk), dim3(AFF_THREADS), 0, ctx->stream2, AffDoublingSource{prev_window_records, doublings}, n,
                        ctx->d_aff_stash, ctx->d_aff_trees, ctx->dm_aff_prod, ctx->dm_aff_flag, ctx->d_aff_count, ctx->d_err + 2, ctx->conv_wave_prio);
   else
     hipLaunchKernelGGL(k_affine_up<AffWireSource>, dim3(nblk), dim3(AFF_THREADS), 0, ctx->stream2, AffWireSource{d_raw}, n, ctx->d_aff_stash, ctx->d_aff_trees,
@@ -294,7 +329,8 @@ int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scala
   uint32_t* split_rows = ctx->d_split_rows;
   WorkItem* work = ctx->d_work;
   uint32_t* ovf = ctx->d_ovf;
-  const uint32_t* bases = ph.table ? ph.table : ph.bases_override ? ph.bases_override : ctx->d_bases + ph.base_first * BP::REC_WORDS;
+  const uint32_t* records = ctx->resident.valid() ? ctx->resident.bases : ctx->d_bases;  // (a twin's resident bases are lent)
+  const uint32_t* bases = ph.table ? ph.table : ph.bases_override ? ph.bases_override : records + ph.base_first * BP::REC_WORDS;
   uint32_t* meta_block = ctx->d_work_meta;  // [work-list counters | key_max[16]]
   uint32_t* key_max = meta_block + (2 * SEG_BINS + 4);
   if (ph.front) {
@@ -313,7 +349,7 @@ int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scala
     {
       StageTimer t(ctx, MSM377_STAGE_DECOMPOSE, st);
       if (wide)
-        hipLaunchKernelGGL(k_decompose_wide, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, ctx->d_wide_digits, n, d_err);
+        hipLaunchKernelGGL(k_decompose_wide, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, ctx->wide.digits, n, d_err);
       else if (narrow)
         hipLaunchKernelGGL(k_decompose_geom, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, digits, n, L, NARROW_EVEN_SIGNED, wc, 1u << L, d_err);
       else if (glv)
@@ -325,14 +361,14 @@ int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scala
 
     if (wide) {  // the 13 n entries into 4096 fine ranges: two staged partition passes per window (kernels/wide.hpp), then k_local_sort_lds
       StageTimer t(ctx, MSM377_STAGE_SORT, st);
-      uint32_t* wc = ctx->d_wide_counts;
-      hipLaunchKernelGGL(k_wide_count, dim3(WS_CHUNKS, WIDE_WINDOWS), dim3(1024), 0, st, (const uint32_t*)ctx->d_wide_digits, wc, n);
+      uint32_t* wc = ctx->wide.counts;
+      hipLaunchKernelGGL(k_wide_count, dim3(WS_CHUNKS, WIDE_WINDOWS), dim3(1024), 0, st, (const uint32_t*)ctx->wide.digits, wc, n);
       hipLaunchKernelGGL(k_wide_sums, dim3(WIDE_NRANGE / 256, WIDE_WINDOWS), dim3(256), 0, st, wc);
       hipLaunchKernelGGL(k_wide_scan, dim3(1), dim3(1024), 0, st, wc, region_base);
       hipLaunchKernelGGL(k_wide_offsets1, dim3(WIDE_WINDOWS), dim3(WS_COARSE), 0, st, wc, n);
-      hipLaunchKernelGGL(k_wide_part1, dim3(WS_CHUNKS, WIDE_WINDOWS), dim3(1024), 0, st, (const uint32_t*)ctx->d_wide_digits, (const uint32_t*)wc, sort_temp, n, (uint32_t)ph.table_stride);
-      hipLaunchKernelGGL(k_wide_part2, dim3(WS_COARSE, WIDE_WINDOWS), dim3(1024), 0, st, (const SortElem*)sort_temp, (const uint32_t*)wc, ctx->d_wide_temp);
-      hipLaunchKernelGGL(k_local_sort_lds, dim3(WIDE_NRANGE, 1), dim3(256), 0, st, (const SortElem*)ctx->d_wide_temp, region_base, row_ptr, val_idx, entries,
+      hipLaunchKernelGGL(k_wide_part1, dim3(WS_CHUNKS, WIDE_WINDOWS), dim3(1024), 0, st, (const uint32_t*)ctx->wide.digits, (const uint32_t*)wc, sort_temp, n, (uint32_t)ph.table_stride);
+      hipLaunchKernelGGL(k_wide_part2, dim3(WS_COARSE, WIDE_WINDOWS), dim3(1024), 0, st, (const SortElem*)sort_temp, (const uint32_t*)wc, ctx->wide.temp);
+      hipLaunchKernelGGL(k_local_sort_lds, dim3(WIDE_NRANGE, 1), dim3(256), 0, st, (const SortElem*)ctx->wide.temp, region_base, row_ptr, val_idx, entries,
                          (const uint32_t*)nullptr, WIDE_NRANGE, NB);
       HIP_TRY(ctx, hipGetLastError());
     } else if (narrow) {
@@ -555,8 +591,10 @@ constexpr int RC_TE_FALLBACK = 1;  // internal: an exceptional case of the twist
 
 // A prefix of a GLV table (records 0..n-1 = the plain points) serves the plain path; the phi half needs all of it.
 inline int resident_form(const msm377_ctx* ctx, uint64_t n) {
-  return (ctx->bases_form == TABLE_XYZZ_GLV && n != ctx->bases_n) ? TABLE_XYZZ : ctx->bases_form;
+  return (ctx->resident.form == TABLE_XYZZ_GLV && n != ctx->resident.n) ? TABLE_XYZZ : ctx->resident.form;
 }
+// The resident table is the 20-bit-window one: 13 windows over one set of 2^19 buckets.
+inline bool wide_table(const ResidentBases& r) { return r.form == TABLE_TE_PRECOMP && r.windows == WIDE_WINDOWS; }
 inline int weierstrass_form(const msm377_ctx* ctx, uint64_t n) { return use_glv(ctx, n) ? TABLE_XYZZ_GLV : TABLE_XYZZ; }
 inline int pick_form(const msm377_ctx* ctx, uint64_t n) { return ctx->g1_form == 1 ? TABLE_TE : weierstrass_form(ctx, n); }
 
@@ -614,13 +652,13 @@ int g1_table_msm(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n, int for
   if (form_is_te(form)) {
     Phase ph;
     if (form == TABLE_TE_PRECOMP) {
-      ph.table = ctx->d_table;
-      ph.table_stride = ctx->bases_n;
+      ph.table = ctx->resident.table;
+      ph.table_stride = ctx->resident.n;
     }
     // Small inputs: narrow windows (k_decompose_geom); the window-indexed buffers are sized for them too
     // (msm377_ctx_create: wcap).  Stage read-backs describe the 16-bit geometry.
     bool narrow = form != TABLE_TE_PRECOMP && n <= ctx->narrow_max_points && n <= SMALL_SORT_MAX && !ctx->capture;
-    bool wide = form == TABLE_TE_PRECOMP && ctx->table_window_bits == WIDE_BITS;
+    bool wide = form == TABLE_TE_PRECOMP && wide_table(ctx->resident);
     bool table0 = false;  // the 16-window path over window 0 of the wide table (= the affine records of the points themselves)
     bool even = ctx->even_windows && form != TABLE_TE_PRECOMP && !ctx->capture;  // (stage read-backs describe sixteen equal windows)
     for (;;) {
@@ -671,7 +709,7 @@ int g1_table_msm(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n, int for
         ph.wide = false;
         ph.table = nullptr;
         ph.table_stride = 0;  // every window slot gathers from the same records
-        ph.bases_override = ctx->d_table;
+        ph.bases_override = ctx->resident.table;
         continue;
       }
       if (ctx->h_err[0] & ERR_TE_ANY) {
@@ -711,13 +749,15 @@ int g1_table_msm(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n, int for
 }
 
 // The resident table hit an exceptional case of the Edwards law: rebuild it in Weierstrass form from the raw
-// copy kept by msm377_g1_set_bases_device.
+// copy kept by msm377_g1_set_bases_device.  Nothing is resident if that fails.
 int resident_table_to_weierstrass(msm377_ctx* ctx) {
   const int form = TABLE_XYZZ;  // points outside the prime-order subgroup: never the GLV front end
-  int rc = convert_table(ctx, ctx->d_raw_points, ctx->bases_n, form);
+  const uint64_t n = ctx->resident.n;
+  ctx->resident.clear();
+  int rc = convert_table(ctx, ctx->d_raw_points, n, form);
   if (rc) return rc;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream2));
-  ctx->bases_form = form;
+  ctx->resident.set(ctx->d_bases, n, form);
   return MSM377_OK;
 }
 
@@ -748,21 +788,22 @@ int run_chunked_upload(msm377_ctx* ctx, const uint8_t* points, const uint8_t* sc
   }
   cut[++K] = n;
   const size_t sc_stage = (size_t)ctx->cap * 96;
-  auto upload_chunk = [&](uint32_t c) -> int {
+  auto upload_chunk = [&](uint32_t c, HipFail* fail) -> int {
     const uint64_t first = cut[c], cnt = cut[c + 1] - cut[c];
-    int r = h2d_staged(ctx, (uint8_t*)ctx->d_raw_scalars + first * 32, scalars + first * 32, cnt * 32, sc_stage + first * 32);
-    if (r == MSM377_OK) r = h2d_staged(ctx, (uint8_t*)ctx->d_raw_points + first * PB, points + first * PB, cnt * PB, first * PB);
+    int r = h2d_staged(ctx, (uint8_t*)ctx->d_raw_scalars + first * 32, scalars + first * 32, cnt * 32, sc_stage + first * 32, fail);
+    if (r == MSM377_OK) r = h2d_staged(ctx, (uint8_t*)ctx->d_raw_points + first * PB, points + first * PB, cnt * PB, first * PB, fail);
     return r;
   };
-  int rc = upload_chunk(0);
+  int rc = upload_chunk(0, nullptr);
   if (rc) return rc;
   int up_rc = MSM377_OK;
+  HipFail up_fail;
   std::atomic<uint32_t> uploaded{1};  // chunks on the device so far
   std::atomic<bool> upload_done{false};
   std::thread upload([&] {
     if (hipSetDevice(ctx->device) != hipSuccess) up_rc = MSM377_EHIP;
     for (uint32_t c = 1; c < K && up_rc == MSM377_OK; c++) {
-      up_rc = upload_chunk(c);
+      up_rc = upload_chunk(c, &up_fail);
       if (up_rc == MSM377_OK) uploaded.store(c + 1, std::memory_order_release);
     }
     upload_done.store(true, std::memory_order_release);
@@ -770,7 +811,7 @@ int run_chunked_upload(msm377_ctx* ctx, const uint8_t* points, const uint8_t* sc
   for (uint32_t c = 0; c < K && rc == MSM377_OK; c++) {
     while (uploaded.load(std::memory_order_acquire) <= c && !upload_done.load(std::memory_order_acquire)) std::this_thread::yield();
     if (uploaded.load(std::memory_order_acquire) <= c) {  // the upload thread stopped on an error
-      rc = up_rc ? up_rc : MSM377_EHIP;
+      rc = up_fail.record(ctx, up_rc ? up_rc : MSM377_EHIP);
       break;
     }
     const uint64_t first = cut[c], cnt = cut[c + 1] - cut[c];
@@ -838,7 +879,7 @@ int g1_msm_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, 
     return MSM377_OK;
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  ctx->bases_n = 0;
+  ctx->resident.clear();
   int form = pick_form(ctx, n);
   // (Queueing the conversion after k_decompose instead was measured: decompose 77 -> 23 us, sort 272 -> 386 us.)
   if (form == TABLE_TE && ctx->te_affine_msm && n >= ctx->affine_min_points) {
@@ -874,7 +915,7 @@ int g1_msm(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint6
     return MSM377_OK;
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  ctx->bases_n = 0;
+  ctx->resident.clear();
   int form = pick_form(ctx, n);
   const uint32_t* d_sc = ctx->d_raw_scalars;
   const uint32_t* d_pt = ctx->d_raw_points;
@@ -911,12 +952,13 @@ int g1_msm(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint6
     rc = h2d_staged(ctx, ctx->d_raw_scalars, scalars, n * 32, (size_t)ctx->cap * 96);
     if (rc) return rc;
     int up_rc = MSM377_OK;
+    HipFail up_fail;
     std::thread upload([&] {
-      up_rc = hipSetDevice(ctx->device) == hipSuccess ? h2d_staged(ctx, ctx->d_raw_points, points, n * 96, 0) : MSM377_EHIP;
+      up_rc = hipSetDevice(ctx->device) == hipSuccess ? h2d_staged(ctx, ctx->d_raw_points, points, n * 96, 0, &up_fail) : MSM377_EHIP;
     });
     ctx->before_accumulate = [&]() -> int {
       if (upload.joinable()) upload.join();
-      if (up_rc) return up_rc;
+      if (up_rc) return up_fail.record(ctx, up_rc);
       return convert_table(ctx, d_pt, n, form);
     };
     rc = g1_table_msm(ctx, d_sc, n, form, out_xy);
@@ -941,7 +983,7 @@ int ed_msm_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, 
     return MSM377_OK;
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  ctx->bases_n = 0;
+  ctx->resident.clear();
   rc = convert_bases<EdDev>(ctx, (const uint32_t*)d_points, n);
   if (rc) return rc;
   TailArm arm(ctx);
@@ -983,8 +1025,8 @@ int ed_msm(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint6
   }
   if (n == 0) return ed_msm_device(ctx, nullptr, nullptr, 0, out_xy);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->resident.clear();  // (both paths upload into d_raw_points)
   if (n >= ctx->upload_chunk_min) {  // chunks of points, like g1_msm: a chunk computes while the next one uploads
-    ctx->bases_n = 0;
     int rc = run_chunked_upload<EdDev>(ctx, points, scalars, n);
     if (rc) return rc;
     HIP_TRY(ctx, hipEventSynchronize(ctx->done_ev[0]));
@@ -1016,19 +1058,21 @@ int ed_generate_bases_device(msm377_ctx* ctx, uint64_t seed, uint64_t n, void* d
   return MSM377_OK;
 }
 
-// The precomputed-window table and its wide-window work buffers (allocated on demand, 2.2-2.7 GB at 2^20 points).
-void free_table(msm377_ctx* ctx) {
-  for (void* p : {(void*)ctx->d_table, (void*)ctx->d_wide_digits, (void*)ctx->d_wide_counts, (void*)ctx->d_wide_temp})
-    if (p) (void)hipFree(p);
-  ctx->d_table = nullptr;
-  ctx->d_wide_digits = nullptr;
-  ctx->d_wide_counts = nullptr;
-  ctx->d_wide_temp = nullptr;
-  ctx->table_cap = 0;
-  ctx->table_windows = 0;
+// The precomputed-window table and its wide-window work buffers (allocated on demand, 2.2-2.7 GB at 2^20 points), once
+// nothing queued on either stream reads them any more.
+int free_table(msm377_ctx* ctx) {
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream2));
+  (void)hipFree(ctx->resident.table);
+  ctx->resident = ResidentBases();  // (its callers have cleared it)
+  ctx->wide.release();
+  return MSM377_OK;
 }
 
+// The four set-bases entry points clear the resident bases before anything else and set them as their last step: a
+// call that fails, for whatever reason, leaves none (include/msm377.h).
 int g1_set_bases_device(msm377_ctx* ctx, const void* d_points, uint64_t n) {
+  if (ctx) ctx->resident.clear();
   int rc = check_args(ctx, d_points, d_points, n, true);
   if (rc) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1040,22 +1084,24 @@ int g1_set_bases_device(msm377_ctx* ctx, const void* d_points, uint64_t n) {
   if (form_is_te(form) && d_points != ctx->d_raw_points)
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_raw_points, d_points, n * 96, hipMemcpyDeviceToDevice, ctx->stream2));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream2));
-  if (ctx->d_table) {  // a plain table replaces a precomputed one: give its gigabytes back
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    free_table(ctx);
+  if (ctx->resident.table) {  // a plain table replaces a precomputed one: give its gigabytes back
+    rc = free_table(ctx);
+    if (rc) return rc;
   }
-  ctx->bases_n = n;
-  ctx->bases_form = form;
+  ctx->resident.set(ctx->d_bases, n, form);
   return MSM377_OK;
 }
 
-int g1_set_bases(msm377_ctx* ctx, const uint8_t* points, uint64_t n) {
+// The host-buffer variants: the points go up into d_raw_points, and the device variant builds from there.
+static int set_bases_from_host(msm377_ctx* ctx, const uint8_t* points, uint64_t n, int (*build)(msm377_ctx*, const void*, uint64_t)) {
+  if (ctx) ctx->resident.clear();
   if (!ctx || n > ctx->cap || (n && !points)) return MSM377_EINVAL;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   int rc = h2d_staged(ctx, ctx->d_raw_points, points, n * 96, 0);
-  if (rc) return rc;
-  return g1_set_bases_device(ctx, ctx->d_raw_points, n);
+  return rc ? rc : build(ctx, ctx->d_raw_points, n);
 }
+
+int g1_set_bases(msm377_ctx* ctx, const uint8_t* points, uint64_t n) { return set_bases_from_host(ctx, points, n, g1_set_bases_device); }
 
 // Precomputed-window tables (BASELINE.json config 5 "precomputed-point reuse"; the reference lists precomputation as
 // future work, README.md:558-563): T[w][i] = [2^(c w)] P_i as affine Edwards records.  Window 0 is the batched
@@ -1065,61 +1111,52 @@ int g1_set_bases(msm377_ctx* ctx, const uint8_t* points, uint64_t n) {
 //   c = 20 (round 3, msm377_ctx_set_precompute_window): 13 windows over ONE set of 2^19 buckets -- 13 n bucket
 //          additions per MSM instead of 16 n (kernels/wide.hpp).
 int g1_set_bases_precomputed_device(msm377_ctx* ctx, const void* d_points, uint64_t n) {
+  if (ctx) ctx->resident.clear();
   int rc = check_args(ctx, d_points, d_points, n, true);
   if (rc) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (ctx->g1_form != 1 || n == 0) return g1_set_bases_device(ctx, d_points, n);  // Weierstrass form: no precomputation
   const bool wide = ctx->precomp_bits == (int)WIDE_BITS;
-  const uint32_t windows = wide ? WIDE_WINDOWS : (uint32_t)MSM377_NUM_WINDOWS;
-  if (ctx->table_cap < n || ctx->table_windows != windows) {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // nothing in flight reads the old table
-    free_table(ctx);
-    bool ok = hipMalloc((void**)&ctx->d_table, (size_t)windows * n * TeAffBase::REC_WORDS * 4) == hipSuccess;
-    if (ok && wide)
-      ok = hipMalloc((void**)&ctx->d_wide_digits, (size_t)WIDE_WINDOWS * n * 4) == hipSuccess &&
-           hipMalloc((void**)&ctx->d_wide_temp, (size_t)WIDE_WINDOWS * n * sizeof(SortElem)) == hipSuccess &&
-           hipMalloc((void**)&ctx->d_wide_counts, WC_WORDS * 4) == hipSuccess;
-    if (!ok) {
-      free_table(ctx);
-      (void)hipGetLastError();
-      ctx->err = "precomputed-window table: out of device memory";
-      return MSM377_ENOMEM;
-    }
-    ctx->table_cap = n;
-    ctx->table_windows = windows;
-  }
   if (wide && (uint64_t)WIDE_WINDOWS * n >= (1ull << 31)) {
     ctx->err = "precomputed-window table: too many points for 20-bit windows (13 n must stay below 2^31)";
     return MSM377_EINVAL;
   }
-  ctx->table_window_bits = wide ? WIDE_BITS : (uint32_t)MSM377_WINDOW_BITS;
+  const uint32_t windows = wide ? WIDE_WINDOWS : (uint32_t)MSM377_NUM_WINDOWS;
+  ResidentBases& r = ctx->resident;
+  if (r.cap < n || r.windows != windows) {
+    rc = free_table(ctx);
+    if (rc) return rc;
+    if (hipMalloc((void**)&r.table, (size_t)windows * n * TeAffBase::REC_WORDS * 4) != hipSuccess || (wide && !ctx->wide.ensure(n))) {
+      (void)free_table(ctx);
+      (void)hipGetLastError();
+      ctx->err = "precomputed-window table: out of device memory";
+      return MSM377_ENOMEM;
+    }
+    r.cap = n;
+    r.windows = windows;
+  }
   for (uint32_t w = 0; w < windows && rc == MSM377_OK; w++) {
-    ctx->table_doublings = !wide ? (uint32_t)MSM377_WINDOW_BITS : w ? wide_width(w - 1) : 0u;  // from the previous window's multiple to this one's
-    uint32_t* mine = ctx->d_table + (size_t)w * n * TeAffBase::REC_WORDS;
-    rc = affine_convert_begin(ctx, (const uint32_t*)d_points, n, w == 0 ? nullptr : mine - (size_t)n * TeAffBase::REC_WORDS, w == 0);
+    const uint32_t doublings = !wide ? (uint32_t)MSM377_WINDOW_BITS : w ? wide_width(w - 1) : 0u;  // from the previous window's multiple to this one's
+    uint32_t* mine = r.table + (size_t)w * n * TeAffBase::REC_WORDS;
+    rc = affine_convert_begin(ctx, (const uint32_t*)d_points, n, w == 0 ? nullptr : mine - (size_t)n * TeAffBase::REC_WORDS, doublings, w == 0);
     if (rc == MSM377_OK) rc = affine_convert_finish(ctx, mine, n);
   }
   if (rc) return rc;
   if (d_points != ctx->d_raw_points) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_raw_points, d_points, n * 96, hipMemcpyDeviceToDevice, ctx->stream2));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream2));
-  ctx->bases_n = n;
-  ctx->bases_form = TABLE_TE_PRECOMP;
+  r.set(ctx->d_bases, n, TABLE_TE_PRECOMP);
   return MSM377_OK;
 }
 
 int g1_set_bases_precomputed(msm377_ctx* ctx, const uint8_t* points, uint64_t n) {
-  if (!ctx || n > ctx->cap || (n && !points)) return MSM377_EINVAL;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int rc = h2d_staged(ctx, ctx->d_raw_points, points, n * 96, 0);
-  if (rc) return rc;
-  return g1_set_bases_precomputed_device(ctx, ctx->d_raw_points, n);
+  return set_bases_from_host(ctx, points, n, g1_set_bases_precomputed_device);
 }
 
 int g1_msm_fixed_base_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n, uint8_t out_xy[96]) {
   if (!out_xy) return MSM377_EINVAL;
   int rc = check_args(ctx, nullptr, d_scalars, n, false);
   if (rc) return rc;
-  if (n > ctx->bases_n) {
+  if (n > ctx->resident.n) {
     ctx->err = "fixed-base MSM needs g1_set_bases with at least n points first";
     return MSM377_ESTATE;
   }
@@ -1147,12 +1184,12 @@ static int fixed_base_batch_share(msm377_ctx* ctx, const void* d_scalars, uint64
   const uint32_t* sc = (const uint32_t*)d_scalars;
   const int form = resident_form(ctx, n);
   const bool glv = form == TABLE_XYZZ_GLV, te = form_is_te(form);
-  const bool wide = form == TABLE_TE_PRECOMP && ctx->table_window_bits == WIDE_BITS;
+  const bool wide = wide_table(ctx->resident);
   const uint32_t W = wide ? 1u : glv ? GLV_WINDOWS : (uint32_t)MSM377_NUM_WINDOWS;  // window slots of a call
   Phase table_phase;
   if (form == TABLE_TE_PRECOMP) {
-    table_phase.table = ctx->d_table;
-    table_phase.table_stride = ctx->bases_n;
+    table_phase.table = ctx->resident.table;
+    table_phase.table_stride = ctx->resident.n;
   }
   if (wide) {
     table_phase.wide = true;
@@ -1192,10 +1229,7 @@ static int fixed_base_batch_share(msm377_ctx* ctx, const void* d_scalars, uint64
         continue;
       }
       rc = finish_windows(ctx, slot);
-      if (rc) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return rc;
-      }
+      if (rc) return rc;
       if (te) {
         if (teh_combine(ctx->h_partials + (size_t)slot * SLOT_WORDS, W_tail, out_xy + (size_t)96 * (b - 1), tail_cbits, tail_planes, tail_short)) {
           te_fallback = true;
@@ -1220,12 +1254,8 @@ static int fixed_base_batch_share(msm377_ctx* ctx, const void* d_scalars, uint64
   return MSM377_OK;
 }
 
-static void twin_return(msm377_ctx* ctx) {
-  msm377_ctx* tw = ctx->twin;
-  if (!tw) return;
-  tw->d_bases = nullptr;
-  tw->d_table = nullptr;
-  tw->bases_n = 0;
+void twin_return(msm377_ctx* ctx) {
+  if (ctx->twin) ctx->twin->resident = ResidentBases();
 }
 
 // The twin of a context: a second context on the same device -- own streams, work buffers, pinned records -- that BORROWS
@@ -1242,7 +1272,7 @@ static int twin_prepare(msm377_ctx* ctx) {
       (void)hipGetLastError();
       return MSM377_ENOMEM;
     }
-    (void)hipFree(tw->d_bases);  // it only ever borrows
+    (void)hipFree(tw->d_bases);  // it only ever borrows the resident bases
     tw->d_bases = nullptr;
     (void)hipFree(tw->d_raw_points);
     tw->d_raw_points = nullptr;
@@ -1250,27 +1280,9 @@ static int twin_prepare(msm377_ctx* ctx) {
     ctx->twin = tw;
   }
   msm377_ctx* tw = ctx->twin;
-  const bool wide = ctx->bases_form == TABLE_TE_PRECOMP && ctx->table_window_bits == WIDE_BITS;
-  if (wide && tw->wide_cap < ctx->bases_n) {
-    for (void* p : {(void*)tw->d_wide_digits, (void*)tw->d_wide_counts, (void*)tw->d_wide_temp})
-      if (p) (void)hipFree(p);
-    tw->d_wide_digits = nullptr, tw->d_wide_counts = nullptr, tw->d_wide_temp = nullptr, tw->wide_cap = 0;
-    const uint64_t n = ctx->bases_n;
-    if (hipMalloc((void**)&tw->d_wide_digits, (size_t)WIDE_WINDOWS * n * 4) != hipSuccess ||
-        hipMalloc((void**)&tw->d_wide_temp, (size_t)WIDE_WINDOWS * n * sizeof(SortElem)) != hipSuccess ||
-        hipMalloc((void**)&tw->d_wide_counts, WC_WORDS * 4) != hipSuccess) {
-      (void)hipGetLastError();
-      return MSM377_ENOMEM;
-    }
-    tw->wide_cap = n;
-  }
+  if (wide_table(ctx->resident) && !tw->wide.ensure(ctx->resident.n)) return MSM377_ENOMEM;
   // lend the table, and the conversion's verdict that travels with it (d_err[2], read by the accumulation kernels)
-  tw->d_bases = ctx->d_bases;
-  tw->d_table = ctx->d_table;
-  tw->bases_n = ctx->bases_n;
-  tw->bases_form = ctx->bases_form;
-  tw->table_window_bits = ctx->table_window_bits;
-  tw->table_windows = ctx->table_windows;
+  tw->resident = ctx->resident;
   tw->seg_plain = ctx->seg_plain, tw->seg_glv = ctx->seg_glv, tw->tail_from = ctx->tail_from;
   if (hipMemcpyAsync(tw->d_err + 2, ctx->d_err + 2, sizeof(int), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
       hipStreamSynchronize(ctx->stream) != hipSuccess) {
@@ -1284,7 +1296,7 @@ int g1_msm_fixed_base_batch_device(msm377_ctx* ctx, const void* d_scalars, uint6
   if (!out_xy) return MSM377_EINVAL;
   int rc = check_args(ctx, nullptr, d_scalars, n, false);
   if (rc) return rc;
-  if (n > ctx->bases_n) {
+  if (n > ctx->resident.n) {
     ctx->err = "fixed-base MSM needs g1_set_bases with at least n points first";
     return MSM377_ESTATE;
   }
@@ -1297,15 +1309,19 @@ int g1_msm_fixed_base_batch_device(msm377_ctx* ctx, const void* d_scalars, uint6
   // fill with the other half's kernels.  Two contexts side by side measured 2.01 -> 1.89 ms per MSM on the 20-bit table
   // and 2.19 -> 2.09 on the plain one (tools/twin_probe.py, profiles/r03_final/twin_probe.txt).
   const bool split = batch >= TWIN_MIN_BATCH && ctx->twin_batches && !ctx->timing && !ctx->capture && twin_prepare(ctx) == MSM377_OK;
-  if (!split) {
-    rc = fixed_base_batch_share(ctx, d_scalars, n, batch, out_xy);
-  } else {
-    msm377_ctx* tw = ctx->twin;
-    const uint32_t mine = batch - batch / 2;
-    int rc2 = MSM377_OK;
-    std::thread other([&] { rc2 = fixed_base_batch_share(tw, (const uint32_t*)d_scalars + (size_t)mine * n * 8, n, batch - mine, out_xy + (size_t)96 * mine); });
-    rc = fixed_base_batch_share(ctx, d_scalars, n, mine, out_xy);
-    other.join();
+  msm377_ctx* tw = split ? ctx->twin : nullptr;
+  const uint32_t mine = split ? batch - batch / 2 : batch;
+  int rc2 = MSM377_OK;
+  std::thread other;
+  if (tw) other = std::thread([&] { rc2 = fixed_base_batch_share(tw, (const uint32_t*)d_scalars + (size_t)mine * n * 8, n, batch - mine, out_xy + (size_t)96 * mine); });
+  rc = fixed_base_batch_share(ctx, d_scalars, n, mine, out_xy);
+  if (tw) other.join();
+  // A share that failed may have left kernels queued that read the (borrowed) table, which the caller may rebuild or
+  // free next: after an error every stream of both contexts is idle before the twin gives it back and the call returns.
+  if (rc || rc2)
+    for (msm377_ctx* c : {ctx, tw})
+      if (c) (void)hipStreamSynchronize(c->stream), (void)hipStreamSynchronize(c->stream2);
+  if (tw) {
     twin_return(ctx);
     if (rc2 && !rc) {  // the first half's error wins; RC_TE_FALLBACK of either half reruns the whole batch
       rc = rc2;
@@ -1351,7 +1367,7 @@ int window_partials(msm377_ctx* ctx, const void* d_points, const void* d_scalars
     if (dev_out) HIP_TRY(ctx, hipMemset(dev_out, 0, bytes));
     return MSM377_OK;
   }
-  ctx->bases_n = 0;
+  ctx->resident.clear();
   // The records are complete in ctx->d_partials (slot 0) once the call's completion event has fired; the copy
   // to the caller's device buffer rides the same stream and the call returns with that stream idle, so a
   // collective on any other stream may read the buffer.
@@ -1410,7 +1426,7 @@ int g1_glv_window_partials_device(msm377_ctx* ctx, const void* d_points, const v
     return MSM377_OK;
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  ctx->bases_n = 0;
+  ctx->resident.clear();
   rc = convert_bases_g1(ctx, (const uint32_t*)d_points, n, true);
   if (rc) return rc;
   rc = enqueue_windows<G1Dev>(ctx, (const uint32_t*)d_scalars, n, win_begin, win_count, 0, true);

@@ -26,6 +26,7 @@ int g1_glv_window_partials_device(msm377_ctx* ctx, const void* d_points, const v
 int g1_generate_bases_device(msm377_ctx* ctx, uint64_t seed, uint64_t n, void* d_points_out);
 
 int reserve_host_staging(msm377_ctx* ctx);
+void twin_return(msm377_ctx* ctx);  // takes back the resident bases a batch call lent to the twin of ctx
 
 // Shared with capi.hip (argument checks of the host-only entry points, the stage read-back).
 bool hip_ok(msm377_ctx* ctx, int hip_error, const char* what);

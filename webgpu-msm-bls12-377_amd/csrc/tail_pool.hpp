@@ -195,7 +195,9 @@ struct TailPool {
     }
     return true;
   }
-  ~TailPool() {
+  // Joins the workers: returns once every job they hold -- a share a timed-out wait left running included -- has
+  // finished, so that the owner may free what those jobs touch.  Idempotent; no posts afterwards.
+  void shutdown() {
     if (!started) return;
     stop.store(true);
     armed_until_ns.store(0);
@@ -207,6 +209,7 @@ struct TailPool {
       if (sl.th.joinable()) sl.th.join();
     }
   }
+  ~TailPool() { shutdown(); }
 };
 
 }  // namespace msm377
