@@ -42,6 +42,7 @@ extern "C" {
                                     case of their (incomplete) addition law -- possible only with input points outside the
                                     prime-order subgroup; recompute the windows in form 0 (msm377_ctx_set_g1_form) and combine
                                     again.  The full-MSM entry points handle this themselves and never return it. */
+#define MSM377_EPOINT (-8)    /* an input point failed a check the caller asked for (msm377_ctx_set_base_checks) */
 
 #define MSM377_NUM_WINDOWS 16          /* ceil(256 / 16): submission.ts:108-109 */
 #define MSM377_WINDOW_BITS 16          /* chunk_size for n >= 2^16: submission.ts:97 */
@@ -190,6 +191,66 @@ int msm377_ed_msm_device(msm377_ctx* ctx, const void* d_points, const void* d_sc
 /* Synthetic Edwards inputs: P_i = [a_i]G_ed (src/reference/utils/FieldMath.ts:108-109), 64 bytes each. */
 int msm377_ed_generate_bases_device(msm377_ctx* ctx, uint64_t seed, uint64_t n, void* d_points_out);
 
+/* ---- input validation -------------------------------------------------------------------
+ * The MSM entry points trust their input: a coordinate of p or more, a pair (x, y) that is not on the curve or a point
+ * outside the prime-order subgroup goes through the pipeline like any other 96 (64) bytes and comes back as a
+ * well-formed, meaningless result with MSM377_OK.  (The reference's shaders make the same assumption; it has no
+ * counterpart of these calls.)  Points that come from a file or from a peer are checked with the calls below, before
+ * the MSM or once per resident base set.
+ *
+ * The checks are a cascade, and a point is counted once, in the first class it fails: non-canonical, then off the curve,
+ * then outside the subgroup.  A subgroup verdict means nothing for a point that is not on the curve (and the addition
+ * laws are only guaranteed there), and the curve equation is evaluated on canonical residues, so MSM377_CHECK_SUBGROUP
+ * implies the other two bits and MSM377_CHECK_CURVE implies MSM377_CHECK_CANONICAL: `flags` normalises to 1, 3 or 7.
+ * flags == 0, a bit outside MSM377_CHECK_ALL or a null report pointer: MSM377_EINVAL. */
+#define MSM377_CHECK_CANONICAL 1u /* every coordinate < p (Edwards-BLS12: < q, the BLS12-377 scalar field) */
+#define MSM377_CHECK_CURVE     2u /* G1: y^2 = x^3 + 1;  Edwards-BLS12: -x^2 + y^2 = 1 + 3021 x^2 y^2 */
+#define MSM377_CHECK_SUBGROUP  4u /* [r]P = O, r the prime group order (G1: the BLS12-377 scalar field modulus; Edwards-BLS12:
+                                     2111115437357092606062206234695386632838870926408408195193685246394721360383, a
+                                     quarter of the group: the Edwards cofactor is 4) */
+#define MSM377_CHECK_ALL       7u
+
+typedef struct {
+  uint64_t checked;          /* n */
+  uint64_t noncanonical;     /* points with a coordinate >= modulus */
+  uint64_t off_curve;        /* canonical, but not on the curve */
+  uint64_t outside_subgroup; /* on the curve, but [r]P != O */
+  uint64_t first_bad;        /* lowest index of a point counted above; UINT64_MAX if none */
+  uint32_t first_bad_reason; /* the MSM377_CHECK_* bit that point failed; 0 if none */
+  uint32_t reserved;         /* 0 */
+} msm377_check_report;
+
+/* A check call that ran returns MSM377_OK whatever it found: the verdict is the report.  The report is deterministic
+ * (first_bad is the LOWEST failing index, whatever order the GPU visits the points in) and correct for every input,
+ * like the MSM itself: the wire format cannot encode the identity, but [r]P passes through it for the points of order
+ * 2, 3, 4 and 6 and for P + T with T one of them; all of those are reported outside the subgroup.  (The subgroup
+ * test of G1 therefore runs in Weierstrass XYZZ coordinates, whatever msm377_ctx_set_g1_form says.)
+ * n == 0: MSM377_OK, all counters zero, first_bad == UINT64_MAX.  n over the context's capacity, a null or misaligned
+ * (16 bytes) device pointer: MSM377_EINVAL, as for the MSM calls.
+ * The calls use the context's stream and work buffers while they run and touch neither the resident bases nor their
+ * table: "check the set, then run the batch" and "run, then audit" both work, and d_points may be memory of the caller's
+ * that it passed to msm377_g1_set_bases*_device before.  msm377_ctx_get_fallback_info is left alone.  The host-buffer
+ * variants upload the points first.  0.08 ms (canonical + curve) and 44 ms (with the subgroup test) per 2^20 G1 points. */
+int msm377_g1_check_points_device(msm377_ctx* ctx, const void* d_points, uint64_t n, uint32_t flags, msm377_check_report* out);
+int msm377_g1_check_points(msm377_ctx* ctx, const uint8_t* points, uint64_t n, uint32_t flags, msm377_check_report* out);
+int msm377_ed_check_points_device(msm377_ctx* ctx, const void* d_points, uint64_t n, uint32_t flags, msm377_check_report* out);
+int msm377_ed_check_points(msm377_ctx* ctx, const uint8_t* points, uint64_t n, uint32_t flags, msm377_check_report* out);
+/* The same reports computed on the calling thread: no context, no device.  For small sets (a subgroup test is ~0.1 ms
+ * per G1 point here) and as the yardstick of the GPU path: a second implementation that shares no field or chain code
+ * with it. */
+int msm377_g1_check_points_host(const uint8_t* points, uint64_t n, uint32_t flags, msm377_check_report* out);
+int msm377_ed_check_points_host(const uint8_t* points, uint64_t n, uint32_t flags, msm377_check_report* out);
+
+/* Opt-in, default 0 = no check (also MSM377_BASE_CHECKS in the environment at msm377_ctx_create): the four
+ * msm377_g1_set_bases* calls check the base set with these flags after they have dropped the resident bases and before
+ * they convert it.  A set with a finding leaves NO resident bases (the fixed-base calls answer MSM377_ESTATE, as after
+ * any failed set-bases call), the call returns MSM377_EPOINT and msm377_last_error names index and reason.  flags is 0
+ * or a valid check mask, else MSM377_EINVAL. */
+int msm377_ctx_set_base_checks(msm377_ctx* ctx, uint32_t flags);
+/* The report of the last check a msm377_g1_set_bases* call ran on this context (checked == 0, first_bad == UINT64_MAX
+ * before the first one). */
+int msm377_ctx_get_last_check(const msm377_ctx* ctx, msm377_check_report* out);
+
 /* ---- stage access for parity tests (the reference's debug=true read-backs,
  *      submission.ts:466-520, 613-641, 724-798) ------------------------------------------- */
 
@@ -220,6 +281,8 @@ int msm377_g1_xyzz_to_affine(const uint32_t xyzz[52], uint8_t out_xy[96]);
  * default 0; 2 = the library's choice = 0).  Scalars outside the GLV range (>~ 2^254) rerun on the plain
  * 16-window path automatically.  1.24 vs 1.39 ms at 2^18, 3.51 vs 3.56 ms at 2^20, 12.4 vs 12.6 ms at 2^22. */
 int msm377_ctx_set_glv(msm377_ctx* ctx, int mode);
+/* The promise of mode 1 can be verified for resident base sets: with MSM377_CHECK_SUBGROUP among the flags of
+ * msm377_ctx_set_base_checks, the msm377_g1_set_bases* calls refuse a set with a point outside the subgroup (MSM377_EPOINT). */
 
 /* Internal coordinate system of the G1 full-MSM entry points (msm, msm_device, set_bases + fixed_base*); results
  * are identical.  form 1 (default): the twisted Edwards form of BLS12-377 G1 (csrc/te377.hpp) -- 7 field products per
@@ -264,7 +327,8 @@ int msm377_ctx_get_fallback_info(const msm377_ctx* ctx, uint64_t* count, uint32_
 /* HIP-event timing on the context's streams (off by default).  enabled = 1: every stage; 2: the accumulation
  * kernel alone (MSM377_STAGE_ACC_KERNEL; the other entries read 0).  Every event pair costs a few microseconds of
  * GPU idle time between the launches it separates -- ~50 us per MSM with all stages on -- so a timed loop that only
- * needs the kernel's duration uses 2. */
+ * needs the kernel's duration uses 2.  A msm377_*_check_points* call with enabled = 1 reports its curve kernel as
+ * MSM377_STAGE_CONVERT and its subgroup kernel as MSM377_STAGE_ACC_KERNEL (the other entries read 0). */
 int msm377_ctx_set_timing(msm377_ctx* ctx, int enabled);
 /* Durations in milliseconds of the last call's stages (MSM377_NUM_STAGES entries; the TAIL
  * entry is host wall time). */

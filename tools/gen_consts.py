@@ -186,6 +186,46 @@ def emit_glv():
     return out
 
 
+# ---- input validation (kernels/validate.hpp, validate_host.hpp) ----
+ED_SUBGROUP = 2111115437357092606062206234695386632838870926408408195193685246394721360383  # prime; the Edwards-BLS12 group has 4 * ED_SUBGROUP points
+
+
+def naf(k):
+    """Non-adjacent form of k, least significant digit first."""
+    out = []
+    while k:
+        d = 0
+        if k & 1:
+            d = 2 - (k & 3)
+            k -= d
+        out.append(d)
+        k >>= 1
+    return out
+
+
+def emit_check():
+    """The fixed chains of the subgroup test: acc = [order]P walks the signed digits from the top, one doubling per digit
+    and an addition (POS bit) or subtraction (NEG bit) of P where the digit is not zero.  ORDER64: the same number in
+    64-bit words, for the host's plain double-and-add."""
+    def words(v, n):
+        return ", ".join("0x%08xu" % ((v >> (32 * i)) & 0xFFFFFFFF) for i in range(n))
+
+    out = "struct CheckConsts {  // [order]P = O: G1 order = Q (the scalar field), Edwards-BLS12 prime subgroup order (cofactor 4)\n"
+    for name, order in (("G1", Q), ("ED", ED_SUBGROUP)):
+        d = naf(order)
+        assert sum(x << i for i, x in enumerate(d)) == order and all(not (a and b) for a, b in zip(d, d[1:])) and d[-1] == 1
+        pos = sum(1 << i for i, x in enumerate(d) if x == 1)
+        neg = sum(1 << i for i, x in enumerate(d) if x == -1)
+        assert len(d) <= 256
+        out += "static constexpr int %s_NAF_LEN = %d;  // %d doublings, %d additions\n" % (name, len(d), len(d) - 1, sum(1 for x in d if x) - 1)
+        out += "static constexpr uint32_t %s_NAF_POS[8] = {%s};\n" % (name, words(pos, 8))
+        out += "static constexpr uint32_t %s_NAF_NEG[8] = {%s};\n" % (name, words(neg, 8))
+        out += "static constexpr uint64_t %s_ORDER64[4] = {%s};\n" % (name, ", ".join("0x%016xull" % ((order >> (64 * i)) & ((1 << 64) - 1)) for i in range(4)))
+        out += "static constexpr int %s_ORDER_BITS = %d;\n" % (name, order.bit_length())
+    out += "};\n\n"
+    return out
+
+
 def main():
     global GLV_BETA
     GLV_BETA = _find_beta()
@@ -202,7 +242,10 @@ def main():
                 # twisted Edwards form (csrc/te377.hpp): Montgomery forms of s, c s, 2d; and the raw (non-Montgomery)
                 # multipliers s R, c s R that take a RAW wire coordinate straight to the Montgomery form of s x, c s x
                 "TE_S": s_, "TE_CS": c_ * s_, "TE_2D": 2 * d_, "TE_INV_D": pow(d_, -1, P), "TE_SR": s_ * R29, "TE_CSR": c_ * s_ * R29,
-                "TE_SBR": s_ * GLV_BETA * R29, "TE_CSBR": c_ * s_ * GLV_BETA * R29}
+                "TE_SBR": s_ * GLV_BETA * R29, "TE_CSBR": c_ * s_ * GLV_BETA * R29,
+                # k_check_curve: (x^3 - y^2) / R^2 of a point on the curve, as a PLAIN residue (the entry is -R^-3, and the
+                # table stores entry * R): the curve test works on the raw wire coordinates, no conversion
+                "CHK_RHS_RAW": -pow(R29, -3, P)}
     s += emit("G1Consts", P, 13, g1_extra, rs=14, lazy=True)
     s += emit_glv()
     # Fq keeps R = 2^261 (9 steps): q is 253 bits, so the radix already leaves 8 bits of slack for the lazy forms
@@ -211,6 +254,7 @@ def main():
     # integer -- the way back for the block inverses of the batched affine conversion (msm377.hip affine_convert_finish)
     s += emit64("G1Consts64", P, 6, 14, {"TE_2D": 2 * d_, "TE_INV_S": pow(s_, -1, P), "TE_C_OVER_S": c_ * pow(s_, -1, P), "TO29": 1 << (29 * 14 - 64 * 6)})
     s += emit64("EdConsts64", Q, 4, 9, {"ED_D": ED_D, "ED_2D": 2 * ED_D})
+    s += emit_check()
     s += "}  // namespace msm377\n"
     with open(dst, "w") as f:
         f.write(s)

@@ -15,7 +15,19 @@ from .host.codecs import (  # noqa: F401
     readBigIntsFromBufferLE,
     u32ArrayToBigInts,
 )
-from .host.engine import MsmEngine, MsmError, library_path, load_library  # noqa: F401
+from .host.engine import (  # noqa: F401
+    CHECK_ALL,
+    CHECK_CANONICAL,
+    CHECK_CURVE,
+    CHECK_SUBGROUP,
+    CheckReport,
+    MsmEngine,
+    MsmError,
+    check_points_host,
+    ed_check_points_host,
+    library_path,
+    load_library,
+)
 from .host.submission import compute_msm, points_to_buffer, scalars_to_buffer  # noqa: F401
 from .host.sharding import combine_partials, windows_for_rank  # noqa: F401
 
@@ -23,6 +35,13 @@ __all__ = [
     "compute_msm",
     "MsmEngine",
     "MsmError",
+    "CheckReport",
+    "check_points_host",
+    "ed_check_points_host",
+    "CHECK_CANONICAL",
+    "CHECK_CURVE",
+    "CHECK_SUBGROUP",
+    "CHECK_ALL",
     "load_library",
     "library_path",
     "windows_for_rank",

@@ -11,6 +11,7 @@
 #include "context.hpp"
 #include "host_tail.hpp"
 #include "sequencer.hpp"
+#include "validate_host.hpp"
 
 using namespace msm377;
 
@@ -35,6 +36,7 @@ const char* msm377_strerror(int code) {
     case MSM377_ESTATE: return "call sequence error";
     case MSM377_EGLVRANGE: return "scalar outside the GLV range";
     case MSM377_EEXCEPTIONAL: return "exceptional case of the twisted Edwards law while combining partial records";
+    case MSM377_EPOINT: return "an input point failed a requested check (canonical / on the curve / in the subgroup)";
     default: return "unknown error";
   }
 }
@@ -74,6 +76,7 @@ int msm377_ctx_create(int device, uint64_t max_points, msm377_ctx** out) {
   if (const char* e = getenv("MSM377_TAIL_LDS")) ctx->tail_lds = atoi(e) != 0;
   if (const char* e = getenv("MSM377_EVEN_WINDOWS")) ctx->even_windows = atoi(e) != 0;
   if (const char* e = getenv("MSM377_TWIN_BATCH")) ctx->twin_batches = atoi(e) != 0;
+  if (const char* e = getenv("MSM377_BASE_CHECKS")) ctx->base_checks = check_flags_normal((uint32_t)strtoul(e, nullptr, 0));  // (an invalid mask reads as 0)
   if (const char* e = getenv("MSM377_TAIL_FROM")) ctx->tail_from = (uint32_t)std::min(std::max(atoi(e), 1), (int)TREE_LEVELS);
   const uint64_t cap = max_points;
   // The main stream outranks the side stream: the base conversion (VALU-heavy, ~0.2 ms) only has to finish before
@@ -334,6 +337,32 @@ int msm377_ctx_set_precompute_window(msm377_ctx* ctx, int window_bits) {
   return MSM377_OK;
 }
 
+int msm377_ctx_set_base_checks(msm377_ctx* ctx, uint32_t flags) {
+  if (!ctx || (flags && !check_flags_normal(flags))) return MSM377_EINVAL;
+  ctx->base_checks = check_flags_normal(flags);
+  return MSM377_OK;
+}
+
+int msm377_ctx_get_last_check(const msm377_ctx* ctx, msm377_check_report* out) {
+  if (!ctx || !out) return MSM377_EINVAL;
+  *out = ctx->last_check;
+  return MSM377_OK;
+}
+
+static int check_host_args(const uint8_t* points, uint64_t n, uint32_t flags, msm377_check_report* out) {
+  return (!out || !check_flags_normal(flags) || (n && !points)) ? MSM377_EINVAL : MSM377_OK;
+}
+int msm377_g1_check_points_host(const uint8_t* points, uint64_t n, uint32_t flags, msm377_check_report* out) {
+  if (check_host_args(points, n, flags, out)) return MSM377_EINVAL;
+  check_points_host<G1HostCheck>(points, n, check_flags_normal(flags), out);
+  return MSM377_OK;
+}
+int msm377_ed_check_points_host(const uint8_t* points, uint64_t n, uint32_t flags, msm377_check_report* out) {
+  if (check_host_args(points, n, flags, out)) return MSM377_EINVAL;
+  check_points_host<EdHostCheck>(points, n, check_flags_normal(flags), out);
+  return MSM377_OK;
+}
+
 int msm377_ctx_set_narrow_max(msm377_ctx* ctx, uint64_t max_points) {
   if (!ctx) return MSM377_EINVAL;
   ctx->narrow_max_points = max_points;
@@ -368,6 +397,10 @@ int msm377_g1_msm_fixed_base_batch_device(msm377_ctx* ctx, const void* d_scalars
 int msm377_g1_msm_fixed_base(msm377_ctx* ctx, const uint8_t* scalars, uint64_t n, uint8_t out_xy[96]) { return eng::g1_msm_fixed_base(ctx, scalars, n, out_xy); }
 int msm377_g1_glv_window_partials_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t win_begin, uint32_t win_count, uint8_t* partials_out) { return eng::g1_glv_window_partials_device(ctx, d_points, d_scalars, n, win_begin, win_count, partials_out); }
 int msm377_g1_generate_bases_device(msm377_ctx* ctx, uint64_t seed, uint64_t n, void* d_points_out) { return eng::g1_generate_bases_device(ctx, seed, n, d_points_out); }
+int msm377_g1_check_points_device(msm377_ctx* ctx, const void* d_points, uint64_t n, uint32_t flags, msm377_check_report* out) { return eng::g1_check_points_device(ctx, d_points, n, flags, out); }
+int msm377_g1_check_points(msm377_ctx* ctx, const uint8_t* points, uint64_t n, uint32_t flags, msm377_check_report* out) { return eng::g1_check_points(ctx, points, n, flags, out); }
+int msm377_ed_check_points_device(msm377_ctx* ctx, const void* d_points, uint64_t n, uint32_t flags, msm377_check_report* out) { return eng::ed_check_points_device(ctx, d_points, n, flags, out); }
+int msm377_ed_check_points(msm377_ctx* ctx, const uint8_t* points, uint64_t n, uint32_t flags, msm377_check_report* out) { return eng::ed_check_points(ctx, points, n, flags, out); }
 
 }  // extern "C"
 

@@ -169,6 +169,10 @@ struct msm377_ctx {
   msm377_ctx* twin = nullptr;   // owned; borrows `resident` for the length of a batch call
   bool twin_batches = true;     // MSM377_TWIN_BATCH=0: batches run on this context alone
   bool twin_failed = false;
+  // MSM377_BASE_CHECKS / msm377_ctx_set_base_checks: MSM377_CHECK_* flags (normalised) the set-bases calls check a base set
+  // with before they convert it; 0 = none.  last_check: the report of the last such check.
+  uint32_t base_checks = 0;
+  msm377_check_report last_check = {0, 0, 0, 0, UINT64_MAX, 0, 0};
   uint64_t fallback_count = 0;  // reruns on the Weierstrass path after an exceptional case of the Edwards law
   uint32_t fallback_mask = 0;   // MSM377_FB_* bits of the last one
 };

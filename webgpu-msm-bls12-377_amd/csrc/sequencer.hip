@@ -35,12 +35,14 @@
 
 #include "context.hpp"
 #include "host_tail.hpp"
+#include "validate_host.hpp"
 #include "kernels/accumulate.hpp"
 #include "kernels/convert.hpp"
 #include "kernels/decompose.hpp"
 #include "kernels/generate.hpp"
 #include "kernels/reduce.hpp"
 #include "kernels/sort.hpp"
+#include "kernels/validate.hpp"
 #include "kernels/wide.hpp"
 
 bool WideBuffers::ensure(uint64_t n) {
@@ -847,11 +849,104 @@ int check_args(msm377_ctx* ctx, const void* a, const void* b, uint64_t n, bool n
   return MSM377_OK;
 }
 
+// One check call (include/msm377.h "input validation"): a tiny clear, k_check_curve, and k_check_subgroup over the
+// points that passed -- on the main stream, then a host-side wait like every entry point.  The scratch lives where no
+// resident form reads: the counters in the front of d_work_meta (every MSM clears that block for itself), the index
+// list in d_val_idx (rebuilt by every MSM's sort).  d_points may be d_raw_points or the caller's memory; it is only read.
+template <class CK>
+int check_points_device(msm377_ctx* ctx, const void* d_points, uint64_t n, uint32_t flags, msm377_check_report* out) {
+  if (!out) return MSM377_EINVAL;
+  flags = check_flags_normal(flags);
+  if (!flags) return MSM377_EINVAL;
+  int rc = check_args(ctx, d_points, d_points, n, true);
+  if (rc) return rc;
+  check_report_empty(out, n);
+  if (n == 0) return MSM377_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  uint32_t* scratch = ctx->d_work_meta;
+  static_assert(CHK_WORDS <= META_BLOCK_WORDS, "the check's counters fit the work-list block");
+  uint32_t* list = (flags & MSM377_CHECK_SUBGROUP) ? ctx->d_val_idx : nullptr;  // cap entries at least (capi.hip: wcap >= 16 cap)
+  const dim3 grid((unsigned)((n + CHK_THREADS - 1) / CHK_THREADS));
+  hipLaunchKernelGGL(k_check_clear, dim3(1), dim3(64), 0, ctx->stream, scratch);
+  // msm377_ctx_set_timing(1): k_check_curve reads as the CONVERT stage, k_check_subgroup as the accumulation kernel
+  const bool timed = ctx->timing == 1;
+  {
+    StageTimer t(ctx, MSM377_STAGE_CONVERT, ctx->stream);
+    hipLaunchKernelGGL(k_check_curve<CK>, grid, dim3(CHK_THREADS), 0, ctx->stream, (const uint32_t*)d_points, n, (flags & MSM377_CHECK_CURVE) ? 1u : 0u, scratch, list);
+  }
+  if (list) {
+    StageTimer t(ctx, MSM377_STAGE_ACC_KERNEL, ctx->stream);
+    hipLaunchKernelGGL(k_check_subgroup<CK>, grid, dim3(CHK_THREADS), 0, ctx->stream, (const uint32_t*)d_points, scratch, (const uint32_t*)list);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  uint32_t h[CHK_WORDS];
+  HIP_TRY(ctx, hipMemcpyAsync(h, scratch, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (timed) {
+    for (int s = 0; s < MSM377_NUM_STAGES; s++) {
+      float ms = 0.f;
+      const bool ran = s == MSM377_STAGE_CONVERT || (list && s == MSM377_STAGE_ACC_KERNEL);
+      ctx->stage_ms[s] = ran && hipEventElapsedTime(&ms, ctx->ev[s][0], ctx->ev[s][1]) == hipSuccess ? ms : 0.0;
+    }
+  }
+  out->noncanonical = h[CHK_NONCANON];
+  out->off_curve = h[CHK_OFFCURVE];
+  out->outside_subgroup = h[CHK_OUTSIDE];
+  const uint64_t key = (uint64_t)h[CHK_FIRST] | ((uint64_t)h[CHK_FIRST + 1] << 32);
+  if (key != UINT64_MAX) {
+    out->first_bad = key >> 2;
+    const uint32_t cls = (uint32_t)(key & 3);
+    out->first_bad_reason = cls == CHK_CLASS_NONCANON ? MSM377_CHECK_CANONICAL : cls == CHK_CLASS_OFFCURVE ? MSM377_CHECK_CURVE : MSM377_CHECK_SUBGROUP;
+  }
+  return MSM377_OK;
+}
 
+// Host-buffer variant: the points go up into d_sort_temp (128 bytes per point of capacity; like the scratch above it
+// belongs to no resident form -- d_raw_points does: it keeps the raw copy of a resident base set).
+template <class CK>
+int check_points_from_host(msm377_ctx* ctx, const uint8_t* points, uint64_t n, uint32_t flags, msm377_check_report* out) {
+  if (!ctx || !out || !check_flags_normal(flags)) return MSM377_EINVAL;
+  ctx->err.clear();
+  if (n > ctx->cap) {
+    ctx->err = "n exceeds the context capacity";
+    return MSM377_EINVAL;
+  }
+  if (n && !points) {
+    ctx->err = "null input pointer";
+    return MSM377_EINVAL;
+  }
+  static_assert(MSM377_NUM_WINDOWS * sizeof(SortElem) >= CK::CV::RAW_WORDS * 4, "d_sort_temp holds the wire points of a full context");
+  if (n) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int rc = h2d_staged(ctx, ctx->d_sort_temp, points, n * CK::CV::RAW_WORDS * 4, 0);
+    if (rc) return rc;
+  }
+  return check_points_device<CK>(ctx, ctx->d_sort_temp, n, flags, out);
+}
+
+// The opt-in check of the set-bases calls (ctx->base_checks): MSM377_EPOINT with index and reason in ctx->err.
+int check_base_set(msm377_ctx* ctx, const void* d_points, uint64_t n) {
+  if (!ctx->base_checks) return MSM377_OK;
+  const int rc = check_points_device<G1Check>(ctx, d_points, n, ctx->base_checks, &ctx->last_check);
+  if (rc) return rc;
+  const msm377_check_report& r = ctx->last_check;
+  if (r.first_bad == UINT64_MAX) return MSM377_OK;
+  const char* why = r.first_bad_reason == MSM377_CHECK_CANONICAL ? "has a coordinate that is not below p"
+                    : r.first_bad_reason == MSM377_CHECK_CURVE   ? "is not on the curve"
+                                                                 : "is outside the prime-order subgroup";
+  ctx->err = "base set refused: point " + std::to_string(r.first_bad) + " " + why + " (" + std::to_string(r.noncanonical + r.off_curve + r.outside_subgroup) + " of " +
+             std::to_string(r.checked) + " points failed)";
+  return MSM377_EPOINT;
+}
 
 }  // namespace
 
 // ---- entry points (C ABI: capi.hip forwards) ----
+
+int g1_check_points_device(msm377_ctx* ctx, const void* d_points, uint64_t n, uint32_t flags, msm377_check_report* out) { return check_points_device<G1Check>(ctx, d_points, n, flags, out); }
+int g1_check_points(msm377_ctx* ctx, const uint8_t* points, uint64_t n, uint32_t flags, msm377_check_report* out) { return check_points_from_host<G1Check>(ctx, points, n, flags, out); }
+int ed_check_points_device(msm377_ctx* ctx, const void* d_points, uint64_t n, uint32_t flags, msm377_check_report* out) { return check_points_device<EdCheck>(ctx, d_points, n, flags, out); }
+int ed_check_points(msm377_ctx* ctx, const uint8_t* points, uint64_t n, uint32_t flags, msm377_check_report* out) { return check_points_from_host<EdCheck>(ctx, points, n, flags, out); }
 
 // The pinned staging buffer (128 bytes per point of capacity) and the copy streams of the host-buffer entry points.
 // h2d_staged allocates them on first use -- which made the FIRST host-buffer call of a context ~35 ms; a caller that
@@ -1076,6 +1171,8 @@ int g1_set_bases_device(msm377_ctx* ctx, const void* d_points, uint64_t n) {
   int rc = check_args(ctx, d_points, d_points, n, true);
   if (rc) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
+  rc = check_base_set(ctx, d_points, n);  // opt-in (msm377_ctx_set_base_checks)
+  if (rc) return rc;
   int form = pick_form(ctx, n);
   if (form == TABLE_TE) form = TABLE_TE_AFFINE;  // resident: affine records by the batched inversion, once
   rc = convert_table(ctx, (const uint32_t*)d_points, n, form);
@@ -1116,6 +1213,8 @@ int g1_set_bases_precomputed_device(msm377_ctx* ctx, const void* d_points, uint6
   if (rc) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (ctx->g1_form != 1 || n == 0) return g1_set_bases_device(ctx, d_points, n);  // Weierstrass form: no precomputation
+  rc = check_base_set(ctx, d_points, n);  // opt-in (msm377_ctx_set_base_checks), before anything is allocated or converted
+  if (rc) return rc;
   const bool wide = ctx->precomp_bits == (int)WIDE_BITS;
   if (wide && (uint64_t)WIDE_WINDOWS * n >= (1ull << 31)) {
     ctx->err = "precomputed-window table: too many points for 20-bit windows (13 n must stay below 2^31)";

@@ -4,6 +4,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "../../include/msm377.h"
+
 struct msm377_ctx;
 
 namespace msm377 {
@@ -24,6 +26,12 @@ int g1_msm_fixed_base(msm377_ctx* ctx, const uint8_t* scalars, uint64_t n, uint8
 int window_partials(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t win_begin, uint32_t win_count, uint8_t* host_out, void* dev_out);
 int g1_glv_window_partials_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t win_begin, uint32_t win_count, uint8_t* partials_out);
 int g1_generate_bases_device(msm377_ctx* ctx, uint64_t seed, uint64_t n, void* d_points_out);
+
+// Input validation (kernels/validate.hpp).  flags: any valid MSM377_CHECK_* mask (normalised inside).
+int g1_check_points_device(msm377_ctx* ctx, const void* d_points, uint64_t n, uint32_t flags, msm377_check_report* out);
+int g1_check_points(msm377_ctx* ctx, const uint8_t* points, uint64_t n, uint32_t flags, msm377_check_report* out);
+int ed_check_points_device(msm377_ctx* ctx, const void* d_points, uint64_t n, uint32_t flags, msm377_check_report* out);
+int ed_check_points(msm377_ctx* ctx, const uint8_t* points, uint64_t n, uint32_t flags, msm377_check_report* out);
 
 int reserve_host_staging(msm377_ctx* ctx);
 void twin_return(msm377_ctx* ctx);  // takes back the resident bases a batch call lent to the twin of ctx

@@ -9,7 +9,7 @@ MsmError(MSM377_EHIP) at context creation.
 import ctypes
 import os
 import sys
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 NUM_WINDOWS = 16
 WINDOW_BITS = 16
@@ -20,12 +20,47 @@ WINDOW_PARTIAL_BYTES = PARTIAL_POINTS * RECORD_POINT_WORDS * 4
 NUM_BUCKETS = 32768
 STAGE_NAMES = ("convert", "decompose", "sort", "accumulate", "reduce", "tail", "accumulate_kernel")
 
-OK, EINVAL, EHIP, ESCALAR, ENOMEM, ESTATE, EGLVRANGE, EEXCEPTIONAL = 0, -1, -2, -3, -4, -5, -6, -7
+OK, EINVAL, EHIP, ESCALAR, ENOMEM, ESTATE, EGLVRANGE, EEXCEPTIONAL, EPOINT = 0, -1, -2, -3, -4, -5, -6, -7, -8
+# input validation (include/msm377.h): a cascade, so a mask normalises to 1, 3 or 7
+CHECK_CANONICAL, CHECK_CURVE, CHECK_SUBGROUP, CHECK_ALL = 1, 2, 4, 7
 # msm377_ctx_get_fallback_info: where an exceptional case of the twisted Edwards law surfaced (include/msm377.h)
 FB_ACCUMULATE, FB_MERGE, FB_TREE, FB_TAIL, FB_CONVERT = 4, 8, 16, 32, 64
 GLV_WINDOWS = 8
 
 _LIB = None
+
+
+class _CheckReportStruct(ctypes.Structure):  # msm377_check_report
+    _fields_ = [
+        ("checked", ctypes.c_uint64),
+        ("noncanonical", ctypes.c_uint64),
+        ("off_curve", ctypes.c_uint64),
+        ("outside_subgroup", ctypes.c_uint64),
+        ("first_bad", ctypes.c_uint64),
+        ("first_bad_reason", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
+class CheckReport(NamedTuple):
+    """msm377_check_report: a point is counted once, in the first class it fails; ``first_bad`` is the lowest failing
+    index (None if every point passed) and ``first_bad_reason`` the CHECK_* bit it failed (0 if none)."""
+
+    checked: int
+    noncanonical: int
+    off_curve: int
+    outside_subgroup: int
+    first_bad: Optional[int]
+    first_bad_reason: int
+
+    @property
+    def ok(self) -> bool:
+        return self.first_bad is None
+
+
+def _report(r: _CheckReportStruct) -> CheckReport:
+    none = r.first_bad == 2**64 - 1
+    return CheckReport(int(r.checked), int(r.noncanonical), int(r.off_curve), int(r.outside_subgroup), None if none else int(r.first_bad), int(r.first_bad_reason))
 
 
 class MsmError(RuntimeError):
@@ -113,6 +148,14 @@ def load_library():
         "msm377_ctx_reserve_host_staging": (i32, [vp]),
         "msm377_ctx_get_stage_form": (i32, [vp]),
         "msm377_ctx_set_narrow_max": (i32, [vp, u64]),
+        "msm377_g1_check_points_device": (i32, [vp, vp, u64, u32, vp]),
+        "msm377_g1_check_points": (i32, [vp, u8p, u64, u32, vp]),
+        "msm377_ed_check_points_device": (i32, [vp, vp, u64, u32, vp]),
+        "msm377_ed_check_points": (i32, [vp, u8p, u64, u32, vp]),
+        "msm377_g1_check_points_host": (i32, [u8p, u64, u32, vp]),
+        "msm377_ed_check_points_host": (i32, [u8p, u64, u32, vp]),
+        "msm377_ctx_set_base_checks": (i32, [vp, u32]),
+        "msm377_ctx_get_last_check": (i32, [vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
@@ -127,6 +170,28 @@ def _strerror(code: int) -> str:
         return load_library().msm377_strerror(code).decode()
     except Exception:  # pragma: no cover
         return "error"
+
+
+def _check_host(fn: str, points: bytes, point_bytes: int, flags: int) -> CheckReport:
+    if len(points) % point_bytes:
+        raise ValueError("points buffer length must be a multiple of %d" % point_bytes)
+    lib = load_library()
+    rep = _CheckReportStruct()
+    rc = getattr(lib, fn)(bytes(points), len(points) // point_bytes, int(flags), ctypes.addressof(rep))
+    if rc:
+        raise MsmError(rc, fn)
+    return _report(rep)
+
+
+def check_points_host(points: bytes, flags: int = CHECK_ALL) -> CheckReport:
+    """Canonical / on-curve / subgroup report of G1 wire points on the calling thread (msm377_g1_check_points_host): no
+    context, no device -- small sets, and the yardstick of MsmEngine.check_points."""
+    return _check_host("msm377_g1_check_points_host", points, 96, flags)
+
+
+def ed_check_points_host(points: bytes, flags: int = CHECK_ALL) -> CheckReport:
+    """The same for Edwards-BLS12 wire points, 64 bytes each (msm377_ed_check_points_host)."""
+    return _check_host("msm377_ed_check_points_host", points, 64, flags)
 
 
 def combine_partials_bytes(partials: bytes, num_windows: int = NUM_WINDOWS) -> bytes:
@@ -348,6 +413,40 @@ class MsmEngine:
 
     def generate_bases_device(self, seed: int, n: int, d_points_out: int):
         self._check(self._lib.msm377_g1_generate_bases_device(self._ctx, int(seed) & (2**64 - 1), int(n), d_points_out), "msm377_g1_generate_bases_device")
+
+    # -- input validation (include/msm377.h): the verdict is the report, a finding is not an error --
+    def _check_points(self, fn: str, points, n: int, flags: int) -> CheckReport:
+        rep = _CheckReportStruct()
+        self._check(getattr(self._lib, fn)(self._ctx, points, int(n), int(flags), ctypes.addressof(rep)), fn)
+        return _report(rep)
+
+    def check_points(self, points: bytes, flags: int = CHECK_ALL) -> CheckReport:
+        """Report on G1 wire points in a host buffer, computed on the GPU; the resident bases survive the call."""
+        if len(points) % 96:
+            raise ValueError("points buffer length must be a multiple of 96")
+        return self._check_points("msm377_g1_check_points", bytes(points), len(points) // 96, flags)
+
+    def check_points_device(self, d_points: int, n: int, flags: int = CHECK_ALL) -> CheckReport:
+        return self._check_points("msm377_g1_check_points_device", d_points, n, flags)
+
+    def ed_check_points(self, points: bytes, flags: int = CHECK_ALL) -> CheckReport:
+        if len(points) % 64:
+            raise ValueError("Edwards points buffer length must be a multiple of 64")
+        return self._check_points("msm377_ed_check_points", bytes(points), len(points) // 64, flags)
+
+    def ed_check_points_device(self, d_points: int, n: int, flags: int = CHECK_ALL) -> CheckReport:
+        return self._check_points("msm377_ed_check_points_device", d_points, n, flags)
+
+    def set_base_checks(self, flags: int = CHECK_ALL):
+        """Opt-in: the set_bases* calls check a base set with these flags before they convert it and raise
+        MsmError(EPOINT) on a finding, leaving no resident bases (msm377_ctx_set_base_checks; 0 = off, the default)."""
+        self._check(self._lib.msm377_ctx_set_base_checks(self._ctx, int(flags)), "msm377_ctx_set_base_checks")
+
+    def last_check(self) -> CheckReport:
+        """The report of the last check a set_bases* call ran (msm377_ctx_get_last_check)."""
+        rep = _CheckReportStruct()
+        self._check(self._lib.msm377_ctx_get_last_check(self._ctx, ctypes.addressof(rep)), "msm377_ctx_get_last_check")
+        return _report(rep)
 
     # -- Twisted-Edwards BLS12 (BASELINE.json config 3): 64-byte points, 64-byte result --
     def ed_msm(self, points: bytes, scalars: bytes) -> bytes:

@@ -75,4 +75,10 @@ const compute_msm_fixed_base = (scalars) => {
   return { x: leBufferToBigInt(out.slice(0, 48)), y: leBufferToBigInt(out.slice(48, 96)) };
 };
 
-module.exports = { compute_msm, compute_msm_edwards, set_bases, compute_msm_fixed_base, pointsToBuffer, scalarsToBuffer, version: addon.version };
+// Input validation (msm377_g1_check_points): are the points canonical (1), on the curve (2), in the prime-order subgroup (4)?
+// compute_msm trusts its input; call this on freshly loaded points first.  Returns the report: counters as bigints, first_bad
+// the lowest failing index or null, first_bad_reason the CHECK_* bit that point failed (0 if none).
+const CHECK_CANONICAL = 1, CHECK_CURVE = 2, CHECK_SUBGROUP = 4, CHECK_ALL = 7;
+const check_points = (points, flags = CHECK_ALL) => addon.checkPointsSync(pointsToBuffer(points), flags);
+
+module.exports = { compute_msm, compute_msm_edwards, set_bases, compute_msm_fixed_base, check_points, CHECK_CANONICAL, CHECK_CURVE, CHECK_SUBGROUP, CHECK_ALL, pointsToBuffer, scalarsToBuffer, version: addon.version };

@@ -10,6 +10,17 @@
  */
 import { BigIntPoint, U32ArrayPoint } from "../reference/types";
 
+/** msm377_check_report: a point is counted once, in the first class it fails. */
+export interface CheckReport {
+  checked: bigint;
+  noncanonical: bigint;
+  off_curve: bigint;
+  outside_subgroup: bigint;
+  first_bad: bigint | null; // lowest failing index
+  first_bad_reason: number; // the CHECK_* bit that point failed; 0 if none
+}
+export const CHECK_CANONICAL = 1, CHECK_CURVE = 2, CHECK_SUBGROUP = 4, CHECK_ALL = 7;
+
 // eslint-disable-next-line @typescript-eslint/no-var-requires
 const addon: {
   computeMsm(points: Buffer, scalars: Buffer): Promise<Buffer>;
@@ -17,6 +28,7 @@ const addon: {
   computeEdMsmSync(points: Buffer, scalars: Buffer): Buffer;
   setBasesSync(points: Buffer): void;
   fixedBaseMsmSync(scalars: Buffer): Buffer;
+  checkPointsSync(points: Buffer, flags?: number): CheckReport;
   version(): string;
 } = require("./msm377/build/msm377_napi.node");
 
@@ -108,3 +120,7 @@ export const compute_msm_fixed_base = (scalars: bigint[] | Uint32Array[] | Buffe
   const out: Buffer = addon.fixedBaseMsmSync(scalarsBuf);
   return { x: leBufferToBigInt(out.subarray(0, 48) as Buffer), y: leBufferToBigInt(out.subarray(48, 96) as Buffer) };
 };
+
+// Input validation (msm377_g1_check_points): compute_msm trusts its input; call this on freshly loaded points first.
+export const check_points = (points: BigIntPoint[] | U32ArrayPoint[] | Buffer, flags: number = CHECK_ALL): CheckReport =>
+  addon.checkPointsSync(pointsToBuffer(points), flags);

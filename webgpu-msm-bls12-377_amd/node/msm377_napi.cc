@@ -11,6 +11,8 @@
 //   computeEdMsmSync(points: Buffer 64n, scalars: Buffer 32n): Buffer   the Edwards-BLS12 twin (msm377_ed_msm), 64-byte x||y
 //   setBasesSync(points: Buffer 96n): void                             fixed-base batches: keep a converted base set in HBM ...
 //   fixedBaseMsmSync(scalars: Buffer 32n): Buffer                      ... and run MSMs of n <= its size against it
+//   checkPointsSync(points: Buffer 96n, flags: number): object         input validation (msm377_g1_check_points): the report's
+//                                                                      64-bit fields as BigInt, firstBad null if none
 //   version(): string
 // Errors reject / throw a JS Error carrying msm377_strerror + msm377_last_error, matching the
 // reference's behaviour of throwing Error (cuzk/gpu.ts:7-10).
@@ -182,6 +184,63 @@ napi_value FixedBaseMsmSync(napi_env env, napi_callback_info info) {
   return buf;
 }
 
+// checkPointsSync(points, flags) -> {checked, noncanonical, off_curve, outside_subgroup, first_bad, first_bad_reason}
+napi_value CheckPointsSync(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  bool is_buf = false;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 1 || napi_is_buffer(env, argv[0], &is_buf) != napi_ok || !is_buf) {
+    napi_throw_type_error(env, nullptr, "expected (points: Buffer of 96 bytes per point, flags?: number)");
+    return nullptr;
+  }
+  uint8_t* p;
+  size_t len;
+  napi_get_buffer_info(env, argv[0], reinterpret_cast<void**>(&p), &len);
+  uint32_t flags = MSM377_CHECK_ALL;
+  if (argc >= 2) {
+    napi_valuetype t;
+    if (napi_typeof(env, argv[1], &t) == napi_ok && t != napi_undefined && napi_get_value_uint32(env, argv[1], &flags) != napi_ok) {
+      napi_throw_type_error(env, nullptr, "flags must be a number (MSM377_CHECK_* bits)");
+      return nullptr;
+    }
+  }
+  if (len % 96) {
+    napi_throw_range_error(env, nullptr, "points must hold 96 bytes per point");
+    return nullptr;
+  }
+  msm377_check_report rep;
+  std::string err;
+  int rc;
+  {
+    std::lock_guard<std::mutex> lock(g_mu);
+    rc = ensure_ctx(len / 96 ? len / 96 : 1, &err);
+    if (!rc) {
+      rc = msm377_g1_check_points(g_ctx, p, len / 96, flags, &rep);
+      if (rc) err = std::string("msm377_g1_check_points: ") + msm377_strerror(rc) + ": " + msm377_last_error(g_ctx);
+    }
+  }
+  if (rc) {
+    napi_throw_error(env, nullptr, err.c_str());
+    return nullptr;
+  }
+  napi_value obj, v;
+  napi_create_object(env, &obj);
+  const struct {
+    const char* name;
+    uint64_t value;
+  } fields[] = {{"checked", rep.checked}, {"noncanonical", rep.noncanonical}, {"off_curve", rep.off_curve}, {"outside_subgroup", rep.outside_subgroup}};
+  for (const auto& f : fields) {
+    napi_create_bigint_uint64(env, f.value, &v);
+    napi_set_named_property(env, obj, f.name, v);
+  }
+  if (rep.first_bad == UINT64_MAX) napi_get_null(env, &v);
+  else napi_create_bigint_uint64(env, rep.first_bad, &v);
+  napi_set_named_property(env, obj, "first_bad", v);
+  napi_create_uint32(env, rep.first_bad_reason, &v);
+  napi_set_named_property(env, obj, "first_bad_reason", v);
+  return obj;
+}
+
 struct Job {
   napi_async_work work = nullptr;
   napi_deferred deferred = nullptr;
@@ -251,6 +310,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"computeEdMsmSync", nullptr, ComputeEdMsmSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"setBasesSync", nullptr, SetBasesSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"fixedBaseMsmSync", nullptr, FixedBaseMsmSync, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"checkPointsSync", nullptr, CheckPointsSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"version", nullptr, Version, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
