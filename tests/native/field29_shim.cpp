@@ -7,6 +7,8 @@
 #include "g1_xyzz.hpp"
 #include "te377.hpp"
 
+#include "primitives_ops.hpp"
+
 using namespace msm377;
 
 static Fp::El load(const uint32_t* w12) { return Fp::to_mont(Fp::from_words<12>(w12)); }
@@ -31,6 +33,29 @@ static G1XYZZ load_xyzz(const uint32_t* w52) {
 }
 
 extern "C" {
+
+// ---- raw-limb entry points (primitives_ops.hpp): n cases, operands case-major; field 0 = Fp (13 limbs), 1 = Fq (9) ----
+void shim_raw_field(int field, int op, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d, uint32_t* out, uint32_t n) {
+  for (uint32_t i = 0; i < n; i++) {
+    if (field == 0)
+      primtest::field_op<Fp>(op, a + 13 * i, b + 13 * i, c + 13 * i, d + 13 * i, out + 13 * i);
+    else
+      primtest::field_op<Fq>(op, a + 9 * i, b + 9 * i, c + 9 * i, d + 9 * i, out + 9 * i);
+  }
+}
+// Te377 (field 0) / EdLazy (field 1) on raw Ext / PBase / ABase limbs: 4 N limbs per operand and result, one flag word per case
+void shim_raw_te(int field, int op, const uint32_t* p, const uint32_t* q, const uint32_t* neg, uint32_t* out, uint32_t* flags, uint32_t n) {
+  for (uint32_t i = 0; i < n; i++) {
+    if (field == 0)
+      flags[i] = primtest::te_op<Te377>(op, p + 52 * i, q + 52 * i, neg[i], out + 52 * i);
+    else
+      flags[i] = primtest::te_op<EdLazy>(op, p + 36 * i, q + 36 * i, neg[i], out + 36 * i);
+  }
+}
+// G1::madd_lz / add_lz / canon_pt on raw XYZZ limbs (52 per operand and result)
+void shim_raw_g1(int op, const uint32_t* a, const uint32_t* q, const uint32_t* neg, uint32_t* out, uint32_t n) {
+  for (uint32_t i = 0; i < n; i++) primtest::g1_op(op, a + 52 * i, q + 52 * i, neg[i], out + 52 * i);
+}
 
 // canonical 12-word little-endian operands -> canonical results
 void shim_fp_ops(const uint32_t* a, const uint32_t* b, uint32_t* mul, uint32_t* add, uint32_t* sub, uint32_t* sqr, uint32_t* neg) {

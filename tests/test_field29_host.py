@@ -1,6 +1,7 @@
 """The product's device math headers (csrc/field29.hpp, g1_xyzz.hpp, fp64_host.hpp) compiled for the
 host and checked against Python big integers.  CPU only.  The same headers compile into the HIP
-kernels; csrc/microbench.hip checks device == host on the GPU."""
+kernels; tests/test_primitives_gpu.py checks device == host on the GPU, bit for bit, and tests/test_primitives_host.py
+feeds the same headers raw limbs at the bounds of their operand contracts (every operand here is canonical)."""
 import ctypes
 import os
 import random

@@ -8,7 +8,11 @@ and that the results satisfy the storage invariant the next addition assumes:
 
     X: N-form, value < 5p + 2^354        Y, ZZ, ZZZ: N-form, value < p + 2^354
 
-Run by tests/test_lazy_bounds.py; exits non-zero on any violation.
+The operand shapes live in ONE table, shapes(): main() reads the ones it starts from (canonical, stored, stored_x) from there, and so do the
+primitive tests (tests/lazy_model.py), which feed the real field29.hpp / te377.hpp / g1_xyzz.hpp code operands at exactly
+these bounds on the host and on the GPU -- tests/test_primitives_host.py::test_shape_table_is_the_proofs pins the two together.
+
+Run by tests/test_field29_host.py::test_lazy_bounds_proof; exits non-zero on any violation.
 """
 import os
 import re
@@ -66,8 +70,55 @@ def nform(hi, lo=0, name=""):
     return V([MASK] * (N - 1) + [(hi - 1) >> (LB * (N - 1))], hi, lo, name)
 
 
+# The generic operand shapes of the lazy products (field29.hpp "Montgomery products"): top limb of an N-form value
+# below 2^31.6 (2^29.1 when the other operand is lazy), a lazy value has limbs below 3 * 2^29 and a top limb below 2^31.
+NFORM_TOP = int(2 ** 31.6)
+NARROW_TOP = int(2 ** 29.1)
+LAZY_LIMB = 3 * BETA
+LAZY_TOP = 1 << 31
+
+
+def shapes():
+    """The operand shapes of the field in use, name -> V, and what the primitive tests generate.  canonical, stored and
+    stored_x are what the replays below START from (main(), te_formulas, conversion_formulas).  The others are not inputs
+    of a replay: wide / narrow / lazy restate field29.hpp's comment, diff3 / diff7 / kp2_sub name intermediate values, and
+    they are tied to the replay only where it asserts that its own values fit them (point_formula, conversion_formulas --
+    Fp; the Fq pass consumes none of them) and where a caller runs check_columns on them (tests/lazy_model.py
+    admits_product).  A V's limbs are inclusive per-limb maxima (what a column sum sees), hi the exclusive value bound.
+        canonical  base records, constants                                         < p
+        stored     a lazy product: Y, ZZ, ZZZ of XYZZ, every Edwards coordinate,
+                   kt of an affine record                                          < p + e
+        stored_x   X of XYZZ (Fp only)                                             < 5p + e
+        wide       the widest carry-normalised operand of a product: Fp top limb < 2^31.6 (P and D of madd_lz, below
+                   7p + e, fit); Fq a value below 5q (use_field: the radix 2^261 carries products of such values)
+        narrow     the N-form partner of a lazy operand: Fp top limb < 2^29.1; Fq a stored value
+        lazy       one limb-wise add_kp_sub / add_lz of such values, not carry-normalised
+        diff3, diff7, kp2_sub (Fp)  the operands of Y3 = R D + (2p - Y1) PPP: R below 3p + e, D (and P of madd_lz) below
+                   7p + e, 2p - Y1 limb-wise (KP2's limbs); point_formula() checks that its values fit them"""
+    t = {
+        "canonical": nform(P, 0, "canonical"),
+        "stored": nform(P + E, 0, "stored"),
+    }
+    if N == 13:
+        t["stored_x"] = nform(5 * P + E, 0, "stored_x")
+        t["diff3"] = nform(3 * P + E, 0, "diff3")
+        t["diff7"] = nform(7 * P + E, 0, "diff7")
+        t["kp2_sub"] = V(list(K["KP2"]), 2 * P + 1, 0, "kp2_sub")
+        t["wide"] = V([MASK] * (N - 1) + [NFORM_TOP - 1], NFORM_TOP << (LB * (N - 1)), 0, "wide")
+        t["narrow"] = V([MASK] * (N - 1) + [NARROW_TOP - 1], NARROW_TOP << (LB * (N - 1)), 0, "narrow")
+        t["lazy"] = V([LAZY_LIMB - 1] * (N - 1) + [LAZY_TOP - 1], (LAZY_TOP << (LB * (N - 1))) + (LAZY_LIMB << (LB * (N - 2))), 0, "lazy")
+    else:
+        t["wide"] = nform(5 * P, 0, "wide")
+        t["narrow"] = nform(P + E, 0, "narrow")
+        top = max(K["KP2"][N - 1], t["stored"].limbs[N - 1]) + t["stored"].limbs[N - 1]
+        t["lazy"] = V([LAZY_LIMB - 1] * (N - 1) + [top], ((top + 1) << (LB * (N - 1))) + (LAZY_LIMB << (LB * (N - 2))), 0, "lazy")
+    assert 7 * P + E <= t["wide"].hi or N != 13
+    return t
+
+
 def m1(name=""):
-    return nform(P + E, 0, name)
+    s = shapes()["stored"]
+    return V(s.limbs, s.hi, 0, name)
 
 
 def check_columns(pairs, what):
@@ -161,6 +212,8 @@ def point_formula(x1, y1, zz1, zzz1, u_in, s_in, kp_p, kname_p, p_mults, tag):
     x3 = norm(add_kp_sub(rr, "KP4W3", 4, ppp, tag + " X3", b2=qq), tag + " X3")
     assert x3.hi <= 5 * P + E, (tag, x3.hi / P)
     d = norm(add_kp_sub(qq, "KP6", 6, x3, tag + " D"), tag + " D")
+    sh = shapes()
+    assert r.hi <= sh["diff3"].hi and p.hi <= sh["diff7"].hi and d.hi <= sh["diff7"].hi, tag
     y3 = mul_add_mul_lz(r, d, kp_sub("KP2", 2, y1, tag + " -Y1"), ppp, tag + " Y3")
     return x3, y3, pp, ppp, r, d, qq
 
@@ -204,14 +257,15 @@ def csub_mod(a, name):
 
 def conversion_formulas():
     """kernels/convert.hpp, the batched affine conversion in lazy forms (AffWireSource::load, k_affine_up, k_affine_down)."""
-    canonical = nform(P, 0, "canonical")
+    canonical = shapes()["canonical"]
     zero = V([0] * N, 1, 0, "zero")
     u = add_lz(mul_lz(canonical, canonical, "conv x*SR"), canonical, "conv u")
     v = mul_lz(canonical, canonical, "conv v")
     cu = csub_mod(norm(add_lz(mul_lz(canonical, canonical, "conv x*CSR"), canonical, "conv cu"), "conv cu"), "conv cu")
     assert cu.hi <= P + E, cu.hi / P
     up = add_lz(u, canonical, "conv u+1")
-    assert max(up.limbs[:-1]) < 3 * BETA and up.limbs[-1] < (1 << 31)
+    assert all(x <= y for x, y in zip(up.limbs, shapes()["lazy"].limbs))  # a lazy operand; v is its N-form partner
+    assert v.limbs[-1] <= shapes()["narrow"].limbs[-1]
     z = mul_lz(up, v, "conv z")
     n1 = mul_lz(up, cu, "conv n1")
     n2 = norm(add_kp_sub(z, "KP4W3", 4, zero, "conv n2", b2=v), "conv n2")
@@ -237,10 +291,10 @@ def conversion_formulas():
 
 def main():
     use_field("Fq")  # Edwards-BLS12 buckets (EdDev): same law over the 9-limb field
-    te_formulas(nform(P, 0, "canonical"))
+    te_formulas(shapes()["canonical"])
     use_field("Fp")
-    canonical = nform(P, 0, "canonical")
-    X1 = nform(5 * P + E, 0, "X1")
+    canonical = shapes()["canonical"]
+    X1 = shapes()["stored_x"]
     Y1, ZZ1, ZZZ1 = m1("Y1"), m1("ZZ1"), m1("ZZZ1")
 
     # ---- madd_lz ----
@@ -252,7 +306,7 @@ def main():
     mul_lz(ZZZ1, ppp, "madd ZZZ3")
 
     # ---- add_lz (thread) ----
-    X2 = nform(5 * P + E, 0, "X2")
+    X2 = shapes()["stored_x"]
     u1 = mul_lz(X1, ZZ1, "add U1")
     u2 = mul_lz(X2, ZZ1, "add U2")
     s1 = mul_lz(Y1, ZZZ1, "add S1")
