@@ -34,7 +34,7 @@ extern "C" {
 #define MSM377_OK 0
 #define MSM377_EINVAL (-1)    /* bad argument (null pointer, n over capacity, window range) */
 #define MSM377_EHIP (-2)      /* a HIP runtime call failed; see msm377_last_error() */
-#define MSM377_ESCALAR (-3)   /* a scalar overflowed the signed 16-bit recode (final carry) */
+#define MSM377_ESCALAR (-3)   /* a scalar overflowed the signed 16-bit recode (final carry), or the scalar_bits a short-scalar call declared */
 #define MSM377_ENOMEM (-4)    /* device or host allocation failed */
 #define MSM377_ESTATE (-5)    /* call sequence error (e.g. fixed-base MSM before set_bases) */
 #define MSM377_EGLVRANGE (-6) /* GLV window sharding only: a scalar >~ 2^254; repeat with the plain window path */
@@ -174,6 +174,55 @@ int msm377_g1_glv_window_partials_device(msm377_ctx* ctx, const void* d_points, 
                                          uint32_t win_begin, uint32_t win_count, uint8_t* partials_out);
 /* Combine `num_windows` gathered partial records (16 plain, 8 GLV).  Host-only. */
 int msm377_g1_combine_window_partials(const uint8_t* partials, uint32_t num_windows, uint8_t out_xy[96]);
+
+/* ---- short scalars -------------------------------------------------------------------------
+ * Most callers of an MSM engine do not multiply by uniform 253-bit scalars: batch verification uses 128-bit challenges,
+ * witness and range-check columns hold 64-bit values, bytes or bits, lookup multiplicities are 32-bit counts.  These
+ * entry points take the scalars compact -- n x scalar_bytes little-endian bytes, scalar_bytes in {4, 8, 16, 32}, device
+ * pointers 16-byte aligned as elsewhere -- together with scalar_bits, 1 .. min(8 scalar_bytes, 253): the caller's PROMISE
+ * that every scalar is below 2^scalar_bits (msm377_scalars_width_* measure it).  Any other stride or width is
+ * MSM377_EINVAL; n == 0 gives the identity.
+ *
+ * Geometry.  The path is chosen by n as for the full-width calls: 2^L buckets per window with L = 11 up to the
+ * msm377_ctx_set_narrow_max size (Edwards form, plain resident bases or none) and L = 15 above it, for every
+ * precomputed table and in form 0.  The call runs
+ *     W = msm377_short_windows(scalar_bits, L) = floor(scalar_bits / (L + 1)) + 1
+ * window slots: the first W - 1 are signed digits of L + 1 bits with a carry into the next window, the top one is the
+ * unsigned rest -- scalar_bits mod (L + 1) bits plus the carry, at most 2^L -- so it never carries out and no scalar
+ * below 2^scalar_bits needs a second pass.  At 253 bits W is 16 (L = 15) and 22 (L = 11), the window counts of the
+ * full-width calls; 64-bit scalars run 5 windows and 128-bit ones 9 at L = 15.  Sort, bucket reduction, partial records
+ * and host tail cover those W windows only.  The top window may hold a few bits or carries only; its sort ranges are
+ * narrowed by its largest key like the top window of the 16-window recode.
+ *
+ * A scalar of 2^scalar_bits or more breaks the promise: the call fails with MSM377_ESCALAR, msm377_last_error names
+ * the declared width and out_xy is left untouched.  There is no rerun at full width -- a wrong width is a caller bug.
+ *
+ * Form: twisted Edwards, with the automatic Weierstrass rerun on an exceptional case as for the full-width calls
+ * (msm377_ctx_get_fallback_info counts it); with msm377_ctx_set_g1_form(0) W windows of XYZZ at L = 15.  Never the GLV
+ * front end.  Affine records per call from MSM377_AFFINE_MIN points on, as for msm377_g1_msm_device.
+ * Not covered: Edwards-BLS12, the window-partials and batch calls, a chunked upload (msm377_g1_msm_short uploads the
+ * n x scalar_bytes scalars, then the points behind decomposition and sort, in one piece each). */
+int msm377_g1_msm_short_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t scalar_bytes,
+                               uint32_t scalar_bits, uint8_t out_xy[96]);
+int msm377_g1_msm_short(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint32_t scalar_bytes,
+                        uint32_t scalar_bits, uint8_t out_xy[96]);
+/* Over whatever the last msm377_g1_set_bases* call left resident (MSM377_ESTATE without): plain records and the 16-bit
+ * table serve window slots 0 .. W - 1 (the table's bucket sets are still added before the one reduction); the 20-bit
+ * table serves through its first window's records, the points themselves, on the L = 15 path -- the wide table buys
+ * nothing for short scalars.  The resident bases are left as they were. */
+int msm377_g1_msm_fixed_base_short_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n, uint32_t scalar_bytes,
+                                          uint32_t scalar_bits, uint8_t out_xy[96]);
+/* The largest bit length among n scalars of scalar_bytes bytes each (0 for all-zero scalars and for n == 0): what a
+ * caller passes as scalar_bits.  The device variant uses the context's stream and touches neither the resident bases
+ * nor a result; n is not bounded by the context's capacity.  The host variant needs no context and no device. */
+int msm377_scalars_width_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n, uint32_t scalar_bytes, uint32_t* bits_out);
+int msm377_scalars_width_host(const uint8_t* scalars, uint64_t n, uint32_t scalar_bytes, uint32_t* bits_out);
+/* W of the rule above: floor(scalar_bits / (bucket_log + 1)) + 1.  Host-only and pure; 0 for scalar_bits outside
+ * 1 .. 253 or bucket_log outside 1 .. 15. */
+uint32_t msm377_short_windows(uint32_t scalar_bits, uint32_t bucket_log);
+/* Window slots and bucket_log (L) of the last G1 MSM call's last pass on this context, e.g. (16, 15), (22, 11),
+ * (1, 19) on the 20-bit table, (5, 15) for a 64-bit short call; (0, 0) before the first call. */
+int msm377_ctx_get_last_geometry(const msm377_ctx* ctx, uint32_t* windows, uint32_t* bucket_log);
 
 /* Synthetic inputs: P_i = [a_i]G, a_i the i-th SplitMix64(seed)
  * output, written in wire format to device memory d_points_out (n x 96 bytes). */

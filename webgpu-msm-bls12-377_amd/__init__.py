@@ -12,6 +12,7 @@ from .host.codecs import (  # noqa: F401
     bigIntsToBufferLE,
     bigIntsToU32Array,
     bigIntToU32Array,
+    encode_scalars,
     readBigIntsFromBufferLE,
     u32ArrayToBigInts,
 )
@@ -27,6 +28,8 @@ from .host.engine import (  # noqa: F401
     ed_check_points_host,
     library_path,
     load_library,
+    scalars_width_host,
+    short_windows,
 )
 from .host.submission import compute_msm, points_to_buffer, scalars_to_buffer  # noqa: F401
 from .host.sharding import combine_partials, windows_for_rank  # noqa: F401
@@ -43,6 +46,9 @@ __all__ = [
     "CHECK_SUBGROUP",
     "CHECK_ALL",
     "load_library",
+    "scalars_width_host",
+    "short_windows",
+    "encode_scalars",
     "library_path",
     "windows_for_rank",
     "combine_partials",

@@ -363,6 +363,35 @@ int msm377_ed_check_points_host(const uint8_t* points, uint64_t n, uint32_t flag
   return MSM377_OK;
 }
 
+// ---- short scalars: the host-only parts ----
+uint32_t msm377_short_windows(uint32_t scalar_bits, uint32_t bucket_log) {
+  if (scalar_bits < 1 || scalar_bits > 253 || bucket_log < 1 || bucket_log > 15) return 0;
+  return short_windows(scalar_bits, bucket_log);
+}
+
+int msm377_scalars_width_host(const uint8_t* scalars, uint64_t n, uint32_t scalar_bytes, uint32_t* bits_out) {
+  if (!bits_out || (n && !scalars) || (scalar_bytes != 4 && scalar_bytes != 8 && scalar_bytes != 16 && scalar_bytes != 32)) return MSM377_EINVAL;
+  uint32_t best = 0;
+  for (uint64_t i = 0; i < n; i++) {
+    const uint8_t* k = scalars + i * scalar_bytes;
+    for (uint32_t j = scalar_bytes; j-- > 0;) {
+      if (!k[j]) continue;
+      const uint32_t len = 8 * j + 32 - (uint32_t)__builtin_clz((uint32_t)k[j]);
+      best = std::max(best, len);
+      break;
+    }
+  }
+  *bits_out = best;
+  return MSM377_OK;
+}
+
+int msm377_ctx_get_last_geometry(const msm377_ctx* ctx, uint32_t* windows, uint32_t* bucket_log) {
+  if (!ctx) return MSM377_EINVAL;
+  if (windows) *windows = ctx->last_geom_windows;
+  if (bucket_log) *bucket_log = ctx->last_geom_log;
+  return MSM377_OK;
+}
+
 int msm377_ctx_set_narrow_max(msm377_ctx* ctx, uint64_t max_points) {
   if (!ctx) return MSM377_EINVAL;
   ctx->narrow_max_points = max_points;
@@ -385,6 +414,10 @@ int msm377_ctx_get_stage_ms(msm377_ctx* ctx, double* ms_out) {
 int msm377_ctx_reserve_host_staging(msm377_ctx* ctx) { return eng::reserve_host_staging(ctx); }
 int msm377_g1_msm_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint8_t out_xy[96]) { return eng::g1_msm_device(ctx, d_points, d_scalars, n, out_xy); }
 int msm377_g1_msm(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint8_t out_xy[96]) { return eng::g1_msm(ctx, points, scalars, n, out_xy); }
+int msm377_g1_msm_short_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t scalar_bytes, uint32_t scalar_bits, uint8_t out_xy[96]) { return eng::g1_msm_short_device(ctx, d_points, d_scalars, n, scalar_bytes, scalar_bits, out_xy); }
+int msm377_g1_msm_short(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint32_t scalar_bytes, uint32_t scalar_bits, uint8_t out_xy[96]) { return eng::g1_msm_short(ctx, points, scalars, n, scalar_bytes, scalar_bits, out_xy); }
+int msm377_g1_msm_fixed_base_short_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n, uint32_t scalar_bytes, uint32_t scalar_bits, uint8_t out_xy[96]) { return eng::g1_msm_fixed_base_short_device(ctx, d_scalars, n, scalar_bytes, scalar_bits, out_xy); }
+int msm377_scalars_width_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n, uint32_t scalar_bytes, uint32_t* bits_out) { return eng::scalars_width_device(ctx, d_scalars, n, scalar_bytes, bits_out); }
 int msm377_ed_msm_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint8_t out_xy[64]) { return eng::ed_msm_device(ctx, d_points, d_scalars, n, out_xy); }
 int msm377_ed_msm(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint8_t out_xy[64]) { return eng::ed_msm(ctx, points, scalars, n, out_xy); }
 int msm377_ed_generate_bases_device(msm377_ctx* ctx, uint64_t seed, uint64_t n, void* d_points_out) { return eng::ed_generate_bases_device(ctx, seed, n, d_points_out); }

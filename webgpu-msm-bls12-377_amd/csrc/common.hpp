@@ -22,6 +22,7 @@ constexpr uint32_t SEG_BINS = SEG_MAX + 1; // work items are counting-sorted by 
 // any of them makes the call rerun on the Weierstrass path.  MSM377_FB_TAIL is raised by the host tail (fp64_host.hpp
 // TeChecked) and never lives in the device word.
 constexpr int ERR_SCALAR = 1, ERR_GLV_RANGE = 2, ERR_NARROW_RANGE = 128;  // 128: a scalar's top digit does not fit the narrow-window path
+constexpr int ERR_SHORT_WIDTH = 256;  // short-scalar calls: a scalar of 2^scalar_bits or more (kernels/decompose.hpp k_decompose_short)
 constexpr int ERR_TE_EXCEPTIONAL = MSM377_FB_ACCUMULATE, ERR_TE_MERGE = MSM377_FB_MERGE, ERR_TE_TREE = MSM377_FB_TREE, ERR_TE_CONVERT = MSM377_FB_CONVERT;
 constexpr int ERR_TE_ANY = ERR_TE_EXCEPTIONAL | ERR_TE_MERGE | ERR_TE_TREE | ERR_TE_CONVERT;
 // The small-input path (kernels/decompose.hpp k_decompose_geom): eleven signed 12-bit windows, then eleven unsigned 11-bit
@@ -32,12 +33,21 @@ constexpr uint32_t NARROW_EVEN_WINDOWS = 22, NARROW_EVEN_SIGNED = 11, NARROW_EVE
 static_assert(NARROW_EVEN_SIGNED * NARROW_EVEN_BITS + (NARROW_EVEN_WINDOWS - NARROW_EVEN_SIGNED) * NARROW_LOG == 253, "the windows cover a 253-bit scalar");
 constexpr uint32_t MAX_WINDOW_SLOTS = NARROW_EVEN_WINDOWS > MSM377_NUM_WINDOWS ? NARROW_EVEN_WINDOWS : MSM377_NUM_WINDOWS;  // partial-record slots
 
+// ---- short scalars (msm377_g1_msm_short*, kernels/decompose.hpp k_decompose_short) ----
+// Window slots of a call whose scalars are below 2^bits, over 2^L buckets per window: floor(bits / (L + 1)) signed digits
+// of L + 1 bits, then one unsigned digit for the bits that are left plus the carry (at most 2^L: no carry out).
+constexpr uint32_t short_windows(uint32_t bits, uint32_t L) { return bits / (L + 1) + 1; }
+static_assert(short_windows(253, 15) == MSM377_NUM_WINDOWS && short_windows(253, NARROW_LOG) == NARROW_EVEN_WINDOWS, "at full width: the window counts of the main and the narrow path");
+
 // ---- sort geometry (kernels/sort.hpp) ----
 // Sort keys: |d| in 0..32768 with the sign carried separately; coarse range = key / 128
 // (256 ranges; the last one also owns key 32768).
 constexpr uint32_t NRANGE = 256;
 constexpr uint32_t KRANGE = NB / NRANGE;  // 128 keys per range
 constexpr uint32_t KEY_TRACKED = 0x80000000u;  // key_max word: bit 31 = "measured", low bits = largest key; 0 = not measured
+// key_max word, bit 30: the slot's digits are stored UNSIGNED and unbiased (key = the stored value, sign +).  The top
+// window of a short-scalar call: its digit reaches +2^15, which a 16-bit digit biased by 2^15 cannot hold.
+constexpr uint32_t KEY_UNSIGNED = 0x40000000u;
 constexpr uint32_t SMALL_SORT_MAX = 1u << 16;            // most points k_small_sort holds in LDS (narrow-window path)
 constexpr uint32_t SMALL_BINS_MAX = (1u << 12) + 1;      // keys 0 .. 2^L for L <= 12
 struct SortElem {

@@ -102,6 +102,7 @@ struct msm377_ctx {
   // state
   uint64_t last_n = 0;
   uint32_t last_wc = 0;
+  uint32_t last_geom_windows = 0, last_geom_log = 0;  // window slots and bucket_log of the last enqueue (msm377_ctx_get_last_geometry)
   int last_form = -1;  // MSM377_STAGE_FORM_* of the buckets the last call left (stage read-backs)
   bool capture = false;
   // Zero-copy output of the full-MSM path (k_gather_partials, wait_zero_copy_out); MSM377_ZERO_COPY_OUT=0: D2H copies + event.

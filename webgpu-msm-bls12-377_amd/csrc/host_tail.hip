@@ -99,9 +99,9 @@ int te_tail(msm377_ctx* ctx, const uint32_t* partials, uint8_t out_xy[96], int n
   return TAIL_OK;
 }
 
-int xyzz_tail(msm377_ctx* ctx, const uint32_t* partials, uint8_t out_xy[96], int short_from) {
-  if (single_threaded(ctx)) {
-    g1h_combine(partials, MSM377_NUM_WINDOWS, out_xy, short_from);
+int xyzz_tail(msm377_ctx* ctx, const uint32_t* partials, uint8_t out_xy[96], int short_from, int num_windows) {
+  if (single_threaded(ctx) || num_windows < 8) {
+    g1h_combine(partials, num_windows, out_xy, short_from);
     return TAIL_OK;
   }
   using St = TailState<G1H::XYZZ, NoExtra>;
@@ -113,7 +113,7 @@ int xyzz_tail(msm377_ctx* ctx, const uint32_t* partials, uint8_t out_xy[96], int
         for (int i = 0; i < lo; i++) acc = G1H::dbl(acc);
         return acc;
       },
-      [](St&, const G1H::XYZZ& a, const G1H::XYZZ& b, int) { return G1H::add(a, b); }, tail_positions(MSM377_NUM_WINDOWS, 16, short_from), &r, std::make_shared<St>());
+      [](St&, const G1H::XYZZ& a, const G1H::XYZZ& b, int) { return G1H::add(a, b); }, tail_positions(num_windows, 16, short_from), &r, std::make_shared<St>());
   if (rc) return rc;
   g1h_to_wire(r, out_xy);
   return TAIL_OK;

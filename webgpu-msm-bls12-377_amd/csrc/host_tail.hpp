@@ -4,6 +4,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "../../include/msm377.h"
+
 struct msm377_ctx;
 
 namespace msm377 {
@@ -15,7 +17,7 @@ namespace eng {
 constexpr int TAIL_OK = 0, TAIL_EXCEPTIONAL = 1;
 
 int te_tail(msm377_ctx* ctx, const uint32_t* partials, uint8_t out_xy[96], int num_windows = 16, int cbits = 16, int planes = 15, int short_from = 0);
-int xyzz_tail(msm377_ctx* ctx, const uint32_t* partials, uint8_t out_xy[96], int short_from = 0);
+int xyzz_tail(msm377_ctx* ctx, const uint32_t* partials, uint8_t out_xy[96], int short_from = 0, int num_windows = MSM377_NUM_WINDOWS);  // 16-bit windows
 int ed_tail(msm377_ctx* ctx, const uint32_t* partials, uint8_t out_xy[64], int short_from = 0);  // Edwards-BLS12: a complete law, nothing to check
 
 // Inverses of the block products [b0, b1) the conversion's way up left in ctx->h_aff_prod, into ctx->h_aff_inv

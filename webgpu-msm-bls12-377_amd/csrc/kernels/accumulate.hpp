@@ -291,6 +291,50 @@ __global__ void __launch_bounds__(256, 2) k_accumulate_quad(const uint32_t* __re
 }
 
 // Quad per split row: bucket += its overflow partials.
+// Short-scalar calls (sequencer.hip Phase::short_bytes): the top window holds a few bits or carries only, so it is a
+// handful of rows of up to n / 2 entries -- thousands of overflow partials per row, which k_merge_split_rows_quad would
+// add one after the other (32 768 serial additions for the carry row of 2^20 32-bit scalars: 170 ms).  Here the rows of
+// that window slot with LONG_ROW_PARTIALS partials and more are folded first: a workgroup per row (rows are dealt
+// round-robin, the long ones have neighbouring keys) halves the row's list of partials in place, a lane quad per
+// addition, until the sum sits in the first record, and marks the row in row_ovf_base (OVF_FOLDED): the merge then adds
+// that one record.  256 + 14 additions deep instead of 32 768.
+constexpr uint32_t OVF_FOLDED = 0x80000000u;
+constexpr uint32_t LONG_ROW_PARTIALS = 32, FOLD_THREADS = 512, FOLD_BLOCKS = 64;
+static_assert((1u << 15) <= FOLD_THREADS * FOLD_BLOCKS, "one pass of the grid sees every row of a window (L <= 15)");
+template <class CV>
+__global__ void __launch_bounds__(FOLD_THREADS) k_fold_long_rows(const uint32_t* __restrict__ row_ptr, uint32_t* __restrict__ row_ovf_base, uint32_t* __restrict__ ovf,
+                                                                 uint32_t SEG, int* __restrict__ err, uint32_t L, uint32_t ws) {
+  __shared__ uint32_t list[FOLD_THREADS];
+  __shared__ uint32_t nlist;
+  if (threadIdx.x == 0) nlist = 0;
+  __syncthreads();
+  {  // bucket t of the slot belongs to workgroup t mod gridDim.x
+    const uint32_t t = blockIdx.x + gridDim.x * threadIdx.x;
+    if (t < (1u << L) && row_split(row_len(row_ptr, L, (ws << L) + t), SEG).nseg > LONG_ROW_PARTIALS) list[atomicAdd(&nlist, 1u)] = (ws << L) + t;
+  }
+  __syncthreads();
+  const uint32_t q = threadIdx.x & 3, quad = threadIdx.x >> 2;
+  bool bad = false;
+  for (uint32_t i = 0; i < nlist; i++) {
+    const uint32_t row = list[i];
+    uint32_t* rec = ovf + (size_t)row_ovf_base[row] * CV::BKT_WORDS;
+    for (uint32_t cur = row_split(row_len(row_ptr, L, row), SEG).nseg - 1; cur > 1;) {  // partials of the row still to add up
+      const uint32_t half = (cur + 1) / 2;
+      for (uint32_t j = quad; j + half < cur; j += FOLD_THREADS / 4) {
+        uint32_t* a = rec + (size_t)j * CV::BKT_WORDS;
+        const typename CV::Pt sum = add_quad(load_record_quad<CV>(a, q), load_record_quad<CV>(rec + (size_t)(j + half) * CV::BKT_WORDS, q), q);
+        bad |= CV::is_bad(sum);
+        store_coord<CV>(a + q * CV::COORD_WORDS, coord4(q, sum).l);  // lane q alone read and writes coordinate q of record j
+      }
+      cur = half;
+      __syncthreads();  // workgroup-scope fence + barrier: the next level reads what this one wrote
+    }
+  }
+  __syncthreads();  // (every lane has read row_ovf_base of its rows)
+  for (uint32_t i = threadIdx.x; i < nlist; i += FOLD_THREADS) row_ovf_base[list[i]] |= OVF_FOLDED;
+  if (bad) atomicOr(err, ERR_TE_MERGE);
+}
+
 template <class CV>
 __global__ void __launch_bounds__(256, 2) k_merge_split_rows_quad(const uint32_t* __restrict__ row_ptr, uint32_t* __restrict__ buckets,
                                                                   const uint32_t* __restrict__ counters, const uint32_t* __restrict__ split_rows,
@@ -305,10 +349,11 @@ __global__ void __launch_bounds__(256, 2) k_merge_split_rows_quad(const uint32_t
   for (uint32_t i = (blockIdx.x * 256 + threadIdx.x) >> 2; i < count; i += gridDim.x * 64) {
     const uint32_t row = split_rows[i];
     const uint32_t len = row_len(row_ptr, L, row);
-    const uint32_t nseg = row_split(len, SEG).nseg;
+    const uint32_t ovf_at = row_ovf_base[row];  // OVF_FOLDED: k_fold_long_rows has added the row's partials up into the first one
+    const uint32_t nseg = (ovf_at & OVF_FOLDED) ? 2u : row_split(len, SEG).nseg;
     const uint32_t ws = row >> L, t = row & ((1u << L) - 1);
     typename CV::Pt acc = load_bucket_quad<CV>(buckets, L, ws, t, q);  // (all four lanes of a quad share i: they are all here)
-    const uint32_t* src = ovf + (size_t)row_ovf_base[row] * CV::BKT_WORDS;
+    const uint32_t* src = ovf + (size_t)(ovf_at & ~OVF_FOLDED) * CV::BKT_WORDS;
     typename CV::Pt nxt = load_record_quad<CV>(src, q);
     bool bad = false;
     for (uint32_t s = 1; s < nseg; s++) {

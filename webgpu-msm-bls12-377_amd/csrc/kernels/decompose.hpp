@@ -1,4 +1,5 @@
-// Stage 1: scalars -> signed window digits (k_decompose, k_decompose_geom, k_decompose_glv).  Replaces
+// Stage 1: scalars -> signed window digits (k_decompose, k_decompose_geom, k_decompose_glv; k_decompose_short and
+// k_scalars_width for scalars of a declared width).  Replaces
 // wgsl/cuzk/convert_point_coords_and_decompose_scalars.template.wgsl:100-141; model cuzk/utils.ts:66-109.
 // Device code; included by sequencer.hip only.
 #pragma once
@@ -12,6 +13,11 @@ __device__ __forceinline__ void digit_key(uint32_t biased, uint32_t& key, uint32
   sign = d < 0 ? 1u : 0u;
   key = (uint32_t)(d < 0 ? -d : d);
 }
+// The same for a slot whose key_max word may carry KEY_UNSIGNED (the top window of a short-scalar call, k_decompose_short).
+__device__ __forceinline__ void digit_key(uint32_t stored, bool uns, uint32_t& key, uint32_t& sign) {
+  digit_key(stored, key, sign);
+  if (uns) key = stored, sign = 0u;
+}
 // A window whose digits stay small (the top window: a 253-bit scalar leaves it 13 bits) would crowd all its
 // elements into a few of the 256 ranges -- regions far beyond what k_local_sort keeps in LDS.  The decomposition
 // records the largest key of window 15 and the sort narrows that window's ranges by a power of two (shift s:
@@ -19,7 +25,7 @@ __device__ __forceinline__ void digit_key(uint32_t biased, uint32_t& key, uint32
 // window slot keeps the full width (key_max = NB).
 __device__ __forceinline__ uint32_t win_shift(uint32_t key_max_word) {
   if (!(key_max_word & KEY_TRACKED)) return 0;
-  const uint32_t max_key = key_max_word & ~KEY_TRACKED;
+  const uint32_t max_key = key_max_word & ~(KEY_TRACKED | KEY_UNSIGNED);
   uint32_t s = 0;
   while (s < 5 && max_key < (NB >> (s + 1))) s++;
   return s;
@@ -147,6 +153,123 @@ __global__ void __launch_bounds__(256) k_decompose_geom(const uint32_t* __restri
 #pragma unroll
   for (uint32_t win = 0; win < 16; win++) carry16 = (((w[win >> 1] >> (16 * (win & 1))) & 0xffffu) + carry16) >= 32768u ? 1u : 0u;
   if (carry16) atomicOr(err, ERR_SCALAR);
+}
+
+// ---- short scalars (include/msm377.h msm377_g1_msm_short*) ----
+// The caller declares that every scalar is below 2^bits and hands them over as n x SB little-endian bytes, SB = 4, 8, 16
+// or 32.  The call then runs W = floor(bits / (L + 1)) + 1 window slots (common.hpp short_windows) instead of the 16 or
+// 22 of a 253-bit scalar: the first W - 1 are SIGNED digits of L + 1 bits (v = field + carry; v >= 2^L: digit
+// v - 2^(L+1) in [-2^L, 0] and a carry into the next window), the top one is the UNSIGNED rest, bits mod (L + 1) <= L
+// bits plus the carry: at most 2^L, so nothing carries out and no scalar below 2^bits needs a second pass.
+// A scalar of 2^bits or more raises ERR_SHORT_WIDTH (the call fails with MSM377_ESCALAR); its excess bits are dropped
+// before the recode, so that every digit stays a valid sort key whatever the input holds.
+//
+// One thread per scalar.  Every lane issues 16-byte loads: with SB = 4 (8) four (two) neighbouring lanes read the same
+// aligned 16 bytes and pick their word(s) -- the wave still covers one contiguous stretch -- except at the end of an
+// array whose last 16 bytes are incomplete, where the lane loads its SB bytes alone.
+template <int SB>
+__device__ __forceinline__ void load_short_scalar(const uint8_t* __restrict__ scalars, uint64_t i, uint64_t n, uint32_t* w /* SB / 4 words */) {
+  if constexpr (SB >= 16) {
+    load_words16(reinterpret_cast<const uint32_t*>(scalars + i * SB), w, SB / 16);
+  } else {
+    constexpr uint64_t PER = 16 / SB;  // scalars per 16 bytes
+    const uint64_t g = i / PER;
+    if ((g + 1) * PER <= n) {
+      uint4 q = reinterpret_cast<const uint4*>(scalars)[g];
+      asm volatile("" : "+v"(q.x), "+v"(q.y), "+v"(q.z), "+v"(q.w));  // all four words: keeps the load 16 bytes wide (else it is narrowed to the word picked below)
+      const uint32_t k = (uint32_t)(i % PER);
+      if constexpr (SB == 8) {
+        w[0] = k ? q.z : q.x;
+        w[1] = k ? q.w : q.y;
+      } else {
+        w[0] = k == 0 ? q.x : k == 1 ? q.y : k == 2 ? q.z : q.w;
+      }
+    } else if constexpr (SB == 8) {
+      const uint2 q = reinterpret_cast<const uint2*>(scalars)[i];
+      w[0] = q.x;
+      w[1] = q.y;
+    } else {
+      w[0] = reinterpret_cast<const uint32_t*>(scalars)[i];
+    }
+  }
+}
+
+// Digits are stored biased by `bias` (2^15 on the main path, 2^L for k_small_sort); the top window's by `top_bias`: the
+// same on the narrow path, 0 on the main path, whose sort then reads that slot as unsigned (KEY_UNSIGNED in its key_max
+// word: +2^15 does not fit a 16-bit digit biased by 2^15).  top_key_max (main path; null otherwise): the largest key of
+// the top window, which holds few bits or carries only -- the sort narrows its ranges by it (win_shift).
+template <int SB>
+__global__ void __launch_bounds__(256) k_decompose_short(const uint8_t* __restrict__ scalars, uint16_t* __restrict__ digits, uint64_t n, uint32_t bits, uint32_t L,
+                                                         uint32_t W, uint32_t bias, uint32_t top_bias, int* __restrict__ err, uint32_t* __restrict__ top_key_max) {
+  constexpr int NW = SB / 4;
+  __shared__ uint32_t wmax;
+  if (threadIdx.x == 0) wmax = 0;
+  __syncthreads();
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) {
+    uint32_t w[NW];
+    load_short_scalar<SB>(scalars, i, n, w);
+    uint32_t excess = 0;  // bits at 2^bits and above
+#pragma unroll
+    for (int j = 0; j < NW; j++) {
+      const uint32_t lo = 32u * j;
+      const uint32_t keep = bits <= lo ? 0u : bits >= lo + 32u ? 0xffffffffu : (1u << (bits - lo)) - 1u;
+      excess |= w[j] & ~keep;
+      w[j] &= keep;
+    }
+    if (excess) atomicOr(err, ERR_SHORT_WIDTH);
+    const uint32_t c = L + 1, mask = (1u << c) - 1u;  // c <= 16
+    uint32_t carry = 0;
+    for (uint32_t win = 0; win + 1 < W; win++) {
+      const uint32_t v = (w[0] & mask) + carry;
+      carry = v >> L ? 1u : 0u;
+      digits[(size_t)win * n + i] = (uint16_t)(v + bias - (carry << c));
+#pragma unroll
+      for (int j = 0; j + 1 < NW; j++) w[j] = (w[j] >> c) | (w[j + 1] << (32u - c));  // the scalar moves down a window: no indexed register access
+      w[NW - 1] >>= c;
+    }
+    const uint32_t top = w[0] + carry;  // what is left is below 2^(bits mod c) <= 2^L
+    digits[(size_t)(W - 1) * n + i] = (uint16_t)(top + top_bias);
+    if (top_key_max && top > wmax) atomicMax(&wmax, top);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && top_key_max) atomicMax(top_key_max, wmax | KEY_TRACKED | KEY_UNSIGNED);
+}
+
+// Largest bit length in an array of n scalars of `wps` 32-bit words each (1, 2, 4 or 8), 0 if all are zero: the array
+// is read as 16-byte groups of words whatever the stride -- word k of the array is word k mod wps of its scalar -- a
+// grid-stride loop, a maximum per wave by lane exchange, one per workgroup through LDS, one atomic per workgroup.
+__global__ void __launch_bounds__(256) k_scalars_width(const uint32_t* __restrict__ words, uint64_t nwords, uint32_t wps, uint32_t* __restrict__ out) {
+  __shared__ uint32_t wave_max[4];
+  const uint32_t tid = threadIdx.x;
+  const uint64_t groups = nwords / 4;
+  const uint4* v = reinterpret_cast<const uint4*>(words);
+  uint32_t m = 0;
+  auto see = [&](uint64_t k, uint32_t x) {
+    if (x) {
+      const uint32_t len = ((uint32_t)k & (wps - 1u)) * 32u + 32u - (uint32_t)__builtin_clz(x);
+      m = len > m ? len : m;
+    }
+  };
+  for (uint64_t g = (uint64_t)blockIdx.x * 256 + tid; g < groups; g += (uint64_t)gridDim.x * 256) {
+    const uint4 q = v[g];
+    see(4 * g, q.x);
+    see(4 * g + 1, q.y);
+    see(4 * g + 2, q.z);
+    see(4 * g + 3, q.w);
+  }
+  if (blockIdx.x == 0 && tid < (uint32_t)(nwords & 3)) see(4 * groups + tid, words[4 * groups + tid]);  // an incomplete last group
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const uint32_t o = (uint32_t)__shfl_xor((int)m, off, 64);
+    m = o > m ? o : m;
+  }
+  if ((tid & 63) == 0) wave_max[tid >> 6] = m;
+  __syncthreads();
+  if (tid == 0) {
+    for (int k = 1; k < 4; k++) m = wave_max[k] > m ? wave_max[k] : m;
+    if (m) atomicMax(out, m);
+  }
 }
 
 // out[0..NA+NB) = a * b on 32-bit words (schoolbook, carries resolved per row).

@@ -47,11 +47,12 @@ __global__ void __launch_bounds__(256, 2) k_tree_step(uint32_t* __restrict__ buc
 // Precomputed-window tables: bucket t of window slot ws += bucket t of slot ws + half (the table of slot ws already
 // carries the weight 2^(16 ws), so the sixteen bucket sets simply add up); log2(16) launches leave the sum in slot 0.
 template <class CV>
-__global__ void __launch_bounds__(256, 2) k_fold_windows(uint32_t* __restrict__ buckets, uint32_t L, uint32_t half, int* __restrict__ err) {
+__global__ void __launch_bounds__(256, 2) k_fold_windows(uint32_t* __restrict__ buckets, uint32_t L, uint32_t half, uint32_t count, int* __restrict__ err) {
+  // window slot ws + half onto slot ws, for ws < count (count = half, or half - 1 when an odd number of slots is folded)
   const uint32_t NB = 1u << L;
-  const uint32_t g = blockIdx.x * 256 + threadIdx.x;  // < half * NB
+  const uint32_t g = blockIdx.x * 256 + threadIdx.x;  // < count * NB
   const uint32_t ws = g / NB, t = g % NB;
-  if (ws >= half) return;
+  if (ws >= count) return;
   const typename CV::Pt b = load_bucket<CV>(buckets, L, ws + half, t);
   if (CV::is_stored_identity(b)) return;
   const typename CV::Pt a = load_bucket<CV>(buckets, L, ws, t);

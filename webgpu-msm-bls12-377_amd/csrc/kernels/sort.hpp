@@ -44,18 +44,22 @@ __device__ __forceinline__ void for_each_digit(const uint16_t* __restrict__ dg, 
   for (uint64_t i = head + groups * 8 + tid; i < end; i += nthreads) f(i, (uint32_t)dg[i]);
 }
 
+// UNS (both partition kernels): a slot's key_max word may carry KEY_UNSIGNED -- short-scalar calls only; the full-width
+// paths instantiate the kernels without the test.
+template <bool UNS = false>
 __global__ void __launch_bounds__(1024) k_range_count(const uint16_t* __restrict__ digits, uint32_t* __restrict__ counts /* [ws][r][c] */,
                                                       uint64_t n, uint32_t chunks, uint64_t per_chunk, const uint32_t* __restrict__ key_max) {
   __shared__ uint32_t cnt[NRANGE];
   const uint32_t c = blockIdx.x, ws = blockIdx.y, tid = threadIdx.x;
   const uint32_t shift = win_shift(key_max[ws]);
+  const bool uns = UNS && (key_max[ws] & KEY_UNSIGNED) != 0;
   if (tid < NRANGE) cnt[tid] = 0;
   __syncthreads();
   const uint64_t beg = (uint64_t)c * per_chunk;
   const uint64_t end = (beg + per_chunk < n) ? beg + per_chunk : n;
   for_each_digit(digits + (size_t)ws * n, beg, end, tid, 1024, [&](uint64_t, uint32_t biased) {
     uint32_t key, sign;
-    digit_key(biased, key, sign);
+    digit_key(biased, uns, key, sign);
     atomicAdd(&cnt[key_range(key, shift)], 1u);
   });
   __syncthreads();
@@ -97,6 +101,7 @@ __global__ void __launch_bounds__(NRANGE) k_range_scan(uint32_t* __restrict__ co
 // out by consecutive lanes -- a range's ~32 elements of the tile are one contiguous run of its stream, so whole lines go
 // out in one piece and only the two ends of a run are partial.  Interleaved A/B at 2^20: sort stage 0.344 -> 0.314 ms.
 constexpr uint32_t PT_TILE = 8192;  // 8 digits (one 16-byte load) per thread; 64 KB of staging: two workgroups per CU
+template <bool UNS = false>
 __global__ void __launch_bounds__(1024) k_partition_staged(const uint16_t* __restrict__ digits, const uint32_t* __restrict__ counts,
                                                            SortElem* __restrict__ temp, uint64_t n, uint32_t chunks, uint64_t per_chunk,
                                                            const uint32_t* __restrict__ key_max) {
@@ -108,6 +113,7 @@ __global__ void __launch_bounds__(1024) k_partition_staged(const uint16_t* __res
   __shared__ SortElem stage[PT_TILE];
   const uint32_t c = blockIdx.x, ws = blockIdx.y, tid = threadIdx.x;
   const uint32_t shift = win_shift(key_max[ws]);
+  const bool uns = UNS && (key_max[ws] & KEY_UNSIGNED) != 0;
   if (tid < NRANGE) {
     cur[tid] = counts[((size_t)ws * NRANGE + tid) * chunks + c];
     cnt[tid] = 0;
@@ -143,7 +149,7 @@ __global__ void __launch_bounds__(1024) k_partition_staged(const uint16_t* __res
     uint32_t key[8], sign[8], rg[8], rk[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) {
-      digit_key(d[j], key[j], sign[j]);
+      digit_key(d[j], uns, key[j], sign[j]);
       rg[j] = key_range(key[j], shift);
       rk[j] = 0;
       if ((valid >> j) & 1u) rk[j] = atomicAdd(&cnt[rg[j]], 1u);

@@ -284,7 +284,23 @@ struct Phase {
   bool wide = false;
   bool even = false;  // whole MSMs on 16 windows: the top three windows 15 bits wide (kernels/decompose.hpp k_decompose); the tail gets short_from = EVEN_FROM
   const uint32_t* bases_override = nullptr;  // base records of the call if not ctx->d_bases (the wide table's window 0 = the plain affine records)
+  // Short scalars (msm377_g1_msm_short*): d_scalars holds n x short_bytes bytes, every scalar below 2^short_bits; the call
+  // runs wc = short_windows(short_bits, bucket_log) window slots recoded by k_decompose_short.  0: 32-byte scalars.
+  uint32_t short_bytes = 0, short_bits = 0;
 };
+
+// k_decompose_short for the stride of the call (4, 8, 16 or 32 bytes: checked by the entry points).
+void launch_decompose_short(hipStream_t st, const void* d_scalars, uint16_t* digits, uint64_t n, uint32_t sbytes, uint32_t bits, uint32_t L, uint32_t W, uint32_t bias,
+                            uint32_t top_bias, int* d_err, uint32_t* top_key_max) {
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  const uint8_t* sc = (const uint8_t*)d_scalars;
+  switch (sbytes) {
+    case 4: hipLaunchKernelGGL(k_decompose_short<4>, grid, block, 0, st, sc, digits, n, bits, L, W, bias, top_bias, d_err, top_key_max); break;
+    case 8: hipLaunchKernelGGL(k_decompose_short<8>, grid, block, 0, st, sc, digits, n, bits, L, W, bias, top_bias, d_err, top_key_max); break;
+    case 16: hipLaunchKernelGGL(k_decompose_short<16>, grid, block, 0, st, sc, digits, n, bits, L, W, bias, top_bias, d_err, top_key_max); break;
+    default: hipLaunchKernelGGL(k_decompose_short<32>, grid, block, 0, st, sc, digits, n, bits, L, W, bias, top_bias, d_err, top_key_max); break;
+  }
+}
 
 // Enqueue stages decompose .. gather for windows [wb, wb + wc) against ctx->d_bases on the main stream, the D2H of
 // the partial records into slot `slot` of ctx->h_partials and that slot's completion event.
@@ -350,7 +366,9 @@ int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scala
     // only within each window: the accumulation kernel went from 0.038 to 0.054 ms at 2^12.)
     {
       StageTimer t(ctx, MSM377_STAGE_DECOMPOSE, st);
-      if (wide)
+      if (ph.short_bytes)  // the top slot of the main path: unsigned digits, its ranges narrowed by its largest key (win_shift)
+        launch_decompose_short(st, d_scalars, digits, n, ph.short_bytes, ph.short_bits, L, wc, narrow ? NB : 32768u, narrow ? NB : 0u, d_err, narrow ? nullptr : key_max + (wc - 1));
+      else if (wide)
         hipLaunchKernelGGL(k_decompose_wide, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, ctx->wide.digits, n, d_err);
       else if (narrow)
         hipLaunchKernelGGL(k_decompose_geom, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, digits, n, L, NARROW_EVEN_SIGNED, wc, 1u << L, d_err);
@@ -383,11 +401,17 @@ int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scala
       const uint64_t want = (n + 4095) / 4096;  // at least ~4096 elements per block
       if (chunks > want) chunks = (uint32_t)(want ? want : 1);
       const uint64_t per_chunk = (n + chunks - 1) / chunks;
-      hipLaunchKernelGGL(k_range_count, dim3(chunks, wc), dim3(1024), 0, st, digits, range_counts, n, chunks, per_chunk, key_max);
+      if (ph.short_bytes)  // (the top slot holds unsigned digits: KEY_UNSIGNED)
+        hipLaunchKernelGGL(k_range_count<true>, dim3(chunks, wc), dim3(1024), 0, st, digits, range_counts, n, chunks, per_chunk, key_max);
+      else
+        hipLaunchKernelGGL(k_range_count<false>, dim3(chunks, wc), dim3(1024), 0, st, digits, range_counts, n, chunks, per_chunk, key_max);
       HIP_TRY(ctx, hipGetLastError());
       hipLaunchKernelGGL(k_range_scan, dim3(wc), dim3(NRANGE), 0, st, range_counts, region_base, chunks);
       HIP_TRY(ctx, hipGetLastError());
-      hipLaunchKernelGGL(k_partition_staged, dim3(chunks, wc), dim3(1024), 0, st, digits, range_counts, sort_temp, n, chunks, per_chunk, key_max);
+      if (ph.short_bytes)
+        hipLaunchKernelGGL(k_partition_staged<true>, dim3(chunks, wc), dim3(1024), 0, st, digits, range_counts, sort_temp, n, chunks, per_chunk, key_max);
+      else
+        hipLaunchKernelGGL(k_partition_staged<false>, dim3(chunks, wc), dim3(1024), 0, st, digits, range_counts, sort_temp, n, chunks, per_chunk, key_max);
       HIP_TRY(ctx, hipGetLastError());
       hipLaunchKernelGGL(k_local_sort_lds, dim3(NRANGE, wc), dim3(256), 0, st, sort_temp, region_base, row_ptr, val_idx, n, key_max, NRANGE, NB);
       HIP_TRY(ctx, hipGetLastError());
@@ -435,6 +459,10 @@ int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scala
       HIP_TRY(ctx, hipGetLastError());
       ctx->acc_seq++;
       static_assert(CV::HAS_QUAD, "every curve policy has the quad-cooperative addition");
+      if (ph.short_bytes) {  // the top window of a short call: few rows, thousands of partials each -- folded before the merge
+        hipLaunchKernelGGL(k_fold_long_rows<CV>, dim3(FOLD_BLOCKS), dim3(FOLD_THREADS), 0, st, row_ptr, row_ovf_base, ovf, SEG, d_err, L, wc - 1);
+        HIP_TRY(ctx, hipGetLastError());
+      }
       // (grid-stride over the split-row list: with the even windows few rows split, and 8192 workgroups that only read the
       // count cost 11 us at 2^20)
       hipLaunchKernelGGL(k_merge_split_rows_quad<CV>, dim3(std::min<uint32_t>((rows + 63) / 64, 1024u)), dim3(256), 0, st, row_ptr, buckets, counters, split_rows, row_ovf_base, ovf, SEG, d_err, L,
@@ -451,9 +479,11 @@ int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scala
   {
     StageTimer t(ctx, MSM377_STAGE_REDUCE, st);
     if (ph.table) {
-      for (uint32_t half = wc / 2; half >= 1; half /= 2) {  // wc = 16: a power of two
-        hipLaunchKernelGGL(k_fold_windows<CV>, dim3(half * NB / 256), dim3(256), 0, st, buckets, L, half, d_err);
+      for (uint32_t m = wc; m > 1;) {  // slots [half, m) onto [0, m - half): 16 -> 8 -> 4 -> 2 -> 1; a short call folds any count
+        const uint32_t half = (m + 1) / 2, count = m - half;
+        hipLaunchKernelGGL(k_fold_windows<CV>, dim3(count * NB / 256), dim3(256), 0, st, buckets, L, half, count, d_err);
         HIP_TRY(ctx, hipGetLastError());
+        m = half;
       }
     }
     const uint32_t levels = L;  // log2 of the buckets per window
@@ -511,6 +541,8 @@ int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scala
   HIP_TRY(ctx, hipEventRecord(ctx->done_ev[slot], st));
   ctx->last_n = n;
   ctx->last_wc = wc;
+  ctx->last_geom_windows = wc;
+  ctx->last_geom_log = L;
   ctx->last_glv = glv;
   ctx->last_form = CV::FORM_ID;
   return MSM377_OK;
@@ -760,6 +792,89 @@ int resident_table_to_weierstrass(msm377_ctx* ctx) {
   if (rc) return rc;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream2));
   ctx->resident.set(ctx->d_bases, n, form);
+  return MSM377_OK;
+}
+
+// The short-scalar counterpart of g1_table_msm: n scalars of `sbytes` bytes, each below 2^bits, against the base records
+// in form `form`.  The path is chosen by n as there -- narrow windows (L = 11) for small inputs in the Edwards form, 2^15
+// buckets otherwise -- and runs W = short_windows(bits, L) window slots, ONE pass: a scalar of 2^bits or more is the
+// caller's error (MSM377_ESCALAR, out_xy untouched), not a reason to rerun at full width.  A precomputed 16-bit table
+// serves slots 0 .. W - 1 (its bucket sets are added before the one reduction); the 20-bit table serves through its
+// first window, the plain affine records.  RC_TE_FALLBACK as for g1_table_msm.
+int short_width_error(msm377_ctx* ctx, uint32_t bits) {
+  ctx->err = "a scalar does not fit the declared width of " + std::to_string(bits) + " bits (scalar_bits)";
+  return MSM377_ESCALAR;
+}
+
+int g1_short_table_msm(msm377_ctx* ctx, const void* d_scalars, uint64_t n, int form, uint32_t sbytes, uint32_t bits, uint8_t out_xy[96]) {
+  TailArm arm(ctx);
+  arm.at_start(n);
+  Phase ph;
+  ph.short_bytes = sbytes;
+  ph.short_bits = bits;
+  const uint32_t* sc = (const uint32_t*)d_scalars;
+  if (form_is_te(form)) {
+    const bool precomp = form == TABLE_TE_PRECOMP;
+    if (precomp && wide_table(ctx->resident)) {
+      ph.bases_override = ctx->resident.table;
+    } else if (precomp) {
+      ph.table = ctx->resident.table;
+      ph.table_stride = ctx->resident.n;
+    }
+    if (!precomp && n <= ctx->narrow_max_points && n <= SMALL_SORT_MAX && !ctx->capture) {
+      ph.cbits = NARROW_EVEN_BITS;
+      ph.bucket_log = NARROW_LOG;
+    }
+    const uint32_t L = ph.bucket_log, W = short_windows(bits, L);
+    ph.zc_out = true;
+    int rc = form == TABLE_TE ? enqueue_windows<TeDev>(ctx, sc, n, 0, W, 0, false, ph) : enqueue_windows<TeDev, TeAffBase>(ctx, sc, n, 0, W, 0, false, ph);
+    if (rc) return rc;
+    arm.after_accumulation();
+    if (ctx->zc_active) {
+      rc = wait_zero_copy_out(ctx);
+      if (rc) return rc;
+    } else {
+      HIP_TRY(ctx, hipEventSynchronize(ctx->done_ev[0]));
+    }
+    if (ctx->h_err[0] & ERR_SHORT_WIDTH) return short_width_error(ctx, bits);
+    if (ctx->h_err[0] & ERR_TE_ANY) {
+      note_fallback(ctx, (uint32_t)(ctx->h_err[0] & ERR_TE_ANY));
+      return RC_TE_FALLBACK;
+    }
+    rc = finish_windows(ctx, 0);
+    if (rc) return rc;
+    auto t0 = std::chrono::steady_clock::now();
+    const int tr = ph.table ? (teh_combine(ctx->h_partials, 1, out_xy, MSM377_WINDOW_BITS, MSM377_WINDOW_BITS - 1) ? TAIL_EXCEPTIONAL : TAIL_OK)
+                            : te_tail(ctx, ctx->h_partials, out_xy, (int)W, (int)L + 1, (int)L, 0);
+    time_tail(ctx, t0);
+    if (tr < 0) return tr;
+    if (tr == TAIL_EXCEPTIONAL) note_fallback(ctx, MSM377_FB_TAIL);
+    return tr == TAIL_EXCEPTIONAL ? RC_TE_FALLBACK : MSM377_OK;
+  }
+  // Weierstrass XYZZ records, never behind the GLV front end: W windows of 2^15 buckets
+  const uint32_t W = short_windows(bits, MSM377_WINDOW_BITS - 1);
+  int rc = enqueue_windows<G1Dev>(ctx, sc, n, 0, W, 0, false, ph);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipEventSynchronize(ctx->done_ev[0]));
+  if (ctx->h_err[0] & ERR_SHORT_WIDTH) return short_width_error(ctx, bits);
+  rc = finish_windows(ctx, 0);
+  if (rc) return rc;
+  auto t0 = std::chrono::steady_clock::now();
+  rc = xyzz_tail(ctx, ctx->h_partials, out_xy, 0, (int)W);
+  time_tail(ctx, t0);
+  return rc;
+}
+
+// scalar_bytes in {4, 8, 16, 32}, 1 <= scalar_bits <= min(8 scalar_bytes, 253) (include/msm377.h).
+int check_short_args(msm377_ctx* ctx, uint32_t sbytes, uint32_t bits) {
+  if (sbytes != 4 && sbytes != 8 && sbytes != 16 && sbytes != 32) {
+    ctx->err = "scalar_bytes must be 4, 8, 16 or 32";
+    return MSM377_EINVAL;
+  }
+  if (bits < 1 || bits > 8 * sbytes || bits > 253) {
+    ctx->err = "scalar_bits must be between 1 and min(8 scalar_bytes, 253)";
+    return MSM377_EINVAL;
+  }
   return MSM377_OK;
 }
 
@@ -1067,6 +1182,106 @@ int g1_msm(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint6
   return g1_table_msm(ctx, d_sc, n, form, out_xy);
 }
 
+// ---- short scalars (include/msm377.h: msm377_g1_msm_short*, msm377_scalars_width_device) ----
+int g1_msm_short_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t sbytes, uint32_t bits, uint8_t out_xy[96]) {
+  if (!out_xy) return MSM377_EINVAL;
+  int rc = check_args(ctx, d_points, d_scalars, n, true);
+  if (rc == MSM377_OK) rc = check_short_args(ctx, sbytes, bits);
+  if (rc) return rc;
+  if (n == 0) {
+    identity_wire(out_xy);
+    return MSM377_OK;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->resident.clear();
+  int form = ctx->g1_form == 1 ? TABLE_TE : TABLE_XYZZ;  // never the GLV front end
+  if (form == TABLE_TE && ctx->te_affine_msm && n >= ctx->affine_min_points) {  // per-call affine records, as in g1_msm_device
+    form = TABLE_TE_AFFINE;
+    rc = affine_convert_begin(ctx, (const uint32_t*)d_points, n);
+    if (rc) return rc;
+    ctx->before_accumulate = [ctx, n]() -> int { return affine_convert_finish(ctx, ctx->d_bases, n, true); };
+    rc = g1_short_table_msm(ctx, d_scalars, n, form, sbytes, bits, out_xy);
+    ctx->before_accumulate = nullptr;
+  } else {
+    rc = convert_table(ctx, (const uint32_t*)d_points, n, form);
+    if (rc) return rc;
+    rc = g1_short_table_msm(ctx, d_scalars, n, form, sbytes, bits, out_xy);
+  }
+  if (rc != RC_TE_FALLBACK) return rc;
+  rc = convert_table(ctx, (const uint32_t*)d_points, n, TABLE_XYZZ);
+  if (rc) return rc;
+  return g1_short_table_msm(ctx, d_scalars, n, TABLE_XYZZ, sbytes, bits, out_xy);
+}
+
+// Host buffers: the compact scalars go up first (n x scalar_bytes), decomposition, sort and work lists run while the
+// points follow on the upload thread; the conversion is launched from the hook, right before the accumulation is
+// queued -- the unchunked schedule of g1_msm (a chunked short upload is not implemented).
+int g1_msm_short(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint32_t sbytes, uint32_t bits, uint8_t out_xy[96]) {
+  if (!ctx || !out_xy) return MSM377_EINVAL;
+  ctx->err.clear();
+  if (n > ctx->cap || (n && (!points || !scalars))) {
+    ctx->err = "bad arguments";
+    return MSM377_EINVAL;
+  }
+  int rc = check_short_args(ctx, sbytes, bits);
+  if (rc) return rc;
+  if (n == 0) {
+    identity_wire(out_xy);
+    return MSM377_OK;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->resident.clear();
+  const uint32_t* d_pt = ctx->d_raw_points;
+  const bool te = ctx->g1_form == 1;
+  const bool affine = te && ctx->te_affine_msm && n >= ctx->affine_min_points;
+  const int form = !te ? TABLE_XYZZ : affine ? TABLE_TE_AFFINE : TABLE_TE;
+  rc = h2d_staged(ctx, ctx->d_raw_scalars, scalars, n * sbytes, (size_t)ctx->cap * 96);
+  if (rc) return rc;
+  int up_rc = MSM377_OK;
+  HipFail up_fail;
+  std::thread upload([&] { up_rc = hipSetDevice(ctx->device) == hipSuccess ? h2d_staged(ctx, ctx->d_raw_points, points, n * 96, 0, &up_fail) : MSM377_EHIP; });
+  ctx->before_accumulate = [&]() -> int {
+    if (upload.joinable()) upload.join();
+    if (up_rc) return up_fail.record(ctx, up_rc);
+    return convert_table(ctx, d_pt, n, form);  // (TABLE_TE_AFFINE: both phases of the batched conversion back to back)
+  };
+  rc = g1_short_table_msm(ctx, ctx->d_raw_scalars, n, form, sbytes, bits, out_xy);
+  ctx->before_accumulate = nullptr;
+  if (upload.joinable()) upload.join();  // an error before the hook ran
+  if (rc != RC_TE_FALLBACK) return rc;
+  rc = convert_table(ctx, d_pt, n, TABLE_XYZZ);
+  if (rc) return rc;
+  return g1_short_table_msm(ctx, ctx->d_raw_scalars, n, TABLE_XYZZ, sbytes, bits, out_xy);
+}
+
+int scalars_width_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n, uint32_t sbytes, uint32_t* bits_out) {
+  if (!ctx || !bits_out) return MSM377_EINVAL;
+  ctx->err.clear();
+  if (sbytes != 4 && sbytes != 8 && sbytes != 16 && sbytes != 32) {
+    ctx->err = "scalar_bytes must be 4, 8, 16 or 32";
+    return MSM377_EINVAL;
+  }
+  if ((n && !d_scalars) || ((uintptr_t)d_scalars & 15)) {
+    ctx->err = "the device scalars pointer must be non-null and 16-byte aligned";
+    return MSM377_EINVAL;
+  }
+  *bits_out = 0;
+  if (n == 0) return MSM377_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // the result word: the front of the work-list block, which every MSM clears for itself and no resident form reads
+  uint32_t* d_out = ctx->d_work_meta;
+  const uint64_t nwords = n * (sbytes / 4);
+  const unsigned blocks = (unsigned)std::min<uint64_t>((nwords / 4 + 255) / 256 + 1, 2048);
+  hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(256), 0, ctx->stream, d_out, 1u, (uint32_t*)nullptr, 0u);
+  hipLaunchKernelGGL(k_scalars_width, dim3(blocks), dim3(256), 0, ctx->stream, (const uint32_t*)d_scalars, nwords, sbytes / 4, d_out);
+  HIP_TRY(ctx, hipGetLastError());
+  uint32_t h = 0;
+  HIP_TRY(ctx, hipMemcpyAsync(&h, d_out, 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  *bits_out = h;
+  return MSM377_OK;
+}
+
 // ---- Edwards-BLS12 (BASELINE.json config 3): same pipeline, EdDev policy ----
 int ed_msm_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint8_t out_xy[64]) {
   if (!out_xy) return MSM377_EINVAL;
@@ -1273,6 +1488,34 @@ int g1_msm_fixed_base_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n,
   rc = resident_table_to_weierstrass(ctx);
   if (rc) return rc;
   return g1_table_msm(ctx, (const uint32_t*)d_scalars, n, resident_form(ctx, n), out_xy);
+}
+
+// The same over scalars of a declared width (g1_short_table_msm): whatever the last set-bases call left resident serves.
+int g1_msm_fixed_base_short_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n, uint32_t sbytes, uint32_t bits, uint8_t out_xy[96]) {
+  if (!out_xy) return MSM377_EINVAL;
+  int rc = check_args(ctx, nullptr, d_scalars, n, false);
+  if (rc == MSM377_OK) rc = check_short_args(ctx, sbytes, bits);
+  if (rc) return rc;
+  if (n > ctx->resident.n) {
+    ctx->err = "fixed-base MSM needs g1_set_bases with at least n points first";
+    return MSM377_ESTATE;
+  }
+  if (n == 0) {
+    identity_wire(out_xy);
+    return MSM377_OK;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (ctx->timing == 1) {  // no conversion in this mode
+    (void)hipEventRecord(ctx->ev[MSM377_STAGE_CONVERT][0], ctx->stream);
+    (void)hipEventRecord(ctx->ev[MSM377_STAGE_CONVERT][1], ctx->stream);
+  }
+  // (records 0 .. n-1 of a GLV table are the plain points: the short path reads those and never the phi half)
+  auto form = [&] { return ctx->resident.form == TABLE_XYZZ_GLV ? (int)TABLE_XYZZ : ctx->resident.form; };
+  rc = g1_short_table_msm(ctx, d_scalars, n, form(), sbytes, bits, out_xy);
+  if (rc != RC_TE_FALLBACK) return rc;
+  rc = resident_table_to_weierstrass(ctx);
+  if (rc) return rc;
+  return g1_short_table_msm(ctx, d_scalars, n, form(), sbytes, bits, out_xy);
 }
 
 // `batch` MSMs of n scalars each against the table resident in (or lent to, twin_borrow) `ctx`, on ctx's own stream and

@@ -55,3 +55,18 @@ def readBigIntsFromBufferLE(buffer: bytes, bigIntSize: int = 256) -> List[int]:
     step = bigIntSize // 8
     buf = bytes(buffer)
     return [int.from_bytes(buf[i : i + step], "little") for i in range(0, len(buf) - step + 1, step)]
+
+
+def encode_scalars(scalars: Iterable[int], scalar_bytes: int = 32) -> bytes:
+    """Scalars as the engine reads them: little-endian integers of ``scalar_bytes`` bytes each -- 32 for the harness's
+    wire format (the default), 4, 8 or 16 for the short-scalar entry points (include/msm377.h).  A value that is negative
+    or does not fit the stride raises ValueError."""
+    if scalar_bytes not in (4, 8, 16, 32):
+        raise ValueError("scalar_bytes must be 4, 8, 16 or 32")
+    out = bytearray()
+    for k in scalars:
+        k = int(k)
+        if k < 0 or k >> (8 * scalar_bytes):
+            raise ValueError("scalar %d does not fit %d bytes" % (k, scalar_bytes))
+        out += k.to_bytes(scalar_bytes, "little")
+    return bytes(out)

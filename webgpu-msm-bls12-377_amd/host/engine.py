@@ -156,6 +156,13 @@ def load_library():
         "msm377_ed_check_points_host": (i32, [u8p, u64, u32, vp]),
         "msm377_ctx_set_base_checks": (i32, [vp, u32]),
         "msm377_ctx_get_last_check": (i32, [vp, vp]),
+        "msm377_g1_msm_short": (i32, [vp, u8p, u8p, u64, u32, u32, vp]),
+        "msm377_g1_msm_short_device": (i32, [vp, vp, vp, u64, u32, u32, vp]),
+        "msm377_g1_msm_fixed_base_short_device": (i32, [vp, vp, u64, u32, u32, vp]),
+        "msm377_scalars_width_device": (i32, [vp, vp, u64, u32, ctypes.POINTER(u32)]),
+        "msm377_scalars_width_host": (i32, [u8p, u64, u32, ctypes.POINTER(u32)]),
+        "msm377_short_windows": (u32, [u32, u32]),
+        "msm377_ctx_get_last_geometry": (i32, [vp, ctypes.POINTER(u32), ctypes.POINTER(u32)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
@@ -192,6 +199,24 @@ def check_points_host(points: bytes, flags: int = CHECK_ALL) -> CheckReport:
 def ed_check_points_host(points: bytes, flags: int = CHECK_ALL) -> CheckReport:
     """The same for Edwards-BLS12 wire points, 64 bytes each (msm377_ed_check_points_host)."""
     return _check_host("msm377_ed_check_points_host", points, 64, flags)
+
+
+def scalars_width_host(scalars: bytes, scalar_bytes: int = 32) -> int:
+    """Largest bit length among little-endian scalars of ``scalar_bytes`` bytes each (msm377_scalars_width_host; 0 for
+    all-zero scalars and for an empty buffer): what a short-scalar call takes as ``scalar_bits``.  No device."""
+    if scalar_bytes in (4, 8, 16, 32) and len(scalars) % scalar_bytes:
+        raise ValueError("scalars buffer length must be a multiple of %d" % scalar_bytes)
+    lib = load_library()
+    bits = ctypes.c_uint32()
+    rc = lib.msm377_scalars_width_host(bytes(scalars), len(scalars) // max(1, int(scalar_bytes)), int(scalar_bytes), ctypes.byref(bits))
+    if rc:
+        raise MsmError(rc, "msm377_scalars_width_host")
+    return int(bits.value)
+
+
+def short_windows(scalar_bits: int, bucket_log: int) -> int:
+    """Window slots of a short-scalar call: floor(scalar_bits / (bucket_log + 1)) + 1 (msm377_short_windows)."""
+    return int(load_library().msm377_short_windows(int(scalar_bits), int(bucket_log)))
 
 
 def combine_partials_bytes(partials: bytes, num_windows: int = NUM_WINDOWS) -> bytes:
@@ -312,6 +337,47 @@ class MsmEngine:
         out = ctypes.create_string_buffer(96)
         self._check(self._lib.msm377_g1_msm_device(self._ctx, d_points, d_scalars, int(n), ctypes.addressof(out)), "msm377_g1_msm_device")
         return out.raw
+
+    # -- short scalars (include/msm377.h): n x scalar_bytes little-endian bytes, every scalar below 2^scalar_bits --
+    def msm_short(self, points: bytes, scalars: bytes, scalar_bytes: int, scalar_bits: int) -> bytes:
+        """compute_msm on host buffers with compact scalars of a declared width: floor(bits / (L + 1)) + 1 windows
+        instead of 16 or 22.  MsmError(ESCALAR) if a scalar is 2^scalar_bits or more."""
+        n = len(scalars) // scalar_bytes if scalar_bytes in (4, 8, 16, 32) and len(scalars) % scalar_bytes == 0 else len(points) // 96
+        if scalar_bytes in (4, 8, 16, 32) and len(points) != 96 * n:
+            raise ValueError("points buffer must hold %d bytes (96 per scalar), got %d" % (96 * n, len(points)))
+        out = ctypes.create_string_buffer(96)
+        self._check(self._lib.msm377_g1_msm_short(self._ctx, bytes(points), bytes(scalars), n, int(scalar_bytes), int(scalar_bits), ctypes.addressof(out)), "msm377_g1_msm_short")
+        return out.raw
+
+    def msm_short_device(self, d_points: int, d_scalars: int, n: int, scalar_bytes: int, scalar_bits: int, out=None) -> bytes:
+        """The same with inputs in HBM.  ``out``: an optional 96-byte ctypes buffer of the caller's (left untouched on error)."""
+        out = ctypes.create_string_buffer(96) if out is None else out
+        self._check(
+            self._lib.msm377_g1_msm_short_device(self._ctx, d_points, d_scalars, int(n), int(scalar_bytes), int(scalar_bits), ctypes.addressof(out)),
+            "msm377_g1_msm_short_device",
+        )
+        return out.raw
+
+    def msm_fixed_base_short_device(self, d_scalars: int, n: int, scalar_bytes: int, scalar_bits: int) -> bytes:
+        """Short scalars against the resident bases of the last set_bases* call (any of them)."""
+        out = ctypes.create_string_buffer(96)
+        self._check(
+            self._lib.msm377_g1_msm_fixed_base_short_device(self._ctx, d_scalars, int(n), int(scalar_bytes), int(scalar_bits), ctypes.addressof(out)),
+            "msm377_g1_msm_fixed_base_short_device",
+        )
+        return out.raw
+
+    def scalars_width_device(self, d_scalars: int, n: int, scalar_bytes: int = 32) -> int:
+        """Largest bit length among n scalars in HBM (msm377_scalars_width_device), 0 if all are zero."""
+        bits = ctypes.c_uint32()
+        self._check(self._lib.msm377_scalars_width_device(self._ctx, d_scalars, int(n), int(scalar_bytes), ctypes.byref(bits)), "msm377_scalars_width_device")
+        return int(bits.value)
+
+    def last_geometry(self) -> Tuple[int, int]:
+        """(window slots, bucket_log) of the last G1 MSM call's last pass (msm377_ctx_get_last_geometry)."""
+        w, log = ctypes.c_uint32(), ctypes.c_uint32()
+        self._check(self._lib.msm377_ctx_get_last_geometry(self._ctx, ctypes.byref(w), ctypes.byref(log)), "msm377_ctx_get_last_geometry")
+        return int(w.value), int(log.value)
 
     def set_bases(self, points: bytes):
         if len(points) % 96:

@@ -11,7 +11,7 @@ Python mirror used by the parity tests and bench.py.  Both call the C ABI (inclu
 """
 from typing import Dict, Optional, Sequence, Union
 
-from .codecs import bigIntsToBufferLE, u32ArrayToBigInts
+from .codecs import bigIntsToBufferLE, encode_scalars, u32ArrayToBigInts
 from .engine import MsmEngine
 
 _ENGINE: Optional[MsmEngine] = None
@@ -69,8 +69,13 @@ def _engine_for(n: int) -> MsmEngine:
     return _ENGINE
 
 
-def compute_msm(baseAffinePoints, scalars, log_result: bool = True, force_recompile: bool = False) -> Dict[str, int]:
+def compute_msm(baseAffinePoints, scalars, log_result: bool = True, force_recompile: bool = False, scalar_bits: Optional[int] = None,
+                scalar_bytes: int = 32) -> Dict[str, int]:
     """Q = sum k_i P_i over BLS12-377 G1; returns affine {"x": int, "y": int}.
+
+    ``scalar_bits`` (None: the reference's call, unchanged): the caller declares that every scalar is below
+    2^scalar_bits and the engine runs the short-scalar path (MsmEngine.msm_short); a scalars Buffer then holds
+    ``scalar_bytes`` (4, 8, 16 or 32) little-endian bytes per scalar, integers are encoded at that stride.
 
     Same contract as the reference: input_size = len(scalars buffer) / 32, empty input gives
     {x: 0, y: 1} (submission.ts:91-95); errors raise (MsmError) instead of rejecting a Promise.
@@ -78,6 +83,20 @@ def compute_msm(baseAffinePoints, scalars, log_result: bool = True, force_recomp
     for gfx950, there is no runtime shader cache to defeat (shader_manager.ts:71-77).
     """
     del force_recompile
+    if scalar_bits is not None:
+        sbuf = bytes(scalars) if _is_buffer(scalars) else encode_scalars([_to_int(s) for s in scalars], scalar_bytes)
+        pbuf = points_to_buffer(baseAffinePoints)
+        if scalar_bytes not in (4, 8, 16, 32) or len(sbuf) % scalar_bytes:
+            raise ValueError("scalars buffer length must be a multiple of scalar_bytes (4, 8, 16 or 32)")
+        n = len(sbuf) // scalar_bytes
+        if n == 0:
+            result = {"x": 0, "y": 1}
+        else:
+            out = _engine_for(n).msm_short(pbuf, sbuf, scalar_bytes, scalar_bits)
+            result = {"x": int.from_bytes(out[:48], "little"), "y": int.from_bytes(out[48:], "little")}
+        if log_result:
+            print(result)
+        return result
     sbuf = scalars_to_buffer(scalars)
     pbuf = points_to_buffer(baseAffinePoints)
     if len(sbuf) % 32:

@@ -40,8 +40,21 @@ const scalarsToBuffer = (scalars) => {
   return Buffer.concat(Array.from(scalars, (s) => bigIntToBufferLE(toBigInt(s), 32)));
 };
 
+// Third argument: log_result as in the reference, or {scalarBytes, scalarBits, log_result?} -- the caller declares that
+// every scalar is below 2^scalarBits; a scalars Buffer then holds scalarBytes (4, 8, 16 or 32; default 32) little-endian
+// bytes per scalar and the engine runs floor(scalarBits / 16) + 1 windows instead of 16 (msm377_g1_msm_short).  Without
+// it the call is the reference's.
 const compute_msm = async (baseAffinePoints, scalars, log_result = true, force_recompile = false) => {
   void force_recompile; // kernels are compiled ahead of time for gfx950; nothing to recompile
+  if (log_result !== null && typeof log_result === 'object') {
+    const { scalarBytes = 32, scalarBits, log_result: log = false } = log_result;
+    const sBuf = Buffer.isBuffer(scalars) ? scalars : Buffer.concat(Array.from(scalars, (s) => bigIntToBufferLE(toBigInt(s), scalarBytes)));
+    if (sBuf.length === 0) return { x: BigInt(0), y: BigInt(1) };
+    const o = addon.computeMsmShortSync(pointsToBuffer(baseAffinePoints), sBuf, scalarBytes, scalarBits);
+    const rs = { x: leBufferToBigInt(o.slice(0, 48)), y: leBufferToBigInt(o.slice(48, 96)) };
+    if (log) console.log(rs);
+    return rs;
+  }
   const scalarsBuf = scalarsToBuffer(scalars);
   const input_size = scalarsBuf.length / 32;
   if (input_size === 0) {

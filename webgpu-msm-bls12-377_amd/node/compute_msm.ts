@@ -69,13 +69,37 @@ export const scalarsToBuffer = (
   );
 };
 
+// Declared scalar width (msm377_g1_msm_short): every scalar is below 2^scalarBits; a scalars Buffer holds scalarBytes
+// (4, 8, 16 or 32; default 32) little-endian bytes per scalar.
+export interface ShortScalars {
+  scalarBytes?: 4 | 8 | 16 | 32;
+  scalarBits: number;
+  log_result?: boolean;
+}
+
+// Third argument: log_result as in the reference, or a ShortScalars object; without one the call is the reference's.
 export const compute_msm = async (
   baseAffinePoints: BigIntPoint[] | U32ArrayPoint[] | Buffer,
   scalars: bigint[] | Uint32Array[] | Buffer,
-  log_result = true,
+  log_result: boolean | ShortScalars = true,
   force_recompile = false,
 ): Promise<{ x: bigint; y: bigint }> => {
   void force_recompile; // kernels are compiled ahead of time for gfx950
+  if (log_result !== null && typeof log_result === 'object') {
+    const { scalarBytes = 32, scalarBits, log_result: log = false } = log_result;
+    const sBuf = Buffer.isBuffer(scalars)
+      ? scalars
+      : Buffer.concat((scalars as (bigint | Uint32Array)[]).map((s) => bigIntToBufferLE(toBigInt(s), scalarBytes)));
+    if (sBuf.length === 0) {
+      return { x: BigInt(0), y: BigInt(1) };
+    }
+    const o: Buffer = addon.computeMsmShortSync(pointsToBuffer(baseAffinePoints), sBuf, scalarBytes, scalarBits);
+    const rs = { x: leBufferToBigInt(o.subarray(0, 48) as Buffer), y: leBufferToBigInt(o.subarray(48, 96) as Buffer) };
+    if (log) {
+      console.log(rs);
+    }
+    return rs;
+  }
   const scalarsBuf = scalarsToBuffer(scalars);
   const input_size = scalarsBuf.length / 32;
 

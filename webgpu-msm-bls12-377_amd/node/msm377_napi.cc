@@ -8,6 +8,8 @@
 // in JS):
 //   computeMsm(points: Buffer, scalars: Buffer): Promise<Buffer>   96-byte x||y, runs off the JS thread
 //   computeMsmSync(points: Buffer, scalars: Buffer): Buffer
+//   computeMsmShortSync(points: Buffer 96n, scalars: Buffer scalarBytes x n, scalarBytes, scalarBits): Buffer
+//                                                                      compact scalars below 2^scalarBits (msm377_g1_msm_short)
 //   computeEdMsmSync(points: Buffer 64n, scalars: Buffer 32n): Buffer   the Edwards-BLS12 twin (msm377_ed_msm), 64-byte x||y
 //   setBasesSync(points: Buffer 96n): void                             fixed-base batches: keep a converted base set in HBM ...
 //   fixedBaseMsmSync(scalars: Buffer 32n): Buffer                      ... and run MSMs of n <= its size against it
@@ -92,6 +94,48 @@ napi_value ComputeMsmSync(napi_env env, napi_callback_info info) {
   uint8_t out[96];
   std::string err;
   if (run(p, s, sl / 32, out, &err)) {
+    napi_throw_error(env, nullptr, err.c_str());
+    return nullptr;
+  }
+  napi_value buf;
+  void* data;
+  napi_create_buffer_copy(env, 96, out, &data, &buf);
+  return buf;
+}
+
+// computeMsmShortSync(points, scalars, scalarBytes, scalarBits): compact scalars of a declared width (msm377_g1_msm_short)
+napi_value ComputeMsmShortSync(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  bool pb = false, sb = false;
+  uint32_t sbytes = 0, sbits = 0;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 4 || napi_is_buffer(env, argv[0], &pb) != napi_ok || !pb ||
+      napi_is_buffer(env, argv[1], &sb) != napi_ok || !sb || napi_get_value_uint32(env, argv[2], &sbytes) != napi_ok ||
+      napi_get_value_uint32(env, argv[3], &sbits) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "expected (points: Buffer, scalars: Buffer, scalarBytes: number, scalarBits: number)");
+    return nullptr;
+  }
+  uint8_t *p, *s;
+  size_t pl, sl;
+  napi_get_buffer_info(env, argv[0], reinterpret_cast<void**>(&p), &pl);
+  napi_get_buffer_info(env, argv[1], reinterpret_cast<void**>(&s), &sl);
+  if ((sbytes != 4 && sbytes != 8 && sbytes != 16 && sbytes != 32) || sl % sbytes != 0 || pl != (sl / sbytes) * 96) {
+    napi_throw_range_error(env, nullptr, "scalarBytes must be 4, 8, 16 or 32; points must hold 96 bytes and scalars scalarBytes bytes per input");
+    return nullptr;
+  }
+  const uint64_t n = sl / sbytes;
+  uint8_t out[96];
+  std::string err;
+  int rc;
+  {
+    std::lock_guard<std::mutex> lock(g_mu);
+    rc = ensure_ctx(n ? n : 1, &err);
+    if (!rc) {
+      rc = msm377_g1_msm_short(g_ctx, p, s, n, sbytes, sbits, out);
+      if (rc) err = std::string("msm377_g1_msm_short: ") + msm377_strerror(rc) + ": " + msm377_last_error(g_ctx);
+    }
+  }
+  if (rc) {
     napi_throw_error(env, nullptr, err.c_str());
     return nullptr;
   }
@@ -307,6 +351,7 @@ napi_value Init(napi_env env, napi_value exports) {
   napi_property_descriptor props[] = {
       {"computeMsm", nullptr, ComputeMsm, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"computeMsmSync", nullptr, ComputeMsmSync, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"computeMsmShortSync", nullptr, ComputeMsmShortSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"computeEdMsmSync", nullptr, ComputeEdMsmSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"setBasesSync", nullptr, SetBasesSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"fixedBaseMsmSync", nullptr, FixedBaseMsmSync, nullptr, nullptr, nullptr, napi_default, nullptr},
