@@ -224,6 +224,55 @@ uint32_t msm377_short_windows(uint32_t scalar_bits, uint32_t bucket_log);
  * (1, 19) on the 20-bit table, (5, 15) for a 64-bit short call; (0, 0) before the first call. */
 int msm377_ctx_get_last_geometry(const msm377_ctx* ctx, uint32_t* windows, uint32_t* bucket_log);
 
+/* ---- native input forms ---------------------------------------------------------------------
+ * A prover built on arkworks or snarkVM keeps nothing in the wire format above: field elements live in Montgomery form
+ * (a G1 coordinate as x * 2^384 mod p in six little-endian u64 limbs, a scalar as s * 2^256 mod r in four), and an affine
+ * point carries an infinity flag (x, y and one flag byte, padded to 104 bytes).  A context can be told to read those
+ * forms directly: an import pass on the GPU (csrc/kernels/import.hpp) writes wire-format data into the context's staging
+ * and the pipeline runs unchanged behind it.  The default is (WIRE, WIRE): nothing is launched or allocated that was
+ * not before.  Results stay in the wire format (msm377_g1_result_to_native converts one).
+ *
+ *   MSM377_POINTS_MONT       a coordinate value v means v * 2^-384 mod p.  Values of p or more are trusted not to occur,
+ *                            as in the wire format: such a point is handed on as its bytes are, the MSM calls compute a
+ *                            meaningless result from it and only the check calls classify it (non-canonical).
+ *   MSM377_POINTS_MONT_FLAG  the same with a flag byte behind the coordinates.  A point whose flag byte is non-zero is
+ *                            the identity: its 96 coordinate bytes are never interpreted and may hold anything, and it
+ *                            contributes nothing to any sum.  Device pointers stay 16-byte aligned; single records are
+ *                            8-byte aligned.
+ *   MSM377_SCALARS_MONT      every 32-byte value v is accepted and means v * 2^-256 mod r, fully reduced, so a call with
+ *                            this form never returns MSM377_ESCALAR.
+ *
+ * Honoured by (all G1): msm377_g1_msm(_device), the four msm377_g1_set_bases* calls, msm377_g1_msm_fixed_base(_device),
+ * msm377_g1_msm_fixed_base_batch_device, msm377_g1_window_partials_device / _resident, msm377_g1_glv_window_partials_device;
+ * with the point form only: msm377_g1_check_points(_device) and the short-scalar calls.  The identity points of a
+ * resident base set are remembered with it (every fixed-base call, whatever its scalar form, leaves them out) and dropped
+ * with it by the next set-bases call.  Check calls: the canonical test compares the Montgomery value the caller wrote
+ * with p, the curve and subgroup tests see the imported point, flagged points are counted in no class and are never
+ * first_bad, `checked` stays n; msm377_ctx_set_base_checks accepts flagged points likewise.
+ * Host-buffer calls in a native form upload each array in one piece into a device buffer allocated with the first such
+ * call (104 + 32 bytes per point of capacity), import from there and continue on the device-pointer path: no chunked
+ * overlap of upload and computation, as for msm377_g1_msm_short.
+ * Not covered: a short-scalar call while MSM377_SCALARS_MONT is set is MSM377_EINVAL (a compact Montgomery scalar does
+ * not exist); the Edwards-BLS12 calls (msm377_ed_*) return MSM377_EINVAL while any non-wire form is set;
+ * msm377_g1_generate_bases_device keeps writing the wire format. */
+#define MSM377_POINTS_WIRE      0  /* 96 B: x || y canonical (the wire format above, the default) */
+#define MSM377_POINTS_MONT      1  /* 96 B: x*2^384 mod p || y*2^384 mod p, little-endian */
+#define MSM377_POINTS_MONT_FLAG 2  /* 104 B: as MONT, then one byte (0 = finite, non-zero = identity), 7 bytes ignored */
+#define MSM377_SCALARS_WIRE     0  /* 32 B canonical little-endian (the wire format above, the default) */
+#define MSM377_SCALARS_MONT     1  /* 32 B: s*2^256 mod r, little-endian */
+/* An unknown value: MSM377_EINVAL, and the forms stay as they were. */
+int msm377_ctx_set_input_format(msm377_ctx* ctx, uint32_t point_form, uint32_t scalar_form);
+int msm377_ctx_get_input_format(const msm377_ctx* ctx, uint32_t* point_form, uint32_t* scalar_form);
+/* The same conversions on the calling thread: no context, no device.  For callers that want wire data, and as the
+ * yardstick of the GPU pass: a second implementation that shares no field code with it.  out_wire: n x 96 (n x 32) bytes;
+ * out_inf_mask (may be NULL): ceil(n / 32) words, bit i % 32 of word i / 32 set for a flagged point, whose record is the
+ * generator's.  in and out_wire may be the same buffer for the 96-byte forms.  A form outside the list: MSM377_EINVAL. */
+int msm377_g1_import_points_host(const uint8_t* in, uint64_t n, uint32_t point_form, uint8_t* out_wire, uint32_t* out_inf_mask);
+int msm377_import_scalars_host(const uint8_t* in, uint64_t n, uint32_t scalar_form, uint8_t* out_wire);
+/* A wire result as a MSM377_POINTS_MONT_FLAG record: Montgomery x, y, the flag, seven zero bytes; the wire identity
+ * (0, 1) sets the flag.  MSM377_EINVAL for a coordinate that is not below p. */
+int msm377_g1_result_to_native(const uint8_t xy[96], uint8_t out[104]);
+
 /* Synthetic inputs: P_i = [a_i]G, a_i the i-th SplitMix64(seed)
  * output, written in wire format to device memory d_points_out (n x 96 bytes). */
 int msm377_g1_generate_bases_device(msm377_ctx* ctx, uint64_t seed, uint64_t n, void* d_points_out);

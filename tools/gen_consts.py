@@ -53,7 +53,7 @@ def redundant(v, n, w):
     return c
 
 
-def emit(ns, mod, n, extra, rs=None, lazy=False):
+def emit(ns, mod, n, extra, rs=None, lazy=False, tail=""):
     rs = rs or n
     R = 1 << (LB * rs)
     assert mod & MASK == 1
@@ -78,6 +78,7 @@ def emit(ns, mod, n, extra, rs=None, lazy=False):
     words = ", ".join("0x%08xu" % (((mod - 2) >> (32 * i)) & 0xffffffff) for i in range(nw))
     out += "static constexpr int PM2_NW = %d;\n" % nw
     out += "static constexpr uint32_t PM2_W[%d] = {%s};  // p - 2, LE u32 words (Fermat inversion)\n" % (nw, words)
+    out += tail
     out += "};\n\n"
     return out
 
@@ -245,11 +246,21 @@ def main():
                 "TE_SBR": s_ * GLV_BETA * R29, "TE_CSBR": c_ * s_ * GLV_BETA * R29,
                 # k_check_curve: (x^3 - y^2) / R^2 of a point on the curve, as a PLAIN residue (the entry is -R^-3, and the
                 # table stores entry * R): the curve test works on the raw wire coordinates, no conversion
-                "CHK_RHS_RAW": -pow(R29, -3, P)}
-    s += emit("G1Consts", P, 13, g1_extra, rs=14, lazy=True)
+                "CHK_RHS_RAW": -pow(R29, -3, P),
+                # k_import_points (kernels/import.hpp): a coordinate in the callers' Montgomery form, v = x 2^384, times
+                # this entry is x -- the table stores entry * R, the plain integer 2^(406 - 384)
+                "IMPORT_MONT384": pow(2, -384, P)}
+    assert g1_extra["IMPORT_MONT384"] * R29 % P == 1 << 22
+    # the generator as a wire record (x || y, canonical, LE u32 words): what k_import_points writes for a flagged point
+    gen_wire = ", ".join("0x%08xu" % ((v >> (32 * i)) & 0xFFFFFFFF) for v in (GX, GY) for i in range(12))
+    g1_tail = "static constexpr uint32_t GEN_WIRE[24] = {%s};  // generator, wire format\n" % gen_wire
+    s += emit("G1Consts", P, 13, g1_extra, rs=14, lazy=True, tail=g1_tail)
     s += emit_glv()
     # Fq keeps R = 2^261 (9 steps): q is 253 bits, so the radix already leaves 8 bits of slack for the lazy forms
-    s += emit("EdConsts", Q, 9, {"ED_D": ED_D, "ED_2D": 2 * ED_D, "GEN_X": ED_GX, "GEN_Y": ED_GY, "TE_2D": 2 * ED_D}, lazy=True)
+    s += emit("EdConsts", Q, 9, {"ED_D": ED_D, "ED_2D": 2 * ED_D, "GEN_X": ED_GX, "GEN_Y": ED_GY, "TE_2D": 2 * ED_D,
+                                   # k_import_scalars: a scalar in Montgomery form, v = s 2^256, times this entry is s (stored: 2^5)
+                                   "IMPORT_MONT256": pow(2, -256, Q)}, lazy=True)
+    assert pow(2, -256, Q) * (1 << 261) % Q == 32
     # TO29: a host-format residue (radix 2^384) times this constant is the DEVICE Montgomery form (radix 2^406) as a plain
     # integer -- the way back for the block inverses of the batched affine conversion (msm377.hip affine_convert_finish)
     s += emit64("G1Consts64", P, 6, 14, {"TE_2D": 2 * d_, "TE_INV_S": pow(s_, -1, P), "TE_C_OVER_S": c_ * pow(s_, -1, P), "TO29": 1 << (29 * 14 - 64 * 6)})

@@ -12,7 +12,11 @@ from .host.codecs import (  # noqa: F401
     bigIntsToBufferLE,
     bigIntsToU32Array,
     bigIntToU32Array,
+    decode_points_native,
+    decode_scalars_native,
+    encode_points_native,
     encode_scalars,
+    encode_scalars_native,
     readBigIntsFromBufferLE,
     u32ArrayToBigInts,
 )
@@ -26,8 +30,11 @@ from .host.engine import (  # noqa: F401
     MsmError,
     check_points_host,
     ed_check_points_host,
+    import_points_host,
+    import_scalars_host,
     library_path,
     load_library,
+    result_to_native,
     scalars_width_host,
     short_windows,
 )
@@ -49,6 +56,13 @@ __all__ = [
     "scalars_width_host",
     "short_windows",
     "encode_scalars",
+    "encode_points_native",
+    "decode_points_native",
+    "encode_scalars_native",
+    "decode_scalars_native",
+    "import_points_host",
+    "import_scalars_host",
+    "result_to_native",
     "library_path",
     "windows_for_rank",
     "combine_partials",

@@ -30,9 +30,15 @@ struct ResidentBases {
   uint32_t* table = nullptr;
   uint64_t cap = 0;
   uint32_t windows = 0;        // 16 (c = 16), or WIDE_WINDOWS (c = 20: six 20-bit + seven 19-bit windows)
+  // Identity points of a set that came in with infinity flags (MSM377_POINTS_MONT_FLAG): their records hold the generator,
+  // and every fixed-base call zeroes their scalars through the mask (kernels/import.hpp).  flagged == 0: nothing to do.
+  uint32_t flagged = 0;
+  const uint32_t* inf_mask = nullptr;  // the owner's d_inf_mask: bit i mod 32 of word i / 32
   bool valid() const { return n != 0; }
-  void clear() { n = 0; }
-  void set(uint32_t* records, uint64_t count, int table_form) { bases = records; n = count; form = table_form; }
+  void clear() { n = 0; flagged = 0; }
+  void set(uint32_t* records, uint64_t count, int table_form, uint32_t flagged_points = 0, const uint32_t* mask = nullptr) {
+    bases = records; n = count; form = table_form; flagged = flagged_points; inf_mask = mask;
+  }
 };
 
 // Work buffers of the 20-bit-window sort (kernels/wide.hpp) for up to `cap` points.
@@ -73,6 +79,12 @@ struct msm377_ctx {
   uint32_t* d_row_ovf_base = nullptr; // 16 x NB
   uint32_t* d_split_rows = nullptr;   // 16 x NB
   uint32_t* d_ovf = nullptr;          // overflow partial points, 52 words each (<= 16 cap / SEG)
+  // Native input forms (msm377_ctx_set_input_format): the import pass (kernels/import.hpp) writes wire-format data into
+  // d_raw_points / d_raw_scalars and the pipeline runs unchanged behind it.  All three allocated on first use.
+  uint32_t point_form = MSM377_POINTS_WIRE, scalar_form = MSM377_SCALARS_WIRE;
+  uint8_t* d_native = nullptr;        // host-buffer calls in a native form: cap x 104 bytes of points, then cap x 32 of scalars
+  uint32_t* d_inf_mask = nullptr;     // two infinity masks (the one that travels with d_raw_points; the check calls' scratch), then their counters
+  hipEvent_t import_done = nullptr;   // the side stream waits for it before it reads imported points
   ResidentBases resident;             // fixed-base mode: the bases of the last successful msm377_g1_set_bases* call
   WideBuffers wide;                   // the 20-bit-window sort's buffers (allocated with such a table; the twin's own set)
   int precomp_bits = MSM377_WINDOW_BITS;  // window width msm377_g1_set_bases_precomputed builds its next table for: 16 or 20 (msm377_ctx_set_precompute_window, MSM377_PRECOMP_BITS)

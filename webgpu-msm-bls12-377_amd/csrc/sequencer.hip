@@ -14,6 +14,8 @@
 //   kernels/reduce.hpp      k_tree_step / k_tree_step_quad / k_reduce_tail / k_gather_partials
 //                           bucket reduction, log-depth bit planes     wgsl/cuzk/bpr.template.wgsl:69-173; models cuzk/bpr.ts:5-126
 //   host_tail.hip           Horner over windows + one inversion        submission.ts:290-321
+// In front of all of it, only while msm377_ctx_set_input_format names a native form: kernels/import.hpp k_import_points /
+// k_import_scalars (Montgomery coordinates and scalars, infinity flags -> wire records in d_raw_points / d_raw_scalars).
 // The kernels are templates over a curve policy (curves.hpp): TeDev (default: G1 in twisted Edwards form, te377.hpp -- 7 field
 // products per bucket addition on affine base records (TeAffBase), 8 on projective ones, unified law, exceptional cases
 // detected and rerun), G1Dev (G1 in Weierstrass XYZZ coordinates, g1_xyzz.hpp: the fallback, the GLV front end, the
@@ -43,6 +45,7 @@
 #include "kernels/reduce.hpp"
 #include "kernels/sort.hpp"
 #include "kernels/validate.hpp"
+#include "kernels/import.hpp"
 #include "kernels/wide.hpp"
 
 bool WideBuffers::ensure(uint64_t n) {
@@ -787,11 +790,13 @@ int g1_table_msm(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n, int for
 int resident_table_to_weierstrass(msm377_ctx* ctx) {
   const int form = TABLE_XYZZ;  // points outside the prime-order subgroup: never the GLV front end
   const uint64_t n = ctx->resident.n;
+  const uint32_t flagged = ctx->resident.flagged;  // the mask describes the raw copy, whatever form its records take
+  const uint32_t* mask = ctx->resident.inf_mask;
   ctx->resident.clear();
   int rc = convert_table(ctx, ctx->d_raw_points, n, form);
   if (rc) return rc;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream2));
-  ctx->resident.set(ctx->d_bases, n, form);
+  ctx->resident.set(ctx->d_bases, n, form, flagged, mask);
   return MSM377_OK;
 }
 
@@ -1054,12 +1059,146 @@ int check_base_set(msm377_ctx* ctx, const void* d_points, uint64_t n) {
   return MSM377_EPOINT;
 }
 
+// ---- native input forms (include/msm377.h "native input forms"; kernels/import.hpp) ----
+// The import pass sits in front of the entry points: it writes wire-format data into the context's staging
+// (d_raw_points, d_raw_scalars) and the call goes on with those pointers.  With the default forms every function below
+// returns at once: no launch, no allocation, the caller's pointers.
+inline bool native_forms(const msm377_ctx* ctx) { return ctx->point_form != MSM377_POINTS_WIRE || ctx->scalar_form != MSM377_SCALARS_WIRE; }
+inline size_t point_stride(const msm377_ctx* ctx) { return ctx->point_form == MSM377_POINTS_MONT_FLAG ? 104 : 96; }
+inline size_t mask_words(const msm377_ctx* ctx) { return (size_t)(((ctx->cap + 31) / 32 + 3) & ~3ull); }
+enum { MASK_BASES = 0, MASK_CHECK = 1 };  // which of the two masks (and counters) in d_inf_mask
+inline uint8_t* native_points(const msm377_ctx* ctx) { return ctx->d_native; }
+inline uint8_t* native_scalars(const msm377_ctx* ctx) { return ctx->d_native + (((size_t)ctx->cap * 104 + 15) & ~(size_t)15); }
+
+int ensure_import_buffers(msm377_ctx* ctx, bool host_staging) {
+  if (!ctx->import_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->import_done, hipEventDisableTiming));
+  if (!ctx->d_inf_mask && hipMalloc((void**)&ctx->d_inf_mask, (2 * mask_words(ctx) + 4) * 4) != hipSuccess) {
+    ctx->d_inf_mask = nullptr;
+    (void)hipGetLastError();
+    ctx->err = "native input forms: out of device memory";
+    return MSM377_ENOMEM;
+  }
+  if (host_staging && !ctx->d_native && hipMalloc((void**)&ctx->d_native, (((size_t)ctx->cap * 104 + 15) & ~(size_t)15) + (size_t)ctx->cap * 32) != hipSuccess) {
+    ctx->d_native = nullptr;
+    (void)hipGetLastError();
+    ctx->err = "native input forms: out of device memory for the host-buffer staging";
+    return MSM377_ENOMEM;
+  }
+  return MSM377_OK;
+}
+
+// n points in the context's (non-wire) point form at d_in -> wire records at d_out, on the main stream; the side stream,
+// which converts them, is ordered behind.  `which`: the mask and counter the pass writes (the counter is cleared first).
+int import_points(msm377_ctx* ctx, const void* d_in, uint64_t n, uint32_t* d_out, int which) {
+  int rc = ensure_import_buffers(ctx, false);
+  if (rc) return rc;
+  uint32_t* mask = ctx->d_inf_mask + (size_t)which * mask_words(ctx);
+  uint32_t* count = ctx->d_inf_mask + 2 * mask_words(ctx) + which;
+  const dim3 grid((unsigned)((n + IMPORT_THREADS - 1) / IMPORT_THREADS)), block(IMPORT_THREADS);
+  if (ctx->point_form == MSM377_POINTS_MONT_FLAG) {
+    hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(256), 0, ctx->stream, count, 1u, (uint32_t*)nullptr, 0u);
+    hipLaunchKernelGGL(k_import_points<MSM377_POINTS_MONT_FLAG>, grid, block, 0, ctx->stream, (const uint8_t*)d_in, d_out, n, mask, count);
+  } else {
+    hipLaunchKernelGGL(k_import_points<MSM377_POINTS_MONT>, grid, block, 0, ctx->stream, (const uint8_t*)d_in, d_out, n, mask, count);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipEventRecord(ctx->import_done, ctx->stream));
+  HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream2, ctx->import_done, 0));
+  return MSM377_OK;
+}
+
+// The scalars of a call as the decomposition kernels read them: d_in itself for wire scalars without a mask (nothing is
+// launched), else ctx->d_raw_scalars, written on the main stream by k_import_scalars.  words: u32 per scalar (8; 1, 2
+// or 4 for compact short scalars, wire form only).  mask: the infinity mask of the call's points, or null.
+int import_scalars(msm377_ctx* ctx, const void* d_in, uint64_t n, uint32_t words, const uint32_t* mask, const uint32_t** d_out) {
+  *d_out = (const uint32_t*)d_in;
+  const bool mont = ctx->scalar_form == MSM377_SCALARS_MONT;
+  if ((!mont && !mask) || n == 0) return MSM377_OK;
+  const dim3 grid((unsigned)((n + IMPORT_THREADS - 1) / IMPORT_THREADS)), block(IMPORT_THREADS);
+  const uint32_t* in = (const uint32_t*)d_in;
+  uint32_t* out = ctx->d_raw_scalars;
+  if (mont && mask) hipLaunchKernelGGL((k_import_scalars<MSM377_SCALARS_MONT, true>), grid, block, 0, ctx->stream, in, out, n, words, mask);
+  else if (mont) hipLaunchKernelGGL((k_import_scalars<MSM377_SCALARS_MONT, false>), grid, block, 0, ctx->stream, in, out, n, words, mask);
+  else hipLaunchKernelGGL((k_import_scalars<MSM377_SCALARS_WIRE, true>), grid, block, 0, ctx->stream, in, out, n, words, mask);
+  HIP_TRY(ctx, hipGetLastError());
+  *d_out = out;
+  return MSM377_OK;
+}
+
+// Points and scalars of a per-call MSM: both pointers are replaced by the staging the pass wrote.  The caller has
+// dropped the resident bases (the pass overwrites their raw copy).
+int import_inputs(msm377_ctx* ctx, const void** d_points, const void** d_scalars, uint64_t n, uint32_t scalar_words = 8) {
+  if (!native_forms(ctx)) return MSM377_OK;
+  const uint32_t* mask = nullptr;
+  if (ctx->point_form != MSM377_POINTS_WIRE) {
+    const int rc = import_points(ctx, *d_points, n, ctx->d_raw_points, MASK_BASES);
+    if (rc) return rc;
+    *d_points = ctx->d_raw_points;
+    if (ctx->point_form == MSM377_POINTS_MONT_FLAG) mask = ctx->d_inf_mask;
+  }
+  const uint32_t* sc = nullptr;
+  const int rc = import_scalars(ctx, *d_scalars, n, scalar_words, mask, &sc);
+  *d_scalars = sc;
+  return rc;
+}
+
+// A base set: the points alone, and the number of flagged ones for the resident-base value (a host-side wait: the
+// set-bases calls wait for the device anyway).
+int import_base_set(msm377_ctx* ctx, const void** d_points, uint64_t n, uint32_t* flagged) {
+  *flagged = 0;
+  if (ctx->point_form == MSM377_POINTS_WIRE || n == 0) return MSM377_OK;
+  const int rc = import_points(ctx, *d_points, n, ctx->d_raw_points, MASK_BASES);
+  if (rc) return rc;
+  *d_points = ctx->d_raw_points;
+  if (ctx->point_form == MSM377_POINTS_MONT_FLAG) {
+    HIP_TRY(ctx, hipMemcpyAsync(flagged, ctx->d_inf_mask + 2 * mask_words(ctx) + MASK_BASES, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return MSM377_OK;
+}
+
+// Host-buffer calls in a native form: each array goes up in one piece into d_native (no chunked overlap), and the call
+// continues on the device-pointer path, which imports from there.  Either array may be absent.
+int upload_native(msm377_ctx* ctx, const uint8_t* points, size_t point_bytes, const uint8_t* scalars, size_t scalar_bytes) {
+  int rc = ensure_import_buffers(ctx, true);
+  if (rc == MSM377_OK && points && point_bytes) rc = h2d_staged(ctx, native_points(ctx), points, point_bytes, 0);
+  if (rc == MSM377_OK && scalars && scalar_bytes) rc = h2d_staged(ctx, native_scalars(ctx), scalars, scalar_bytes, 0);
+  return rc;
+}
+
+int refuse_mont_short(msm377_ctx* ctx) {
+  if (ctx->scalar_form != MSM377_SCALARS_MONT) return MSM377_OK;
+  ctx->err = "short-scalar calls take wire-format scalars: there is no compact Montgomery scalar (msm377_ctx_set_input_format)";
+  return MSM377_EINVAL;
+}
+
 }  // namespace
 
 // ---- entry points (C ABI: capi.hip forwards) ----
 
-int g1_check_points_device(msm377_ctx* ctx, const void* d_points, uint64_t n, uint32_t flags, msm377_check_report* out) { return check_points_device<G1Check>(ctx, d_points, n, flags, out); }
-int g1_check_points(msm377_ctx* ctx, const uint8_t* points, uint64_t n, uint32_t flags, msm377_check_report* out) { return check_points_from_host<G1Check>(ctx, points, n, flags, out); }
+// G1 points in a native form are imported into d_sort_temp first (as the host-buffer variant uploads there: it belongs to
+// no resident form), with the check calls' own mask: a coordinate of p or more arrives unchanged and is counted
+// non-canonical, a flagged point arrives as the generator and is counted in no class.
+int g1_check_points_device(msm377_ctx* ctx, const void* d_points, uint64_t n, uint32_t flags, msm377_check_report* out) {
+  if (ctx && ctx->point_form != MSM377_POINTS_WIRE && out && check_flags_normal(flags) && n) {
+    int rc = check_args(ctx, d_points, d_points, n, true);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    rc = import_points(ctx, d_points, n, (uint32_t*)ctx->d_sort_temp, MASK_CHECK);
+    if (rc) return rc;
+    d_points = ctx->d_sort_temp;
+  }
+  return check_points_device<G1Check>(ctx, d_points, n, flags, out);
+}
+int g1_check_points(msm377_ctx* ctx, const uint8_t* points, uint64_t n, uint32_t flags, msm377_check_report* out) {
+  if (ctx && ctx->point_form != MSM377_POINTS_WIRE && out && check_flags_normal(flags) && n && n <= ctx->cap && points) {
+    ctx->err.clear();
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int rc = upload_native(ctx, points, n * point_stride(ctx), nullptr, 0);
+    return rc ? rc : g1_check_points_device(ctx, native_points(ctx), n, flags, out);
+  }
+  return check_points_from_host<G1Check>(ctx, points, n, flags, out);
+}
 int ed_check_points_device(msm377_ctx* ctx, const void* d_points, uint64_t n, uint32_t flags, msm377_check_report* out) { return check_points_device<EdCheck>(ctx, d_points, n, flags, out); }
 int ed_check_points(msm377_ctx* ctx, const uint8_t* points, uint64_t n, uint32_t flags, msm377_check_report* out) { return check_points_from_host<EdCheck>(ctx, points, n, flags, out); }
 
@@ -1090,6 +1229,8 @@ int g1_msm_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, 
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   ctx->resident.clear();
+  rc = import_inputs(ctx, &d_points, &d_scalars, n);  // (native input forms only)
+  if (rc) return rc;
   int form = pick_form(ctx, n);
   // (Queueing the conversion after k_decompose instead was measured: decompose 77 -> 23 us, sort 272 -> 386 us.)
   if (form == TABLE_TE && ctx->te_affine_msm && n >= ctx->affine_min_points) {
@@ -1125,6 +1266,10 @@ int g1_msm(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint6
     return MSM377_OK;
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (native_forms(ctx)) {  // one upload per array, then the device-pointer path
+    const int up = upload_native(ctx, points, n * point_stride(ctx), scalars, n * 32);
+    return up ? up : g1_msm_device(ctx, native_points(ctx), native_scalars(ctx), n, out_xy);
+  }
   ctx->resident.clear();
   int form = pick_form(ctx, n);
   const uint32_t* d_sc = ctx->d_raw_scalars;
@@ -1187,6 +1332,7 @@ int g1_msm_short_device(msm377_ctx* ctx, const void* d_points, const void* d_sca
   if (!out_xy) return MSM377_EINVAL;
   int rc = check_args(ctx, d_points, d_scalars, n, true);
   if (rc == MSM377_OK) rc = check_short_args(ctx, sbytes, bits);
+  if (rc == MSM377_OK) rc = refuse_mont_short(ctx);
   if (rc) return rc;
   if (n == 0) {
     identity_wire(out_xy);
@@ -1194,6 +1340,8 @@ int g1_msm_short_device(msm377_ctx* ctx, const void* d_points, const void* d_sca
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   ctx->resident.clear();
+  rc = import_inputs(ctx, &d_points, &d_scalars, n, sbytes / 4);  // (native point forms only)
+  if (rc) return rc;
   int form = ctx->g1_form == 1 ? TABLE_TE : TABLE_XYZZ;  // never the GLV front end
   if (form == TABLE_TE && ctx->te_affine_msm && n >= ctx->affine_min_points) {  // per-call affine records, as in g1_msm_device
     form = TABLE_TE_AFFINE;
@@ -1224,12 +1372,17 @@ int g1_msm_short(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars,
     return MSM377_EINVAL;
   }
   int rc = check_short_args(ctx, sbytes, bits);
+  if (rc == MSM377_OK) rc = refuse_mont_short(ctx);
   if (rc) return rc;
   if (n == 0) {
     identity_wire(out_xy);
     return MSM377_OK;
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (native_forms(ctx)) {
+    rc = upload_native(ctx, points, n * point_stride(ctx), scalars, n * sbytes);
+    return rc ? rc : g1_msm_short_device(ctx, native_points(ctx), native_scalars(ctx), n, sbytes, bits, out_xy);
+  }
   ctx->resident.clear();
   const uint32_t* d_pt = ctx->d_raw_points;
   const bool te = ctx->g1_form == 1;
@@ -1381,12 +1534,22 @@ int free_table(msm377_ctx* ctx) {
 
 // The four set-bases entry points clear the resident bases before anything else and set them as their last step: a
 // call that fails, for whatever reason, leaves none (include/msm377.h).
+static int build_bases(msm377_ctx* ctx, const void* d_points, uint64_t n, uint32_t flagged);
 int g1_set_bases_device(msm377_ctx* ctx, const void* d_points, uint64_t n) {
   if (ctx) ctx->resident.clear();
   int rc = check_args(ctx, d_points, d_points, n, true);
   if (rc) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  rc = check_base_set(ctx, d_points, n);  // opt-in (msm377_ctx_set_base_checks)
+  uint32_t flagged = 0;
+  rc = import_base_set(ctx, &d_points, n, &flagged);  // (native point forms only)
+  if (rc) return rc;
+  return build_bases(ctx, d_points, n, flagged);
+}
+
+// d_points: wire records (the caller's, or d_raw_points after an upload or an import); flagged: how many of them stand
+// in for identity points, ctx->d_inf_mask says which.
+static int build_bases(msm377_ctx* ctx, const void* d_points, uint64_t n, uint32_t flagged) {
+  int rc = check_base_set(ctx, d_points, n);  // opt-in (msm377_ctx_set_base_checks)
   if (rc) return rc;
   int form = pick_form(ctx, n);
   if (form == TABLE_TE) form = TABLE_TE_AFFINE;  // resident: affine records by the batched inversion, once
@@ -1400,7 +1563,7 @@ int g1_set_bases_device(msm377_ctx* ctx, const void* d_points, uint64_t n) {
     rc = free_table(ctx);
     if (rc) return rc;
   }
-  ctx->resident.set(ctx->d_bases, n, form);
+  ctx->resident.set(ctx->d_bases, n, form, flagged, ctx->d_inf_mask);
   return MSM377_OK;
 }
 
@@ -1409,6 +1572,10 @@ static int set_bases_from_host(msm377_ctx* ctx, const uint8_t* points, uint64_t 
   if (ctx) ctx->resident.clear();
   if (!ctx || n > ctx->cap || (n && !points)) return MSM377_EINVAL;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (ctx->point_form != MSM377_POINTS_WIRE) {  // the native records go up as they are; the device variant imports them
+    const int up = upload_native(ctx, points, n * point_stride(ctx), nullptr, 0);
+    return up ? up : build(ctx, native_points(ctx), n);
+  }
   int rc = h2d_staged(ctx, ctx->d_raw_points, points, n * 96, 0);
   return rc ? rc : build(ctx, ctx->d_raw_points, n);
 }
@@ -1427,7 +1594,10 @@ int g1_set_bases_precomputed_device(msm377_ctx* ctx, const void* d_points, uint6
   int rc = check_args(ctx, d_points, d_points, n, true);
   if (rc) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (ctx->g1_form != 1 || n == 0) return g1_set_bases_device(ctx, d_points, n);  // Weierstrass form: no precomputation
+  uint32_t flagged = 0;
+  rc = import_base_set(ctx, &d_points, n, &flagged);  // (native point forms only)
+  if (rc) return rc;
+  if (ctx->g1_form != 1 || n == 0) return build_bases(ctx, d_points, n, flagged);  // Weierstrass form: no precomputation
   rc = check_base_set(ctx, d_points, n);  // opt-in (msm377_ctx_set_base_checks), before anything is allocated or converted
   if (rc) return rc;
   const bool wide = ctx->precomp_bits == (int)WIDE_BITS;
@@ -1458,7 +1628,7 @@ int g1_set_bases_precomputed_device(msm377_ctx* ctx, const void* d_points, uint6
   if (rc) return rc;
   if (d_points != ctx->d_raw_points) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_raw_points, d_points, n * 96, hipMemcpyDeviceToDevice, ctx->stream2));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream2));
-  r.set(ctx->d_bases, n, TABLE_TE_PRECOMP);
+  r.set(ctx->d_bases, n, TABLE_TE_PRECOMP, flagged, ctx->d_inf_mask);
   return MSM377_OK;
 }
 
@@ -1483,11 +1653,14 @@ int g1_msm_fixed_base_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n,
     (void)hipEventRecord(ctx->ev[MSM377_STAGE_CONVERT][0], ctx->stream);
     (void)hipEventRecord(ctx->ev[MSM377_STAGE_CONVERT][1], ctx->stream);
   }
-  rc = g1_table_msm(ctx, (const uint32_t*)d_scalars, n, resident_form(ctx, n), out_xy);
+  const uint32_t* sc = nullptr;  // d_scalars, or their import: Montgomery scalars, the zeroed scalars of flagged bases
+  rc = import_scalars(ctx, d_scalars, n, 8, ctx->resident.flagged ? ctx->resident.inf_mask : nullptr, &sc);
+  if (rc) return rc;
+  rc = g1_table_msm(ctx, sc, n, resident_form(ctx, n), out_xy);
   if (rc != RC_TE_FALLBACK) return rc;
   rc = resident_table_to_weierstrass(ctx);
   if (rc) return rc;
-  return g1_table_msm(ctx, (const uint32_t*)d_scalars, n, resident_form(ctx, n), out_xy);
+  return g1_table_msm(ctx, sc, n, resident_form(ctx, n), out_xy);
 }
 
 // The same over scalars of a declared width (g1_short_table_msm): whatever the last set-bases call left resident serves.
@@ -1495,6 +1668,7 @@ int g1_msm_fixed_base_short_device(msm377_ctx* ctx, const void* d_scalars, uint6
   if (!out_xy) return MSM377_EINVAL;
   int rc = check_args(ctx, nullptr, d_scalars, n, false);
   if (rc == MSM377_OK) rc = check_short_args(ctx, sbytes, bits);
+  if (rc == MSM377_OK) rc = refuse_mont_short(ctx);
   if (rc) return rc;
   if (n > ctx->resident.n) {
     ctx->err = "fixed-base MSM needs g1_set_bases with at least n points first";
@@ -1511,11 +1685,14 @@ int g1_msm_fixed_base_short_device(msm377_ctx* ctx, const void* d_scalars, uint6
   }
   // (records 0 .. n-1 of a GLV table are the plain points: the short path reads those and never the phi half)
   auto form = [&] { return ctx->resident.form == TABLE_XYZZ_GLV ? (int)TABLE_XYZZ : ctx->resident.form; };
-  rc = g1_short_table_msm(ctx, d_scalars, n, form(), sbytes, bits, out_xy);
+  const uint32_t* sc = nullptr;  // (a masked copy when the resident set has flagged points)
+  rc = import_scalars(ctx, d_scalars, n, sbytes / 4, ctx->resident.flagged ? ctx->resident.inf_mask : nullptr, &sc);
+  if (rc) return rc;
+  rc = g1_short_table_msm(ctx, sc, n, form(), sbytes, bits, out_xy);
   if (rc != RC_TE_FALLBACK) return rc;
   rc = resident_table_to_weierstrass(ctx);
   if (rc) return rc;
-  return g1_short_table_msm(ctx, d_scalars, n, form(), sbytes, bits, out_xy);
+  return g1_short_table_msm(ctx, sc, n, form(), sbytes, bits, out_xy);
 }
 
 // `batch` MSMs of n scalars each against the table resident in (or lent to, twin_borrow) `ctx`, on ctx's own stream and
@@ -1524,6 +1701,11 @@ static int fixed_base_batch_share(msm377_ctx* ctx, const void* d_scalars, uint64
   int rc = MSM377_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const uint32_t* sc = (const uint32_t*)d_scalars;
+  // MSM b's scalars as its decomposition reads them: in place, or imported into THIS context's staging right in front
+  // of it on its stream -- the decomposition is the only reader, so MSM b + 1's import may follow MSM b's kernels.
+  const uint32_t* inf_mask = ctx->resident.flagged ? ctx->resident.inf_mask : nullptr;
+  auto scalars_of = [&](uint32_t b, const uint32_t** out) { return import_scalars(ctx, sc + (size_t)b * n * 8, n, 8, inf_mask, out); };
+  const uint32_t* sb = nullptr;
   const int form = resident_form(ctx, n);
   const bool glv = form == TABLE_XYZZ_GLV, te = form_is_te(form);
   const bool wide = wide_table(ctx->resident);
@@ -1549,9 +1731,11 @@ static int fixed_base_batch_share(msm377_ctx* ctx, const void* d_scalars, uint64
   // (Horner + inversion on the other slot's partial records).
   for (uint32_t b = 0; b <= batch; b++) {
     if (b < batch && !te_fallback) {
-      rc = (form == TABLE_TE_AFFINE || form == TABLE_TE_PRECOMP) ? enqueue_windows<TeDev, TeAffBase>(ctx, sc + (size_t)b * n * 8, n, 0, W, (int)(b & 1), false, table_phase)
-           : te                    ? enqueue_windows<TeDev>(ctx, sc + (size_t)b * n * 8, n, 0, W, (int)(b & 1), false, table_phase)
-                                   : enqueue_windows<G1Dev>(ctx, sc + (size_t)b * n * 8, n, 0, W, (int)(b & 1), glv);
+      rc = scalars_of(b, &sb);
+      if (rc) return rc;
+      rc = (form == TABLE_TE_AFFINE || form == TABLE_TE_PRECOMP) ? enqueue_windows<TeDev, TeAffBase>(ctx, sb, n, 0, W, (int)(b & 1), false, table_phase)
+           : te                    ? enqueue_windows<TeDev>(ctx, sb, n, 0, W, (int)(b & 1), false, table_phase)
+                                   : enqueue_windows<G1Dev>(ctx, sb, n, 0, W, (int)(b & 1), glv);
       if (rc) return rc;
     }
     if (b > 0) {
@@ -1586,11 +1770,13 @@ static int fixed_base_batch_share(msm377_ctx* ctx, const void* d_scalars, uint64
     return RC_TE_FALLBACK;
   }
   for (uint32_t b : redo) {
-    rc = g1_table_msm(ctx, sc + (size_t)b * n * 8, n, TABLE_XYZZ, out_xy + (size_t)96 * b);
+    rc = scalars_of(b, &sb);
+    if (rc == MSM377_OK) rc = g1_table_msm(ctx, sb, n, TABLE_XYZZ, out_xy + (size_t)96 * b);
     if (rc) return rc;
   }
   for (uint32_t b : redo_wide) {
-    rc = g1_table_msm(ctx, sc + (size_t)b * n * 8, n, form, out_xy + (size_t)96 * b);
+    rc = scalars_of(b, &sb);
+    if (rc == MSM377_OK) rc = g1_table_msm(ctx, sb, n, form, out_xy + (size_t)96 * b);
     if (rc) return rc;  // RC_TE_FALLBACK included
   }
   return MSM377_OK;
@@ -1625,6 +1811,7 @@ static int twin_prepare(msm377_ctx* ctx) {
   if (wide_table(ctx->resident) && !tw->wide.ensure(ctx->resident.n)) return MSM377_ENOMEM;
   // lend the table, and the conversion's verdict that travels with it (d_err[2], read by the accumulation kernels)
   tw->resident = ctx->resident;
+  tw->scalar_form = ctx->scalar_form;  // (its share imports its own scalars into its own staging)
   tw->seg_plain = ctx->seg_plain, tw->seg_glv = ctx->seg_glv, tw->tail_from = ctx->tail_from;
   if (hipMemcpyAsync(tw->d_err + 2, ctx->d_err + 2, sizeof(int), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
       hipStreamSynchronize(ctx->stream) != hipSuccess) {
@@ -1684,6 +1871,10 @@ int g1_msm_fixed_base_batch_device(msm377_ctx* ctx, const void* d_scalars, uint6
 int g1_msm_fixed_base(msm377_ctx* ctx, const uint8_t* scalars, uint64_t n, uint8_t out_xy[96]) {
   if (!ctx || !out_xy || n > ctx->cap || (n && !scalars)) return MSM377_EINVAL;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (ctx->scalar_form != MSM377_SCALARS_WIRE || ctx->resident.flagged) {  // the import reads them from the native staging
+    const int up = upload_native(ctx, nullptr, 0, scalars, n * 32);
+    return up ? up : g1_msm_fixed_base_device(ctx, native_scalars(ctx), n, out_xy);
+  }
   int rc = h2d_staged(ctx, ctx->d_raw_scalars, scalars, n * 32, (size_t)ctx->cap * 96);
   if (rc) return rc;
   return g1_msm_fixed_base_device(ctx, ctx->d_raw_scalars, n, out_xy);
@@ -1710,6 +1901,8 @@ int window_partials(msm377_ctx* ctx, const void* d_points, const void* d_scalars
     return MSM377_OK;
   }
   ctx->resident.clear();
+  rc = import_inputs(ctx, &d_points, &d_scalars, n);  // (native input forms only)
+  if (rc) return rc;
   // The records are complete in ctx->d_partials (slot 0) once the call's completion event has fired; the copy
   // to the caller's device buffer rides the same stream and the call returns with that stream idle, so a
   // collective on any other stream may read the buffer.
@@ -1769,6 +1962,8 @@ int g1_glv_window_partials_device(msm377_ctx* ctx, const void* d_points, const v
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   ctx->resident.clear();
+  rc = import_inputs(ctx, &d_points, &d_scalars, n);  // (native input forms only)
+  if (rc) return rc;
   rc = convert_bases_g1(ctx, (const uint32_t*)d_points, n, true);
   if (rc) return rc;
   rc = enqueue_windows<G1Dev>(ctx, (const uint32_t*)d_scalars, n, win_begin, win_count, 0, true);

@@ -70,3 +70,69 @@ def encode_scalars(scalars: Iterable[int], scalar_bytes: int = 32) -> bytes:
             raise ValueError("scalar %d does not fit %d bytes" % (k, scalar_bytes))
         out += k.to_bytes(scalar_bytes, "little")
     return bytes(out)
+
+
+# ---- native input forms (include/msm377.h "native input forms") ----
+# What a prover built on arkworks or snarkVM keeps in memory: G1 coordinates as x * 2^384 mod p, scalars as
+# s * 2^256 mod r, an affine point as x, y and an infinity flag byte padded to 104 bytes.  Plain Python integers: a
+# third implementation beside the engine's import pass and its host helpers, for tests and for users.
+G1_P = 0x01AE3A4617C510EAC63B05C06CA1493B1A22D9F300F5138F1EF3622FBA094800170B5D44300000008508C00000000001
+G1_R = 8444461749428370424248824938781546531375899335154063827935233455917409239041
+POINT_FORMS = {"wire": 0, "mont": 1, "mont_flag": 2}
+SCALAR_FORMS = {"wire": 0, "mont": 1}
+POINT_STRIDE = {"wire": 96, "mont": 96, "mont_flag": 104}
+_INV384 = pow(1 << 384, -1, G1_P)
+_INV256 = pow(1 << 256, -1, G1_R)
+
+
+def encode_points_native(points, form: str = "mont_flag") -> bytes:
+    """Affine points (x, y) -- None for the identity, ``mont_flag`` only -- in the named form."""
+    if form not in POINT_FORMS:
+        raise ValueError("point form must be one of %s" % sorted(POINT_FORMS))
+    out = bytearray()
+    for pt in points:
+        if pt is None:
+            if form != "mont_flag":
+                raise ValueError("only the mont_flag form can express the identity")
+            out += bytes(96) + b"\x01" + bytes(7)
+            continue
+        x, y = int(pt[0]), int(pt[1])
+        if form != "wire":
+            x, y = (x << 384) % G1_P, (y << 384) % G1_P
+        out += x.to_bytes(48, "little") + y.to_bytes(48, "little")
+        if form == "mont_flag":
+            out += bytes(8)
+    return bytes(out)
+
+
+def decode_points_native(buf: bytes, form: str = "mont_flag") -> list:
+    """Inverse of encode_points_native: (x, y) tuples, None for a flagged point (whatever its coordinate bytes hold).
+    A Montgomery value v decodes to v * 2^-384 mod p."""
+    stride = POINT_STRIDE[form]
+    buf = bytes(buf)
+    if len(buf) % stride:
+        raise ValueError("points buffer length must be a multiple of %d" % stride)
+    out = []
+    for i in range(0, len(buf), stride):
+        if form == "mont_flag" and buf[i + 96]:
+            out.append(None)
+            continue
+        x, y = int.from_bytes(buf[i : i + 48], "little"), int.from_bytes(buf[i + 48 : i + 96], "little")
+        if form != "wire":
+            x, y = x * _INV384 % G1_P, y * _INV384 % G1_P
+        out.append((x, y))
+    return out
+
+
+def encode_scalars_native(scalars: Iterable[int], form: str = "mont") -> bytes:
+    """Scalars as 32 little-endian bytes each: canonical (``wire``) or s * 2^256 mod r (``mont``)."""
+    if form not in SCALAR_FORMS:
+        raise ValueError("scalar form must be one of %s" % sorted(SCALAR_FORMS))
+    return b"".join(((int(k) << 256) % G1_R if form == "mont" else int(k)).to_bytes(32, "little") for k in scalars)
+
+
+def decode_scalars_native(buf: bytes, form: str = "mont") -> List[int]:
+    """Inverse of encode_scalars_native.  Every 32-byte Montgomery value v is accepted and decodes to
+    v * 2^-256 mod r, fully reduced."""
+    vals = readBigIntsFromBufferLE(buf, 256)
+    return [v * _INV256 % G1_R for v in vals] if form == "mont" else vals

@@ -26,6 +26,12 @@ CHECK_CANONICAL, CHECK_CURVE, CHECK_SUBGROUP, CHECK_ALL = 1, 2, 4, 7
 # msm377_ctx_get_fallback_info: where an exceptional case of the twisted Edwards law surfaced (include/msm377.h)
 FB_ACCUMULATE, FB_MERGE, FB_TREE, FB_TAIL, FB_CONVERT = 4, 8, 16, 32, 64
 GLV_WINDOWS = 8
+# msm377_ctx_set_input_format (include/msm377.h "native input forms")
+POINTS_WIRE, POINTS_MONT, POINTS_MONT_FLAG = 0, 1, 2
+SCALARS_WIRE, SCALARS_MONT = 0, 1
+_POINT_FORMS = {"wire": POINTS_WIRE, "mont": POINTS_MONT, "mont_flag": POINTS_MONT_FLAG}
+_SCALAR_FORMS = {"wire": SCALARS_WIRE, "mont": SCALARS_MONT}
+_POINT_STRIDE = {POINTS_WIRE: 96, POINTS_MONT: 96, POINTS_MONT_FLAG: 104}
 
 _LIB = None
 
@@ -163,6 +169,11 @@ def load_library():
         "msm377_scalars_width_host": (i32, [u8p, u64, u32, ctypes.POINTER(u32)]),
         "msm377_short_windows": (u32, [u32, u32]),
         "msm377_ctx_get_last_geometry": (i32, [vp, ctypes.POINTER(u32), ctypes.POINTER(u32)]),
+        "msm377_ctx_set_input_format": (i32, [vp, u32, u32]),
+        "msm377_ctx_get_input_format": (i32, [vp, ctypes.POINTER(u32), ctypes.POINTER(u32)]),
+        "msm377_g1_import_points_host": (i32, [u8p, u64, u32, vp, vp]),
+        "msm377_import_scalars_host": (i32, [u8p, u64, u32, vp]),
+        "msm377_g1_result_to_native": (i32, [u8p, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
@@ -212,6 +223,56 @@ def scalars_width_host(scalars: bytes, scalar_bytes: int = 32) -> int:
     if rc:
         raise MsmError(rc, "msm377_scalars_width_host")
     return int(bits.value)
+
+
+def _form(table, form, what):
+    if form in table:
+        return table[form]
+    if isinstance(form, str):
+        raise ValueError("%s form must be one of %s" % (what, sorted(table)))
+    return int(form)  # a raw value: the library validates it
+
+
+def import_points_host(points: bytes, form="mont_flag") -> Tuple[bytes, List[int]]:
+    """Native-form G1 points -> (wire records, infinity mask words) on the calling thread
+    (msm377_g1_import_points_host): no context, no device.  A flagged point's record is the generator's and its mask
+    bit (bit i % 32 of word i // 32) is set."""
+    f = _form(_POINT_FORMS, form, "point")
+    stride = _POINT_STRIDE.get(f, 96)
+    if len(points) % stride:
+        raise ValueError("points buffer length must be a multiple of %d" % stride)
+    n = len(points) // stride
+    out = ctypes.create_string_buffer(max(1, 96 * n))
+    mask = (ctypes.c_uint32 * max(1, (n + 31) // 32))()
+    rc = load_library().msm377_g1_import_points_host(bytes(points), n, f, ctypes.addressof(out), ctypes.addressof(mask))
+    if rc:
+        raise MsmError(rc, "msm377_g1_import_points_host")
+    return out.raw[: 96 * n], list(mask)[: (n + 31) // 32]
+
+
+def import_scalars_host(scalars: bytes, form="mont") -> bytes:
+    """Native-form scalars -> canonical 32-byte scalars (msm377_import_scalars_host): every Montgomery value v gives
+    v * 2^-256 mod r."""
+    if len(scalars) % 32:
+        raise ValueError("scalars buffer length must be a multiple of 32")
+    n = len(scalars) // 32
+    out = ctypes.create_string_buffer(max(1, 32 * n))
+    rc = load_library().msm377_import_scalars_host(bytes(scalars), n, _form(_SCALAR_FORMS, form, "scalar"), ctypes.addressof(out))
+    if rc:
+        raise MsmError(rc, "msm377_import_scalars_host")
+    return out.raw[: 32 * n]
+
+
+def result_to_native(xy: bytes) -> bytes:
+    """A 96-byte wire result as a 104-byte mont_flag record; the wire identity (0, 1) sets the flag
+    (msm377_g1_result_to_native)."""
+    if len(xy) != 96:
+        raise ValueError("a result is 96 bytes")
+    out = ctypes.create_string_buffer(104)
+    rc = load_library().msm377_g1_result_to_native(bytes(xy), ctypes.addressof(out))
+    if rc:
+        raise MsmError(rc, "msm377_g1_result_to_native")
+    return out.raw
 
 
 def short_windows(scalar_bits: int, bucket_log: int) -> int:
@@ -301,6 +362,7 @@ class MsmEngine:
             raise MsmError(rc, "msm377_ctx_create", "device %d, max_points %d (is a HIP device visible?)" % (device, max_points))
         self.max_points = int(max_points)
         self.device = int(device)
+        self._point_bytes = 96  # bytes per point of the active input form (set_input_format)
 
     # -- lifetime --
     def close(self):
@@ -324,10 +386,29 @@ class MsmEngine:
         if rc:
             raise MsmError(rc, what, self._lib.msm377_last_error(self._ctx).decode())
 
+    # -- native input forms (include/msm377.h) --
+    def set_input_format(self, points="wire", scalars="wire"):
+        """Form of the points ("wire", "mont", "mont_flag") and scalars ("wire", "mont") every G1 call of this engine
+        reads from now on (msm377_ctx_set_input_format).  Results stay in the wire format.  An unknown value raises
+        MsmError(EINVAL) and leaves the forms as they were."""
+        pf, sf = _form(_POINT_FORMS, points, "point"), _form(_SCALAR_FORMS, scalars, "scalar")
+        self._check(self._lib.msm377_ctx_set_input_format(self._ctx, pf, sf), "msm377_ctx_set_input_format")
+        self._point_bytes = _POINT_STRIDE[pf]
+
+    def get_input_format(self) -> Tuple[str, str]:
+        pf, sf = ctypes.c_uint32(), ctypes.c_uint32()
+        self._check(self._lib.msm377_ctx_get_input_format(self._ctx, ctypes.byref(pf), ctypes.byref(sf)), "msm377_ctx_get_input_format")
+        return {v: k for k, v in _POINT_FORMS.items()}[pf.value], {v: k for k, v in _SCALAR_FORMS.items()}[sf.value]
+
+    def _count_points(self, points: bytes) -> int:
+        if len(points) % self._point_bytes:
+            raise ValueError("points buffer length must be a multiple of %d" % self._point_bytes)
+        return len(points) // self._point_bytes
+
     # -- G1 MSM --
     def msm(self, points: bytes, scalars: bytes) -> bytes:
-        """compute_msm on host buffers; returns x||y (96 bytes)."""
-        n = _check_lengths(points, scalars)
+        """compute_msm on host buffers (in the active input form); returns x||y (96 bytes)."""
+        n = _check_lengths(points, scalars, self._point_bytes)
         out = ctypes.create_string_buffer(96)
         self._check(self._lib.msm377_g1_msm(self._ctx, bytes(points), bytes(scalars), n, ctypes.addressof(out)), "msm377_g1_msm")
         return out.raw
@@ -342,9 +423,10 @@ class MsmEngine:
     def msm_short(self, points: bytes, scalars: bytes, scalar_bytes: int, scalar_bits: int) -> bytes:
         """compute_msm on host buffers with compact scalars of a declared width: floor(bits / (L + 1)) + 1 windows
         instead of 16 or 22.  MsmError(ESCALAR) if a scalar is 2^scalar_bits or more."""
-        n = len(scalars) // scalar_bytes if scalar_bytes in (4, 8, 16, 32) and len(scalars) % scalar_bytes == 0 else len(points) // 96
-        if scalar_bytes in (4, 8, 16, 32) and len(points) != 96 * n:
-            raise ValueError("points buffer must hold %d bytes (96 per scalar), got %d" % (96 * n, len(points)))
+        pb = self._point_bytes
+        n = len(scalars) // scalar_bytes if scalar_bytes in (4, 8, 16, 32) and len(scalars) % scalar_bytes == 0 else len(points) // pb
+        if scalar_bytes in (4, 8, 16, 32) and len(points) != pb * n:
+            raise ValueError("points buffer must hold %d bytes (%d per scalar), got %d" % (pb * n, pb, len(points)))
         out = ctypes.create_string_buffer(96)
         self._check(self._lib.msm377_g1_msm_short(self._ctx, bytes(points), bytes(scalars), n, int(scalar_bytes), int(scalar_bits), ctypes.addressof(out)), "msm377_g1_msm_short")
         return out.raw
@@ -380,9 +462,7 @@ class MsmEngine:
         return int(w.value), int(log.value)
 
     def set_bases(self, points: bytes):
-        if len(points) % 96:
-            raise ValueError("points buffer length must be a multiple of 96")
-        self._check(self._lib.msm377_g1_set_bases(self._ctx, bytes(points), len(points) // 96), "msm377_g1_set_bases")
+        self._check(self._lib.msm377_g1_set_bases(self._ctx, bytes(points), self._count_points(points)), "msm377_g1_set_bases")
 
     def set_bases_device(self, d_points: int, n: int):
         self._check(self._lib.msm377_g1_set_bases_device(self._ctx, d_points, int(n)), "msm377_g1_set_bases_device")
@@ -390,9 +470,7 @@ class MsmEngine:
     def set_bases_precomputed(self, points: bytes):
         """Resident bases WITH precomputed window multiples [2^(16 w)] P_i (msm377_g1_set_bases_precomputed): one bucket
         reduction and a 16-step tail per fixed-base MSM."""
-        if len(points) % 96:
-            raise ValueError("points buffer length must be a multiple of 96")
-        self._check(self._lib.msm377_g1_set_bases_precomputed(self._ctx, bytes(points), len(points) // 96), "msm377_g1_set_bases_precomputed")
+        self._check(self._lib.msm377_g1_set_bases_precomputed(self._ctx, bytes(points), self._count_points(points)), "msm377_g1_set_bases_precomputed")
 
     def reserve_host_staging(self):
         """Allocate the pinned staging of the host-buffer entry points now instead of inside the first call
@@ -487,10 +565,9 @@ class MsmEngine:
         return _report(rep)
 
     def check_points(self, points: bytes, flags: int = CHECK_ALL) -> CheckReport:
-        """Report on G1 wire points in a host buffer, computed on the GPU; the resident bases survive the call."""
-        if len(points) % 96:
-            raise ValueError("points buffer length must be a multiple of 96")
-        return self._check_points("msm377_g1_check_points", bytes(points), len(points) // 96, flags)
+        """Report on G1 points (in the active point form) in a host buffer, computed on the GPU; the resident bases
+        survive the call."""
+        return self._check_points("msm377_g1_check_points", bytes(points), self._count_points(points), flags)
 
     def check_points_device(self, d_points: int, n: int, flags: int = CHECK_ALL) -> CheckReport:
         return self._check_points("msm377_g1_check_points_device", d_points, n, flags)
@@ -590,11 +667,11 @@ class MsmEngine:
         return int(self._lib.msm377_ctx_get_products_per_addition(self._ctx))
 
 
-def _check_lengths(points: bytes, scalars: bytes) -> int:
+def _check_lengths(points: bytes, scalars: bytes, point_bytes: int = 96) -> int:
     """input_size = scalars.length / 32 (submission.ts:91)."""
     if len(scalars) % 32:
         raise ValueError("scalars buffer length must be a multiple of 32")
     n = len(scalars) // 32
-    if len(points) != 96 * n:
-        raise ValueError("points buffer must hold %d bytes (96 per scalar), got %d" % (96 * n, len(points)))
+    if len(points) != point_bytes * n:
+        raise ValueError("points buffer must hold %d bytes (%d per scalar), got %d" % (point_bytes * n, point_bytes, len(points)))
     return n

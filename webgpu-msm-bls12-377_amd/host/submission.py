@@ -11,7 +11,7 @@ Python mirror used by the parity tests and bench.py.  Both call the C ABI (inclu
 """
 from typing import Dict, Optional, Sequence, Union
 
-from .codecs import bigIntsToBufferLE, encode_scalars, u32ArrayToBigInts
+from .codecs import POINT_STRIDE, bigIntsToBufferLE, encode_scalars, u32ArrayToBigInts
 from .engine import MsmEngine
 
 _ENGINE: Optional[MsmEngine] = None
@@ -70,12 +70,16 @@ def _engine_for(n: int) -> MsmEngine:
 
 
 def compute_msm(baseAffinePoints, scalars, log_result: bool = True, force_recompile: bool = False, scalar_bits: Optional[int] = None,
-                scalar_bytes: int = 32) -> Dict[str, int]:
+                scalar_bytes: int = 32, point_form: str = "wire", scalar_form: str = "wire") -> Dict[str, int]:
     """Q = sum k_i P_i over BLS12-377 G1; returns affine {"x": int, "y": int}.
 
     ``scalar_bits`` (None: the reference's call, unchanged): the caller declares that every scalar is below
     2^scalar_bits and the engine runs the short-scalar path (MsmEngine.msm_short); a scalars Buffer then holds
     ``scalar_bytes`` (4, 8, 16 or 32) little-endian bytes per scalar, integers are encoded at that stride.
+
+    ``point_form`` / ``scalar_form`` (default "wire": unchanged): the Buffers hold the callers' native forms --
+    "mont" / "mont_flag" points, "mont" scalars (MsmEngine.set_input_format; integers and point objects are always
+    plain values and are only accepted with "wire").  The result stays {x, y} in plain integers.
 
     Same contract as the reference: input_size = len(scalars buffer) / 32, empty input gives
     {x: 0, y: 1} (submission.ts:91-95); errors raise (MsmError) instead of rejecting a Promise.
@@ -83,6 +87,27 @@ def compute_msm(baseAffinePoints, scalars, log_result: bool = True, force_recomp
     for gfx950, there is no runtime shader cache to defeat (shader_manager.ts:71-77).
     """
     del force_recompile
+    if (point_form, scalar_form) != ("wire", "wire"):
+        if not (_is_buffer(baseAffinePoints) and _is_buffer(scalars)):
+            raise ValueError("native input forms are Buffers; integers and point objects are plain values (wire)")
+        stride = POINT_STRIDE.get(point_form, 96)
+        sb = scalar_bytes if scalar_bits is not None else 32
+        if sb not in (4, 8, 16, 32) or len(scalars) % sb or len(baseAffinePoints) != len(scalars) // sb * stride:
+            raise ValueError("points buffer must hold %d bytes and scalars %d bytes per input" % (stride, sb))
+        n = len(scalars) // sb
+        if n == 0:
+            result = {"x": 0, "y": 1}
+        else:
+            eng = _engine_for(n)
+            eng.set_input_format(point_form, scalar_form)
+            try:
+                out = eng.msm(bytes(baseAffinePoints), bytes(scalars)) if scalar_bits is None else eng.msm_short(bytes(baseAffinePoints), bytes(scalars), sb, scalar_bits)
+            finally:
+                eng.set_input_format("wire", "wire")
+            result = {"x": int.from_bytes(out[:48], "little"), "y": int.from_bytes(out[48:], "little")}
+        if log_result:
+            print(result)
+        return result
     if scalar_bits is not None:
         sbuf = bytes(scalars) if _is_buffer(scalars) else encode_scalars([_to_int(s) for s in scalars], scalar_bytes)
         pbuf = points_to_buffer(baseAffinePoints)

@@ -43,9 +43,24 @@ const scalarsToBuffer = (scalars) => {
 // Third argument: log_result as in the reference, or {scalarBytes, scalarBits, log_result?} -- the caller declares that
 // every scalar is below 2^scalarBits; a scalars Buffer then holds scalarBytes (4, 8, 16 or 32; default 32) little-endian
 // bytes per scalar and the engine runs floor(scalarBits / 16) + 1 windows instead of 16 (msm377_g1_msm_short).  Without
-// it the call is the reference's.
+// it the call is the reference's.  {pointForm, scalarForm} next to them (or alone) name the callers' native forms of the
+// Buffers -- pointForm 'wire' | 'mont' | 'mont_flag' (104-byte records with an infinity flag), scalarForm 'wire' | 'mont'
+// (msm377_ctx_set_input_format; full-width scalars only).  The result stays {x, y} in plain bigints.
+const POINT_FORMS = { wire: 0, mont: 1, mont_flag: 2 };
+const SCALAR_FORMS = { wire: 0, mont: 1 };
 const compute_msm = async (baseAffinePoints, scalars, log_result = true, force_recompile = false) => {
   void force_recompile; // kernels are compiled ahead of time for gfx950; nothing to recompile
+  if (log_result !== null && typeof log_result === 'object' && (log_result.pointForm !== undefined || log_result.scalarForm !== undefined)) {
+    const { pointForm = 'wire', scalarForm = 'wire', scalarBits, log_result: log = false } = log_result;
+    if (!(pointForm in POINT_FORMS) || !(scalarForm in SCALAR_FORMS)) throw new RangeError('pointForm: wire | mont | mont_flag; scalarForm: wire | mont');
+    if (scalarBits !== undefined) throw new RangeError('native input forms take full-width scalars (no scalarBits)');
+    if (!Buffer.isBuffer(baseAffinePoints) || !Buffer.isBuffer(scalars)) throw new TypeError('native input forms are Buffers');
+    if (scalars.length === 0) return { x: BigInt(0), y: BigInt(1) };
+    const o = addon.computeMsmNativeSync(baseAffinePoints, scalars, POINT_FORMS[pointForm], SCALAR_FORMS[scalarForm]);
+    const rn = { x: leBufferToBigInt(o.slice(0, 48)), y: leBufferToBigInt(o.slice(48, 96)) };
+    if (log) console.log(rn);
+    return rn;
+  }
   if (log_result !== null && typeof log_result === 'object') {
     const { scalarBytes = 32, scalarBits, log_result: log = false } = log_result;
     const sBuf = Buffer.isBuffer(scalars) ? scalars : Buffer.concat(Array.from(scalars, (s) => bigIntToBufferLE(toBigInt(s), scalarBytes)));

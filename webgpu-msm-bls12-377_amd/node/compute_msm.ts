@@ -77,16 +77,44 @@ export interface ShortScalars {
   log_result?: boolean;
 }
 
-// Third argument: log_result as in the reference, or a ShortScalars object; without one the call is the reference's.
+// The callers' native forms of the two Buffers (msm377_ctx_set_input_format): Montgomery coordinates, 104-byte records
+// with an infinity flag, Montgomery scalars.  Full-width scalars only; the result stays {x, y} in plain bigints.
+export interface NativeForms {
+  pointForm?: 'wire' | 'mont' | 'mont_flag';
+  scalarForm?: 'wire' | 'mont';
+  log_result?: boolean;
+}
+const POINT_FORMS = { wire: 0, mont: 1, mont_flag: 2 };
+const SCALAR_FORMS = { wire: 0, mont: 1 };
+
+// Third argument: log_result as in the reference, a ShortScalars object or a NativeForms object; without one the call
+// is the reference's.
 export const compute_msm = async (
   baseAffinePoints: BigIntPoint[] | U32ArrayPoint[] | Buffer,
   scalars: bigint[] | Uint32Array[] | Buffer,
-  log_result: boolean | ShortScalars = true,
+  log_result: boolean | ShortScalars | NativeForms = true,
   force_recompile = false,
 ): Promise<{ x: bigint; y: bigint }> => {
   void force_recompile; // kernels are compiled ahead of time for gfx950
+  if (log_result !== null && typeof log_result === 'object' && ('pointForm' in log_result || 'scalarForm' in log_result)) {
+    const { pointForm = 'wire', scalarForm = 'wire', log_result: log = false } = log_result as NativeForms;
+    if (!(pointForm in POINT_FORMS) || !(scalarForm in SCALAR_FORMS)) {
+      throw new RangeError('pointForm: wire | mont | mont_flag; scalarForm: wire | mont');
+    }
+    if ('scalarBits' in log_result) throw new RangeError('native input forms take full-width scalars (no scalarBits)');
+    if (!Buffer.isBuffer(baseAffinePoints) || !Buffer.isBuffer(scalars)) throw new TypeError('native input forms are Buffers');
+    if (scalars.length === 0) {
+      return { x: BigInt(0), y: BigInt(1) };
+    }
+    const o: Buffer = addon.computeMsmNativeSync(baseAffinePoints, scalars, POINT_FORMS[pointForm], SCALAR_FORMS[scalarForm]);
+    const rn = { x: leBufferToBigInt(o.subarray(0, 48) as Buffer), y: leBufferToBigInt(o.subarray(48, 96) as Buffer) };
+    if (log) {
+      console.log(rn);
+    }
+    return rn;
+  }
   if (log_result !== null && typeof log_result === 'object') {
-    const { scalarBytes = 32, scalarBits, log_result: log = false } = log_result;
+    const { scalarBytes = 32, scalarBits, log_result: log = false } = log_result as ShortScalars;
     const sBuf = Buffer.isBuffer(scalars)
       ? scalars
       : Buffer.concat((scalars as (bigint | Uint32Array)[]).map((s) => bigIntToBufferLE(toBigInt(s), scalarBytes)));

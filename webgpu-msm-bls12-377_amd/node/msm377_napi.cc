@@ -145,6 +145,52 @@ napi_value ComputeMsmShortSync(napi_env env, napi_callback_info info) {
   return buf;
 }
 
+// computeMsmNativeSync(points, scalars, pointForm, scalarForm): the callers' native forms (msm377_ctx_set_input_format:
+// MSM377_POINTS_* / MSM377_SCALARS_* values) for this one call; the shared context goes back to the wire format.
+napi_value ComputeMsmNativeSync(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  bool pb = false, sb = false;
+  uint32_t pform = 0, sform = 0;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 4 || napi_is_buffer(env, argv[0], &pb) != napi_ok || !pb ||
+      napi_is_buffer(env, argv[1], &sb) != napi_ok || !sb || napi_get_value_uint32(env, argv[2], &pform) != napi_ok ||
+      napi_get_value_uint32(env, argv[3], &sform) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "expected (points: Buffer, scalars: Buffer, pointForm: number, scalarForm: number)");
+    return nullptr;
+  }
+  uint8_t *p, *s;
+  size_t pl, sl;
+  napi_get_buffer_info(env, argv[0], reinterpret_cast<void**>(&p), &pl);
+  napi_get_buffer_info(env, argv[1], reinterpret_cast<void**>(&s), &sl);
+  const size_t stride = pform == MSM377_POINTS_MONT_FLAG ? 104 : 96;
+  if (pform > MSM377_POINTS_MONT_FLAG || sform > MSM377_SCALARS_MONT || sl % 32 != 0 || pl != (sl / 32) * stride) {
+    napi_throw_range_error(env, nullptr, "pointForm 0..2, scalarForm 0..1; points must hold 96 (104 with flags) bytes and scalars 32 bytes per input");
+    return nullptr;
+  }
+  const uint64_t n = sl / 32;
+  uint8_t out[96];
+  std::string err;
+  int rc;
+  {
+    std::lock_guard<std::mutex> lock(g_mu);
+    rc = ensure_ctx(n ? n : 1, &err);
+    if (!rc) {
+      rc = msm377_ctx_set_input_format(g_ctx, pform, sform);
+      if (!rc) rc = msm377_g1_msm(g_ctx, p, s, n, out);
+      if (rc) err = std::string("msm377_g1_msm (native input forms): ") + msm377_strerror(rc) + ": " + msm377_last_error(g_ctx);
+      msm377_ctx_set_input_format(g_ctx, MSM377_POINTS_WIRE, MSM377_SCALARS_WIRE);
+    }
+  }
+  if (rc) {
+    napi_throw_error(env, nullptr, err.c_str());
+    return nullptr;
+  }
+  napi_value buf;
+  void* data;
+  napi_create_buffer_copy(env, 96, out, &data, &buf);
+  return buf;
+}
+
 // ---- the other entry points of the C ABI a TypeScript host may want (synchronous forms) ----
 napi_value ComputeEdMsmSync(napi_env env, napi_callback_info info) {
   uint8_t *p, *s;
@@ -352,6 +398,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"computeMsm", nullptr, ComputeMsm, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"computeMsmSync", nullptr, ComputeMsmSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"computeMsmShortSync", nullptr, ComputeMsmShortSync, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"computeMsmNativeSync", nullptr, ComputeMsmNativeSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"computeEdMsmSync", nullptr, ComputeEdMsmSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"setBasesSync", nullptr, SetBasesSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"fixedBaseMsmSync", nullptr, FixedBaseMsmSync, nullptr, nullptr, nullptr, napi_default, nullptr},
