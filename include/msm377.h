@@ -369,6 +369,53 @@ int msm377_ctx_get_last_check(const msm377_ctx* ctx, msm377_check_report* out);
 int msm377_ctx_get_stage_form(const msm377_ctx* ctx); /* -1: nothing captured */
 int msm377_ctx_set_stage_capture(msm377_ctx* ctx, int enabled);
 int msm377_g1_read_stage(msm377_ctx* ctx, uint32_t slot, uint16_t* digits, uint32_t* row_ptr, uint32_t* val_idx, uint32_t* buckets);
+
+/* Capture modes of msm377_ctx_set_stage_capture (any other value: MSM377_EINVAL, the mode stays as it was; before mode 2
+ * existed every non-zero value meant mode 1).  msm377_g1_read_stage answers under mode 1 only, msm377_g1_read_stage_ex
+ * under modes 1 and 2; each returns MSM377_ESTATE otherwise.
+ *   0  off.
+ *   1  the route the read-backs above describe: sixteen equal 16-bit windows of 2^15 buckets, whatever the input size --
+ *      the narrow-window path, the even geometry, the chunked upload and twin batches are switched off while it is set.
+ *   2  AS RUN: the call takes the route it would take without capture (narrow windows, the even geometry, short
+ *      scalars, the wide table, the GLV front end, reruns) and msm377_g1_read_stage_ex describes whatever its LAST pass
+ *      launched.  Out of scope, and therefore still switched off by mode 2 as by mode 1: the chunked upload of the
+ *      host-buffer calls and twin batches, whose rows are laid out per chunk / per half.  Not described either
+ *      (MSM377_ESTATE): Edwards-BLS12 calls and window-partials calls that do not start at window 0.
+ *
+ * msm377_stage_info is filled from the arguments the last pass's kernels were launched with:
+ *   slots           window slots (16; 22 narrow; floor(bits / (L + 1)) + 1 short; 1 wide table; 8 GLV)
+ *   bucket_log      L: 2^L buckets per slot, keys 0 .. 2^L
+ *   columns         entries per slot: n, 2 n behind the GLV front end (column n + i = phi(P_i)), 13 n on the wide table
+ *                   (window-major: digit column w n + i; val_idx entries name table record w * table_stride + i)
+ *   digit_bytes     2 or 4: element size of `digits`
+ *   row_ptr_len     2^L + 2
+ *   bucket_records  2^L records of 52 words per slot, bucket t = key t + 1 at record t
+ *   form            MSM377_STAGE_FORM_* of the records
+ *   table_stride    records per window of a precomputed table (0: every slot gathers from the same base records)
+ *   geometry_reruns passes this context has discarded so far because a scalar did not fit their window geometry (2^253 and
+ *                   more, a carry out of the top window, or a GLV half of 2^127 and more) and run again on another one; counted up to and including the
+ *                   call described, so a test can tell a silent rerun from none
+ *   bias[s]         stored digit = digit + bias[s]
+ *   key_unsigned[s] 1: the sort reads the slot's stored digits as unsigned keys (the top slot of a short call on 2^15 buckets)
+ *   key_max[s]      the slot's key_max word as the sort read it (bit 31 = tracked, bit 30 = unsigned, low bits = largest
+ *                   key; 0 = not tracked, and always 0 where the sort takes no such word: narrow windows, the wide table) */
+#define MSM377_STAGE_MAX_SLOTS 22
+typedef struct msm377_stage_info {
+  uint32_t slots, bucket_log;
+  uint64_t columns;
+  uint32_t digit_bytes, row_ptr_len, bucket_records;
+  int32_t form;
+  uint64_t table_stride;
+  uint64_t geometry_reruns;
+  uint32_t bias[MSM377_STAGE_MAX_SLOTS];
+  uint32_t key_unsigned[MSM377_STAGE_MAX_SLOTS];
+  uint32_t key_max[MSM377_STAGE_MAX_SLOTS];
+} msm377_stage_info;
+/* Stage outputs of window slot `slot` of the last G1 MSM call, at the sizes `info` reports (any pointer may be NULL; call
+ * once with buffers NULL to size them): digits columns x digit_bytes, row_ptr row_ptr_len u32, val_idx columns u32,
+ * buckets bucket_records x 52 u32.  MSM377_ESTATE (and nothing written) unless capture is on and the last call's last
+ * pass ran to the end under it on a route the mode describes. */
+int msm377_g1_read_stage_ex(msm377_ctx* ctx, uint32_t slot, msm377_stage_info* info, void* digits, uint32_t* row_ptr, uint32_t* val_idx, uint32_t* buckets);
 /* Convert one Montgomery XYZZ point (52 words) to the affine wire format (host-only). */
 int msm377_g1_xyzz_to_affine(const uint32_t xyzz[52], uint8_t out_xy[96]);
 

@@ -26,6 +26,7 @@ from .host.engine import (  # noqa: F401
     CHECK_CURVE,
     CHECK_SUBGROUP,
     CheckReport,
+    StageInfo,
     MsmEngine,
     MsmError,
     check_points_host,
@@ -46,6 +47,7 @@ __all__ = [
     "MsmEngine",
     "MsmError",
     "CheckReport",
+    "StageInfo",
     "check_points_host",
     "ed_check_points_host",
     "CHECK_CANONICAL",

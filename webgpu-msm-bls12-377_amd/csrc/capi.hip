@@ -270,19 +270,21 @@ int msm377_g1_combine_partials_split(const uint8_t* partials, uint32_t pieces, u
 
 
 int msm377_ctx_set_stage_capture(msm377_ctx* ctx, int enabled) {
-  if (!ctx) return MSM377_EINVAL;
+  if (!ctx || enabled < 0 || enabled > 2) return MSM377_EINVAL;
   if (enabled && !ctx->d_buckets_snap) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (hipMalloc((void**)&ctx->d_buckets_snap, (size_t)MSM377_NUM_WINDOWS * BKT_WORDS * NB * 4) != hipSuccess) return MSM377_ENOMEM;
   }
-  ctx->capture = enabled != 0;
+  ctx->capture = enabled;
+  ctx->stage.valid = false;  // what an earlier call left was captured (or not) under another mode
   return MSM377_OK;
 }
 
 int msm377_g1_read_stage(msm377_ctx* ctx, uint32_t slot, uint16_t* digits, uint32_t* row_ptr, uint32_t* val_idx, uint32_t* buckets) {
   if (!ctx) return MSM377_EINVAL;
-  if (!ctx->capture || ctx->last_n == 0 || slot >= ctx->last_wc || ctx->last_form < 0 || ctx->last_glv) {
-    ctx->err = "no captured stage data for that window slot";
+  // capture mode 1 only: the sizes below are those of its route; under mode 2 a call lays its stages out as it runs
+  if (ctx->capture != 1 || ctx->last_n == 0 || slot >= ctx->last_wc || ctx->last_form < 0 || ctx->last_glv) {
+    ctx->err = "no captured stage data for that window slot (capture mode 2 is read with msm377_g1_read_stage_ex)";
     return MSM377_ESTATE;
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -298,6 +300,46 @@ int msm377_g1_read_stage(msm377_ctx* ctx, uint32_t slot, uint16_t* digits, uint3
       for (uint32_t t = 0; t < NB; t++)
         for (uint32_t c = 0; c < 4; c++)
           for (uint32_t j = 0; j < 13; j++) buckets[(size_t)t * PT_WORDS + c * 13 + j] = tmp[(size_t)t * BKT_WORDS + c * 16 + j];
+    free(tmp);
+    HIP_TRY(ctx, e);
+  }
+  return MSM377_OK;
+}
+
+// The as-run read-back: sizes, biases and pointers are those enqueue_windows recorded at its launches (StageLayout);
+// nothing about the geometry is worked out here.
+int msm377_g1_read_stage_ex(msm377_ctx* ctx, uint32_t slot, msm377_stage_info* info, void* digits, uint32_t* row_ptr, uint32_t* val_idx, uint32_t* buckets) {
+  if (!ctx) return MSM377_EINVAL;
+  const StageLayout& sl = ctx->stage;
+  if (!ctx->capture || !sl.valid || !ctx->d_buckets_snap) {
+    ctx->err = "no captured stage data: stage capture is off, or the last call is not one the capture mode describes";
+    return MSM377_ESTATE;
+  }
+  if (slot >= sl.info.slots) {
+    ctx->err = "no captured stage data for that window slot";
+    return MSM377_ESTATE;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  msm377_stage_info out = sl.info;
+  if (sl.d_key_max) {
+    uint32_t words[MSM377_NUM_WINDOWS] = {};
+    HIP_TRY(ctx, hipMemcpy(words, sl.d_key_max, sizeof words, hipMemcpyDeviceToHost));
+    for (uint32_t s = 0; s < out.slots && s < MSM377_NUM_WINDOWS; s++) out.key_max[s] = words[s];
+  }
+  if (info) *info = out;
+  const uint64_t cols = out.columns;
+  const size_t records = out.bucket_records;
+  if (digits) HIP_TRY(ctx, hipMemcpy(digits, (const uint8_t*)sl.d_digits + (size_t)slot * cols * out.digit_bytes, cols * out.digit_bytes, hipMemcpyDeviceToHost));
+  if (row_ptr) HIP_TRY(ctx, hipMemcpy(row_ptr, ctx->d_row_ptr + (size_t)slot * out.row_ptr_len, (size_t)out.row_ptr_len * 4, hipMemcpyDeviceToHost));
+  if (val_idx) HIP_TRY(ctx, hipMemcpy(val_idx, ctx->d_val_idx + (size_t)slot * cols, cols * 4, hipMemcpyDeviceToHost));
+  if (buckets) {
+    uint32_t* tmp = (uint32_t*)malloc(records * BKT_WORDS * 4);
+    if (!tmp) return MSM377_ENOMEM;
+    hipError_t e = hipMemcpy(tmp, ctx->d_buckets_snap + (size_t)slot * records * BKT_WORDS, records * BKT_WORDS * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess)  // 64-word records (four 16-word coordinate slots) -> the 52 packed words of the ABI
+      for (size_t t = 0; t < records; t++)
+        for (uint32_t c = 0; c < 4; c++)
+          for (uint32_t j = 0; j < 13; j++) buckets[t * PT_WORDS + c * 13 + j] = tmp[t * BKT_WORDS + c * 16 + j];
     free(tmp);
     HIP_TRY(ctx, e);
   }

@@ -54,6 +54,16 @@ struct WideBuffers {
   }
 };
 
+// What the last enqueue_windows launched with, for msm377_g1_read_stage_ex: written next to the launches themselves
+// (sequencer.hip) from the values they were given, so that the read-back describes the kernels' arguments and not a second
+// derivation of them.  valid: a whole call (front and back phase, from window 0) ran to its end under stage capture.
+struct StageLayout {
+  bool valid = false;
+  msm377_stage_info info = {};
+  const void* d_digits = nullptr;       // the digit matrix the decomposition wrote: ctx->d_digits (u16) or ctx->wide.digits (u32)
+  const uint32_t* d_key_max = nullptr;  // the call's key_max words, or null where the sort reads none
+};
+
 struct msm377_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -116,7 +126,8 @@ struct msm377_ctx {
   uint32_t last_wc = 0;
   uint32_t last_geom_windows = 0, last_geom_log = 0;  // window slots and bucket_log of the last enqueue (msm377_ctx_get_last_geometry)
   int last_form = -1;  // MSM377_STAGE_FORM_* of the buckets the last call left (stage read-backs)
-  bool capture = false;
+  int capture = 0;  // msm377_ctx_set_stage_capture: 0 off, 1 the sixteen-equal-windows route of msm377_g1_read_stage, 2 as run
+  StageLayout stage;  // what the last enqueue_windows launched with (msm377_g1_read_stage_ex)
   // Zero-copy output of the full-MSM path (k_gather_partials, wait_zero_copy_out); MSM377_ZERO_COPY_OUT=0: D2H copies + event.
   int zc_out = 1;
   bool zc_active = false;         // the call being enqueued / waited for uses it
@@ -187,5 +198,6 @@ struct msm377_ctx {
   uint32_t base_checks = 0;
   msm377_check_report last_check = {0, 0, 0, 0, UINT64_MAX, 0, 0};
   uint64_t fallback_count = 0;  // reruns on the Weierstrass path after an exceptional case of the Edwards law
+  uint64_t geometry_reruns = 0; // passes discarded because a scalar did not fit their window geometry (ERR_NARROW_RANGE) and run again on another; msm377_stage_info
   uint32_t fallback_mask = 0;   // MSM377_FB_* bits of the last one
 };

@@ -321,6 +321,8 @@ int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scala
   hipStream_t st = ctx->stream;
   int* d_err = ctx->d_err + slot;
   uint32_t* d_partials = ctx->d_partials + (size_t)slot * SLOT_WORDS;
+  StageLayout& layout = ctx->stage;  // set again at the end of a whole call under stage capture
+  layout.valid = false;
   // the error word is cleared by the call's first kernel together with its counters -- unless there is no such kernel
   // (back phase only)
   if (ph.clear_err && !ph.front) hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(256), 0, st, (uint32_t*)d_err, 1u, (uint32_t*)nullptr, 0u);
@@ -369,16 +371,39 @@ int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scala
     // only within each window: the accumulation kernel went from 0.038 to 0.054 ms at 2^12.)
     {
       StageTimer t(ctx, MSM377_STAGE_DECOMPOSE, st);
-      if (ph.short_bytes)  // the top slot of the main path: unsigned digits, its ranges narrowed by its largest key (win_shift)
-        launch_decompose_short(st, d_scalars, digits, n, ph.short_bytes, ph.short_bits, L, wc, narrow ? NB : 32768u, narrow ? NB : 0u, d_err, narrow ? nullptr : key_max + (wc - 1));
-      else if (wide)
+      // The stage layout (msm377_g1_read_stage_ex) is written here, from the very values the launches below are given.
+      layout.info = msm377_stage_info{};
+      layout.info.slots = wc;
+      layout.info.bucket_log = L;
+      layout.info.columns = entries / wc;  // n; 2 n_scalars behind the GLV front end; 13 n in the one slot of the wide table
+      layout.info.digit_bytes = wide ? 4u : 2u;
+      layout.info.row_ptr_len = NB + 2;
+      layout.info.bucket_records = NB;
+      layout.info.form = CV::FORM_ID;
+      layout.info.table_stride = ph.table_stride;
+      layout.info.geometry_reruns = ctx->geometry_reruns;
+      layout.d_digits = wide ? (const void*)ctx->wide.digits : (const void*)digits;
+      layout.d_key_max = (wide || narrow) ? nullptr : key_max;  // k_local_sort_lds of the wide table and k_small_sort read none
+      static_assert(MAX_WINDOW_SLOTS <= MSM377_STAGE_MAX_SLOTS, "a stage layout names every window slot");
+      uint32_t bias = 1u << (MSM377_WINDOW_BITS - 1);  // k_decompose / k_decompose_glv: digit_key's bias
+      if (ph.short_bytes) {  // the top slot of the main path: unsigned digits, its ranges narrowed by its largest key (win_shift)
+        bias = narrow ? NB : 32768u;
+        const uint32_t top_bias = narrow ? NB : 0u;
+        launch_decompose_short(st, d_scalars, digits, n, ph.short_bytes, ph.short_bits, L, wc, bias, top_bias, d_err, narrow ? nullptr : key_max + (wc - 1));
+        for (uint32_t s = 0; s < wc; s++) layout.info.bias[s] = s + 1 < wc ? bias : top_bias;
+        layout.info.key_unsigned[wc - 1] = narrow ? 0u : 1u;  // (KEY_UNSIGNED in that slot's key_max word)
+      } else if (wide) {
+        bias = 1u << WIDE_LOG;  // k_decompose_wide's BIAS
         hipLaunchKernelGGL(k_decompose_wide, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, ctx->wide.digits, n, d_err);
-      else if (narrow)
-        hipLaunchKernelGGL(k_decompose_geom, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, digits, n, L, NARROW_EVEN_SIGNED, wc, 1u << L, d_err);
-      else if (glv)
+      } else if (narrow) {
+        bias = 1u << L;
+        hipLaunchKernelGGL(k_decompose_geom, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, digits, n, L, NARROW_EVEN_SIGNED, wc, bias, d_err);
+      } else if (glv)
         hipLaunchKernelGGL(k_decompose_glv, dim3((unsigned)((n_scalars + 255) / 256)), dim3(256), 0, st, d_scalars, digits, n_scalars, wb, wc, d_err);
       else
         hipLaunchKernelGGL(k_decompose, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, digits, n, wb, wc, d_err, top_key_max, ph.even ? 1u : 0u);
+      if (!ph.short_bytes)
+        for (uint32_t s = 0; s < wc; s++) layout.info.bias[s] = bias;
       HIP_TRY(ctx, hipGetLastError());
     }
 
@@ -548,6 +573,8 @@ int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scala
   ctx->last_geom_log = L;
   ctx->last_glv = glv;
   ctx->last_form = CV::FORM_ID;
+  // A whole call in one piece from window 0 in a form with read-backs: the layout written at the decomposition describes it.
+  layout.valid = ctx->capture && ph.front && !ph.into && wb == 0 && CV::FORM_ID >= 0;
   return MSM377_OK;
 }
 
@@ -693,11 +720,11 @@ int g1_table_msm(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n, int for
       ph.table_stride = ctx->resident.n;
     }
     // Small inputs: narrow windows (k_decompose_geom); the window-indexed buffers are sized for them too
-    // (msm377_ctx_create: wcap).  Stage read-backs describe the 16-bit geometry.
-    bool narrow = form != TABLE_TE_PRECOMP && n <= ctx->narrow_max_points && n <= SMALL_SORT_MAX && !ctx->capture;
+    // (msm377_ctx_create: wcap).  Capture mode 1 describes the 16-bit geometry.
+    bool narrow = form != TABLE_TE_PRECOMP && n <= ctx->narrow_max_points && n <= SMALL_SORT_MAX && ctx->capture != 1;
     bool wide = form == TABLE_TE_PRECOMP && wide_table(ctx->resident);
     bool table0 = false;  // the 16-window path over window 0 of the wide table (= the affine records of the points themselves)
-    bool even = ctx->even_windows && form != TABLE_TE_PRECOMP && !ctx->capture;  // (stage read-backs describe sixteen equal windows)
+    bool even = ctx->even_windows && form != TABLE_TE_PRECOMP && ctx->capture != 1;  // (capture mode 1 describes sixteen equal windows)
     for (;;) {
       uint32_t windows = MSM377_NUM_WINDOWS;
       int cbits = MSM377_WINDOW_BITS, planes = MSM377_WINDOW_BITS - 1, short_from = 0;  // the host tail's view of the geometry
@@ -734,15 +761,18 @@ int g1_table_msm(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n, int for
       if (narrow && (ctx->h_err[0] & ERR_NARROW_RANGE) && !(ctx->h_err[0] & ERR_SCALAR)) {  // a scalar >= 2^253: sixteen 16-bit windows take it
         narrow = false;
         even = false;
+        ctx->geometry_reruns++;
         continue;
       }
       if (ph.even && (ctx->h_err[0] & ERR_NARROW_RANGE) && !(ctx->h_err[0] & ERR_SCALAR)) {  // likewise: sixteen equal windows take it
         even = false;
+        ctx->geometry_reruns++;
         continue;
       }
       if (wide && (ctx->h_err[0] & ERR_NARROW_RANGE) && !(ctx->h_err[0] & ERR_SCALAR)) {  // likewise: its top window holds 19 bits
         wide = false;
         table0 = true;
+        ctx->geometry_reruns++;
         ph.wide = false;
         ph.table = nullptr;
         ph.table_stride = 0;  // every window slot gathers from the same records
@@ -776,6 +806,7 @@ int g1_table_msm(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n, int for
       time_tail(ctx, t0);
       return MSM377_OK;
     }
+    ctx->geometry_reruns++;  // a half scalar of 2^127 and more: the GLV pass is discarded, sixteen plain windows take the call
   }
   int rc = run_windows<G1Dev>(ctx, d_scalars, n, 0, MSM377_NUM_WINDOWS);
   if (rc) return rc;
@@ -826,7 +857,7 @@ int g1_short_table_msm(msm377_ctx* ctx, const void* d_scalars, uint64_t n, int f
       ph.table = ctx->resident.table;
       ph.table_stride = ctx->resident.n;
     }
-    if (!precomp && n <= ctx->narrow_max_points && n <= SMALL_SORT_MAX && !ctx->capture) {
+    if (!precomp && n <= ctx->narrow_max_points && n <= SMALL_SORT_MAX && ctx->capture != 1) {
       ph.cbits = NARROW_EVEN_BITS;
       ph.bucket_log = NARROW_LOG;
     }
@@ -1284,6 +1315,7 @@ int g1_msm(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint6
     if (even && (ctx->h_err[0] & ERR_NARROW_RANGE) && !(ctx->h_err[0] & (ERR_SCALAR | ERR_TE_ANY))) {
       // a scalar of 2^253 and more: everything is on the device by now, rerun in one piece (g1_table_msm falls back to
       // sixteen equal windows by itself)
+      ctx->geometry_reruns++;
       rc = convert_table(ctx, d_pt, n, form);
       if (rc) return rc;
       rc = g1_table_msm(ctx, d_sc, n, form, out_xy);
@@ -1451,7 +1483,7 @@ int ed_msm_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, 
   if (rc) return rc;
   TailArm arm(ctx);
   arm.at_start(n);
-  bool even = ctx->even_windows && !ctx->capture && !ctx->ed_equal_windows_once;
+  bool even = ctx->even_windows && ctx->capture != 1 && !ctx->ed_equal_windows_once;
   ctx->ed_equal_windows_once = false;
   for (;;) {
     Phase ph;
@@ -1468,6 +1500,7 @@ int ed_msm_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, 
     }
     if (even && (ctx->h_err[0] & ERR_NARROW_RANGE) && !(ctx->h_err[0] & ERR_SCALAR)) {  // a scalar of 2^253 and more: sixteen equal windows
       even = false;
+      ctx->geometry_reruns++;
       continue;
     }
     rc = finish_windows(ctx, 0);
@@ -1496,6 +1529,7 @@ int ed_msm(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint6
     const bool even = upload_even<EdDev>(ctx);
     if (even && (ctx->h_err[0] & ERR_NARROW_RANGE) && !(ctx->h_err[0] & ERR_SCALAR)) {  // everything is on the device: once more in one piece
       ctx->ed_equal_windows_once = true;
+      ctx->geometry_reruns++;
       return ed_msm_device(ctx, ctx->d_raw_points, ctx->d_raw_scalars, n, out_xy);
     }
     rc = finish_windows(ctx, 0);
@@ -1752,6 +1786,7 @@ static int fixed_base_batch_share(msm377_ctx* ctx, const void* d_scalars, uint64
       }
       if ((wide || even) && (ctx->h_err[slot] & ERR_NARROW_RANGE) && !(ctx->h_err[slot] & ERR_SCALAR)) {
         redo_wide.push_back(b - 1);
+        ctx->geometry_reruns++;
         continue;
       }
       rc = finish_windows(ctx, slot);

@@ -48,6 +48,44 @@ class _CheckReportStruct(ctypes.Structure):  # msm377_check_report
     ]
 
 
+STAGE_MAX_SLOTS = 22
+
+
+class _StageInfoStruct(ctypes.Structure):  # msm377_stage_info
+    _fields_ = [
+        ("slots", ctypes.c_uint32),
+        ("bucket_log", ctypes.c_uint32),
+        ("columns", ctypes.c_uint64),
+        ("digit_bytes", ctypes.c_uint32),
+        ("row_ptr_len", ctypes.c_uint32),
+        ("bucket_records", ctypes.c_uint32),
+        ("form", ctypes.c_int32),
+        ("table_stride", ctypes.c_uint64),
+        ("geometry_reruns", ctypes.c_uint64),
+        ("bias", ctypes.c_uint32 * STAGE_MAX_SLOTS),
+        ("key_unsigned", ctypes.c_uint32 * STAGE_MAX_SLOTS),
+        ("key_max", ctypes.c_uint32 * STAGE_MAX_SLOTS),
+    ]
+
+
+class StageInfo(NamedTuple):
+    """msm377_stage_info: the layout of the last call's last pass as its kernels were launched (include/msm377.h);
+    ``bias``, ``key_unsigned`` and ``key_max`` hold one entry per window slot."""
+
+    slots: int
+    bucket_log: int
+    columns: int
+    digit_bytes: int
+    row_ptr_len: int
+    bucket_records: int
+    form: int
+    table_stride: int
+    geometry_reruns: int
+    bias: Tuple[int, ...]
+    key_unsigned: Tuple[int, ...]
+    key_max: Tuple[int, ...]
+
+
 class CheckReport(NamedTuple):
     """msm377_check_report: a point is counted once, in the first class it fails; ``first_bad`` is the lowest failing
     index (None if every point passed) and ``first_bad_reason`` the CHECK_* bit it failed (0 if none)."""
@@ -142,6 +180,7 @@ def load_library():
         "msm377_ed_generate_bases_device": (i32, [vp, u64, u64, vp]),
         "msm377_ctx_set_stage_capture": (i32, [vp, i32]),
         "msm377_g1_read_stage": (i32, [vp, u32, vp, vp, vp, vp]),
+        "msm377_g1_read_stage_ex": (i32, [vp, u32, vp, vp, vp, vp, vp]),
         "msm377_g1_xyzz_to_affine": (i32, [vp, vp]),
         "msm377_g1_fold_window_partials": (i32, [vp, ctypes.c_uint32]),
         "msm377_ctx_set_glv": (i32, [vp, i32]),
@@ -608,8 +647,32 @@ class MsmEngine:
         self._check(self._lib.msm377_ed_generate_bases_device(self._ctx, int(seed) & (2**64 - 1), int(n), d_points_out), "msm377_ed_generate_bases_device")
 
     # -- stage access (the reference's debug=true read-backs) --
-    def set_stage_capture(self, enabled: bool = True):
-        self._check(self._lib.msm377_ctx_set_stage_capture(self._ctx, int(bool(enabled))), "msm377_ctx_set_stage_capture")
+    def set_stage_capture(self, mode=True):
+        """Stage capture mode (msm377_ctx_set_stage_capture): False / 0 off, True / 1 the sixteen-equal-windows route that
+        read_stage describes, 2 as run -- the call keeps its own route and read_stage_ex describes its last pass."""
+        self._check(self._lib.msm377_ctx_set_stage_capture(self._ctx, int(mode)), "msm377_ctx_set_stage_capture")
+
+    def read_stage_ex(self, slot: int, want=("digits", "row_ptr", "val_idx", "buckets")):
+        """(StageInfo, dict of numpy arrays) for window slot ``slot`` of the last call's last pass, at the sizes the
+        library reports (msm377_g1_read_stage_ex).  MsmError(ESTATE) when nothing describable was captured."""
+        import numpy as np
+
+        raw = _StageInfoStruct()
+        self._check(self._lib.msm377_g1_read_stage_ex(self._ctx, int(slot), ctypes.addressof(raw), None, None, None, None), "msm377_g1_read_stage_ex")
+        w = int(raw.slots)
+        info = StageInfo(w, int(raw.bucket_log), int(raw.columns), int(raw.digit_bytes), int(raw.row_ptr_len), int(raw.bucket_records), int(raw.form),
+                         int(raw.table_stride), int(raw.geometry_reruns), tuple(raw.bias[:w]), tuple(raw.key_unsigned[:w]), tuple(raw.key_max[:w]))
+        bufs = {
+            "digits": np.empty(info.columns, dtype=np.uint32 if info.digit_bytes == 4 else np.uint16),
+            "row_ptr": np.empty(info.row_ptr_len, dtype=np.uint32),
+            "val_idx": np.empty(info.columns, dtype=np.uint32),
+            "buckets": np.empty((info.bucket_records, POINT_WORDS), dtype=np.uint32),
+        }
+        res = {k: v for k, v in bufs.items() if k in want}
+        if res:
+            ptr = [res[k].ctypes.data if k in res else None for k in ("digits", "row_ptr", "val_idx", "buckets")]
+            self._check(self._lib.msm377_g1_read_stage_ex(self._ctx, int(slot), None, *ptr), "msm377_g1_read_stage_ex")
+        return info, res
 
     def read_stage(self, slot: int, n: int, want=("digits", "row_ptr", "val_idx", "buckets")):
         """Returns a dict of numpy arrays for window slot ``slot`` of the last call."""
