@@ -223,6 +223,10 @@ uint32_t msm377_short_windows(uint32_t scalar_bits, uint32_t bucket_log);
 /* Window slots and bucket_log (L) of the last G1 MSM call's last pass on this context, e.g. (16, 15), (22, 11),
  * (1, 19) on the 20-bit table, (5, 15) for a 64-bit short call; (0, 0) before the first call. */
 int msm377_ctx_get_last_geometry(const msm377_ctx* ctx, uint32_t* windows, uint32_t* bucket_log);
+/* Bytes per element of the sort's intermediate buffer in the last call's last pass: 8; 4 (packed) with MSM377_SORT_ELEM=4
+ * in the environment when the context was created, for calls of at most 2^23 columns on the two-level sort of the
+ * 2^15-bucket path; 0 where no such sort ran (narrow windows, before the first call).  Results do not depend on it. */
+uint32_t msm377_ctx_get_last_sort_elem_bytes(const msm377_ctx* ctx);
 
 /* ---- native input forms ---------------------------------------------------------------------
  * A prover built on arkworks or snarkVM keeps nothing in the wire format above: field elements live in Montgomery form

@@ -76,6 +76,7 @@ int msm377_ctx_create(int device, uint64_t max_points, msm377_ctx** out) {
   if (const char* e = getenv("MSM377_NARROW_TAIL_FROM")) ctx->narrow_tail_from = (uint32_t)std::min(std::max(atoi(e), 1), (int)TREE_LEVELS);
   if (const char* e = getenv("MSM377_TAIL_LDS")) ctx->tail_lds = atoi(e) != 0;
   if (const char* e = getenv("MSM377_EVEN_WINDOWS")) ctx->even_windows = atoi(e) != 0;
+  if (const char* e = getenv("MSM377_SORT_ELEM")) ctx->sort_elem = atoi(e) == 4 ? 4u : 8u;
   if (const char* e = getenv("MSM377_TWIN_BATCH")) ctx->twin_batches = atoi(e) != 0;
   if (const char* e = getenv("MSM377_BASE_CHECKS")) ctx->base_checks = check_flags_normal((uint32_t)strtoul(e, nullptr, 0));  // (an invalid mask reads as 0)
   if (const char* e = getenv("MSM377_TAIL_FROM")) ctx->tail_from = (uint32_t)std::min(std::max(atoi(e), 1), (int)TREE_LEVELS);
@@ -467,6 +468,8 @@ int msm377_ctx_get_last_geometry(const msm377_ctx* ctx, uint32_t* windows, uint3
   if (bucket_log) *bucket_log = ctx->last_geom_log;
   return MSM377_OK;
 }
+
+uint32_t msm377_ctx_get_last_sort_elem_bytes(const msm377_ctx* ctx) { return ctx ? ctx->last_sort_elem : 0u; }
 
 int msm377_ctx_set_narrow_max(msm377_ctx* ctx, uint64_t max_points) {
   if (!ctx) return MSM377_EINVAL;

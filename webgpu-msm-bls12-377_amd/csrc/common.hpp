@@ -5,6 +5,15 @@
 
 #include "../../include/msm377.h"
 
+#ifndef MSM_HD  // as in field29.hpp, for translation units that include this header alone
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define MSM_HD __host__ __device__ __forceinline__
+#else
+#define MSM_HD inline __attribute__((always_inline))
+#endif
+#endif
+
 namespace msm377 {
 
 constexpr uint32_t NB = 32768;     // buckets per window: |d| = 1..32768
@@ -12,7 +21,7 @@ constexpr uint32_t NBIN = NB + 1;  // sort keys 0..32768 (key 0 = digit 0, never
 constexpr uint32_t RP = NBIN + 1;  // row_ptr entries per window
 constexpr uint32_t PT_WORDS = 52;  // X, Y, ZZ, ZZZ
 constexpr uint32_t BKT_WORDS = 64; // the largest bucket record (four 64-byte coordinate slots), sizes the shared buffers
-constexpr uint32_t MAX_SORT_BLOCKS = 256;  // (window slot, chunk) blocks of the partition pass
+constexpr uint32_t MAX_SORT_BLOCKS = 256;  // (window slot, chunk) blocks of the partition pass (512 measured the same with packed sort elements)
 constexpr uint32_t TREE_LEVELS = 15;       // log2(NB)
 constexpr uint32_t SEG_MIN = 16;           // entries per accumulation work item (one thread), see auto_seg(); the work-item and overflow buffers are sized for SEG_MIN
 constexpr uint32_t SEG_MAX = 128;
@@ -54,6 +63,25 @@ struct SortElem {
   uint32_t idx_sign;  // point index | sign << 31
   uint32_t key;       // |d|
 };
+// The packed element of the main path's sort_temp: inside region r of a window the key is known up to its offset in
+// the range, so 4 bytes hold an element.  bit 31: sign; bits 30..23: sub = key - first key of its range in that window's
+// range geometry, 0..KRANGE (KRANGE itself only in the last range of a full-width window, for key NB); bits 22..0: the
+// column index.  Calls of more than SORT_PACKED_MAX_COLUMNS columns and the wide table (indices to 13 n) keep SortElem.
+struct SortElem4 {
+  uint32_t v;
+};
+constexpr uint32_t SORT_IDX_BITS = 23, SORT_SUB_BITS = 8;
+constexpr uint64_t SORT_PACKED_MAX_COLUMNS = 1ull << SORT_IDX_BITS;
+static_assert(SORT_IDX_BITS + SORT_SUB_BITS + 1 == 32, "index, sub and sign fill the 32-bit element");
+static_assert(KRANGE < (1u << SORT_SUB_BITS), "sub = 0..KRANGE fits its field");
+MSM_HD SortElem4 sort_pack(uint32_t idx, uint32_t sign, uint32_t sub) { return SortElem4{(sign << 31) | (sub << SORT_IDX_BITS) | idx}; }
+MSM_HD uint32_t sort_sub(SortElem4 e) { return (e.v >> SORT_IDX_BITS) & ((1u << SORT_SUB_BITS) - 1u); }
+MSM_HD uint32_t sort_idx_sign(SortElem4 e) { return e.v & ~(((1u << SORT_SUB_BITS) - 1u) << SORT_IDX_BITS); }  // index | sign << 31: a val_idx entry
+// First key of coarse range rg in a window whose ranges are narrowed by `shift` (kernels/decompose.hpp win_shift, key_range).
+MSM_HD uint32_t range_first_key(uint32_t rg, uint32_t shift) { return rg * (KRANGE >> shift); }
+// Bytes per sort_temp element of a call: the packed form while every column index fits its field (columns = n, or 2 n
+// behind the GLV front end) and the call is not the wide table's.
+inline uint32_t sort_elem_bytes(uint64_t columns, bool wide) { return (!wide && columns <= SORT_PACKED_MAX_COLUMNS) ? 4u : 8u; }
 
 // ---- accumulation work list (kernels/accumulate.hpp) ----
 struct WorkItem {

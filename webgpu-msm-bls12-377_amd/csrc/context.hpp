@@ -78,7 +78,7 @@ struct msm377_ctx {
   uint16_t* d_digits = nullptr;       // 16 x cap
   uint32_t* d_range_counts = nullptr; // NRANGE x (window slots x chunks <= MAX_SORT_BLOCKS): per-chunk range counts, then write offsets
   uint32_t* d_region_base = nullptr;  // 16 x (NRANGE + 1)
-  SortElem* d_sort_temp = nullptr;    // 16 x cap partitioned (index|sign, key) pairs
+  SortElem* d_sort_temp = nullptr;    // 16 x cap partitioned (index|sign, key) pairs; the packed form (SortElem4) fills half of it
   uint32_t* d_row_ptr = nullptr;      // 16 x RP
   uint32_t* d_val_idx = nullptr;      // 16 x cap
   uint32_t* d_buckets = nullptr;      // 16 x 52 x NB
@@ -125,6 +125,7 @@ struct msm377_ctx {
   uint64_t last_n = 0;
   uint32_t last_wc = 0;
   uint32_t last_geom_windows = 0, last_geom_log = 0;  // window slots and bucket_log of the last enqueue (msm377_ctx_get_last_geometry)
+  uint32_t last_sort_elem = 0;  // bytes per sort_temp element of the last enqueue's sort, 0: the narrow path (msm377_ctx_get_last_sort_elem_bytes)
   int last_form = -1;  // MSM377_STAGE_FORM_* of the buckets the last call left (stage read-backs)
   int capture = 0;  // msm377_ctx_set_stage_capture: 0 off, 1 the sixteen-equal-windows route of msm377_g1_read_stage, 2 as run
   StageLayout stage;  // what the last enqueue_windows launched with (msm377_g1_read_stage_ex)
@@ -188,6 +189,11 @@ struct msm377_ctx {
   // Batches on two sets of streams and buffers (sequencer.hip twin_prepare)
   bool tail_lds = true;         // MSM377_TAIL_LDS=0: the single-launch reduction tail works in global memory (k_reduce_tail)
   bool even_windows = true;     // MSM377_EVEN_WINDOWS=0: sixteen 16-bit windows on the 16-window paths (kernels/decompose.hpp k_decompose); the narrow path keeps its geometry
+  // MSM377_SORT_ELEM: bytes per sort_temp element of the main path's sort.  8 (default): SortElem.  4: the packed SortElem4
+  // wherever the call allows it (common.hpp sort_elem_bytes), for A/B runs and the tests, which run both forms.  Interleaved
+  // A/B at 2^20, 15 pairs (profiles/sort_elem4/ab_sort_elem.txt): sort stage 0.264 -> 0.249 ms, k_accumulate starts 12-17 us
+  // sooner, whole MSM 2.477 -> 2.469 ms (medians) with run-to-run spreads of 0.06 and 0.09: inside the noise, so 8 stays the default.
+  uint32_t sort_elem = 8;
   bool ed_equal_windows_once = false;  // ed_msm -> ed_msm_device: this call reruns a chunked upload whose scalars did not fit
   uint32_t acc_seq = 0;  // calls' accumulation kernels so far; h_out_flag[ACC_FLAG_WORD] follows it (k_merge_split_rows_quad)
   msm377_ctx* twin = nullptr;   // owned; borrows `resident` for the length of a batch call

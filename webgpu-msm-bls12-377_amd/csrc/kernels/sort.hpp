@@ -13,8 +13,9 @@ namespace {
 // Two-level (MSD) counting sort; every pass touches each (window, point) element once:
 //   k_range_count  block (chunk, window): LDS histogram of the chunk over 256 coarse key ranges
 //   k_range_scan   block per window: region bases per range, per-chunk write offsets
-//   k_partition_staged  block (chunk, window): appends each element (index|sign, key) to its
-//                  range's region at LDS-ranked offsets, a tile at a time -- contiguous runs, no global atomics
+//   k_partition_staged  block (chunk, window): appends each element (index|sign, key -- or, packed into 4 bytes,
+//                  index|sign|key's offset in its range: SortElem4) to its range's region at LDS-ranked offsets,
+//                  a tile at a time -- contiguous runs, no global atomics
 //   k_local_sort_lds  block (range, window): counting sort of the region's <= 129 keys in LDS;
 //                  writes its row_ptr slice and its val_idx slice, a CONTIGUOUS output owned by
 //                  one block, so the 4-byte stores combine in that XCD's L2.
@@ -93,6 +94,29 @@ __global__ void __launch_bounds__(NRANGE) k_range_scan(uint32_t* __restrict__ co
   }
 }
 
+// What the two kernels below need of a sort_temp element: SortElem carries the whole key, SortElem4 (common.hpp) its
+// offset `sub` in the range -- the range is the region the element lies in, so neither kernel needs more.
+template <class E>
+struct ElemOps;
+template <>
+struct ElemOps<SortElem> {
+  static constexpr bool TAGGED = false;  // the drain of the staged tile finds an element's range from its key
+  static __device__ __forceinline__ SortElem make(uint32_t idx, uint32_t sign, uint32_t key, uint32_t, uint32_t) { return SortElem{idx | (sign << 31), key}; }
+  static __device__ __forceinline__ SortElem none(uint32_t lo) { return SortElem{0u, lo}; }
+  static __device__ __forceinline__ uint32_t bin(SortElem e, uint32_t lo) { return e.key - lo; }
+  static __device__ __forceinline__ uint32_t idx_sign(SortElem e) { return e.idx_sign; }
+};
+template <>
+struct ElemOps<SortElem4> {
+  static constexpr bool TAGGED = true;  // ... from a one-byte range tag that stays in LDS
+  static __device__ __forceinline__ SortElem4 make(uint32_t idx, uint32_t sign, uint32_t key, uint32_t rg, uint32_t shift) {
+    return sort_pack(idx, sign, key - range_first_key(rg, shift));
+  }
+  static __device__ __forceinline__ SortElem4 none(uint32_t) { return SortElem4{0u}; }
+  static __device__ __forceinline__ uint32_t bin(SortElem4 e, uint32_t) { return sort_sub(e); }
+  static __device__ __forceinline__ uint32_t idx_sign(SortElem4 e) { return sort_idx_sign(e); }
+};
+
 // The partition pass, its scatter staged through LDS (round 3).  Round 2's k_partition appended every element straight to
 // one of 256 write streams per workgroup, 8 bytes at a time; a stream advances by 2 KB over the workgroup's whole life,
 // so its lines left L2 half-written: WRITE_SIZE 184 MB for 131 MB of sort_temp, 87 us.  Here a workgroup takes its
@@ -100,17 +124,24 @@ __global__ void __launch_bounds__(NRANGE) k_range_scan(uint32_t* __restrict__ co
 // left), an exclusive scan over the 256 ranges, the elements parked in LDS in range order, and then the tile is written
 // out by consecutive lanes -- a range's ~32 elements of the tile are one contiguous run of its stream, so whole lines go
 // out in one piece and only the two ends of a run are partial.  Interleaved A/B at 2^20: sort stage 0.344 -> 0.314 ms.
-constexpr uint32_t PT_TILE = 8192;  // 8 digits (one 16-byte load) per thread; 64 KB of staging: two workgroups per CU
-template <bool UNS = false>
+// E = SortElem4: 4 bytes per element to sort_temp and 32 KB of staging plus 8 KB of range tags (an element's range is
+// not in its word: the drain reads it from the tag; the tags never leave LDS).
+// (A tile of 16384 packed elements, two 16-byte loads per thread and 84 KB of LDS, one workgroup per CU: 2.509 against
+// 2.450 ms per MSM at 2^20, profiles/sort_elem4/ab_sort_elem.txt.)
+constexpr uint32_t PT_TILE = 8192;  // 8 digits (one 16-byte load) per thread; 64 KB of staging with SortElem: two workgroups per CU
+template <class E, bool UNS = false>
 __global__ void __launch_bounds__(1024) k_partition_staged(const uint16_t* __restrict__ digits, const uint32_t* __restrict__ counts,
-                                                           SortElem* __restrict__ temp, uint64_t n, uint32_t chunks, uint64_t per_chunk,
+                                                           E* __restrict__ temp, uint64_t n, uint32_t chunks, uint64_t per_chunk,
                                                            const uint32_t* __restrict__ key_max) {
+  using Ops = ElemOps<E>;
   __shared__ uint32_t cur[NRANGE];     // this workgroup's write cursor in every range's region
   __shared__ uint32_t cnt[NRANGE];     // elements of the tile per range
   __shared__ uint32_t toff[NRANGE];    // first slot of the range in the staged tile
   __shared__ uint32_t gdelta[NRANGE];  // region position of a staged element = its slot + gdelta[range]
   __shared__ uint32_t wsum[NRANGE / 64];
-  __shared__ SortElem stage[PT_TILE];
+  __shared__ E stage[PT_TILE];
+  __shared__ uint8_t tag[Ops::TAGGED ? PT_TILE : 1];  // range of the staged element
+  static_assert(NRANGE <= 256, "a range fits the one-byte tag");
   const uint32_t c = blockIdx.x, ws = blockIdx.y, tid = threadIdx.x;
   const uint32_t shift = win_shift(key_max[ws]);
   const bool uns = UNS && (key_max[ws] & KEY_UNSIGNED) != 0;
@@ -122,7 +153,7 @@ __global__ void __launch_bounds__(1024) k_partition_staged(const uint16_t* __res
   const uint64_t beg = (uint64_t)c * per_chunk;
   const uint64_t end = (beg + per_chunk < n) ? beg + per_chunk : n;
   const uint16_t* dg = digits + (size_t)ws * n;
-  SortElem* out = temp + (size_t)ws * n;
+  E* out = temp + (size_t)ws * n;
   for (uint64_t tile0 = beg; tile0 < end; tile0 += PT_TILE) {
     const uint64_t i0 = tile0 + (uint64_t)tid * 8;
     uint32_t d[8];
@@ -180,12 +211,21 @@ __global__ void __launch_bounds__(1024) k_partition_staged(const uint16_t* __res
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < 8; j++)
-      if ((valid >> j) & 1u) stage[toff[rg[j]] + rk[j]] = SortElem{(uint32_t)(i0 + j) | (sign[j] << 31), key[j]};
+      if ((valid >> j) & 1u) {
+        const uint32_t slot = toff[rg[j]] + rk[j];
+        stage[slot] = Ops::make((uint32_t)(i0 + j), sign[j], key[j], rg[j], shift);
+        if constexpr (Ops::TAGGED) tag[slot] = (uint8_t)rg[j];
+      }
     __syncthreads();
     const uint32_t tile_len = (uint32_t)((end - tile0 < PT_TILE) ? end - tile0 : PT_TILE);
     for (uint32_t p = tid; p < tile_len; p += 1024) {
-      const SortElem e = stage[p];
-      out[gdelta[key_range(e.key, shift)] + p] = e;
+      const E e = stage[p];
+      uint32_t range;
+      if constexpr (Ops::TAGGED)
+        range = tag[p];
+      else
+        range = key_range(e.key, shift);
+      out[gdelta[range] + p] = e;
     }
     __syncthreads();
   }
@@ -198,13 +238,18 @@ __global__ void __launch_bounds__(1024) k_partition_staged(const uint16_t* __res
 // random places of the slice, and 25 KB of LDS per workgroup (round 2 kept the region in 48 KB of LDS and scattered
 // straight to val_idx: three workgroups per CU and no room for the base conversion that runs beside the sort; interleaved
 // A/B at 2^20: sort stage 0.344 -> 0.296 ms, whole MSM 2.60 -> 2.55).  Longer regions (skewed scalars) are streamed twice.
+// E = SortElem4: the bin of an element is its sub field (lo = r KR is the first key of the range in this window's
+// geometry, so key - lo = sub), and the region in registers is 24 words per thread instead of 48.
 constexpr uint32_t LS_CACHE = 6144;           // region length (n / 256 = 4096 on average at n = 2^20) the register / LDS path holds
+// (8192 for packed elements: sort stage 0.237 against 0.249 ms at 2^20, whole MSM within the noise: profiles/sort_elem4/ab_sort_elem.txt.)
 constexpr uint32_t LS_REG = LS_CACHE / 256;  // elements per thread
-__global__ void __launch_bounds__(256) k_local_sort_lds(const SortElem* __restrict__ temp, const uint32_t* __restrict__ region_base,
+template <class E>
+__global__ void __launch_bounds__(256) k_local_sort_lds(const E* __restrict__ temp, const uint32_t* __restrict__ region_base,
                                                         uint32_t* __restrict__ row_ptr, uint32_t* __restrict__ val_idx, uint64_t n,
                                                         const uint32_t* __restrict__ key_max, uint32_t NR, uint32_t NBK) {
   // NR ranges per window over keys 0 .. NBK (256 x 2^15 on the main path; 4096 x 2^19, one window, no key_max, for the
   // wide windows of kernels/wide.hpp); the last range also owns key NBK.
+  using Ops = ElemOps<E>;
   constexpr uint32_t NBINS = KRANGE + 1;  // keys of a range, bin = key - lo; a thread owns one in the scan
   static_assert(NBINS <= 256, "one bin per thread");
   __shared__ uint32_t bins[NBINS];
@@ -220,34 +265,32 @@ __global__ void __launch_bounds__(256) k_local_sort_lds(const SortElem* __restri
   const uint32_t rbeg = region_base[ws * (NR + 1) + r], rend = region_base[ws * (NR + 1) + r + 1];
   const uint32_t len = rend - rbeg;
   const bool cached = len <= LS_CACHE;
-  const SortElem* in = temp + (size_t)ws * n + rbeg;
+  const E* in = temp + (size_t)ws * n + rbeg;
   if (tid < NBINS) bins[tid] = 0;
   __syncthreads();
-  SortElem e[LS_REG];
+  E e[LS_REG];
   if (cached) {
 #pragma unroll
     for (uint32_t u = 0; u < LS_REG; u++) {
       const uint32_t i = u * 256 + tid;
-      e[u].key = lo;
-      e[u].idx_sign = 0;
+      e[u] = Ops::none(lo);
       if (i < len) e[u] = in[i];
     }
 #pragma unroll
     for (uint32_t u = 0; u < LS_REG; u++)
-      if (u * 256 + tid < len) atomicAdd(&bins[e[u].key - lo], 1u);
+      if (u * 256 + tid < len) atomicAdd(&bins[Ops::bin(e[u], lo)], 1u);
   } else {
     for (uint32_t i0 = 0; i0 < len; i0 += 2048) {
-      SortElem f[8];
+      E f[8];
 #pragma unroll
       for (int u = 0; u < 8; u++) {
         const uint32_t i = i0 + u * 256 + tid;
-        f[u].key = lo;
-        f[u].idx_sign = 0;
+        f[u] = Ops::none(lo);
         if (i < len) f[u] = in[i];
       }
 #pragma unroll
       for (int u = 0; u < 8; u++)
-        if (i0 + u * 256 + tid < len) atomicAdd(&bins[f[u].key - lo], 1u);
+        if (i0 + u * 256 + tid < len) atomicAdd(&bins[Ops::bin(f[u], lo)], 1u);
     }
   }
   __syncthreads();
@@ -283,23 +326,22 @@ __global__ void __launch_bounds__(256) k_local_sort_lds(const SortElem* __restri
   if (cached) {
 #pragma unroll
     for (uint32_t u = 0; u < LS_REG; u++)
-      if (u * 256 + tid < len) sorted[atomicAdd(&bins[e[u].key - lo], 1u) - rbeg] = e[u].idx_sign;
+      if (u * 256 + tid < len) sorted[atomicAdd(&bins[Ops::bin(e[u], lo)], 1u) - rbeg] = Ops::idx_sign(e[u]);
     __syncthreads();
     for (uint32_t i = tid; i < len; i += 256) vi[rbeg + i] = sorted[i];
   } else {
     for (uint32_t i0 = 0; i0 < len; i0 += 2048) {
-      SortElem f[8];
+      E f[8];
 #pragma unroll
       for (int u = 0; u < 8; u++) {
         const uint32_t i = i0 + u * 256 + tid;
-        f[u].key = lo;
-        f[u].idx_sign = 0;
+        f[u] = Ops::none(lo);
         if (i < len) f[u] = in[i];
       }
 #pragma unroll
       for (int u = 0; u < 8; u++) {
         const uint32_t i = i0 + u * 256 + tid;
-        if (i < len) vi[atomicAdd(&bins[f[u].key - lo], 1u)] = f[u].idx_sign;
+        if (i < len) vi[atomicAdd(&bins[Ops::bin(f[u], lo)], 1u)] = Ops::idx_sign(f[u]);
       }
     }
   }

@@ -410,17 +410,19 @@ int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scala
     if (wide) {  // the 13 n entries into 4096 fine ranges: two staged partition passes per window (kernels/wide.hpp), then k_local_sort_lds
       StageTimer t(ctx, MSM377_STAGE_SORT, st);
       uint32_t* wc = ctx->wide.counts;
+      ctx->last_sort_elem = sort_elem_bytes(entries, true);
       hipLaunchKernelGGL(k_wide_count, dim3(WS_CHUNKS, WIDE_WINDOWS), dim3(1024), 0, st, (const uint32_t*)ctx->wide.digits, wc, n);
       hipLaunchKernelGGL(k_wide_sums, dim3(WIDE_NRANGE / 256, WIDE_WINDOWS), dim3(256), 0, st, wc);
       hipLaunchKernelGGL(k_wide_scan, dim3(1), dim3(1024), 0, st, wc, region_base);
       hipLaunchKernelGGL(k_wide_offsets1, dim3(WIDE_WINDOWS), dim3(WS_COARSE), 0, st, wc, n);
       hipLaunchKernelGGL(k_wide_part1, dim3(WS_CHUNKS, WIDE_WINDOWS), dim3(1024), 0, st, (const uint32_t*)ctx->wide.digits, (const uint32_t*)wc, sort_temp, n, (uint32_t)ph.table_stride);
       hipLaunchKernelGGL(k_wide_part2, dim3(WS_COARSE, WIDE_WINDOWS), dim3(1024), 0, st, (const SortElem*)sort_temp, (const uint32_t*)wc, ctx->wide.temp);
-      hipLaunchKernelGGL(k_local_sort_lds, dim3(WIDE_NRANGE, 1), dim3(256), 0, st, (const SortElem*)ctx->wide.temp, region_base, row_ptr, val_idx, entries,
+      hipLaunchKernelGGL(k_local_sort_lds<SortElem>, dim3(WIDE_NRANGE, 1), dim3(256), 0, st, (const SortElem*)ctx->wide.temp, region_base, row_ptr, val_idx, entries,
                          (const uint32_t*)nullptr, WIDE_NRANGE, NB);
       HIP_TRY(ctx, hipGetLastError());
     } else if (narrow) {
       StageTimer t(ctx, MSM377_STAGE_SORT, st);
+      ctx->last_sort_elem = 0;
       hipLaunchKernelGGL(k_small_sort, dim3(wc), dim3(1024), 0, st, digits, row_ptr, val_idx, (uint32_t)n, L);
       HIP_TRY(ctx, hipGetLastError());
     } else {
@@ -436,13 +438,22 @@ int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scala
       HIP_TRY(ctx, hipGetLastError());
       hipLaunchKernelGGL(k_range_scan, dim3(wc), dim3(NRANGE), 0, st, range_counts, region_base, chunks);
       HIP_TRY(ctx, hipGetLastError());
-      if (ph.short_bytes)
-        hipLaunchKernelGGL(k_partition_staged<true>, dim3(chunks, wc), dim3(1024), 0, st, digits, range_counts, sort_temp, n, chunks, per_chunk, key_max);
-      else
-        hipLaunchKernelGGL(k_partition_staged<false>, dim3(chunks, wc), dim3(1024), 0, st, digits, range_counts, sort_temp, n, chunks, per_chunk, key_max);
-      HIP_TRY(ctx, hipGetLastError());
-      hipLaunchKernelGGL(k_local_sort_lds, dim3(NRANGE, wc), dim3(256), 0, st, sort_temp, region_base, row_ptr, val_idx, n, key_max, NRANGE, NB);
-      HIP_TRY(ctx, hipGetLastError());
+      // sort_temp elements: 8 bytes, or with MSM377_SORT_ELEM=4 packed into 4 while every column index fits 23 bits
+      // (common.hpp sort_elem_bytes); the buffer is sized for 8 either way.
+      const bool packed = ctx->sort_elem == 4 && sort_elem_bytes(n, false) == 4;
+      ctx->last_sort_elem = packed ? 4u : 8u;
+      auto partition_and_sort = [&](auto* temp) {
+        using E = std::remove_pointer_t<decltype(temp)>;
+        if (ph.short_bytes)
+          hipLaunchKernelGGL((k_partition_staged<E, true>), dim3(chunks, wc), dim3(1024), 0, st, digits, range_counts, temp, n, chunks, per_chunk, key_max);
+        else
+          hipLaunchKernelGGL((k_partition_staged<E, false>), dim3(chunks, wc), dim3(1024), 0, st, digits, range_counts, temp, n, chunks, per_chunk, key_max);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_local_sort_lds<E>, dim3(NRANGE, wc), dim3(256), 0, st, (const E*)temp, region_base, row_ptr, val_idx, n, key_max, NRANGE, NB);
+        return hipGetLastError();
+      };
+      HIP_TRY(ctx, packed ? partition_and_sort(reinterpret_cast<SortElem4*>(sort_temp)) : partition_and_sort(sort_temp));
     }
 
     {  // work list, accumulation, merge of split rows

@@ -208,6 +208,7 @@ def load_library():
         "msm377_scalars_width_host": (i32, [u8p, u64, u32, ctypes.POINTER(u32)]),
         "msm377_short_windows": (u32, [u32, u32]),
         "msm377_ctx_get_last_geometry": (i32, [vp, ctypes.POINTER(u32), ctypes.POINTER(u32)]),
+        "msm377_ctx_get_last_sort_elem_bytes": (u32, [vp]),
         "msm377_ctx_set_input_format": (i32, [vp, u32, u32]),
         "msm377_ctx_get_input_format": (i32, [vp, ctypes.POINTER(u32), ctypes.POINTER(u32)]),
         "msm377_g1_import_points_host": (i32, [u8p, u64, u32, vp, vp]),
@@ -499,6 +500,11 @@ class MsmEngine:
         w, log = ctypes.c_uint32(), ctypes.c_uint32()
         self._check(self._lib.msm377_ctx_get_last_geometry(self._ctx, ctypes.byref(w), ctypes.byref(log)), "msm377_ctx_get_last_geometry")
         return int(w.value), int(log.value)
+
+    def last_sort_elem_bytes(self) -> int:
+        """Bytes per element of the sort's intermediate buffer in the last call's last pass: 4 packed, 8, or 0 where the
+        two-level sort did not run (msm377_ctx_get_last_sort_elem_bytes)."""
+        return int(self._lib.msm377_ctx_get_last_sort_elem_bytes(self._ctx))
 
     def set_bases(self, points: bytes):
         self._check(self._lib.msm377_g1_set_bases(self._ctx, bytes(points), self._count_points(points)), "msm377_g1_set_bases")
