@@ -22,6 +22,7 @@ def main():
     ap.add_argument("--log-n", type=int, default=20)
     ap.add_argument("--reps", type=int, default=6)
     ap.add_argument("--iters", type=int, default=8)
+    ap.add_argument("--series", action="store_true", help="also print every repetition's ms per MSM and reduce-stage ms, configuration by configuration")
     ap.add_argument("configs", nargs="+")
     args = ap.parse_args()
     import torch
@@ -69,6 +70,9 @@ def main():
             front[i].append((st["convert"], st["decompose"], st["sort"], st["accumulate"]))
     for cfg, m, a, r, t, f in zip(args.configs, ms, acc, red, tail, front):
         fm = [statistics.median(x[k] for x in f) for k in range(4)]
+        if args.series:
+            print("%-48s ms     %s" % (cfg, " ".join("%.4f" % x for x in m)))
+            print("%-48s reduce %s" % (cfg, " ".join("%.4f" % x for x in r)))
         print("%-48s median %.4f  min %.4f  acc_kernel %.4f  reduce %.4f  tail %.4f  | convert %.3f decompose %.3f sort %.3f acc_stage %.3f" % (cfg, statistics.median(m), min(m), statistics.median(a), statistics.median(r), statistics.median(t), fm[0], fm[1], fm[2], fm[3]), flush=True)
 
 

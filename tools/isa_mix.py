@@ -88,7 +88,7 @@ def main():
         if "k_" not in name:
             continue
         entry = mix(body)
-        if "k_accumulate" in name or "k_merge" in name or "k_reduce_tail" in name or "k_tree_step" in name:
+        if "k_accumulate" in name or "k_merge" in name or "k_reduce_tail" in name or "k_tree_step" in name or "k_tree_columns" in name:
             entry["hottest_loop"] = hottest_loop(body)
         key = demangle_hint(name)
         while key in res:

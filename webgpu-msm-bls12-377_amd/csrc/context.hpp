@@ -151,6 +151,9 @@ struct msm377_ctx {
   uint64_t narrow_quad_items = 100000;  // MSM377_NARROW_QUAD_ITEMS: most work items k_accumulate_quad is used for (0: a thread per work item, like the main path)
   // First level of the single-launch tail of the reduction (k_reduce_tail); MSM377_TAIL_FROM, 15 = one launch per level throughout.
   uint32_t tail_from = 7;  // measured (tools/ab_knobs.py, 2^20): 15: 2.874 ms, 7: 2.842, 6: 2.885, 5: 2.916, 4: 3.062
+  // MSM377_REDUCE_COLUMNS=0: the levels below tail_from run one launch per level (k_tree_step / k_tree_step_quad) instead of
+  // as column launches of up to four levels each (k_tree_columns); same records either way, kept for A/B runs and the tests.
+  bool reduce_columns = true;
   // GLV front end of the Weierstrass path: 0 = off (default), 1 = on.  phi(P) = [lambda] P holds only for points of
   // the prime-order subgroup, so it is an opt-in: the caller vouches for the inputs (every protocol use does).
   // Interleaved A/B on one MI355X (tools/ab_knobs.py), Weierstrass plain vs GLV ms per MSM: 2^18 1.39 / 1.24,

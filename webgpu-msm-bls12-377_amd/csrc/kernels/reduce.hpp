@@ -1,4 +1,4 @@
-// Stage 4: bucket reduction (k_tree_step, k_tree_step_quad, k_reduce_tail, k_fold_windows), the quad-cooperative additions
+// Stage 4: bucket reduction (k_tree_step, k_tree_columns, k_tree_step_quad, k_reduce_tail, k_fold_windows), the quad-cooperative additions
 // and the output stage k_gather_partials.  Replaces wgsl/cuzk/bpr.template.wgsl:69-173; models cuzk/bpr.ts:5-126.
 // Device code; included by sequencer.hip only.
 #pragma once
@@ -42,6 +42,83 @@ __global__ void __launch_bounds__(256, 2) k_tree_step(uint32_t* __restrict__ buc
   const typename CV::Pt sum = CV::is_stored_identity(a) ? b : CV::add(a, b);
   if (CV::is_bad(sum)) atomicOr(err, ERR_TE_TREE);
   store_bucket<CV>(buckets, L, ws, x, sum);
+}
+
+// Levels [r0, r0 + k) of the same scheme in ONE launch, k <= 4, without global memory between the levels.  At level
+// r0 a window holds r0 + 1 arrays of len = NB >> r0 buckets: the running block at 0 and the list of level r' at
+// NB >> (r' + 1).  At every level r < r0 + k both `half` and every `lo` above are multiples of stride = len >> k, so
+// a bucket only meets buckets with the same index mod stride: an array is `stride` independent columns of 2^k rows
+// (row j of column c = bucket base + c + j * stride), and level r0 + s folds rows [h, 2h) of a column onto rows [0, h),
+// h = 2^(k-1-s), in every list the column holds by then.  A group of H = 2^(k-1) neighbouring lanes owns one (array,
+// column).  Every lane holds a (lower, upper) pair of records and every step is lower += upper under k_tree_step's
+// rule; between steps lane i trades one record with lane i ^ m, m = H >> s (ds_bpermute, as quad_bcast), which
+// re-pairs the rows exactly as level r0 + s pairs them:
+//   lane without bit m ("low"):  keeps its sum, gives its upper away, takes the partner's sum as the new upper
+//                                (sum_i += sum_(i^m): the fold of the list the two sums belong to);
+//   lane with bit m ("high"):    gives its sum away and takes the partner's upper as the new lower.  On the running
+//                                block's lanes i < 2m the two uppers are the halves of the list the block left behind
+//                                at the previous level, and the high lane folds it; any other high lane is finished.
+// The low lane's new upper stays in memory as it is when the array is a list (nothing reads it again), and is the
+// list the running block leaves behind when it is the block -- so at the end only the rows that a later stage reads
+// are stored: every live lane's sum (row 0 of a list; rows 0, 2^(k-1), .., 2, of the block's column = the heads of
+// block and spawned lists) and lane 0's upper of the block's column (row 1, the list of level r0 + k - 1).  For k = 4
+// the block's column makes 8 + 8 + 6 + 4 additions, reads 16 records and writes 5.  Same additions on the same
+// operands in the same order as the per-level launches.  The per-level launches apply k_tree_step's rule for empty
+// buckets below level `quad_from` (the sequencer's coop_from) and add unconditionally from there on, as k_tree_step_quad
+// does (the law is complete; the identity comes out as another (0 : c : 0 : c)), and so does this kernel: the twisted
+// Edwards additions of a thread and of a lane quad are the same products in the same order, so the records come out
+// bit for bit the same as from the per-level launches.  (Not so in the Weierstrass form, the fallback: its quad addition
+// reduces Y3 differently from G1::add, so there only the levels below quad_from agree word for word.)
+// (Shared with the host model of the plan in tests/test_reduce_columns_host.py.)
+constexpr uint32_t COLUMN_LEVELS_MAX = 4;
+template <class CV>
+__global__ void __launch_bounds__(256, 2) k_tree_columns(uint32_t* buckets, uint32_t L, uint32_t r0, uint32_t k, uint32_t quad_from, uint32_t threads_per_window,
+                                                         int* __restrict__ err) {
+  const uint32_t NB = 1u << L;
+  const uint32_t g = blockIdx.x * 256 + threadIdx.x;
+  const uint32_t ws = blockIdx.y;
+  if (g >= threads_per_window) return;  // whole groups leave together (H divides the count and the wave)
+  const uint32_t H = 1u << (k - 1), stride = NB >> (r0 + k);
+  const uint32_t i = g & (H - 1), col = g >> (k - 1);
+  const uint32_t arr = col / stride, c = col % stride;
+  const uint32_t base = (arr == 0 ? 0u : (NB >> arr)) + c;
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t row_lo = i, row_up = i + H;
+  uint32_t lo[CV::PT_WORDS], up[CV::PT_WORDS];
+  CV::to_words(load_bucket<CV>(buckets, L, ws, base + row_lo * stride), lo);
+  CV::to_words(load_bucket<CV>(buckets, L, ws, base + row_up * stride), up);
+  bool live = true, bad = false;
+#pragma unroll 1
+  for (uint32_t s = 0; s < k; s++) {
+    if (s != 0) {
+      const uint32_t m = H >> s;
+      const bool low = (i & m) == 0;
+      const int src = (int)(lane ^ m);
+#pragma unroll
+      for (uint32_t j = 0; j < CV::PT_WORDS; j++) {
+        const uint32_t got = (uint32_t)__shfl((int)(low ? up[j] : lo[j]), src, 64);
+        const uint32_t keep = low ? lo[j] : up[j];
+        lo[j] = low ? keep : got;
+        up[j] = low ? got : keep;
+      }
+      const uint32_t got_row = (uint32_t)__shfl((int)(low ? row_up : row_lo), src, 64);
+      const uint32_t keep_row = low ? row_lo : row_up;
+      row_lo = low ? keep_row : got_row;
+      row_up = low ? got_row : keep_row;
+      live = live && (low || (arr == 0 && i < 2 * m));
+    }
+    const bool rule = r0 + s < quad_from;  // uniform
+    const typename CV::Pt b = CV::from_words(up);
+    if (live && !(rule && CV::is_stored_identity(b))) {
+      const typename CV::Pt a = CV::from_words(lo);
+      const typename CV::Pt sum = rule && CV::is_stored_identity(a) ? b : CV::add(a, b);
+      bad |= CV::is_bad(sum);
+      CV::to_words(sum, lo);
+    }
+  }
+  if (bad) atomicOr(err, ERR_TE_TREE);
+  if (live) store_bucket<CV>(buckets, L, ws, base + row_lo * stride, CV::from_words(lo));
+  if (arr == 0 && i == 0) store_bucket<CV>(buckets, L, ws, base + row_up * stride, CV::from_words(up));
 }
 
 // Precomputed-window tables: bucket t of window slot ws += bucket t of slot ws + half (the table of slot ws already

@@ -11,7 +11,7 @@
 //   kernels/sort.hpp        k_range_count / k_range_scan / k_partition / k_local_sort (k_small_sort on the narrow path)
 //                           per-window counting sort -> CSR            wgsl/cuzk/transpose_serial.wgsl:34-76 (16 serial threads there); model cuzk/transpose.ts:14-62
 //   kernels/accumulate.hpp  k_accumulate: bucket sums (the dominant kernel)   wgsl/cuzk/smvp_bls12_377.template.wgsl:72-160
-//   kernels/reduce.hpp      k_tree_step / k_tree_step_quad / k_reduce_tail / k_gather_partials
+//   kernels/reduce.hpp      k_tree_step / k_tree_columns / k_tree_step_quad / k_reduce_tail / k_gather_partials
 //                           bucket reduction, log-depth bit planes     wgsl/cuzk/bpr.template.wgsl:69-173; models cuzk/bpr.ts:5-126
 //   host_tail.hip           Horner over windows + one inversion        submission.ts:290-321
 // In front of all of it, only while msm377_ctx_set_input_format names a native form: kernels/import.hpp k_import_points /
@@ -540,7 +540,22 @@ int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scala
     // per launch; a thread with four serial additions only lengthens that.)
     // More waves do not help either: k_tree_step at 3 / 4 waves per SIMD (132 VGPRs, no scratch) reduces in 0.300 /
     // 0.32 ms against 0.298 at 2; lane quads for levels 0-4 (MSM377_COOP_THREADS up to 2^20 threads) in 0.36.
-    for (uint32_t r = 0; r < tail_from; r++) {
+    // What does help is not going through memory between the levels at all: the levels below tail_from run as column
+    // launches of up to four levels each (k_tree_columns: 0-3 and 4-6 on the main path, 0-3 on the narrow one, 0-3,
+    // 4-7, 8-10 for a wide window), every geometry and window count alike.  coop_from does not choose their kernel any more; it only tells them from
+    // which level on the per-level launches add empty buckets like any other (k_tree_step_quad), so that both give the same records.
+    // MSM377_REDUCE_COLUMNS=0: one launch per level as below.
+    uint32_t r = 0;
+    if (ctx->reduce_columns) {
+      while (r < tail_from) {
+        const uint32_t k = std::min(tail_from - r, COLUMN_LEVELS_MAX);
+        const uint32_t threads = (r + 1) * (NB >> (r + 1));  // per window: (r + 1) arrays x (NB >> (r + k)) columns x 2^(k-1) lanes
+        hipLaunchKernelGGL(k_tree_columns<CV>, dim3((threads + 255) / 256, wc_out), dim3(256), 0, st, buckets, L, r, k, coop_from, threads, d_err);
+        HIP_TRY(ctx, hipGetLastError());
+        r += k;
+      }
+    }
+    for (; r < tail_from; r++) {
       const uint32_t ops = (r + 1) * (NB >> (r + 1));
       bool done = false;
       if constexpr (CV::HAS_QUAD) {
@@ -1858,7 +1873,7 @@ static int twin_prepare(msm377_ctx* ctx) {
   // lend the table, and the conversion's verdict that travels with it (d_err[2], read by the accumulation kernels)
   tw->resident = ctx->resident;
   tw->scalar_form = ctx->scalar_form;  // (its share imports its own scalars into its own staging)
-  tw->seg_plain = ctx->seg_plain, tw->seg_glv = ctx->seg_glv, tw->tail_from = ctx->tail_from;
+  tw->seg_plain = ctx->seg_plain, tw->seg_glv = ctx->seg_glv, tw->tail_from = ctx->tail_from, tw->reduce_columns = ctx->reduce_columns;
   if (hipMemcpyAsync(tw->d_err + 2, ctx->d_err + 2, sizeof(int), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
       hipStreamSynchronize(ctx->stream) != hipSuccess) {
     twin_return(ctx);
