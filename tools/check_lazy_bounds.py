@@ -136,6 +136,8 @@ def check_columns(pairs, what):
             if 0 <= j < N:
                 s += MASK * MOD[j]
         s += 1 << 40  # carry from the column below (a column is < 2^64, >> 29 leaves < 2^35)
+        if k < RS:  # a column that a reduction step consumes starts from 2^29 - 1 (field29.hpp column_bias)
+            s += MASK
         worst = max(worst, s)
     assert worst < (1 << 64), "%s: column sum 2^%.2f" % (what, __import__("math").log2(worst))
     return worst

@@ -73,6 +73,13 @@ struct G1Dev {
   static __device__ __forceinline__ bool is_stored_identity(const Pt& p) { return G1::is_identity(p); }
   static __device__ __forceinline__ Pt identity() { return G1::identity(); }
   static __device__ __forceinline__ Pt madd(const Pt& a, const Base& q, bool negq) { return G1::madd(a, q, negq); }  // a + q or a - q
+  // Ops: what an addition keeps of a record once its sign is known (k_accumulate forms it, then loads the next record)
+  struct Ops {
+    Base q;
+    uint32_t neg;
+  };
+  static __device__ __forceinline__ Ops signed_ops(const Base& q, bool negq) { return Ops{q, negq ? 1u : 0u}; }
+  static __device__ __forceinline__ Pt madd(const Pt& a, const Ops& o) { return G1::madd(a, o.q, o.neg != 0); }
   static __device__ __forceinline__ Pt first(const Base& q, bool negq) { return G1::madd(G1::identity(), q, negq); }  // identity + q: a copy
   static __device__ __forceinline__ Pt add(const Pt& a, const Pt& b) { return G1::add(a, b); }
   static __device__ __forceinline__ void to_words(const Pt& p, uint32_t* w) {
@@ -145,6 +152,9 @@ struct EdDev {
   static __device__ __forceinline__ bool is_stored_identity(const Pt& p) { return Fq::is_zero(p.x) && Fq::eq(p.y, p.z); }  // (0 : c : 0 : c)
   static __device__ __forceinline__ Pt identity() { return EdLazy::identity(); }
   static __device__ __forceinline__ Pt madd(const Pt& a, const Base& q, bool negq) { return EdLazy::madd_affine(a, q, negq); }
+  using Ops = EdLazy::AOps;
+  static __device__ __forceinline__ Ops signed_ops(const Base& q, bool negq) { return EdLazy::signed_ops(q, negq); }
+  static __device__ __forceinline__ Pt madd(const Pt& a, const Ops& o) { return EdLazy::madd_affine(a, o); }
   static __device__ __forceinline__ Pt first(const Base& q, bool negq) { return EdLazy::madd_affine(EdLazy::identity(), q, negq); }
   static __device__ __forceinline__ Pt add(const Pt& a, const Pt& b) { return EdLazy::add(a, b); }
   static __device__ __forceinline__ void to_words(const Pt& p, uint32_t* w) {
@@ -217,6 +227,9 @@ struct TeDev {
   static __device__ __forceinline__ bool is_stored_identity(const Pt& p) { return Fp::is_zero(p.x) && Fp::eq(p.y, p.z); }  // (0 : c : 0 : c), c != 0
   static __device__ __forceinline__ Pt identity() { return Te377::identity(); }
   static __device__ __forceinline__ Pt madd(const Pt& a, const Base& q, bool negq) { return Te377::madd(a, q, negq); }
+  using Ops = Te377::POps;
+  static __device__ __forceinline__ Ops signed_ops(const Base& q, bool negq) { return Te377::signed_ops(q, negq); }
+  static __device__ __forceinline__ Pt madd(const Pt& a, const Ops& o) { return Te377::madd(a, o); }
   static __device__ __forceinline__ Pt first(const Base& q, bool negq) { return Te377::from_base(q, negq); }  // 1 product instead of 8
   static __device__ __forceinline__ Pt add(const Pt& a, const Pt& b) { return Te377::add(a, b); }
   static __device__ __forceinline__ void to_words(const Pt& p, uint32_t* w) {
@@ -262,6 +275,9 @@ struct TeAffBase {
     return p;
   }
   static __device__ __forceinline__ Pt madd(const Pt& a, const Base& q, bool negq) { return Te377::madd_affine(a, q, negq); }
+  using Ops = Te377::AOps;
+  static __device__ __forceinline__ Ops signed_ops(const Base& q, bool negq) { return Te377::signed_ops(q, negq); }
+  static __device__ __forceinline__ Pt madd(const Pt& a, const Ops& o) { return Te377::madd_affine(a, o); }
   static __device__ __forceinline__ Pt first(const Base& q, bool negq) { return Te377::from_base_affine(q, negq); }
 };
 

@@ -156,30 +156,52 @@ struct Field {
   //
   // Column bound (every column of the schoolbook product is ONE u64 accumulator): with limb
   // bounds A_i, B_j the worst column holds sum A_i B_j + 12 * 2^58 (the q p terms) + a carry
-  // < 2^36.  Allowed operand shapes, checked per call site in g1_xyzz.hpp:
+  // < 2^36 + the bias 2^29 - 1 of a reduced column (mont_digit below).  Allowed operand shapes, checked per call site in g1_xyzz.hpp:
   //   "N-form"  limbs 0..11 < 2^29, top limb < 2^31.6   (norm() output, value < 7.1 p)
   //   "lazy"    limbs < 3 * 2^29, top limb < 2^31       (one add_kp_sub of N-form values with top limbs < 2^29.1)
   // N x N, lazy x N (top limb of the N operand < 2^29.1) and N^2 fit; lazy x lazy does not.
 
+  // One reduction step costs three instructions beside its N - 1 multiply-adds.  The quotient digit is
+  // q = -t0 mod 2^29 (MOD[0] = 1) and the carry into the next column (t0 + q) >> 29 = ceil(t0 / 2^29)
+  // = (t0 + LMASK) >> 29.  Every column that a step reduces therefore STARTS at LMASK instead of 0 (the addend
+  // of its first multiply-add, free): with t0' = t0 + LMASK the digit is ~t0' & LMASK (one bit-field operation:
+  // the low 29 bits of t0' are those of t0 - 1, and ~(x - 1) = -x), the carry is t0' >> 29, and the third
+  // instruction adds it to the next column.  The bias is spent in the step that reduces the column; the result
+  // columns carry none.  Per bucket addition (7 products): 3 251 VALU instructions in k_accumulate's loop instead of
+  // 3 496 with this step, the loop's register rotation and the exceptional-pair check off the straight path; 2 360 of
+  // them multiply-adds either way (profiles/valu_trim/isa_mix.json).  Digits, carries and result limbs are those of the plain form
+  // q = (0 - t0) & LMASK, carry = (t0 + q) >> 29 (tests/native/mont_step_host.cpp keeps that form as the reference).
+  static MSM_HD uint32_t mont_digit(uint64_t t0_biased) { return ~(uint32_t)t0_biased & LMASK; }
+  // The bias a reduced column starts from.  On the GPU the value is hidden from the optimizer: sums are reordered with
+  // known constants LAST, which turned the column's first multiply-add back into one with addend 0 and the bias into
+  // a 64-bit add of its own -- the instruction this form is there to save.
+  static MSM_HD uint64_t column_bias() {
+    uint64_t b = LMASK;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+s"(b));
+#endif
+    return b;
+  }
+
   // Lazy product: see above.  Output N-form with value < p + 2^354 (top limb <= MOD[N-1] + 64).
   static MSM_HD El mul_lz(const El& a, const El& b) {
+    const uint64_t bias = column_bias();
     uint64_t t[N];
 #pragma unroll
-    for (int j = 0; j < N; j++) t[j] = 0;
+    for (int j = 0; j < N; j++) t[j] = bias;  // columns 0..N-1 are all reduced (N <= RS)
 #pragma unroll
     for (int i = 0; i < RS; i++) {
       if (i < N) {
 #pragma unroll
         for (int j = 0; j < N; j++) t[j] += (uint64_t)a.l[i] * b.l[j];
       }
-      uint32_t q = (0u - (uint32_t)t[0]) & LMASK;
-      uint64_t carry = (t[0] + q) >> LB;  // low 29 bits cancel exactly
+      const uint32_t q = mont_digit(t[0]);
 #pragma unroll
       for (int j = 1; j < N; j++) t[j] += (uint64_t)q * C::MOD[j];
-      t[1] += carry;
+      t[1] += t[0] >> LB;
 #pragma unroll
       for (int j = 0; j < N - 1; j++) t[j] = t[j + 1];
-      t[N - 1] = 0;
+      t[N - 1] = (i + N < RS) ? bias : 0;  // column i + N enters: biased if a later step reduces it
     }
     El r;
 #pragma unroll
@@ -194,9 +216,10 @@ struct Field {
   // a*b + e*d in ONE reduction (Y3 = R (Q - X3) + (-Y1) PPP of every point addition): the quotient
   // digits serve both products.  Same output contract as mul_lz; the column bound covers both sums.
   static MSM_HD El mul_add_mul_lz(const El& a, const El& b, const El& e, const El& d) {
+    const uint64_t bias = column_bias();
     uint64_t t[N];
 #pragma unroll
-    for (int j = 0; j < N; j++) t[j] = 0;
+    for (int j = 0; j < N; j++) t[j] = bias;  // columns 0..N-1 are all reduced (N <= RS)
 #pragma unroll
     for (int i = 0; i < RS; i++) {
       if (i < N) {
@@ -205,14 +228,13 @@ struct Field {
 #pragma unroll
         for (int j = 0; j < N; j++) t[j] += (uint64_t)e.l[i] * d.l[j];
       }
-      uint32_t q = (0u - (uint32_t)t[0]) & LMASK;
-      uint64_t carry = (t[0] + q) >> LB;
+      const uint32_t q = mont_digit(t[0]);
 #pragma unroll
       for (int j = 1; j < N; j++) t[j] += (uint64_t)q * C::MOD[j];
-      t[1] += carry;
+      t[1] += t[0] >> LB;
 #pragma unroll
       for (int j = 0; j < N - 1; j++) t[j] = t[j + 1];
-      t[N - 1] = 0;
+      t[N - 1] = (i + N < RS) ? bias : 0;  // column i + N enters: biased if a later step reduces it
     }
     El r;
 #pragma unroll
@@ -227,9 +249,10 @@ struct Field {
   // Lazy square of an N-form value: off-diagonal terms once with a doubled operand (2 a_i < 2^30 for
   // i <= N-2; the top limb is never the doubled one).
   static MSM_HD El sqr_lz(const El& a) {
+    const uint64_t bias = column_bias();
     uint64_t t[RS + N];
 #pragma unroll
-    for (int j = 0; j < RS + N; j++) t[j] = 0;
+    for (int j = 0; j < RS + N; j++) t[j] = (j < RS) ? bias : 0;  // the reduced columns
 #pragma unroll
     for (int i = 0; i < N; i++) {
       t[2 * i] += (uint64_t)a.l[i] * a.l[i];
@@ -239,11 +262,10 @@ struct Field {
     }
 #pragma unroll
     for (int i = 0; i < RS; i++) {
-      uint32_t q = (0u - (uint32_t)t[i]) & LMASK;
-      uint64_t carry = (t[i] + q) >> LB;
+      const uint32_t q = mont_digit(t[i]);
 #pragma unroll
       for (int j = 1; j < N; j++) t[i + j] += (uint64_t)q * C::MOD[j];
-      t[i + 1] += carry;
+      t[i + 1] += t[i] >> LB;
     }
     El r;
 #pragma unroll

@@ -124,6 +124,20 @@ __global__ void __launch_bounds__(1024) k_work_scatter(const uint32_t* __restric
   }
 }
 
+// Pins the words of `o` in registers at this point of the program: what was computed into them stays ahead of every
+// memory access that follows.  k_accumulate forms an addition's operands from the record with it and THEN gathers the
+// next record; left alone, the compiler sinks the selects below the gather, the old record stays live across it and the
+// new one lands in other registers, to be copied over at the end of every iteration.
+template <class T>
+__device__ __forceinline__ void pin_registers(T& o) {
+  static_assert(sizeof(T) % 4 == 0, "whole words");
+  uint32_t w[sizeof(T) / 4];
+  __builtin_memcpy(w, &o, sizeof(T));
+#pragma unroll
+  for (int j = 0; j < (int)(sizeof(T) / 4); j++) asm volatile("" : "+v"(w[j]));
+  __builtin_memcpy(&o, w, sizeof(T));
+}
+
 // One thread per work item.  OCC = waves per SIMD the register allocator must allow.
 template <class CV, int OCC, class BP = CV, int PF = 0>  // BP: where the input points come from (CV itself, or TeAffBase); PF: extra records in flight
 __global__ void __launch_bounds__(256, OCC) k_accumulate(const uint32_t* __restrict__ row_ptr, const uint32_t* __restrict__ val_idx,
@@ -149,45 +163,50 @@ __global__ void __launch_bounds__(256, OCC) k_accumulate(const uint32_t* __restr
   const bool start_fresh = !(into && it.seg == 0);
   bool bad = false;  // an exceptional pair of the twisted Edwards law (te377.hpp): sticky, the caller falls back
   if (k < end) {
-    // Software pipeline: while entry k is added the record of entry k+PF+1 is on its way (its gather is issued at the
-    // start of the stage), the records of entries k+1 .. k+PF have been requested one to PF additions ago, and the index
-    // of entry k+PF+2 is being read -- so neither the val_idx -> bases address dependency nor the gather latency stalls
-    // the wave.  PF = 0 everywhere: one addition, ~10 us, covers a gather even from the 2.2 GB tables of precomputed
-    // window multiples, which miss the Infinity Cache -- PF = 1 (one more record in flight, 252 VGPRs) was measured on
-    // the 20-bit-window table: kernel 1.388 -> 1.435 ms, 64 x 2^20 batch 2.199 -> 2.274 ms per MSM.
-    typename BP::Base rec[PF + 1];  // rec[0]: the entry being added
-    uint32_t e[PF + 2];             // e[j]: entry of rec[j]; e[PF + 1]: the next index, already loaded
-#pragma unroll
-    for (int j = 0; j <= PF + 1; j++) e[j] = (k + j < end) ? vi[k + j] : 0u;
-#pragma unroll
-    for (int j = 0; j <= PF; j++) rec[j] = BP::load_base(bases, e[j] & 0x7fffffffu);  // (past the end: record 0, never used)
-    bool more = true;  // rec[0] / e[0] hold an entry that has not been added yet
-    // One stage: start the gathers for the entries further down, add entry rec[0], rotate.  FIRST is a compile-time
+    // Software pipeline: while entry k is added the record of entry k+1 is on its way (its gather is issued before the
+    // addition's first product) and the index of entry k+2 is being read -- so neither the val_idx -> bases address
+    // dependency nor the gather latency stalls the wave.  One record and one index in flight: one addition, ~10 us,
+    // covers a gather even from the 2.2 GB tables of precomputed window multiples, which miss the Infinity Cache -- one
+    // more record in flight (252 VGPRs) was measured on the 20-bit-window table: kernel 1.388 -> 1.435 ms, 64 x 2^20
+    // batch 2.199 -> 2.274 ms per MSM.
+    static_assert(PF == 0, "one record in flight");
+    uint32_t e_cur = vi[k];                          // entry of rec
+    uint32_t e_nxt = (k + 1 < end) ? vi[k + 1] : 0u;  // the next index, already loaded
+    typename BP::Base rec = BP::load_base(bases, e_cur & 0x7fffffffu);
+    bool more = true;  // rec / e_cur hold an entry that has not been added yet
+    // the gather of the next entry, into the registers of `rec` (whatever the addition needs of it has been taken out),
+    // and the index after it
+    auto advance = [&]() {
+      k++;
+      more = k < end;
+      if (more) {
+        rec = BP::load_base(bases, e_nxt & 0x7fffffffu);
+        e_cur = e_nxt;
+        e_nxt = (k + 1 < end) ? vi[k + 1] : 0u;
+      }
+    };
+    // One stage: take the record's factors with the entry's sign applied (BP::signed_ops: the selects an addition
+    // makes anyway), start the gather of the next entry, add.  The record's own registers are dead once the factors are
+    // formed, so the gather writes straight into them and the loop rotates nothing: the listing of the earlier form
+    // (load into a second buffer, add, copy the buffer over) held 127 v_mov per addition.  FIRST is a compile-time
     // switch so that the chain's first entry (BP::first: a copy, one product) is PEELED off the loop -- written as
     // `start_fresh ? first(cur) : madd(acc, cur)` inside the loop the compiler evaluated both sides every
     // iteration and selected: 8 products per iteration instead of 7 (9 instead of 8 with projective records; 2697
     // v_mad_u64_u32 in the loop body instead of 2360 -- tools/isa_mix.py, profiles/r02_final/isa_mix.json).
     auto stage = [&](auto first_tag) {
       constexpr bool FIRST = decltype(first_tag)::value;
-      k++;
-      more = k < end;
-      typename BP::Base fresh = rec[PF];
-      uint32_t e_new = 0u;
-      if (k + PF < end) {
-        fresh = BP::load_base(bases, e[PF + 1] & 0x7fffffffu);
-        if (k + PF + 1 < end) e_new = vi[k + PF + 1];
+      const bool neg = (e_cur >> 31) != 0;
+      if constexpr (FIRST) {
+        const typename BP::Base cur = rec;
+        advance();
+        acc = BP::first(cur, neg);
+      } else {
+        typename BP::Ops ops = BP::signed_ops(rec, neg);
+        pin_registers(ops);
+        advance();
+        acc = BP::madd(acc, ops);
       }
-      if constexpr (FIRST)
-        acc = BP::first(rec[0], (e[0] >> 31) != 0);
-      else
-        acc = BP::madd(acc, rec[0], (e[0] >> 31) != 0);
       bad |= CV::is_bad(acc);
-#pragma unroll
-      for (int j = 0; j < PF; j++) rec[j] = rec[j + 1];
-      rec[PF] = fresh;
-#pragma unroll
-      for (int j = 0; j <= PF; j++) e[j] = e[j + 1];
-      e[PF + 1] = e_new;
     };
     if (start_fresh) stage(std::true_type{});  // a chain that starts from the identity: its first entry needs no addition
     while (more) stage(std::false_type{});

@@ -61,25 +61,62 @@ struct TeLazy {
   }
   // A stored coordinate (lazy product, carry-normalised) that is 0 mod p: all limbs zero, or exactly p.
   static MSM_HD bool is_zero_mod_p(const El& a) { return F::is_zero(a) || F::eq(a, F::from_const(K::MOD)); }
-  static MSM_HD bool is_bad(const Ext& p) { return is_zero_mod_p(p.z); }
+  // Z3 = 0 mod p: Z3 is 0 or p, so its lowest limb is 0 or MOD[0].  Only that limb is tested per addition; the full
+  // comparison runs behind it -- on the GPU under a branch the whole wave takes or skips (two values of 2^29 per lane)
+  // -- and decides alone, so the outcome is is_zero_mod_p's exactly.
+  static MSM_HD bool is_bad(const Ext& p) {
+    const bool maybe = p.z.l[0] == 0 || p.z.l[0] == K::MOD[0];
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (__builtin_amdgcn_ballot_w64(maybe) == 0) return false;
+#else
+    if (!maybe) return false;
+#endif
+    return is_zero_mod_p(p.z);
+  }
 
-  // p + q (neg: p - q; -(x, y) = (-x, y) swaps Y - X with Y + X and negates T): 8 products.
+  // The factors a mixed addition takes from the record of q, with the sign applied (-(x, y) = (-x, y) swaps Y - X
+  // with Y + X and negates T): fa multiplies Y1 - X1, fb Y1 + X1, fc T1.  Forming them is all that reads the record,
+  // so the accumulation loop forms them first and lets the next record load into the registers this one leaves.
+  struct AOps {
+    El fa, fb, fc;
+  };
+  struct POps {
+    El fa, fb, fc, z2;
+  };
+  static MSM_HD AOps signed_ops(const ABase& q, bool neg) {
+    AOps o;
+    o.fa = F::select(neg, q.ypx, q.ymx);
+    o.fb = F::select(neg, q.ymx, q.ypx);
+    o.fc = F::select(neg, F::kp_sub(K::KP2, q.kt), q.kt);
+    return o;
+  }
+  static MSM_HD POps signed_ops(const PBase& q, bool neg) {
+    POps o;
+    o.fa = F::select(neg, q.ypx, q.ymx);
+    o.fb = F::select(neg, q.ymx, q.ypx);
+    o.fc = F::select(neg, F::kp_sub(K::KP2, q.kt), q.kt);
+    o.z2 = q.z2;
+    return o;
+  }
+  // p + q (neg: p - q): 8 products.
   //   A, B, C, D lazy products (< p + e);  E = B - A + 2p, F = D - C + 2p  in (p - e, 3p + e),
   //   G = D + C, H = B + A  < 2p + 2e;  E, F, G carry-normalised, H left limb-wise (limbs < 2^30).
-  static MSM_HD Ext madd(const Ext& p, const PBase& q, bool neg) {
-    const El a = F::mul_lz(F::add_kp_sub(p.y, K::KP2, p.x), F::select(neg, q.ypx, q.ymx));
-    const El b = F::mul_lz(F::add_lz(p.y, p.x), F::select(neg, q.ymx, q.ypx));
-    const El c = F::mul_lz(F::select(neg, F::kp_sub(K::KP2, q.kt), q.kt), p.t);
+  static MSM_HD Ext madd(const Ext& p, const POps& q) {
+    const El a = F::mul_lz(F::add_kp_sub(p.y, K::KP2, p.x), q.fa);
+    const El b = F::mul_lz(F::add_lz(p.y, p.x), q.fb);
+    const El c = F::mul_lz(q.fc, p.t);
     const El d = F::mul_lz(p.z, q.z2);
     return finish(a, b, c, d);
   }
+  static MSM_HD Ext madd(const Ext& p, const PBase& q, bool neg) { return madd(p, signed_ops(q, neg)); }
   // The same with an affine input point (Z2 = 1): 7 products; D = 2 Z1 limb-wise.
-  static MSM_HD Ext madd_affine(const Ext& p, const ABase& q, bool neg) {
-    const El a = F::mul_lz(F::add_kp_sub(p.y, K::KP2, p.x), F::select(neg, q.ypx, q.ymx));
-    const El b = F::mul_lz(F::add_lz(p.y, p.x), F::select(neg, q.ymx, q.ypx));
-    const El c = F::mul_lz(F::select(neg, F::kp_sub(K::KP2, q.kt), q.kt), p.t);
+  static MSM_HD Ext madd_affine(const Ext& p, const AOps& q) {
+    const El a = F::mul_lz(F::add_kp_sub(p.y, K::KP2, p.x), q.fa);
+    const El b = F::mul_lz(F::add_lz(p.y, p.x), q.fb);
+    const El c = F::mul_lz(q.fc, p.t);
     return finish(a, b, c, F::add_lz(p.z, p.z));
   }
+  static MSM_HD Ext madd_affine(const Ext& p, const ABase& q, bool neg) { return madd_affine(p, signed_ops(q, neg)); }
   // General addition: 9 products (one of them by the constant 2d).
   static MSM_HD Ext add(const Ext& p, const Ext& q) {
     const El a = F::mul_lz(F::norm(F::add_kp_sub(p.y, K::KP2, p.x)), F::norm(F::add_kp_sub(q.y, K::KP2, q.x)));
