@@ -462,6 +462,53 @@ int msm377_ctx_set_narrow_max(msm377_ctx* ctx, uint64_t max_points);
 #define MSM377_FB_CONVERT 64    /* an input point the Edwards model cannot represent (order 2 or 4) */
 int msm377_ctx_get_fallback_info(const msm377_ctx* ctx, uint64_t* count, uint32_t* last_mask);
 
+/* ---- fixed-base batch multiplication ------------------------------------------------------ */
+
+/* out[i] = [s_i]B: n scalar multiples of ONE base point, each returned as its own affine point (arkworks' batch_mul /
+ * FixedBase::msm: an SRS [tau^i]G, the G1 query vectors of a proving key, any base set for msm377_g1_set_bases*).  The
+ * reference has no counterpart: it computes sums only.
+ *
+ * Meaning.  s_i is the integer its 32 bytes encode; every value in [0, 2^256) is accepted -- no MSM377_ESCALAR, no rerun
+ * -- and it is NOT reduced mod r in the wire scalar form, because the answer is right for EVERY curve point B, not only
+ * for the prime-order subgroup: bases of order 2, 3, 4, 6, of 2-power order, P + T.  Every exceptional case of the
+ * addition formulas is followed through (csrc/kernels/batch_mul.hpp).
+ *
+ * Base and scalars.  base_xy is a HOST pointer, always the 96-byte wire format (the context's point form does not apply
+ * to it), trusted like any MSM input except that a coordinate of p or more is MSM377_EINVAL.  The scalars follow the
+ * context's SCALAR form (msm377_ctx_set_input_format): MSM377_SCALARS_WIRE, or MSM377_SCALARS_MONT (v 2^-256 mod r, fully
+ * reduced, the product of the import pass).  msm377_g1_batch_mul_host takes wire scalars.
+ *
+ * Output.  out_form is MSM377_POINTS_WIRE or MSM377_POINTS_MONT_FLAG; plain MSM377_POINTS_MONT cannot say "identity" and
+ * is MSM377_EINVAL.
+ *   MSM377_POINTS_WIRE       96-byte records; an identity result is x = 0, y = 1 as compute_msm writes it.  (0, 1) is ALSO a
+ *                            real point of order 3, so out_inf is the only unambiguous record.
+ *   MSM377_POINTS_MONT_FLAG  104-byte records, byte for byte what msm377_g1_result_to_native makes of the wire record, but
+ *                            with the flag set ONLY for a true identity; they can be handed straight to
+ *                            msm377_g1_set_bases* on a context set to that point form.
+ *   out_inf (may be NULL)    n bytes: 1 for the identity, 0 otherwise, in either form.
+ *
+ * Arguments.  Any n: 0 is MSM377_OK without a launch, and n may exceed the context's max_points (the scratch has a fixed
+ * size, ~330 MB of device memory allocated by the first call, and the call walks n in chunks of 2^20).  Device pointers:
+ * scalars and wire records 16-byte aligned, mont_flag records 8-byte aligned.  A null pointer with n > 0 or an unknown
+ * form is MSM377_EINVAL with the outputs untouched.  The calls are synchronous: on return the outputs are complete.
+ *
+ * Table.  The call keeps a window table of the base on the context -- rows w = 0 .. ceil(256 / c) - 1 of [d 2^(c w)]B,
+ * d = 1 .. 2^(c-1), signed digits pick the negative, plus [2^(c ceil(256 / c))]B for the carry out of the top window --
+ * keyed by the 96 base bytes and the width c.  It is rebuilt only when either changes (msm377_ctx_get_mul_table_builds
+ * counts the builds), is freed by msm377_ctx_destroy, and a failed build leaves none behind.  The resident MSM bases and
+ * a check call's state are untouched by these calls, and the other way round.
+ * Widths: c = 8 (33 additions per output, a 0.5 MB table) and c = 16 (17 additions, 64 MB).  msm377_ctx_set_mul_window:
+ * 0 = the rule by n (default: 16 from 2^19 outputs on, else 8), 8 or 16 forces the width, anything else is
+ * MSM377_EINVAL.  msm377_ctx_get_last_mul_window: the width the last batch_mul call ran, 0 before the first. */
+int msm377_g1_batch_mul_device(msm377_ctx* ctx, const uint8_t base_xy[96], const void* d_scalars, uint64_t n, uint32_t out_form, void* d_out_points, uint8_t* d_out_inf);
+int msm377_g1_batch_mul(msm377_ctx* ctx, const uint8_t base_xy[96], const uint8_t* scalars, uint64_t n, uint32_t out_form, uint8_t* out_points, uint8_t* out_inf);
+/* The same on ONE CPU thread: no device, no context (csrc/batch_mul_host.hpp) -- small batches, and the yardstick of the
+ * device call. */
+int msm377_g1_batch_mul_host(const uint8_t base_xy[96], const uint8_t* scalars, uint64_t n, uint32_t out_form, uint8_t* out_points, uint8_t* out_inf);
+int msm377_ctx_set_mul_window(msm377_ctx* ctx, int window_bits);
+int msm377_ctx_get_last_mul_window(const msm377_ctx* ctx);
+uint64_t msm377_ctx_get_mul_table_builds(const msm377_ctx* ctx);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 
 #define MSM377_STAGE_CONVERT 0     /* points -> Montgomery records */

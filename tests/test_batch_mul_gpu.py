@@ -1,0 +1,347 @@
+"""Fixed-base batch multiplication on the GPU (include/msm377.h "fixed-base batch multiplication";
+csrc/kernels/batch_mul.hpp): out[i] = [s_i]B through msm377_g1_batch_mul_device / msm377_g1_batch_mul for both window
+widths and the rule by n.  Expected values: tests/pyref.py (every exceptional case), the C oracle's scalar multiplication
+(subgroup bases in bulk) and the host twin (which tests/test_batch_mul_host.py pins to pyref); at scale, one MSM over the
+outputs with random weights against the oracle's closed form.  No expected value comes from the device call.  Every test
+leaves the engine at the rule (width 0) and at (wire, wire)."""
+import contextlib
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+
+import batch_mul_vectors as V
+import pyref as R
+import util
+import webgpu_msm_bls12_377_amd as msm
+from webgpu_msm_bls12_377_amd.host.engine import EINVAL
+
+pytestmark = pytest.mark.gpu
+
+r = R.R_ORDER
+G_BYTES = V.base_bytes(R.G)
+BLOCK = 1024  # outputs per workgroup product tree of the normalisation (4 per thread, 256 threads)
+SIZES = (1, 2, 63, 64, 65, 255, 256, 257, 1023, 1025, 4097)  # around a wave, a workgroup, a thread's outputs, a tree
+
+
+def dev(buf: bytes):
+    import torch
+
+    return torch.frombuffer(bytearray(buf) if buf else bytearray(16), dtype=torch.uint8).cuda()
+
+
+@contextlib.contextmanager
+def window(engine, bits):
+    engine.set_mul_window(bits)
+    try:
+        yield
+    finally:
+        engine.set_mul_window(0)
+
+
+def run_device(engine, base: bytes, scalars: bytes, out_form="wire", flags=True):
+    """(records, flag bytes) of one device call on freshly poisoned output buffers."""
+    import torch
+
+    n = len(scalars) // 32
+    stride = 104 if out_form == "mont_flag" else 96
+    d_s = dev(scalars)
+    d_out = torch.full((max(16, stride * n),), 0xEE, dtype=torch.uint8, device="cuda")
+    d_inf = torch.full((max(16, n),), 0xEE, dtype=torch.uint8, device="cuda")
+    engine.batch_mul_device(base, d_s.data_ptr(), n, d_out.data_ptr(), d_inf.data_ptr() if flags else 0, out_form)
+    return bytes(d_out.cpu().numpy()[: stride * n]), bytes(d_inf.cpu().numpy()[:n])
+
+
+def oracle_mul_g(oracle, scalars):
+    """[s]G for every s by the C oracle (G lies in the subgroup: s mod r)."""
+    gen = ctypes.create_string_buffer(96)
+    oracle.oracle_g1_generator(ctypes.addressof(gen))
+    out = ctypes.create_string_buffer(96)
+    recs = []
+    for s in scalars:
+        assert oracle.oracle_g1_scalar_mul(gen.raw, (s % r).to_bytes(32, "little"), 32, ctypes.addressof(out)) == 0
+        recs.append(out.raw)
+    return b"".join(recs)
+
+
+# ---- GPU == host twin == oracle ----
+@pytest.fixture(scope="module")
+def g_reference(oracle):
+    """The edge list, then seeded full-width scalars: 4097 of them, their multiples of G by the oracle and by the host
+    twin.  Every size takes a prefix."""
+    scalars = (V.EDGE + V.random_scalars(0xF1BA5E, max(SIZES)))[: max(SIZES)]
+    buf = R.encode_scalars(scalars)
+    wire = oracle_mul_g(oracle, scalars)
+    flags = bytes(1 if s % r == 0 else 0 for s in scalars)
+    assert msm.batch_mul_host(G_BYTES, buf) == (wire, flags)
+    return buf, wire, flags
+
+
+@pytest.mark.parametrize("width", V.WIDTHS)
+@pytest.mark.parametrize("n", SIZES)
+def test_generator_against_host_twin_and_oracle(engine, g_reference, n, width):
+    buf, wire, flags = g_reference
+    with window(engine, width):
+        got, got_flags = run_device(engine, G_BYTES, buf[: 32 * n])
+        assert engine.last_mul_window() == width
+    assert got_flags == flags[:n]
+    assert got == wire[: 96 * n]
+
+
+def test_rule_picks_the_narrow_table_for_small_batches(engine, g_reference):
+    buf, wire, flags = g_reference
+    got, got_flags = run_device(engine, G_BYTES, buf[: 32 * 257])
+    assert engine.last_mul_window() == 8
+    assert (got, got_flags) == (wire[: 96 * 257], flags[:257])
+
+
+@pytest.mark.parametrize("width", V.WIDTHS)
+@pytest.mark.parametrize("out_form", ["wire", "mont_flag"])
+def test_host_buffer_call(engine, g_reference, out_form, width):
+    buf, wire, flags = g_reference
+    n = 1025
+    exp = wire[: 96 * n] if out_form == "wire" else V.mont_flag_records(wire[: 96 * n], flags[:n])
+    with window(engine, width):
+        assert engine.batch_mul(G_BYTES, buf[: 32 * n], out_form) == (exp, flags[:n])
+        assert engine.batch_mul(G_BYTES, b"", out_form) == (b"", b"")
+
+
+# ---- identity outputs: a zero in a product tree would wipe a block ----
+@pytest.mark.parametrize("width", V.WIDTHS)
+def test_identity_outputs_leave_their_neighbours_exact(engine, oracle, width):
+    n = 3 * BLOCK + 7
+    scalars = V.random_scalars(0x1DE47, n)
+    zeros = [0, r, 2 * r]
+    where = [0, n - 1, 255, 256, BLOCK - 1, 2 * BLOCK, 3 * BLOCK] + list(range(BLOCK, 2 * BLOCK))  # one whole workgroup's outputs
+    where += [2 * BLOCK + 5 + 256 * j for j in range(4)]  # all four outputs of one thread
+    for k, i in enumerate(where):
+        scalars[i] = zeros[k % 3]
+    buf = R.encode_scalars(scalars)
+    wire, flags = msm.batch_mul_host(G_BYTES, buf)
+    assert flags == bytes(1 if i in set(where) else 0 for i in range(n))
+    probe = [0, 1, 254, 257, BLOCK - 2, BLOCK, 2 * BLOCK - 1, 2 * BLOCK + 1, n - 2, n - 1]
+    assert b"".join(wire[96 * i : 96 * i + 96] for i in probe) == oracle_mul_g(oracle, [scalars[i] for i in probe])
+    with window(engine, width):
+        for out_form in ("wire", "mont_flag"):
+            got, got_flags = run_device(engine, G_BYTES, buf, out_form)
+            assert got_flags == flags, out_form
+            assert got == (wire if out_form == "wire" else V.mont_flag_records(wire, flags)), out_form
+
+
+# ---- exceptional bases ----
+@pytest.fixture(scope="module")
+def base_reference():
+    scalars = V.gpu_base_scalars(130)
+    buf = R.encode_scalars(scalars)
+    return {name: (V.base_bytes(pt), buf) + V.expected(pt, scalars)[:2] for name, pt in V.bases()}
+
+
+@pytest.mark.parametrize("width", V.WIDTHS)
+@pytest.mark.parametrize("name", [name for name, _ in V.bases()])
+def test_every_curve_point_is_a_base(engine, base_reference, name, width):
+    base, buf, wire, flags = base_reference[name]
+    with window(engine, width):
+        got, got_flags = run_device(engine, base, buf)
+        assert got_flags == flags, name
+        assert got == wire, name
+        got, got_flags = run_device(engine, base, buf, "mont_flag")
+        assert got_flags == flags, name
+        assert got == V.mont_flag_records(wire, flags), name
+    if name == "small_3":  # (0, 1), order 3: the wire identity's bytes with flag 0
+        i = 1  # scalar 1
+        assert wire[96 * i : 96 * i + 96] == V.IDENTITY_WIRE and flags[i] == 0
+
+
+# ---- scale: every output enters one MSM with a random weight ----
+@functools.lru_cache(maxsize=None)
+def scale_inputs(n):
+    """(scalar bytes s_i in [1, 2^252), weight bytes t_i below 2^252, the integers s_i, t_i)."""
+    rng = np.random.default_rng(0x5CA1E + n)
+    s = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+    t = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+    s[:, 31] &= 0x0F  # below 2^252 < r
+    t[:, 31] &= 0x0F
+    s[:, 0] |= 1      # not zero
+    sb, tb = s.tobytes(), t.tobytes()
+    si = [int.from_bytes(sb[32 * i : 32 * i + 32], "little") for i in range(n)]
+    ti = [int.from_bytes(tb[32 * i : 32 * i + 32], "little") for i in range(n)]
+    return sb, tb, si, ti
+
+
+def weighted_sum_matches(engine, oracle, d_points, tb, si, ti, lo, hi):
+    d_t = dev(tb[32 * lo : 32 * hi])
+    got = engine.msm_device(d_points.data_ptr() + 96 * lo, d_t.data_ptr(), hi - lo)
+    return got == util.closed_form(oracle, sum(a * b for a, b in zip(si[lo:hi], ti[lo:hi])))
+
+
+@pytest.mark.parametrize("width", V.WIDTHS + (0,))
+@pytest.mark.parametrize("n", [65537, (1 << 18) + 3])
+def test_scale(engine, oracle, n, width):
+    import torch
+
+    sb, tb, si, ti = scale_inputs(n)
+    d_s = dev(sb)
+    d_out = torch.empty(96 * n, dtype=torch.uint8, device="cuda")
+    d_inf = torch.full((n,), 0xEE, dtype=torch.uint8, device="cuda")
+    with window(engine, width):
+        engine.batch_mul_device(G_BYTES, d_s.data_ptr(), n, d_out.data_ptr(), d_inf.data_ptr())
+        assert engine.last_mul_window() == (width or 8)  # the rule takes the wide table from 2^19 outputs on
+    assert not d_inf.any().item()
+    assert weighted_sum_matches(engine, oracle, d_out, tb, si, ti, 0, n)
+
+
+@pytest.mark.parametrize("width", [8, 0])
+def test_chunks_past_the_context_capacity(engine, oracle, width):
+    """n = 2^20 + 1 on an engine created for 2^16 points: two chunks, the second of one output."""
+    import torch
+
+    n = (1 << 20) + 1
+    sb, tb, si, ti = scale_inputs(n)
+    d_s = dev(sb)
+    d_out = torch.empty(96 * n, dtype=torch.uint8, device="cuda")
+    with msm.MsmEngine(1 << 16) as small:
+        small.set_mul_window(width)
+        small.batch_mul_device(G_BYTES, d_s.data_ptr(), n, d_out.data_ptr())
+        assert small.last_mul_window() == (width or 16)
+        assert small.mul_table_builds() == 1
+    assert weighted_sum_matches(engine, oracle, d_out, tb, si, ti, 0, 1 << 20)  # the session engine holds 2^20 points
+    last = bytes(d_out[96 * (n - 1) :].cpu().numpy())
+    assert last == util.closed_form(oracle, si[-1])
+
+
+# ---- MONT_FLAG records feed set_bases / msm on a mont_flag context ----
+@pytest.mark.parametrize("width", V.WIDTHS)
+def test_mont_flag_round_trip(engine, oracle, width):
+    import torch
+
+    n = 257
+    scalars = V.random_scalars(0xF1A6, n)
+    identities = {0, 63, 64, 128, 256}
+    for k, i in enumerate(sorted(identities)):
+        scalars[i] = (0, r, 2 * r)[k % 3]
+    weights = R.rand_scalars(0x7E16, n)
+    d_s, d_t = dev(R.encode_scalars(scalars)), dev(R.encode_scalars(weights))
+    d_out = torch.empty(104 * n, dtype=torch.uint8, device="cuda")
+    with window(engine, width):
+        engine.batch_mul_device(G_BYTES, d_s.data_ptr(), n, d_out.data_ptr(), 0, "mont_flag")
+    exp = util.closed_form(oracle, sum(s * t for i, (s, t) in enumerate(zip(scalars, weights)) if i not in identities))
+    engine.set_input_format("mont_flag", "wire")
+    try:
+        assert engine.msm_device(d_out.data_ptr(), d_t.data_ptr(), n) == exp
+        engine.set_bases_device(d_out.data_ptr(), n)
+        assert engine.msm_fixed_base_device(d_t.data_ptr(), n) == exp
+    finally:
+        engine.set_input_format("wire", "wire")
+
+
+# ---- the parent's only route to many points: byte-identical ----
+@pytest.mark.parametrize("width", V.WIDTHS)
+def test_yardstick_parity(engine, width):
+    import torch
+
+    n, seed = 4096, 0xBA5E5
+    g = R.splitmix64(seed)
+    scalars = [next(g) or 1 for _ in range(n)]
+    d_ref = torch.empty(96 * n, dtype=torch.uint8, device="cuda")
+    engine.generate_bases_device(seed, n, d_ref.data_ptr())
+    with window(engine, width):
+        got, flags = run_device(engine, G_BYTES, R.encode_scalars(scalars))
+    assert got == bytes(d_ref.cpu().numpy())
+    assert flags == bytes(n)
+
+
+# ---- the table cache ----
+def test_table_is_kept_per_base_and_width(engine, oracle):
+    scalars = V.EDGE + V.random_scalars(0xCAC4E, 57)
+    buf = R.encode_scalars(scalars)
+    b1, b2 = V.base_bytes(R.mul(R.G, 0xCAFE)), V.base_bytes(R.FIXED_BASE)
+    e1, e2 = msm.batch_mul_host(b1, buf), msm.batch_mul_host(b2, buf)
+    with window(engine, 8):
+        before = engine.mul_table_builds()
+        assert run_device(engine, b1, buf) == e1
+        assert engine.mul_table_builds() == before + 1
+        assert run_device(engine, b1, buf) == e1
+        assert run_device(engine, b1, buf, "mont_flag")[1] == e1[1]
+        assert engine.mul_table_builds() == before + 1  # same base, same width: no rebuild
+        assert run_device(engine, b2, buf) == e2
+        assert run_device(engine, b1, buf) == e1
+        assert engine.mul_table_builds() == before + 3
+        engine.set_mul_window(16)
+        assert run_device(engine, b1, buf) == e1
+        assert engine.mul_table_builds() == before + 4  # the width is part of the key
+
+
+def test_resident_bases_survive(engine, oracle):
+    n = 1000
+    points = util.oracle_gen_points(oracle, n, 0x1234567, 0x89AB)
+    ks = R.encode_scalars(R.rand_scalars(0x4E51, n))
+    d_p, d_k = dev(points), dev(ks)
+    exp = util.oracle_msm(oracle, points, ks)
+    engine.set_bases_device(d_p.data_ptr(), n)
+    assert engine.msm_fixed_base_device(d_k.data_ptr(), n) == exp
+    buf = R.encode_scalars(V.EDGE + V.random_scalars(0x4E52, 300))
+    base = V.base_bytes(R.mul(R.G, 0xD00D))
+    for width in V.WIDTHS:
+        with window(engine, width):
+            assert run_device(engine, base, buf) == msm.batch_mul_host(base, buf)
+        assert engine.msm_fixed_base_device(d_k.data_ptr(), n) == exp
+    rep = engine.check_points_device(d_p.data_ptr(), n)  # a check call in between: neither state touches the other
+    assert rep.ok
+    assert run_device(engine, base, buf) == msm.batch_mul_host(base, buf)
+    assert engine.msm_fixed_base_device(d_k.data_ptr(), n) == exp
+
+
+# ---- Montgomery scalars ----
+@pytest.mark.parametrize("width", V.WIDTHS)
+def test_montgomery_scalars(engine, width):
+    n = 257
+    values = ([0, 1, r - 1, r, r + 1, 2**256 - 1, 2**255] + V.random_scalars(0x30A7, n))[:n]
+    reduced = [v * pow(2**256, -1, r) % r for v in values]
+    exp = msm.batch_mul_host(G_BYTES, R.encode_scalars(reduced))
+    with window(engine, width):
+        assert run_device(engine, G_BYTES, R.encode_scalars(reduced)) == exp
+        engine.set_input_format("wire", "mont")
+        try:
+            assert run_device(engine, G_BYTES, R.encode_scalars(values)) == exp
+            assert engine.batch_mul(G_BYTES, R.encode_scalars(values)) == exp
+        finally:
+            engine.set_input_format("wire", "wire")
+
+
+# ---- arguments ----
+def test_arguments(engine):
+    import torch
+
+    lib = msm.load_library()
+    ctx = engine._ctx
+    d_s = dev(R.encode_scalars([3, 4]))
+    d_out = torch.full((208,), 0xA5, dtype=torch.uint8, device="cuda")
+    d_inf = torch.full((16,), 0xA5, dtype=torch.uint8, device="cuda")
+    builds = engine.mul_table_builds()
+    fresh = V.base_bytes(R.mul(R.G, 0xE1A7))
+
+    def call(base, s, n, form, out):
+        return lib.msm377_g1_batch_mul_device(ctx, base, s, n, form, out, d_inf.data_ptr())
+
+    assert call(fresh, d_s.data_ptr(), 0, V.WIRE, d_out.data_ptr()) == 0  # n = 0: no launch, no table
+    assert call(None, None, 0, V.MONT_FLAG, None) == 0
+    assert call(fresh, d_s.data_ptr(), 2, V.MONT, d_out.data_ptr()) == EINVAL
+    assert call(fresh, d_s.data_ptr(), 0, V.MONT, d_out.data_ptr()) == EINVAL
+    assert call(fresh, d_s.data_ptr(), 2, 3, d_out.data_ptr()) == EINVAL
+    assert call(None, d_s.data_ptr(), 2, V.WIRE, d_out.data_ptr()) == EINVAL
+    assert call(fresh, None, 2, V.WIRE, d_out.data_ptr()) == EINVAL
+    assert call(fresh, d_s.data_ptr(), 2, V.WIRE, None) == EINVAL
+    assert call(fresh, d_s.data_ptr() + 4, 2, V.WIRE, d_out.data_ptr()) == EINVAL  # alignment
+    noncanonical = (R.P).to_bytes(48, "little") + R.G[1].to_bytes(48, "little")
+    assert call(noncanonical, d_s.data_ptr(), 2, V.WIRE, d_out.data_ptr()) == EINVAL
+    assert lib.msm377_g1_batch_mul(ctx, fresh, None, 2, V.WIRE, None, None) == EINVAL
+    assert lib.msm377_g1_batch_mul(ctx, fresh, None, 0, V.WIRE, None, None) == 0
+    assert engine.mul_table_builds() == builds
+    assert bytes(d_out.cpu().numpy()) == b"\xa5" * 208 and bytes(d_inf.cpu().numpy()) == b"\xa5" * 16
+    for bad in (1, 4, 12, 17, -8):
+        with pytest.raises(msm.MsmError) as e:
+            engine.set_mul_window(bad)
+        assert e.value.code == EINVAL
+    got, flags = run_device(engine, fresh, R.encode_scalars([3, 4]), flags=False)  # d_out_inf may be null
+    assert got == R.encode_points([R.mul(R.G, 3 * 0xE1A7), R.mul(R.G, 4 * 0xE1A7)]) and flags == b"\xee\xee"

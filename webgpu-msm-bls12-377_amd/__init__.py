@@ -29,6 +29,7 @@ from .host.engine import (  # noqa: F401
     StageInfo,
     MsmEngine,
     MsmError,
+    batch_mul_host,
     check_points_host,
     ed_check_points_host,
     import_points_host,
@@ -48,6 +49,7 @@ __all__ = [
     "MsmError",
     "CheckReport",
     "StageInfo",
+    "batch_mul_host",
     "check_points_host",
     "ed_check_points_host",
     "CHECK_CANONICAL",

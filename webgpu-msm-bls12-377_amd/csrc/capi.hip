@@ -11,6 +11,7 @@
 #include "context.hpp"
 #include "host_tail.hpp"
 #include "sequencer.hpp"
+#include "batch_mul_host.hpp"
 #include "import_host.hpp"
 #include "validate_host.hpp"
 
@@ -161,7 +162,8 @@ void msm377_ctx_destroy(msm377_ctx* ctx) {
     ctx->twin = nullptr;
   }
   void* bufs[] = {ctx->d_raw_points, ctx->d_raw_scalars, ctx->d_bases, ctx->d_digits, ctx->d_range_counts, ctx->d_region_base, ctx->d_sort_temp,
-                  ctx->d_row_ptr, ctx->d_val_idx, ctx->d_buckets, ctx->d_buckets_snap, ctx->d_partials, ctx->d_work, ctx->d_work_meta, ctx->d_row_ovf_base, ctx->d_split_rows, ctx->d_ovf, ctx->d_err, ctx->d_aff_stash, ctx->d_aff_trees, ctx->d_aff_count, ctx->d_out_count, ctx->resident.table, ctx->d_native, ctx->d_inf_mask};
+                  ctx->d_row_ptr, ctx->d_val_idx, ctx->d_buckets, ctx->d_buckets_snap, ctx->d_partials, ctx->d_work, ctx->d_work_meta, ctx->d_row_ovf_base, ctx->d_split_rows, ctx->d_ovf, ctx->d_err, ctx->d_aff_stash, ctx->d_aff_trees, ctx->d_aff_count, ctx->d_out_count, ctx->resident.table, ctx->d_native, ctx->d_inf_mask,
+                  ctx->bm.table, ctx->bm.stash, ctx->bm.trees, ctx->bm.block_prod, ctx->bm.block_inv, ctx->bm.row_bases, ctx->bm.base_wire};
   for (void* p : bufs)
     if (p) (void)hipFree(p);
   ctx->wide.release();
@@ -421,6 +423,21 @@ int msm377_g1_result_to_native(const uint8_t xy[96], uint8_t out[104]) {
   return result_to_native_host(xy, out) ? MSM377_OK : MSM377_EINVAL;
 }
 
+// ---- fixed-base batch multiplication: the host-only parts (batch_mul_host.hpp) and the settings ----
+int msm377_g1_batch_mul_host(const uint8_t base_xy[96], const uint8_t* scalars, uint64_t n, uint32_t out_form, uint8_t* out_points, uint8_t* out_inf) {
+  return batch_mul_host(base_xy, scalars, n, MSM377_SCALARS_WIRE, out_form, out_points, out_inf);
+}
+
+int msm377_ctx_set_mul_window(msm377_ctx* ctx, int window_bits) {
+  if (!ctx || (window_bits != 0 && !batch_mul_width_supported(window_bits))) return MSM377_EINVAL;
+  ctx->bm.window = window_bits;
+  return MSM377_OK;
+}
+
+int msm377_ctx_get_last_mul_window(const msm377_ctx* ctx) { return ctx ? ctx->bm.last_window : 0; }
+
+uint64_t msm377_ctx_get_mul_table_builds(const msm377_ctx* ctx) { return ctx ? ctx->bm.builds : 0; }
+
 int msm377_ctx_get_last_check(const msm377_ctx* ctx, msm377_check_report* out) {
   if (!ctx || !out) return MSM377_EINVAL;
   *out = ctx->last_check;
@@ -516,6 +533,8 @@ int msm377_g1_msm_fixed_base_batch_device(msm377_ctx* ctx, const void* d_scalars
 int msm377_g1_msm_fixed_base(msm377_ctx* ctx, const uint8_t* scalars, uint64_t n, uint8_t out_xy[96]) { return eng::g1_msm_fixed_base(ctx, scalars, n, out_xy); }
 int msm377_g1_glv_window_partials_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t win_begin, uint32_t win_count, uint8_t* partials_out) { return eng::g1_glv_window_partials_device(ctx, d_points, d_scalars, n, win_begin, win_count, partials_out); }
 int msm377_g1_generate_bases_device(msm377_ctx* ctx, uint64_t seed, uint64_t n, void* d_points_out) { return eng::g1_generate_bases_device(ctx, seed, n, d_points_out); }
+int msm377_g1_batch_mul_device(msm377_ctx* ctx, const uint8_t base_xy[96], const void* d_scalars, uint64_t n, uint32_t out_form, void* d_out_points, uint8_t* d_out_inf) { return eng::g1_batch_mul_device(ctx, base_xy, d_scalars, n, out_form, d_out_points, d_out_inf); }
+int msm377_g1_batch_mul(msm377_ctx* ctx, const uint8_t base_xy[96], const uint8_t* scalars, uint64_t n, uint32_t out_form, uint8_t* out_points, uint8_t* out_inf) { return eng::g1_batch_mul(ctx, base_xy, scalars, n, out_form, out_points, out_inf); }
 int msm377_g1_check_points_device(msm377_ctx* ctx, const void* d_points, uint64_t n, uint32_t flags, msm377_check_report* out) { return eng::g1_check_points_device(ctx, d_points, n, flags, out); }
 int msm377_g1_check_points(msm377_ctx* ctx, const uint8_t* points, uint64_t n, uint32_t flags, msm377_check_report* out) { return eng::g1_check_points(ctx, points, n, flags, out); }
 int msm377_ed_check_points_device(msm377_ctx* ctx, const void* d_points, uint64_t n, uint32_t flags, msm377_check_report* out) { return ed_wire_only(ctx) ? MSM377_EINVAL : eng::ed_check_points_device(ctx, d_points, n, flags, out); }

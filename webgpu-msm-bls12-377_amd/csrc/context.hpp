@@ -41,6 +41,27 @@ struct ResidentBases {
   }
 };
 
+// Fixed-base batch multiplication (msm377_g1_batch_mul*, kernels/batch_mul.hpp): the window table of ONE base, keyed by
+// the base's 96 wire bytes and the window width, and the fixed-size scratch a chunk of outputs passes through.  Like the
+// resident base table the window table is valid only from the successful end of a build: a build clears `valid` first
+// and sets it as its last step.  Nothing here is shared with the MSM paths or the check calls.
+struct BatchMulState {
+  int window = 0;          // msm377_ctx_set_mul_window: 0 = the rule by n, else the forced width
+  int last_window = 0;     // width the last call ran (msm377_ctx_get_last_mul_window)
+  uint64_t builds = 0;     // table builds so far (msm377_ctx_get_mul_table_builds)
+  bool valid = false;
+  uint8_t base[96] = {};   // key: the base ...
+  int width = 0;           // ... and the width of the table in `table`
+  uint32_t* table = nullptr;        // records of the current table
+  uint64_t table_cap = 0;           // records allocated
+  uint32_t* stash = nullptr;        // BM_PIECES x BM_CHUNK 16-byte pieces
+  uint32_t* trees = nullptr;        // one product tree per workgroup of a chunk
+  uint32_t* block_prod = nullptr;   // 13 limbs per workgroup: its product, then (block_inv) the inverse
+  uint32_t* block_inv = nullptr;
+  uint32_t* row_bases = nullptr;    // (W + 1) table records: [2^(c w)]B
+  uint32_t* base_wire = nullptr;    // the base's 96 bytes on the device
+};
+
 // Work buffers of the 20-bit-window sort (kernels/wide.hpp) for up to `cap` points.
 struct WideBuffers {
   uint32_t* digits = nullptr;  // 13 x n u32 biased 20-bit digits, the flat list the sort reads
@@ -96,6 +117,7 @@ struct msm377_ctx {
   uint32_t* d_inf_mask = nullptr;     // two infinity masks (the one that travels with d_raw_points; the check calls' scratch), then their counters
   hipEvent_t import_done = nullptr;   // the side stream waits for it before it reads imported points
   ResidentBases resident;             // fixed-base mode: the bases of the last successful msm377_g1_set_bases* call
+  BatchMulState bm;                   // fixed-base batch multiplication: its table and scratch (allocated on first use)
   WideBuffers wide;                   // the 20-bit-window sort's buffers (allocated with such a table; the twin's own set)
   int precomp_bits = MSM377_WINDOW_BITS;  // window width msm377_g1_set_bases_precomputed builds its next table for: 16 or 20 (msm377_ctx_set_precompute_window, MSM377_PRECOMP_BITS)
   uint32_t* d_aff_stash = nullptr;    // cap x 52 words: N1, N2, Z, running product per point (k_affine_up -> k_affine_down)

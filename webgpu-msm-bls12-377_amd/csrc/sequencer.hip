@@ -39,6 +39,7 @@
 #include "host_tail.hpp"
 #include "validate_host.hpp"
 #include "kernels/accumulate.hpp"
+#include "kernels/batch_mul.hpp"
 #include "kernels/convert.hpp"
 #include "kernels/decompose.hpp"
 #include "kernels/generate.hpp"
@@ -2038,6 +2039,170 @@ int g1_glv_window_partials_device(msm377_ctx* ctx, const void* d_points, const v
   if (rc) return rc;
   memcpy(partials_out, ctx->h_partials, (size_t)win_count * MSM377_G1_WINDOW_PARTIAL_BYTES);
   return MSM377_OK;
+}
+
+// ---- fixed-base batch multiplication (include/msm377.h "fixed-base batch multiplication"; kernels/batch_mul.hpp) ----
+// Everything runs on ctx->stream, launch after launch; the one host wait is the synchronisation at the end of the call.
+namespace {
+
+int bm_alloc(msm377_ctx* ctx, uint32_t** p, size_t bytes) {
+  if (*p) return MSM377_OK;
+  if (hipMalloc((void**)p, bytes) != hipSuccess) {
+    *p = nullptr;
+    (void)hipGetLastError();
+    ctx->err = "out of device memory for the batch multiplication scratch";
+    return MSM377_ENOMEM;
+  }
+  return MSM377_OK;
+}
+
+// The scratch of one chunk: fixed sizes, whatever n and the context's capacity are.
+int bm_ensure_scratch(msm377_ctx* ctx) {
+  BatchMulState& bm = ctx->bm;
+  int rc = bm_alloc(ctx, &bm.stash, (size_t)BM_PIECES * BM_CHUNK * 16);
+  if (!rc) rc = bm_alloc(ctx, &bm.trees, (size_t)BM_CHUNK_BLOCKS * BM_TREE_WORDS * 4);
+  if (!rc) rc = bm_alloc(ctx, &bm.block_prod, (size_t)BM_CHUNK_BLOCKS * 13 * 4);
+  if (!rc) rc = bm_alloc(ctx, &bm.block_inv, (size_t)BM_CHUNK_BLOCKS * 13 * 4);
+  if (!rc) rc = bm_alloc(ctx, &bm.row_bases, (size_t)(bm_windows(BM_MIN_WIDTH) + 1) * BM_REC_WORDS * 4);
+  if (!rc) rc = bm_alloc(ctx, &bm.base_wire, 96);
+  return rc;
+}
+
+// The m <= BM_CHUNK points the stash holds -> records of `form` at d_out: three launches.
+int bm_normalise(msm377_ctx* ctx, uint64_t m, uint32_t form, void* d_out, uint8_t* d_out_inf) {
+  BatchMulState& bm = ctx->bm;
+  const uint32_t blocks = (uint32_t)((m + BM_BLOCK - 1) / BM_BLOCK);
+  uint4* stash = reinterpret_cast<uint4*>(bm.stash);
+  hipLaunchKernelGGL(k_bm_up, dim3(blocks), dim3(BM_THREADS), 0, ctx->stream, stash, m, bm.trees, bm.block_prod);
+  hipLaunchKernelGGL(k_bm_across, dim3(1), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)bm.block_prod, blocks, bm.block_inv);
+  const dim3 grid(blocks), block(BM_THREADS);
+  if (form == MSM377_POINTS_WIRE)
+    hipLaunchKernelGGL(k_bm_down<MSM377_POINTS_WIRE>, grid, block, 0, ctx->stream, (const uint4*)stash, m, (const uint32_t*)bm.trees, (const uint32_t*)bm.block_inv, (uint8_t*)d_out, d_out_inf);
+  else if (form == MSM377_POINTS_MONT_FLAG)
+    hipLaunchKernelGGL(k_bm_down<MSM377_POINTS_MONT_FLAG>, grid, block, 0, ctx->stream, (const uint4*)stash, m, (const uint32_t*)bm.trees, (const uint32_t*)bm.block_inv, (uint8_t*)d_out, d_out_inf);
+  else
+    hipLaunchKernelGGL(k_bm_down<BM_FORM_TABLE>, grid, block, 0, ctx->stream, (const uint4*)stash, m, (const uint32_t*)bm.trees, (const uint32_t*)bm.block_inv, (uint8_t*)d_out, d_out_inf);
+  HIP_TRY(ctx, hipGetLastError());
+  return MSM377_OK;
+}
+
+// The window table of (base, c): kept until either key changes.  A build drops the old table FIRST and marks the new one
+// valid as its last step, behind a wait for its launches: a failed build leaves no table behind.
+int bm_ensure_table(msm377_ctx* ctx, const uint8_t base_xy[96], int c) {
+  BatchMulState& bm = ctx->bm;
+  if (bm.valid && bm.width == c && memcmp(bm.base, base_xy, 96) == 0) return MSM377_OK;
+  bm.valid = false;
+  const uint64_t records = bm_table_records((uint32_t)c);
+  if (bm.table_cap < records) {
+    if (bm.table) (void)hipFree(bm.table);
+    bm.table = nullptr;
+    bm.table_cap = 0;
+    const int rc = bm_alloc(ctx, &bm.table, (size_t)records * BM_REC_WORDS * 4);
+    if (rc) return rc;
+    bm.table_cap = records;
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(bm.base_wire, base_xy, 96, hipMemcpyHostToDevice, ctx->stream));
+  uint4* stash = reinterpret_cast<uint4*>(bm.stash);
+  hipLaunchKernelGGL(k_bm_row_bases, dim3(1), dim3(64), 0, ctx->stream, (const uint32_t*)bm.base_wire, (uint32_t)c, stash);
+  int rc = bm_normalise(ctx, (uint64_t)bm_windows(c) + 1, BM_FORM_TABLE, bm.row_bases, nullptr);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_bm_entries, dim3((unsigned)((records + BM_THREADS - 1) / BM_THREADS)), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)bm.row_bases, (uint32_t)c, stash);
+  rc = bm_normalise(ctx, records, BM_FORM_TABLE, bm.table, nullptr);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // the base bytes are the caller's; and a table is valid only once it is there
+  memcpy(bm.base, base_xy, 96);
+  bm.width = c;
+  bm.builds++;
+  bm.valid = true;
+  return MSM377_OK;
+}
+
+bool bm_base_canonical(const uint8_t base_xy[96]) {
+  uint64_t lim[2][6];
+  memcpy(lim, base_xy, 96);
+  return !Fp64::geq_p(lim[0]) && !Fp64::geq_p(lim[1]);
+}
+
+int bm_check_form(msm377_ctx* ctx, uint32_t out_form) {
+  if (!ctx) return MSM377_EINVAL;
+  ctx->err.clear();
+  if (out_form == MSM377_POINTS_WIRE || out_form == MSM377_POINTS_MONT_FLAG) return MSM377_OK;
+  ctx->err = out_form == MSM377_POINTS_MONT ? "batch_mul outputs need a form that can say \"identity\": MSM377_POINTS_WIRE or MSM377_POINTS_MONT_FLAG" : "unknown output form";
+  return MSM377_EINVAL;
+}
+
+}  // namespace
+
+int g1_batch_mul_device(msm377_ctx* ctx, const uint8_t base_xy[96], const void* d_scalars, uint64_t n, uint32_t out_form, void* d_out_points, uint8_t* d_out_inf) {
+  int rc = bm_check_form(ctx, out_form);
+  if (rc) return rc;
+  if (n == 0) return MSM377_OK;
+  if (!base_xy || !d_scalars || !d_out_points) {
+    ctx->err = "null pointer";
+    return MSM377_EINVAL;
+  }
+  const uintptr_t out_align = out_form == MSM377_POINTS_WIRE ? 15 : 7;
+  if (((uintptr_t)d_scalars & 15) || ((uintptr_t)d_out_points & out_align)) {
+    ctx->err = "device pointers must be 16-byte aligned (8-byte for mont_flag records)";
+    return MSM377_EINVAL;
+  }
+  if (!bm_base_canonical(base_xy)) {
+    ctx->err = "the base has a coordinate that is not below p";
+    return MSM377_EINVAL;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const int c = ctx->bm.window ? ctx->bm.window : batch_mul_rule(n);
+  rc = bm_ensure_scratch(ctx);
+  if (!rc) rc = bm_ensure_table(ctx, base_xy, c);
+  if (rc) {
+    (void)hipStreamSynchronize(ctx->stream);
+    return rc;
+  }
+  ctx->bm.last_window = c;
+  const size_t stride = out_form == MSM377_POINTS_WIRE ? 96 : 104;
+  for (uint64_t off = 0; off < n && !rc; off += BM_CHUNK) {
+    const uint64_t m = std::min<uint64_t>(BM_CHUNK, n - off);
+    hipLaunchKernelGGL(k_bm_accumulate, dim3((unsigned)((m + BM_THREADS - 1) / BM_THREADS)), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)ctx->bm.table,
+                       (const uint32_t*)d_scalars + off * 8, m, (uint32_t)c, ctx->scalar_form == MSM377_SCALARS_MONT ? 1u : 0u, reinterpret_cast<uint4*>(ctx->bm.stash));
+    rc = bm_normalise(ctx, m, out_form, (uint8_t*)d_out_points + off * stride, d_out_inf ? d_out_inf + off : nullptr);
+  }
+  const hipError_t e = hipStreamSynchronize(ctx->stream);
+  if (rc) return rc;
+  HIP_TRY(ctx, e);
+  return MSM377_OK;
+}
+
+// Host buffers: scalars up, records (and flags) down, a chunk's worth of device staging for the length of the call.
+int g1_batch_mul(msm377_ctx* ctx, const uint8_t base_xy[96], const uint8_t* scalars, uint64_t n, uint32_t out_form, uint8_t* out_points, uint8_t* out_inf) {
+  int rc = bm_check_form(ctx, out_form);
+  if (rc) return rc;
+  if (n == 0) return MSM377_OK;
+  if (!base_xy || !scalars || !out_points) {
+    ctx->err = "null pointer";
+    return MSM377_EINVAL;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t stride = out_form == MSM377_POINTS_WIRE ? 96 : 104;
+  const uint64_t piece = std::min<uint64_t>(n, BM_CHUNK);
+  uint8_t* d_io = nullptr;  // scalars, records, flags: 16-byte aligned parts
+  const size_t off_out = (size_t)piece * 32, off_inf = off_out + (((size_t)piece * stride + 15) & ~(size_t)15);
+  if (hipMalloc((void**)&d_io, off_inf + piece) != hipSuccess) {
+    (void)hipGetLastError();
+    ctx->err = "out of device memory for the batch multiplication staging";
+    return MSM377_ENOMEM;
+  }
+  const int forced = ctx->bm.window;
+  if (!forced) ctx->bm.window = batch_mul_rule(n);  // one width for the whole call, whatever the pieces' sizes
+  for (uint64_t off = 0; off < n && !rc; off += piece) {
+    const uint64_t m = std::min<uint64_t>(piece, n - off);
+    rc = hip_ok(ctx, hipMemcpy(d_io, scalars + off * 32, m * 32, hipMemcpyHostToDevice), "hipMemcpy(scalars)") ? MSM377_OK : MSM377_EHIP;
+    if (!rc) rc = g1_batch_mul_device(ctx, base_xy, d_io, m, out_form, d_io + off_out, d_io + off_inf);
+    if (!rc) rc = hip_ok(ctx, hipMemcpy(out_points + off * stride, d_io + off_out, m * stride, hipMemcpyDeviceToHost), "hipMemcpy(records)") ? MSM377_OK : MSM377_EHIP;
+    if (!rc && out_inf) rc = hip_ok(ctx, hipMemcpy(out_inf + off, d_io + off_inf, m, hipMemcpyDeviceToHost), "hipMemcpy(flags)") ? MSM377_OK : MSM377_EHIP;
+  }
+  ctx->bm.window = forced;
+  (void)hipFree(d_io);
+  return rc;
 }
 
 int g1_generate_bases_device(msm377_ctx* ctx, uint64_t seed, uint64_t n, void* d_points_out) {

@@ -38,6 +38,10 @@ int g1_check_points(msm377_ctx* ctx, const uint8_t* points, uint64_t n, uint32_t
 int ed_check_points_device(msm377_ctx* ctx, const void* d_points, uint64_t n, uint32_t flags, msm377_check_report* out);
 int ed_check_points(msm377_ctx* ctx, const uint8_t* points, uint64_t n, uint32_t flags, msm377_check_report* out);
 
+// Fixed-base batch multiplication (kernels/batch_mul.hpp): out[i] = [s_i]B, every output its own affine point.
+int g1_batch_mul_device(msm377_ctx* ctx, const uint8_t base_xy[96], const void* d_scalars, uint64_t n, uint32_t out_form, void* d_out_points, uint8_t* d_out_inf);
+int g1_batch_mul(msm377_ctx* ctx, const uint8_t base_xy[96], const uint8_t* scalars, uint64_t n, uint32_t out_form, uint8_t* out_points, uint8_t* out_inf);
+
 int reserve_host_staging(msm377_ctx* ctx);
 void twin_return(msm377_ctx* ctx);  // takes back the resident bases a batch call lent to the twin of ctx
 

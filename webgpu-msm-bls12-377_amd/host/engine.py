@@ -214,6 +214,12 @@ def load_library():
         "msm377_g1_import_points_host": (i32, [u8p, u64, u32, vp, vp]),
         "msm377_import_scalars_host": (i32, [u8p, u64, u32, vp]),
         "msm377_g1_result_to_native": (i32, [u8p, vp]),
+        "msm377_g1_batch_mul_device": (i32, [vp, u8p, vp, u64, u32, vp, vp]),
+        "msm377_g1_batch_mul": (i32, [vp, u8p, u8p, u64, u32, vp, vp]),
+        "msm377_g1_batch_mul_host": (i32, [u8p, u8p, u64, u32, vp, vp]),
+        "msm377_ctx_set_mul_window": (i32, [vp, i32]),
+        "msm377_ctx_get_last_mul_window": (i32, [vp]),
+        "msm377_ctx_get_mul_table_builds": (u64, [vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
@@ -313,6 +319,31 @@ def result_to_native(xy: bytes) -> bytes:
     if rc:
         raise MsmError(rc, "msm377_g1_result_to_native")
     return out.raw
+
+
+def _batch_mul_out_form(out_form) -> int:
+    """Output forms of the batch_mul calls: "wire" or "mont_flag" (plain "mont" cannot say "identity": the library
+    refuses it)."""
+    return _form(_POINT_FORMS, out_form, "output")
+
+
+def batch_mul_host(base: bytes, scalars: bytes, out_form="wire") -> Tuple[bytes, bytes]:
+    """out[i] = [s_i]B on the calling thread (msm377_g1_batch_mul_host): no context, no device.  ``base``: 96 wire
+    bytes; ``scalars``: 32-byte little-endian integers, any value below 2^256.  Returns (records, identity flags): 96-byte
+    wire or 104-byte mont_flag records and one byte per output, 1 for the identity."""
+    if len(base) != 96:
+        raise ValueError("a base is 96 bytes")
+    if len(scalars) % 32:
+        raise ValueError("scalars buffer length must be a multiple of 32")
+    f = _batch_mul_out_form(out_form)
+    n = len(scalars) // 32
+    stride = _POINT_STRIDE.get(f, 96)
+    out = ctypes.create_string_buffer(max(1, stride * n))
+    inf = ctypes.create_string_buffer(max(1, n))
+    rc = load_library().msm377_g1_batch_mul_host(bytes(base), bytes(scalars), n, f, ctypes.addressof(out), ctypes.addressof(inf))
+    if rc:
+        raise MsmError(rc, "msm377_g1_batch_mul_host")
+    return out.raw[: stride * n], inf.raw[:n]
 
 
 def short_windows(scalar_bits: int, bucket_log: int) -> int:
@@ -602,6 +633,45 @@ class MsmEngine:
 
     def generate_bases_device(self, seed: int, n: int, d_points_out: int):
         self._check(self._lib.msm377_g1_generate_bases_device(self._ctx, int(seed) & (2**64 - 1), int(n), d_points_out), "msm377_g1_generate_bases_device")
+
+    # -- fixed-base batch multiplication (include/msm377.h): out[i] = [s_i]B, every output its own point --
+    def batch_mul_device(self, base: bytes, d_scalars: int, n: int, d_out: int, d_inf: int = 0, out_form="wire"):
+        """n scalars in HBM (in the engine's scalar form) times the base ``base`` (96 wire bytes, a host buffer): n
+        records at ``d_out`` -- 96-byte wire or 104-byte "mont_flag" -- and, if ``d_inf`` is given, n identity flag bytes
+        there (msm377_g1_batch_mul_device).  Any n; every curve point is a legal base."""
+        if len(base) != 96:
+            raise ValueError("a base is 96 bytes")
+        rc = self._lib.msm377_g1_batch_mul_device(self._ctx, bytes(base), d_scalars, int(n), _batch_mul_out_form(out_form), d_out, d_inf or None)
+        self._check(rc, "msm377_g1_batch_mul_device")
+
+    def batch_mul(self, base: bytes, scalars: bytes, out_form="wire") -> Tuple[bytes, bytes]:
+        """The same on host buffers: returns (records, identity flags), one flag byte per output (msm377_g1_batch_mul)."""
+        if len(base) != 96:
+            raise ValueError("a base is 96 bytes")
+        if len(scalars) % 32:
+            raise ValueError("scalars buffer length must be a multiple of 32")
+        f = _batch_mul_out_form(out_form)
+        n = len(scalars) // 32
+        stride = _POINT_STRIDE.get(f, 96)
+        out = ctypes.create_string_buffer(max(1, stride * n))
+        inf = ctypes.create_string_buffer(max(1, n))
+        rc = self._lib.msm377_g1_batch_mul(self._ctx, bytes(base), bytes(scalars), n, f, ctypes.addressof(out), ctypes.addressof(inf))
+        self._check(rc, "msm377_g1_batch_mul")
+        return out.raw[: stride * n], inf.raw[:n]
+
+    def set_mul_window(self, bits: int = 0):
+        """Window width of the batch_mul calls' table: 8 or 16, 0 = by the number of outputs (the default;
+        msm377_ctx_set_mul_window)."""
+        self._check(self._lib.msm377_ctx_set_mul_window(self._ctx, int(bits)), "msm377_ctx_set_mul_window")
+
+    def last_mul_window(self) -> int:
+        """Width the last batch_mul call ran, 0 before the first (msm377_ctx_get_last_mul_window)."""
+        return int(self._lib.msm377_ctx_get_last_mul_window(self._ctx))
+
+    def mul_table_builds(self) -> int:
+        """Window tables this engine has built so far: a repeated (base, width) builds none
+        (msm377_ctx_get_mul_table_builds)."""
+        return int(self._lib.msm377_ctx_get_mul_table_builds(self._ctx))
 
     # -- input validation (include/msm377.h): the verdict is the report, a finding is not an error --
     def _check_points(self, fn: str, points, n: int, flags: int) -> CheckReport:

@@ -109,4 +109,15 @@ const compute_msm_fixed_base = (scalars) => {
 const CHECK_CANONICAL = 1, CHECK_CURVE = 2, CHECK_SUBGROUP = 4, CHECK_ALL = 7;
 const check_points = (points, flags = CHECK_ALL) => addon.checkPointsSync(pointsToBuffer(points), flags);
 
-module.exports = { compute_msm, compute_msm_edwards, set_bases, compute_msm_fixed_base, check_points, CHECK_CANONICAL, CHECK_CURVE, CHECK_SUBGROUP, CHECK_ALL, pointsToBuffer, scalarsToBuffer, version: addon.version };
+// Fixed-base batch multiplication (msm377_g1_batch_mul): out[i] = [s_i]B for ONE base B ({x, y}, or a 96-byte Buffer) and n
+// scalars, every output its own point.  Returns {points, infinity}: n records -- 96-byte wire (outForm 'wire', default) or
+// 104-byte 'mont_flag' -- and one byte per output, 1 for the identity.  Any curve point is a legal base and any 32-byte
+// value a legal scalar.
+const BATCH_MUL_FORMS = { wire: 0, mont_flag: 2 };
+const batch_mul = (base, scalars, { outForm = 'wire' } = {}) => {
+  if (!(outForm in BATCH_MUL_FORMS)) throw new RangeError("outForm: wire | mont_flag (plain mont cannot say 'identity')");
+  const baseBuf = Buffer.isBuffer(base) ? base : pointsToBuffer([base]);
+  return addon.batchMulSync(baseBuf, scalarsToBuffer(scalars), BATCH_MUL_FORMS[outForm]);
+};
+
+module.exports = { batch_mul, compute_msm, compute_msm_edwards, set_bases, compute_msm_fixed_base, check_points, CHECK_CANONICAL, CHECK_CURVE, CHECK_SUBGROUP, CHECK_ALL, pointsToBuffer, scalarsToBuffer, version: addon.version };

@@ -176,3 +176,19 @@ export const compute_msm_fixed_base = (scalars: bigint[] | Uint32Array[] | Buffe
 // Input validation (msm377_g1_check_points): compute_msm trusts its input; call this on freshly loaded points first.
 export const check_points = (points: BigIntPoint[] | U32ArrayPoint[] | Buffer, flags: number = CHECK_ALL): CheckReport =>
   addon.checkPointsSync(pointsToBuffer(points), flags);
+
+// Fixed-base batch multiplication (msm377_g1_batch_mul): out[i] = [s_i]B for ONE base B and n scalars, every output its own
+// point.  `points`: n records -- 96-byte wire (outForm 'wire', default) or 104-byte 'mont_flag'; `infinity`: one byte per
+// output, 1 for the identity.  Any curve point is a legal base and any 32-byte value a legal scalar.
+const BATCH_MUL_FORMS = { wire: 0, mont_flag: 2 } as const;
+export const batch_mul = (
+  base: BigIntPoint | U32ArrayPoint | Buffer,
+  scalars: bigint[] | Uint32Array[] | Buffer,
+  { outForm = 'wire' }: { outForm?: keyof typeof BATCH_MUL_FORMS } = {},
+): { points: Buffer; infinity: Buffer } => {
+  if (!(outForm in BATCH_MUL_FORMS)) {
+    throw new RangeError("outForm: wire | mont_flag (plain mont cannot say 'identity')");
+  }
+  const baseBuf = Buffer.isBuffer(base) ? base : pointsToBuffer([base] as BigIntPoint[] | U32ArrayPoint[]);
+  return addon.batchMulSync(baseBuf, scalarsToBuffer(scalars), BATCH_MUL_FORMS[outForm]);
+};

@@ -15,6 +15,9 @@
 //   fixedBaseMsmSync(scalars: Buffer 32n): Buffer                      ... and run MSMs of n <= its size against it
 //   checkPointsSync(points: Buffer 96n, flags: number): object         input validation (msm377_g1_check_points): the report's
 //                                                                      64-bit fields as BigInt, firstBad null if none
+//   batchMulSync(base: Buffer 96, scalars: Buffer 32n, outForm: number): {points: Buffer, infinity: Buffer}
+//                                                                      out[i] = [s_i]B (msm377_g1_batch_mul): 96-byte wire or
+//                                                                      104-byte mont_flag records, one identity byte per output
 //   version(): string
 // Errors reject / throw a JS Error carrying msm377_strerror + msm377_last_error, matching the
 // reference's behaviour of throwing Error (cuzk/gpu.ts:7-10).
@@ -331,6 +334,50 @@ napi_value CheckPointsSync(napi_env env, napi_callback_info info) {
   return obj;
 }
 
+// batchMulSync(base, scalars, outForm) -> {points, infinity}: n multiples of one base, each its own point
+napi_value BatchMulSync(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  bool bb = false, sb = false;
+  uint32_t form = MSM377_POINTS_WIRE;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 3 || napi_is_buffer(env, argv[0], &bb) != napi_ok || !bb ||
+      napi_is_buffer(env, argv[1], &sb) != napi_ok || !sb || napi_get_value_uint32(env, argv[2], &form) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "expected (base: Buffer of 96 bytes, scalars: Buffer of 32 bytes per scalar, outForm: number)");
+    return nullptr;
+  }
+  uint8_t *b, *s;
+  size_t bl, sl;
+  napi_get_buffer_info(env, argv[0], reinterpret_cast<void**>(&b), &bl);
+  napi_get_buffer_info(env, argv[1], reinterpret_cast<void**>(&s), &sl);
+  if (bl != 96 || sl % 32 != 0 || (form != MSM377_POINTS_WIRE && form != MSM377_POINTS_MONT_FLAG)) {
+    napi_throw_range_error(env, nullptr, "base must hold 96 bytes, scalars 32 bytes each; outForm is 0 (wire) or 2 (mont_flag)");
+    return nullptr;
+  }
+  const uint64_t n = sl / 32;
+  const size_t stride = form == MSM377_POINTS_MONT_FLAG ? 104 : 96;
+  napi_value points, infinity, obj;
+  void *pd = nullptr, *id = nullptr;
+  if (napi_create_buffer(env, n * stride, &pd, &points) != napi_ok || napi_create_buffer(env, n, &id, &infinity) != napi_ok) return nullptr;
+  std::string err;
+  int rc;
+  {
+    std::lock_guard<std::mutex> lock(g_mu);
+    rc = ensure_ctx(1, &err);  // any capacity: the call walks n in chunks of its own
+    if (!rc) {
+      rc = msm377_g1_batch_mul(g_ctx, b, s, n, form, static_cast<uint8_t*>(pd), static_cast<uint8_t*>(id));
+      if (rc) err = std::string("msm377_g1_batch_mul: ") + msm377_strerror(rc) + ": " + msm377_last_error(g_ctx);
+    }
+  }
+  if (rc) {
+    napi_throw_error(env, nullptr, err.c_str());
+    return nullptr;
+  }
+  napi_create_object(env, &obj);
+  napi_set_named_property(env, obj, "points", points);
+  napi_set_named_property(env, obj, "infinity", infinity);
+  return obj;
+}
+
 struct Job {
   napi_async_work work = nullptr;
   napi_deferred deferred = nullptr;
@@ -403,6 +450,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"setBasesSync", nullptr, SetBasesSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"fixedBaseMsmSync", nullptr, FixedBaseMsmSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"checkPointsSync", nullptr, CheckPointsSync, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"batchMulSync", nullptr, BatchMulSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"version", nullptr, Version, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
