@@ -509,6 +509,43 @@ int msm377_ctx_set_mul_window(msm377_ctx* ctx, int window_bits);
 int msm377_ctx_get_last_mul_window(const msm377_ctx* ctx);
 uint64_t msm377_ctx_get_mul_table_builds(const msm377_ctx* ctx);
 
+/* ---- variable-base batch multiplication --------------------------------------------------- */
+
+/* out[i] = [s_i]P_i: n scalar multiples of n points, each returned as its own affine point (an SRS or powers-of-tau
+ * update [tau^i]P_i, key specialisation [delta^-1]L_i, each half of an inner-product basis fold).  Wherever the two
+ * overlap the contract is that of msm377_g1_batch_mul* above -- the meaning of a scalar (every 32-byte value, a wire scalar
+ * NOT reduced mod r, no MSM377_ESCALAR, no rerun), the context's scalar form, the two output forms and out_inf, any n in
+ * passes over a fixed scratch, synchronous calls, MSM377_EINVAL with the outputs untouched -- and this section states only
+ * what differs (csrc/kernels/batch_mul_var.hpp).
+ *
+ * Points.  They follow the context's POINT form (msm377_ctx_set_input_format): MSM377_POINTS_WIRE, MSM377_POINTS_MONT or
+ * MSM377_POINTS_MONT_FLAG.  A flagged record is the identity: its coordinate bytes are never interpreted, its output is
+ * the identity with out_inf = 1.  Every curve point is a legal input, mixed freely within one array: orders 2, 3, 4 and
+ * 6, points outside the prime-order subgroup, P + T.  Coordinates of p or more are trusted not to occur, as in the MSM
+ * calls.
+ *
+ * Scalars.  scalar_stride is 32 (one scalar per point) or 0 (ONE scalar for all n points: 32 bytes are read); any other
+ * value is MSM377_EINVAL.
+ *
+ * Arguments.  Device pointers: scalars and 96-byte records 16-byte aligned, 104-byte records 8-byte aligned, inputs
+ * and outputs alike; a misaligned pointer is MSM377_EINVAL.  d_out_points == d_points is allowed when input and
+ * output records have the same size (wire to wire, mont_flag to mont_flag); ANY other overlap of an output with an input
+ * or with the other output is the caller's bug and the result is undefined.
+ *
+ * State.  The call walks n in passes of 2^17 points; per pass it builds the table [1..8]P_i of every point (128 MB of
+ * device memory beside the batch_mul scratch, allocated by the first call, freed by msm377_ctx_destroy, never valid
+ * between calls).  The resident MSM bases, the batch_mul window table (msm377_ctx_get_mul_table_builds does not move)
+ * and a check call's state are untouched by these calls, and the other way round.  msm377_g1_batch_mul_var stages host
+ * buffers through device memory in pieces of 2^20 points. */
+int msm377_g1_batch_mul_var_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t scalar_stride, uint32_t out_form, void* d_out_points,
+                                   uint8_t* d_out_inf);
+int msm377_g1_batch_mul_var(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint32_t scalar_stride, uint32_t out_form, uint8_t* out_points,
+                            uint8_t* out_inf);
+/* The same on ONE CPU thread: no device, no context (csrc/batch_mul_var_host.hpp): plain double-and-add, the yardstick of
+ * the device call.  The forms are arguments here. */
+int msm377_g1_batch_mul_var_host(const uint8_t* points, uint32_t point_form, const uint8_t* scalars, uint32_t scalar_form, uint64_t n, uint32_t scalar_stride,
+                                 uint32_t out_form, uint8_t* out_points, uint8_t* out_inf);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 
 #define MSM377_STAGE_CONVERT 0     /* points -> Montgomery records */

@@ -30,6 +30,7 @@ from .host.engine import (  # noqa: F401
     MsmEngine,
     MsmError,
     batch_mul_host,
+    batch_mul_var_host,
     check_points_host,
     ed_check_points_host,
     import_points_host,
@@ -50,6 +51,7 @@ __all__ = [
     "CheckReport",
     "StageInfo",
     "batch_mul_host",
+    "batch_mul_var_host",
     "check_points_host",
     "ed_check_points_host",
     "CHECK_CANONICAL",

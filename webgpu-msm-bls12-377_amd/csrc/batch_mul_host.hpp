@@ -17,6 +17,43 @@ namespace msm377 {
 
 constexpr int BM_HOST_WIDTH = 4;  // 64 windows of 8 entries + the carry's entry: a table of 513 points per call
 
+// The output-writing tail of both host twins (this one and batch_mul_var_host.hpp): Montgomery's trick over the XYZZ
+// results on the calling thread, then the records of out_form (MSM377_POINTS_WIRE or MSM377_POINTS_MONT_FLAG) and the
+// optional flag bytes.  An identity contributes 1 to the products.
+inline void batch_mul_write_outputs_host(const std::vector<G1H::XYZZ>& acc, uint32_t out_form, uint8_t* out_points, uint8_t* out_inf) {
+  const uint64_t n = acc.size();
+  std::vector<Fp64::El> prefix(n);
+  Fp64::El run = Fp64::one();
+  for (uint64_t i = 0; i < n; i++) {
+    prefix[i] = run;
+    if (!G1H::is_identity(acc[i])) run = Fp64::mul(run, acc[i].zzz);
+  }
+  Fp64::El inv = Fp64::inv(run);
+  for (uint64_t i = n; i-- > 0;) {
+    const G1H::XYZZ& a = acc[i];
+    const bool ident = G1H::is_identity(a);
+    Fp64::El x = Fp64::zero(), y = Fp64::one();
+    if (!ident) {
+      const Fp64::El zi = Fp64::mul(inv, prefix[i]);  // 1 / ZZZ_i
+      inv = Fp64::mul(inv, a.zzz);
+      const Fp64::El t = Fp64::mul(zi, a.zz);
+      x = Fp64::mul(a.x, Fp64::sqr(t));
+      y = Fp64::mul(a.y, zi);
+    }
+    if (out_form == MSM377_POINTS_WIRE) {
+      Fp64::to_wire(x, out_points + i * 96);
+      Fp64::to_wire(y, out_points + i * 96 + 48);
+    } else {  // the host's Montgomery radix 2^384 IS the callers'
+      uint8_t* rec = out_points + i * 104;
+      memcpy(rec, x.v, 48);
+      memcpy(rec + 48, y.v, 48);
+      memset(rec + 96, 0, 8);
+      rec[96] = ident ? 1 : 0;
+    }
+    if (out_inf) out_inf[i] = ident ? 1 : 0;
+  }
+}
+
 // scalar_form: MSM377_SCALARS_WIRE (32-byte integers, any value below 2^256, NOT reduced mod r: B may lie outside the
 // prime-order subgroup) or MSM377_SCALARS_MONT (v 2^-256 mod r, fully reduced, as the MSM calls read them).
 // out_form: MSM377_POINTS_WIRE (96-byte records, the identity as x = 0, y = 1) or MSM377_POINTS_MONT_FLAG (104-byte
@@ -46,8 +83,6 @@ inline int batch_mul_host(const uint8_t base_xy[96], const uint8_t* scalars, uin
   }
 
   std::vector<G1H::XYZZ> acc(n);
-  std::vector<Fp64::El> prefix(n);
-  Fp64::El run = Fp64::one();
   for (uint64_t i = 0; i < n; i++) {
     uint8_t wire[32];
     import_scalars_host(scalars + i * 32, 1, scalar_form, wire);
@@ -62,33 +97,8 @@ inline int batch_mul_host(const uint8_t base_xy[96], const uint8_t* scalars, uin
       a = G1H::add(a, d < 0 ? G1H::neg(e) : e);  // identity, equal and opposite operands handled inside
     }
     acc[i] = a;
-    prefix[i] = run;
-    if (!G1H::is_identity(a)) run = Fp64::mul(run, a.zzz);  // an identity contributes 1
   }
-  Fp64::El inv = Fp64::inv(run);
-  for (uint64_t i = n; i-- > 0;) {
-    const G1H::XYZZ& a = acc[i];
-    const bool ident = G1H::is_identity(a);
-    Fp64::El x = Fp64::zero(), y = Fp64::one();
-    if (!ident) {
-      const Fp64::El zi = Fp64::mul(inv, prefix[i]);  // 1 / ZZZ_i
-      inv = Fp64::mul(inv, a.zzz);
-      const Fp64::El t = Fp64::mul(zi, a.zz);
-      x = Fp64::mul(a.x, Fp64::sqr(t));
-      y = Fp64::mul(a.y, zi);
-    }
-    if (out_form == MSM377_POINTS_WIRE) {
-      Fp64::to_wire(x, out_points + i * 96);
-      Fp64::to_wire(y, out_points + i * 96 + 48);
-    } else {  // the host's Montgomery radix 2^384 IS the callers'
-      uint8_t* rec = out_points + i * 104;
-      memcpy(rec, x.v, 48);
-      memcpy(rec + 48, y.v, 48);
-      memset(rec + 96, 0, 8);
-      rec[96] = ident ? 1 : 0;
-    }
-    if (out_inf) out_inf[i] = ident ? 1 : 0;
-  }
+  batch_mul_write_outputs_host(acc, out_form, out_points, out_inf);
   return MSM377_OK;
 }
 

@@ -12,6 +12,7 @@
 #include "host_tail.hpp"
 #include "sequencer.hpp"
 #include "batch_mul_host.hpp"
+#include "batch_mul_var_host.hpp"
 #include "import_host.hpp"
 #include "validate_host.hpp"
 
@@ -163,7 +164,7 @@ void msm377_ctx_destroy(msm377_ctx* ctx) {
   }
   void* bufs[] = {ctx->d_raw_points, ctx->d_raw_scalars, ctx->d_bases, ctx->d_digits, ctx->d_range_counts, ctx->d_region_base, ctx->d_sort_temp,
                   ctx->d_row_ptr, ctx->d_val_idx, ctx->d_buckets, ctx->d_buckets_snap, ctx->d_partials, ctx->d_work, ctx->d_work_meta, ctx->d_row_ovf_base, ctx->d_split_rows, ctx->d_ovf, ctx->d_err, ctx->d_aff_stash, ctx->d_aff_trees, ctx->d_aff_count, ctx->d_out_count, ctx->resident.table, ctx->d_native, ctx->d_inf_mask,
-                  ctx->bm.table, ctx->bm.stash, ctx->bm.trees, ctx->bm.block_prod, ctx->bm.block_inv, ctx->bm.row_bases, ctx->bm.base_wire};
+                  ctx->bm.table, ctx->bm.stash, ctx->bm.trees, ctx->bm.block_prod, ctx->bm.block_inv, ctx->bm.row_bases, ctx->bm.base_wire, ctx->bm.var_table};
   for (void* p : bufs)
     if (p) (void)hipFree(p);
   ctx->wide.release();
@@ -428,6 +429,11 @@ int msm377_g1_batch_mul_host(const uint8_t base_xy[96], const uint8_t* scalars, 
   return batch_mul_host(base_xy, scalars, n, MSM377_SCALARS_WIRE, out_form, out_points, out_inf);
 }
 
+int msm377_g1_batch_mul_var_host(const uint8_t* points, uint32_t point_form, const uint8_t* scalars, uint32_t scalar_form, uint64_t n, uint32_t scalar_stride, uint32_t out_form,
+                                 uint8_t* out_points, uint8_t* out_inf) {
+  return batch_mul_var_host(points, point_form, scalars, scalar_form, n, scalar_stride, out_form, out_points, out_inf);
+}
+
 int msm377_ctx_set_mul_window(msm377_ctx* ctx, int window_bits) {
   if (!ctx || (window_bits != 0 && !batch_mul_width_supported(window_bits))) return MSM377_EINVAL;
   ctx->bm.window = window_bits;
@@ -535,6 +541,12 @@ int msm377_g1_glv_window_partials_device(msm377_ctx* ctx, const void* d_points, 
 int msm377_g1_generate_bases_device(msm377_ctx* ctx, uint64_t seed, uint64_t n, void* d_points_out) { return eng::g1_generate_bases_device(ctx, seed, n, d_points_out); }
 int msm377_g1_batch_mul_device(msm377_ctx* ctx, const uint8_t base_xy[96], const void* d_scalars, uint64_t n, uint32_t out_form, void* d_out_points, uint8_t* d_out_inf) { return eng::g1_batch_mul_device(ctx, base_xy, d_scalars, n, out_form, d_out_points, d_out_inf); }
 int msm377_g1_batch_mul(msm377_ctx* ctx, const uint8_t base_xy[96], const uint8_t* scalars, uint64_t n, uint32_t out_form, uint8_t* out_points, uint8_t* out_inf) { return eng::g1_batch_mul(ctx, base_xy, scalars, n, out_form, out_points, out_inf); }
+int msm377_g1_batch_mul_var_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t scalar_stride, uint32_t out_form, void* d_out_points, uint8_t* d_out_inf) {
+  return eng::g1_batch_mul_var_device(ctx, d_points, d_scalars, n, scalar_stride, out_form, d_out_points, d_out_inf);
+}
+int msm377_g1_batch_mul_var(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint32_t scalar_stride, uint32_t out_form, uint8_t* out_points, uint8_t* out_inf) {
+  return eng::g1_batch_mul_var(ctx, points, scalars, n, scalar_stride, out_form, out_points, out_inf);
+}
 int msm377_g1_check_points_device(msm377_ctx* ctx, const void* d_points, uint64_t n, uint32_t flags, msm377_check_report* out) { return eng::g1_check_points_device(ctx, d_points, n, flags, out); }
 int msm377_g1_check_points(msm377_ctx* ctx, const uint8_t* points, uint64_t n, uint32_t flags, msm377_check_report* out) { return eng::g1_check_points(ctx, points, n, flags, out); }
 int msm377_ed_check_points_device(msm377_ctx* ctx, const void* d_points, uint64_t n, uint32_t flags, msm377_check_report* out) { return ed_wire_only(ctx) ? MSM377_EINVAL : eng::ed_check_points_device(ctx, d_points, n, flags, out); }

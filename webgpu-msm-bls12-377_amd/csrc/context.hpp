@@ -60,6 +60,9 @@ struct BatchMulState {
   uint32_t* block_inv = nullptr;
   uint32_t* row_bases = nullptr;    // (W + 1) table records: [2^(c w)]B
   uint32_t* base_wire = nullptr;    // the base's 96 bytes on the device
+  // Variable-base calls (msm377_g1_batch_mul_var*, kernels/batch_mul_var.hpp): the per-point tables of ONE pass, [1..8]P_i
+  // as 128-byte records (128 MB), rebuilt by every pass and never valid between calls.  They share the scratch above.
+  uint32_t* var_table = nullptr;
 };
 
 // Work buffers of the 20-bit-window sort (kernels/wide.hpp) for up to `cap` points.

@@ -47,6 +47,7 @@
 #include "kernels/sort.hpp"
 #include "kernels/validate.hpp"
 #include "kernels/import.hpp"
+#include "kernels/batch_mul_var.hpp"
 #include "kernels/wide.hpp"
 
 bool WideBuffers::ensure(uint64_t n) {
@@ -2201,6 +2202,103 @@ int g1_batch_mul(msm377_ctx* ctx, const uint8_t base_xy[96], const uint8_t* scal
     if (!rc && out_inf) rc = hip_ok(ctx, hipMemcpy(out_inf + off, d_io + off_inf, m, hipMemcpyDeviceToHost), "hipMemcpy(flags)") ? MSM377_OK : MSM377_EHIP;
   }
   ctx->bm.window = forced;
+  (void)hipFree(d_io);
+  return rc;
+}
+
+// ---- variable-base batch multiplication (include/msm377.h "variable-base batch multiplication"; kernels/batch_mul_var.hpp) ----
+// Per pass of BMV_PASS points: the per-point tables through the stash and the normalisation, then the walk and the
+// normalisation again, all on ctx->stream; the one host wait is the synchronisation at the end of the call.  A pass reads
+// its points before it writes its outputs, and passes cover disjoint index ranges: d_out_points == d_points is safe for
+// records of equal size.
+namespace {
+
+size_t bmv_point_stride(uint32_t form) { return form == MSM377_POINTS_MONT_FLAG ? 104 : 96; }
+
+int bmv_check_args(msm377_ctx* ctx, uint32_t scalar_stride, uint32_t out_form) {
+  const int rc = bm_check_form(ctx, out_form);
+  if (rc) return rc;
+  if (scalar_stride != 0 && scalar_stride != 32) {
+    ctx->err = "scalar_stride is 32 (a scalar per point) or 0 (one scalar for all points)";
+    return MSM377_EINVAL;
+  }
+  return MSM377_OK;
+}
+
+}  // namespace
+
+int g1_batch_mul_var_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t scalar_stride, uint32_t out_form, void* d_out_points,
+                            uint8_t* d_out_inf) {
+  int rc = bmv_check_args(ctx, scalar_stride, out_form);
+  if (rc) return rc;
+  if (n == 0) return MSM377_OK;
+  if (!d_points || !d_scalars || !d_out_points) {
+    ctx->err = "null pointer";
+    return MSM377_EINVAL;
+  }
+  const uint32_t form = ctx->point_form;
+  const size_t in_stride = bmv_point_stride(form), out_stride = bmv_point_stride(out_form);
+  if (((uintptr_t)d_scalars & 15) || ((uintptr_t)d_points & (in_stride == 96 ? 15 : 7)) || ((uintptr_t)d_out_points & (out_stride == 96 ? 15 : 7))) {
+    ctx->err = "device pointers must be 16-byte aligned (8-byte for mont_flag records)";
+    return MSM377_EINVAL;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  rc = bm_ensure_scratch(ctx);
+  if (!rc) rc = bm_alloc(ctx, &ctx->bm.var_table, (size_t)BM_CHUNK * BM_REC_WORDS * 4);
+  if (rc) return rc;
+  uint4* stash = reinterpret_cast<uint4*>(ctx->bm.stash);
+  const uint32_t* table = ctx->bm.var_table;
+  const uint32_t stride_words = scalar_stride / 4, scalars_mont = ctx->scalar_form == MSM377_SCALARS_MONT ? 1u : 0u;
+  for (uint64_t off = 0; off < n && !rc; off += BMV_PASS) {
+    const uint64_t m = std::min<uint64_t>(BMV_PASS, n - off);
+    const dim3 grid((unsigned)((m + BM_THREADS - 1) / BM_THREADS)), block(BM_THREADS);
+    const uint8_t* pts = (const uint8_t*)d_points + off * in_stride;
+    if (form == MSM377_POINTS_WIRE)
+      hipLaunchKernelGGL(k_bmv_table<MSM377_POINTS_WIRE>, grid, block, 0, ctx->stream, pts, m, stash);
+    else if (form == MSM377_POINTS_MONT)
+      hipLaunchKernelGGL(k_bmv_table<MSM377_POINTS_MONT>, grid, block, 0, ctx->stream, pts, m, stash);
+    else
+      hipLaunchKernelGGL(k_bmv_table<MSM377_POINTS_MONT_FLAG>, grid, block, 0, ctx->stream, pts, m, stash);
+    rc = bm_normalise(ctx, m * BMV_ENTRIES, BM_FORM_TABLE, ctx->bm.var_table, nullptr);
+    if (rc) break;
+    hipLaunchKernelGGL(k_bmv_accumulate, grid, block, 0, ctx->stream, table, (const uint32_t*)d_scalars + off * stride_words, m, stride_words, scalars_mont, stash);
+    rc = bm_normalise(ctx, m, out_form, (uint8_t*)d_out_points + off * out_stride, d_out_inf ? d_out_inf + off : nullptr);
+  }
+  const hipError_t e = hipStreamSynchronize(ctx->stream);
+  if (rc) return rc;
+  HIP_TRY(ctx, e);
+  return MSM377_OK;
+}
+
+// Host buffers: points and scalars up, records (and flags) down, a chunk's worth of device staging for the length of the call.
+int g1_batch_mul_var(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint32_t scalar_stride, uint32_t out_form, uint8_t* out_points, uint8_t* out_inf) {
+  int rc = bmv_check_args(ctx, scalar_stride, out_form);
+  if (rc) return rc;
+  if (n == 0) return MSM377_OK;
+  if (!points || !scalars || !out_points) {
+    ctx->err = "null pointer";
+    return MSM377_EINVAL;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t in_stride = bmv_point_stride(ctx->point_form), out_stride = bmv_point_stride(out_form);
+  const uint64_t piece = std::min<uint64_t>(n, BM_CHUNK);
+  const auto round16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  uint8_t* d_io = nullptr;  // scalars, points, records, flags: 16-byte aligned parts
+  const size_t off_pts = (size_t)piece * 32, off_out = off_pts + round16((size_t)piece * in_stride), off_inf = off_out + round16((size_t)piece * out_stride);
+  if (hipMalloc((void**)&d_io, off_inf + piece) != hipSuccess) {
+    (void)hipGetLastError();
+    ctx->err = "out of device memory for the batch multiplication staging";
+    return MSM377_ENOMEM;
+  }
+  if (scalar_stride == 0) rc = hip_ok(ctx, hipMemcpy(d_io, scalars, 32, hipMemcpyHostToDevice), "hipMemcpy(scalar)") ? MSM377_OK : MSM377_EHIP;
+  for (uint64_t off = 0; off < n && !rc; off += piece) {
+    const uint64_t m = std::min<uint64_t>(piece, n - off);
+    if (scalar_stride) rc = hip_ok(ctx, hipMemcpy(d_io, scalars + off * 32, m * 32, hipMemcpyHostToDevice), "hipMemcpy(scalars)") ? MSM377_OK : MSM377_EHIP;
+    if (!rc) rc = hip_ok(ctx, hipMemcpy(d_io + off_pts, points + off * in_stride, m * in_stride, hipMemcpyHostToDevice), "hipMemcpy(points)") ? MSM377_OK : MSM377_EHIP;
+    if (!rc) rc = g1_batch_mul_var_device(ctx, d_io + off_pts, d_io, m, scalar_stride, out_form, d_io + off_out, d_io + off_inf);
+    if (!rc) rc = hip_ok(ctx, hipMemcpy(out_points + off * out_stride, d_io + off_out, m * out_stride, hipMemcpyDeviceToHost), "hipMemcpy(records)") ? MSM377_OK : MSM377_EHIP;
+    if (!rc && out_inf) rc = hip_ok(ctx, hipMemcpy(out_inf + off, d_io + off_inf, m, hipMemcpyDeviceToHost), "hipMemcpy(flags)") ? MSM377_OK : MSM377_EHIP;
+  }
   (void)hipFree(d_io);
   return rc;
 }

@@ -217,6 +217,9 @@ def load_library():
         "msm377_g1_batch_mul_device": (i32, [vp, u8p, vp, u64, u32, vp, vp]),
         "msm377_g1_batch_mul": (i32, [vp, u8p, u8p, u64, u32, vp, vp]),
         "msm377_g1_batch_mul_host": (i32, [u8p, u8p, u64, u32, vp, vp]),
+        "msm377_g1_batch_mul_var_device": (i32, [vp, vp, vp, u64, u32, u32, vp, vp]),
+        "msm377_g1_batch_mul_var": (i32, [vp, u8p, u8p, u64, u32, u32, vp, vp]),
+        "msm377_g1_batch_mul_var_host": (i32, [u8p, u32, u8p, u32, u64, u32, u32, vp, vp]),
         "msm377_ctx_set_mul_window": (i32, [vp, i32]),
         "msm377_ctx_get_last_mul_window": (i32, [vp]),
         "msm377_ctx_get_mul_table_builds": (u64, [vp]),
@@ -343,6 +346,36 @@ def batch_mul_host(base: bytes, scalars: bytes, out_form="wire") -> Tuple[bytes,
     rc = load_library().msm377_g1_batch_mul_host(bytes(base), bytes(scalars), n, f, ctypes.addressof(out), ctypes.addressof(inf))
     if rc:
         raise MsmError(rc, "msm377_g1_batch_mul_host")
+    return out.raw[: stride * n], inf.raw[:n]
+
+
+def _var_scalar_stride(scalars: bytes, n: int) -> int:
+    """32 (a scalar per point), or 0 when ONE 32-byte scalar stands for all n > 1 points."""
+    if len(scalars) == 32 and n > 1:
+        return 0
+    if len(scalars) != 32 * n:
+        raise ValueError("scalars: 32 bytes per point, or 32 bytes for all points")
+    return 32
+
+
+def batch_mul_var_host(points: bytes, scalars: bytes, out_form="wire", point_form="wire", scalar_form="wire") -> Tuple[bytes, bytes]:
+    """out[i] = [s_i]P_i on the calling thread (msm377_g1_batch_mul_var_host): no context, no device.  ``points``:
+    records of ``point_form``; ``scalars``: 32 bytes per point, or 32 bytes for all of them.  Returns (records, identity
+    flags) as batch_mul_host does."""
+    pf = _form(_POINT_FORMS, point_form, "point")
+    in_stride = _POINT_STRIDE.get(pf, 96)
+    if len(points) % in_stride:
+        raise ValueError("points buffer length must be a multiple of %d" % in_stride)
+    n = len(points) // in_stride
+    f = _batch_mul_out_form(out_form)
+    stride = _POINT_STRIDE.get(f, 96)
+    out = ctypes.create_string_buffer(max(1, stride * n))
+    inf = ctypes.create_string_buffer(max(1, n))
+    rc = load_library().msm377_g1_batch_mul_var_host(
+        bytes(points), pf, bytes(scalars), _form(_SCALAR_FORMS, scalar_form, "scalar"), n, _var_scalar_stride(scalars, n), f, ctypes.addressof(out), ctypes.addressof(inf)
+    )
+    if rc:
+        raise MsmError(rc, "msm377_g1_batch_mul_var_host")
     return out.raw[: stride * n], inf.raw[:n]
 
 
@@ -657,6 +690,27 @@ class MsmEngine:
         inf = ctypes.create_string_buffer(max(1, n))
         rc = self._lib.msm377_g1_batch_mul(self._ctx, bytes(base), bytes(scalars), n, f, ctypes.addressof(out), ctypes.addressof(inf))
         self._check(rc, "msm377_g1_batch_mul")
+        return out.raw[: stride * n], inf.raw[:n]
+
+    # -- variable-base batch multiplication (include/msm377.h): out[i] = [s_i]P_i --
+    def batch_mul_var_device(self, d_points: int, d_scalars: int, n: int, d_out: int, d_inf: int = 0, out_form="wire", scalar_stride: int = 32):
+        """n points and n scalars in HBM (in the engine's point and scalar forms; ``scalar_stride`` 0: one scalar for all
+        points): n records at ``d_out`` and, if ``d_inf`` is given, n identity flag bytes there
+        (msm377_g1_batch_mul_var_device).  Any n; every curve point is a legal input; ``d_out`` may be ``d_points`` when
+        the records have the same size."""
+        rc = self._lib.msm377_g1_batch_mul_var_device(self._ctx, d_points or None, d_scalars or None, int(n), int(scalar_stride), _batch_mul_out_form(out_form), d_out or None, d_inf or None)
+        self._check(rc, "msm377_g1_batch_mul_var_device")
+
+    def batch_mul_var(self, points: bytes, scalars: bytes, out_form="wire") -> Tuple[bytes, bytes]:
+        """The same on host buffers: returns (records, identity flags).  A 32-byte ``scalars`` with more than one point
+        is the one scalar of all points (msm377_g1_batch_mul_var)."""
+        n = self._count_points(points)
+        f = _batch_mul_out_form(out_form)
+        stride = _POINT_STRIDE.get(f, 96)
+        out = ctypes.create_string_buffer(max(1, stride * n))
+        inf = ctypes.create_string_buffer(max(1, n))
+        rc = self._lib.msm377_g1_batch_mul_var(self._ctx, bytes(points), bytes(scalars), n, _var_scalar_stride(scalars, n), f, ctypes.addressof(out), ctypes.addressof(inf))
+        self._check(rc, "msm377_g1_batch_mul_var")
         return out.raw[: stride * n], inf.raw[:n]
 
     def set_mul_window(self, bits: int = 0):

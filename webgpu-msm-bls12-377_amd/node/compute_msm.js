@@ -120,4 +120,12 @@ const batch_mul = (base, scalars, { outForm = 'wire' } = {}) => {
   return addon.batchMulSync(baseBuf, scalarsToBuffer(scalars), BATCH_MUL_FORMS[outForm]);
 };
 
-module.exports = { batch_mul, compute_msm, compute_msm_edwards, set_bases, compute_msm_fixed_base, check_points, CHECK_CANONICAL, CHECK_CURVE, CHECK_SUBGROUP, CHECK_ALL, pointsToBuffer, scalarsToBuffer, version: addon.version };
+// Variable-base batch multiplication (msm377_g1_batch_mul_var): out[i] = [s_i]P_i, every output its own point.  `points`: {x, y}
+// points or a Buffer of 96-byte wire records; `scalars`: one per point, or ONE scalar (a 32-byte Buffer, a one-element array)
+// for all points.  Returns {points, infinity} as batch_mul does.  Any curve point is a legal input.
+const batch_mul_var = (points, scalars, { outForm = 'wire' } = {}) => {
+  if (!(outForm in BATCH_MUL_FORMS)) throw new RangeError("outForm: wire | mont_flag (plain mont cannot say 'identity')");
+  return addon.batchMulVarSync(pointsToBuffer(points), scalarsToBuffer(scalars), BATCH_MUL_FORMS[outForm]);
+};
+
+module.exports = { batch_mul, batch_mul_var, compute_msm, compute_msm_edwards, set_bases, compute_msm_fixed_base, check_points, CHECK_CANONICAL, CHECK_CURVE, CHECK_SUBGROUP, CHECK_ALL, pointsToBuffer, scalarsToBuffer, version: addon.version };

@@ -192,3 +192,16 @@ export const batch_mul = (
   const baseBuf = Buffer.isBuffer(base) ? base : pointsToBuffer([base] as BigIntPoint[] | U32ArrayPoint[]);
   return addon.batchMulSync(baseBuf, scalarsToBuffer(scalars), BATCH_MUL_FORMS[outForm]);
 };
+
+// Variable-base batch multiplication (msm377_g1_batch_mul_var): out[i] = [s_i]P_i, every output its own point.  `scalars`: one
+// per point, or ONE scalar (a 32-byte Buffer, a one-element array) for all points.  Returns what batch_mul returns.
+export const batch_mul_var = (
+  points: BigIntPoint[] | U32ArrayPoint[] | Buffer,
+  scalars: bigint[] | Uint32Array[] | Buffer,
+  { outForm = 'wire' }: { outForm?: keyof typeof BATCH_MUL_FORMS } = {},
+): { points: Buffer; infinity: Buffer } => {
+  if (!(outForm in BATCH_MUL_FORMS)) {
+    throw new RangeError("outForm: wire | mont_flag (plain mont cannot say 'identity')");
+  }
+  return addon.batchMulVarSync(pointsToBuffer(points), scalarsToBuffer(scalars), BATCH_MUL_FORMS[outForm]);
+};

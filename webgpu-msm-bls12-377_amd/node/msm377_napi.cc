@@ -18,6 +18,9 @@
 //   batchMulSync(base: Buffer 96, scalars: Buffer 32n, outForm: number): {points: Buffer, infinity: Buffer}
 //                                                                      out[i] = [s_i]B (msm377_g1_batch_mul): 96-byte wire or
 //                                                                      104-byte mont_flag records, one identity byte per output
+//   batchMulVarSync(points: Buffer 96n, scalars: Buffer 32n | 32, outForm: number): {points: Buffer, infinity: Buffer}
+//                                                                      out[i] = [s_i]P_i (msm377_g1_batch_mul_var); 32 bytes of
+//                                                                      scalars for n > 1 points: one scalar for all
 //   version(): string
 // Errors reject / throw a JS Error carrying msm377_strerror + msm377_last_error, matching the
 // reference's behaviour of throwing Error (cuzk/gpu.ts:7-10).
@@ -378,6 +381,52 @@ napi_value BatchMulSync(napi_env env, napi_callback_info info) {
   return obj;
 }
 
+// batchMulVarSync(points, scalars, outForm) -> {points, infinity}: out[i] = [s_i]P_i on wire points; 32 bytes of scalars
+// for more than one point are the ONE scalar of all points (scalar_stride 0)
+napi_value BatchMulVarSync(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  bool pb = false, sb = false;
+  uint32_t form = MSM377_POINTS_WIRE;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 3 || napi_is_buffer(env, argv[0], &pb) != napi_ok || !pb ||
+      napi_is_buffer(env, argv[1], &sb) != napi_ok || !sb || napi_get_value_uint32(env, argv[2], &form) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "expected (points: Buffer of 96 bytes per point, scalars: Buffer of 32 bytes per scalar, outForm: number)");
+    return nullptr;
+  }
+  uint8_t *p, *s;
+  size_t pl, sl;
+  napi_get_buffer_info(env, argv[0], reinterpret_cast<void**>(&p), &pl);
+  napi_get_buffer_info(env, argv[1], reinterpret_cast<void**>(&s), &sl);
+  const uint64_t n = pl / 96;
+  const uint32_t scalar_stride = (sl == 32 && n > 1) ? 0 : 32;
+  if (pl % 96 != 0 || (scalar_stride && sl != n * 32) || (form != MSM377_POINTS_WIRE && form != MSM377_POINTS_MONT_FLAG)) {
+    napi_throw_range_error(env, nullptr, "points must hold 96 bytes each, scalars 32 bytes per point (or 32 bytes for all); outForm is 0 (wire) or 2 (mont_flag)");
+    return nullptr;
+  }
+  const size_t stride = form == MSM377_POINTS_MONT_FLAG ? 104 : 96;
+  napi_value points, infinity, obj;
+  void *pd = nullptr, *id = nullptr;
+  if (napi_create_buffer(env, n * stride, &pd, &points) != napi_ok || napi_create_buffer(env, n, &id, &infinity) != napi_ok) return nullptr;
+  std::string err;
+  int rc;
+  {
+    std::lock_guard<std::mutex> lock(g_mu);
+    rc = ensure_ctx(1, &err);  // any capacity: the call walks n in passes of its own
+    if (!rc) {
+      rc = msm377_g1_batch_mul_var(g_ctx, p, s, n, scalar_stride, form, static_cast<uint8_t*>(pd), static_cast<uint8_t*>(id));
+      if (rc) err = std::string("msm377_g1_batch_mul_var: ") + msm377_strerror(rc) + ": " + msm377_last_error(g_ctx);
+    }
+  }
+  if (rc) {
+    napi_throw_error(env, nullptr, err.c_str());
+    return nullptr;
+  }
+  napi_create_object(env, &obj);
+  napi_set_named_property(env, obj, "points", points);
+  napi_set_named_property(env, obj, "infinity", infinity);
+  return obj;
+}
+
 struct Job {
   napi_async_work work = nullptr;
   napi_deferred deferred = nullptr;
@@ -451,6 +500,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"fixedBaseMsmSync", nullptr, FixedBaseMsmSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"checkPointsSync", nullptr, CheckPointsSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"batchMulSync", nullptr, BatchMulSync, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"batchMulVarSync", nullptr, BatchMulVarSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"version", nullptr, Version, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
