@@ -341,7 +341,54 @@ def test_window_partials_with_an_exceptional_pair_in_one_rank(aff, oracle, pool)
     assert msm.combine_partials(r0 + r1) == R.encode_result(exp) == aff.combine_partials(r0 + r1)
 
 
-# ---- h. full size on the session engine, default knobs ----
+# ---- h. short scalars on per-call affine records ----
+SHORT_N, SHORT_BITS = 2049, 64  # two workgroups of the conversion; 64-bit scalars in 8 bytes
+
+
+@pytest.fixture(scope="module")
+def short_case(oracle, pool):
+    pts = pool[: 96 * SHORT_N]
+    kl = [k & ((1 << SHORT_BITS) - 1) for k in R.rand_scalars(0x5409, SHORT_N)]
+    kl[0], kl[SHORT_N - 1] = (1 << SHORT_BITS) - 1, 1 << (SHORT_BITS - 1)
+    kl[AFF_BLOCK_POINTS] |= 1  # (an odd multiple of a two-torsion point is the point itself)
+    return pts, kl, util.oracle_msm(oracle, pts, R.encode_scalars(kl))
+
+
+@pytest.mark.parametrize("geometry, log", [("narrow", 11), ("main", 15)])
+def test_short_scalars_on_affine_records(aff, short_case, geometry, log):
+    """msm_short_device (the conversion's way up now, the rest from the hook) and msm_short (host buffers: both phases
+    back to back from the hook) on affine records, on 2^11 and on 2^15 buckets: the oracle's sum, the 7-product kernel,
+    the short geometry, no rerun."""
+    pts, kl, exp = short_case
+    ks = msm.encode_scalars(kl, 8)
+    d_p, d_s = dev(pts), dev(ks)
+    aff.set_narrow_max(1 << 16 if geometry == "narrow" else 0)
+    try:
+        for call in (lambda: aff.msm_short_device(d_p.data_ptr(), d_s.data_ptr(), SHORT_N, 8, SHORT_BITS), lambda: aff.msm_short(pts, ks, 8, SHORT_BITS)):
+            with util.edwards_only(aff, products=7):
+                assert call() == exp, geometry
+            assert aff.accumulate_products() == 7
+            assert aff.last_geometry() == (msm.short_windows(SHORT_BITS, log), log), geometry
+    finally:
+        aff.set_narrow_max()
+
+
+def test_short_host_call_with_a_two_torsion_point(aff, short_case):
+    """(-1, 0) among the points of a short host-buffer call: the conversion inside the hook flags it, the call reruns
+    exactly once on the Weierstrass path (W windows of 2^15 buckets) and answers pyref's sum."""
+    pts, kl, exp = short_case
+    i = AFF_BLOCK_POINTS  # the one point of the second workgroup
+    bad = bytearray(pts)
+    bad[96 * i : 96 * i + 96] = R.encode_points([T2])
+    want = R.encode_result(replaced(R.decode_result(exp), R.decode_points(pts), kl, i, pt=T2))
+    before, _ = aff.fallback_info()
+    assert aff.msm_short(bytes(bad), msm.encode_scalars(kl, 8), 8, SHORT_BITS) == want
+    count, mask = aff.fallback_info()
+    assert count == before + 1 and mask & FB_CONVERT, (count - before, mask)
+    assert aff.last_geometry() == (msm.short_windows(SHORT_BITS, 15), 15)
+
+
+# ---- i. full size on the session engine, default knobs ----
 A0, D = 0x1234567890ABCDEF1234567890ABCDEF, 0xFEDCBA0987654321FEDCBA
 N_FULL = 1 << 20
 

@@ -18,11 +18,6 @@
 
 using namespace msm377;
 
-#define HIP_TRY(ctx, call)                                                  \
-  do {                                                                      \
-    if (!eng::hip_ok((ctx), (int)(call), #call)) return MSM377_EHIP;        \
-  } while (0)
-
 // --------------------------------------------------------------------------- C ABI ----
 
 extern "C" {
@@ -191,19 +186,6 @@ void msm377_ctx_destroy(msm377_ctx* ctx) {
 }
 
 const char* msm377_last_error(const msm377_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
-
-
-
-
-
-
-
-
-
-
-
-
-
 
 int msm377_g1_window_partials_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t win_begin,
                                      uint32_t win_count, uint8_t* partials_out) {

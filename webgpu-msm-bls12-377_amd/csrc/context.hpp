@@ -222,7 +222,6 @@ struct msm377_ctx {
   // A/B at 2^20, 15 pairs (profiles/sort_elem4/ab_sort_elem.txt): sort stage 0.264 -> 0.249 ms, k_accumulate starts 12-17 us
   // sooner, whole MSM 2.477 -> 2.469 ms (medians) with run-to-run spreads of 0.06 and 0.09: inside the noise, so 8 stays the default.
   uint32_t sort_elem = 8;
-  bool ed_equal_windows_once = false;  // ed_msm -> ed_msm_device: this call reruns a chunked upload whose scalars did not fit
   uint32_t acc_seq = 0;  // calls' accumulation kernels so far; h_out_flag[ACC_FLAG_WORD] follows it (k_merge_split_rows_quad)
   msm377_ctx* twin = nullptr;   // owned; borrows `resident` for the length of a batch call
   bool twin_batches = true;     // MSM377_TWIN_BATCH=0: batches run on this context alone

@@ -22,6 +22,13 @@
 // stage read-backs) and EdDev (Edwards-BLS12 over the scalar field, ed_ext.hpp).  Everything behind the sort takes the
 // bucket geometry as a run-time argument L (2^L buckets per window: 15 on the main path, 11 on the narrow one).
 // HBM layout: DESIGN.md section 3.
+//
+// Host control flow, top to bottom in this file: a WindowPlan says which windows one attempt of a call runs and how the
+// host combines their records (one constructor per geometry); enqueue_windows queues the stages of a Phase for its plan;
+// wait_windows / geometry_refused / collect_windows / run_tail are the steps behind it.  g1_table_msm strings them
+// together for every G1 MSM on base records that are in place, at full width or over short scalars, and the entry
+// points are thin wrappers over one flow per kind of input (g1_device_flow, g1_host_flow, g1_fixed_base_flow,
+// ed_device_flow); the chunked uploads, the batches and the window shards keep schedules of their own over the same steps.
 #include "sequencer.hpp"
 
 #include <hip/hip_runtime.h>
@@ -80,10 +87,6 @@ void note_fallback(msm377_ctx* ctx, uint32_t mask) {
   ctx->fallback_count++;
   ctx->fallback_mask = mask;
 }
-#define HIP_TRY(ctx, call)                            \
-  do {                                                \
-    if (!msm377::eng::hip_ok((ctx), (int)(call), #call)) return MSM377_EHIP; \
-  } while (0)
 
 // Pageable host memory -> device through a pinned staging buffer: four workers copy ~4 MB pieces
 // into it and queue the DMA of each piece on their own stream, so the CPU copy of one piece
@@ -220,7 +223,7 @@ int affine_convert_begin(msm377_ctx* ctx, const uint32_t* d_raw, uint64_t n, con
 
 // Phase 2: waits for phase 1 (the main stream keeps the GPU busy meanwhile), inverts the block products on the tail
 // threads, queues the way down and signals `bases_ready`.
-int affine_convert_finish(msm377_ctx* ctx, uint32_t* d_records_out, uint64_t n, bool behind_sort = false) {
+int affine_convert_finish(msm377_ctx* ctx, uint32_t* d_records_out, uint64_t n) {
   if (n == 0) return MSM377_OK;
   const uint32_t nblk = affine_blocks(n);
   // Poll the flag in pinned memory (no runtime calls: they would contend with nothing, but they are not free either);
@@ -266,7 +269,105 @@ uint32_t auto_seg(const msm377_ctx* ctx, uint64_t entries, bool glv) {
 }
 
 
-// Which stages of a call to enqueue (all of them, except for the chunked host-buffer entry point).
+// The windows of ONE attempt of a call: what the kernels run (enqueue_windows reads the first half) and what the host
+// tail combines afterwards (run_tail reads the second), written once, by the constructor of the geometry.  The recode
+// families carry the names of tests/stage_model.py.
+enum Recode { RECODE_EQUAL16, RECODE_EVEN16, RECODE_NARROW22, RECODE_SHORT, RECODE_WIDE13, RECODE_GLV8 };
+enum TailKind { TE_TAIL, XYZZ_TAIL, ED_TAIL };  // te_tail / xyzz_tail / ed_tail, or (on_caller) teh_combine / g1h_combine
+struct WindowPlan {
+  Recode recode = RECODE_EQUAL16;
+  uint32_t slots = MSM377_NUM_WINDOWS;           // window slots the call runs (GLV: over twice the columns; wide: one, fed 13 digits per point)
+  uint32_t bucket_log = MSM377_WINDOW_BITS - 1;  // L: 2^L buckets per slot; everything behind the sort takes it as a run-time argument
+  // Precomputed-window tables (msm377_g1_set_bases_precomputed): window slot ws gathers from record ws * table_stride + i
+  // of `table`, and because the table already carries the windows' weights the bucket sets are ADDED together before
+  // the reduction: one window's reduction, one window's partial record.
+  const uint32_t* table = nullptr;
+  uint64_t table_stride = 0;
+  const uint32_t* bases_override = nullptr;  // base records of the call if not ctx->d_bases (the wide table's window 0 = the plain affine records)
+  // Short scalars (RECODE_SHORT): d_scalars holds n x short_bytes bytes, every scalar below 2^short_bits.
+  uint32_t short_bytes = 0, short_bits = 0;
+  // The host tail: `records` window records of cbits()-bit digits, from window short_from on one bit narrower.
+  TailKind tail = TE_TAIL;
+  bool on_caller = false;  // combined on the calling thread: one folded record, the GLV windows, the MSMs of a batch beside the GPU
+  int records = MSM377_NUM_WINDOWS;
+  int short_from = 0;
+  int cbits() const { return (int)bucket_log + 1; }  // signed digits: a window of c bits has 2^(c - 1) buckets
+  int planes() const { return (int)bucket_log; }
+};
+
+// One constructor per geometry.
+WindowPlan plan_equal16(TailKind tail, uint32_t slots = MSM377_NUM_WINDOWS) {  // sixteen 16-bit windows, or a shard's `slots` of them
+  WindowPlan p;
+  p.tail = tail;
+  p.slots = slots;
+  p.records = (int)slots;
+  return p;
+}
+WindowPlan plan_even16(TailKind tail) {  // whole MSMs: the top three windows 15 bits wide (kernels/decompose.hpp k_decompose)
+  WindowPlan p = plan_equal16(tail);
+  p.recode = RECODE_EVEN16;
+  p.short_from = EVEN_FROM;
+  return p;
+}
+WindowPlan plan_narrow22() {  // small inputs: eleven signed 12-bit + eleven unsigned 11-bit windows (k_decompose_geom + k_small_sort)
+  WindowPlan p = plan_equal16(TE_TAIL, NARROW_EVEN_WINDOWS);
+  p.recode = RECODE_NARROW22;
+  p.bucket_log = NARROW_LOG;
+  p.short_from = NARROW_EVEN_SIGNED;
+  return p;
+}
+// Behind a precomputed 16-bit table: the slots are folded on the GPU and the host combines the one record that is left.
+WindowPlan folded_behind_table(WindowPlan p, const uint32_t* table, uint64_t stride) {
+  p.table = table;
+  p.table_stride = stride;
+  p.records = 1;
+  p.on_caller = true;
+  return p;
+}
+// The 20-bit table (kernels/wide.hpp): `table` holds [2^(20 w)] P_i for 13 windows, the call has ONE window slot of 2^19
+// buckets fed by the flat list of 13 n digits.
+WindowPlan plan_wide13(const uint32_t* table, uint64_t stride) {
+  WindowPlan p = folded_behind_table(plan_equal16(TE_TAIL, 1), table, stride);
+  p.recode = RECODE_WIDE13;
+  p.bucket_log = WIDE_LOG;
+  return p;
+}
+WindowPlan plan_glv8(uint32_t slots = GLV_WINDOWS) {  // GLV front end: n scalars become 2 n (point, half-scalar) columns over 8 windows
+  WindowPlan p = plan_equal16(XYZZ_TAIL, slots);
+  p.recode = RECODE_GLV8;
+  p.on_caller = true;
+  return p;
+}
+// Scalars below 2^bits in `bytes` bytes each: short_windows(bits, L) slots recoded by k_decompose_short, on 2^11
+// buckets (small inputs in the Edwards form) or 2^15.
+WindowPlan plan_short(TailKind tail, uint32_t bytes, uint32_t bits, bool narrow) {
+  const uint32_t L = narrow ? NARROW_LOG : (uint32_t)MSM377_WINDOW_BITS - 1;
+  WindowPlan p = plan_equal16(tail, short_windows(bits, L));
+  p.recode = RECODE_SHORT;
+  p.bucket_log = L;
+  p.short_bytes = bytes;
+  p.short_bits = bits;
+  return p;
+}
+// Whole MSMs on sixteen windows: even in the Edwards forms unless MSM377_EVEN_WINDOWS=0 (the Weierstrass forms keep equal ones).
+WindowPlan plan_whole16(const msm377_ctx* ctx, TailKind tail) { return ctx->even_windows && tail != XYZZ_TAIL ? plan_even16(tail) : plan_equal16(tail); }
+
+// This geometry refused a scalar that sixteen equal windows may still take: the pass is discarded and the call runs
+// the plan next_plan names.  (A scalar that overflows the recode outright, ERR_SCALAR, fits no geometry: no rerun.)
+bool geometry_refused(const WindowPlan& p, int err) {
+  if (p.recode == RECODE_GLV8) return (err & ERR_GLV_RANGE) != 0;  // a half scalar of 2^127 and more
+  const bool can_refuse = p.recode == RECODE_EVEN16 || p.recode == RECODE_NARROW22 || p.recode == RECODE_WIDE13;  // a scalar of 2^253 and more
+  return can_refuse && (err & ERR_NARROW_RANGE) && !(err & ERR_SCALAR);
+}
+// Sixteen equal windows with the same kind of tail; after the wide table over its window 0, the plain affine records:
+// every slot gathers from the same records, and sixteen records reach the host.
+WindowPlan next_plan(const WindowPlan& refused) {
+  WindowPlan p = plan_equal16(refused.tail);
+  if (refused.recode == RECODE_WIDE13) p.bases_override = refused.table;
+  return p;
+}
+
+// Which stages of a call to enqueue (all of them, except for the chunked host-buffer entry point), and on which windows.
 struct Phase {
   bool clear_err = true;   // first chunk of a call
   bool front = true;       // decompose .. merge
@@ -274,24 +375,7 @@ struct Phase {
   bool back = true;        // bucket reduction, gather, D2H, completion event
   bool zc_out = false;     // the gather kernel writes the records and the error word into pinned host memory itself (k_gather_partials)
   uint64_t base_first = 0; // first record of ctx->d_bases this chunk's indices refer to
-  // Precomputed-window tables (msm377_g1_set_bases_precomputed): window slot ws gathers from record ws * table_stride + i
-  // of `table`, and because the table already carries the 2^(16 ws) weights the 16 bucket sets are ADDED together
-  // before the reduction: one window's reduction, one window's partial record, a 16-step host tail.
-  const uint32_t* table = nullptr;
-  uint64_t table_stride = 0;
-  // Window width of the call: 16 (the main path: 16 windows x 2^15 buckets, the two-level sort) or NARROW_EVEN_BITS
-  // (small inputs: k_decompose_geom + k_small_sort, 22 windows x 2^11 buckets); everything behind the sort takes
-  // L = bucket_log as a run-time argument.
-  uint32_t cbits = MSM377_WINDOW_BITS;
-  uint32_t bucket_log = MSM377_WINDOW_BITS - 1;  // L: 2^L buckets per window (NARROW_LOG on the small-input path)
-  // Wide windows over a precomputed table (kernels/wide.hpp): `table` holds [2^(20 w)] P_i for 13 windows, the call has
-  // ONE window slot of 2^19 buckets fed by the flat list of 13 n digits (cbits = WIDE_BITS, bucket_log = WIDE_LOG).
-  bool wide = false;
-  bool even = false;  // whole MSMs on 16 windows: the top three windows 15 bits wide (kernels/decompose.hpp k_decompose); the tail gets short_from = EVEN_FROM
-  const uint32_t* bases_override = nullptr;  // base records of the call if not ctx->d_bases (the wide table's window 0 = the plain affine records)
-  // Short scalars (msm377_g1_msm_short*): d_scalars holds n x short_bytes bytes, every scalar below 2^short_bits; the call
-  // runs wc = short_windows(short_bits, bucket_log) window slots recoded by k_decompose_short.  0: 32-byte scalars.
-  uint32_t short_bytes = 0, short_bits = 0;
+  WindowPlan plan;
 };
 
 // k_decompose_short for the stride of the call (4, 8, 16 or 32 bytes: checked by the entry points).
@@ -316,9 +400,10 @@ void launch_decompose_short(hipStream_t st, const void* d_scalars, uint16_t* dig
 // accumulation kernel owns every VGPR of the chip, kernels of another stream do not become co-resident.  Removed in
 // round 3.)
 template <class CV, class BP = CV>
-int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scalars, uint32_t wb, uint32_t wc, int slot, bool glv = false,
-                    const Phase& ph = Phase()) {
-  // GLV front end: n_scalars scalars become 2 n_scalars (point, half-scalar) columns over 8 windows.
+int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scalars, uint32_t wb, int slot, const Phase& ph) {
+  const WindowPlan& plan = ph.plan;
+  const uint32_t wc = plan.slots;
+  const bool glv = plan.recode == RECODE_GLV8, wide = plan.recode == RECODE_WIDE13, even = plan.recode == RECODE_EVEN16;
   const uint64_t n = glv ? 2 * n_scalars : n_scalars;
   hipStream_t st = ctx->stream;
   int* d_err = ctx->d_err + slot;
@@ -328,11 +413,10 @@ int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scala
   // the error word is cleared by the call's first kernel together with its counters -- unless there is no such kernel
   // (back phase only)
   if (ph.clear_err && !ph.front) hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(256), 0, st, (uint32_t*)d_err, 1u, (uint32_t*)nullptr, 0u);
-  ctx->zc_active = ph.zc_out && ph.back && ctx->zc_out && slot == 0 && !ph.table;
+  ctx->zc_active = ph.zc_out && ph.back && ctx->zc_out && slot == 0 && !plan.table;
   if (ctx->zc_active) ctx->out_seq++;
-  const uint32_t L = ph.bucket_log, NB = 1u << L;  // this call's bucket geometry (shadows the main path's constant)
-  const bool wide = ph.wide;
-  const bool narrow = !wide && ph.cbits != MSM377_WINDOW_BITS;
+  const uint32_t L = plan.bucket_log, NB = 1u << L;  // this call's bucket geometry (shadows the main path's constant)
+  const bool narrow = !wide && L != MSM377_WINDOW_BITS - 1;  // the small-input front end (k_small_sort), at full width or short
   const uint64_t entries = (wide ? (uint64_t)WIDE_WINDOWS : (uint64_t)wc) * n;  // (window, point) pairs this call accumulates
   static_assert((uint64_t)NARROW_EVEN_WINDOWS * SMALL_SORT_MAX / NARROW_SEG + NARROW_EVEN_WINDOWS * (1u << NARROW_LOG) <= (uint64_t)MSM377_NUM_WINDOWS * 32768,
                 "narrow work items fit the work-item buffer");
@@ -355,18 +439,18 @@ int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scala
   WorkItem* work = ctx->d_work;
   uint32_t* ovf = ctx->d_ovf;
   const uint32_t* records = ctx->resident.valid() ? ctx->resident.bases : ctx->d_bases;  // (a twin's resident bases are lent)
-  const uint32_t* bases = ph.table ? ph.table : ph.bases_override ? ph.bases_override : records + ph.base_first * BP::REC_WORDS;
+  const uint32_t* bases = plan.table ? plan.table : plan.bases_override ? plan.bases_override : records + ph.base_first * BP::REC_WORDS;
   uint32_t* meta_block = ctx->d_work_meta;  // [work-list counters | key_max[16]]
   uint32_t* key_max = meta_block + (2 * SEG_BINS + 4);
   if (ph.front) {
     // One memset clears the call's work-list counters AND its key_max words (0 = full-width ranges); k_decompose
     // then measures window 15 of the plain front end.
     hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(256), 0, st, meta_block, META_BLOCK_WORDS, (uint32_t*)d_err, ph.clear_err ? 1u : 0u);
-    uint32_t* top_key_max = (!glv && !ph.even && wb + wc == MSM377_NUM_WINDOWS) ? key_max + (wc - 1) : nullptr;
+    uint32_t* top_key_max = (!glv && !even && wb + wc == MSM377_NUM_WINDOWS) ? key_max + (wc - 1) : nullptr;
     const uint64_t max_items = (uint64_t)wc * NB + entries / SEG;  // every row has an item; extra ones are full segments
     // a lane quad per work item while the launch is one chain's latency (up to 2^14 points: ~94 k items); beyond that
     // the quads are VALU-bound like threads and only add their exchange instructions (kernel at 2^16: 0.216 / 0.183 ms)
-    const bool quad_acc = std::is_same<BP, CV>::value && std::is_same<CV, TeDev>::value && narrow && !ph.table && max_items <= ctx->narrow_quad_items;
+    const bool quad_acc = std::is_same<BP, CV>::value && std::is_same<CV, TeDev>::value && narrow && !plan.table && max_items <= ctx->narrow_quad_items;
     // (One launch for the whole front end of such a call -- each window's workgroup recoding, sorting and listing its
     // work items itself, one global atomic per list and workgroup -- was built and dropped: 0.271 -> 0.293 ms at 2^12,
     // 0.342 -> 0.373 at 2^14.  Saving four dispatch latencies did not pay for a work list that is sorted by length
@@ -382,16 +466,16 @@ int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scala
       layout.info.row_ptr_len = NB + 2;
       layout.info.bucket_records = NB;
       layout.info.form = CV::FORM_ID;
-      layout.info.table_stride = ph.table_stride;
+      layout.info.table_stride = plan.table_stride;
       layout.info.geometry_reruns = ctx->geometry_reruns;
       layout.d_digits = wide ? (const void*)ctx->wide.digits : (const void*)digits;
       layout.d_key_max = (wide || narrow) ? nullptr : key_max;  // k_local_sort_lds of the wide table and k_small_sort read none
       static_assert(MAX_WINDOW_SLOTS <= MSM377_STAGE_MAX_SLOTS, "a stage layout names every window slot");
       uint32_t bias = 1u << (MSM377_WINDOW_BITS - 1);  // k_decompose / k_decompose_glv: digit_key's bias
-      if (ph.short_bytes) {  // the top slot of the main path: unsigned digits, its ranges narrowed by its largest key (win_shift)
+      if (plan.short_bytes) {  // the top slot of the main path: unsigned digits, its ranges narrowed by its largest key (win_shift)
         bias = narrow ? NB : 32768u;
         const uint32_t top_bias = narrow ? NB : 0u;
-        launch_decompose_short(st, d_scalars, digits, n, ph.short_bytes, ph.short_bits, L, wc, bias, top_bias, d_err, narrow ? nullptr : key_max + (wc - 1));
+        launch_decompose_short(st, d_scalars, digits, n, plan.short_bytes, plan.short_bits, L, wc, bias, top_bias, d_err, narrow ? nullptr : key_max + (wc - 1));
         for (uint32_t s = 0; s < wc; s++) layout.info.bias[s] = s + 1 < wc ? bias : top_bias;
         layout.info.key_unsigned[wc - 1] = narrow ? 0u : 1u;  // (KEY_UNSIGNED in that slot's key_max word)
       } else if (wide) {
@@ -403,8 +487,8 @@ int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scala
       } else if (glv)
         hipLaunchKernelGGL(k_decompose_glv, dim3((unsigned)((n_scalars + 255) / 256)), dim3(256), 0, st, d_scalars, digits, n_scalars, wb, wc, d_err);
       else
-        hipLaunchKernelGGL(k_decompose, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, digits, n, wb, wc, d_err, top_key_max, ph.even ? 1u : 0u);
-      if (!ph.short_bytes)
+        hipLaunchKernelGGL(k_decompose, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, digits, n, wb, wc, d_err, top_key_max, even ? 1u : 0u);
+      if (!plan.short_bytes)
         for (uint32_t s = 0; s < wc; s++) layout.info.bias[s] = bias;
       HIP_TRY(ctx, hipGetLastError());
     }
@@ -417,7 +501,7 @@ int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scala
       hipLaunchKernelGGL(k_wide_sums, dim3(WIDE_NRANGE / 256, WIDE_WINDOWS), dim3(256), 0, st, wc);
       hipLaunchKernelGGL(k_wide_scan, dim3(1), dim3(1024), 0, st, wc, region_base);
       hipLaunchKernelGGL(k_wide_offsets1, dim3(WIDE_WINDOWS), dim3(WS_COARSE), 0, st, wc, n);
-      hipLaunchKernelGGL(k_wide_part1, dim3(WS_CHUNKS, WIDE_WINDOWS), dim3(1024), 0, st, (const uint32_t*)ctx->wide.digits, (const uint32_t*)wc, sort_temp, n, (uint32_t)ph.table_stride);
+      hipLaunchKernelGGL(k_wide_part1, dim3(WS_CHUNKS, WIDE_WINDOWS), dim3(1024), 0, st, (const uint32_t*)ctx->wide.digits, (const uint32_t*)wc, sort_temp, n, (uint32_t)plan.table_stride);
       hipLaunchKernelGGL(k_wide_part2, dim3(WS_COARSE, WIDE_WINDOWS), dim3(1024), 0, st, (const SortElem*)sort_temp, (const uint32_t*)wc, ctx->wide.temp);
       hipLaunchKernelGGL(k_local_sort_lds<SortElem>, dim3(WIDE_NRANGE, 1), dim3(256), 0, st, (const SortElem*)ctx->wide.temp, region_base, row_ptr, val_idx, entries,
                          (const uint32_t*)nullptr, WIDE_NRANGE, NB);
@@ -433,7 +517,7 @@ int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scala
       const uint64_t want = (n + 4095) / 4096;  // at least ~4096 elements per block
       if (chunks > want) chunks = (uint32_t)(want ? want : 1);
       const uint64_t per_chunk = (n + chunks - 1) / chunks;
-      if (ph.short_bytes)  // (the top slot holds unsigned digits: KEY_UNSIGNED)
+      if (plan.short_bytes)  // (the top slot holds unsigned digits: KEY_UNSIGNED)
         hipLaunchKernelGGL(k_range_count<true>, dim3(chunks, wc), dim3(1024), 0, st, digits, range_counts, n, chunks, per_chunk, key_max);
       else
         hipLaunchKernelGGL(k_range_count<false>, dim3(chunks, wc), dim3(1024), 0, st, digits, range_counts, n, chunks, per_chunk, key_max);
@@ -446,7 +530,7 @@ int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scala
       ctx->last_sort_elem = packed ? 4u : 8u;
       auto partition_and_sort = [&](auto* temp) {
         using E = std::remove_pointer_t<decltype(temp)>;
-        if (ph.short_bytes)
+        if (plan.short_bytes)
           hipLaunchKernelGGL((k_partition_staged<E, true>), dim3(chunks, wc), dim3(1024), 0, st, digits, range_counts, temp, n, chunks, per_chunk, key_max);
         else
           hipLaunchKernelGGL((k_partition_staged<E, false>), dim3(chunks, wc), dim3(1024), 0, st, digits, range_counts, temp, n, chunks, per_chunk, key_max);
@@ -492,15 +576,15 @@ int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scala
         if (launched) {
         } else if constexpr (!std::is_same<BP, CV>::value)
           hipLaunchKernelGGL((k_accumulate<CV, 2, BP>), grid, dim3(256), 0, st, row_ptr, val_idx, bases, buckets, n, work, total, row_ovf_base, ovf, SEG, d_err,
-                             ctx->d_err + 2, ph.into ? 1u : 0u, ph.table_stride, L);
+                             ctx->d_err + 2, ph.into ? 1u : 0u, plan.table_stride, L);
         else
           hipLaunchKernelGGL((k_accumulate<CV, 2>), grid, dim3(256), 0, st, row_ptr, val_idx, bases, buckets, n, work, total, row_ovf_base, ovf, SEG, d_err,
-                             ctx->d_err + 2, ph.into ? 1u : 0u, ph.table_stride, L);
+                             ctx->d_err + 2, ph.into ? 1u : 0u, plan.table_stride, L);
       }
       HIP_TRY(ctx, hipGetLastError());
       ctx->acc_seq++;
       static_assert(CV::HAS_QUAD, "every curve policy has the quad-cooperative addition");
-      if (ph.short_bytes) {  // the top window of a short call: few rows, thousands of partials each -- folded before the merge
+      if (plan.short_bytes) {  // the top window of a short call: few rows, thousands of partials each -- folded before the merge
         hipLaunchKernelGGL(k_fold_long_rows<CV>, dim3(FOLD_BLOCKS), dim3(FOLD_THREADS), 0, st, row_ptr, row_ovf_base, ovf, SEG, d_err, L, wc - 1);
         HIP_TRY(ctx, hipGetLastError());
       }
@@ -515,11 +599,11 @@ int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scala
   if (ctx->capture) {
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_buckets_snap, buckets, (size_t)wc * CV::BKT_WORDS * NB * 4, hipMemcpyDeviceToDevice, st));
   }
-  const uint32_t wc_out = ph.table ? 1u : wc;  // precomputed-window tables fold the windows on the GPU
+  const uint32_t wc_out = plan.table ? 1u : wc;  // precomputed-window tables fold the windows on the GPU
   const uint32_t pp = wide ? WIDE_POINTS : (uint32_t)MSM377_G1_PARTIAL_POINTS;  // points per window record
   {
     StageTimer t(ctx, MSM377_STAGE_REDUCE, st);
-    if (ph.table) {
+    if (plan.table) {
       for (uint32_t m = wc; m > 1;) {  // slots [half, m) onto [0, m - half): 16 -> 8 -> 4 -> 2 -> 1; a short call folds any count
         const uint32_t half = (m + 1) / 2, count = m - half;
         hipLaunchKernelGGL(k_fold_windows<CV>, dim3(count * NB / 256), dim3(256), 0, st, buckets, L, half, count, d_err);
@@ -606,8 +690,7 @@ int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scala
   return MSM377_OK;
 }
 
-// Wait for slot `slot`; its partial records are then in ctx->h_partials + slot * SLOT_WORDS.
-// Zero-copy output (Phase::zc_out): poll the sequence number the gather kernel's last block writes behind the records;
+// Zero-copy output (Phase::zc_out, slot 0): poll the sequence number the gather kernel's last block writes behind the records;
 // the stream's completion event is waited for only when stage timing needs it (or after 50 ms without the flag, which
 // then also surfaces a failed kernel).
 int wait_zero_copy_out(msm377_ctx* ctx) {
@@ -627,17 +710,21 @@ int wait_zero_copy_out(msm377_ctx* ctx) {
   return MSM377_OK;
 }
 
-int finish_windows(msm377_ctx* ctx, int slot) {
+// Wait for slot `slot`: its error word is then in ctx->h_err[slot], its records in ctx->h_partials + slot * SLOT_WORDS.
+int wait_windows(msm377_ctx* ctx, int slot) {
   if (ctx->zc_active && slot == 0) {
     const int rc = wait_zero_copy_out(ctx);
-    if (rc) return rc;
-    if (ctx->timing) HIP_TRY(ctx, hipEventSynchronize(ctx->done_ev[slot]));
-  } else {
-    HIP_TRY(ctx, hipEventSynchronize(ctx->done_ev[slot]));
+    if (rc || !ctx->timing) return rc;
   }
+  HIP_TRY(ctx, hipEventSynchronize(ctx->done_ev[slot]));
+  return MSM377_OK;
+}
+
+// Behind wait_windows, once the caller has decided to keep the pass: the stage times, and the one error no geometry helps.
+int collect_windows(msm377_ctx* ctx, int slot) {
   if (ctx->timing) {
     for (int s = 0; s < MSM377_NUM_STAGES; s++) {
-      if (s == MSM377_STAGE_TAIL) continue;  // host wall time, set by the caller
+      if (s == MSM377_STAGE_TAIL) continue;  // host wall time, set by run_tail
       if (ctx->timing == 2 && s != MSM377_STAGE_ACC_KERNEL) {
         ctx->stage_ms[s] = 0.0;
         continue;
@@ -654,14 +741,7 @@ int finish_windows(msm377_ctx* ctx, int slot) {
   return MSM377_OK;
 }
 
-template <class CV>
-int run_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n, uint32_t wb, uint32_t wc, bool glv = false) {
-  int rc = enqueue_windows<CV>(ctx, d_scalars, n, wb, wc, 0, glv);
-  if (rc) return rc;
-  return finish_windows(ctx, 0);
-}
-
-inline bool use_glv(const msm377_ctx* ctx, uint64_t) { return ctx->glv_mode == 1; }  // see msm377_ctx::glv_mode
+inline bool use_glv(const msm377_ctx* ctx) { return ctx->glv_mode == 1; }  // see msm377_ctx::glv_mode
 
 // Base conversion for the G1 entry points: with the GLV front end the table also gets phi(P_i).
 int convert_bases_g1(msm377_ctx* ctx, const uint32_t* d_raw, uint64_t n, bool glv) {
@@ -687,8 +767,8 @@ inline int resident_form(const msm377_ctx* ctx, uint64_t n) {
 }
 // The resident table is the 20-bit-window one: 13 windows over one set of 2^19 buckets.
 inline bool wide_table(const ResidentBases& r) { return r.form == TABLE_TE_PRECOMP && r.windows == WIDE_WINDOWS; }
-inline int weierstrass_form(const msm377_ctx* ctx, uint64_t n) { return use_glv(ctx, n) ? TABLE_XYZZ_GLV : TABLE_XYZZ; }
-inline int pick_form(const msm377_ctx* ctx, uint64_t n) { return ctx->g1_form == 1 ? TABLE_TE : weierstrass_form(ctx, n); }
+inline int weierstrass_form(const msm377_ctx* ctx) { return use_glv(ctx) ? TABLE_XYZZ_GLV : TABLE_XYZZ; }
+inline int pick_form(const msm377_ctx* ctx) { return ctx->g1_form == 1 ? TABLE_TE : weierstrass_form(ctx); }
 
 int convert_table(msm377_ctx* ctx, const uint32_t* d_raw, uint64_t n, int form) {
   if (form == TABLE_TE) return convert_bases<TeDev>(ctx, d_raw, n);
@@ -699,15 +779,27 @@ int convert_table(msm377_ctx* ctx, const uint32_t* d_raw, uint64_t n, int form) 
   return convert_bases_g1(ctx, d_raw, n, form == TABLE_XYZZ_GLV);
 }
 
-void time_tail(msm377_ctx* ctx, std::chrono::steady_clock::time_point t0) {
+// The host tail `plan` names over the window records at `partials`, timed into stage_ms[MSM377_STAGE_TAIL].
+// RC_TE_FALLBACK (noted): the Edwards tail hit an exceptional case, out_xy is untouched.
+int run_tail(msm377_ctx* ctx, const WindowPlan& plan, const uint32_t* partials, uint8_t* out_xy) {
+  const auto t0 = std::chrono::steady_clock::now();
+  int tr = TAIL_OK;
+  if (plan.tail == ED_TAIL)
+    tr = ed_tail(ctx, partials, out_xy, plan.short_from);
+  else if (plan.tail == XYZZ_TAIL && plan.on_caller)
+    g1h_combine(partials, plan.records, out_xy, plan.short_from);
+  else if (plan.tail == XYZZ_TAIL)
+    tr = xyzz_tail(ctx, partials, out_xy, plan.short_from, plan.records);
+  else if (plan.on_caller)
+    tr = teh_combine(partials, plan.records, out_xy, plan.cbits(), plan.planes(), plan.short_from) ? TAIL_EXCEPTIONAL : TAIL_OK;
+  else
+    tr = te_tail(ctx, partials, out_xy, plan.records, plan.cbits(), plan.planes(), plan.short_from);
   ctx->stage_ms[MSM377_STAGE_TAIL] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (tr != TAIL_EXCEPTIONAL) return tr;
+  note_fallback(ctx, MSM377_FB_TAIL);
+  return RC_TE_FALLBACK;
 }
 
-// Full G1 MSM of n scalars against ctx->d_bases in form `form` (already converted or being converted on the
-// side stream).  TABLE_TE: 16 windows in twisted Edwards form; RC_TE_FALLBACK when an addition or an input point
-// hit an exceptional case (the caller reconverts and reruns).  TABLE_XYZZ_GLV: the GLV front end; a scalar outside
-// its range (bit 1 of the error word) reruns on the plain 16-window path, whose records 0..n-1 of the table are
-// the plain points either way.
 // Arms the tail workers of one call once its accumulation kernel is through (TailPool::prewake: they poll for their
 // jobs while the GPU reduces the buckets); disarmed when the tail is done.
 struct TailArm {
@@ -738,110 +830,74 @@ struct TailArm {
   ~TailArm() { c->tail_pool.disarm(); }
 };
 
-int g1_table_msm(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n, int form, uint8_t out_xy[96]) {
+// enqueue_windows for the records of a table form, from window 0.
+int enqueue_form(msm377_ctx* ctx, int form, const uint32_t* d_scalars, uint64_t n, int slot, const Phase& ph) {
+  if (form == TABLE_TE) return enqueue_windows<TeDev>(ctx, d_scalars, n, 0, slot, ph);
+  if (form_is_te(form)) return enqueue_windows<TeDev, TeAffBase>(ctx, d_scalars, n, 0, slot, ph);
+  return enqueue_windows<G1Dev>(ctx, d_scalars, n, 0, slot, ph);
+}
+
+// The first plan of a G1 MSM of n scalars on records of `form`.  sbytes = 0: 32-byte scalars of any width; else scalars
+// of sbytes bytes below 2^bits (never even, never behind the GLV front end: a GLV table serves through its plain half).
+WindowPlan first_plan(const msm377_ctx* ctx, uint64_t n, int form, uint32_t sbytes, uint32_t bits) {
+  if (!form_is_te(form)) return sbytes ? plan_short(XYZZ_TAIL, sbytes, bits, false) : form == TABLE_XYZZ_GLV ? plan_glv8() : plan_equal16(XYZZ_TAIL);
+  const ResidentBases& r = ctx->resident;
+  // Small inputs: narrow windows; the window-indexed buffers are sized for them too (msm377_ctx_create: wcap).  A
+  // precomputed table has its own geometry, and capture mode 1 describes sixteen equal 16-bit windows.
+  const bool precomp = form == TABLE_TE_PRECOMP;
+  const bool narrow = !precomp && n <= ctx->narrow_max_points && n <= SMALL_SORT_MAX && ctx->capture != 1;
+  if (sbytes) {
+    WindowPlan p = plan_short(TE_TAIL, sbytes, bits, narrow);
+    if (precomp && wide_table(r))
+      p.bases_override = r.table;  // the 20-bit table serves through its window 0, the plain affine records
+    else if (precomp)
+      p = folded_behind_table(p, r.table, r.n);
+    return p;
+  }
+  if (precomp) return wide_table(r) ? plan_wide13(r.table, r.n) : folded_behind_table(plan_equal16(TE_TAIL), r.table, r.n);
+  if (narrow) return plan_narrow22();  // (whatever MSM377_EVEN_WINDOWS says)
+  return ctx->capture == 1 ? plan_equal16(TE_TAIL) : plan_whole16(ctx, TE_TAIL);
+}
+
+int short_width_error(msm377_ctx* ctx, uint32_t bits) {
+  ctx->err = "a scalar does not fit the declared width of " + std::to_string(bits) + " bits (scalar_bits)";
+  return MSM377_ESCALAR;
+}
+
+// G1 MSM of n scalars against the base records in form `form` (ctx->d_bases or the resident table; already converted or
+// being converted on the side stream).  A geometry that refuses a scalar hands the call to the next one (each refusal
+// counts one geometry rerun); a short call (sbytes != 0) runs ONE pass: a scalar of 2^bits or more is the caller's
+// error (MSM377_ESCALAR, out_xy untouched), not a reason to rerun at full width.  RC_TE_FALLBACK: an addition or an
+// input point hit an exceptional case of the Edwards law (the caller reconverts to TABLE_XYZZ and calls again).
+// Zero-copy output and the early arming of the tail workers belong to the Edwards forms.
+int g1_table_msm(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n, int form, uint8_t out_xy[96], uint32_t sbytes = 0, uint32_t bits = 0) {
+  const bool te = form_is_te(form);
   TailArm arm(ctx);
   arm.at_start(n);
-  if (form_is_te(form)) {
-    Phase ph;
-    if (form == TABLE_TE_PRECOMP) {
-      ph.table = ctx->resident.table;
-      ph.table_stride = ctx->resident.n;
-    }
-    // Small inputs: narrow windows (k_decompose_geom); the window-indexed buffers are sized for them too
-    // (msm377_ctx_create: wcap).  Capture mode 1 describes the 16-bit geometry.
-    bool narrow = form != TABLE_TE_PRECOMP && n <= ctx->narrow_max_points && n <= SMALL_SORT_MAX && ctx->capture != 1;
-    bool wide = form == TABLE_TE_PRECOMP && wide_table(ctx->resident);
-    bool table0 = false;  // the 16-window path over window 0 of the wide table (= the affine records of the points themselves)
-    bool even = ctx->even_windows && form != TABLE_TE_PRECOMP && ctx->capture != 1;  // (capture mode 1 describes sixteen equal windows)
-    for (;;) {
-      uint32_t windows = MSM377_NUM_WINDOWS;
-      int cbits = MSM377_WINDOW_BITS, planes = MSM377_WINDOW_BITS - 1, short_from = 0;  // the host tail's view of the geometry
-      ph.cbits = MSM377_WINDOW_BITS;
-      ph.bucket_log = MSM377_WINDOW_BITS - 1;
-      if (wide) {  // one window slot of 2^19 buckets over the 13-window table
-        ph.wide = true;
-        ph.cbits = WIDE_BITS;
-        ph.bucket_log = WIDE_LOG;
-        windows = 1;
-        cbits = WIDE_BITS;
-        planes = WIDE_LOG;
-      } else if (narrow) {  // eleven signed 12-bit + eleven unsigned 11-bit windows (whatever MSM377_EVEN_WINDOWS says)
-        ph.cbits = NARROW_EVEN_BITS;
-        ph.bucket_log = NARROW_LOG;
-        windows = NARROW_EVEN_WINDOWS;
-        cbits = NARROW_EVEN_BITS;
-        planes = NARROW_LOG;
-        short_from = NARROW_EVEN_SIGNED;
-      }
-      ph.even = even && !wide && !table0;
-      if (ph.even && !narrow) short_from = EVEN_FROM;
-      ph.zc_out = true;
-      int rc = form == TABLE_TE ? enqueue_windows<TeDev>(ctx, d_scalars, n, 0, windows, 0, false, ph)
-                                : enqueue_windows<TeDev, TeAffBase>(ctx, d_scalars, n, 0, windows, 0, false, ph);
-      if (rc) return rc;
-      arm.after_accumulation();
-      if (ctx->zc_active) {
-        rc = wait_zero_copy_out(ctx);
-        if (rc) return rc;
-      } else {
-        HIP_TRY(ctx, hipEventSynchronize(ctx->done_ev[0]));
-      }
-      if (narrow && (ctx->h_err[0] & ERR_NARROW_RANGE) && !(ctx->h_err[0] & ERR_SCALAR)) {  // a scalar >= 2^253: sixteen 16-bit windows take it
-        narrow = false;
-        even = false;
-        ctx->geometry_reruns++;
-        continue;
-      }
-      if (ph.even && (ctx->h_err[0] & ERR_NARROW_RANGE) && !(ctx->h_err[0] & ERR_SCALAR)) {  // likewise: sixteen equal windows take it
-        even = false;
-        ctx->geometry_reruns++;
-        continue;
-      }
-      if (wide && (ctx->h_err[0] & ERR_NARROW_RANGE) && !(ctx->h_err[0] & ERR_SCALAR)) {  // likewise: its top window holds 19 bits
-        wide = false;
-        table0 = true;
-        ctx->geometry_reruns++;
-        ph.wide = false;
-        ph.table = nullptr;
-        ph.table_stride = 0;  // every window slot gathers from the same records
-        ph.bases_override = ctx->resident.table;
-        continue;
-      }
-      if (ctx->h_err[0] & ERR_TE_ANY) {
-        note_fallback(ctx, (uint32_t)(ctx->h_err[0] & ERR_TE_ANY));
-        return RC_TE_FALLBACK;
-      }
-      rc = finish_windows(ctx, 0);
-      if (rc) return rc;
-      auto t0 = std::chrono::steady_clock::now();
-      const int tr = form == TABLE_TE_PRECOMP && !table0 ? (teh_combine(ctx->h_partials, 1, out_xy, cbits, planes) ? TAIL_EXCEPTIONAL : TAIL_OK)
-                                              : te_tail(ctx, ctx->h_partials, out_xy, (int)windows, cbits, planes, short_from);
-      time_tail(ctx, t0);
-      if (tr < 0) return tr;
-      if (tr == TAIL_EXCEPTIONAL) note_fallback(ctx, MSM377_FB_TAIL);
-      return tr == TAIL_EXCEPTIONAL ? RC_TE_FALLBACK : MSM377_OK;
-    }
-  }
-  if (form == TABLE_XYZZ_GLV) {
-    int rc = enqueue_windows<G1Dev>(ctx, d_scalars, n, 0, GLV_WINDOWS, 0, true);
+  Phase ph;
+  ph.zc_out = te;
+  ph.plan = first_plan(ctx, n, form, sbytes, bits);
+  for (;;) {
+    int rc = enqueue_form(ctx, form, d_scalars, n, 0, ph);
     if (rc) return rc;
-    HIP_TRY(ctx, hipEventSynchronize(ctx->done_ev[0]));
-    if ((ctx->h_err[0] & ERR_GLV_RANGE) == 0) {
-      rc = finish_windows(ctx, 0);
-      if (rc) return rc;
-      auto t0 = std::chrono::steady_clock::now();
-      g1h_combine(ctx->h_partials, GLV_WINDOWS, out_xy);
-      time_tail(ctx, t0);
-      return MSM377_OK;
+    if (te) arm.after_accumulation();
+    rc = wait_windows(ctx, 0);
+    if (rc) return rc;
+    const int err = ctx->h_err[0];
+    if (geometry_refused(ph.plan, err)) {
+      ctx->geometry_reruns++;
+      ph.plan = next_plan(ph.plan);
+      continue;
     }
-    ctx->geometry_reruns++;  // a half scalar of 2^127 and more: the GLV pass is discarded, sixteen plain windows take the call
+    if (sbytes && (err & ERR_SHORT_WIDTH)) return short_width_error(ctx, bits);
+    if (te && (err & ERR_TE_ANY)) {
+      note_fallback(ctx, (uint32_t)(err & ERR_TE_ANY));
+      return RC_TE_FALLBACK;
+    }
+    rc = collect_windows(ctx, 0);
+    if (rc) return rc;
+    return run_tail(ctx, ph.plan, ctx->h_partials, out_xy);
   }
-  int rc = run_windows<G1Dev>(ctx, d_scalars, n, 0, MSM377_NUM_WINDOWS);
-  if (rc) return rc;
-  auto t0 = std::chrono::steady_clock::now();
-  rc = xyzz_tail(ctx, ctx->h_partials, out_xy);
-  time_tail(ctx, t0);
-  return rc;
 }
 
 // The resident table hit an exceptional case of the Edwards law: rebuild it in Weierstrass form from the raw
@@ -857,76 +913,6 @@ int resident_table_to_weierstrass(msm377_ctx* ctx) {
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream2));
   ctx->resident.set(ctx->d_bases, n, form, flagged, mask);
   return MSM377_OK;
-}
-
-// The short-scalar counterpart of g1_table_msm: n scalars of `sbytes` bytes, each below 2^bits, against the base records
-// in form `form`.  The path is chosen by n as there -- narrow windows (L = 11) for small inputs in the Edwards form, 2^15
-// buckets otherwise -- and runs W = short_windows(bits, L) window slots, ONE pass: a scalar of 2^bits or more is the
-// caller's error (MSM377_ESCALAR, out_xy untouched), not a reason to rerun at full width.  A precomputed 16-bit table
-// serves slots 0 .. W - 1 (its bucket sets are added before the one reduction); the 20-bit table serves through its
-// first window, the plain affine records.  RC_TE_FALLBACK as for g1_table_msm.
-int short_width_error(msm377_ctx* ctx, uint32_t bits) {
-  ctx->err = "a scalar does not fit the declared width of " + std::to_string(bits) + " bits (scalar_bits)";
-  return MSM377_ESCALAR;
-}
-
-int g1_short_table_msm(msm377_ctx* ctx, const void* d_scalars, uint64_t n, int form, uint32_t sbytes, uint32_t bits, uint8_t out_xy[96]) {
-  TailArm arm(ctx);
-  arm.at_start(n);
-  Phase ph;
-  ph.short_bytes = sbytes;
-  ph.short_bits = bits;
-  const uint32_t* sc = (const uint32_t*)d_scalars;
-  if (form_is_te(form)) {
-    const bool precomp = form == TABLE_TE_PRECOMP;
-    if (precomp && wide_table(ctx->resident)) {
-      ph.bases_override = ctx->resident.table;
-    } else if (precomp) {
-      ph.table = ctx->resident.table;
-      ph.table_stride = ctx->resident.n;
-    }
-    if (!precomp && n <= ctx->narrow_max_points && n <= SMALL_SORT_MAX && ctx->capture != 1) {
-      ph.cbits = NARROW_EVEN_BITS;
-      ph.bucket_log = NARROW_LOG;
-    }
-    const uint32_t L = ph.bucket_log, W = short_windows(bits, L);
-    ph.zc_out = true;
-    int rc = form == TABLE_TE ? enqueue_windows<TeDev>(ctx, sc, n, 0, W, 0, false, ph) : enqueue_windows<TeDev, TeAffBase>(ctx, sc, n, 0, W, 0, false, ph);
-    if (rc) return rc;
-    arm.after_accumulation();
-    if (ctx->zc_active) {
-      rc = wait_zero_copy_out(ctx);
-      if (rc) return rc;
-    } else {
-      HIP_TRY(ctx, hipEventSynchronize(ctx->done_ev[0]));
-    }
-    if (ctx->h_err[0] & ERR_SHORT_WIDTH) return short_width_error(ctx, bits);
-    if (ctx->h_err[0] & ERR_TE_ANY) {
-      note_fallback(ctx, (uint32_t)(ctx->h_err[0] & ERR_TE_ANY));
-      return RC_TE_FALLBACK;
-    }
-    rc = finish_windows(ctx, 0);
-    if (rc) return rc;
-    auto t0 = std::chrono::steady_clock::now();
-    const int tr = ph.table ? (teh_combine(ctx->h_partials, 1, out_xy, MSM377_WINDOW_BITS, MSM377_WINDOW_BITS - 1) ? TAIL_EXCEPTIONAL : TAIL_OK)
-                            : te_tail(ctx, ctx->h_partials, out_xy, (int)W, (int)L + 1, (int)L, 0);
-    time_tail(ctx, t0);
-    if (tr < 0) return tr;
-    if (tr == TAIL_EXCEPTIONAL) note_fallback(ctx, MSM377_FB_TAIL);
-    return tr == TAIL_EXCEPTIONAL ? RC_TE_FALLBACK : MSM377_OK;
-  }
-  // Weierstrass XYZZ records, never behind the GLV front end: W windows of 2^15 buckets
-  const uint32_t W = short_windows(bits, MSM377_WINDOW_BITS - 1);
-  int rc = enqueue_windows<G1Dev>(ctx, sc, n, 0, W, 0, false, ph);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipEventSynchronize(ctx->done_ev[0]));
-  if (ctx->h_err[0] & ERR_SHORT_WIDTH) return short_width_error(ctx, bits);
-  rc = finish_windows(ctx, 0);
-  if (rc) return rc;
-  auto t0 = std::chrono::steady_clock::now();
-  rc = xyzz_tail(ctx, ctx->h_partials, out_xy, 0, (int)W);
-  time_tail(ctx, t0);
-  return rc;
 }
 
 // scalar_bytes in {4, 8, 16, 32}, 1 <= scalar_bits <= min(8 scalar_bytes, 253) (include/msm377.h).
@@ -949,15 +935,10 @@ int check_short_args(msm377_ctx* ctx, uint32_t sbytes, uint32_t bits) {
 // end -- decompose .. accumulate .. merge -- while the next one is on its way.  (Sorting all scalars once and
 // accumulating each chunk through its own sub-rows was built, passed and measured slower: HISTORY.md, "Sort-once
 // schedule".)
-// The chunks' decompositions use the even window geometry in the Edwards forms (g1_msm / ed_msm hand EVEN_FROM to the
-// tail and rerun in one piece when a scalar does not fit).
+// Every chunk runs `plan` (g1_msm / ed_msm: the even geometry in the Edwards forms; they rerun in one piece when a scalar
+// does not fit it) and the last one queues the back phase; the caller waits, classifies and runs the plan's tail.
 template <class CV>
-inline bool upload_even(const msm377_ctx* ctx) {
-  return (std::is_same<CV, TeDev>::value || std::is_same<CV, EdDev>::value) && ctx->even_windows;
-}
-
-template <class CV>
-int run_chunked_upload(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n) {
+int run_chunked_upload(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, const WindowPlan& plan) {
   constexpr size_t PB = CV::RAW_WORDS * 4;  // bytes per wire point
   uint64_t cut[10];  // chunk c = points [cut[c], cut[c + 1]): the first one upload_split_pct of n, the rest even
   uint32_t K = 0;
@@ -1001,9 +982,9 @@ int run_chunked_upload(msm377_ctx* ctx, const uint8_t* points, const uint8_t* sc
     ph.into = c > 0;
     ph.back = c + 1 == K;
     ph.base_first = first;
-    ph.even = upload_even<CV>(ctx);
+    ph.plan = plan;
     rc = convert_bases<CV>(ctx, ctx->d_raw_points + first * CV::RAW_WORDS, cnt, first, c == 0);
-    if (rc == MSM377_OK) rc = enqueue_windows<CV>(ctx, ctx->d_raw_scalars + first * 8, cnt, 0, MSM377_NUM_WINDOWS, 0, false, ph);
+    if (rc == MSM377_OK) rc = enqueue_windows<CV>(ctx, ctx->d_raw_scalars + first * 8, cnt, 0, 0, ph);
   }
   upload.join();
   if (rc) (void)hipStreamSynchronize(ctx->stream);
@@ -1278,39 +1259,74 @@ int reserve_host_staging(msm377_ctx* ctx) {
   return MSM377_OK;
 }
 
-int g1_msm_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint8_t out_xy[96]) {
-  if (!out_xy) return MSM377_EINVAL;
-  int rc = check_args(ctx, d_points, d_scalars, n, true);
-  if (rc) return rc;
+// ---- per-call G1 MSMs: msm377_g1_msm* and, with a short spec (sbytes scalar bytes, every scalar below 2^bits; 0 = full
+// width), msm377_g1_msm_short* ----
+namespace {
+
+// An exceptional case of the Edwards law means points outside the prime-order subgroup: the call runs again on
+// Weierstrass records, never behind the GLV front end.
+int g1_rerun_weierstrass(msm377_ctx* ctx, const uint32_t* d_points, const uint32_t* d_scalars, uint64_t n, uint8_t out_xy[96], uint32_t sbytes, uint32_t bits) {
+  const int rc = convert_table(ctx, d_points, n, TABLE_XYZZ);
+  return rc ? rc : g1_table_msm(ctx, d_scalars, n, TABLE_XYZZ, out_xy, sbytes, bits);
+}
+
+// Device pointers: import, pick the form, convert, run the table call, rerun on the Weierstrass path if it asks for it.
+int g1_device_flow(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint8_t out_xy[96], uint32_t sbytes, uint32_t bits) {
   if (n == 0) {
     identity_wire(out_xy);
     return MSM377_OK;
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   ctx->resident.clear();
-  rc = import_inputs(ctx, &d_points, &d_scalars, n);  // (native input forms only)
+  int rc = import_inputs(ctx, &d_points, &d_scalars, n, sbytes ? sbytes / 4 : 8);  // (native input forms only)
   if (rc) return rc;
-  int form = pick_form(ctx, n);
+  const uint32_t *pts = (const uint32_t*)d_points, *sc = (const uint32_t*)d_scalars;
+  int form = sbytes && ctx->g1_form != 1 ? (int)TABLE_XYZZ : pick_form(ctx);  // a short call never takes the GLV front end
   // (Queueing the conversion after k_decompose instead was measured: decompose 77 -> 23 us, sort 272 -> 386 us.)
   if (form == TABLE_TE && ctx->te_affine_msm && n >= ctx->affine_min_points) {
     // Affine records (7-product additions) by the batched conversion: its way up is queued now, the host's inversion
     // and the way down happen from the hook, once decompose .. work list are queued on the main stream.
     form = TABLE_TE_AFFINE;
-    rc = affine_convert_begin(ctx, (const uint32_t*)d_points, n);
+    rc = affine_convert_begin(ctx, pts, n);
     if (rc) return rc;
-    ctx->before_accumulate = [ctx, n]() -> int { return affine_convert_finish(ctx, ctx->d_bases, n, true); };
-    rc = g1_table_msm(ctx, (const uint32_t*)d_scalars, n, form, out_xy);
-    ctx->before_accumulate = nullptr;
+    ctx->before_accumulate = [ctx, n]() -> int { return affine_convert_finish(ctx, ctx->d_bases, n); };
   } else {
-    rc = convert_table(ctx, (const uint32_t*)d_points, n, form);
+    rc = convert_table(ctx, pts, n, form);
     if (rc) return rc;
-    rc = g1_table_msm(ctx, (const uint32_t*)d_scalars, n, form, out_xy);
   }
-  if (rc != RC_TE_FALLBACK) return rc;
-  form = TABLE_XYZZ;  // an exceptional case means points outside the prime-order subgroup: never the GLV front end
-  rc = convert_table(ctx, (const uint32_t*)d_points, n, form);
+  rc = g1_table_msm(ctx, sc, n, form, out_xy, sbytes, bits);
+  ctx->before_accumulate = nullptr;
+  return rc == RC_TE_FALLBACK ? g1_rerun_weierstrass(ctx, pts, sc, n, out_xy, sbytes, bits) : rc;
+}
+
+// Host buffers in one piece.  Scalars first: decomposition, sort and the work lists need nothing else, so they run
+// while the points (three quarters of the bytes at full width) are still on their way on the upload thread; the hook
+// joins it and launches the conversion to `form` right before the accumulation is queued (TABLE_TE_AFFINE: both phases
+// of the batched conversion back to back).
+int g1_host_flow(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, int form, uint8_t out_xy[96], uint32_t sbytes, uint32_t bits) {
+  const uint32_t *d_sc = ctx->d_raw_scalars, *d_pt = ctx->d_raw_points;
+  int rc = h2d_staged(ctx, ctx->d_raw_scalars, scalars, n * (sbytes ? sbytes : 32), (size_t)ctx->cap * 96);
   if (rc) return rc;
-  return g1_table_msm(ctx, (const uint32_t*)d_scalars, n, form, out_xy);
+  int up_rc = MSM377_OK;
+  HipFail up_fail;
+  std::thread upload([&] { up_rc = hipSetDevice(ctx->device) == hipSuccess ? h2d_staged(ctx, ctx->d_raw_points, points, n * 96, 0, &up_fail) : MSM377_EHIP; });
+  ctx->before_accumulate = [&]() -> int {
+    if (upload.joinable()) upload.join();
+    if (up_rc) return up_fail.record(ctx, up_rc);
+    return convert_table(ctx, d_pt, n, form);
+  };
+  rc = g1_table_msm(ctx, d_sc, n, form, out_xy, sbytes, bits);
+  ctx->before_accumulate = nullptr;
+  if (upload.joinable()) upload.join();  // an error before the hook ran
+  return rc == RC_TE_FALLBACK ? g1_rerun_weierstrass(ctx, d_pt, d_sc, n, out_xy, sbytes, bits) : rc;
+}
+
+}  // namespace
+
+int g1_msm_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint8_t out_xy[96]) {
+  if (!out_xy) return MSM377_EINVAL;
+  const int rc = check_args(ctx, d_points, d_scalars, n, true);
+  return rc ? rc : g1_device_flow(ctx, d_points, d_scalars, n, out_xy, 0, 0);
 }
 
 int g1_msm(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint8_t out_xy[96]) {
@@ -1330,100 +1346,41 @@ int g1_msm(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint6
     return up ? up : g1_msm_device(ctx, native_points(ctx), native_scalars(ctx), n, out_xy);
   }
   ctx->resident.clear();
-  int form = pick_form(ctx, n);
-  const uint32_t* d_sc = ctx->d_raw_scalars;
-  const uint32_t* d_pt = ctx->d_raw_points;
-  int rc;
-  if (n >= ctx->upload_chunk_min && form != TABLE_XYZZ_GLV && !ctx->capture) {  // (stage read-backs describe the plain row layout)
-    const bool te = form == TABLE_TE;
-    rc = te ? run_chunked_upload<TeDev>(ctx, points, scalars, n) : run_chunked_upload<G1Dev>(ctx, points, scalars, n);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipEventSynchronize(ctx->done_ev[0]));
-    const bool even = te && upload_even<TeDev>(ctx);
-    if (even && (ctx->h_err[0] & ERR_NARROW_RANGE) && !(ctx->h_err[0] & (ERR_SCALAR | ERR_TE_ANY))) {
-      // a scalar of 2^253 and more: everything is on the device by now, rerun in one piece (g1_table_msm falls back to
-      // sixteen equal windows by itself)
-      ctx->geometry_reruns++;
-      rc = convert_table(ctx, d_pt, n, form);
-      if (rc) return rc;
-      rc = g1_table_msm(ctx, d_sc, n, form, out_xy);
-      if (rc != RC_TE_FALLBACK) return rc;
-    } else if (!(te && (ctx->h_err[0] & ERR_TE_ANY))) {
-      rc = finish_windows(ctx, 0);
-      if (rc) return rc;
-      auto t0 = std::chrono::steady_clock::now();
-      const int tr = te ? te_tail(ctx, ctx->h_partials, out_xy, 16, 16, 15, even ? (int)EVEN_FROM : 0) : xyzz_tail(ctx, ctx->h_partials, out_xy);
-      time_tail(ctx, t0);
-      if (tr != TAIL_EXCEPTIONAL) return tr;
-      note_fallback(ctx, MSM377_FB_TAIL);
-    } else {
-      note_fallback(ctx, (uint32_t)(ctx->h_err[0] & ERR_TE_ANY));
-    }
-    // exceptional case of the Edwards law: everything is on the device by now, rerun in one piece below
+  const int form = pick_form(ctx);  // (projective Edwards records at any n)
+  if (n < ctx->upload_chunk_min || form == TABLE_XYZZ_GLV || ctx->capture)  // (stage read-backs describe the plain row layout)
+    return g1_host_flow(ctx, points, scalars, n, form, out_xy, 0, 0);
+  const bool te = form == TABLE_TE;
+  const WindowPlan plan = plan_whole16(ctx, te ? TE_TAIL : XYZZ_TAIL);
+  int rc = te ? run_chunked_upload<TeDev>(ctx, points, scalars, n, plan) : run_chunked_upload<G1Dev>(ctx, points, scalars, n, plan);
+  if (rc == MSM377_OK) rc = wait_windows(ctx, 0);
+  if (rc) return rc;
+  // Whatever sends the call round again below finds everything on the device by now and runs in one piece.
+  const int err = ctx->h_err[0];
+  if (te && (err & ERR_TE_ANY)) {
+    note_fallback(ctx, (uint32_t)(err & ERR_TE_ANY));
+  } else if (geometry_refused(plan, err)) {  // a scalar of 2^253 and more: g1_table_msm falls back to sixteen equal windows by itself
+    ctx->geometry_reruns++;
+    rc = convert_table(ctx, ctx->d_raw_points, n, form);
+    if (rc == MSM377_OK) rc = g1_table_msm(ctx, ctx->d_raw_scalars, n, form, out_xy);
+    if (rc != RC_TE_FALLBACK) return rc;
   } else {
-    // Scalars first: decomposition, sort and the work lists need nothing else, so they run while the points (three
-    // quarters of the bytes) are still on their way; the conversion is launched when the upload lands, right before
-    // the accumulation is queued.
-    rc = h2d_staged(ctx, ctx->d_raw_scalars, scalars, n * 32, (size_t)ctx->cap * 96);
-    if (rc) return rc;
-    int up_rc = MSM377_OK;
-    HipFail up_fail;
-    std::thread upload([&] {
-      up_rc = hipSetDevice(ctx->device) == hipSuccess ? h2d_staged(ctx, ctx->d_raw_points, points, n * 96, 0, &up_fail) : MSM377_EHIP;
-    });
-    ctx->before_accumulate = [&]() -> int {
-      if (upload.joinable()) upload.join();
-      if (up_rc) return up_fail.record(ctx, up_rc);
-      return convert_table(ctx, d_pt, n, form);
-    };
-    rc = g1_table_msm(ctx, d_sc, n, form, out_xy);
-    ctx->before_accumulate = nullptr;
-    if (upload.joinable()) upload.join();  // an error before the hook ran
+    rc = collect_windows(ctx, 0);
+    if (rc == MSM377_OK) rc = run_tail(ctx, plan, ctx->h_partials, out_xy);
     if (rc != RC_TE_FALLBACK) return rc;
   }
-  form = TABLE_XYZZ;
-  rc = convert_table(ctx, d_pt, n, form);
-  if (rc) return rc;
-  return g1_table_msm(ctx, d_sc, n, form, out_xy);
+  return g1_rerun_weierstrass(ctx, ctx->d_raw_points, ctx->d_raw_scalars, n, out_xy, 0, 0);
 }
 
-// ---- short scalars (include/msm377.h: msm377_g1_msm_short*, msm377_scalars_width_device) ----
 int g1_msm_short_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t sbytes, uint32_t bits, uint8_t out_xy[96]) {
   if (!out_xy) return MSM377_EINVAL;
   int rc = check_args(ctx, d_points, d_scalars, n, true);
   if (rc == MSM377_OK) rc = check_short_args(ctx, sbytes, bits);
   if (rc == MSM377_OK) rc = refuse_mont_short(ctx);
-  if (rc) return rc;
-  if (n == 0) {
-    identity_wire(out_xy);
-    return MSM377_OK;
-  }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  ctx->resident.clear();
-  rc = import_inputs(ctx, &d_points, &d_scalars, n, sbytes / 4);  // (native point forms only)
-  if (rc) return rc;
-  int form = ctx->g1_form == 1 ? TABLE_TE : TABLE_XYZZ;  // never the GLV front end
-  if (form == TABLE_TE && ctx->te_affine_msm && n >= ctx->affine_min_points) {  // per-call affine records, as in g1_msm_device
-    form = TABLE_TE_AFFINE;
-    rc = affine_convert_begin(ctx, (const uint32_t*)d_points, n);
-    if (rc) return rc;
-    ctx->before_accumulate = [ctx, n]() -> int { return affine_convert_finish(ctx, ctx->d_bases, n, true); };
-    rc = g1_short_table_msm(ctx, d_scalars, n, form, sbytes, bits, out_xy);
-    ctx->before_accumulate = nullptr;
-  } else {
-    rc = convert_table(ctx, (const uint32_t*)d_points, n, form);
-    if (rc) return rc;
-    rc = g1_short_table_msm(ctx, d_scalars, n, form, sbytes, bits, out_xy);
-  }
-  if (rc != RC_TE_FALLBACK) return rc;
-  rc = convert_table(ctx, (const uint32_t*)d_points, n, TABLE_XYZZ);
-  if (rc) return rc;
-  return g1_short_table_msm(ctx, d_scalars, n, TABLE_XYZZ, sbytes, bits, out_xy);
+  return rc ? rc : g1_device_flow(ctx, d_points, d_scalars, n, out_xy, sbytes, bits);
 }
 
-// Host buffers: the compact scalars go up first (n x scalar_bytes), decomposition, sort and work lists run while the
-// points follow on the upload thread; the conversion is launched from the hook, right before the accumulation is
-// queued -- the unchunked schedule of g1_msm (a chunked short upload is not implemented).
+// Host buffers: the compact scalars go up first (n x scalar_bytes), always in one piece (a chunked short upload is not
+// implemented), on affine records from affine_min_points on.
 int g1_msm_short(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint32_t sbytes, uint32_t bits, uint8_t out_xy[96]) {
   if (!ctx || !out_xy) return MSM377_EINVAL;
   ctx->err.clear();
@@ -1444,27 +1401,9 @@ int g1_msm_short(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars,
     return rc ? rc : g1_msm_short_device(ctx, native_points(ctx), native_scalars(ctx), n, sbytes, bits, out_xy);
   }
   ctx->resident.clear();
-  const uint32_t* d_pt = ctx->d_raw_points;
   const bool te = ctx->g1_form == 1;
   const bool affine = te && ctx->te_affine_msm && n >= ctx->affine_min_points;
-  const int form = !te ? TABLE_XYZZ : affine ? TABLE_TE_AFFINE : TABLE_TE;
-  rc = h2d_staged(ctx, ctx->d_raw_scalars, scalars, n * sbytes, (size_t)ctx->cap * 96);
-  if (rc) return rc;
-  int up_rc = MSM377_OK;
-  HipFail up_fail;
-  std::thread upload([&] { up_rc = hipSetDevice(ctx->device) == hipSuccess ? h2d_staged(ctx, ctx->d_raw_points, points, n * 96, 0, &up_fail) : MSM377_EHIP; });
-  ctx->before_accumulate = [&]() -> int {
-    if (upload.joinable()) upload.join();
-    if (up_rc) return up_fail.record(ctx, up_rc);
-    return convert_table(ctx, d_pt, n, form);  // (TABLE_TE_AFFINE: both phases of the batched conversion back to back)
-  };
-  rc = g1_short_table_msm(ctx, ctx->d_raw_scalars, n, form, sbytes, bits, out_xy);
-  ctx->before_accumulate = nullptr;
-  if (upload.joinable()) upload.join();  // an error before the hook ran
-  if (rc != RC_TE_FALLBACK) return rc;
-  rc = convert_table(ctx, d_pt, n, TABLE_XYZZ);
-  if (rc) return rc;
-  return g1_short_table_msm(ctx, ctx->d_raw_scalars, n, TABLE_XYZZ, sbytes, bits, out_xy);
+  return g1_host_flow(ctx, points, scalars, n, !te ? TABLE_XYZZ : affine ? TABLE_TE_AFFINE : TABLE_TE, out_xy, sbytes, bits);
 }
 
 int scalars_width_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n, uint32_t sbytes, uint32_t* bits_out) {
@@ -1496,6 +1435,35 @@ int scalars_width_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n, uin
 }
 
 // ---- Edwards-BLS12 (BASELINE.json config 3): same pipeline, EdDev policy ----
+namespace {
+// equal_windows: the rerun of a chunked upload whose scalars did not fit the even geometry.
+int ed_device_flow(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint8_t out_xy[64], bool equal_windows) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->resident.clear();
+  int rc = convert_bases<EdDev>(ctx, (const uint32_t*)d_points, n);
+  if (rc) return rc;
+  TailArm arm(ctx);
+  arm.at_start(n);
+  Phase ph;
+  ph.zc_out = true;
+  ph.plan = equal_windows || ctx->capture == 1 ? plan_equal16(ED_TAIL) : plan_whole16(ctx, ED_TAIL);
+  for (;;) {
+    rc = enqueue_windows<EdDev>(ctx, (const uint32_t*)d_scalars, n, 0, 0, ph);
+    if (rc) return rc;
+    arm.after_accumulation();
+    rc = wait_windows(ctx, 0);
+    if (rc) return rc;
+    if (geometry_refused(ph.plan, ctx->h_err[0])) {  // a scalar of 2^253 and more: sixteen equal windows
+      ctx->geometry_reruns++;
+      ph.plan = next_plan(ph.plan);
+      continue;
+    }
+    rc = collect_windows(ctx, 0);
+    return rc ? rc : run_tail(ctx, ph.plan, ctx->h_partials, out_xy);
+  }
+}
+}  // namespace
+
 int ed_msm_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint8_t out_xy[64]) {
   if (!out_xy) return MSM377_EINVAL;
   int rc = check_args(ctx, d_points, d_scalars, n, true);
@@ -1505,39 +1473,7 @@ int ed_msm_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, 
     out_xy[32] = 1;
     return MSM377_OK;
   }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  ctx->resident.clear();
-  rc = convert_bases<EdDev>(ctx, (const uint32_t*)d_points, n);
-  if (rc) return rc;
-  TailArm arm(ctx);
-  arm.at_start(n);
-  bool even = ctx->even_windows && ctx->capture != 1 && !ctx->ed_equal_windows_once;
-  ctx->ed_equal_windows_once = false;
-  for (;;) {
-    Phase ph;
-    ph.zc_out = true;
-    ph.even = even;
-    rc = enqueue_windows<EdDev>(ctx, (const uint32_t*)d_scalars, n, 0, MSM377_NUM_WINDOWS, 0, false, ph);
-    if (rc) return rc;
-    arm.after_accumulation();
-    if (ctx->zc_active) {
-      rc = wait_zero_copy_out(ctx);
-      if (rc) return rc;
-    } else {
-      HIP_TRY(ctx, hipEventSynchronize(ctx->done_ev[0]));
-    }
-    if (even && (ctx->h_err[0] & ERR_NARROW_RANGE) && !(ctx->h_err[0] & ERR_SCALAR)) {  // a scalar of 2^253 and more: sixteen equal windows
-      even = false;
-      ctx->geometry_reruns++;
-      continue;
-    }
-    rc = finish_windows(ctx, 0);
-    if (rc) return rc;
-    auto t0 = std::chrono::steady_clock::now();
-    rc = ed_tail(ctx, ctx->h_partials, out_xy, even ? (int)EVEN_FROM : 0);
-    time_tail(ctx, t0);
-    return rc;
-  }
+  return ed_device_flow(ctx, d_points, d_scalars, n, out_xy, false);
 }
 
 int ed_msm(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint8_t out_xy[64]) {
@@ -1551,21 +1487,16 @@ int ed_msm(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint6
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   ctx->resident.clear();  // (both paths upload into d_raw_points)
   if (n >= ctx->upload_chunk_min) {  // chunks of points, like g1_msm: a chunk computes while the next one uploads
-    int rc = run_chunked_upload<EdDev>(ctx, points, scalars, n);
+    const WindowPlan plan = plan_whole16(ctx, ED_TAIL);
+    int rc = run_chunked_upload<EdDev>(ctx, points, scalars, n, plan);
+    if (rc == MSM377_OK) rc = wait_windows(ctx, 0);
     if (rc) return rc;
-    HIP_TRY(ctx, hipEventSynchronize(ctx->done_ev[0]));
-    const bool even = upload_even<EdDev>(ctx);
-    if (even && (ctx->h_err[0] & ERR_NARROW_RANGE) && !(ctx->h_err[0] & ERR_SCALAR)) {  // everything is on the device: once more in one piece
-      ctx->ed_equal_windows_once = true;
+    if (geometry_refused(plan, ctx->h_err[0])) {  // everything is on the device: once more in one piece
       ctx->geometry_reruns++;
-      return ed_msm_device(ctx, ctx->d_raw_points, ctx->d_raw_scalars, n, out_xy);
+      return ed_device_flow(ctx, ctx->d_raw_points, ctx->d_raw_scalars, n, out_xy, true);
     }
-    rc = finish_windows(ctx, 0);
-    if (rc) return rc;
-    auto t0 = std::chrono::steady_clock::now();
-    rc = ed_tail(ctx, ctx->h_partials, out_xy, even ? (int)EVEN_FROM : 0);
-    time_tail(ctx, t0);
-    return rc;
+    rc = collect_windows(ctx, 0);
+    return rc ? rc : run_tail(ctx, plan, ctx->h_partials, out_xy);
   }
   int rc = h2d_staged(ctx, ctx->d_raw_points, points, n * 64, 0);
   if (rc == MSM377_OK) rc = h2d_staged(ctx, ctx->d_raw_scalars, scalars, n * 32, (size_t)ctx->cap * 96);
@@ -1613,7 +1544,7 @@ int g1_set_bases_device(msm377_ctx* ctx, const void* d_points, uint64_t n) {
 static int build_bases(msm377_ctx* ctx, const void* d_points, uint64_t n, uint32_t flagged) {
   int rc = check_base_set(ctx, d_points, n);  // opt-in (msm377_ctx_set_base_checks)
   if (rc) return rc;
-  int form = pick_form(ctx, n);
+  int form = pick_form(ctx);
   if (form == TABLE_TE) form = TABLE_TE_AFFINE;  // resident: affine records by the batched inversion, once
   rc = convert_table(ctx, (const uint32_t*)d_points, n, form);
   if (rc) return rc;
@@ -1698,10 +1629,8 @@ int g1_set_bases_precomputed(msm377_ctx* ctx, const uint8_t* points, uint64_t n)
   return set_bases_from_host(ctx, points, n, g1_set_bases_precomputed_device);
 }
 
-int g1_msm_fixed_base_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n, uint8_t out_xy[96]) {
-  if (!out_xy) return MSM377_EINVAL;
-  int rc = check_args(ctx, nullptr, d_scalars, n, false);
-  if (rc) return rc;
+// Whatever the last set-bases call left resident serves, at full width or (sbytes != 0) over scalars of a declared width.
+static int g1_fixed_base_flow(msm377_ctx* ctx, const void* d_scalars, uint64_t n, uint8_t out_xy[96], uint32_t sbytes, uint32_t bits) {
   if (n > ctx->resident.n) {
     ctx->err = "fixed-base MSM needs g1_set_bases with at least n points first";
     return MSM377_ESTATE;
@@ -1715,46 +1644,29 @@ int g1_msm_fixed_base_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n,
     (void)hipEventRecord(ctx->ev[MSM377_STAGE_CONVERT][0], ctx->stream);
     (void)hipEventRecord(ctx->ev[MSM377_STAGE_CONVERT][1], ctx->stream);
   }
+  // (records 0 .. n-1 of a GLV table are the plain points: a short call reads those and never the phi half)
+  auto form = [&] { return sbytes && ctx->resident.form == TABLE_XYZZ_GLV ? (int)TABLE_XYZZ : resident_form(ctx, n); };
   const uint32_t* sc = nullptr;  // d_scalars, or their import: Montgomery scalars, the zeroed scalars of flagged bases
-  rc = import_scalars(ctx, d_scalars, n, 8, ctx->resident.flagged ? ctx->resident.inf_mask : nullptr, &sc);
+  int rc = import_scalars(ctx, d_scalars, n, sbytes ? sbytes / 4 : 8, ctx->resident.flagged ? ctx->resident.inf_mask : nullptr, &sc);
   if (rc) return rc;
-  rc = g1_table_msm(ctx, sc, n, resident_form(ctx, n), out_xy);
+  rc = g1_table_msm(ctx, sc, n, form(), out_xy, sbytes, bits);
   if (rc != RC_TE_FALLBACK) return rc;
   rc = resident_table_to_weierstrass(ctx);
-  if (rc) return rc;
-  return g1_table_msm(ctx, sc, n, resident_form(ctx, n), out_xy);
+  return rc ? rc : g1_table_msm(ctx, sc, n, form(), out_xy, sbytes, bits);
 }
 
-// The same over scalars of a declared width (g1_short_table_msm): whatever the last set-bases call left resident serves.
+int g1_msm_fixed_base_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n, uint8_t out_xy[96]) {
+  if (!out_xy) return MSM377_EINVAL;
+  const int rc = check_args(ctx, nullptr, d_scalars, n, false);
+  return rc ? rc : g1_fixed_base_flow(ctx, d_scalars, n, out_xy, 0, 0);
+}
+
 int g1_msm_fixed_base_short_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n, uint32_t sbytes, uint32_t bits, uint8_t out_xy[96]) {
   if (!out_xy) return MSM377_EINVAL;
   int rc = check_args(ctx, nullptr, d_scalars, n, false);
   if (rc == MSM377_OK) rc = check_short_args(ctx, sbytes, bits);
   if (rc == MSM377_OK) rc = refuse_mont_short(ctx);
-  if (rc) return rc;
-  if (n > ctx->resident.n) {
-    ctx->err = "fixed-base MSM needs g1_set_bases with at least n points first";
-    return MSM377_ESTATE;
-  }
-  if (n == 0) {
-    identity_wire(out_xy);
-    return MSM377_OK;
-  }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (ctx->timing == 1) {  // no conversion in this mode
-    (void)hipEventRecord(ctx->ev[MSM377_STAGE_CONVERT][0], ctx->stream);
-    (void)hipEventRecord(ctx->ev[MSM377_STAGE_CONVERT][1], ctx->stream);
-  }
-  // (records 0 .. n-1 of a GLV table are the plain points: the short path reads those and never the phi half)
-  auto form = [&] { return ctx->resident.form == TABLE_XYZZ_GLV ? (int)TABLE_XYZZ : ctx->resident.form; };
-  const uint32_t* sc = nullptr;  // (a masked copy when the resident set has flagged points)
-  rc = import_scalars(ctx, d_scalars, n, sbytes / 4, ctx->resident.flagged ? ctx->resident.inf_mask : nullptr, &sc);
-  if (rc) return rc;
-  rc = g1_short_table_msm(ctx, sc, n, form(), sbytes, bits, out_xy);
-  if (rc != RC_TE_FALLBACK) return rc;
-  rc = resident_table_to_weierstrass(ctx);
-  if (rc) return rc;
-  return g1_short_table_msm(ctx, sc, n, form(), sbytes, bits, out_xy);
+  return rc ? rc : g1_fixed_base_flow(ctx, d_scalars, n, out_xy, sbytes, bits);
 }
 
 // `batch` MSMs of n scalars each against the table resident in (or lent to, twin_borrow) `ctx`, on ctx's own stream and
@@ -1770,22 +1682,12 @@ static int fixed_base_batch_share(msm377_ctx* ctx, const void* d_scalars, uint64
   const uint32_t* sb = nullptr;
   const int form = resident_form(ctx, n);
   const bool glv = form == TABLE_XYZZ_GLV, te = form_is_te(form);
-  const bool wide = wide_table(ctx->resident);
-  const uint32_t W = wide ? 1u : glv ? GLV_WINDOWS : (uint32_t)MSM377_NUM_WINDOWS;  // window slots of a call
-  Phase table_phase;
-  if (form == TABLE_TE_PRECOMP) {
-    table_phase.table = ctx->resident.table;
-    table_phase.table_stride = ctx->resident.n;
-  }
-  if (wide) {
-    table_phase.wide = true;
-    table_phase.cbits = WIDE_BITS;
-    table_phase.bucket_log = WIDE_LOG;
-  }
-  const bool even = te && form != TABLE_TE_PRECOMP && ctx->even_windows;  // (the Weierstrass forms keep sixteen equal windows)
-  table_phase.even = even;
-  const int tail_cbits = wide ? (int)WIDE_BITS : 16, tail_planes = wide ? (int)WIDE_LOG : 15, tail_short = even ? (int)EVEN_FROM : 0;
-  const int W_tail = form == TABLE_TE_PRECOMP ? 1 : (int)W;  // window records the host combines per MSM
+  Phase ph;  // every MSM of the share runs this plan; its records are combined on this thread, beside the GPU
+  ph.plan = wide_table(ctx->resident)    ? plan_wide13(ctx->resident.table, ctx->resident.n)
+            : form == TABLE_TE_PRECOMP ? folded_behind_table(plan_equal16(TE_TAIL), ctx->resident.table, ctx->resident.n)
+            : glv                      ? plan_glv8()
+                                       : plan_whole16(ctx, te ? TE_TAIL : XYZZ_TAIL);
+  ph.plan.on_caller = true;
   std::vector<uint32_t> redo;  // elements whose scalars fall outside the GLV range: rerun plain afterwards
   std::vector<uint32_t> redo_wide;  // elements with a scalar of 2^253 and more on the wide table or the even windows: rerun one by one (g1_table_msm falls back)
   bool te_fallback = false;
@@ -1795,37 +1697,30 @@ static int fixed_base_batch_share(msm377_ctx* ctx, const void* d_scalars, uint64
     if (b < batch && !te_fallback) {
       rc = scalars_of(b, &sb);
       if (rc) return rc;
-      rc = (form == TABLE_TE_AFFINE || form == TABLE_TE_PRECOMP) ? enqueue_windows<TeDev, TeAffBase>(ctx, sb, n, 0, W, (int)(b & 1), false, table_phase)
-           : te                    ? enqueue_windows<TeDev>(ctx, sb, n, 0, W, (int)(b & 1), false, table_phase)
-                                   : enqueue_windows<G1Dev>(ctx, sb, n, 0, W, (int)(b & 1), glv);
+      rc = enqueue_form(ctx, form, sb, n, (int)(b & 1), ph);
       if (rc) return rc;
     }
     if (b > 0) {
       const int slot = (int)((b - 1) & 1);
-      HIP_TRY(ctx, hipEventSynchronize(ctx->done_ev[slot]));
-      if (te && !te_fallback && (ctx->h_err[slot] & ERR_TE_ANY)) {
+      rc = wait_windows(ctx, slot);
+      if (rc) return rc;
+      const int err = ctx->h_err[slot];
+      if (te && !te_fallback && (err & ERR_TE_ANY)) {
         te_fallback = true;
-        note_fallback(ctx, (uint32_t)(ctx->h_err[slot] & ERR_TE_ANY));
+        note_fallback(ctx, (uint32_t)(err & ERR_TE_ANY));
       }
       if (te_fallback) continue;
-      if (glv && (ctx->h_err[slot] & ERR_GLV_RANGE)) {
-        redo.push_back(b - 1);
+      if (geometry_refused(ph.plan, err)) {
+        (glv ? redo : redo_wide).push_back(b - 1);
+        if (!glv) ctx->geometry_reruns++;
         continue;
       }
-      if ((wide || even) && (ctx->h_err[slot] & ERR_NARROW_RANGE) && !(ctx->h_err[slot] & ERR_SCALAR)) {
-        redo_wide.push_back(b - 1);
-        ctx->geometry_reruns++;
-        continue;
-      }
-      rc = finish_windows(ctx, slot);
-      if (rc) return rc;
-      if (te) {
-        if (teh_combine(ctx->h_partials + (size_t)slot * SLOT_WORDS, W_tail, out_xy + (size_t)96 * (b - 1), tail_cbits, tail_planes, tail_short)) {
-          te_fallback = true;
-          note_fallback(ctx, MSM377_FB_TAIL);
-        }
-      } else
-        g1h_combine(ctx->h_partials + (size_t)slot * SLOT_WORDS, W, out_xy + (size_t)96 * (b - 1));
+      rc = collect_windows(ctx, slot);
+      if (rc == MSM377_OK) rc = run_tail(ctx, ph.plan, ctx->h_partials + (size_t)slot * SLOT_WORDS, out_xy + (size_t)96 * (b - 1));
+      if (rc == RC_TE_FALLBACK)
+        te_fallback = true;
+      else if (rc)
+        return rc;
     }
   }
   if (te_fallback) {  // an exceptional case of the Edwards law somewhere in the batch: the caller rebuilds the table and reruns
@@ -1977,6 +1872,8 @@ int window_partials(msm377_ctx* ctx, const void* d_points, const void* d_scalars
     }
     return MSM377_OK;
   };
+  Phase ph;
+  ph.plan = plan_equal16(TE_TAIL, win_count);  // (a shard of sixteen equal windows; the records go to the caller, no tail here)
   if (ctx->g1_form == 1) {  // twisted Edwards form; k_gather_partials tags the records (fp64_host.hpp TE_RECORD_TAG)
     // Affine base records (7-product additions, batched inversion) once a point takes part in enough additions to pay for
     // its ~9 extra conversion products: windows x points >= 2^24 -- e.g. the 8 windows a rank of a 2-GPU run owns at 2^21
@@ -1985,29 +1882,28 @@ int window_partials(msm377_ctx* ctx, const void* d_points, const void* d_scalars
     if (affine) {
       rc = affine_convert_begin(ctx, (const uint32_t*)d_points, n);
       if (rc) return rc;
-      ctx->before_accumulate = [ctx, n]() -> int { return affine_convert_finish(ctx, ctx->d_bases, n, true); };
-      rc = enqueue_windows<TeDev, TeAffBase>(ctx, (const uint32_t*)d_scalars, n, win_begin, win_count, 0);
+      ctx->before_accumulate = [ctx, n]() -> int { return affine_convert_finish(ctx, ctx->d_bases, n); };
+      rc = enqueue_windows<TeDev, TeAffBase>(ctx, (const uint32_t*)d_scalars, n, win_begin, 0, ph);
       ctx->before_accumulate = nullptr;
     } else {
       rc = convert_bases<TeDev>(ctx, (const uint32_t*)d_points, n);
       if (rc) return rc;
-      rc = enqueue_windows<TeDev>(ctx, (const uint32_t*)d_scalars, n, win_begin, win_count, 0);
+      rc = enqueue_windows<TeDev>(ctx, (const uint32_t*)d_scalars, n, win_begin, 0, ph);
     }
+    if (rc == MSM377_OK) rc = wait_windows(ctx, 0);
     if (rc) return rc;
-    HIP_TRY(ctx, hipEventSynchronize(ctx->done_ev[0]));
     if ((ctx->h_err[0] & ERR_TE_ANY) == 0) {
-      rc = finish_windows(ctx, 0);
-      if (rc) return rc;
-      return deliver();
+      rc = collect_windows(ctx, 0);
+      return rc ? rc : deliver();
     }
     note_fallback(ctx, (uint32_t)(ctx->h_err[0] & ERR_TE_ANY));
     // an exceptional case of the Edwards law in THESE windows: they alone rerun below, untagged
   }
   rc = convert_bases<G1Dev>(ctx, (const uint32_t*)d_points, n);
-  if (rc) return rc;
-  rc = run_windows<G1Dev>(ctx, (const uint32_t*)d_scalars, n, win_begin, win_count);
-  if (rc) return rc;
-  return deliver();
+  if (rc == MSM377_OK) rc = enqueue_windows<G1Dev>(ctx, (const uint32_t*)d_scalars, n, win_begin, 0, ph);
+  if (rc == MSM377_OK) rc = wait_windows(ctx, 0);
+  if (rc == MSM377_OK) rc = collect_windows(ctx, 0);
+  return rc ? rc : deliver();
 }
 
 int g1_glv_window_partials_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t win_begin,
@@ -2029,14 +1925,16 @@ int g1_glv_window_partials_device(msm377_ctx* ctx, const void* d_points, const v
   if (rc) return rc;
   rc = convert_bases_g1(ctx, (const uint32_t*)d_points, n, true);
   if (rc) return rc;
-  rc = enqueue_windows<G1Dev>(ctx, (const uint32_t*)d_scalars, n, win_begin, win_count, 0, true);
+  Phase ph;
+  ph.plan = plan_glv8(win_count);
+  rc = enqueue_windows<G1Dev>(ctx, (const uint32_t*)d_scalars, n, win_begin, 0, ph);
+  if (rc == MSM377_OK) rc = wait_windows(ctx, 0);
   if (rc) return rc;
-  HIP_TRY(ctx, hipEventSynchronize(ctx->done_ev[0]));
-  if (ctx->h_err[0] & 2) {
+  if (geometry_refused(ph.plan, ctx->h_err[0])) {
     ctx->err = "a scalar is outside the GLV range; use the plain window path";
     return MSM377_EGLVRANGE;
   }
-  rc = finish_windows(ctx, 0);
+  rc = collect_windows(ctx, 0);
   if (rc) return rc;
   memcpy(partials_out, ctx->h_partials, (size_t)win_count * MSM377_G1_WINDOW_PARTIAL_BYTES);
   return MSM377_OK;

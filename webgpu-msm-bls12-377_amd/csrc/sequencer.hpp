@@ -50,6 +50,10 @@ void twin_return(msm377_ctx* ctx);  // takes back the resident bases a batch cal
 
 // Shared with capi.hip (argument checks of the host-only entry points, the stage read-back).
 bool hip_ok(msm377_ctx* ctx, int hip_error, const char* what);
+#define HIP_TRY(ctx, call)                                                   \
+  do {                                                                       \
+    if (!msm377::eng::hip_ok((ctx), (int)(call), #call)) return MSM377_EHIP; \
+  } while (0)
 
 }  // namespace eng
 }  // namespace msm377
