@@ -1,5 +1,5 @@
 """The launch plan of the bucket reduction's column kernel (csrc/kernels/reduce.hpp k_tree_columns, sequencer.hip
-enqueue_windows) as a plain model: lanes, their (lower, upper) pairs and the exchanges between steps, exactly as the kernel
+enqueue_reduce) as a plain model: lanes, their (lower, upper) pairs and the exchanges between steps, exactly as the kernel
 indexes them, against the per-level plan of k_tree_step.  For every bucket_log the stage serves and every tail_from:
 
   * the multiset of (level, lower index, upper index) additions of the column plan equals the per-level plan's;

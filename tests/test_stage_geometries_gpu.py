@@ -495,3 +495,41 @@ def test_capture_off_leaves_the_context_as_it_was(engine, oracle, golden, pool):
         assert engine.last_geometry() == (16, 15)
     finally:
         engine.set_stage_capture(0)
+
+
+# ---- what the driver of a pass owns: the bookkeeping behind the last stage ----
+def test_shard_call_leaves_nothing_describable(oracle, pool):
+    """Capture mode 2 on a context of 2^12 points: a window-partials call for windows [3, 5) records its geometry (two
+    slots of 2^15 buckets) and no stage layout -- the as-run read-back refuses -- and the whole call right after is
+    describable again, with the slots its own pass ran."""
+    n = 2049
+    pts, ks = pool[: 96 * n], R.encode_scalars(R.rand_scalars(0x5A4D, n))
+    d_p, d_s = dev(pts), dev(ks)
+    eng = msm.MsmEngine(1 << 12)
+    try:
+        eng.set_stage_capture(2)
+        eng.window_partials_device(d_p.data_ptr(), d_s.data_ptr(), n, 3, 2)
+        with pytest.raises(msm.MsmError) as e:
+            eng.read_stage_ex(0)
+        assert e.value.code == ESTATE
+        assert eng.last_geometry() == (2, 15)
+        assert eng.msm_device(d_p.data_ptr(), d_s.data_ptr(), n) == util.oracle_msm(oracle, pts, ks)
+        info, _ = eng.read_stage_ex(0, want=())
+        assert info.slots == eng.last_geometry()[0]
+    finally:
+        eng.close()
+
+
+def test_chunked_host_call_reports_the_geometry_of_its_back_phase(oracle, pool):
+    """MSM377_UPLOAD_CHUNK_MIN=100, capture off: the chunks' front phases accumulate into one set of buckets and ONE back
+    phase reduces them; last_geometry() is that phase's -- sixteen slots of 2^15 buckets on the chunked route at this n."""
+    n = 2049
+    pts, ks = pool[: 96 * n], R.encode_scalars(R.rand_scalars(0xC4A2, n))
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setenv("MSM377_UPLOAD_CHUNK_MIN", "100")
+        eng = msm.MsmEngine(1 << 12)
+    try:
+        assert eng.msm(pts, ks) == util.oracle_msm(oracle, pts, ks)
+        assert eng.last_geometry() == (16, 15)
+    finally:
+        eng.close()

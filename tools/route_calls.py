@@ -153,4 +153,33 @@ expect(chunked.ed_msm_device(d_ed.data_ptr(), sp, N), ed_exp, "Edwards-BLS12 dev
 expect(chunked.ed_msm(ed_pts, ks), ed_exp, "Edwards-BLS12 chunked")
 expect(chunked.ed_msm(ed_pts, ks_big), ed_exp_big, "Edwards-BLS12 chunked, big scalar")
 chunked.close()
+
+# launch shapes decided inside the pass (sequencer.hip launch_record and its stage functions): one knob per context
+for knob, value, paths in (
+    ("MSM377_REDUCE_COLUMNS", 0, ("main", "narrow")),  # one launch per reduction level: k_tree_step / k_tree_step_quad
+    ("MSM377_TAIL_LDS", 0, ("main",)),                 # k_reduce_tail in global memory
+    ("MSM377_TAIL_FROM", 4, ("main",)),                # a stretch of buckets beyond the LDS of a CU: k_reduce_tail
+    ("MSM377_TAIL_FROM", 6, ("main",)),                # 104 KB of LDS: the dynamic-LDS attribute in front of k_reduce_tail_lds
+    ("MSM377_SORT_ELEM", 4, ("main",)),
+    ("MSM377_NARROW_QUAD_ITEMS", 0, ("narrow",)),
+    ("MSM377_COOP_THREADS", 1048576, ("main",)),
+    ("MSM377_ZERO_COPY_OUT", 0, ("narrow",)),
+):
+    knobbed = engine(**{knob: value})
+    for path in paths:
+        knobbed.set_narrow_max(0 if path == "main" else 1 << 16)
+        expect(knobbed.msm_device(pp, sp, N), exp, "%s=%d, %s path" % (knob, value, path))
+    knobbed.close()
+
+# a short call on the narrow path; a shard of three windows beside the records of a whole call; stage timing
+plain = engine()
+expect(plain.msm_short_device(pp, d_64.data_ptr(), N, 8, 64), exp64, "short device, narrow path")
+W = len(plain.window_partials_device(pp, sp, N, 0, 1))
+whole, shard = plain.window_partials_device(pp, sp, N, 0, 16), plain.window_partials_device(pp, sp, N, 5, 3)
+expect(plain.combine_partials(whole[: 5 * W] + shard + whole[8 * W :]), exp, "window partials [5, 8)")
+for mode in (1, 2):
+    plain.set_timing(mode)
+    expect(plain.msm_device(pp, sp, N), exp, "timing %d" % mode)
+plain.set_timing(0)
+plain.close()
 print("ok")

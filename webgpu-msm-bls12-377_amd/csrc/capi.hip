@@ -270,7 +270,7 @@ int msm377_ctx_set_stage_capture(msm377_ctx* ctx, int enabled) {
 int msm377_g1_read_stage(msm377_ctx* ctx, uint32_t slot, uint16_t* digits, uint32_t* row_ptr, uint32_t* val_idx, uint32_t* buckets) {
   if (!ctx) return MSM377_EINVAL;
   // capture mode 1 only: the sizes below are those of its route; under mode 2 a call lays its stages out as it runs
-  if (ctx->capture != 1 || ctx->last_n == 0 || slot >= ctx->last_wc || ctx->last_form < 0 || ctx->last_glv) {
+  if (ctx->capture != 1 || ctx->last_n == 0 || slot >= ctx->last_geom_windows || ctx->last_form < 0 || ctx->last_glv) {
     ctx->err = "no captured stage data for that window slot (capture mode 2 is read with msm377_g1_read_stage_ex)";
     return MSM377_ESTATE;
   }
@@ -293,7 +293,7 @@ int msm377_g1_read_stage(msm377_ctx* ctx, uint32_t slot, uint16_t* digits, uint3
   return MSM377_OK;
 }
 
-// The as-run read-back: sizes, biases and pointers are those enqueue_windows recorded at its launches (StageLayout);
+// The as-run read-back: sizes, biases and pointers are those enqueue_decompose recorded at its launch (StageLayout);
 // nothing about the geometry is worked out here.
 int msm377_g1_read_stage_ex(msm377_ctx* ctx, uint32_t slot, msm377_stage_info* info, void* digits, uint32_t* row_ptr, uint32_t* val_idx, uint32_t* buckets) {
   if (!ctx) return MSM377_EINVAL;

@@ -78,7 +78,7 @@ struct WideBuffers {
   }
 };
 
-// What the last enqueue_windows launched with, for msm377_g1_read_stage_ex: written next to the launches themselves
+// What the last enqueue_decompose launched with, for msm377_g1_read_stage_ex: written next to the launch itself
 // (sequencer.hip) from the values they were given, so that the read-back describes the kernels' arguments and not a second
 // derivation of them.  valid: a whole call (front and back phase, from window 0) ran to its end under stage capture.
 struct StageLayout {
@@ -148,12 +148,11 @@ struct msm377_ctx {
   hipStream_t copy_stream[8] = {};
   // state
   uint64_t last_n = 0;
-  uint32_t last_wc = 0;
-  uint32_t last_geom_windows = 0, last_geom_log = 0;  // window slots and bucket_log of the last enqueue (msm377_ctx_get_last_geometry)
+  uint32_t last_geom_windows = 0, last_geom_log = 0;  // window slots and bucket_log of the last enqueue (msm377_ctx_get_last_geometry, msm377_g1_read_stage)
   uint32_t last_sort_elem = 0;  // bytes per sort_temp element of the last enqueue's sort, 0: the narrow path (msm377_ctx_get_last_sort_elem_bytes)
   int last_form = -1;  // MSM377_STAGE_FORM_* of the buckets the last call left (stage read-backs)
   int capture = 0;  // msm377_ctx_set_stage_capture: 0 off, 1 the sixteen-equal-windows route of msm377_g1_read_stage, 2 as run
-  StageLayout stage;  // what the last enqueue_windows launched with (msm377_g1_read_stage_ex)
+  StageLayout stage;  // what the last enqueue_decompose launched with; valid is enqueue_windows' (msm377_g1_read_stage_ex)
   // Zero-copy output of the full-MSM path (k_gather_partials, wait_zero_copy_out); MSM377_ZERO_COPY_OUT=0: D2H copies + event.
   int zc_out = 1;
   bool zc_active = false;         // the call being enqueued / waited for uses it
@@ -172,7 +171,7 @@ struct msm377_ctx {
   // MSM377_NARROW_TAIL_FROM: tail_from of the narrow-window path (2048 buckets per window).  Reduce stage at 2^12 with
   // 7 / 5 / 4 / 3 / 2: 0.106 / 0.099 / 0.096 / 0.101 / 0.122 ms (profiles/r02_final/ab_narrow_tree.txt).
   uint32_t narrow_tail_from = 4;
-  uint32_t narrow_seg = 0;  // MSM377_NARROW_SEG (>= NARROW_SEG: the buffers are sized for that); 0 = by input size (enqueue_windows)
+  uint32_t narrow_seg = 0;  // MSM377_NARROW_SEG (>= NARROW_SEG: the buffers are sized for that); 0 = by input size (launch_record)
   uint64_t narrow_quad_items = 100000;  // MSM377_NARROW_QUAD_ITEMS: most work items k_accumulate_quad is used for (0: a thread per work item, like the main path)
   // First level of the single-launch tail of the reduction (k_reduce_tail); MSM377_TAIL_FROM, 15 = one launch per level throughout.
   uint32_t tail_from = 7;  // measured (tools/ab_knobs.py, 2^20): 15: 2.874 ms, 7: 2.842, 6: 2.885, 5: 2.916, 4: 3.062
@@ -191,7 +190,7 @@ struct msm377_ctx {
   uint64_t upload_chunk_min = 1ull << 18;  // msm377_g1_msm: inputs of at least this many points upload and run as two chunks (MSM377_UPLOAD_CHUNK_MIN)
   uint32_t upload_chunks = 4;              // chunks of the host-buffer upload (MSM377_UPLOAD_CHUNKS, 2..7): 2: 5.07, 3: 4.89, 4-6: 4.70, 8: 4.95 ms at 2^20 (round 2)
   uint32_t upload_split_pct = 30;          // share of the points in the first chunk (MSM377_UPLOAD_SPLIT, 5..90)
-  std::function<int()> before_accumulate;  // host-buffer entry point: joins the point upload and launches the base conversion (enqueue_windows)
+  std::function<int()> before_accumulate;  // host-buffer entry point: joins the point upload and launches the base conversion (enqueue_accumulate)
   TailPool tail_pool;
   int tail_threads = 6;               // MSM377_TAIL_THREADS: threads of the host tail (1..8, tail_horner_mt)
   // MSM377_TAIL_SPIN_US: how long at most the tail workers poll for their job after a call has armed them (TailPool;

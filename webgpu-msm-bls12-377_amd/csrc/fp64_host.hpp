@@ -497,7 +497,7 @@ inline void g1h_to_wire(const G1H::XYZZ& p, uint8_t out[96]) {
 // front end).  partials layout: [window][point][48 words], point 0 =
 // Sum_w, point 1 + l = Plane_{w,l}.
 // Bit positions [lo, hi) of the chain only (position b = 16 w + l): sum_b 2^(b - lo) record_b.
-// Window geometry of the chain (sequencer.hip Phase::even): short_from = 0 -- every window is cbits wide; otherwise the
+// Window geometry of the chain (sequencer.hip WindowPlan::recode): short_from = 0 -- every window is cbits wide; otherwise the
 // windows from short_from on are one bit shorter (common.hpp even_offset: thirteen 16-bit and three 15-bit windows).
 inline void tail_position(int b, int cbits, int short_from, int& w, int& l) {
   const int full = cbits * short_from;

@@ -310,7 +310,7 @@ __global__ void __launch_bounds__(256, 2) k_accumulate_quad(const uint32_t* __re
 }
 
 // Quad per split row: bucket += its overflow partials.
-// Short-scalar calls (sequencer.hip Phase::short_bytes): the top window holds a few bits or carries only, so it is a
+// Short-scalar calls (sequencer.hip WindowPlan::short_bytes): the top window holds a few bits or carries only, so it is a
 // handful of rows of up to n / 2 entries -- thousands of overflow partials per row, which k_merge_split_rows_quad would
 // add one after the other (32 768 serial additions for the carry row of 2^20 32-bit scalars: 170 ms).  Here the rows of
 // that window slot with LONG_ROW_PARTIALS partials and more are folded first: a workgroup per row (rows are dealt

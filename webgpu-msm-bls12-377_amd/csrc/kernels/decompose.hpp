@@ -38,7 +38,7 @@ __device__ __forceinline__ uint32_t key_range(uint32_t key, uint32_t s) {
 // Only windows [wb, wb + wc) are written (window sharding); the carry chain always runs over
 // all 16.  A final carry (scalar >= 2^255 - 2^239) sets *err, as cuzk/utils.ts:95-98 throws.
 //
-// even != 0 (whole MSMs, sequencer.hip Phase::even): the three bits a 253-bit scalar leaves unused are spread over the
+// even != 0 (whole MSMs, sequencer.hip WindowPlan::recode): the three bits a 253-bit scalar leaves unused are spread over the
 // top THREE windows instead of emptying the last one -- windows 0..12 as above, windows 13, 14, 15 take 15 bits each
 // (bit offsets 208, 223, 238: common.hpp even_offset) as UNSIGNED digits in [0, 2^15) with a carry chain of their own
 // (limb + carry = 2^15 -> digit 0, carry 1).  Every window then fills its 2^15 buckets with rows of n / 2^15 entries;

@@ -24,11 +24,12 @@
 // HBM layout: DESIGN.md section 3.
 //
 // Host control flow, top to bottom in this file: a WindowPlan says which windows one attempt of a call runs and how the
-// host combines their records (one constructor per geometry); enqueue_windows queues the stages of a Phase for its plan;
-// wait_windows / geometry_refused / collect_windows / run_tail are the steps behind it.  g1_table_msm strings them
-// together for every G1 MSM on base records that are in place, at full width or over short scalars, and the entry
-// points are thin wrappers over one flow per kind of input (g1_device_flow, g1_host_flow, g1_fixed_base_flow,
-// ed_device_flow); the chunked uploads, the batches and the window shards keep schedules of their own over the same steps.
+// host combines their records (one constructor per geometry); enqueue_windows queues the stages of a Phase for its plan:
+// one LaunchRecord of derived values, then enqueue_decompose / _sort / _accumulate / _reduce, one function per stage;
+// wait_windows / geometry_refused / collect_windows / run_tail are the steps behind it.  g1_table_msm strings them together for
+// every G1 MSM on base records that are in place, at full width or over short scalars, and the entry points are thin wrappers over one
+// flow per kind of input (g1_device_flow, g1_host_flow, g1_fixed_base_flow, ed_device_flow); the chunked uploads, the
+// batches and the window shards keep schedules of their own over the same steps.
 #include "sequencer.hpp"
 
 #include <hip/hip_runtime.h>
@@ -269,7 +270,7 @@ uint32_t auto_seg(const msm377_ctx* ctx, uint64_t entries, bool glv) {
 }
 
 
-// The windows of ONE attempt of a call: what the kernels run (enqueue_windows reads the first half) and what the host
+// The windows of ONE attempt of a call: what the kernels run (launch_record reads the first half) and what the host
 // tail combines afterwards (run_tail reads the second), written once, by the constructor of the geometry.  The recode
 // families carry the names of tests/stage_model.py.
 enum Recode { RECODE_EQUAL16, RECODE_EVEN16, RECODE_NARROW22, RECODE_SHORT, RECODE_WIDE13, RECODE_GLV8 };
@@ -378,315 +379,314 @@ struct Phase {
   WindowPlan plan;
 };
 
-// k_decompose_short for the stride of the call (4, 8, 16 or 32 bytes: checked by the entry points).
-void launch_decompose_short(hipStream_t st, const void* d_scalars, uint16_t* digits, uint64_t n, uint32_t sbytes, uint32_t bits, uint32_t L, uint32_t W, uint32_t bias,
-                            uint32_t top_bias, int* d_err, uint32_t* top_key_max) {
-  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  const uint8_t* sc = (const uint8_t*)d_scalars;
-  switch (sbytes) {
-    case 4: hipLaunchKernelGGL(k_decompose_short<4>, grid, block, 0, st, sc, digits, n, bits, L, W, bias, top_bias, d_err, top_key_max); break;
-    case 8: hipLaunchKernelGGL(k_decompose_short<8>, grid, block, 0, st, sc, digits, n, bits, L, W, bias, top_bias, d_err, top_key_max); break;
-    case 16: hipLaunchKernelGGL(k_decompose_short<16>, grid, block, 0, st, sc, digits, n, bits, L, W, bias, top_bias, d_err, top_key_max); break;
-    default: hipLaunchKernelGGL(k_decompose_short<32>, grid, block, 0, st, sc, digits, n, bits, L, W, bias, top_bias, d_err, top_key_max); break;
-  }
+// What the host needs of the curve policies of a pass: CV's form and buckets and records out, BP's base records in;
+// quad_items: k_accumulate_quad serves the pair (TeDev on its own projective records).
+struct CurveDims { int form; uint32_t bkt_words, pt_words, out_words, rec_words; bool quad_items; };
+template <class CV, class BP>
+constexpr CurveDims curve_dims() {
+  return {CV::FORM_ID, CV::BKT_WORDS, CV::PT_WORDS, CV::OUT_WORDS, BP::REC_WORDS, std::is_same<BP, CV>::value && std::is_same<CV, TeDev>::value};
 }
 
-// Enqueue stages decompose .. gather for windows [wb, wb + wc) against ctx->d_bases on the main stream, the D2H of
-// the partial records into slot `slot` of ctx->h_partials and that slot's completion event.
-// Nothing here waits for the GPU.
-//
-// (Rounds 1 and 2 could run a large call as TWO parts of half the windows on two streams, so that one part's sort and
-// reduction hid under the other's accumulation: 3.19 vs 3.17 ms at 2^20, then 2.72 -> 2.89 on round 2's kernels -- the
-// accumulation kernel owns every VGPR of the chip, kernels of another stream do not become co-resident.  Removed in
-// round 3.)
-template <class CV, class BP = CV>
-int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scalars, uint32_t wb, int slot, const Phase& ph) {
+// What ONE enqueue_windows call launches with: every size, route flag and per-slot word its stages read, derived once by
+// launch_record (no HIP call) from the plan, the phase and the context's knobs; the ctx->d_* buffers are read where used.
+struct LaunchRecord {
+  const WindowPlan& plan;
+  CurveDims cv;
+  uint32_t into;               // Phase::into, as the accumulation kernels take it
+  uint64_t n_scalars, n;       // scalars of the call; columns of the digit matrix (2 n_scalars behind the GLV front end)
+  uint32_t wb, slots;          // windows [wb, wb + slots)
+  uint32_t L, buckets, rows;   // 2^L buckets per slot, slots x buckets rows
+  uint64_t entries, max_items; // (window, point) pairs this call accumulates; every row has a work item, extra ones are full segments
+  uint32_t SEG;                // entries per accumulation work item
+  uint32_t wc_out, pp;         // window records out (precomputed-window tables fold the windows on the GPU), points per record
+  bool narrow, wide, glv, even, is_short, quad_acc, packed_sort;  // the route
+  // reduction schedule: levels [0, coop_from): one thread per addition (VALU-bound: 2^18 additions per level at first);
+  // [coop_from, tail_from): one lane quad per addition, one launch per level; [tail_from, L): k_reduce_tail, one launch.
+  uint32_t coop_from, tail_from;
+  size_t tail_lds_bytes;  // the stretch of buckets a workgroup of the tail works on
+  int* d_err;            // the slot's error word ...
+  uint32_t* d_partials;  // ... and partial records
+  const uint32_t* bases;
+  uint32_t *work_hist, *cursor, *total, *counters;  // the meta block: [work-list counters | key_max[16]]; counters: [0] split rows, [1] overflow slots
+  uint32_t *key_max, *top_key_max;
+};
+
+LaunchRecord launch_record(msm377_ctx* ctx, const Phase& ph, uint64_t n_scalars, uint32_t wb, int slot, const CurveDims& cv) {
   const WindowPlan& plan = ph.plan;
-  const uint32_t wc = plan.slots;
-  const bool glv = plan.recode == RECODE_GLV8, wide = plan.recode == RECODE_WIDE13, even = plan.recode == RECODE_EVEN16;
-  const uint64_t n = glv ? 2 * n_scalars : n_scalars;
-  hipStream_t st = ctx->stream;
-  int* d_err = ctx->d_err + slot;
-  uint32_t* d_partials = ctx->d_partials + (size_t)slot * SLOT_WORDS;
-  StageLayout& layout = ctx->stage;  // set again at the end of a whole call under stage capture
-  layout.valid = false;
-  // the error word is cleared by the call's first kernel together with its counters -- unless there is no such kernel
-  // (back phase only)
-  if (ph.clear_err && !ph.front) hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(256), 0, st, (uint32_t*)d_err, 1u, (uint32_t*)nullptr, 0u);
-  ctx->zc_active = ph.zc_out && ph.back && ctx->zc_out && slot == 0 && !plan.table;
-  if (ctx->zc_active) ctx->out_seq++;
-  const uint32_t L = plan.bucket_log, NB = 1u << L;  // this call's bucket geometry (shadows the main path's constant)
-  const bool narrow = !wide && L != MSM377_WINDOW_BITS - 1;  // the small-input front end (k_small_sort), at full width or short
-  const uint64_t entries = (wide ? (uint64_t)WIDE_WINDOWS : (uint64_t)wc) * n;  // (window, point) pairs this call accumulates
-  static_assert((uint64_t)NARROW_EVEN_WINDOWS * SMALL_SORT_MAX / NARROW_SEG + NARROW_EVEN_WINDOWS * (1u << NARROW_LOG) <= (uint64_t)MSM377_NUM_WINDOWS * 32768,
-                "narrow work items fit the work-item buffer");
+  LaunchRecord k{plan, cv, ph.into ? 1u : 0u};
+  k.glv = plan.recode == RECODE_GLV8, k.wide = plan.recode == RECODE_WIDE13, k.even = plan.recode == RECODE_EVEN16, k.is_short = plan.short_bytes != 0;
+  k.n_scalars = n_scalars, k.n = k.glv ? 2 * n_scalars : n_scalars, k.wb = wb, k.slots = plan.slots;
+  k.L = plan.bucket_log, k.buckets = 1u << k.L;  // this call's bucket geometry
+  k.narrow = !k.wide && k.L != MSM377_WINDOW_BITS - 1;  // the small-input front end (k_small_sort), at full width or short
+  k.entries = (k.wide ? (uint64_t)WIDE_WINDOWS : (uint64_t)k.slots) * k.n;
   // Each launch must fill the GPU on its own.  Narrow windows: a small input is all latency -- a work item is
   // a serial chain of ~10 us additions -- so its chains are cut at 8 entries (the buffers, sized for 16 windows of
   // 2^15 rows plus entries / SEG_MIN items, hold the 22 x 2^11 rows and 22 n / 8 items of an input this small easily).
   // (With the even geometry and quad-cooperative record loads in the merge, 16 entries win from 2^14 points on and 12
   // at 2^13 -- accumulate + merge 0.288 / 0.277 / 0.284 / 0.270 ms for 8 / 10 / 12 / 16 at 2^16, 0.077 / 0.077 / 0.074 /
   // 0.085 at 2^13, profiles/r03_final/sweep_narrow_seg_even.txt; below that a row has two entries on average.)
-  const uint32_t SEG = (narrow && !ctx->seg_plain) ? (ctx->narrow_seg ? ctx->narrow_seg : (n > 8192 ? 16u : 12u)) : auto_seg(ctx, entries, glv);
-  uint16_t* digits = ctx->d_digits;
-  uint32_t* range_counts = ctx->d_range_counts;
-  uint32_t* region_base = ctx->d_region_base;
-  SortElem* sort_temp = ctx->d_sort_temp;
-  uint32_t* row_ptr = ctx->d_row_ptr;
-  uint32_t* val_idx = ctx->d_val_idx;
-  uint32_t* buckets = ctx->d_buckets;
-  uint32_t* row_ovf_base = ctx->d_row_ovf_base;
-  uint32_t* split_rows = ctx->d_split_rows;
-  WorkItem* work = ctx->d_work;
-  uint32_t* ovf = ctx->d_ovf;
+  static_assert((uint64_t)NARROW_EVEN_WINDOWS * SMALL_SORT_MAX / NARROW_SEG + NARROW_EVEN_WINDOWS * (1u << NARROW_LOG) <= (uint64_t)MSM377_NUM_WINDOWS * 32768,
+                "narrow work items fit the work-item buffer");
+  k.SEG = (k.narrow && !ctx->seg_plain) ? (ctx->narrow_seg ? ctx->narrow_seg : (k.n > 8192 ? 16u : 12u)) : auto_seg(ctx, k.entries, k.glv);
+  k.rows = k.slots * k.buckets, k.max_items = (uint64_t)k.rows + k.entries / k.SEG;
+  k.wc_out = plan.table ? 1u : k.slots, k.pp = k.wide ? WIDE_POINTS : (uint32_t)MSM377_G1_PARTIAL_POINTS;
+  // a lane quad per work item while the launch is one chain's latency (up to 2^14 points: ~94 k items); beyond that
+  // the quads are VALU-bound like threads and only add their exchange instructions (kernel at 2^16: 0.216 / 0.183 ms)
+  k.quad_acc = cv.quad_items && k.narrow && !plan.table && k.max_items <= ctx->narrow_quad_items;
+  // (One launch for the whole front end of such a call -- each window's workgroup recoding, sorting and listing its
+  // work items itself, one global atomic per list and workgroup -- was built and dropped: 0.271 -> 0.293 ms at 2^12,
+  // 0.342 -> 0.373 at 2^14.  Saving four dispatch latencies did not pay for a work list that is sorted by length
+  // only within each window: the accumulation kernel went from 0.038 to 0.054 ms at 2^12.)
+  // sort_temp elements: 8 bytes, or with MSM377_SORT_ELEM=4 packed into 4 while every column index fits 23 bits
+  // (common.hpp sort_elem_bytes); the buffer is sized for 8 either way.
+  k.packed_sort = !k.wide && !k.narrow && ctx->sort_elem == 4 && sort_elem_bytes(k.n, false) == 4;
+  for (k.coop_from = 0; k.coop_from < k.L && 4ull * (k.coop_from + 1) * (k.buckets >> (k.coop_from + 1)) * k.wc_out > ctx->coop_threads;) k.coop_from++;
+  // (wide windows: 2^19 buckets in one window -- the lists of the single-launch tail must be down to one round of
+  // 128 lane quads, which is level L - 8)
+  k.tail_from = std::min(k.wide ? k.L - 8 : k.narrow ? ctx->narrow_tail_from : ctx->tail_from, k.L);
+  k.tail_lds_bytes = (size_t)(k.buckets >> k.tail_from) * cv.pt_words * 4;
+  k.d_err = ctx->d_err + slot, k.d_partials = ctx->d_partials + (size_t)slot * SLOT_WORDS;
   const uint32_t* records = ctx->resident.valid() ? ctx->resident.bases : ctx->d_bases;  // (a twin's resident bases are lent)
-  const uint32_t* bases = plan.table ? plan.table : plan.bases_override ? plan.bases_override : records + ph.base_first * BP::REC_WORDS;
-  uint32_t* meta_block = ctx->d_work_meta;  // [work-list counters | key_max[16]]
-  uint32_t* key_max = meta_block + (2 * SEG_BINS + 4);
-  if (ph.front) {
-    // One memset clears the call's work-list counters AND its key_max words (0 = full-width ranges); k_decompose
-    // then measures window 15 of the plain front end.
-    hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(256), 0, st, meta_block, META_BLOCK_WORDS, (uint32_t*)d_err, ph.clear_err ? 1u : 0u);
-    uint32_t* top_key_max = (!glv && !even && wb + wc == MSM377_NUM_WINDOWS) ? key_max + (wc - 1) : nullptr;
-    const uint64_t max_items = (uint64_t)wc * NB + entries / SEG;  // every row has an item; extra ones are full segments
-    // a lane quad per work item while the launch is one chain's latency (up to 2^14 points: ~94 k items); beyond that
-    // the quads are VALU-bound like threads and only add their exchange instructions (kernel at 2^16: 0.216 / 0.183 ms)
-    const bool quad_acc = std::is_same<BP, CV>::value && std::is_same<CV, TeDev>::value && narrow && !plan.table && max_items <= ctx->narrow_quad_items;
-    // (One launch for the whole front end of such a call -- each window's workgroup recoding, sorting and listing its
-    // work items itself, one global atomic per list and workgroup -- was built and dropped: 0.271 -> 0.293 ms at 2^12,
-    // 0.342 -> 0.373 at 2^14.  Saving four dispatch latencies did not pay for a work list that is sorted by length
-    // only within each window: the accumulation kernel went from 0.038 to 0.054 ms at 2^12.)
-    {
-      StageTimer t(ctx, MSM377_STAGE_DECOMPOSE, st);
-      // The stage layout (msm377_g1_read_stage_ex) is written here, from the very values the launches below are given.
-      layout.info = msm377_stage_info{};
-      layout.info.slots = wc;
-      layout.info.bucket_log = L;
-      layout.info.columns = entries / wc;  // n; 2 n_scalars behind the GLV front end; 13 n in the one slot of the wide table
-      layout.info.digit_bytes = wide ? 4u : 2u;
-      layout.info.row_ptr_len = NB + 2;
-      layout.info.bucket_records = NB;
-      layout.info.form = CV::FORM_ID;
-      layout.info.table_stride = plan.table_stride;
-      layout.info.geometry_reruns = ctx->geometry_reruns;
-      layout.d_digits = wide ? (const void*)ctx->wide.digits : (const void*)digits;
-      layout.d_key_max = (wide || narrow) ? nullptr : key_max;  // k_local_sort_lds of the wide table and k_small_sort read none
-      static_assert(MAX_WINDOW_SLOTS <= MSM377_STAGE_MAX_SLOTS, "a stage layout names every window slot");
-      uint32_t bias = 1u << (MSM377_WINDOW_BITS - 1);  // k_decompose / k_decompose_glv: digit_key's bias
-      if (plan.short_bytes) {  // the top slot of the main path: unsigned digits, its ranges narrowed by its largest key (win_shift)
-        bias = narrow ? NB : 32768u;
-        const uint32_t top_bias = narrow ? NB : 0u;
-        launch_decompose_short(st, d_scalars, digits, n, plan.short_bytes, plan.short_bits, L, wc, bias, top_bias, d_err, narrow ? nullptr : key_max + (wc - 1));
-        for (uint32_t s = 0; s < wc; s++) layout.info.bias[s] = s + 1 < wc ? bias : top_bias;
-        layout.info.key_unsigned[wc - 1] = narrow ? 0u : 1u;  // (KEY_UNSIGNED in that slot's key_max word)
-      } else if (wide) {
-        bias = 1u << WIDE_LOG;  // k_decompose_wide's BIAS
-        hipLaunchKernelGGL(k_decompose_wide, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, ctx->wide.digits, n, d_err);
-      } else if (narrow) {
-        bias = 1u << L;
-        hipLaunchKernelGGL(k_decompose_geom, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, digits, n, L, NARROW_EVEN_SIGNED, wc, bias, d_err);
-      } else if (glv)
-        hipLaunchKernelGGL(k_decompose_glv, dim3((unsigned)((n_scalars + 255) / 256)), dim3(256), 0, st, d_scalars, digits, n_scalars, wb, wc, d_err);
-      else
-        hipLaunchKernelGGL(k_decompose, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, digits, n, wb, wc, d_err, top_key_max, even ? 1u : 0u);
-      if (!plan.short_bytes)
-        for (uint32_t s = 0; s < wc; s++) layout.info.bias[s] = bias;
-      HIP_TRY(ctx, hipGetLastError());
-    }
+  k.bases = plan.table ? plan.table : plan.bases_override ? plan.bases_override : records + ph.base_first * cv.rec_words;
+  k.work_hist = ctx->d_work_meta, k.cursor = k.work_hist + SEG_BINS, k.total = k.work_hist + 2 * SEG_BINS, k.counters = k.total + 1;
+  k.key_max = k.work_hist + (2 * SEG_BINS + 4);
+  // The recode measures the top slot where its digits are unsigned: window 15 of the plain front end, the top slot of a
+  // short call on the main path (its ranges narrowed by its largest key, win_shift).
+  const bool measured = k.is_short ? !k.narrow : (!k.glv && !k.even && wb + k.slots == MSM377_NUM_WINDOWS);
+  k.top_key_max = measured ? k.key_max + (k.slots - 1) : nullptr;
+  return k;
+}
 
-    if (wide) {  // the 13 n entries into 4096 fine ranges: two staged partition passes per window (kernels/wide.hpp), then k_local_sort_lds
-      StageTimer t(ctx, MSM377_STAGE_SORT, st);
-      uint32_t* wc = ctx->wide.counts;
-      ctx->last_sort_elem = sort_elem_bytes(entries, true);
-      hipLaunchKernelGGL(k_wide_count, dim3(WS_CHUNKS, WIDE_WINDOWS), dim3(1024), 0, st, (const uint32_t*)ctx->wide.digits, wc, n);
-      hipLaunchKernelGGL(k_wide_sums, dim3(WIDE_NRANGE / 256, WIDE_WINDOWS), dim3(256), 0, st, wc);
-      hipLaunchKernelGGL(k_wide_scan, dim3(1), dim3(1024), 0, st, wc, region_base);
-      hipLaunchKernelGGL(k_wide_offsets1, dim3(WIDE_WINDOWS), dim3(WS_COARSE), 0, st, wc, n);
-      hipLaunchKernelGGL(k_wide_part1, dim3(WS_CHUNKS, WIDE_WINDOWS), dim3(1024), 0, st, (const uint32_t*)ctx->wide.digits, (const uint32_t*)wc, sort_temp, n, (uint32_t)plan.table_stride);
-      hipLaunchKernelGGL(k_wide_part2, dim3(WS_COARSE, WIDE_WINDOWS), dim3(1024), 0, st, (const SortElem*)sort_temp, (const uint32_t*)wc, ctx->wide.temp);
-      hipLaunchKernelGGL(k_local_sort_lds<SortElem>, dim3(WIDE_NRANGE, 1), dim3(256), 0, st, (const SortElem*)ctx->wide.temp, region_base, row_ptr, val_idx, entries,
-                         (const uint32_t*)nullptr, WIDE_NRANGE, NB);
-      HIP_TRY(ctx, hipGetLastError());
-    } else if (narrow) {
-      StageTimer t(ctx, MSM377_STAGE_SORT, st);
-      ctx->last_sort_elem = 0;
-      hipLaunchKernelGGL(k_small_sort, dim3(wc), dim3(1024), 0, st, digits, row_ptr, val_idx, (uint32_t)n, L);
-      HIP_TRY(ctx, hipGetLastError());
-    } else {
-      StageTimer t(ctx, MSM377_STAGE_SORT, st);
-      uint32_t chunks = MAX_SORT_BLOCKS / wc;
-      const uint64_t want = (n + 4095) / 4096;  // at least ~4096 elements per block
-      if (chunks > want) chunks = (uint32_t)(want ? want : 1);
-      const uint64_t per_chunk = (n + chunks - 1) / chunks;
-      if (plan.short_bytes)  // (the top slot holds unsigned digits: KEY_UNSIGNED)
-        hipLaunchKernelGGL(k_range_count<true>, dim3(chunks, wc), dim3(1024), 0, st, digits, range_counts, n, chunks, per_chunk, key_max);
-      else
-        hipLaunchKernelGGL(k_range_count<false>, dim3(chunks, wc), dim3(1024), 0, st, digits, range_counts, n, chunks, per_chunk, key_max);
-      HIP_TRY(ctx, hipGetLastError());
-      hipLaunchKernelGGL(k_range_scan, dim3(wc), dim3(NRANGE), 0, st, range_counts, region_base, chunks);
-      HIP_TRY(ctx, hipGetLastError());
-      // sort_temp elements: 8 bytes, or with MSM377_SORT_ELEM=4 packed into 4 while every column index fits 23 bits
-      // (common.hpp sort_elem_bytes); the buffer is sized for 8 either way.
-      const bool packed = ctx->sort_elem == 4 && sort_elem_bytes(n, false) == 4;
-      ctx->last_sort_elem = packed ? 4u : 8u;
-      auto partition_and_sort = [&](auto* temp) {
-        using E = std::remove_pointer_t<decltype(temp)>;
-        if (plan.short_bytes)
-          hipLaunchKernelGGL((k_partition_staged<E, true>), dim3(chunks, wc), dim3(1024), 0, st, digits, range_counts, temp, n, chunks, per_chunk, key_max);
-        else
-          hipLaunchKernelGGL((k_partition_staged<E, false>), dim3(chunks, wc), dim3(1024), 0, st, digits, range_counts, temp, n, chunks, per_chunk, key_max);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_local_sort_lds<E>, dim3(NRANGE, wc), dim3(256), 0, st, (const E*)temp, region_base, row_ptr, val_idx, n, key_max, NRANGE, NB);
-        return hipGetLastError();
-      };
-      HIP_TRY(ctx, packed ? partition_and_sort(reinterpret_cast<SortElem4*>(sort_temp)) : partition_and_sort(sort_temp));
-    }
+// Stage 1: scalars -> digits, and the stage layout (msm377_g1_read_stage_ex) from the very values the launch is given,
+// so that the read-back describes the kernels' arguments and not a second derivation of them.
+int enqueue_decompose(msm377_ctx* ctx, const LaunchRecord& k, const uint32_t* d_scalars) {
+  StageTimer t(ctx, MSM377_STAGE_DECOMPOSE, ctx->stream);
+  hipStream_t st = ctx->stream;
+  const dim3 grid((unsigned)((k.n_scalars + 255) / 256)), block(256);  // (one thread per scalar; n_scalars = n except behind GLV)
+  // digit_key's bias per slot: k_decompose / k_decompose_glv 2^15, k_decompose_wide's BIAS, the narrow path's 2^L; the top
+  // slot of a short call on the main path holds unsigned digits
+  const uint32_t bias = k.wide ? 1u << WIDE_LOG : k.narrow ? k.buckets : 1u << (MSM377_WINDOW_BITS - 1);
+  const uint32_t top_bias = k.is_short && !k.narrow ? 0u : bias;
+  if (k.is_short) {  // k_decompose_short for the stride of the call (4, 8, 16 or 32 bytes: checked by the entry points)
+    const uint32_t sb = k.plan.short_bytes;
+    const auto recode = sb == 4 ? k_decompose_short<4> : sb == 8 ? k_decompose_short<8> : sb == 16 ? k_decompose_short<16> : k_decompose_short<32>;
+    hipLaunchKernelGGL(recode, grid, block, 0, st, (const uint8_t*)d_scalars, ctx->d_digits, k.n, k.plan.short_bits, k.L, k.slots, bias, top_bias, k.d_err, k.top_key_max);
+  } else if (k.wide)
+    hipLaunchKernelGGL(k_decompose_wide, grid, block, 0, st, d_scalars, ctx->wide.digits, k.n, k.d_err);
+  else if (k.narrow)
+    hipLaunchKernelGGL(k_decompose_geom, grid, block, 0, st, d_scalars, ctx->d_digits, k.n, k.L, NARROW_EVEN_SIGNED, k.slots, bias, k.d_err);
+  else if (k.glv)
+    hipLaunchKernelGGL(k_decompose_glv, grid, block, 0, st, d_scalars, ctx->d_digits, k.n_scalars, k.wb, k.slots, k.d_err);
+  else
+    hipLaunchKernelGGL(k_decompose, grid, block, 0, st, d_scalars, ctx->d_digits, k.n, k.wb, k.slots, k.d_err, k.top_key_max, k.even ? 1u : 0u);
+  HIP_TRY(ctx, hipGetLastError());
+  static_assert(MAX_WINDOW_SLOTS <= MSM377_STAGE_MAX_SLOTS, "a stage layout names every window slot");
+  msm377_stage_info& info = ctx->stage.info = msm377_stage_info{};
+  info.slots = k.slots, info.bucket_log = k.L;
+  info.columns = k.entries / k.slots;  // n; 2 n_scalars behind the GLV front end; 13 n in the one slot of the wide table
+  info.digit_bytes = k.wide ? 4u : 2u;
+  info.row_ptr_len = k.buckets + 2, info.bucket_records = k.buckets;
+  info.form = k.cv.form, info.table_stride = k.plan.table_stride, info.geometry_reruns = ctx->geometry_reruns;
+  for (uint32_t s = 0; s < k.slots; s++) info.bias[s] = s + 1 < k.slots ? bias : top_bias;
+  if (k.is_short && !k.narrow) info.key_unsigned[k.slots - 1] = 1u;  // (KEY_UNSIGNED in that slot's key_max word)
+  ctx->stage.d_digits = k.wide ? (const void*)ctx->wide.digits : (const void*)ctx->d_digits;
+  ctx->stage.d_key_max = (k.wide || k.narrow) ? nullptr : k.key_max;  // k_local_sort_lds of the wide table and k_small_sort read none
+  return MSM377_OK;
+}
 
-    {  // work list, accumulation, merge of split rows
-      StageTimer t(ctx, MSM377_STAGE_ACCUMULATE, st);
-      const uint32_t rows = wc * NB;
-      uint32_t* meta = meta_block;
-      uint32_t* work_hist = meta;
-      uint32_t* cursor = meta + SEG_BINS;
-      uint32_t* total = meta + 2 * SEG_BINS;
-      uint32_t* counters = meta + 2 * SEG_BINS + 1;  // [0] split rows, [1] overflow slots
-      hipLaunchKernelGGL(k_work_hist, dim3((rows + 1023) / 1024), dim3(1024), 0, st, row_ptr, L, rows, SEG, work_hist, row_ovf_base, counters, split_rows);
-      HIP_TRY(ctx, hipGetLastError());
-      hipLaunchKernelGGL(k_work_scatter, dim3((rows + 1023) / 1024), dim3(1024), 0, st, row_ptr, L, rows, SEG, (const uint32_t*)work_hist, cursor, total, work);
-      HIP_TRY(ctx, hipGetLastError());
-      if (ctx->before_accumulate) {  // must run before the wait below is queued: the wait binds to the event's latest record
-        std::function<int()> f;
-        f.swap(ctx->before_accumulate);
-        const int hook_rc = f();
-        if (hook_rc) return hook_rc;
-      }
-      HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->bases_ready, 0));
-      ctx->last_products = BP::MADD_PRODUCTS;
-      {
-        StageTimer tk(ctx, MSM377_STAGE_ACC_KERNEL, st);
-        const dim3 grid((unsigned)((max_items + 255) / 256));
-        bool launched = false;
-        if constexpr (std::is_same<BP, CV>::value && std::is_same<CV, TeDev>::value) {
-          if (quad_acc) {
-            hipLaunchKernelGGL(k_accumulate_quad<CV>, dim3((unsigned)((4 * max_items + 255) / 256)), dim3(256), 0, st, row_ptr, val_idx, bases, buckets, n, work, total,
-                               row_ovf_base, ovf, SEG, d_err, ctx->d_err + 2, ph.into ? 1u : 0u, L);
-            launched = true;
-          }
-        }
-        if (launched) {
-        } else if constexpr (!std::is_same<BP, CV>::value)
-          hipLaunchKernelGGL((k_accumulate<CV, 2, BP>), grid, dim3(256), 0, st, row_ptr, val_idx, bases, buckets, n, work, total, row_ovf_base, ovf, SEG, d_err,
-                             ctx->d_err + 2, ph.into ? 1u : 0u, plan.table_stride, L);
-        else
-          hipLaunchKernelGGL((k_accumulate<CV, 2>), grid, dim3(256), 0, st, row_ptr, val_idx, bases, buckets, n, work, total, row_ovf_base, ovf, SEG, d_err,
-                             ctx->d_err + 2, ph.into ? 1u : 0u, plan.table_stride, L);
-      }
-      HIP_TRY(ctx, hipGetLastError());
-      ctx->acc_seq++;
-      static_assert(CV::HAS_QUAD, "every curve policy has the quad-cooperative addition");
-      if (plan.short_bytes) {  // the top window of a short call: few rows, thousands of partials each -- folded before the merge
-        hipLaunchKernelGGL(k_fold_long_rows<CV>, dim3(FOLD_BLOCKS), dim3(FOLD_THREADS), 0, st, row_ptr, row_ovf_base, ovf, SEG, d_err, L, wc - 1);
-        HIP_TRY(ctx, hipGetLastError());
-      }
-      // (grid-stride over the split-row list: with the even windows few rows split, and 8192 workgroups that only read the
-      // count cost 11 us at 2^20)
-      hipLaunchKernelGGL(k_merge_split_rows_quad<CV>, dim3(std::min<uint32_t>((rows + 63) / 64, 1024u)), dim3(256), 0, st, row_ptr, buckets, counters, split_rows, row_ovf_base, ovf, SEG, d_err, L,
-                         ctx->dm_out_flag + ACC_FLAG_WORD, ctx->acc_seq);
-      HIP_TRY(ctx, hipGetLastError());
-    }
-  }  // ph.front
-  if (!ph.back) return MSM377_OK;
-  if (ctx->capture) {
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_buckets_snap, buckets, (size_t)wc * CV::BKT_WORDS * NB * 4, hipMemcpyDeviceToDevice, st));
+// Stage 2: digits -> CSR (row_ptr, val_idx) per window slot.
+int enqueue_sort(msm377_ctx* ctx, const LaunchRecord& k) {
+  StageTimer t(ctx, MSM377_STAGE_SORT, ctx->stream);
+  hipStream_t st = ctx->stream;
+  if (k.wide) {  // the 13 n entries into 4096 fine ranges: two staged partition passes per window (kernels/wide.hpp), then k_local_sort_lds
+    uint32_t* counts = ctx->wide.counts;
+    ctx->last_sort_elem = sort_elem_bytes(k.entries, true);
+    hipLaunchKernelGGL(k_wide_count, dim3(WS_CHUNKS, WIDE_WINDOWS), dim3(1024), 0, st, (const uint32_t*)ctx->wide.digits, counts, k.n);
+    hipLaunchKernelGGL(k_wide_sums, dim3(WIDE_NRANGE / 256, WIDE_WINDOWS), dim3(256), 0, st, counts);
+    hipLaunchKernelGGL(k_wide_scan, dim3(1), dim3(1024), 0, st, counts, ctx->d_region_base);
+    hipLaunchKernelGGL(k_wide_offsets1, dim3(WIDE_WINDOWS), dim3(WS_COARSE), 0, st, counts, k.n);
+    hipLaunchKernelGGL(k_wide_part1, dim3(WS_CHUNKS, WIDE_WINDOWS), dim3(1024), 0, st, (const uint32_t*)ctx->wide.digits, (const uint32_t*)counts, ctx->d_sort_temp, k.n, (uint32_t)k.plan.table_stride);
+    hipLaunchKernelGGL(k_wide_part2, dim3(WS_COARSE, WIDE_WINDOWS), dim3(1024), 0, st, (const SortElem*)ctx->d_sort_temp, (const uint32_t*)counts, ctx->wide.temp);
+    hipLaunchKernelGGL(k_local_sort_lds<SortElem>, dim3(WIDE_NRANGE, 1), dim3(256), 0, st, (const SortElem*)ctx->wide.temp, ctx->d_region_base, ctx->d_row_ptr, ctx->d_val_idx,
+                       k.entries, (const uint32_t*)nullptr, WIDE_NRANGE, k.buckets);
+    HIP_TRY(ctx, hipGetLastError());
+  } else if (k.narrow) {
+    ctx->last_sort_elem = 0;
+    hipLaunchKernelGGL(k_small_sort, dim3(k.slots), dim3(1024), 0, st, ctx->d_digits, ctx->d_row_ptr, ctx->d_val_idx, (uint32_t)k.n, k.L);
+    HIP_TRY(ctx, hipGetLastError());
+  } else {
+    uint32_t chunks = MAX_SORT_BLOCKS / k.slots;
+    const uint64_t want = (k.n + 4095) / 4096;  // at least ~4096 elements per block
+    if (chunks > want) chunks = (uint32_t)(want ? want : 1);
+    const uint64_t per_chunk = (k.n + chunks - 1) / chunks;
+    const dim3 grid(chunks, k.slots);
+    // (is_short: the top slot holds unsigned digits, KEY_UNSIGNED)
+    hipLaunchKernelGGL(k.is_short ? k_range_count<true> : k_range_count<false>, grid, dim3(1024), 0, st, ctx->d_digits, ctx->d_range_counts, k.n, chunks, per_chunk, k.key_max);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_range_scan, dim3(k.slots), dim3(NRANGE), 0, st, ctx->d_range_counts, ctx->d_region_base, chunks);
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->last_sort_elem = k.packed_sort ? 4u : 8u;
+    auto partition_and_sort = [&](auto* temp) {
+      using E = std::remove_pointer_t<decltype(temp)>;
+      hipLaunchKernelGGL((k.is_short ? k_partition_staged<E, true> : k_partition_staged<E, false>), grid, dim3(1024), 0, st, ctx->d_digits, ctx->d_range_counts, temp, k.n, chunks,
+                         per_chunk, k.key_max);
+      const hipError_t e = hipGetLastError();
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(k_local_sort_lds<E>, dim3(NRANGE, k.slots), dim3(256), 0, st, (const E*)temp, ctx->d_region_base, ctx->d_row_ptr, ctx->d_val_idx, k.n, k.key_max, NRANGE,
+                         k.buckets);
+      return hipGetLastError();
+    };
+    HIP_TRY(ctx, k.packed_sort ? partition_and_sort(reinterpret_cast<SortElem4*>(ctx->d_sort_temp)) : partition_and_sort(ctx->d_sort_temp));
   }
-  const uint32_t wc_out = plan.table ? 1u : wc;  // precomputed-window tables fold the windows on the GPU
-  const uint32_t pp = wide ? WIDE_POINTS : (uint32_t)MSM377_G1_PARTIAL_POINTS;  // points per window record
-  {
-    StageTimer t(ctx, MSM377_STAGE_REDUCE, st);
-    if (plan.table) {
-      for (uint32_t m = wc; m > 1;) {  // slots [half, m) onto [0, m - half): 16 -> 8 -> 4 -> 2 -> 1; a short call folds any count
-        const uint32_t half = (m + 1) / 2, count = m - half;
-        hipLaunchKernelGGL(k_fold_windows<CV>, dim3(count * NB / 256), dim3(256), 0, st, buckets, L, half, count, d_err);
-        HIP_TRY(ctx, hipGetLastError());
-        m = half;
-      }
+  return MSM377_OK;
+}
+
+// The accumulation launch of stage 3: a thread per work item, or (quad_acc) a lane quad.
+template <class CV, class BP>
+void launch_accumulate(msm377_ctx* ctx, const LaunchRecord& k) {
+  StageTimer tk(ctx, MSM377_STAGE_ACC_KERNEL, ctx->stream);
+  hipStream_t st = ctx->stream;
+  if constexpr (curve_dims<CV, BP>().quad_items) {
+    if (k.quad_acc) {
+      hipLaunchKernelGGL(k_accumulate_quad<CV>, dim3((unsigned)((4 * k.max_items + 255) / 256)), dim3(256), 0, st, ctx->d_row_ptr, ctx->d_val_idx, k.bases, ctx->d_buckets, k.n,
+                         ctx->d_work, k.total, ctx->d_row_ovf_base, ctx->d_ovf, k.SEG, k.d_err, ctx->d_err + 2, k.into, k.L);
+      return;
     }
-    const uint32_t levels = L;  // log2 of the buckets per window
-    uint32_t coop_from = 0;
-    for (coop_from = 0; coop_from < levels && 4ull * (coop_from + 1) * (NB >> (coop_from + 1)) * wc_out > ctx->coop_threads; coop_from++) {
-      }
-    // Levels [0, coop_from): one thread per addition (VALU-bound: 2^18 additions per level at first); [coop_from,
-    // tail_from): one lane quad per addition, one launch per level; [tail_from, levels): k_reduce_tail, one launch.
-    // (wide windows: 2^19 buckets in one window -- the lists of the single-launch tail must be down to one round of
-    // 128 lane quads, which is level L - 8)
-    const uint32_t tail_from = CV::HAS_QUAD ? std::min(wide ? levels - 8 : narrow ? ctx->narrow_tail_from : ctx->tail_from, levels) : levels;
-    // (Fusing pairs of thread-level levels -- four buckets a quarter-list apart per thread, four additions, three
-    // stores -- halves their HBM traffic and was slower all the same: reduce 0.290 -> 0.310 ms at 2^20, 0.278 -> 0.296
-    // at 2^16.  The first levels are VALU-bound at two waves per SIMD, the later ones cost one addition's latency
-    // per launch; a thread with four serial additions only lengthens that.)
-    // More waves do not help either: k_tree_step at 3 / 4 waves per SIMD (132 VGPRs, no scratch) reduces in 0.300 /
-    // 0.32 ms against 0.298 at 2; lane quads for levels 0-4 (MSM377_COOP_THREADS up to 2^20 threads) in 0.36.
-    // What does help is not going through memory between the levels at all: the levels below tail_from run as column
-    // launches of up to four levels each (k_tree_columns: 0-3 and 4-6 on the main path, 0-3 on the narrow one, 0-3,
-    // 4-7, 8-10 for a wide window), every geometry and window count alike.  coop_from does not choose their kernel any more; it only tells them from
-    // which level on the per-level launches add empty buckets like any other (k_tree_step_quad), so that both give the same records.
-    // MSM377_REDUCE_COLUMNS=0: one launch per level as below.
-    uint32_t r = 0;
-    if (ctx->reduce_columns) {
-      while (r < tail_from) {
-        const uint32_t k = std::min(tail_from - r, COLUMN_LEVELS_MAX);
-        const uint32_t threads = (r + 1) * (NB >> (r + 1));  // per window: (r + 1) arrays x (NB >> (r + k)) columns x 2^(k-1) lanes
-        hipLaunchKernelGGL(k_tree_columns<CV>, dim3((threads + 255) / 256, wc_out), dim3(256), 0, st, buckets, L, r, k, coop_from, threads, d_err);
-        HIP_TRY(ctx, hipGetLastError());
-        r += k;
-      }
-    }
-    for (; r < tail_from; r++) {
-      const uint32_t ops = (r + 1) * (NB >> (r + 1));
-      bool done = false;
-      if constexpr (CV::HAS_QUAD) {
-        if (r >= coop_from) {
-          hipLaunchKernelGGL(k_tree_step_quad<CV>, dim3((4 * ops + 255) / 256, wc_out), dim3(256), 0, st, buckets, L, r, ops, d_err);
-          done = true;
-        }
-      }
-      if (!done) hipLaunchKernelGGL(k_tree_step<CV>, dim3((ops + 255) / 256, wc_out), dim3(256), 0, st, buckets, L, r, ops, d_err);
-      HIP_TRY(ctx, hipGetLastError());
-    }
-    if constexpr (CV::HAS_QUAD) {
-      if (tail_from < levels) {
-        const size_t lds_bytes = (size_t)(NB >> tail_from) * CV::PT_WORDS * 4;  // the stretch of buckets a workgroup works on
-        if (ctx->tail_lds && lds_bytes > 64 * 1024 && lds_bytes <= TAIL_LDS_BYTES_MAX)  // (only with MSM377_TAIL_FROM below its default; per device, so every time)
-          HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_reduce_tail_lds<CV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TAIL_LDS_BYTES_MAX));
-        if (ctx->tail_lds && lds_bytes <= TAIL_LDS_BYTES_MAX)
-          hipLaunchKernelGGL(k_reduce_tail_lds<CV>, dim3(tail_from + 1, wc_out), dim3(TAIL_THREADS), lds_bytes, st, buckets, L, tail_from, d_err);
-        else
-          hipLaunchKernelGGL(k_reduce_tail<CV>, dim3(tail_from + 1, wc_out), dim3(TAIL_THREADS), 0, st, buckets, L, tail_from, d_err);
-        HIP_TRY(ctx, hipGetLastError());
-      }
-    }
-    if (ctx->zc_active)
-      hipLaunchKernelGGL(k_gather_partials<CV>, dim3((wc_out * pp * 4 + 63) / 64), dim3(64), 0, st, buckets, d_partials, wc_out, L, ctx->dm_partials,
-                         ctx->dm_out_flag, ctx->d_out_count, (const int*)d_err, ctx->out_seq, pp);
-    else
-      hipLaunchKernelGGL(k_gather_partials<CV>, dim3((wc_out * pp * 4 + 63) / 64), dim3(64), 0, st, buckets, d_partials, wc_out, L, (uint32_t*)nullptr,
-                         (uint32_t*)nullptr, (uint32_t*)nullptr, (const int*)nullptr, 0u, pp);
+  }
+  hipLaunchKernelGGL((k_accumulate<CV, 2, BP>), dim3((unsigned)((k.max_items + 255) / 256)), dim3(256), 0, st, ctx->d_row_ptr, ctx->d_val_idx, k.bases, ctx->d_buckets, k.n,
+                     ctx->d_work, k.total, ctx->d_row_ovf_base, ctx->d_ovf, k.SEG, k.d_err, ctx->d_err + 2, k.into, k.plan.table_stride, k.L);
+}
+
+// Stage 3: work list, accumulation, merge of split rows.  The before_accumulate hook (the host-buffer entry points: join
+// the point upload, launch the base conversion) is swapped out of the context and called once k_work_scatter is queued
+// and BEFORE the wait for bases_ready is queued: the wait binds to the event's latest record.
+template <class CV, class BP>
+int enqueue_accumulate(msm377_ctx* ctx, const LaunchRecord& k) {
+  StageTimer t(ctx, MSM377_STAGE_ACCUMULATE, ctx->stream);
+  hipStream_t st = ctx->stream;
+  const dim3 row_grid((k.rows + 1023) / 1024);
+  hipLaunchKernelGGL(k_work_hist, row_grid, dim3(1024), 0, st, ctx->d_row_ptr, k.L, k.rows, k.SEG, k.work_hist, ctx->d_row_ovf_base, k.counters, ctx->d_split_rows);
+  HIP_TRY(ctx, hipGetLastError());
+  hipLaunchKernelGGL(k_work_scatter, row_grid, dim3(1024), 0, st, ctx->d_row_ptr, k.L, k.rows, k.SEG, (const uint32_t*)k.work_hist, k.cursor, k.total, ctx->d_work);
+  HIP_TRY(ctx, hipGetLastError());
+  if (ctx->before_accumulate) {
+    std::function<int()> f;
+    f.swap(ctx->before_accumulate);
+    const int hook_rc = f();
+    if (hook_rc) return hook_rc;
+  }
+  HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->bases_ready, 0));
+  ctx->last_products = BP::MADD_PRODUCTS;
+  launch_accumulate<CV, BP>(ctx, k);
+  HIP_TRY(ctx, hipGetLastError());
+  ctx->acc_seq++;
+  if (k.is_short) {  // the top window of a short call: few rows, thousands of partials each -- folded before the merge
+    hipLaunchKernelGGL(k_fold_long_rows<CV>, dim3(FOLD_BLOCKS), dim3(FOLD_THREADS), 0, st, ctx->d_row_ptr, ctx->d_row_ovf_base, ctx->d_ovf, k.SEG, k.d_err, k.L, k.slots - 1);
     HIP_TRY(ctx, hipGetLastError());
   }
+  // (grid-stride over the split-row list: with the even windows few rows split, and 8192 workgroups that only read the
+  // count cost 11 us at 2^20)
+  hipLaunchKernelGGL(k_merge_split_rows_quad<CV>, dim3(std::min<uint32_t>((k.rows + 63) / 64, 1024u)), dim3(256), 0, st, ctx->d_row_ptr, ctx->d_buckets, k.counters,
+                     ctx->d_split_rows, ctx->d_row_ovf_base, ctx->d_ovf, k.SEG, k.d_err, k.L, ctx->dm_out_flag + ACC_FLAG_WORD, ctx->acc_seq);
+  HIP_TRY(ctx, hipGetLastError());
+  return MSM377_OK;
+}
+
+// Stage 4: bucket reduction (schedule: LaunchRecord::coop_from / tail_from) and the gather of the window records.
+// (Fusing pairs of thread-level levels -- four buckets a quarter-list apart per thread, four additions, three
+// stores -- halves their HBM traffic and was slower all the same: reduce 0.290 -> 0.310 ms at 2^20, 0.278 -> 0.296
+// at 2^16.  The first levels are VALU-bound at two waves per SIMD, the later ones cost one addition's latency
+// per launch; a thread with four serial additions only lengthens that.)
+// More waves do not help either: k_tree_step at 3 / 4 waves per SIMD (132 VGPRs, no scratch) reduces in 0.300 /
+// 0.32 ms against 0.298 at 2; lane quads for levels 0-4 (MSM377_COOP_THREADS up to 2^20 threads) in 0.36.
+// What does help is not going through memory between the levels at all: the levels below tail_from run as column
+// launches of up to four levels each (k_tree_columns: 0-3 and 4-6 on the main path, 0-3 on the narrow one, 0-3,
+// 4-7, 8-10 for a wide window), every geometry and window count alike.  coop_from does not choose their kernel any more;
+// it only tells them from which level on the per-level launches add empty buckets like any other (k_tree_step_quad),
+// so that both give the same records.  MSM377_REDUCE_COLUMNS=0: one launch per level.
+template <class CV>
+int enqueue_reduce(msm377_ctx* ctx, const LaunchRecord& k) {
+  static_assert(CV::HAS_QUAD, "every curve policy has the quad-cooperative addition");
+  StageTimer t(ctx, MSM377_STAGE_REDUCE, ctx->stream);
+  hipStream_t st = ctx->stream;
+  // behind a table, slots [half, m) onto [0, m - half): 16 -> 8 -> 4 -> 2 -> 1; a short call folds any count
+  for (uint32_t m = k.plan.table ? k.slots : 1; m > 1;) {
+    const uint32_t half = (m + 1) / 2, count = m - half;
+    hipLaunchKernelGGL(k_fold_windows<CV>, dim3(count * k.buckets / 256), dim3(256), 0, st, ctx->d_buckets, k.L, half, count, k.d_err);
+    HIP_TRY(ctx, hipGetLastError());
+    m = half;
+  }
+  uint32_t r = 0;
+  while (ctx->reduce_columns && r < k.tail_from) {
+    const uint32_t levels = std::min(k.tail_from - r, COLUMN_LEVELS_MAX);
+    const uint32_t threads = (r + 1) * (k.buckets >> (r + 1));  // per window: (r + 1) arrays x (buckets >> (r + levels)) columns x 2^(levels-1) lanes
+    hipLaunchKernelGGL(k_tree_columns<CV>, dim3((threads + 255) / 256, k.wc_out), dim3(256), 0, st, ctx->d_buckets, k.L, r, levels, k.coop_from, threads, k.d_err);
+    HIP_TRY(ctx, hipGetLastError());
+    r += levels;
+  }
+  for (; r < k.tail_from; r++) {
+    const uint32_t ops = (r + 1) * (k.buckets >> (r + 1));
+    if (r >= k.coop_from)
+      hipLaunchKernelGGL(k_tree_step_quad<CV>, dim3((4 * ops + 255) / 256, k.wc_out), dim3(256), 0, st, ctx->d_buckets, k.L, r, ops, k.d_err);
+    else
+      hipLaunchKernelGGL(k_tree_step<CV>, dim3((ops + 255) / 256, k.wc_out), dim3(256), 0, st, ctx->d_buckets, k.L, r, ops, k.d_err);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  if (k.tail_from < k.L) {
+    const bool in_lds = ctx->tail_lds && k.tail_lds_bytes <= TAIL_LDS_BYTES_MAX;
+    if (in_lds && k.tail_lds_bytes > 64 * 1024)  // (only with MSM377_TAIL_FROM below its default; per device, so every time)
+      HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_reduce_tail_lds<CV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TAIL_LDS_BYTES_MAX));
+    if (in_lds)
+      hipLaunchKernelGGL(k_reduce_tail_lds<CV>, dim3(k.tail_from + 1, k.wc_out), dim3(TAIL_THREADS), k.tail_lds_bytes, st, ctx->d_buckets, k.L, k.tail_from, k.d_err);
+    else
+      hipLaunchKernelGGL(k_reduce_tail<CV>, dim3(k.tail_from + 1, k.wc_out), dim3(TAIL_THREADS), 0, st, ctx->d_buckets, k.L, k.tail_from, k.d_err);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  // Zero-copy output: the kernel writes the records and the error word into pinned host memory itself and publishes out_seq.
+  const bool zc = ctx->zc_active;
+  hipLaunchKernelGGL(k_gather_partials<CV>, dim3((k.wc_out * k.pp * 4 + 63) / 64), dim3(64), 0, st, ctx->d_buckets, k.d_partials, k.wc_out, k.L, zc ? ctx->dm_partials : nullptr,
+                     zc ? ctx->dm_out_flag : nullptr, zc ? ctx->d_out_count : nullptr, zc ? (const int*)k.d_err : nullptr, zc ? ctx->out_seq : 0u, k.pp);
+  HIP_TRY(ctx, hipGetLastError());
+  return MSM377_OK;
+}
+
+// Enqueue stages decompose .. gather for windows [wb, wb + plan.slots) against ctx->d_bases on the main stream, the D2H
+// of the partial records into slot `slot` of ctx->h_partials (unless the gather kernel delivered them) and that slot's
+// completion event: one LaunchRecord, then the stage functions above in order.  Nothing here waits for the GPU.
+// (Rounds 1 and 2 could run a large call as TWO parts of half the windows on two streams, so that one part's sort and
+// reduction hid under the other's accumulation: 3.19 vs 3.17 ms at 2^20, then 2.72 -> 2.89 on round 2's kernels -- the
+// accumulation kernel owns every VGPR of the chip, kernels of another stream do not become co-resident.  Removed in
+// round 3.)
+template <class CV, class BP = CV>
+int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scalars, uint32_t wb, int slot, const Phase& ph) {
+  const LaunchRecord k = launch_record(ctx, ph, n_scalars, wb, slot, curve_dims<CV, BP>());
+  hipStream_t st = ctx->stream;
+  ctx->stage.valid = false;  // set again at the end of a whole call under stage capture
+  ctx->zc_active = ph.zc_out && ph.back && ctx->zc_out && slot == 0 && !k.plan.table;
+  if (ctx->zc_active) ctx->out_seq++;
+  // The error word is cleared by the call's first kernel: with the front stages one launch clears the call's work-list
+  // counters, its key_max words (0 = full-width ranges; the recode then measures the top slot) and the error word.
+  if (ph.front) {
+    hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(256), 0, st, k.work_hist, META_BLOCK_WORDS, (uint32_t*)k.d_err, ph.clear_err ? 1u : 0u);
+    int rc = enqueue_decompose(ctx, k, d_scalars);
+    if (rc == MSM377_OK) rc = enqueue_sort(ctx, k);
+    if (rc == MSM377_OK) rc = enqueue_accumulate<CV, BP>(ctx, k);
+    if (rc) return rc;
+  } else if (ph.clear_err)
+    hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(256), 0, st, (uint32_t*)k.d_err, 1u, (uint32_t*)nullptr, 0u);
+  if (!ph.back) return MSM377_OK;
+  if (ctx->capture) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_buckets_snap, ctx->d_buckets, (size_t)k.slots * k.cv.bkt_words * k.buckets * 4, hipMemcpyDeviceToDevice, st));
+  const int rc = enqueue_reduce<CV>(ctx, k);
+  if (rc) return rc;
   if (!ctx->zc_active) {
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_partials + (size_t)slot * SLOT_WORDS, d_partials, (size_t)wc_out * pp * CV::OUT_WORDS * 4,
-                                 hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_err + slot, d_err, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_partials + (size_t)slot * SLOT_WORDS, k.d_partials, (size_t)k.wc_out * k.pp * k.cv.out_words * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_err + slot, k.d_err, sizeof(int), hipMemcpyDeviceToHost, st));
   }
   HIP_TRY(ctx, hipEventRecord(ctx->done_ev[slot], st));
-  ctx->last_n = n;
-  ctx->last_wc = wc;
-  ctx->last_geom_windows = wc;
-  ctx->last_geom_log = L;
-  ctx->last_glv = glv;
-  ctx->last_form = CV::FORM_ID;
+  ctx->last_n = k.n, ctx->last_glv = k.glv, ctx->last_form = k.cv.form;
+  ctx->last_geom_windows = k.slots, ctx->last_geom_log = k.L;
   // A whole call in one piece from window 0 in a form with read-backs: the layout written at the decomposition describes it.
-  layout.valid = ctx->capture && ph.front && !ph.into && wb == 0 && CV::FORM_ID >= 0;
+  ctx->stage.valid = ctx->capture && ph.front && !ph.into && wb == 0 && k.cv.form >= 0;
   return MSM377_OK;
 }
 
