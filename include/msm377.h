@@ -370,21 +370,28 @@ int msm377_ctx_get_last_check(const msm377_ctx* ctx, msm377_check_report* out);
  * residues below p + 2^354, the identity stored as (0, c, 0, c)) for the default form. */
 #define MSM377_STAGE_FORM_XYZZ 0
 #define MSM377_STAGE_FORM_TE 1
-int msm377_ctx_get_stage_form(const msm377_ctx* ctx); /* -1: nothing captured */
+/* Edwards-BLS12 calls (msm377_ed_msm*), msm377_stage_info.form only: (X, Y, T, Z) extended twisted Edwards coordinates over
+ * the 9-limb field Fq, 9 Montgomery words each (radix 2^261, lazy residues below q + e, the identity stored as (0, c, 0, c)):
+ * 36 words per record.  Read as run only (capture mode 2, msm377_g1_read_stage_ex). */
+#define MSM377_STAGE_FORM_ED 2
+int msm377_ctx_get_stage_form(const msm377_ctx* ctx); /* -1: nothing captured, or the last call was an Edwards-BLS12 one */
 int msm377_ctx_set_stage_capture(msm377_ctx* ctx, int enabled);
 int msm377_g1_read_stage(msm377_ctx* ctx, uint32_t slot, uint16_t* digits, uint32_t* row_ptr, uint32_t* val_idx, uint32_t* buckets);
 
 /* Capture modes of msm377_ctx_set_stage_capture (any other value: MSM377_EINVAL, the mode stays as it was; before mode 2
  * existed every non-zero value meant mode 1).  msm377_g1_read_stage answers under mode 1 only, msm377_g1_read_stage_ex
- * under modes 1 and 2; each returns MSM377_ESTATE otherwise.
+ * under modes 1 and 2; each returns MSM377_ESTATE otherwise.  Mode 1 and msm377_g1_read_stage describe G1 calls only:
+ * after an Edwards-BLS12 call both read-backs return MSM377_ESTATE under mode 1.
  *   0  off.
  *   1  the route the read-backs above describe: sixteen equal 16-bit windows of 2^15 buckets, whatever the input size --
  *      the narrow-window path, the even geometry, the chunked upload and twin batches are switched off while it is set.
  *   2  AS RUN: the call takes the route it would take without capture (narrow windows, the even geometry, short
  *      scalars, the wide table, the GLV front end, reruns) and msm377_g1_read_stage_ex describes whatever its LAST pass
  *      launched.  Out of scope, and therefore still switched off by mode 2 as by mode 1: the chunked upload of the
- *      host-buffer calls and twin batches, whose rows are laid out per chunk / per half.  Not described either
- *      (MSM377_ESTATE): Edwards-BLS12 calls and window-partials calls that do not start at window 0.
+ *      host-buffer calls (msm377_g1_msm and msm377_ed_msm alike) and twin batches, whose rows are laid out per chunk / per
+ *      half.  Edwards-BLS12 calls are described like G1 calls: the even geometry, or sixteen equal windows after a rerun
+ *      or under MSM377_EVEN_WINDOWS=0, with records of form MSM377_STAGE_FORM_ED.  Not described (MSM377_ESTATE):
+ *      window-partials calls that do not start at window 0.
  *
  * msm377_stage_info is filled from the arguments the last pass's kernels were launched with:
  *   slots           window slots (16; 22 narrow; floor(bits / (L + 1)) + 1 short; 1 wide table; 8 GLV)
@@ -393,7 +400,8 @@ int msm377_g1_read_stage(msm377_ctx* ctx, uint32_t slot, uint16_t* digits, uint3
  *                   (window-major: digit column w n + i; val_idx entries name table record w * table_stride + i)
  *   digit_bytes     2 or 4: element size of `digits`
  *   row_ptr_len     2^L + 2
- *   bucket_records  2^L records of 52 words per slot, bucket t = key t + 1 at record t
+ *   bucket_records  2^L records per slot, bucket t = key t + 1 at record t: 52 words each (four coordinates of 13 limbs), 36
+ *                   (four of 9) for MSM377_STAGE_FORM_ED
  *   form            MSM377_STAGE_FORM_* of the records
  *   table_stride    records per window of a precomputed table (0: every slot gathers from the same base records)
  *   geometry_reruns passes this context has discarded so far because a scalar did not fit their window geometry (2^253 and
@@ -415,9 +423,9 @@ typedef struct msm377_stage_info {
   uint32_t key_unsigned[MSM377_STAGE_MAX_SLOTS];
   uint32_t key_max[MSM377_STAGE_MAX_SLOTS];
 } msm377_stage_info;
-/* Stage outputs of window slot `slot` of the last G1 MSM call, at the sizes `info` reports (any pointer may be NULL; call
- * once with buffers NULL to size them): digits columns x digit_bytes, row_ptr row_ptr_len u32, val_idx columns u32,
- * buckets bucket_records x 52 u32.  MSM377_ESTATE (and nothing written) unless capture is on and the last call's last
+/* Stage outputs of window slot `slot` of the last G1 or Edwards-BLS12 MSM call, at the sizes `info` reports (any pointer
+ * may be NULL; call once with buffers NULL to size them): digits columns x digit_bytes, row_ptr row_ptr_len u32, val_idx
+ * columns u32, buckets bucket_records x 52 u32 (x 36 for MSM377_STAGE_FORM_ED).  MSM377_ESTATE (and nothing written) unless capture is on and the last call's last
  * pass ran to the end under it on a route the mode describes. */
 int msm377_g1_read_stage_ex(msm377_ctx* ctx, uint32_t slot, msm377_stage_info* info, void* digits, uint32_t* row_ptr, uint32_t* val_idx, uint32_t* buckets);
 /* Convert one Montgomery XYZZ point (52 words) to the affine wire format (host-only). */

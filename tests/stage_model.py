@@ -6,7 +6,9 @@ csrc/kernels/decompose.hpp and wide.hpp), not from their code:
     recode(k, geometry)   digits of one scalar, the flags the kernel must raise, the values it must store
     digit_matrix(...)     the same for a list of scalars, as the digit columns of every window slot
     csr(stored, ...)      per key of a slot: how many entries, and which (entry, sign) pairs
-    bucket_sum(...)       the sum a bucket must hold, by pyref's group law
+    bucket_sum(...)       the sum a bucket must hold, by pyref's group law (ed=True: Edwards-BLS12 points, pyref.ed_add /
+                          ed_neg, the identity (0, 1); such calls take k_decompose, so their recode is even16() / equal16())
+    ed_record_affine(...) the affine point an Edwards-BLS12 bucket record stands for
 
 A geometry is a Geometry value from equal16 / even16 / narrow22 / short / wide13 / glv8.  tests/test_stage_model_host.py
 pins this module (digits rebuild the scalar, ranges, flag sets, agreement with the oracle's recode and with the short
@@ -225,9 +227,12 @@ def phi(pt):
     return None if pt is None else (beta * pt[0] % R.P, pt[1])
 
 
-def entry_base(points, entry, g: Geometry, n: int, cache: Optional[dict] = None):
+def entry_base(points, entry, g: Geometry, n: int, cache: Optional[dict] = None, ed: bool = False):
     """The point an entry of a slot adds: P_i; behind the GLV front end P_i for entry i and phi(P_i) for entry n + i; on
-    the wide table [2^wide_offset(w)] P_i for entry w n + i."""
+    the wide table [2^wide_offset(w)] P_i for entry w n + i.  ed: an Edwards-BLS12 call, whose slots all gather P_i."""
+    if ed:
+        assert g.name in ("even16", "equal16"), "Edwards-BLS12 calls run sixteen windows over their own points"
+        return points[entry]
     if g.name == "glv8":
         return points[entry] if entry < n else phi(points[entry - n])
     if g.name == "wide13":
@@ -241,8 +246,15 @@ def entry_base(points, entry, g: Geometry, n: int, cache: Optional[dict] = None)
     return points[entry]
 
 
-def bucket_sum(points, row, g: Geometry, n: int, cache: Optional[dict] = None):
-    """Sum over a row's (entry, sign) pairs of +-base(entry): what bucket key - 1 of the slot must hold."""
+def bucket_sum(points, row, g: Geometry, n: int, cache: Optional[dict] = None, ed: bool = False):
+    """Sum over a row's (entry, sign) pairs of +-base(entry): what bucket key - 1 of the slot must hold.  The identity is
+    None for G1 and (0, 1) for Edwards-BLS12 (ed), whose complete law takes every curve point, low-order ones included."""
+    if ed:
+        acc = R.ED_ID
+        for entry, sign in row:
+            pt = entry_base(points, entry, g, n, cache, ed=True)
+            acc = R.ed_add(acc, R.ed_neg(pt) if sign else pt)
+        return acc
     acc = None
     for entry, sign in row:
         pt = entry_base(points, entry, g, n, cache)
@@ -254,3 +266,30 @@ def key_max_word(stored: np.ndarray, bias: int, key_unsigned: bool) -> int:
     """The key_max word of a slot whose largest key the decomposition tracks."""
     key, _ = keys_and_signs(stored, bias, key_unsigned)
     return int(key.max(initial=0)) | KEY_TRACKED | (KEY_UNSIGNED if key_unsigned else 0)
+
+
+_FQ = None
+
+
+def fq_model():
+    """lazy_model.FieldModel("Fq"): modulus, limb count, Montgomery radix 2^261 and the stored-record shapes of the 9-limb field."""
+    global _FQ
+    if _FQ is None:
+        import lazy_model
+
+        _FQ = lazy_model.FieldModel("Fq")
+    return _FQ
+
+
+def ed_record_affine(words):
+    """An Edwards-BLS12 bucket record as read back -- X, Y, T, Z of 9 limbs each, lazy residues in Montgomery form -- as the
+    affine point (X / Z, Y / Z): limbs to a value, times 2^-261 mod q.  Zero may be stored as 0 or as q; the point (0, 1) is
+    the identity whichever it is.  The record must be a point: Z != 0, T Z = X Y, on the curve."""
+    fq = fq_model()
+    n = fq.N
+    X, Y, T, Z = (sum(int(x) << (29 * j) for j, x in enumerate(words[n * c : n * c + n])) * fq.Rinv % fq.P for c in range(4))
+    assert Z != 0 and (X * Y - T * Z) % fq.P == 0, "extended-coordinate invariant T Z = X Y violated"
+    zi = pow(Z, -1, fq.P)
+    pt = (X * zi % fq.P, Y * zi % fq.P)
+    assert R.ed_on_curve(pt), "not on the Edwards-BLS12 curve"
+    return pt

@@ -24,25 +24,44 @@ pytestmark = pytest.mark.gpu
 
 DECODE_CAP = 300  # buckets per slot decoded with Python integers
 MIN_NONEMPTY, MIN_MULTI = 300, 50  # what a slot must offer for that cap to be a cap and not the whole check
-FORM_XYZZ, FORM_TE = 0, 1
+FORM_XYZZ, FORM_TE, FORM_ED = 0, 1, 2  # MSM377_STAGE_FORM_*: G1 in XYZZ, G1 in twisted Edwards form, the Edwards-BLS12 curve
 FP = lazy_model.FieldModel("Fp")
 STORED, STORED_X = FP.shapes["stored"], FP.shapes["stored_x"]  # the boxes tools/check_lazy_bounds.py starts from
+STORED_FQ = M.fq_model().shapes["stored"]  # ... under use_field("Fq"): every coordinate of an Edwards-BLS12 record, below q + e
+LIMBS = {FORM_XYZZ: 13, FORM_TE: 13, FORM_ED: 9}  # per coordinate of a record as read back
 
 
 def coordinate_shapes(form):
-    """Stored-record contract per coordinate: every Edwards coordinate and Y, ZZ, ZZZ of XYZZ below p + e, X of XYZZ below 5p + e."""
+    """Stored-record contract per coordinate: every Edwards coordinate and Y, ZZ, ZZZ of XYZZ below p + e, X of XYZZ below
+    5p + e; every coordinate of an Edwards-BLS12 record below q + e in the 9-limb box."""
+    if form == FORM_ED:
+        return (STORED_FQ,) * 4
     return (STORED_X if form == FORM_XYZZ else STORED, STORED, STORED, STORED)
 
 
 def identity_mask(bk, form):
-    """Records that ARE the stored identity: XYZZ with ZZ = 0; Edwards (0 : c : 0 : c)."""
+    """Records that ARE the stored identity: XYZZ with ZZ = 0; Edwards (0 : c : 0 : c), on either curve."""
+    nl = LIMBS[form]
     if form == FORM_XYZZ:
-        return ~bk[:, 26:39].any(axis=1)
-    return ~bk[:, 0:13].any(axis=1) & ~bk[:, 26:39].any(axis=1) & (bk[:, 13:26] == bk[:, 39:52]).all(axis=1)
+        return ~bk[:, 2 * nl : 3 * nl].any(axis=1)
+    return ~bk[:, 0:nl].any(axis=1) & ~bk[:, 2 * nl : 3 * nl].any(axis=1) & (bk[:, nl : 2 * nl] == bk[:, 3 * nl : 4 * nl]).all(axis=1)
 
 
 def decode(words, form):
+    if form == FORM_ED:
+        return M.ed_record_affine(words)
     return util.affine_from_xyzz_words(words) if form == FORM_XYZZ else util.affine_from_te_ext_words(words)
+
+
+def model_identity(form):
+    """What stage_model.bucket_sum returns for a row that adds up to nothing: None on G1, the point (0, 1) on Edwards-BLS12
+    (a record that decodes to it counts as the identity whichever representative of zero it stores)."""
+    return R.ED_ID if form == FORM_ED else None
+
+
+def wire_points(points_wire, form):
+    return [(int.from_bytes(points_wire[64 * i : 64 * i + 32], "little"), int.from_bytes(points_wire[64 * i + 32 : 64 * i + 64], "little"))
+            for i in range(len(points_wire) // 64)] if form == FORM_ED else R.decode_points(points_wire)
 
 
 def slot_of(g, slot):
@@ -51,7 +70,7 @@ def slot_of(g, slot):
 
 
 def values_below(limbs, hi):
-    """value(limbs) < hi for every row of an (m, 13) limb array: carries propagated in 64-bit words, then compared with
+    """value(limbs) < hi for every row of an (m, 13) or (m, 9) limb array: carries propagated in 64-bit words, then compared with
     the limbs of hi from the top down -- lazy_model.value without a Python integer per record."""
     lb, mask, nl = lazy_model.LB, lazy_model.MASK, limbs.shape[1]
     l = limbs.astype(np.uint64)
@@ -112,14 +131,16 @@ def check_slot(engine, slot, g, cols, c, points, n, form, small=False, key_max=N
     assert np.array_equal(sign[entry], (vi >> 31).astype(bool)), tag  # ... with its sign
     # buckets: bucket t (key t + 1) of every row
     bk = st["buckets"]
+    nl, ed = LIMBS[form], form == FORM_ED
+    assert bk.shape == (1 << L, 4 * nl), tag
     lens = c.counts[1:]
     ident = identity_mask(bk, form)
     assert ident[lens == 0].all(), (tag, "a bucket without entries is not the stored identity")
     for t in np.nonzero(ident & (lens > 0))[0]:  # entries that cancel (repeated points): the model must agree
-        assert M.bucket_sum(points, c.row(int(t) + 1), g, n) is None, (tag, int(t))
+        assert M.bucket_sum(points, c.row(int(t) + 1), g, n, ed=ed) == model_identity(form), (tag, int(t))
     live = ~ident
     for ci, shape in enumerate(coordinate_shapes(form)):  # the representation contract, every coordinate of every record
-        limbs = bk[live][:, 13 * ci : 13 * ci + 13]
+        limbs = bk[live][:, nl * ci : nl * ci + nl]
         assert (limbs <= np.array(shape.box, dtype=np.uint64)).all(), (tag, "coordinate %d outside its stored box" % ci)
         assert values_below(limbs, shape.hi).all(), (tag, "coordinate %d at or above its stored bound" % ci)
     multi, single = np.nonzero(live & (lens >= 2))[0], np.nonzero(live & (lens == 1))[0]
@@ -131,7 +152,7 @@ def check_slot(engine, slot, g, cols, c, points, n, form, small=False, key_max=N
     cache = {}
     for t in chosen:
         words = bk[t]
-        assert decode(words, form) == M.bucket_sum(points, c.row(int(t) + 1), g, n, cache), (tag, int(t), int(lens[t]))
+        assert decode(words, form) == M.bucket_sum(points, c.row(int(t) + 1), g, n, cache, ed=ed), (tag, int(t), int(lens[t]))
     return info
 
 
@@ -149,7 +170,7 @@ def tracked_key_max(g, cols):
 def run_case(engine, call, g, scalars, points_wire, form, slots, other_scalars, expected, small=(), label="", reruns=0):
     """call(scalars) runs the MSM under test; first once with other_scalars (same size, same context)."""
     n = len(scalars)
-    points = R.decode_points(points_wire)
+    points = wire_points(points_wire, form)
     cols, flags = M.digit_matrix(scalars, g)
     assert flags == 0, "the case's scalars must fit the geometry it promises"
     assert len(other_scalars) == n and list(other_scalars) != list(scalars) and sorted(other_scalars) != sorted(scalars), "the call before runs other scalars"

@@ -204,3 +204,110 @@ def test_digit_matrix_layouts_and_csr():
     assert M.entry_base(pts, 4 * 7 + 2, M.wide13(), 4) == R.mul(pts[2], 1 << M.wide_offset(7)) and M.wide_offset(7) == 139
     assert M.bucket_sum(pts, [(0, 0), (1, 1), (3, 0)], M.equal16(), 4) == R.add(R.add(pts[0], R.neg(pts[1])), pts[3])
     assert M.key_max_word(np.array([5, 9], dtype=np.uint16), 0, True) == 9 | M.KEY_TRACKED | M.KEY_UNSIGNED
+
+
+# ---- Edwards-BLS12: the model of tests/test_ed_stages_gpu.py and the vectors of tests/ed_curve_points.py ----
+import ed_curve_points as V  # noqa: E402
+from check_vectors import ed_low_order_points  # noqa: E402
+
+
+def ed_weighted_sum(points, ks, g):
+    """sum over slots of 2^offset sum over keys of key * bucket_sum: what the reduction and the host tail make of the buckets."""
+    n = len(ks)
+    cols, flags = M.digit_matrix(ks, g)
+    assert flags == 0
+    total = R.ED_ID
+    for slot, s in enumerate(g.slots):
+        c = M.csr(cols[slot], g.bucket_log, s.bias, s.key_unsigned)
+        acc = R.ED_ID
+        for key in np.nonzero(c.counts)[0]:
+            if key:
+                acc = R.ed_add(acc, R.ed_mul(M.bucket_sum(points, c.row(int(key)), g, n, ed=True), int(key)))
+        total = R.ed_add(total, R.ed_mul(acc, 1 << s.offset))
+    return total
+
+
+@pytest.mark.parametrize("name", ["even16", "equal16"])
+def test_ed_model_buckets_add_up_to_the_naive_msm(name):
+    """48 points with every low-order class among them: the weighted sum of the model's bucket sums is pyref.ed_msm_naive."""
+    points, ks, planted, expected = V.every_curve_point(48, 7)
+    low = [R.ED_ID] + ed_low_order_points()
+    assert all(t in points for t in low) and any(R.ed_mul(pt, R.ED_SUBGROUP) not in low[:1] + [pt] and pt not in low for pt in points)  # P + T too
+    assert R.ed_msm_naive(points, ks) == expected
+    assert ed_weighted_sum(points, ks, FULL[name]) == expected
+    assert M.bucket_sum(points, [], FULL[name], 48, ed=True) == R.ED_ID
+    assert M.bucket_sum(points, [(3, 0), (3, 1)], FULL[name], 48, ed=True) == R.ED_ID and M.entry_base(points, 5, FULL[name], 48, ed=True) == points[5]
+
+
+def test_ed_oracle_and_closed_form_agree_with_pyref_on_low_order_inputs():
+    """The C oracle (its windowed MSM and its naive one) and the closed form over the progression equal pyref.ed_msm_naive
+    on the vectors the GPU tests feed: every curve point, low-order points alone, a total that is the identity; and the
+    oracle's point generator is the progression the closed form assumes."""
+    oracle = util.load_oracle()
+    cases = []
+    for n in (1, 2, 63, 65):
+        points, ks, _, expected = V.every_curve_point(n, 1)
+        cases.append((points, ks, expected))
+    points, ks = V.only_low_order(64, 1)
+    cases.append((points, ks, None))
+    points, ks = V.total_is_identity(64, 1)
+    cases.append((points, ks, R.ED_ID))
+    for points, ks, expected in cases:
+        exp = R.ed_msm_naive(points, ks)
+        assert expected is None or exp == expected
+        pts_b, ks_b = R.ed_encode_points(points), R.encode_scalars(ks)
+        assert util.oracle_ed_msm(oracle, pts_b, ks_b) == R.ed_encode_result(exp)
+        assert util.oracle_ed_msm(oracle, pts_b, ks_b, fn="oracle_ed_msm_naive") == R.ed_encode_result(exp)
+    # the larger vectors of the GPU tests: the closed form against the oracle (pinned to pyref just above)
+    for n in (257, 600, 1000):
+        points, ks, _, expected = V.every_curve_point(n, 1)
+        assert util.oracle_ed_msm(oracle, R.ed_encode_points(points), R.encode_scalars(ks)) == R.ed_encode_result(expected), n
+    a0, d = 0xED57A6E5, 0xD15717C7
+    assert util.oracle_ed_gen_points(oracle, 40, a0, d) == R.ed_encode_points(V.subgroup_points(40, a0, d))
+    ks = V.uniform_scalars(40, 0)
+    assert V.progression_msm(a0, d, ks) == R.ed_msm_naive(V.subgroup_points(40, a0, d), ks)
+
+
+def test_ed_record_decode():
+    """ed_record_affine: 9-limb coordinates in Montgomery form with radix 2^261, lazy residues (zero as 0 or as q, values up
+    to q + e), any projective factor."""
+    fq = M.fq_model()
+    assert (fq.N, fq.P, fq.R) == (9, R.Q, 1 << 261)
+    rnd = random.Random(0xEDDEC)
+    t2, t4a, _ = ed_low_order_points()
+
+    def record(pt, z, lift):
+        x, y = pt
+        vals = [x * z % R.Q, y * z % R.Q, x * y * z % R.Q, z % R.Q]
+        words = []
+        for v, up in zip(vals, lift):
+            m = v * fq.R % R.Q
+            if up and m + R.Q < fq.shapes["stored"].hi:  # the same residue one modulus higher where q + e admits it: zero as q
+                m += R.Q
+            words += [(m >> (29 * j)) & ((1 << 29) - 1) for j in range(8)] + [m >> 232]
+        return np.array(words, dtype=np.uint32)
+
+    assert R.Q < fq.shapes["stored"].hi
+    for pt in [R.ED_ID, t2, t4a, R.ED_G, R.ed_add(R.ED_G, t4a), R.ed_mul(R.ED_G, 12345)]:
+        for lift in ((0, 0, 0, 0), (1, 0, 1, 0), (1, 1, 1, 1)):
+            assert M.ed_record_affine(record(pt, rnd.randrange(1, R.Q), lift)) == pt
+    bad = record(R.ED_G, 5, (0, 0, 0, 0))
+    bad[9] ^= 1
+    with pytest.raises(AssertionError):
+        M.ed_record_affine(bad)
+
+
+def test_ed_stage_cases_meet_the_decode_floors():
+    """What tests/test_ed_stages_gpu.py asserts again before it touches the GPU, here without one: every slot of its
+    5000-point cases that is not listed as small offers 300 non-empty buckets and 50 rows of two and more entries (about
+    340 such rows are expected among 5000 uniform entries over 2^15 keys), and its case scalars fit their geometry."""
+    cases = [(M.even16(), V.uniform_scalars(5000, 1)), (M.even16(), V.uniform_scalars(5000, 2)), (M.equal16(), R.rand_scalars(0xED3E12, 5000))]
+    for g, ks in cases:
+        cols, flags = M.digit_matrix(ks, g)
+        assert flags == 0
+        for slot in (0, 8, 12, 15):
+            lens = M.csr(cols[slot], 15, g.slots[slot].bias).counts[1:]
+            assert int((lens > 0).sum()) >= 300 and int((lens >= 2).sum()) >= 50, (g.name, slot)
+    for ks in (V.few_distinct_scalars(3000, 5, 8), V.one_long_row_scalars(1100, 600, 10), V.every_curve_point(600, 1)[1]):
+        assert M.digit_matrix(ks, M.even16())[1] == 0
+    assert len([k for k in V.even_edge_scalars() if M.recode(k, M.even16()).flags == 0]) == 13  # the others rerun

@@ -267,10 +267,13 @@ int msm377_ctx_set_stage_capture(msm377_ctx* ctx, int enabled) {
   return MSM377_OK;
 }
 
+// The fixed-size read-back and msm377_ctx_get_stage_form describe G1 records only (52 words); Edwards-BLS12 records are read as run.
+static bool is_g1_form(int form) { return form == MSM377_STAGE_FORM_XYZZ || form == MSM377_STAGE_FORM_TE; }
+
 int msm377_g1_read_stage(msm377_ctx* ctx, uint32_t slot, uint16_t* digits, uint32_t* row_ptr, uint32_t* val_idx, uint32_t* buckets) {
   if (!ctx) return MSM377_EINVAL;
   // capture mode 1 only: the sizes below are those of its route; under mode 2 a call lays its stages out as it runs
-  if (ctx->capture != 1 || ctx->last_n == 0 || slot >= ctx->last_geom_windows || ctx->last_form < 0 || ctx->last_glv) {
+  if (ctx->capture != 1 || ctx->last_n == 0 || slot >= ctx->last_geom_windows || !is_g1_form(ctx->last_form) || ctx->last_glv) {
     ctx->err = "no captured stage data for that window slot (capture mode 2 is read with msm377_g1_read_stage_ex)";
     return MSM377_ESTATE;
   }
@@ -320,20 +323,22 @@ int msm377_g1_read_stage_ex(msm377_ctx* ctx, uint32_t slot, msm377_stage_info* i
   if (row_ptr) HIP_TRY(ctx, hipMemcpy(row_ptr, ctx->d_row_ptr + (size_t)slot * out.row_ptr_len, (size_t)out.row_ptr_len * 4, hipMemcpyDeviceToHost));
   if (val_idx) HIP_TRY(ctx, hipMemcpy(val_idx, ctx->d_val_idx + (size_t)slot * cols, cols * 4, hipMemcpyDeviceToHost));
   if (buckets) {
-    uint32_t* tmp = (uint32_t*)malloc(records * BKT_WORDS * 4);
+    // records as the pass stored them (four coordinate slots of coord_words words) -> 4 x limbs packed words: 52 for G1, 36 for Edwards-BLS12
+    const size_t cw = sl.coord_words, nl = sl.limbs, bw = 4 * cw;
+    uint32_t* tmp = (uint32_t*)malloc(records * bw * 4);
     if (!tmp) return MSM377_ENOMEM;
-    hipError_t e = hipMemcpy(tmp, ctx->d_buckets_snap + (size_t)slot * records * BKT_WORDS, records * BKT_WORDS * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess)  // 64-word records (four 16-word coordinate slots) -> the 52 packed words of the ABI
+    hipError_t e = hipMemcpy(tmp, ctx->d_buckets_snap + (size_t)slot * records * bw, records * bw * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess)
       for (size_t t = 0; t < records; t++)
-        for (uint32_t c = 0; c < 4; c++)
-          for (uint32_t j = 0; j < 13; j++) buckets[t * PT_WORDS + c * 13 + j] = tmp[t * BKT_WORDS + c * 16 + j];
+        for (size_t c = 0; c < 4; c++)
+          for (size_t j = 0; j < nl; j++) buckets[(t * 4 + c) * nl + j] = tmp[t * bw + c * cw + j];
     free(tmp);
     HIP_TRY(ctx, e);
   }
   return MSM377_OK;
 }
 
-int msm377_ctx_get_stage_form(const msm377_ctx* ctx) { return (ctx && ctx->capture && ctx->last_n) ? ctx->last_form : -1; }
+int msm377_ctx_get_stage_form(const msm377_ctx* ctx) { return (ctx && ctx->capture && ctx->last_n && is_g1_form(ctx->last_form)) ? ctx->last_form : -1; }
 
 int msm377_g1_xyzz_to_affine(const uint32_t xyzz[52], uint8_t out_xy[96]) {
   if (!xyzz || !out_xy) return MSM377_EINVAL;

@@ -86,6 +86,7 @@ struct StageLayout {
   msm377_stage_info info = {};
   const void* d_digits = nullptr;       // the digit matrix the decomposition wrote: ctx->d_digits (u16) or ctx->wide.digits (u32)
   const uint32_t* d_key_max = nullptr;  // the call's key_max words, or null where the sort reads none
+  uint32_t coord_words = 16, limbs = 13;  // a bucket record of the pass: four coordinate slots of coord_words words, `limbs` of them used
 };
 
 struct msm377_ctx {

@@ -114,7 +114,7 @@ struct EdDev {
   static constexpr uint32_t OUT_WORDS = 32;  // a partial-record point: 4 coordinates x 8 u32 (host-tail format)
   static constexpr uint32_t RECORD_TAG = 0;
   static constexpr int MADD_PRODUCTS = 7;
-  static constexpr int FORM_ID = -1;  // no stage read-back for the Edwards-BLS12 curve
+  static constexpr int FORM_ID = MSM377_STAGE_FORM_ED;
   using F = Fq;
   static constexpr uint32_t NL = 9, NW32 = 8;
   static __device__ __forceinline__ Fq::El to64() { return Fq::from_const(EdConsts::TO64); }

@@ -381,10 +381,10 @@ struct Phase {
 
 // What the host needs of the curve policies of a pass: CV's form and buckets and records out, BP's base records in;
 // quad_items: k_accumulate_quad serves the pair (TeDev on its own projective records).
-struct CurveDims { int form; uint32_t bkt_words, pt_words, out_words, rec_words; bool quad_items; };
+struct CurveDims { int form; uint32_t bkt_words, coord_words, limbs, pt_words, out_words, rec_words; bool quad_items; };
 template <class CV, class BP>
 constexpr CurveDims curve_dims() {
-  return {CV::FORM_ID, CV::BKT_WORDS, CV::PT_WORDS, CV::OUT_WORDS, BP::REC_WORDS, std::is_same<BP, CV>::value && std::is_same<CV, TeDev>::value};
+  return {CV::FORM_ID, CV::BKT_WORDS, CV::COORD_WORDS, CV::NL, CV::PT_WORDS, CV::OUT_WORDS, BP::REC_WORDS, std::is_same<BP, CV>::value && std::is_same<CV, TeDev>::value};
 }
 
 // What ONE enqueue_windows call launches with: every size, route flag and per-slot word its stages read, derived once by
@@ -491,6 +491,7 @@ int enqueue_decompose(msm377_ctx* ctx, const LaunchRecord& k, const uint32_t* d_
   if (k.is_short && !k.narrow) info.key_unsigned[k.slots - 1] = 1u;  // (KEY_UNSIGNED in that slot's key_max word)
   ctx->stage.d_digits = k.wide ? (const void*)ctx->wide.digits : (const void*)ctx->d_digits;
   ctx->stage.d_key_max = (k.wide || k.narrow) ? nullptr : k.key_max;  // k_local_sort_lds of the wide table and k_small_sort read none
+  ctx->stage.coord_words = k.cv.coord_words, ctx->stage.limbs = k.cv.limbs;  // the bucket records of the pass: four slots of coord_words, `limbs` used
   return MSM377_OK;
 }
 
@@ -685,8 +686,9 @@ int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scala
   HIP_TRY(ctx, hipEventRecord(ctx->done_ev[slot], st));
   ctx->last_n = k.n, ctx->last_glv = k.glv, ctx->last_form = k.cv.form;
   ctx->last_geom_windows = k.slots, ctx->last_geom_log = k.L;
-  // A whole call in one piece from window 0 in a form with read-backs: the layout written at the decomposition describes it.
-  ctx->stage.valid = ctx->capture && ph.front && !ph.into && wb == 0 && k.cv.form >= 0;
+  // A whole call in one piece from window 0: the layout written at the decomposition describes it.  Capture mode 1 is G1's:
+  // an Edwards-BLS12 call is described as run only (mode 2).
+  ctx->stage.valid = ctx->capture && ph.front && !ph.into && wb == 0 && (k.cv.form != MSM377_STAGE_FORM_ED || ctx->capture == 2);
   return MSM377_OK;
 }
 
@@ -1486,7 +1488,7 @@ int ed_msm(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint6
   if (n == 0) return ed_msm_device(ctx, nullptr, nullptr, 0, out_xy);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   ctx->resident.clear();  // (both paths upload into d_raw_points)
-  if (n >= ctx->upload_chunk_min) {  // chunks of points, like g1_msm: a chunk computes while the next one uploads
+  if (n >= ctx->upload_chunk_min && !ctx->capture) {  // chunks of points, like g1_msm: a chunk computes while the next one uploads (stage read-backs describe the plain row layout)
     const WindowPlan plan = plan_whole16(ctx, ED_TAIL);
     int rc = run_chunked_upload<EdDev>(ctx, points, scalars, n, plan);
     if (rc == MSM377_OK) rc = wait_windows(ctx, 0);

@@ -15,6 +15,8 @@ NUM_WINDOWS = 16
 WINDOW_BITS = 16
 PARTIAL_POINTS = 16
 POINT_WORDS = 52  # a bucket point in the device format (stage read-backs)
+ED_POINT_WORDS = 36  # ... of an Edwards-BLS12 call: four coordinates of 9 limbs
+STAGE_FORM_XYZZ, STAGE_FORM_TE, STAGE_FORM_ED = 0, 1, 2  # MSM377_STAGE_FORM_*: StageInfo.form
 RECORD_POINT_WORDS = 48  # a point of a window partial record (host-tail format)
 WINDOW_PARTIAL_BYTES = PARTIAL_POINTS * RECORD_POINT_WORDS * 4
 NUM_BUCKETS = 32768
@@ -784,7 +786,8 @@ class MsmEngine:
 
     def read_stage_ex(self, slot: int, want=("digits", "row_ptr", "val_idx", "buckets")):
         """(StageInfo, dict of numpy arrays) for window slot ``slot`` of the last call's last pass, at the sizes the
-        library reports (msm377_g1_read_stage_ex).  MsmError(ESTATE) when nothing describable was captured."""
+        library reports (msm377_g1_read_stage_ex): a G1 call, or under mode 2 an Edwards-BLS12 call (form STAGE_FORM_ED,
+        buckets of 36 words: X, Y, T, Z of 9 limbs).  MsmError(ESTATE) when nothing describable was captured."""
         import numpy as np
 
         raw = _StageInfoStruct()
@@ -796,7 +799,7 @@ class MsmEngine:
             "digits": np.empty(info.columns, dtype=np.uint32 if info.digit_bytes == 4 else np.uint16),
             "row_ptr": np.empty(info.row_ptr_len, dtype=np.uint32),
             "val_idx": np.empty(info.columns, dtype=np.uint32),
-            "buckets": np.empty((info.bucket_records, POINT_WORDS), dtype=np.uint32),
+            "buckets": np.empty((info.bucket_records, ED_POINT_WORDS if info.form == STAGE_FORM_ED else POINT_WORDS), dtype=np.uint32),
         }
         res = {k: v for k, v in bufs.items() if k in want}
         if res:
