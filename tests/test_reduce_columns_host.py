@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 COLUMN_LEVELS_MAX = 4  # reduce.hpp
-COOP_THREADS = 131072  # context.hpp
+COOP_THREADS = 131072  # knobs.hpp
 MASK = (1 << 64) - 1
 
 

@@ -6,7 +6,7 @@ root=$(cd "$(dirname "$0")/.." && pwd)
 src=$root/webgpu-msm-bls12-377_amd/csrc
 out=$root/ab
 mkdir -p $out/obj_$name
-for tu in sequencer host_tail capi; do
+for tu in sequencer host_tail capi context; do
   hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wall -Wno-unused-function "$@" -c -o $out/obj_$name/$tu.o $src/$tu.hip &
 done
 wait

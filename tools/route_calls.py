@@ -2,7 +2,11 @@
 """One call of every route of the stage sequencer, fixed seeds, a few thousand points, contexts of 2^17 points; every
 answer is checked against the CPU oracle (pyref's group law where a point lies outside the prime-order subgroup).  Prints
 "ok" and nothing else.  Meant to run under a kernel trace, once per build (MSM377_LIB), so that the launches of two builds
-can be compared route by route: the order of the calls below is the order of the trace."""
+can be compared route by route: the order of the calls below is the order of the trace.
+  route_calls.py            every route
+  route_calls.py existing   every route but the last one (the twin's knobs)
+  route_calls.py twin       that one alone: a batch of 4 on a context whose knobs differ from the environment's when its
+                            twin is made -- the twin's half runs its owner's launch shapes"""
 import os, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,6 +22,7 @@ CAP, N = 1 << 17, 2049
 BIG = (1 << 253) + 12345  # fits sixteen equal windows only
 T2 = (R.P - 1, 0)  # a point of order two: no Edwards record
 oracle = util.load_oracle()
+which = sys.argv[1] if len(sys.argv) > 1 else "all"
 
 
 def engine(**env):
@@ -58,6 +63,27 @@ def with_t2(i):
 
 d_p, d_s, d_big = dev(pts), dev(ks), dev(ks_big)
 pp, sp, bp = d_p.data_ptr(), d_s.data_ptr(), d_big.data_ptr()
+ks2 = R.encode_scalars(R.rand_scalars(0xBA7C4, N))
+exp2 = util.oracle_msm(oracle, pts, ks2)
+d_b = dev(ks + ks2 + ks2 + ks)
+
+
+def twin_route():
+    """The variables are gone when the first batch of 4 makes the twin: both halves reduce with coop_threads = 2^20.  The
+    column launches take the first quad level as an argument, so (kernel, grid, workgroup) shows the knob only in the
+    second context, whose levels run one launch each: k_tree_step below that level, k_tree_step_quad from it on."""
+    for env in ({"MSM377_COOP_THREADS": 1048576}, {"MSM377_COOP_THREADS": 1048576, "MSM377_REDUCE_COLUMNS": 0}):
+        owner = engine(**env)
+        owner.set_narrow_max(0)
+        owner.set_bases(pts)
+        expect(owner.msm_fixed_base_batch_device(d_b.data_ptr(), N, 4), [exp, exp2, exp2, exp], "batch of 4, knobs of the owner: %s" % sorted(env))
+        owner.close()
+
+
+if which == "twin":
+    twin_route()
+    print("ok")
+    sys.exit(0)
 eng = engine()
 
 # per-call Edwards form: narrow, even16, each with a scalar of 2^253 and more
@@ -95,10 +121,7 @@ except msm.MsmError as e:
     expect(e.code, ESCALAR, "broken promise")
 
 # batches over a resident set: 2 on one context, 4 on the twin as well
-ks2 = R.encode_scalars(R.rand_scalars(0xBA7C4, N))
-exp2 = util.oracle_msm(oracle, pts, ks2)
 eng.set_bases(pts)
-d_b = dev(ks + ks2 + ks2 + ks)
 expect(eng.msm_fixed_base_batch_device(d_b.data_ptr(), N, 2), [exp, exp2], "batch of 2")
 expect(eng.msm_fixed_base_batch_device(d_b.data_ptr(), N, 4), [exp, exp2, exp2, exp], "batch of 4")
 
@@ -182,4 +205,6 @@ for mode in (1, 2):
     expect(plain.msm_device(pp, sp, N), exp, "timing %d" % mode)
 plain.set_timing(0)
 plain.close()
+if which == "all":
+    twin_route()
 print("ok")

@@ -43,13 +43,13 @@ template <class Pt, class Extra, class PieceFn, class AddFn>
 int tail_horner_mt(msm377_ctx* ctx, PieceFn piece, AddFn add, int positions, Pt* out, std::shared_ptr<TailState<Pt, Extra>> st) {
   constexpr int MAXC = TailPool::WORKERS + 1;
   TailPool& pool = ctx->tail_pool;
-  const int want = std::max(1, std::min(ctx->tail_threads, MAXC));
+  const int want = std::max(1, std::min(ctx->knobs.tail_threads, MAXC));
   if (want > 1) pool.start();
   int worker_of[MAXC];  // helper threads that are free to take a piece (one that still holds a job it never started is not)
   const int helpers = want > 1 ? pool.idle_workers(worker_of, want - 1) : 0;
   const int used = tail_split(positions, helpers + 1, st->bounds);
   // MSM377_TAIL_TRACE=1: per-piece start / end (us after the call) and CPU, on stderr
-  const bool trace = ctx->tail_trace;
+  const bool trace = ctx->knobs.tail_trace;
   const int64_t t_call = trace ? TailPool::now_ns() : 0;
   auto chain = [st, trace, piece](int k) {
     if (trace) st->mark[k].t0 = TailPool::now_ns(), st->mark[k].cpu = sched_getcpu();
@@ -80,7 +80,7 @@ struct TeFlags {
 };
 struct NoExtra {};
 
-inline bool single_threaded(const msm377_ctx* ctx) { return ctx->tail_threads <= 1 || ctx->tail_pool.poisoned.load(); }
+inline bool single_threaded(const msm377_ctx* ctx) { return ctx->knobs.tail_threads <= 1 || ctx->tail_pool.poisoned.load(); }
 
 }  // namespace
 
@@ -145,18 +145,18 @@ int ed_tail(msm377_ctx* ctx, const uint32_t* partials, uint8_t out_xy[64], int s
 // Montgomery radix (G1Consts64::TO29) as 12 plain words each.
 void invert_block_products(msm377_ctx* ctx, uint32_t b0, uint32_t b1) {
   if (b0 >= b1) return;
-  Fp64::El* pre = ctx->aff_scratch.data();
+  Fp64::El* pre = ctx->aff.scratch.data();
   Fp64::El acc = Fp64::one();
   for (uint32_t b = b0; b < b1; b++) {
     pre[b] = acc;
-    acc = Fp64::mul(acc, Fp64::from_words32(ctx->h_aff_prod + (size_t)b * 12));
+    acc = Fp64::mul(acc, Fp64::from_words32(ctx->aff.h_prod + (size_t)b * 12));
   }
   Fp64::El inv = Fp64::inv(acc);
   const Fp64::El to29 = Fp64::from_const(G1Consts64::TO29);
   for (uint32_t b = b1; b-- > b0;) {
     const Fp64::El mine = Fp64::mul(Fp64::mul(inv, pre[b]), to29);  // a plain integer now: x 2^406 mod p
-    inv = Fp64::mul(inv, Fp64::from_words32(ctx->h_aff_prod + (size_t)b * 12));
-    words_from_fp64(mine, ctx->h_aff_inv + (size_t)b * 12);
+    inv = Fp64::mul(inv, Fp64::from_words32(ctx->aff.h_prod + (size_t)b * 12));
+    words_from_fp64(mine, ctx->aff.h_inv + (size_t)b * 12);
   }
 }
 
@@ -166,10 +166,10 @@ int invert_block_products_mt(msm377_ctx* ctx, uint32_t b0, uint32_t b1) {
     TailPool& pool = ctx->tail_pool;
     pool.start();
     int worker_of[TailPool::WORKERS + 1];
-    const int parts = 1 + pool.idle_workers(worker_of, std::min(ctx->tail_threads, TailPool::WORKERS + 1) - 1);
+    const int parts = 1 + pool.idle_workers(worker_of, std::min(ctx->knobs.tail_threads, TailPool::WORKERS + 1) - 1);
     const uint32_t per = (nblk + parts - 1) / parts;
     // shares (tail_pool.hpp): the caller takes over a range whose helper has not started on it.  A helper that comes back
-    // late finds its share claimed and touches nothing of this call (ctx->aff_scratch, h_aff_inv belong to the next one by then).
+    // late finds its share claimed and touches nothing of this call (ctx->aff.scratch, aff.h_inv belong to the next one by then).
     auto shares = std::make_shared<TailPool::Shares>();
     auto range = [ctx, per, b0, b1](int k) { invert_block_products(ctx, std::min(b1, b0 + (uint32_t)(k + 1) * per), std::min(b1, b0 + (uint32_t)(k + 2) * per)); };
     for (int k = 0; k + 1 < parts; k++) pool.post_share(worker_of[k], shares, k, [range, k] { range(k); });

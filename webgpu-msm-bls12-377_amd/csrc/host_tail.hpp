@@ -20,7 +20,7 @@ int te_tail(msm377_ctx* ctx, const uint32_t* partials, uint8_t out_xy[96], int n
 int xyzz_tail(msm377_ctx* ctx, const uint32_t* partials, uint8_t out_xy[96], int short_from = 0, int num_windows = MSM377_NUM_WINDOWS);  // 16-bit windows
 int ed_tail(msm377_ctx* ctx, const uint32_t* partials, uint8_t out_xy[64], int short_from = 0);  // Edwards-BLS12: a complete law, nothing to check
 
-// Inverses of the block products [b0, b1) the conversion's way up left in ctx->h_aff_prod, into ctx->h_aff_inv
+// Inverses of the block products [b0, b1) the conversion's way up left in ctx->aff.h_prod, into ctx->aff.h_inv
 // (Montgomery's trick with one Fermat inversion per thread; results re-based to the device's Montgomery radix).
 int invert_block_products_mt(msm377_ctx* ctx, uint32_t b0, uint32_t b1);
 // The same for blocks [b0, b1) on the calling thread.

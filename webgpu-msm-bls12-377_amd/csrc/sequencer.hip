@@ -1,7 +1,8 @@
 // msm377: BLS12-377 G1 multi-scalar multiplication for MI355X (gfx950), C ABI in include/msm377.h.
 // This translation unit is the stage sequencer: it owns every kernel launch (kernels/*.hpp are compiled here and only
 // here), the stream / event choreography of a call and the entry points' control flow (fallbacks, chunked uploads,
-// batches, window shards).  The C ABI itself is capi.hip, the host tail host_tail.hip, the context context.hpp.
+// batches, window shards).  The C ABI itself is capi.hip, the host tail host_tail.hip, the context context.hpp and
+// its life cycle (create, destroy, every allocation) context.hip.
 //
 // Pipeline (each stage names the reference code it replaces; paths relative to /root/reference/src/submission/):
 //   kernels/convert.hpp     k_affine_up / host inversion / k_affine_down (n >= 2^20, resident tables), k_convert_bases (otherwise)
@@ -58,20 +59,6 @@
 #include "kernels/batch_mul_var.hpp"
 #include "kernels/wide.hpp"
 
-bool WideBuffers::ensure(uint64_t n) {
-  using namespace msm377;
-  if (cap >= n) return true;
-  release();
-  if (hipMalloc((void**)&digits, (size_t)WIDE_WINDOWS * n * 4) == hipSuccess && hipMalloc((void**)&temp, (size_t)WIDE_WINDOWS * n * sizeof(SortElem)) == hipSuccess &&
-      hipMalloc((void**)&counts, WC_WORDS * 4) == hipSuccess) {
-    cap = n;
-    return true;
-  }
-  release();
-  (void)hipGetLastError();
-  return false;
-}
-
 namespace msm377 {
 namespace eng {
 
@@ -85,8 +72,8 @@ bool hip_ok(msm377_ctx* ctx, int hip_error, const char* what) {
 namespace {
 
 void note_fallback(msm377_ctx* ctx, uint32_t mask) {
-  ctx->fallback_count++;
-  ctx->fallback_mask = mask;
+  ctx->fallback.count++;
+  ctx->fallback.mask = mask;
 }
 
 // Pageable host memory -> device through a pinned staging buffer: four workers copy ~4 MB pieces
@@ -104,7 +91,6 @@ struct HipFail {
   }
 };
 int h2d_staged(msm377_ctx* ctx, void* d_dst, const uint8_t* src, size_t bytes, size_t stage_off, HipFail* fail = nullptr) {
-  using msm377::eng::reserve_host_staging;
 #define H2D_TRY(call)                \
   do {                               \
     const hipError_t e_ = (call);    \
@@ -121,7 +107,7 @@ int h2d_staged(msm377_ctx* ctx, void* d_dst, const uint8_t* src, size_t bytes, s
     H2D_TRY(hipMemcpy(d_dst, src, bytes, hipMemcpyHostToDevice));
     return MSM377_OK;
   }
-  if (!ctx->h_stage && reserve_host_staging(ctx) != MSM377_OK) {
+  if (!ctx->staging.h_stage && reserve_host_staging(ctx) != MSM377_OK) {
     (void)hipGetLastError();
     H2D_TRY(hipMemcpy(d_dst, src, bytes, hipMemcpyHostToDevice));  // fall back to the runtime's pageable path
     return MSM377_OK;
@@ -133,7 +119,7 @@ int h2d_staged(msm377_ctx* ctx, void* d_dst, const uint8_t* src, size_t bytes, s
   size_t npieces = (bytes + PIECE - 1) / PIECE;
   npieces = (npieces + NT - 1) / NT * NT;
   const size_t piece = ((bytes + npieces - 1) / npieces + 4095) & ~(size_t)4095;
-  uint8_t* stage = ctx->h_stage + stage_off;
+  uint8_t* stage = ctx->staging.h_stage + stage_off;
   hipError_t errs[NT_MAX + 1];
   std::thread workers[NT_MAX];
   const int device = ctx->device;
@@ -146,9 +132,9 @@ int h2d_staged(msm377_ctx* ctx, void* d_dst, const uint8_t* src, size_t bytes, s
       if (c >= npieces || off >= bytes || e != hipSuccess) break;
       const size_t len = (bytes - off < piece) ? bytes - off : piece;
       memcpy(stage + off, src + off, len);
-      e = hipMemcpyAsync((uint8_t*)d_dst + off, stage + off, len, hipMemcpyHostToDevice, ctx->copy_stream[t]);
+      e = hipMemcpyAsync((uint8_t*)d_dst + off, stage + off, len, hipMemcpyHostToDevice, ctx->staging.copy_stream[t]);
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->copy_stream[t]);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->staging.copy_stream[t]);
     errs[t] = e;
   };
   for (int t = 0; t <= NT; t++) errs[t] = hipSuccess;
@@ -208,17 +194,17 @@ int affine_convert_begin(msm377_ctx* ctx, const uint32_t* d_raw, uint64_t n, con
   if (n == 0) return MSM377_OK;
   const uint32_t nblk = affine_blocks(n);
   if (ctx->timing == 1) (void)hipEventRecord(ctx->ev[MSM377_STAGE_CONVERT][0], ctx->stream2);
-  __atomic_store_n(ctx->h_aff_flag, 0u, __ATOMIC_RELEASE);
+  __atomic_store_n(ctx->aff.h_flag, 0u, __ATOMIC_RELEASE);
   if (clear_err) hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(256), 0, ctx->stream2, (uint32_t*)(ctx->d_err + 2), 1u, (uint32_t*)nullptr, 0u);
   if (prev_window_records)
     hipLaunchKernelGGL(k_affine_up<AffDoublingSource>, dim3(nblk), dim3(AFF_THREADS), 0, ctx->stream2, AffDoublingSource{prev_window_records, doublings}, n,
-                       ctx->d_aff_stash, ctx->d_aff_trees, ctx->dm_aff_prod, ctx->dm_aff_flag, ctx->d_aff_count, ctx->d_err + 2, ctx->conv_wave_prio);
+                       ctx->aff.d_stash, ctx->aff.d_trees, ctx->aff.dm_prod, ctx->aff.dm_flag, ctx->aff.d_count, ctx->d_err + 2, ctx->knobs.conv_wave_prio);
   else
-    hipLaunchKernelGGL(k_affine_up<AffWireSource>, dim3(nblk), dim3(AFF_THREADS), 0, ctx->stream2, AffWireSource{d_raw}, n, ctx->d_aff_stash, ctx->d_aff_trees,
-                       ctx->dm_aff_prod, ctx->dm_aff_flag, ctx->d_aff_count, ctx->d_err + 2, ctx->conv_wave_prio);
+    hipLaunchKernelGGL(k_affine_up<AffWireSource>, dim3(nblk), dim3(AFF_THREADS), 0, ctx->stream2, AffWireSource{d_raw}, n, ctx->aff.d_stash, ctx->aff.d_trees,
+                       ctx->aff.dm_prod, ctx->aff.dm_flag, ctx->aff.d_count, ctx->d_err + 2, ctx->knobs.conv_wave_prio);
   HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipEventRecord(ctx->aff_up_done, ctx->stream2));
-  if (ctx->tail_threads > 1 && nblk >= 32) ctx->tail_pool.prewake(ctx->aff_prewake_us, std::min(ctx->tail_threads, TailPool::WORKERS + 1) - 1);
+  HIP_TRY(ctx, hipEventRecord(ctx->aff.up_done, ctx->stream2));
+  if (ctx->knobs.tail_threads > 1 && nblk >= 32) ctx->tail_pool.prewake(ctx->knobs.aff_prewake_us, std::min(ctx->knobs.tail_threads, TailPool::WORKERS + 1) - 1);
   return MSM377_OK;
 }
 
@@ -230,14 +216,14 @@ int affine_convert_finish(msm377_ctx* ctx, uint32_t* d_records_out, uint64_t n) 
   // Poll the flag in pinned memory (no runtime calls: they would contend with nothing, but they are not free either);
   // after 20 ms fall back to the event, which also surfaces a failed kernel.
   const auto t0 = std::chrono::steady_clock::now();
-  for (uint32_t spins = 0; __atomic_load_n(ctx->h_aff_flag, __ATOMIC_ACQUIRE) != nblk; spins++) {
+  for (uint32_t spins = 0; __atomic_load_n(ctx->aff.h_flag, __ATOMIC_ACQUIRE) != nblk; spins++) {
     __builtin_ia32_pause();
     if ((spins & 0xfff) == 0xfff && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) {
-      HIP_TRY(ctx, hipEventSynchronize(ctx->aff_up_done));
+      HIP_TRY(ctx, hipEventSynchronize(ctx->aff.up_done));
       break;
     }
   }
-  if (__atomic_load_n(ctx->h_aff_flag, __ATOMIC_ACQUIRE) != nblk) {
+  if (__atomic_load_n(ctx->aff.h_flag, __ATOMIC_ACQUIRE) != nblk) {
     ctx->err = "batched affine conversion: the block products did not arrive";
     return MSM377_EHIP;
   }
@@ -248,7 +234,7 @@ int affine_convert_finish(msm377_ctx* ctx, uint32_t* d_records_out, uint64_t n) 
   }
   // The way down starts as soon as the host has inverted the block products, beside whatever the sort is doing (letting
   // it wait for the sort was measured both ways in round 2: 2^20 2.62 -> 2.59 ms, 2^22 10.39 -> 10.21 without the wait).
-  hipLaunchKernelGGL(k_affine_down, dim3(nblk), dim3(AFF_THREADS), 0, ctx->stream2, n, ctx->d_aff_stash, ctx->d_aff_trees, ctx->dm_aff_inv, d_records_out, ctx->conv_wave_prio);
+  hipLaunchKernelGGL(k_affine_down, dim3(nblk), dim3(AFF_THREADS), 0, ctx->stream2, n, ctx->aff.d_stash, ctx->aff.d_trees, ctx->aff.dm_inv, d_records_out, ctx->knobs.conv_wave_prio);
   HIP_TRY(ctx, hipGetLastError());
   if (ctx->timing == 1) (void)hipEventRecord(ctx->ev[MSM377_STAGE_CONVERT][1], ctx->stream2);
   HIP_TRY(ctx, hipEventRecord(ctx->bases_ready, ctx->stream2));
@@ -263,7 +249,7 @@ int affine_convert_finish(msm377_ctx* ctx, uint32_t* d_records_out, uint64_t n) 
 // n = 2^19, 64 at 2^20, 96-128 at 2^21; a rank that owns one or two windows of a sharded MSM gets short chains,
 // so that its few rows still fill the GPU.
 uint32_t auto_seg(const msm377_ctx* ctx, uint64_t entries, bool glv) {
-  const uint32_t forced = glv ? ctx->seg_glv : ctx->seg_plain;
+  const uint32_t forced = glv ? ctx->knobs.seg_glv : ctx->knobs.seg_plain;
   if (forced) return forced;
   const uint64_t s = ((entries >> 18) + 7) & ~7ull;
   return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(s, SEG_MIN), SEG_MAX);
@@ -351,7 +337,7 @@ WindowPlan plan_short(TailKind tail, uint32_t bytes, uint32_t bits, bool narrow)
   return p;
 }
 // Whole MSMs on sixteen windows: even in the Edwards forms unless MSM377_EVEN_WINDOWS=0 (the Weierstrass forms keep equal ones).
-WindowPlan plan_whole16(const msm377_ctx* ctx, TailKind tail) { return ctx->even_windows && tail != XYZZ_TAIL ? plan_even16(tail) : plan_equal16(tail); }
+WindowPlan plan_whole16(const msm377_ctx* ctx, TailKind tail) { return ctx->knobs.even_windows && tail != XYZZ_TAIL ? plan_even16(tail) : plan_equal16(tail); }
 
 // This geometry refused a scalar that sixteen equal windows may still take: the pass is discarded and the call runs
 // the plan next_plan names.  (A scalar that overflows the recode outright, ERR_SCALAR, fits no geometry: no rerun.)
@@ -427,23 +413,23 @@ LaunchRecord launch_record(msm377_ctx* ctx, const Phase& ph, uint64_t n_scalars,
   // 0.085 at 2^13, profiles/r03_final/sweep_narrow_seg_even.txt; below that a row has two entries on average.)
   static_assert((uint64_t)NARROW_EVEN_WINDOWS * SMALL_SORT_MAX / NARROW_SEG + NARROW_EVEN_WINDOWS * (1u << NARROW_LOG) <= (uint64_t)MSM377_NUM_WINDOWS * 32768,
                 "narrow work items fit the work-item buffer");
-  k.SEG = (k.narrow && !ctx->seg_plain) ? (ctx->narrow_seg ? ctx->narrow_seg : (k.n > 8192 ? 16u : 12u)) : auto_seg(ctx, k.entries, k.glv);
+  k.SEG = (k.narrow && !ctx->knobs.seg_plain) ? (ctx->knobs.narrow_seg ? ctx->knobs.narrow_seg : (k.n > 8192 ? 16u : 12u)) : auto_seg(ctx, k.entries, k.glv);
   k.rows = k.slots * k.buckets, k.max_items = (uint64_t)k.rows + k.entries / k.SEG;
   k.wc_out = plan.table ? 1u : k.slots, k.pp = k.wide ? WIDE_POINTS : (uint32_t)MSM377_G1_PARTIAL_POINTS;
   // a lane quad per work item while the launch is one chain's latency (up to 2^14 points: ~94 k items); beyond that
   // the quads are VALU-bound like threads and only add their exchange instructions (kernel at 2^16: 0.216 / 0.183 ms)
-  k.quad_acc = cv.quad_items && k.narrow && !plan.table && k.max_items <= ctx->narrow_quad_items;
+  k.quad_acc = cv.quad_items && k.narrow && !plan.table && k.max_items <= ctx->knobs.narrow_quad_items;
   // (One launch for the whole front end of such a call -- each window's workgroup recoding, sorting and listing its
   // work items itself, one global atomic per list and workgroup -- was built and dropped: 0.271 -> 0.293 ms at 2^12,
   // 0.342 -> 0.373 at 2^14.  Saving four dispatch latencies did not pay for a work list that is sorted by length
   // only within each window: the accumulation kernel went from 0.038 to 0.054 ms at 2^12.)
   // sort_temp elements: 8 bytes, or with MSM377_SORT_ELEM=4 packed into 4 while every column index fits 23 bits
   // (common.hpp sort_elem_bytes); the buffer is sized for 8 either way.
-  k.packed_sort = !k.wide && !k.narrow && ctx->sort_elem == 4 && sort_elem_bytes(k.n, false) == 4;
-  for (k.coop_from = 0; k.coop_from < k.L && 4ull * (k.coop_from + 1) * (k.buckets >> (k.coop_from + 1)) * k.wc_out > ctx->coop_threads;) k.coop_from++;
+  k.packed_sort = !k.wide && !k.narrow && ctx->knobs.sort_elem == 4 && sort_elem_bytes(k.n, false) == 4;
+  for (k.coop_from = 0; k.coop_from < k.L && 4ull * (k.coop_from + 1) * (k.buckets >> (k.coop_from + 1)) * k.wc_out > ctx->knobs.coop_threads;) k.coop_from++;
   // (wide windows: 2^19 buckets in one window -- the lists of the single-launch tail must be down to one round of
   // 128 lane quads, which is level L - 8)
-  k.tail_from = std::min(k.wide ? k.L - 8 : k.narrow ? ctx->narrow_tail_from : ctx->tail_from, k.L);
+  k.tail_from = std::min(k.wide ? k.L - 8 : k.narrow ? ctx->knobs.narrow_tail_from : ctx->knobs.tail_from, k.L);
   k.tail_lds_bytes = (size_t)(k.buckets >> k.tail_from) * cv.pt_words * 4;
   k.d_err = ctx->d_err + slot, k.d_partials = ctx->d_partials + (size_t)slot * SLOT_WORDS;
   const uint32_t* records = ctx->resident.valid() ? ctx->resident.bases : ctx->d_bases;  // (a twin's resident bases are lent)
@@ -481,17 +467,17 @@ int enqueue_decompose(msm377_ctx* ctx, const LaunchRecord& k, const uint32_t* d_
     hipLaunchKernelGGL(k_decompose, grid, block, 0, st, d_scalars, ctx->d_digits, k.n, k.wb, k.slots, k.d_err, k.top_key_max, k.even ? 1u : 0u);
   HIP_TRY(ctx, hipGetLastError());
   static_assert(MAX_WINDOW_SLOTS <= MSM377_STAGE_MAX_SLOTS, "a stage layout names every window slot");
-  msm377_stage_info& info = ctx->stage.info = msm377_stage_info{};
+  msm377_stage_info& info = ctx->last.stage.info = msm377_stage_info{};
   info.slots = k.slots, info.bucket_log = k.L;
   info.columns = k.entries / k.slots;  // n; 2 n_scalars behind the GLV front end; 13 n in the one slot of the wide table
   info.digit_bytes = k.wide ? 4u : 2u;
   info.row_ptr_len = k.buckets + 2, info.bucket_records = k.buckets;
-  info.form = k.cv.form, info.table_stride = k.plan.table_stride, info.geometry_reruns = ctx->geometry_reruns;
+  info.form = k.cv.form, info.table_stride = k.plan.table_stride, info.geometry_reruns = ctx->fallback.geometry_reruns;
   for (uint32_t s = 0; s < k.slots; s++) info.bias[s] = s + 1 < k.slots ? bias : top_bias;
   if (k.is_short && !k.narrow) info.key_unsigned[k.slots - 1] = 1u;  // (KEY_UNSIGNED in that slot's key_max word)
-  ctx->stage.d_digits = k.wide ? (const void*)ctx->wide.digits : (const void*)ctx->d_digits;
-  ctx->stage.d_key_max = (k.wide || k.narrow) ? nullptr : k.key_max;  // k_local_sort_lds of the wide table and k_small_sort read none
-  ctx->stage.coord_words = k.cv.coord_words, ctx->stage.limbs = k.cv.limbs;  // the bucket records of the pass: four slots of coord_words, `limbs` used
+  ctx->last.stage.d_digits = k.wide ? (const void*)ctx->wide.digits : (const void*)ctx->d_digits;
+  ctx->last.stage.d_key_max = (k.wide || k.narrow) ? nullptr : k.key_max;  // k_local_sort_lds of the wide table and k_small_sort read none
+  ctx->last.stage.coord_words = k.cv.coord_words, ctx->last.stage.limbs = k.cv.limbs;  // the bucket records of the pass: four slots of coord_words, `limbs` used
   return MSM377_OK;
 }
 
@@ -501,7 +487,7 @@ int enqueue_sort(msm377_ctx* ctx, const LaunchRecord& k) {
   hipStream_t st = ctx->stream;
   if (k.wide) {  // the 13 n entries into 4096 fine ranges: two staged partition passes per window (kernels/wide.hpp), then k_local_sort_lds
     uint32_t* counts = ctx->wide.counts;
-    ctx->last_sort_elem = sort_elem_bytes(k.entries, true);
+    ctx->last.sort_elem = sort_elem_bytes(k.entries, true);
     hipLaunchKernelGGL(k_wide_count, dim3(WS_CHUNKS, WIDE_WINDOWS), dim3(1024), 0, st, (const uint32_t*)ctx->wide.digits, counts, k.n);
     hipLaunchKernelGGL(k_wide_sums, dim3(WIDE_NRANGE / 256, WIDE_WINDOWS), dim3(256), 0, st, counts);
     hipLaunchKernelGGL(k_wide_scan, dim3(1), dim3(1024), 0, st, counts, ctx->d_region_base);
@@ -512,7 +498,7 @@ int enqueue_sort(msm377_ctx* ctx, const LaunchRecord& k) {
                        k.entries, (const uint32_t*)nullptr, WIDE_NRANGE, k.buckets);
     HIP_TRY(ctx, hipGetLastError());
   } else if (k.narrow) {
-    ctx->last_sort_elem = 0;
+    ctx->last.sort_elem = 0;
     hipLaunchKernelGGL(k_small_sort, dim3(k.slots), dim3(1024), 0, st, ctx->d_digits, ctx->d_row_ptr, ctx->d_val_idx, (uint32_t)k.n, k.L);
     HIP_TRY(ctx, hipGetLastError());
   } else {
@@ -526,7 +512,7 @@ int enqueue_sort(msm377_ctx* ctx, const LaunchRecord& k) {
     HIP_TRY(ctx, hipGetLastError());
     hipLaunchKernelGGL(k_range_scan, dim3(k.slots), dim3(NRANGE), 0, st, ctx->d_range_counts, ctx->d_region_base, chunks);
     HIP_TRY(ctx, hipGetLastError());
-    ctx->last_sort_elem = k.packed_sort ? 4u : 8u;
+    ctx->last.sort_elem = k.packed_sort ? 4u : 8u;
     auto partition_and_sort = [&](auto* temp) {
       using E = std::remove_pointer_t<decltype(temp)>;
       hipLaunchKernelGGL((k.is_short ? k_partition_staged<E, true> : k_partition_staged<E, false>), grid, dim3(1024), 0, st, ctx->d_digits, ctx->d_range_counts, temp, k.n, chunks,
@@ -577,10 +563,10 @@ int enqueue_accumulate(msm377_ctx* ctx, const LaunchRecord& k) {
     if (hook_rc) return hook_rc;
   }
   HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->bases_ready, 0));
-  ctx->last_products = BP::MADD_PRODUCTS;
+  ctx->last.products = BP::MADD_PRODUCTS;
   launch_accumulate<CV, BP>(ctx, k);
   HIP_TRY(ctx, hipGetLastError());
-  ctx->acc_seq++;
+  ctx->zc.acc_seq++;
   if (k.is_short) {  // the top window of a short call: few rows, thousands of partials each -- folded before the merge
     hipLaunchKernelGGL(k_fold_long_rows<CV>, dim3(FOLD_BLOCKS), dim3(FOLD_THREADS), 0, st, ctx->d_row_ptr, ctx->d_row_ovf_base, ctx->d_ovf, k.SEG, k.d_err, k.L, k.slots - 1);
     HIP_TRY(ctx, hipGetLastError());
@@ -588,7 +574,7 @@ int enqueue_accumulate(msm377_ctx* ctx, const LaunchRecord& k) {
   // (grid-stride over the split-row list: with the even windows few rows split, and 8192 workgroups that only read the
   // count cost 11 us at 2^20)
   hipLaunchKernelGGL(k_merge_split_rows_quad<CV>, dim3(std::min<uint32_t>((k.rows + 63) / 64, 1024u)), dim3(256), 0, st, ctx->d_row_ptr, ctx->d_buckets, k.counters,
-                     ctx->d_split_rows, ctx->d_row_ovf_base, ctx->d_ovf, k.SEG, k.d_err, k.L, ctx->dm_out_flag + ACC_FLAG_WORD, ctx->acc_seq);
+                     ctx->d_split_rows, ctx->d_row_ovf_base, ctx->d_ovf, k.SEG, k.d_err, k.L, ctx->zc.dm_flag + ACC_FLAG_WORD, ctx->zc.acc_seq);
   HIP_TRY(ctx, hipGetLastError());
   return MSM377_OK;
 }
@@ -618,7 +604,7 @@ int enqueue_reduce(msm377_ctx* ctx, const LaunchRecord& k) {
     m = half;
   }
   uint32_t r = 0;
-  while (ctx->reduce_columns && r < k.tail_from) {
+  while (ctx->knobs.reduce_columns && r < k.tail_from) {
     const uint32_t levels = std::min(k.tail_from - r, COLUMN_LEVELS_MAX);
     const uint32_t threads = (r + 1) * (k.buckets >> (r + 1));  // per window: (r + 1) arrays x (buckets >> (r + levels)) columns x 2^(levels-1) lanes
     hipLaunchKernelGGL(k_tree_columns<CV>, dim3((threads + 255) / 256, k.wc_out), dim3(256), 0, st, ctx->d_buckets, k.L, r, levels, k.coop_from, threads, k.d_err);
@@ -634,7 +620,7 @@ int enqueue_reduce(msm377_ctx* ctx, const LaunchRecord& k) {
     HIP_TRY(ctx, hipGetLastError());
   }
   if (k.tail_from < k.L) {
-    const bool in_lds = ctx->tail_lds && k.tail_lds_bytes <= TAIL_LDS_BYTES_MAX;
+    const bool in_lds = ctx->knobs.tail_lds && k.tail_lds_bytes <= TAIL_LDS_BYTES_MAX;
     if (in_lds && k.tail_lds_bytes > 64 * 1024)  // (only with MSM377_TAIL_FROM below its default; per device, so every time)
       HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_reduce_tail_lds<CV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TAIL_LDS_BYTES_MAX));
     if (in_lds)
@@ -644,9 +630,9 @@ int enqueue_reduce(msm377_ctx* ctx, const LaunchRecord& k) {
     HIP_TRY(ctx, hipGetLastError());
   }
   // Zero-copy output: the kernel writes the records and the error word into pinned host memory itself and publishes out_seq.
-  const bool zc = ctx->zc_active;
-  hipLaunchKernelGGL(k_gather_partials<CV>, dim3((k.wc_out * k.pp * 4 + 63) / 64), dim3(64), 0, st, ctx->d_buckets, k.d_partials, k.wc_out, k.L, zc ? ctx->dm_partials : nullptr,
-                     zc ? ctx->dm_out_flag : nullptr, zc ? ctx->d_out_count : nullptr, zc ? (const int*)k.d_err : nullptr, zc ? ctx->out_seq : 0u, k.pp);
+  const bool zc = ctx->zc.active;
+  hipLaunchKernelGGL(k_gather_partials<CV>, dim3((k.wc_out * k.pp * 4 + 63) / 64), dim3(64), 0, st, ctx->d_buckets, k.d_partials, k.wc_out, k.L, zc ? ctx->zc.dm_partials : nullptr,
+                     zc ? ctx->zc.dm_flag : nullptr, zc ? ctx->zc.d_count : nullptr, zc ? (const int*)k.d_err : nullptr, zc ? ctx->zc.out_seq : 0u, k.pp);
   HIP_TRY(ctx, hipGetLastError());
   return MSM377_OK;
 }
@@ -662,9 +648,9 @@ template <class CV, class BP = CV>
 int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scalars, uint32_t wb, int slot, const Phase& ph) {
   const LaunchRecord k = launch_record(ctx, ph, n_scalars, wb, slot, curve_dims<CV, BP>());
   hipStream_t st = ctx->stream;
-  ctx->stage.valid = false;  // set again at the end of a whole call under stage capture
-  ctx->zc_active = ph.zc_out && ph.back && ctx->zc_out && slot == 0 && !k.plan.table;
-  if (ctx->zc_active) ctx->out_seq++;
+  ctx->last.stage.valid = false;  // set again at the end of a whole call under stage capture
+  ctx->zc.active = ph.zc_out && ph.back && ctx->knobs.zc_out && slot == 0 && !k.plan.table;
+  if (ctx->zc.active) ctx->zc.out_seq++;
   // The error word is cleared by the call's first kernel: with the front stages one launch clears the call's work-list
   // counters, its key_max words (0 = full-width ranges; the recode then measures the top slot) and the error word.
   if (ph.front) {
@@ -679,16 +665,16 @@ int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scala
   if (ctx->capture) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_buckets_snap, ctx->d_buckets, (size_t)k.slots * k.cv.bkt_words * k.buckets * 4, hipMemcpyDeviceToDevice, st));
   const int rc = enqueue_reduce<CV>(ctx, k);
   if (rc) return rc;
-  if (!ctx->zc_active) {
+  if (!ctx->zc.active) {
     HIP_TRY(ctx, hipMemcpyAsync(ctx->h_partials + (size_t)slot * SLOT_WORDS, k.d_partials, (size_t)k.wc_out * k.pp * k.cv.out_words * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->h_err + slot, k.d_err, sizeof(int), hipMemcpyDeviceToHost, st));
   }
   HIP_TRY(ctx, hipEventRecord(ctx->done_ev[slot], st));
-  ctx->last_n = k.n, ctx->last_glv = k.glv, ctx->last_form = k.cv.form;
-  ctx->last_geom_windows = k.slots, ctx->last_geom_log = k.L;
+  ctx->last.n = k.n, ctx->last.glv = k.glv, ctx->last.form = k.cv.form;
+  ctx->last.geom_windows = k.slots, ctx->last.geom_log = k.L;
   // A whole call in one piece from window 0: the layout written at the decomposition describes it.  Capture mode 1 is G1's:
   // an Edwards-BLS12 call is described as run only (mode 2).
-  ctx->stage.valid = ctx->capture && ph.front && !ph.into && wb == 0 && (k.cv.form != MSM377_STAGE_FORM_ED || ctx->capture == 2);
+  ctx->last.stage.valid = ctx->capture && ph.front && !ph.into && wb == 0 && (k.cv.form != MSM377_STAGE_FORM_ED || ctx->capture == 2);
   return MSM377_OK;
 }
 
@@ -697,24 +683,24 @@ int enqueue_windows(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n_scala
 // then also surfaces a failed kernel).
 int wait_zero_copy_out(msm377_ctx* ctx) {
   const auto t0 = std::chrono::steady_clock::now();
-  for (uint32_t spins = 0; __atomic_load_n(&ctx->h_out_flag[0], __ATOMIC_ACQUIRE) != ctx->out_seq; spins++) {
+  for (uint32_t spins = 0; __atomic_load_n(&ctx->zc.h_flag[0], __ATOMIC_ACQUIRE) != ctx->zc.out_seq; spins++) {
     __builtin_ia32_pause();
     if ((spins & 0xfff) == 0xfff && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(50)) {
       HIP_TRY(ctx, hipEventSynchronize(ctx->done_ev[0]));
       break;
     }
   }
-  if (__atomic_load_n(&ctx->h_out_flag[0], __ATOMIC_ACQUIRE) != ctx->out_seq) {
+  if (__atomic_load_n(&ctx->zc.h_flag[0], __ATOMIC_ACQUIRE) != ctx->zc.out_seq) {
     ctx->err = "zero-copy output: the window records did not arrive";
     return MSM377_EHIP;
   }
-  ctx->h_err[0] = (int)__atomic_load_n(&ctx->h_out_flag[1], __ATOMIC_RELAXED);
+  ctx->h_err[0] = (int)__atomic_load_n(&ctx->zc.h_flag[1], __ATOMIC_RELAXED);
   return MSM377_OK;
 }
 
 // Wait for slot `slot`: its error word is then in ctx->h_err[slot], its records in ctx->h_partials + slot * SLOT_WORDS.
 int wait_windows(msm377_ctx* ctx, int slot) {
-  if (ctx->zc_active && slot == 0) {
+  if (ctx->zc.active && slot == 0) {
     const int rc = wait_zero_copy_out(ctx);
     if (rc || !ctx->timing) return rc;
   }
@@ -728,11 +714,11 @@ int collect_windows(msm377_ctx* ctx, int slot) {
     for (int s = 0; s < MSM377_NUM_STAGES; s++) {
       if (s == MSM377_STAGE_TAIL) continue;  // host wall time, set by run_tail
       if (ctx->timing == 2 && s != MSM377_STAGE_ACC_KERNEL) {
-        ctx->stage_ms[s] = 0.0;
+        ctx->last.stage_ms[s] = 0.0;
         continue;
       }
       float ms = 0.f;
-      ctx->stage_ms[s] = hipEventElapsedTime(&ms, ctx->ev[s][0], ctx->ev[s][1]) == hipSuccess ? ms : 0.0;
+      ctx->last.stage_ms[s] = hipEventElapsedTime(&ms, ctx->ev[s][0], ctx->ev[s][1]) == hipSuccess ? ms : 0.0;
     }
     (void)hipGetLastError();  // a stage that did not run in this call must not leave its error for the next launch check
   }
@@ -743,7 +729,7 @@ int collect_windows(msm377_ctx* ctx, int slot) {
   return MSM377_OK;
 }
 
-inline bool use_glv(const msm377_ctx* ctx) { return ctx->glv_mode == 1; }  // see msm377_ctx::glv_mode
+inline bool use_glv(const msm377_ctx* ctx) { return ctx->knobs.glv_mode == 1; }  // see Knobs::glv_mode
 
 // Base conversion for the G1 entry points: with the GLV front end the table also gets phi(P_i).
 int convert_bases_g1(msm377_ctx* ctx, const uint32_t* d_raw, uint64_t n, bool glv) {
@@ -770,7 +756,7 @@ inline int resident_form(const msm377_ctx* ctx, uint64_t n) {
 // The resident table is the 20-bit-window one: 13 windows over one set of 2^19 buckets.
 inline bool wide_table(const ResidentBases& r) { return r.form == TABLE_TE_PRECOMP && r.windows == WIDE_WINDOWS; }
 inline int weierstrass_form(const msm377_ctx* ctx) { return use_glv(ctx) ? TABLE_XYZZ_GLV : TABLE_XYZZ; }
-inline int pick_form(const msm377_ctx* ctx) { return ctx->g1_form == 1 ? TABLE_TE : weierstrass_form(ctx); }
+inline int pick_form(const msm377_ctx* ctx) { return ctx->knobs.g1_form == 1 ? TABLE_TE : weierstrass_form(ctx); }
 
 int convert_table(msm377_ctx* ctx, const uint32_t* d_raw, uint64_t n, int form) {
   if (form == TABLE_TE) return convert_bases<TeDev>(ctx, d_raw, n);
@@ -796,7 +782,7 @@ int run_tail(msm377_ctx* ctx, const WindowPlan& plan, const uint32_t* partials, 
     tr = teh_combine(partials, plan.records, out_xy, plan.cbits(), plan.planes(), plan.short_from) ? TAIL_EXCEPTIONAL : TAIL_OK;
   else
     tr = te_tail(ctx, partials, out_xy, plan.records, plan.cbits(), plan.planes(), plan.short_from);
-  ctx->stage_ms[MSM377_STAGE_TAIL] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  ctx->last.stage_ms[MSM377_STAGE_TAIL] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (tr != TAIL_EXCEPTIONAL) return tr;
   note_fallback(ctx, MSM377_FB_TAIL);
   return RC_TE_FALLBACK;
@@ -809,9 +795,9 @@ struct TailArm {
   bool armed = false;
   explicit TailArm(msm377_ctx* ctx) : c(ctx) {}
   void arm() {
-    if (armed || c->tail_threads <= 1 || c->tail_spin_us <= 0) return;
+    if (armed || c->knobs.tail_threads <= 1 || c->knobs.tail_spin_us <= 0) return;
     armed = true;
-    c->tail_pool.prewake(c->tail_spin_us, std::min(c->tail_threads, TailPool::WORKERS + 1) - 1);
+    c->tail_pool.prewake(c->knobs.tail_spin_us, std::min(c->knobs.tail_threads, TailPool::WORKERS + 1) - 1);
   }
   // A small input is over in a few hundred microseconds, its bucket reduction in 0.1 ms -- no longer than a sleeping
   // worker may take to come back -- so its call arms the workers before it enqueues anything.
@@ -819,11 +805,11 @@ struct TailArm {
     if (n <= (1ull << 17)) arm();
   }
   void after_accumulation() {
-    if (armed || c->tail_threads <= 1 || c->tail_spin_us <= 0) return;
+    if (armed || c->knobs.tail_threads <= 1 || c->knobs.tail_spin_us <= 0) return;
     // k_merge_split_rows_quad, the launch behind the accumulation kernel, writes the call's sequence number; without it
     // within 100 ms the caller's own wait reports whatever went wrong
     const auto t0 = std::chrono::steady_clock::now();
-    for (uint32_t spins = 0; __atomic_load_n(&c->h_out_flag[ACC_FLAG_WORD], __ATOMIC_ACQUIRE) != c->acc_seq; spins++) {
+    for (uint32_t spins = 0; __atomic_load_n(&c->zc.h_flag[ACC_FLAG_WORD], __ATOMIC_ACQUIRE) != c->zc.acc_seq; spins++) {
       __builtin_ia32_pause();
       if ((spins & 0xfff) == 0xfff && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(100)) return;
     }
@@ -844,10 +830,10 @@ int enqueue_form(msm377_ctx* ctx, int form, const uint32_t* d_scalars, uint64_t 
 WindowPlan first_plan(const msm377_ctx* ctx, uint64_t n, int form, uint32_t sbytes, uint32_t bits) {
   if (!form_is_te(form)) return sbytes ? plan_short(XYZZ_TAIL, sbytes, bits, false) : form == TABLE_XYZZ_GLV ? plan_glv8() : plan_equal16(XYZZ_TAIL);
   const ResidentBases& r = ctx->resident;
-  // Small inputs: narrow windows; the window-indexed buffers are sized for them too (msm377_ctx_create: wcap).  A
+  // Small inputs: narrow windows; the window-indexed buffers are sized for them too (context.hip ctx_create: wcap).  A
   // precomputed table has its own geometry, and capture mode 1 describes sixteen equal 16-bit windows.
   const bool precomp = form == TABLE_TE_PRECOMP;
-  const bool narrow = !precomp && n <= ctx->narrow_max_points && n <= SMALL_SORT_MAX && ctx->capture != 1;
+  const bool narrow = !precomp && n <= ctx->knobs.narrow_max_points && n <= SMALL_SORT_MAX && ctx->capture != 1;
   if (sbytes) {
     WindowPlan p = plan_short(TE_TAIL, sbytes, bits, narrow);
     if (precomp && wide_table(r))
@@ -887,7 +873,7 @@ int g1_table_msm(msm377_ctx* ctx, const uint32_t* d_scalars, uint64_t n, int for
     if (rc) return rc;
     const int err = ctx->h_err[0];
     if (geometry_refused(ph.plan, err)) {
-      ctx->geometry_reruns++;
+      ctx->fallback.geometry_reruns++;
       ph.plan = next_plan(ph.plan);
       continue;
     }
@@ -945,9 +931,9 @@ int run_chunked_upload(msm377_ctx* ctx, const uint8_t* points, const uint8_t* sc
   uint64_t cut[10];  // chunk c = points [cut[c], cut[c + 1]): the first one upload_split_pct of n, the rest even
   uint32_t K = 0;
   cut[0] = 0;
-  for (uint32_t c = 1; c < ctx->upload_chunks; c++) {
-    const uint64_t first_end = std::max<uint64_t>(64, (n * ctx->upload_split_pct / 100) & ~63ull);
-    const uint64_t b = c == 1 ? first_end : (first_end + (n - first_end) * (c - 1) / (ctx->upload_chunks - 1)) & ~63ull;
+  for (uint32_t c = 1; c < ctx->knobs.upload_chunks; c++) {
+    const uint64_t first_end = std::max<uint64_t>(64, (n * ctx->knobs.upload_split_pct / 100) & ~63ull);
+    const uint64_t b = c == 1 ? first_end : (first_end + (n - first_end) * (c - 1) / (ctx->knobs.upload_chunks - 1)) & ~63ull;
     if (b > cut[K] && b < n) cut[++K] = b;  // no empty chunks (small n)
   }
   cut[++K] = n;
@@ -1048,7 +1034,7 @@ int check_points_device(msm377_ctx* ctx, const void* d_points, uint64_t n, uint3
     for (int s = 0; s < MSM377_NUM_STAGES; s++) {
       float ms = 0.f;
       const bool ran = s == MSM377_STAGE_CONVERT || (list && s == MSM377_STAGE_ACC_KERNEL);
-      ctx->stage_ms[s] = ran && hipEventElapsedTime(&ms, ctx->ev[s][0], ctx->ev[s][1]) == hipSuccess ? ms : 0.0;
+      ctx->last.stage_ms[s] = ran && hipEventElapsedTime(&ms, ctx->ev[s][0], ctx->ev[s][1]) == hipSuccess ? ms : 0.0;
     }
   }
   out->noncanonical = h[CHK_NONCANON];
@@ -1086,10 +1072,10 @@ int check_points_from_host(msm377_ctx* ctx, const uint8_t* points, uint64_t n, u
   return check_points_device<CK>(ctx, ctx->d_sort_temp, n, flags, out);
 }
 
-// The opt-in check of the set-bases calls (ctx->base_checks): MSM377_EPOINT with index and reason in ctx->err.
+// The opt-in check of the set-bases calls (ctx->knobs.base_checks): MSM377_EPOINT with index and reason in ctx->err.
 int check_base_set(msm377_ctx* ctx, const void* d_points, uint64_t n) {
-  if (!ctx->base_checks) return MSM377_OK;
-  const int rc = check_points_device<G1Check>(ctx, d_points, n, ctx->base_checks, &ctx->last_check);
+  if (!ctx->knobs.base_checks) return MSM377_OK;
+  const int rc = check_points_device<G1Check>(ctx, d_points, n, ctx->knobs.base_checks, &ctx->last_check);
   if (rc) return rc;
   const msm377_check_report& r = ctx->last_check;
   if (r.first_bad == UINT64_MAX) return MSM377_OK;
@@ -1107,35 +1093,15 @@ int check_base_set(msm377_ctx* ctx, const void* d_points, uint64_t n) {
 // returns at once: no launch, no allocation, the caller's pointers.
 inline bool native_forms(const msm377_ctx* ctx) { return ctx->point_form != MSM377_POINTS_WIRE || ctx->scalar_form != MSM377_SCALARS_WIRE; }
 inline size_t point_stride(const msm377_ctx* ctx) { return ctx->point_form == MSM377_POINTS_MONT_FLAG ? 104 : 96; }
-inline size_t mask_words(const msm377_ctx* ctx) { return (size_t)(((ctx->cap + 31) / 32 + 3) & ~3ull); }
-enum { MASK_BASES = 0, MASK_CHECK = 1 };  // which of the two masks (and counters) in d_inf_mask
-inline uint8_t* native_points(const msm377_ctx* ctx) { return ctx->d_native; }
-inline uint8_t* native_scalars(const msm377_ctx* ctx) { return ctx->d_native + (((size_t)ctx->cap * 104 + 15) & ~(size_t)15); }
-
-int ensure_import_buffers(msm377_ctx* ctx, bool host_staging) {
-  if (!ctx->import_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->import_done, hipEventDisableTiming));
-  if (!ctx->d_inf_mask && hipMalloc((void**)&ctx->d_inf_mask, (2 * mask_words(ctx) + 4) * 4) != hipSuccess) {
-    ctx->d_inf_mask = nullptr;
-    (void)hipGetLastError();
-    ctx->err = "native input forms: out of device memory";
-    return MSM377_ENOMEM;
-  }
-  if (host_staging && !ctx->d_native && hipMalloc((void**)&ctx->d_native, (((size_t)ctx->cap * 104 + 15) & ~(size_t)15) + (size_t)ctx->cap * 32) != hipSuccess) {
-    ctx->d_native = nullptr;
-    (void)hipGetLastError();
-    ctx->err = "native input forms: out of device memory for the host-buffer staging";
-    return MSM377_ENOMEM;
-  }
-  return MSM377_OK;
-}
+enum { MASK_BASES = 0, MASK_CHECK = 1 };  // which of the two masks (and counters) in native.d_inf_mask
 
 // n points in the context's (non-wire) point form at d_in -> wire records at d_out, on the main stream; the side stream,
 // which converts them, is ordered behind.  `which`: the mask and counter the pass writes (the counter is cleared first).
 int import_points(msm377_ctx* ctx, const void* d_in, uint64_t n, uint32_t* d_out, int which) {
   int rc = ensure_import_buffers(ctx, false);
   if (rc) return rc;
-  uint32_t* mask = ctx->d_inf_mask + (size_t)which * mask_words(ctx);
-  uint32_t* count = ctx->d_inf_mask + 2 * mask_words(ctx) + which;
+  uint32_t* mask = ctx->native.d_inf_mask + (size_t)which * ctx->native.mask_words();
+  uint32_t* count = ctx->native.d_inf_mask + 2 * ctx->native.mask_words() + which;
   const dim3 grid((unsigned)((n + IMPORT_THREADS - 1) / IMPORT_THREADS)), block(IMPORT_THREADS);
   if (ctx->point_form == MSM377_POINTS_MONT_FLAG) {
     hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(256), 0, ctx->stream, count, 1u, (uint32_t*)nullptr, 0u);
@@ -1144,8 +1110,8 @@ int import_points(msm377_ctx* ctx, const void* d_in, uint64_t n, uint32_t* d_out
     hipLaunchKernelGGL(k_import_points<MSM377_POINTS_MONT>, grid, block, 0, ctx->stream, (const uint8_t*)d_in, d_out, n, mask, count);
   }
   HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipEventRecord(ctx->import_done, ctx->stream));
-  HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream2, ctx->import_done, 0));
+  HIP_TRY(ctx, hipEventRecord(ctx->native.import_done, ctx->stream));
+  HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream2, ctx->native.import_done, 0));
   return MSM377_OK;
 }
 
@@ -1176,7 +1142,7 @@ int import_inputs(msm377_ctx* ctx, const void** d_points, const void** d_scalars
     const int rc = import_points(ctx, *d_points, n, ctx->d_raw_points, MASK_BASES);
     if (rc) return rc;
     *d_points = ctx->d_raw_points;
-    if (ctx->point_form == MSM377_POINTS_MONT_FLAG) mask = ctx->d_inf_mask;
+    if (ctx->point_form == MSM377_POINTS_MONT_FLAG) mask = ctx->native.d_inf_mask;
   }
   const uint32_t* sc = nullptr;
   const int rc = import_scalars(ctx, *d_scalars, n, scalar_words, mask, &sc);
@@ -1193,7 +1159,7 @@ int import_base_set(msm377_ctx* ctx, const void** d_points, uint64_t n, uint32_t
   if (rc) return rc;
   *d_points = ctx->d_raw_points;
   if (ctx->point_form == MSM377_POINTS_MONT_FLAG) {
-    HIP_TRY(ctx, hipMemcpyAsync(flagged, ctx->d_inf_mask + 2 * mask_words(ctx) + MASK_BASES, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(flagged, ctx->native.d_inf_mask + 2 * ctx->native.mask_words() + MASK_BASES, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
   return MSM377_OK;
@@ -1203,8 +1169,8 @@ int import_base_set(msm377_ctx* ctx, const void** d_points, uint64_t n, uint32_t
 // continues on the device-pointer path, which imports from there.  Either array may be absent.
 int upload_native(msm377_ctx* ctx, const uint8_t* points, size_t point_bytes, const uint8_t* scalars, size_t scalar_bytes) {
   int rc = ensure_import_buffers(ctx, true);
-  if (rc == MSM377_OK && points && point_bytes) rc = h2d_staged(ctx, native_points(ctx), points, point_bytes, 0);
-  if (rc == MSM377_OK && scalars && scalar_bytes) rc = h2d_staged(ctx, native_scalars(ctx), scalars, scalar_bytes, 0);
+  if (rc == MSM377_OK && points && point_bytes) rc = h2d_staged(ctx, ctx->native.native_points(), points, point_bytes, 0);
+  if (rc == MSM377_OK && scalars && scalar_bytes) rc = h2d_staged(ctx, ctx->native.native_scalars(), scalars, scalar_bytes, 0);
   return rc;
 }
 
@@ -1237,29 +1203,12 @@ int g1_check_points(msm377_ctx* ctx, const uint8_t* points, uint64_t n, uint32_t
     ctx->err.clear();
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int rc = upload_native(ctx, points, n * point_stride(ctx), nullptr, 0);
-    return rc ? rc : g1_check_points_device(ctx, native_points(ctx), n, flags, out);
+    return rc ? rc : g1_check_points_device(ctx, ctx->native.native_points(), n, flags, out);
   }
   return check_points_from_host<G1Check>(ctx, points, n, flags, out);
 }
 int ed_check_points_device(msm377_ctx* ctx, const void* d_points, uint64_t n, uint32_t flags, msm377_check_report* out) { return check_points_device<EdCheck>(ctx, d_points, n, flags, out); }
 int ed_check_points(msm377_ctx* ctx, const uint8_t* points, uint64_t n, uint32_t flags, msm377_check_report* out) { return check_points_from_host<EdCheck>(ctx, points, n, flags, out); }
-
-// The pinned staging buffer (128 bytes per point of capacity) and the copy streams of the host-buffer entry points.
-// h2d_staged allocates them on first use -- which made the FIRST host-buffer call of a context ~35 ms; a caller that
-// cares calls this right after msm377_ctx_create.
-int reserve_host_staging(msm377_ctx* ctx) {
-  if (!ctx) return MSM377_EINVAL;
-  if (ctx->h_stage) return MSM377_OK;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (hipHostMalloc((void**)&ctx->h_stage, (size_t)ctx->cap * 128) != hipSuccess) {
-    ctx->h_stage = nullptr;
-    ctx->err = "host staging buffer: out of pinned memory";
-    return MSM377_ENOMEM;
-  }
-  for (int t = 0; t < 8; t++)
-    if (!ctx->copy_stream[t]) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_stream[t], hipStreamNonBlocking));
-  return MSM377_OK;
-}
 
 // ---- per-call G1 MSMs: msm377_g1_msm* and, with a short spec (sbytes scalar bytes, every scalar below 2^bits; 0 = full
 // width), msm377_g1_msm_short* ----
@@ -1283,9 +1232,9 @@ int g1_device_flow(msm377_ctx* ctx, const void* d_points, const void* d_scalars,
   int rc = import_inputs(ctx, &d_points, &d_scalars, n, sbytes ? sbytes / 4 : 8);  // (native input forms only)
   if (rc) return rc;
   const uint32_t *pts = (const uint32_t*)d_points, *sc = (const uint32_t*)d_scalars;
-  int form = sbytes && ctx->g1_form != 1 ? (int)TABLE_XYZZ : pick_form(ctx);  // a short call never takes the GLV front end
+  int form = sbytes && ctx->knobs.g1_form != 1 ? (int)TABLE_XYZZ : pick_form(ctx);  // a short call never takes the GLV front end
   // (Queueing the conversion after k_decompose instead was measured: decompose 77 -> 23 us, sort 272 -> 386 us.)
-  if (form == TABLE_TE && ctx->te_affine_msm && n >= ctx->affine_min_points) {
+  if (form == TABLE_TE && ctx->knobs.te_affine_msm && n >= ctx->knobs.affine_min_points) {
     // Affine records (7-product additions) by the batched conversion: its way up is queued now, the host's inversion
     // and the way down happen from the hook, once decompose .. work list are queued on the main stream.
     form = TABLE_TE_AFFINE;
@@ -1345,11 +1294,11 @@ int g1_msm(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint6
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (native_forms(ctx)) {  // one upload per array, then the device-pointer path
     const int up = upload_native(ctx, points, n * point_stride(ctx), scalars, n * 32);
-    return up ? up : g1_msm_device(ctx, native_points(ctx), native_scalars(ctx), n, out_xy);
+    return up ? up : g1_msm_device(ctx, ctx->native.native_points(), ctx->native.native_scalars(), n, out_xy);
   }
   ctx->resident.clear();
   const int form = pick_form(ctx);  // (projective Edwards records at any n)
-  if (n < ctx->upload_chunk_min || form == TABLE_XYZZ_GLV || ctx->capture)  // (stage read-backs describe the plain row layout)
+  if (n < ctx->knobs.upload_chunk_min || form == TABLE_XYZZ_GLV || ctx->capture)  // (stage read-backs describe the plain row layout)
     return g1_host_flow(ctx, points, scalars, n, form, out_xy, 0, 0);
   const bool te = form == TABLE_TE;
   const WindowPlan plan = plan_whole16(ctx, te ? TE_TAIL : XYZZ_TAIL);
@@ -1361,7 +1310,7 @@ int g1_msm(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint6
   if (te && (err & ERR_TE_ANY)) {
     note_fallback(ctx, (uint32_t)(err & ERR_TE_ANY));
   } else if (geometry_refused(plan, err)) {  // a scalar of 2^253 and more: g1_table_msm falls back to sixteen equal windows by itself
-    ctx->geometry_reruns++;
+    ctx->fallback.geometry_reruns++;
     rc = convert_table(ctx, ctx->d_raw_points, n, form);
     if (rc == MSM377_OK) rc = g1_table_msm(ctx, ctx->d_raw_scalars, n, form, out_xy);
     if (rc != RC_TE_FALLBACK) return rc;
@@ -1400,11 +1349,11 @@ int g1_msm_short(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars,
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (native_forms(ctx)) {
     rc = upload_native(ctx, points, n * point_stride(ctx), scalars, n * sbytes);
-    return rc ? rc : g1_msm_short_device(ctx, native_points(ctx), native_scalars(ctx), n, sbytes, bits, out_xy);
+    return rc ? rc : g1_msm_short_device(ctx, ctx->native.native_points(), ctx->native.native_scalars(), n, sbytes, bits, out_xy);
   }
   ctx->resident.clear();
-  const bool te = ctx->g1_form == 1;
-  const bool affine = te && ctx->te_affine_msm && n >= ctx->affine_min_points;
+  const bool te = ctx->knobs.g1_form == 1;
+  const bool affine = te && ctx->knobs.te_affine_msm && n >= ctx->knobs.affine_min_points;
   return g1_host_flow(ctx, points, scalars, n, !te ? TABLE_XYZZ : affine ? TABLE_TE_AFFINE : TABLE_TE, out_xy, sbytes, bits);
 }
 
@@ -1456,7 +1405,7 @@ int ed_device_flow(msm377_ctx* ctx, const void* d_points, const void* d_scalars,
     rc = wait_windows(ctx, 0);
     if (rc) return rc;
     if (geometry_refused(ph.plan, ctx->h_err[0])) {  // a scalar of 2^253 and more: sixteen equal windows
-      ctx->geometry_reruns++;
+      ctx->fallback.geometry_reruns++;
       ph.plan = next_plan(ph.plan);
       continue;
     }
@@ -1488,13 +1437,13 @@ int ed_msm(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint6
   if (n == 0) return ed_msm_device(ctx, nullptr, nullptr, 0, out_xy);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   ctx->resident.clear();  // (both paths upload into d_raw_points)
-  if (n >= ctx->upload_chunk_min && !ctx->capture) {  // chunks of points, like g1_msm: a chunk computes while the next one uploads (stage read-backs describe the plain row layout)
+  if (n >= ctx->knobs.upload_chunk_min && !ctx->capture) {  // chunks of points, like g1_msm: a chunk computes while the next one uploads (stage read-backs describe the plain row layout)
     const WindowPlan plan = plan_whole16(ctx, ED_TAIL);
     int rc = run_chunked_upload<EdDev>(ctx, points, scalars, n, plan);
     if (rc == MSM377_OK) rc = wait_windows(ctx, 0);
     if (rc) return rc;
     if (geometry_refused(plan, ctx->h_err[0])) {  // everything is on the device: once more in one piece
-      ctx->geometry_reruns++;
+      ctx->fallback.geometry_reruns++;
       return ed_device_flow(ctx, ctx->d_raw_points, ctx->d_raw_scalars, n, out_xy, true);
     }
     rc = collect_windows(ctx, 0);
@@ -1521,9 +1470,9 @@ int ed_generate_bases_device(msm377_ctx* ctx, uint64_t seed, uint64_t n, void* d
 int free_table(msm377_ctx* ctx) {
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream2));
-  (void)hipFree(ctx->resident.table);
+  ctx->own.release(ctx->resident.table);
   ctx->resident = ResidentBases();  // (its callers have cleared it)
-  ctx->wide.release();
+  ctx->wide.release(ctx->own);
   return MSM377_OK;
 }
 
@@ -1542,7 +1491,7 @@ int g1_set_bases_device(msm377_ctx* ctx, const void* d_points, uint64_t n) {
 }
 
 // d_points: wire records (the caller's, or d_raw_points after an upload or an import); flagged: how many of them stand
-// in for identity points, ctx->d_inf_mask says which.
+// in for identity points, ctx->native.d_inf_mask says which.
 static int build_bases(msm377_ctx* ctx, const void* d_points, uint64_t n, uint32_t flagged) {
   int rc = check_base_set(ctx, d_points, n);  // opt-in (msm377_ctx_set_base_checks)
   if (rc) return rc;
@@ -1558,7 +1507,7 @@ static int build_bases(msm377_ctx* ctx, const void* d_points, uint64_t n, uint32
     rc = free_table(ctx);
     if (rc) return rc;
   }
-  ctx->resident.set(ctx->d_bases, n, form, flagged, ctx->d_inf_mask);
+  ctx->resident.set(ctx->d_bases, n, form, flagged, ctx->native.d_inf_mask);
   return MSM377_OK;
 }
 
@@ -1569,7 +1518,7 @@ static int set_bases_from_host(msm377_ctx* ctx, const uint8_t* points, uint64_t 
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (ctx->point_form != MSM377_POINTS_WIRE) {  // the native records go up as they are; the device variant imports them
     const int up = upload_native(ctx, points, n * point_stride(ctx), nullptr, 0);
-    return up ? up : build(ctx, native_points(ctx), n);
+    return up ? up : build(ctx, ctx->native.native_points(), n);
   }
   int rc = h2d_staged(ctx, ctx->d_raw_points, points, n * 96, 0);
   return rc ? rc : build(ctx, ctx->d_raw_points, n);
@@ -1592,10 +1541,10 @@ int g1_set_bases_precomputed_device(msm377_ctx* ctx, const void* d_points, uint6
   uint32_t flagged = 0;
   rc = import_base_set(ctx, &d_points, n, &flagged);  // (native point forms only)
   if (rc) return rc;
-  if (ctx->g1_form != 1 || n == 0) return build_bases(ctx, d_points, n, flagged);  // Weierstrass form: no precomputation
+  if (ctx->knobs.g1_form != 1 || n == 0) return build_bases(ctx, d_points, n, flagged);  // Weierstrass form: no precomputation
   rc = check_base_set(ctx, d_points, n);  // opt-in (msm377_ctx_set_base_checks), before anything is allocated or converted
   if (rc) return rc;
-  const bool wide = ctx->precomp_bits == (int)WIDE_BITS;
+  const bool wide = ctx->knobs.precomp_bits == (int)WIDE_BITS;
   if (wide && (uint64_t)WIDE_WINDOWS * n >= (1ull << 31)) {
     ctx->err = "precomputed-window table: too many points for 20-bit windows (13 n must stay below 2^31)";
     return MSM377_EINVAL;
@@ -1605,7 +1554,7 @@ int g1_set_bases_precomputed_device(msm377_ctx* ctx, const void* d_points, uint6
   if (r.cap < n || r.windows != windows) {
     rc = free_table(ctx);
     if (rc) return rc;
-    if (hipMalloc((void**)&r.table, (size_t)windows * n * TeAffBase::REC_WORDS * 4) != hipSuccess || (wide && !ctx->wide.ensure(n))) {
+    if (ctx->own.alloc((void**)&r.table, (size_t)windows * n * TeAffBase::REC_WORDS * 4) != hipSuccess || (wide && !ctx->wide.ensure(ctx->own, n, WC_WORDS))) {
       (void)free_table(ctx);
       (void)hipGetLastError();
       ctx->err = "precomputed-window table: out of device memory";
@@ -1623,7 +1572,7 @@ int g1_set_bases_precomputed_device(msm377_ctx* ctx, const void* d_points, uint6
   if (rc) return rc;
   if (d_points != ctx->d_raw_points) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_raw_points, d_points, n * 96, hipMemcpyDeviceToDevice, ctx->stream2));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream2));
-  r.set(ctx->d_bases, n, TABLE_TE_PRECOMP, flagged, ctx->d_inf_mask);
+  r.set(ctx->d_bases, n, TABLE_TE_PRECOMP, flagged, ctx->native.d_inf_mask);
   return MSM377_OK;
 }
 
@@ -1714,7 +1663,7 @@ static int fixed_base_batch_share(msm377_ctx* ctx, const void* d_scalars, uint64
       if (te_fallback) continue;
       if (geometry_refused(ph.plan, err)) {
         (glv ? redo : redo_wide).push_back(b - 1);
-        if (!glv) ctx->geometry_reruns++;
+        if (!glv) ctx->fallback.geometry_reruns++;
         continue;
       }
       rc = collect_windows(ctx, slot);
@@ -1755,24 +1704,20 @@ static int twin_prepare(msm377_ctx* ctx) {
   if (!ctx->twin) {
     if (ctx->twin_failed) return MSM377_ENOMEM;
     msm377_ctx* tw = nullptr;
-    if (msm377_ctx_create(ctx->device, ctx->cap, &tw) != MSM377_OK) {
+    if (ctx_create(ctx->device, ctx->cap, ctx->knobs, true, &tw) != MSM377_OK) {  // (true: it only ever borrows the resident bases)
       ctx->twin_failed = true;  // out of memory for a second set: batches run on one
       (void)hipGetLastError();
       return MSM377_ENOMEM;
     }
-    (void)hipFree(tw->d_bases);  // it only ever borrows the resident bases
-    tw->d_bases = nullptr;
-    (void)hipFree(tw->d_raw_points);
-    tw->d_raw_points = nullptr;
-    tw->twin_batches = false;
     ctx->twin = tw;
   }
   msm377_ctx* tw = ctx->twin;
-  if (wide_table(ctx->resident) && !tw->wide.ensure(ctx->resident.n)) return MSM377_ENOMEM;
+  if (wide_table(ctx->resident) && !tw->wide.ensure(tw->own, ctx->resident.n, WC_WORDS)) return MSM377_ENOMEM;
   // lend the table, and the conversion's verdict that travels with it (d_err[2], read by the accumulation kernels)
   tw->resident = ctx->resident;
   tw->scalar_form = ctx->scalar_form;  // (its share imports its own scalars into its own staging)
-  tw->seg_plain = ctx->seg_plain, tw->seg_glv = ctx->seg_glv, tw->tail_from = ctx->tail_from, tw->reduce_columns = ctx->reduce_columns;
+  tw->knobs = ctx->knobs;  // every launch shape of its share is its owner's, whatever a setter has changed since it was made
+  tw->knobs.twin_batches = false;
   if (hipMemcpyAsync(tw->d_err + 2, ctx->d_err + 2, sizeof(int), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
       hipStreamSynchronize(ctx->stream) != hipSuccess) {
     twin_return(ctx);
@@ -1797,7 +1742,7 @@ int g1_msm_fixed_base_batch_device(msm377_ctx* ctx, const void* d_scalars, uint6
   // the last tree levels and the tail of its reduction, the drain of its accumulation kernel, its memory-bound sort --
   // fill with the other half's kernels.  Two contexts side by side measured 2.01 -> 1.89 ms per MSM on the 20-bit table
   // and 2.19 -> 2.09 on the plain one (tools/twin_probe.py, profiles/r03_final/twin_probe.txt).
-  const bool split = batch >= TWIN_MIN_BATCH && ctx->twin_batches && !ctx->timing && !ctx->capture && twin_prepare(ctx) == MSM377_OK;
+  const bool split = batch >= TWIN_MIN_BATCH && ctx->knobs.twin_batches && !ctx->timing && !ctx->capture && twin_prepare(ctx) == MSM377_OK;
   msm377_ctx* tw = split ? ctx->twin : nullptr;
   const uint32_t mine = split ? batch - batch / 2 : batch;
   int rc2 = MSM377_OK;
@@ -1816,10 +1761,10 @@ int g1_msm_fixed_base_batch_device(msm377_ctx* ctx, const void* d_scalars, uint6
       rc = rc2;
       if (rc2 != RC_TE_FALLBACK) ctx->err = tw->err;
     }
-    if (tw->fallback_count) {
-      ctx->fallback_count += tw->fallback_count;
-      ctx->fallback_mask = tw->fallback_mask;
-      tw->fallback_count = 0;
+    if (tw->fallback.count) {
+      ctx->fallback.count += tw->fallback.count;
+      ctx->fallback.mask = tw->fallback.mask;
+      tw->fallback.count = 0;
     }
   }
   if (rc != RC_TE_FALLBACK) return rc;
@@ -1833,7 +1778,7 @@ int g1_msm_fixed_base(msm377_ctx* ctx, const uint8_t* scalars, uint64_t n, uint8
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (ctx->scalar_form != MSM377_SCALARS_WIRE || ctx->resident.flagged) {  // the import reads them from the native staging
     const int up = upload_native(ctx, nullptr, 0, scalars, n * 32);
-    return up ? up : g1_msm_fixed_base_device(ctx, native_scalars(ctx), n, out_xy);
+    return up ? up : g1_msm_fixed_base_device(ctx, ctx->native.native_scalars(), n, out_xy);
   }
   int rc = h2d_staged(ctx, ctx->d_raw_scalars, scalars, n * 32, (size_t)ctx->cap * 96);
   if (rc) return rc;
@@ -1876,11 +1821,11 @@ int window_partials(msm377_ctx* ctx, const void* d_points, const void* d_scalars
   };
   Phase ph;
   ph.plan = plan_equal16(TE_TAIL, win_count);  // (a shard of sixteen equal windows; the records go to the caller, no tail here)
-  if (ctx->g1_form == 1) {  // twisted Edwards form; k_gather_partials tags the records (fp64_host.hpp TE_RECORD_TAG)
+  if (ctx->knobs.g1_form == 1) {  // twisted Edwards form; k_gather_partials tags the records (fp64_host.hpp TE_RECORD_TAG)
     // Affine base records (7-product additions, batched inversion) once a point takes part in enough additions to pay for
     // its ~9 extra conversion products: windows x points >= 2^24 -- e.g. the 8 windows a rank of a 2-GPU run owns at 2^21
     // points and more, the 2 of an 8-GPU run at 2^23 (msm377_g1_msm_device: 16 windows, n >= 2^20).
-    const bool affine = ctx->te_affine_msm && n >= ctx->affine_min_points / 4 && (uint64_t)win_count * n >= 16 * ctx->affine_min_points;
+    const bool affine = ctx->knobs.te_affine_msm && n >= ctx->knobs.affine_min_points / 4 && (uint64_t)win_count * n >= 16 * ctx->knobs.affine_min_points;
     if (affine) {
       rc = affine_convert_begin(ctx, (const uint32_t*)d_points, n);
       if (rc) return rc;
@@ -1946,17 +1891,6 @@ int g1_glv_window_partials_device(msm377_ctx* ctx, const void* d_points, const v
 // Everything runs on ctx->stream, launch after launch; the one host wait is the synchronisation at the end of the call.
 namespace {
 
-int bm_alloc(msm377_ctx* ctx, uint32_t** p, size_t bytes) {
-  if (*p) return MSM377_OK;
-  if (hipMalloc((void**)p, bytes) != hipSuccess) {
-    *p = nullptr;
-    (void)hipGetLastError();
-    ctx->err = "out of device memory for the batch multiplication scratch";
-    return MSM377_ENOMEM;
-  }
-  return MSM377_OK;
-}
-
 // The scratch of one chunk: fixed sizes, whatever n and the context's capacity are.
 int bm_ensure_scratch(msm377_ctx* ctx) {
   BatchMulState& bm = ctx->bm;
@@ -1995,7 +1929,7 @@ int bm_ensure_table(msm377_ctx* ctx, const uint8_t base_xy[96], int c) {
   bm.valid = false;
   const uint64_t records = bm_table_records((uint32_t)c);
   if (bm.table_cap < records) {
-    if (bm.table) (void)hipFree(bm.table);
+    ctx->own.release(bm.table);
     bm.table = nullptr;
     bm.table_cap = 0;
     const int rc = bm_alloc(ctx, &bm.table, (size_t)records * BM_REC_WORDS * 4);

@@ -45,7 +45,6 @@ int g1_batch_mul(msm377_ctx* ctx, const uint8_t base_xy[96], const uint8_t* scal
 int g1_batch_mul_var_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t scalar_stride, uint32_t out_form, void* d_out_points, uint8_t* d_out_inf);
 int g1_batch_mul_var(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint32_t scalar_stride, uint32_t out_form, uint8_t* out_points, uint8_t* out_inf);
 
-int reserve_host_staging(msm377_ctx* ctx);
 void twin_return(msm377_ctx* ctx);  // takes back the resident bases a batch call lent to the twin of ctx
 
 // Shared with capi.hip (argument checks of the host-only entry points, the stage read-back).
