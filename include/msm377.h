@@ -554,6 +554,43 @@ int msm377_g1_batch_mul_var(msm377_ctx* ctx, const uint8_t* points, const uint8_
 int msm377_g1_batch_mul_var_host(const uint8_t* points, uint32_t point_form, const uint8_t* scalars, uint32_t scalar_form, uint64_t n, uint32_t scalar_stride,
                                  uint32_t out_form, uint8_t* out_points, uint8_t* out_inf);
 
+/* ---- pairwise linear combination ---------------------------------------------------------- */
+
+/* out[i] = [a_i]P_i + [b_i]Q_i: n combinations of n pairs of points, each returned as its own affine point (a basis fold
+ * G'_i = [x^-1]G_i + [x]G_{i+n/2} of an inner-product argument, an SRS update with a blinding term, a random linear
+ * combination of two key vectors; with a = b = 1, plain P_i + Q_i).  Wherever the two overlap the contract is that of
+ * msm377_g1_batch_mul_var* above -- the meaning of a scalar (every 32-byte value, a wire scalar NOT reduced mod r, no
+ * MSM377_ESCALAR), the context's scalar form for BOTH scalars and its point form for BOTH point arrays (a flagged record
+ * is the identity, its coordinate bytes are never interpreted), every curve point a legal input in either array, the two
+ * output forms and out_inf, any n, the alignment of device pointers (all four inputs and the output), synchronous calls,
+ * MSM377_EINVAL with the outputs untouched -- and this section states only what differs (csrc/kernels/batch_lincomb2.hpp).
+ *
+ * Scalars.  a_stride and b_stride are each, independently, 32 (one scalar per pair) or 0 (ONE scalar for all n pairs: 32
+ * bytes are read); any other value is MSM377_EINVAL.
+ *
+ * Relations.  Every relation between the two arrays is legal and followed through: Q_i = P_i, Q_i = -P_i, Q_i a multiple
+ * of P_i, a result of O with P_i != +-Q_i.
+ *
+ * Overlap.  d_p and d_q are only read: they may overlap or be the same pointer.  d_out_points may equal d_p OR equal d_q
+ * when input and output records have the same size.  A pass reads all of its inputs before it writes, and passes cover
+ * disjoint index ranges, so a fold in place works: d_p = G, d_q = G + h records, d_out_points = G, n = h.  ANY other
+ * overlap of an output with an input or with the other output is the caller's bug and the result is undefined.
+ *
+ * State.  The call walks n in passes of 2^16 pairs; per pass it builds the tables [1..8]P_i and [1..8]Q_i in the table
+ * memory of msm377_g1_batch_mul_var* (allocated by the first call of either, never valid between calls): one joint walk
+ * of 3 584 field products per output instead of two walks of 2 944 and an addition.  The resident MSM bases, the
+ * batch_mul window table (msm377_ctx_get_mul_table_builds does not move) and a check call's state are untouched by these
+ * calls, and the other way round.  msm377_g1_batch_lincomb2 stages host buffers through device memory in pieces of 2^20
+ * pairs; a stride-0 scalar is uploaded once. */
+int msm377_g1_batch_lincomb2_device(msm377_ctx* ctx, const void* d_p, const void* d_q, const void* d_a, const void* d_b, uint64_t n, uint32_t a_stride, uint32_t b_stride,
+                                    uint32_t out_form, void* d_out_points, uint8_t* d_out_inf);
+int msm377_g1_batch_lincomb2(msm377_ctx* ctx, const uint8_t* p, const uint8_t* q, const uint8_t* a, const uint8_t* b, uint64_t n, uint32_t a_stride, uint32_t b_stride,
+                             uint32_t out_form, uint8_t* out_points, uint8_t* out_inf);
+/* The same on ONE CPU thread: no device, no context (csrc/batch_lincomb2_host.hpp): each term by plain double-and-add,
+ * then one general addition; the yardstick of the device call.  The forms are arguments here. */
+int msm377_g1_batch_lincomb2_host(const uint8_t* p, const uint8_t* q, uint32_t point_form, const uint8_t* a, const uint8_t* b, uint32_t scalar_form, uint64_t n, uint32_t a_stride,
+                                  uint32_t b_stride, uint32_t out_form, uint8_t* out_points, uint8_t* out_inf);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 
 #define MSM377_STAGE_CONVERT 0     /* points -> Montgomery records */

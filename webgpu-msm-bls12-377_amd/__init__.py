@@ -29,6 +29,7 @@ from .host.engine import (  # noqa: F401
     StageInfo,
     MsmEngine,
     MsmError,
+    batch_lincomb2_host,
     batch_mul_host,
     batch_mul_var_host,
     check_points_host,
@@ -50,6 +51,7 @@ __all__ = [
     "MsmError",
     "CheckReport",
     "StageInfo",
+    "batch_lincomb2_host",
     "batch_mul_host",
     "batch_mul_var_host",
     "check_points_host",

@@ -11,6 +11,7 @@
 #include "host_tail.hpp"
 #include "sequencer.hpp"
 #include "batch_mul_host.hpp"
+#include "batch_lincomb2_host.hpp"
 #include "batch_mul_var_host.hpp"
 #include "import_host.hpp"
 #include "validate_host.hpp"
@@ -268,6 +269,11 @@ int msm377_g1_batch_mul_var_host(const uint8_t* points, uint32_t point_form, con
   return batch_mul_var_host(points, point_form, scalars, scalar_form, n, scalar_stride, out_form, out_points, out_inf);
 }
 
+int msm377_g1_batch_lincomb2_host(const uint8_t* p, const uint8_t* q, uint32_t point_form, const uint8_t* a, const uint8_t* b, uint32_t scalar_form, uint64_t n, uint32_t a_stride,
+                                  uint32_t b_stride, uint32_t out_form, uint8_t* out_points, uint8_t* out_inf) {
+  return batch_lincomb2_host(p, q, point_form, a, b, scalar_form, n, a_stride, b_stride, out_form, out_points, out_inf);
+}
+
 int msm377_ctx_set_mul_window(msm377_ctx* ctx, int window_bits) {
   if (!ctx || (window_bits != 0 && !batch_mul_width_supported(window_bits))) return MSM377_EINVAL;
   ctx->bm.window = window_bits;
@@ -380,6 +386,14 @@ int msm377_g1_batch_mul_var_device(msm377_ctx* ctx, const void* d_points, const 
 }
 int msm377_g1_batch_mul_var(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint32_t scalar_stride, uint32_t out_form, uint8_t* out_points, uint8_t* out_inf) {
   return eng::g1_batch_mul_var(ctx, points, scalars, n, scalar_stride, out_form, out_points, out_inf);
+}
+int msm377_g1_batch_lincomb2_device(msm377_ctx* ctx, const void* d_p, const void* d_q, const void* d_a, const void* d_b, uint64_t n, uint32_t a_stride, uint32_t b_stride,
+                                    uint32_t out_form, void* d_out_points, uint8_t* d_out_inf) {
+  return eng::g1_batch_lincomb2_device(ctx, d_p, d_q, d_a, d_b, n, a_stride, b_stride, out_form, d_out_points, d_out_inf);
+}
+int msm377_g1_batch_lincomb2(msm377_ctx* ctx, const uint8_t* p, const uint8_t* q, const uint8_t* a, const uint8_t* b, uint64_t n, uint32_t a_stride, uint32_t b_stride,
+                             uint32_t out_form, uint8_t* out_points, uint8_t* out_inf) {
+  return eng::g1_batch_lincomb2(ctx, p, q, a, b, n, a_stride, b_stride, out_form, out_points, out_inf);
 }
 int msm377_g1_check_points_device(msm377_ctx* ctx, const void* d_points, uint64_t n, uint32_t flags, msm377_check_report* out) { return eng::g1_check_points_device(ctx, d_points, n, flags, out); }
 int msm377_g1_check_points(msm377_ctx* ctx, const uint8_t* points, uint64_t n, uint32_t flags, msm377_check_report* out) { return eng::g1_check_points(ctx, points, n, flags, out); }

@@ -81,6 +81,8 @@ struct BatchMulState {
   uint32_t* base_wire = nullptr;    // the base's 96 bytes on the device
   // Variable-base calls (msm377_g1_batch_mul_var*, kernels/batch_mul_var.hpp): the per-point tables of ONE pass, [1..8]P_i
   // as 128-byte records (128 MB), rebuilt by every pass and never valid between calls.  They share the scratch above.
+  // The pairwise linear combination (msm377_g1_batch_lincomb2*, kernels/batch_lincomb2.hpp) keeps the two tables of ITS
+  // pass here, [1..8]P_i then [1..8]Q_i for half as many indices.
   uint32_t* var_table = nullptr;
 };
 

@@ -40,6 +40,7 @@
 #include <atomic>
 #include <chrono>
 #include <functional>
+#include <initializer_list>
 #include <thread>
 #include <type_traits>
 #include <vector>
@@ -57,6 +58,7 @@
 #include "kernels/validate.hpp"
 #include "kernels/import.hpp"
 #include "kernels/batch_mul_var.hpp"
+#include "kernels/batch_lincomb2.hpp"
 #include "kernels/wide.hpp"
 
 namespace msm377 {
@@ -2049,14 +2051,43 @@ namespace {
 
 size_t bmv_point_stride(uint32_t form) { return form == MSM377_POINTS_MONT_FLAG ? 104 : 96; }
 
+bool bmv_stride_ok(uint32_t scalar_stride) { return scalar_stride == 0 || scalar_stride == 32; }
+
 int bmv_check_args(msm377_ctx* ctx, uint32_t scalar_stride, uint32_t out_form) {
   const int rc = bm_check_form(ctx, out_form);
   if (rc) return rc;
-  if (scalar_stride != 0 && scalar_stride != 32) {
+  if (!bmv_stride_ok(scalar_stride)) {
     ctx->err = "scalar_stride is 32 (a scalar per point) or 0 (one scalar for all points)";
     return MSM377_EINVAL;
   }
   return MSM377_OK;
+}
+
+// The device pointers of a call: none null, scalars and 96-byte records 16-byte aligned, 104-byte records 8-byte aligned.
+int bmv_check_pointers(msm377_ctx* ctx, std::initializer_list<const void*> scalars, std::initializer_list<const void*> points, size_t in_stride, const void* out, size_t out_stride) {
+  bool null = !out, misaligned = ((uintptr_t)out & (out_stride == 96 ? 15 : 7)) != 0;
+  for (const void* s : scalars) null |= !s, misaligned |= ((uintptr_t)s & 15) != 0;
+  for (const void* p : points) null |= !p, misaligned |= ((uintptr_t)p & (in_stride == 96 ? 15 : 7)) != 0;
+  if (null) {
+    ctx->err = "null pointer";
+    return MSM377_EINVAL;
+  }
+  if (misaligned) {
+    ctx->err = "device pointers must be 16-byte aligned (8-byte for mont_flag records)";
+    return MSM377_EINVAL;
+  }
+  return MSM377_OK;
+}
+
+// [1..8] of m points of `form` into the stash at (e - 1) m + i.
+void bmv_launch_table(msm377_ctx* ctx, uint32_t form, const uint8_t* pts, uint64_t m, uint4* stash) {
+  const dim3 grid((unsigned)((m + BM_THREADS - 1) / BM_THREADS)), block(BM_THREADS);
+  if (form == MSM377_POINTS_WIRE)
+    hipLaunchKernelGGL(k_bmv_table<MSM377_POINTS_WIRE>, grid, block, 0, ctx->stream, pts, m, stash);
+  else if (form == MSM377_POINTS_MONT)
+    hipLaunchKernelGGL(k_bmv_table<MSM377_POINTS_MONT>, grid, block, 0, ctx->stream, pts, m, stash);
+  else
+    hipLaunchKernelGGL(k_bmv_table<MSM377_POINTS_MONT_FLAG>, grid, block, 0, ctx->stream, pts, m, stash);
 }
 
 }  // namespace
@@ -2066,16 +2097,10 @@ int g1_batch_mul_var_device(msm377_ctx* ctx, const void* d_points, const void* d
   int rc = bmv_check_args(ctx, scalar_stride, out_form);
   if (rc) return rc;
   if (n == 0) return MSM377_OK;
-  if (!d_points || !d_scalars || !d_out_points) {
-    ctx->err = "null pointer";
-    return MSM377_EINVAL;
-  }
   const uint32_t form = ctx->point_form;
   const size_t in_stride = bmv_point_stride(form), out_stride = bmv_point_stride(out_form);
-  if (((uintptr_t)d_scalars & 15) || ((uintptr_t)d_points & (in_stride == 96 ? 15 : 7)) || ((uintptr_t)d_out_points & (out_stride == 96 ? 15 : 7))) {
-    ctx->err = "device pointers must be 16-byte aligned (8-byte for mont_flag records)";
-    return MSM377_EINVAL;
-  }
+  rc = bmv_check_pointers(ctx, {d_scalars}, {d_points}, in_stride, d_out_points, out_stride);
+  if (rc) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   rc = bm_ensure_scratch(ctx);
   if (!rc) rc = bm_alloc(ctx, &ctx->bm.var_table, (size_t)BM_CHUNK * BM_REC_WORDS * 4);
@@ -2086,13 +2111,7 @@ int g1_batch_mul_var_device(msm377_ctx* ctx, const void* d_points, const void* d
   for (uint64_t off = 0; off < n && !rc; off += BMV_PASS) {
     const uint64_t m = std::min<uint64_t>(BMV_PASS, n - off);
     const dim3 grid((unsigned)((m + BM_THREADS - 1) / BM_THREADS)), block(BM_THREADS);
-    const uint8_t* pts = (const uint8_t*)d_points + off * in_stride;
-    if (form == MSM377_POINTS_WIRE)
-      hipLaunchKernelGGL(k_bmv_table<MSM377_POINTS_WIRE>, grid, block, 0, ctx->stream, pts, m, stash);
-    else if (form == MSM377_POINTS_MONT)
-      hipLaunchKernelGGL(k_bmv_table<MSM377_POINTS_MONT>, grid, block, 0, ctx->stream, pts, m, stash);
-    else
-      hipLaunchKernelGGL(k_bmv_table<MSM377_POINTS_MONT_FLAG>, grid, block, 0, ctx->stream, pts, m, stash);
+    bmv_launch_table(ctx, form, (const uint8_t*)d_points + off * in_stride, m, stash);
     rc = bm_normalise(ctx, m * BMV_ENTRIES, BM_FORM_TABLE, ctx->bm.var_table, nullptr);
     if (rc) break;
     hipLaunchKernelGGL(k_bmv_accumulate, grid, block, 0, ctx->stream, table, (const uint32_t*)d_scalars + off * stride_words, m, stride_words, scalars_mont, stash);
@@ -2130,6 +2149,97 @@ int g1_batch_mul_var(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scal
     if (scalar_stride) rc = hip_ok(ctx, hipMemcpy(d_io, scalars + off * 32, m * 32, hipMemcpyHostToDevice), "hipMemcpy(scalars)") ? MSM377_OK : MSM377_EHIP;
     if (!rc) rc = hip_ok(ctx, hipMemcpy(d_io + off_pts, points + off * in_stride, m * in_stride, hipMemcpyHostToDevice), "hipMemcpy(points)") ? MSM377_OK : MSM377_EHIP;
     if (!rc) rc = g1_batch_mul_var_device(ctx, d_io + off_pts, d_io, m, scalar_stride, out_form, d_io + off_out, d_io + off_inf);
+    if (!rc) rc = hip_ok(ctx, hipMemcpy(out_points + off * out_stride, d_io + off_out, m * out_stride, hipMemcpyDeviceToHost), "hipMemcpy(records)") ? MSM377_OK : MSM377_EHIP;
+    if (!rc && out_inf) rc = hip_ok(ctx, hipMemcpy(out_inf + off, d_io + off_inf, m, hipMemcpyDeviceToHost), "hipMemcpy(flags)") ? MSM377_OK : MSM377_EHIP;
+  }
+  (void)hipFree(d_io);
+  return rc;
+}
+
+// ---- pairwise linear combination (include/msm377.h "pairwise linear combination"; kernels/batch_lincomb2.hpp) ----
+// Per pass of BL2_PASS pairs: both tables through the stash and ONE normalisation, then the joint walk and the
+// normalisation again, all on ctx->stream; the one host wait is the synchronisation at the end of the call.  A pass reads
+// all of its inputs before it writes its outputs, and passes cover disjoint index ranges: d_out_points == d_p or == d_q
+// is safe for records of equal size, and so is the fold in place (q = p + h records, out = p, n = h).
+namespace {
+
+int bl2_check_args(msm377_ctx* ctx, uint32_t a_stride, uint32_t b_stride, uint32_t out_form) {
+  const int rc = bm_check_form(ctx, out_form);
+  if (rc) return rc;
+  if (!bmv_stride_ok(a_stride) || !bmv_stride_ok(b_stride)) {
+    ctx->err = "a_stride and b_stride are each 32 (a scalar per pair) or 0 (one scalar for all pairs)";
+    return MSM377_EINVAL;
+  }
+  return MSM377_OK;
+}
+
+}  // namespace
+
+int g1_batch_lincomb2_device(msm377_ctx* ctx, const void* d_p, const void* d_q, const void* d_a, const void* d_b, uint64_t n, uint32_t a_stride, uint32_t b_stride,
+                             uint32_t out_form, void* d_out_points, uint8_t* d_out_inf) {
+  int rc = bl2_check_args(ctx, a_stride, b_stride, out_form);
+  if (rc) return rc;
+  if (n == 0) return MSM377_OK;
+  const uint32_t form = ctx->point_form;
+  const size_t in_stride = bmv_point_stride(form), out_stride = bmv_point_stride(out_form);
+  rc = bmv_check_pointers(ctx, {d_a, d_b}, {d_p, d_q}, in_stride, d_out_points, out_stride);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  rc = bm_ensure_scratch(ctx);
+  if (!rc) rc = bm_alloc(ctx, &ctx->bm.var_table, (size_t)BM_CHUNK * BM_REC_WORDS * 4);
+  if (rc) return rc;
+  uint4* stash = reinterpret_cast<uint4*>(ctx->bm.stash);
+  const uint32_t* table = ctx->bm.var_table;
+  const uint32_t a_words = a_stride / 4, b_words = b_stride / 4, scalars_mont = ctx->scalar_form == MSM377_SCALARS_MONT ? 1u : 0u;
+  for (uint64_t off = 0; off < n && !rc; off += BL2_PASS) {
+    const uint64_t m = std::min<uint64_t>(BL2_PASS, n - off);
+    bmv_launch_table(ctx, form, (const uint8_t*)d_p + off * in_stride, m, stash);
+    bmv_launch_table(ctx, form, (const uint8_t*)d_q + off * in_stride, m, stash + BMV_ENTRIES * m);
+    rc = bm_normalise(ctx, m * BL2_TERMS * BMV_ENTRIES, BM_FORM_TABLE, ctx->bm.var_table, nullptr);
+    if (rc) break;
+    hipLaunchKernelGGL(k_bl2_accumulate, dim3((unsigned)((m + BM_THREADS - 1) / BM_THREADS)), dim3(BM_THREADS), 0, ctx->stream, table, (const uint32_t*)d_a + off * a_words,
+                       (const uint32_t*)d_b + off * b_words, m, a_words, b_words, scalars_mont, stash);
+    rc = bm_normalise(ctx, m, out_form, (uint8_t*)d_out_points + off * out_stride, d_out_inf ? d_out_inf + off : nullptr);
+  }
+  const hipError_t e = hipStreamSynchronize(ctx->stream);
+  if (rc) return rc;
+  HIP_TRY(ctx, e);
+  return MSM377_OK;
+}
+
+// Host buffers: both scalar arrays and both point arrays up, records (and flags) down, a chunk's worth of device staging
+// for the length of the call.  A stride-0 scalar is uploaded once.
+int g1_batch_lincomb2(msm377_ctx* ctx, const uint8_t* p, const uint8_t* q, const uint8_t* a, const uint8_t* b, uint64_t n, uint32_t a_stride, uint32_t b_stride, uint32_t out_form,
+                      uint8_t* out_points, uint8_t* out_inf) {
+  int rc = bl2_check_args(ctx, a_stride, b_stride, out_form);
+  if (rc) return rc;
+  if (n == 0) return MSM377_OK;
+  if (!p || !q || !a || !b || !out_points) {
+    ctx->err = "null pointer";
+    return MSM377_EINVAL;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t in_stride = bmv_point_stride(ctx->point_form), out_stride = bmv_point_stride(out_form);
+  const uint64_t piece = std::min<uint64_t>(n, BM_CHUNK);
+  const auto round16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  uint8_t* d_io = nullptr;  // a, b, p, q, records, flags: 16-byte aligned parts
+  const size_t off_b = (size_t)piece * 32, off_p = 2 * off_b, off_q = off_p + round16((size_t)piece * in_stride), off_out = off_q + round16((size_t)piece * in_stride),
+               off_inf = off_out + round16((size_t)piece * out_stride);
+  if (hipMalloc((void**)&d_io, off_inf + piece) != hipSuccess) {
+    (void)hipGetLastError();
+    ctx->err = "out of device memory for the linear combination staging";
+    return MSM377_ENOMEM;
+  }
+  const auto up = [&](size_t dst, const uint8_t* src, size_t bytes, const char* what) { return hip_ok(ctx, hipMemcpy(d_io + dst, src, bytes, hipMemcpyHostToDevice), what) ? MSM377_OK : MSM377_EHIP; };
+  if (a_stride == 0) rc = up(0, a, 32, "hipMemcpy(scalar a)");
+  if (!rc && b_stride == 0) rc = up(off_b, b, 32, "hipMemcpy(scalar b)");
+  for (uint64_t off = 0; off < n && !rc; off += piece) {
+    const uint64_t m = std::min<uint64_t>(piece, n - off);
+    if (a_stride) rc = up(0, a + off * 32, m * 32, "hipMemcpy(scalars a)");
+    if (!rc && b_stride) rc = up(off_b, b + off * 32, m * 32, "hipMemcpy(scalars b)");
+    if (!rc) rc = up(off_p, p + off * in_stride, m * in_stride, "hipMemcpy(points p)");
+    if (!rc) rc = up(off_q, q + off * in_stride, m * in_stride, "hipMemcpy(points q)");
+    if (!rc) rc = g1_batch_lincomb2_device(ctx, d_io + off_p, d_io + off_q, d_io, d_io + off_b, m, a_stride, b_stride, out_form, d_io + off_out, d_io + off_inf);
     if (!rc) rc = hip_ok(ctx, hipMemcpy(out_points + off * out_stride, d_io + off_out, m * out_stride, hipMemcpyDeviceToHost), "hipMemcpy(records)") ? MSM377_OK : MSM377_EHIP;
     if (!rc && out_inf) rc = hip_ok(ctx, hipMemcpy(out_inf + off, d_io + off_inf, m, hipMemcpyDeviceToHost), "hipMemcpy(flags)") ? MSM377_OK : MSM377_EHIP;
   }

@@ -44,6 +44,11 @@ int g1_batch_mul(msm377_ctx* ctx, const uint8_t base_xy[96], const uint8_t* scal
 // Variable-base batch multiplication (kernels/batch_mul_var.hpp): out[i] = [s_i]P_i.
 int g1_batch_mul_var_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t scalar_stride, uint32_t out_form, void* d_out_points, uint8_t* d_out_inf);
 int g1_batch_mul_var(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint32_t scalar_stride, uint32_t out_form, uint8_t* out_points, uint8_t* out_inf);
+// Pairwise linear combination (kernels/batch_lincomb2.hpp): out[i] = [a_i]P_i + [b_i]Q_i.
+int g1_batch_lincomb2_device(msm377_ctx* ctx, const void* d_p, const void* d_q, const void* d_a, const void* d_b, uint64_t n, uint32_t a_stride, uint32_t b_stride,
+                             uint32_t out_form, void* d_out_points, uint8_t* d_out_inf);
+int g1_batch_lincomb2(msm377_ctx* ctx, const uint8_t* p, const uint8_t* q, const uint8_t* a, const uint8_t* b, uint64_t n, uint32_t a_stride, uint32_t b_stride, uint32_t out_form,
+                      uint8_t* out_points, uint8_t* out_inf);
 
 void twin_return(msm377_ctx* ctx);  // takes back the resident bases a batch call lent to the twin of ctx
 

@@ -222,6 +222,9 @@ def load_library():
         "msm377_g1_batch_mul_var_device": (i32, [vp, vp, vp, u64, u32, u32, vp, vp]),
         "msm377_g1_batch_mul_var": (i32, [vp, u8p, u8p, u64, u32, u32, vp, vp]),
         "msm377_g1_batch_mul_var_host": (i32, [u8p, u32, u8p, u32, u64, u32, u32, vp, vp]),
+        "msm377_g1_batch_lincomb2_device": (i32, [vp, vp, vp, vp, vp, u64, u32, u32, u32, vp, vp]),
+        "msm377_g1_batch_lincomb2": (i32, [vp, u8p, u8p, u8p, u8p, u64, u32, u32, u32, vp, vp]),
+        "msm377_g1_batch_lincomb2_host": (i32, [u8p, u8p, u32, u8p, u8p, u32, u64, u32, u32, u32, vp, vp]),
         "msm377_ctx_set_mul_window": (i32, [vp, i32]),
         "msm377_ctx_get_last_mul_window": (i32, [vp]),
         "msm377_ctx_get_mul_table_builds": (u64, [vp]),
@@ -378,6 +381,28 @@ def batch_mul_var_host(points: bytes, scalars: bytes, out_form="wire", point_for
     )
     if rc:
         raise MsmError(rc, "msm377_g1_batch_mul_var_host")
+    return out.raw[: stride * n], inf.raw[:n]
+
+
+def batch_lincomb2_host(p: bytes, q: bytes, a: bytes, b: bytes, out_form="wire", point_form="wire", scalar_form="wire") -> Tuple[bytes, bytes]:
+    """out[i] = [a_i]P_i + [b_i]Q_i on the calling thread (msm377_g1_batch_lincomb2_host): no context, no device.  ``p``,
+    ``q``: records of ``point_form``, as many of one as of the other; ``a``, ``b``: each 32 bytes per pair, or 32 bytes for
+    all of them.  Returns (records, identity flags) as batch_mul_host does."""
+    pf = _form(_POINT_FORMS, point_form, "point")
+    in_stride = _POINT_STRIDE.get(pf, 96)
+    if len(p) % in_stride or len(q) != len(p):
+        raise ValueError("p and q: the same number of %d-byte records" % in_stride)
+    n = len(p) // in_stride
+    f = _batch_mul_out_form(out_form)
+    stride = _POINT_STRIDE.get(f, 96)
+    out = ctypes.create_string_buffer(max(1, stride * n))
+    inf = ctypes.create_string_buffer(max(1, n))
+    rc = load_library().msm377_g1_batch_lincomb2_host(
+        bytes(p), bytes(q), pf, bytes(a), bytes(b), _form(_SCALAR_FORMS, scalar_form, "scalar"), n, _var_scalar_stride(a, n), _var_scalar_stride(b, n), f,
+        ctypes.addressof(out), ctypes.addressof(inf)
+    )
+    if rc:
+        raise MsmError(rc, "msm377_g1_batch_lincomb2_host")
     return out.raw[: stride * n], inf.raw[:n]
 
 
@@ -713,6 +738,33 @@ class MsmEngine:
         inf = ctypes.create_string_buffer(max(1, n))
         rc = self._lib.msm377_g1_batch_mul_var(self._ctx, bytes(points), bytes(scalars), n, _var_scalar_stride(scalars, n), f, ctypes.addressof(out), ctypes.addressof(inf))
         self._check(rc, "msm377_g1_batch_mul_var")
+        return out.raw[: stride * n], inf.raw[:n]
+
+    # -- pairwise linear combination (include/msm377.h): out[i] = [a_i]P_i + [b_i]Q_i --
+    def batch_lincomb2_device(self, d_p: int, d_q: int, d_a: int, d_b: int, n: int, d_out: int, d_inf: int = 0, out_form="wire", a_stride: int = 32, b_stride: int = 32):
+        """n pairs of points and of scalars in HBM (in the engine's point and scalar forms; ``a_stride`` / ``b_stride`` 0:
+        one scalar for all pairs): n records at ``d_out`` and, if ``d_inf`` is given, n identity flag bytes there
+        (msm377_g1_batch_lincomb2_device).  Any n; every curve point is a legal input and every relation between the two
+        arrays; ``d_out`` may be ``d_p`` or ``d_q`` when the records have the same size."""
+        rc = self._lib.msm377_g1_batch_lincomb2_device(
+            self._ctx, d_p or None, d_q or None, d_a or None, d_b or None, int(n), int(a_stride), int(b_stride), _batch_mul_out_form(out_form), d_out or None, d_inf or None
+        )
+        self._check(rc, "msm377_g1_batch_lincomb2_device")
+
+    def batch_lincomb2(self, p: bytes, q: bytes, a: bytes, b: bytes, out_form="wire") -> Tuple[bytes, bytes]:
+        """The same on host buffers: returns (records, identity flags).  A 32-byte ``a`` or ``b`` with more than one pair
+        is the one scalar of all pairs (msm377_g1_batch_lincomb2)."""
+        n = self._count_points(p)
+        if len(q) != len(p):
+            raise ValueError("p and q: the same number of records")
+        f = _batch_mul_out_form(out_form)
+        stride = _POINT_STRIDE.get(f, 96)
+        out = ctypes.create_string_buffer(max(1, stride * n))
+        inf = ctypes.create_string_buffer(max(1, n))
+        rc = self._lib.msm377_g1_batch_lincomb2(
+            self._ctx, bytes(p), bytes(q), bytes(a), bytes(b), n, _var_scalar_stride(a, n), _var_scalar_stride(b, n), f, ctypes.addressof(out), ctypes.addressof(inf)
+        )
+        self._check(rc, "msm377_g1_batch_lincomb2")
         return out.raw[: stride * n], inf.raw[:n]
 
     def set_mul_window(self, bits: int = 0):

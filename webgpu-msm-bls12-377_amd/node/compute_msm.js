@@ -128,4 +128,13 @@ const batch_mul_var = (points, scalars, { outForm = 'wire' } = {}) => {
   return addon.batchMulVarSync(pointsToBuffer(points), scalarsToBuffer(scalars), BATCH_MUL_FORMS[outForm]);
 };
 
-module.exports = { batch_mul, batch_mul_var, compute_msm, compute_msm_edwards, set_bases, compute_msm_fixed_base, check_points, CHECK_CANONICAL, CHECK_CURVE, CHECK_SUBGROUP, CHECK_ALL, pointsToBuffer, scalarsToBuffer, version: addon.version };
+// Pairwise linear combination (msm377_g1_batch_lincomb2): out[i] = [a_i]P_i + [b_i]Q_i, every output its own point.  `p`, `q`:
+// as many {x, y} points, or Buffers of 96-byte wire records; `a`, `b`: each one scalar per pair, or ONE scalar (a 32-byte
+// Buffer, a one-element array) for all pairs.  Returns {points, infinity} as batch_mul does.  Any curve point is a legal
+// input, and any relation between p[i] and q[i].
+const batch_lincomb2 = (p, q, a, b, { outForm = 'wire' } = {}) => {
+  if (!(outForm in BATCH_MUL_FORMS)) throw new RangeError("outForm: wire | mont_flag (plain mont cannot say 'identity')");
+  return addon.batchLincomb2Sync(pointsToBuffer(p), pointsToBuffer(q), scalarsToBuffer(a), scalarsToBuffer(b), BATCH_MUL_FORMS[outForm]);
+};
+
+module.exports = { batch_lincomb2, batch_mul, batch_mul_var, compute_msm, compute_msm_edwards, set_bases, compute_msm_fixed_base, check_points, CHECK_CANONICAL, CHECK_CURVE, CHECK_SUBGROUP, CHECK_ALL, pointsToBuffer, scalarsToBuffer, version: addon.version };

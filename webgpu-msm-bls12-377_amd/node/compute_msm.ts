@@ -205,3 +205,19 @@ export const batch_mul_var = (
   }
   return addon.batchMulVarSync(pointsToBuffer(points), scalarsToBuffer(scalars), BATCH_MUL_FORMS[outForm]);
 };
+
+// Pairwise linear combination (msm377_g1_batch_lincomb2): out[i] = [a_i]P_i + [b_i]Q_i, every output its own point.  `a`, `b`:
+// each one scalar per pair, or ONE scalar (a 32-byte Buffer, a one-element array) for all pairs.  Returns what batch_mul
+// returns.
+export const batch_lincomb2 = (
+  p: BigIntPoint[] | U32ArrayPoint[] | Buffer,
+  q: BigIntPoint[] | U32ArrayPoint[] | Buffer,
+  a: bigint[] | Uint32Array[] | Buffer,
+  b: bigint[] | Uint32Array[] | Buffer,
+  { outForm = 'wire' }: { outForm?: keyof typeof BATCH_MUL_FORMS } = {},
+): { points: Buffer; infinity: Buffer } => {
+  if (!(outForm in BATCH_MUL_FORMS)) {
+    throw new RangeError("outForm: wire | mont_flag (plain mont cannot say 'identity')");
+  }
+  return addon.batchLincomb2Sync(pointsToBuffer(p), pointsToBuffer(q), scalarsToBuffer(a), scalarsToBuffer(b), BATCH_MUL_FORMS[outForm]);
+};

@@ -21,6 +21,8 @@
 //   batchMulVarSync(points: Buffer 96n, scalars: Buffer 32n | 32, outForm: number): {points: Buffer, infinity: Buffer}
 //                                                                      out[i] = [s_i]P_i (msm377_g1_batch_mul_var); 32 bytes of
 //                                                                      scalars for n > 1 points: one scalar for all
+//   batchLincomb2Sync(p: Buffer 96n, q: Buffer 96n, a: Buffer 32n | 32, b: Buffer 32n | 32, outForm: number): {points, infinity}
+//                                                                      out[i] = [a_i]P_i + [b_i]Q_i (msm377_g1_batch_lincomb2)
 //   version(): string
 // Errors reject / throw a JS Error carrying msm377_strerror + msm377_last_error, matching the
 // reference's behaviour of throwing Error (cuzk/gpu.ts:7-10).
@@ -427,6 +429,54 @@ napi_value BatchMulVarSync(napi_env env, napi_callback_info info) {
   return obj;
 }
 
+// batchLincomb2Sync(p, q, a, b, outForm) -> {points, infinity}: out[i] = [a_i]P_i + [b_i]Q_i on wire points; 32 bytes of a
+// or of b for more than one pair are the ONE scalar of all pairs (stride 0)
+napi_value BatchLincomb2Sync(napi_env env, napi_callback_info info) {
+  size_t argc = 5;
+  napi_value argv[5];
+  uint32_t form = MSM377_POINTS_WIRE;
+  bool ok = napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) == napi_ok && argc >= 5;
+  for (int k = 0; ok && k < 4; k++) {
+    bool is = false;
+    ok = napi_is_buffer(env, argv[k], &is) == napi_ok && is;
+  }
+  if (!ok || napi_get_value_uint32(env, argv[4], &form) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "expected (p, q: Buffers of 96 bytes per point, a, b: Buffers of 32 bytes per scalar, outForm: number)");
+    return nullptr;
+  }
+  uint8_t* in[4];
+  size_t len[4];
+  for (int k = 0; k < 4; k++) napi_get_buffer_info(env, argv[k], reinterpret_cast<void**>(&in[k]), &len[k]);
+  const uint64_t n = len[0] / 96;
+  const uint32_t a_stride = (len[2] == 32 && n > 1) ? 0 : 32, b_stride = (len[3] == 32 && n > 1) ? 0 : 32;
+  if (len[0] % 96 != 0 || len[1] != len[0] || (a_stride && len[2] != n * 32) || (b_stride && len[3] != n * 32) || (form != MSM377_POINTS_WIRE && form != MSM377_POINTS_MONT_FLAG)) {
+    napi_throw_range_error(env, nullptr, "p and q must hold the same number of 96-byte points, a and b 32 bytes per pair (or 32 bytes for all); outForm is 0 (wire) or 2 (mont_flag)");
+    return nullptr;
+  }
+  const size_t stride = form == MSM377_POINTS_MONT_FLAG ? 104 : 96;
+  napi_value points, infinity, obj;
+  void *pd = nullptr, *id = nullptr;
+  if (napi_create_buffer(env, n * stride, &pd, &points) != napi_ok || napi_create_buffer(env, n, &id, &infinity) != napi_ok) return nullptr;
+  std::string err;
+  int rc;
+  {
+    std::lock_guard<std::mutex> lock(g_mu);
+    rc = ensure_ctx(1, &err);  // any capacity: the call walks n in passes of its own
+    if (!rc) {
+      rc = msm377_g1_batch_lincomb2(g_ctx, in[0], in[1], in[2], in[3], n, a_stride, b_stride, form, static_cast<uint8_t*>(pd), static_cast<uint8_t*>(id));
+      if (rc) err = std::string("msm377_g1_batch_lincomb2: ") + msm377_strerror(rc) + ": " + msm377_last_error(g_ctx);
+    }
+  }
+  if (rc) {
+    napi_throw_error(env, nullptr, err.c_str());
+    return nullptr;
+  }
+  napi_create_object(env, &obj);
+  napi_set_named_property(env, obj, "points", points);
+  napi_set_named_property(env, obj, "infinity", infinity);
+  return obj;
+}
+
 struct Job {
   napi_async_work work = nullptr;
   napi_deferred deferred = nullptr;
@@ -501,6 +551,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"checkPointsSync", nullptr, CheckPointsSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"batchMulSync", nullptr, BatchMulSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"batchMulVarSync", nullptr, BatchMulVarSync, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"batchLincomb2Sync", nullptr, BatchLincomb2Sync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"version", nullptr, Version, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
