@@ -517,6 +517,51 @@ int msm377_ctx_set_mul_window(msm377_ctx* ctx, int window_bits);
 int msm377_ctx_get_last_mul_window(const msm377_ctx* ctx);
 uint64_t msm377_ctx_get_mul_table_builds(const msm377_ctx* ctx);
 
+/* ---- multi-base batch multiplication ------------------------------------------------------ */
+
+/* out[i] = sum_{j<k} [s_ij]B_j: n outputs over a handful of fixed bases, each returned as its own affine point (Pedersen
+ * commitments [m_i]G + [r_i]H, the second half of an ElGamal ciphertext [m_i]G + [r_i]PK, a hiding SRS
+ * [tau^i]G + [rho_i]H, commitments to n short vectors over k generators).  Wherever the two overlap the contract is that
+ * of msm377_g1_batch_mul* above -- the meaning of a scalar (every 32-byte value, a wire scalar NOT reduced mod r, no
+ * MSM377_ESCALAR), the context's scalar form (the host twin takes wire scalars), bases as 96 wire bytes in HOST memory
+ * with a coordinate of p or more MSM377_EINVAL, every curve point a legal base, the two output forms and out_inf, any n
+ * in passes of 2^20 outputs over the same scratch, the alignment of device pointers, synchronous calls, MSM377_EINVAL
+ * with the outputs untouched -- and this section states only what differs (csrc/kernels/batch_mul_multi.hpp).
+ *
+ * Bases and scalars.  bases_xy holds k records of 96 bytes, k = 1 .. MSM377_MUL_MAX_BASES.  s_ij is the 32 bytes at
+ * scalars + i * out_stride + j * base_stride; both strides are byte counts and non-zero multiples of 32:
+ *   row-major       out_stride = 32 k, base_stride = 32
+ *   column-major    out_stride = 32,   base_stride = 32 n
+ *   padded rows     out_stride > 32 k, base_stride = 32
+ * Scalars are only read, so rows may overlap as the caller likes.  Any other k or stride is MSM377_EINVAL.  k = 1
+ * returns byte for byte what msm377_g1_batch_mul* returns.
+ *
+ * Relations.  Every relation between the bases is legal and followed through: B_1 = B_0, B_1 = -B_0, B_1 = [m]B_0, bases
+ * of order 2, 3, 4 and 6, an output of O with no term O.
+ *
+ * Width.  msm377_ctx_set_mul_window applies (0 = the rule, 8, 16) and msm377_ctx_get_last_mul_window reports the width
+ * the call ran.  The rule of THIS call (csrc/batch_mul_recode.hpp batch_mul_multi_rule) depends on n and k.
+ *
+ * State.  MSM377_MUL_MAX_BASES table slots on the context, beside the single-base table: slot j holds the window table
+ * of (the 96 bytes of the base at position j, the width).  A call reuses slot j < k if it is valid and both keys match
+ * and rebuilds every other slot among j < k in ONE build (msm377_ctx_get_mul_multi_table_builds counts the slots
+ * built); slots at k and above are left as they are; a failed build leaves the slots it touched invalid.  A slot's
+ * memory (0.5 MB at c = 8, 64 MB at c = 16) is allocated when it is first built and freed by msm377_ctx_destroy.  The
+ * resident MSM bases, the single-base table (msm377_ctx_get_mul_table_builds does not move), the variable-base table
+ * memory and a check call's state are untouched by these calls, and the other way round.  msm377_g1_batch_mul_multi
+ * accepts the same layouts in host memory, repacks them row-major and stages them through device memory in pieces of at
+ * most 2^20 scalars. */
+#define MSM377_MUL_MAX_BASES 16
+int msm377_g1_batch_mul_multi_device(msm377_ctx* ctx, const uint8_t* bases_xy /* k x 96, HOST */, uint32_t k, const void* d_scalars, uint64_t n, uint64_t out_stride,
+                                     uint64_t base_stride, uint32_t out_form, void* d_out_points, uint8_t* d_out_inf);
+int msm377_g1_batch_mul_multi(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k, const uint8_t* scalars, uint64_t n, uint64_t out_stride, uint64_t base_stride,
+                              uint32_t out_form, uint8_t* out_points, uint8_t* out_inf);
+/* The same on ONE CPU thread: no device, no context (csrc/batch_mul_multi_host.hpp): the terms of each base by the
+ * single-base twin, then general additions; the yardstick of the device call. */
+int msm377_g1_batch_mul_multi_host(const uint8_t* bases_xy, uint32_t k, const uint8_t* scalars, uint64_t n, uint64_t out_stride, uint64_t base_stride, uint32_t out_form,
+                                   uint8_t* out_points, uint8_t* out_inf);
+uint64_t msm377_ctx_get_mul_multi_table_builds(const msm377_ctx* ctx);
+
 /* ---- variable-base batch multiplication --------------------------------------------------- */
 
 /* out[i] = [s_i]P_i: n scalar multiples of n points, each returned as its own affine point (an SRS or powers-of-tau

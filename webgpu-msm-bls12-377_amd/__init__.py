@@ -31,6 +31,7 @@ from .host.engine import (  # noqa: F401
     MsmError,
     batch_lincomb2_host,
     batch_mul_host,
+    batch_mul_multi_host,
     batch_mul_var_host,
     check_points_host,
     ed_check_points_host,
@@ -53,6 +54,7 @@ __all__ = [
     "StageInfo",
     "batch_lincomb2_host",
     "batch_mul_host",
+    "batch_mul_multi_host",
     "batch_mul_var_host",
     "check_points_host",
     "ed_check_points_host",

@@ -54,22 +54,12 @@ inline void batch_mul_write_outputs_host(const std::vector<G1H::XYZZ>& acc, uint
   }
 }
 
-// scalar_form: MSM377_SCALARS_WIRE (32-byte integers, any value below 2^256, NOT reduced mod r: B may lie outside the
-// prime-order subgroup) or MSM377_SCALARS_MONT (v 2^-256 mod r, fully reduced, as the MSM calls read them).
-// out_form: MSM377_POINTS_WIRE (96-byte records, the identity as x = 0, y = 1) or MSM377_POINTS_MONT_FLAG (104-byte
-// records: what msm377_g1_result_to_native makes of the wire record, the flag set for a true identity only).
-// out_inf (may be null): n bytes, 1 for the identity.  MSM377_EINVAL leaves the outputs untouched.
-inline int batch_mul_host(const uint8_t base_xy[96], const uint8_t* scalars, uint64_t n, uint32_t scalar_form, uint32_t out_form, uint8_t* out_points, uint8_t* out_inf) {
-  if (out_form != MSM377_POINTS_WIRE && out_form != MSM377_POINTS_MONT_FLAG) return MSM377_EINVAL;
-  if (scalar_form > MSM377_SCALARS_MONT) return MSM377_EINVAL;
-  if (n == 0) return MSM377_OK;
-  if (!base_xy || !scalars || !out_points) return MSM377_EINVAL;
-  uint64_t lim[2][6];
-  memcpy(lim, base_xy, 96);  // little-endian host
-  if (Fp64::geq_p(lim[0]) || Fp64::geq_p(lim[1])) return MSM377_EINVAL;
+// The terms of one base: acc[i] = [s_i]B as XYZZ points, s_i the 32 bytes at scalars + i * stride.  base_xy: 96 canonical
+// wire bytes (the callers check).  batch_mul_host below and batch_mul_multi_host.hpp (one call per base) run this.
+inline std::vector<G1H::XYZZ> batch_mul_terms_host(const uint8_t base_xy[96], const uint8_t* scalars, uint64_t n, uint64_t stride, uint32_t scalar_form) {
   G1H::Affine b;
-  memcpy(b.x.v, lim[0], 48);
-  memcpy(b.y.v, lim[1], 48);
+  memcpy(b.x.v, base_xy, 48);  // little-endian host
+  memcpy(b.y.v, base_xy + 48, 48);
   b.x = Fp64::mul(b.x, Fp64::from_const(G1Consts64::R2));
   b.y = Fp64::mul(b.y, Fp64::from_const(G1Consts64::R2));
 
@@ -85,7 +75,7 @@ inline int batch_mul_host(const uint8_t base_xy[96], const uint8_t* scalars, uin
   std::vector<G1H::XYZZ> acc(n);
   for (uint64_t i = 0; i < n; i++) {
     uint8_t wire[32];
-    import_scalars_host(scalars + i * 32, 1, scalar_form, wire);
+    import_scalars_host(scalars + i * stride, 1, scalar_form, wire);
     uint32_t s[8];
     memcpy(s, wire, 32);
     G1H::XYZZ a = G1H::identity();
@@ -98,6 +88,23 @@ inline int batch_mul_host(const uint8_t base_xy[96], const uint8_t* scalars, uin
     }
     acc[i] = a;
   }
+  return acc;
+}
+
+// scalar_form: MSM377_SCALARS_WIRE (32-byte integers, any value below 2^256, NOT reduced mod r: B may lie outside the
+// prime-order subgroup) or MSM377_SCALARS_MONT (v 2^-256 mod r, fully reduced, as the MSM calls read them).
+// out_form: MSM377_POINTS_WIRE (96-byte records, the identity as x = 0, y = 1) or MSM377_POINTS_MONT_FLAG (104-byte
+// records: what msm377_g1_result_to_native makes of the wire record, the flag set for a true identity only).
+// out_inf (may be null): n bytes, 1 for the identity.  MSM377_EINVAL leaves the outputs untouched.
+inline int batch_mul_host(const uint8_t base_xy[96], const uint8_t* scalars, uint64_t n, uint32_t scalar_form, uint32_t out_form, uint8_t* out_points, uint8_t* out_inf) {
+  if (out_form != MSM377_POINTS_WIRE && out_form != MSM377_POINTS_MONT_FLAG) return MSM377_EINVAL;
+  if (scalar_form > MSM377_SCALARS_MONT) return MSM377_EINVAL;
+  if (n == 0) return MSM377_OK;
+  if (!base_xy || !scalars || !out_points) return MSM377_EINVAL;
+  uint64_t lim[2][6];
+  memcpy(lim, base_xy, 96);  // little-endian host
+  if (Fp64::geq_p(lim[0]) || Fp64::geq_p(lim[1])) return MSM377_EINVAL;
+  const std::vector<G1H::XYZZ> acc = batch_mul_terms_host(base_xy, scalars, n, 32, scalar_form);
   batch_mul_write_outputs_host(acc, out_form, out_points, out_inf);
   return MSM377_OK;
 }

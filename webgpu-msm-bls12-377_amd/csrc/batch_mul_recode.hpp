@@ -55,4 +55,17 @@ constexpr uint64_t BM_WIDE_MIN_OUTPUTS = 1ull << 19;
 inline bool batch_mul_width_supported(int c) { return c == BM_NARROW_WIDTH || c == BM_WIDE_WIDTH; }
 inline int batch_mul_rule(uint64_t n) { return n >= BM_WIDE_MIN_OUTPUTS ? BM_WIDE_WIDTH : BM_NARROW_WIDTH; }
 
+// The multi-base call (msm377_g1_batch_mul_multi*, k tables walked into one accumulator): per base the trade is the one
+// above -- the row-base chain is paid once per build whatever k, the entries and their normalisation once per table, the
+// saving of the wide table once per walk.  Measured for k = 2, 4, 8 (profiles/batch_mul_multi/sweep.txt): a warm call of
+// 2^20 outputs saves 1.75 to 1.86 ms PER TABLE on the wide tables (2^19: 0.90 to 0.99 ms) and a build costs 2.4 to 2.6 ms
+// more PER TABLE (k = 2: 12.5 against 7.3 ms, k = 8: 26.9 against 7.3).  Both sides scale with k, so the crossover in n is
+// the single-base call's for every k -- one cold call breaks even at about 1.4 million outputs, two calls at 2^19.5, three
+// at 2^19 -- and so is the rule.  k stays an argument: it is what a rule for tables far past the Infinity Cache would read
+// (1.07 GB at k = 16 showed no slowdown).
+inline int batch_mul_multi_rule(uint64_t n, uint32_t k) {
+  (void)k;
+  return batch_mul_rule(n);
+}
+
 }  // namespace msm377

@@ -11,6 +11,7 @@
 #include "host_tail.hpp"
 #include "sequencer.hpp"
 #include "batch_mul_host.hpp"
+#include "batch_mul_multi_host.hpp"
 #include "batch_lincomb2_host.hpp"
 #include "batch_mul_var_host.hpp"
 #include "import_host.hpp"
@@ -264,6 +265,11 @@ int msm377_g1_batch_mul_host(const uint8_t base_xy[96], const uint8_t* scalars, 
   return batch_mul_host(base_xy, scalars, n, MSM377_SCALARS_WIRE, out_form, out_points, out_inf);
 }
 
+int msm377_g1_batch_mul_multi_host(const uint8_t* bases_xy, uint32_t k, const uint8_t* scalars, uint64_t n, uint64_t out_stride, uint64_t base_stride, uint32_t out_form,
+                                   uint8_t* out_points, uint8_t* out_inf) {
+  return batch_mul_multi_host(bases_xy, k, scalars, n, out_stride, base_stride, MSM377_SCALARS_WIRE, out_form, out_points, out_inf);
+}
+
 int msm377_g1_batch_mul_var_host(const uint8_t* points, uint32_t point_form, const uint8_t* scalars, uint32_t scalar_form, uint64_t n, uint32_t scalar_stride, uint32_t out_form,
                                  uint8_t* out_points, uint8_t* out_inf) {
   return batch_mul_var_host(points, point_form, scalars, scalar_form, n, scalar_stride, out_form, out_points, out_inf);
@@ -283,6 +289,8 @@ int msm377_ctx_set_mul_window(msm377_ctx* ctx, int window_bits) {
 int msm377_ctx_get_last_mul_window(const msm377_ctx* ctx) { return ctx ? ctx->bm.last_window : 0; }
 
 uint64_t msm377_ctx_get_mul_table_builds(const msm377_ctx* ctx) { return ctx ? ctx->bm.builds : 0; }
+
+uint64_t msm377_ctx_get_mul_multi_table_builds(const msm377_ctx* ctx) { return ctx ? ctx->bmm.builds : 0; }
 
 int msm377_ctx_get_last_check(const msm377_ctx* ctx, msm377_check_report* out) {
   if (!ctx || !out) return MSM377_EINVAL;
@@ -381,6 +389,14 @@ int msm377_g1_glv_window_partials_device(msm377_ctx* ctx, const void* d_points, 
 int msm377_g1_generate_bases_device(msm377_ctx* ctx, uint64_t seed, uint64_t n, void* d_points_out) { return eng::g1_generate_bases_device(ctx, seed, n, d_points_out); }
 int msm377_g1_batch_mul_device(msm377_ctx* ctx, const uint8_t base_xy[96], const void* d_scalars, uint64_t n, uint32_t out_form, void* d_out_points, uint8_t* d_out_inf) { return eng::g1_batch_mul_device(ctx, base_xy, d_scalars, n, out_form, d_out_points, d_out_inf); }
 int msm377_g1_batch_mul(msm377_ctx* ctx, const uint8_t base_xy[96], const uint8_t* scalars, uint64_t n, uint32_t out_form, uint8_t* out_points, uint8_t* out_inf) { return eng::g1_batch_mul(ctx, base_xy, scalars, n, out_form, out_points, out_inf); }
+int msm377_g1_batch_mul_multi_device(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k, const void* d_scalars, uint64_t n, uint64_t out_stride, uint64_t base_stride,
+                                     uint32_t out_form, void* d_out_points, uint8_t* d_out_inf) {
+  return eng::g1_batch_mul_multi_device(ctx, bases_xy, k, d_scalars, n, out_stride, base_stride, out_form, d_out_points, d_out_inf);
+}
+int msm377_g1_batch_mul_multi(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k, const uint8_t* scalars, uint64_t n, uint64_t out_stride, uint64_t base_stride, uint32_t out_form,
+                              uint8_t* out_points, uint8_t* out_inf) {
+  return eng::g1_batch_mul_multi(ctx, bases_xy, k, scalars, n, out_stride, base_stride, out_form, out_points, out_inf);
+}
 int msm377_g1_batch_mul_var_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t scalar_stride, uint32_t out_form, void* d_out_points, uint8_t* d_out_inf) {
   return eng::g1_batch_mul_var_device(ctx, d_points, d_scalars, n, scalar_stride, out_form, d_out_points, d_out_inf);
 }

@@ -86,6 +86,26 @@ struct BatchMulState {
   uint32_t* var_table = nullptr;
 };
 
+// Multi-base batch multiplication (msm377_g1_batch_mul_multi*, kernels/batch_mul_multi.hpp): one window table per base
+// POSITION, each keyed like BatchMulState's by the base's 96 wire bytes and the width, each its own allocation (made when
+// the slot is first built, regrown for a wider table).  A build clears `valid` of every slot it rebuilds first and sets
+// it as its last step.  The stash, the trees and the block products are BatchMulState's; the forced width and the last
+// width are too (msm377_ctx_set_mul_window speaks for every batch_mul call).  Nothing else is shared with it: the
+// single-base table, its key and its build count are not touched from here.
+struct BatchMulMultiState {
+  struct Slot {
+    bool valid = false;
+    uint8_t base[96] = {};
+    int width = 0;
+    uint32_t* table = nullptr;
+    uint64_t table_cap = 0;  // records allocated
+  };
+  Slot slot[MSM377_MUL_MAX_BASES];
+  uint64_t builds = 0;              // slots built so far (msm377_ctx_get_mul_multi_table_builds)
+  uint32_t* row_bases = nullptr;    // MSM377_MUL_MAX_BASES x (W + 1) table records: [2^(c w)]B_b of the slots being built
+  uint32_t* bases_wire = nullptr;   // their 96 bytes each on the device
+};
+
 // Work buffers of the 20-bit-window sort (kernels/wide.hpp) for up to `cap` points.
 struct WideBuffers {
   uint32_t* digits = nullptr;  // 13 x n u32 biased 20-bit digits, the flat list the sort reads
@@ -212,6 +232,7 @@ struct msm377_ctx {
   int timing = 0;   // msm377_ctx_set_timing: 0 off, 1 every stage, 2 the accumulation kernel only
   ResidentBases resident;             // fixed-base mode: the bases of the last successful msm377_g1_set_bases* call
   BatchMulState bm;                   // fixed-base batch multiplication: its table and scratch (allocated on first use)
+  BatchMulMultiState bmm;             // multi-base batch multiplication: a table per base position (allocated when built)
   WideBuffers wide;                   // the 20-bit-window sort's buffers (allocated with such a table; the twin's own set)
   AffineConvert aff;
   ZeroCopyOut zc;

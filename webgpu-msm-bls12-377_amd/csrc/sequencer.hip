@@ -50,6 +50,7 @@
 #include "validate_host.hpp"
 #include "kernels/accumulate.hpp"
 #include "kernels/batch_mul.hpp"
+#include "kernels/batch_mul_multi.hpp"
 #include "kernels/convert.hpp"
 #include "kernels/decompose.hpp"
 #include "kernels/generate.hpp"
@@ -2034,6 +2035,181 @@ int g1_batch_mul(msm377_ctx* ctx, const uint8_t base_xy[96], const uint8_t* scal
     const uint64_t m = std::min<uint64_t>(piece, n - off);
     rc = hip_ok(ctx, hipMemcpy(d_io, scalars + off * 32, m * 32, hipMemcpyHostToDevice), "hipMemcpy(scalars)") ? MSM377_OK : MSM377_EHIP;
     if (!rc) rc = g1_batch_mul_device(ctx, base_xy, d_io, m, out_form, d_io + off_out, d_io + off_inf);
+    if (!rc) rc = hip_ok(ctx, hipMemcpy(out_points + off * stride, d_io + off_out, m * stride, hipMemcpyDeviceToHost), "hipMemcpy(records)") ? MSM377_OK : MSM377_EHIP;
+    if (!rc && out_inf) rc = hip_ok(ctx, hipMemcpy(out_inf + off, d_io + off_inf, m, hipMemcpyDeviceToHost), "hipMemcpy(flags)") ? MSM377_OK : MSM377_EHIP;
+  }
+  ctx->bm.window = forced;
+  (void)hipFree(d_io);
+  return rc;
+}
+
+// ---- multi-base batch multiplication (include/msm377.h "multi-base batch multiplication"; kernels/batch_mul_multi.hpp) ----
+// Everything runs on ctx->stream, launch after launch, over the scratch of the single-base call; the one host wait of a
+// warm call is the synchronisation at its end.
+namespace {
+
+// Strides and k; a coordinate of p or more in any base.  Nothing is allocated, launched or changed before these pass.
+int bmm_check_shape(msm377_ctx* ctx, uint32_t k, uint64_t out_stride, uint64_t base_stride) {
+  if (k < 1 || k > MSM377_MUL_MAX_BASES) {
+    ctx->err = "k is 1 to MSM377_MUL_MAX_BASES bases";
+    return MSM377_EINVAL;
+  }
+  if (!out_stride || !base_stride || (out_stride & 31) || (base_stride & 31)) {
+    ctx->err = "out_stride and base_stride are byte counts: non-zero multiples of 32";
+    return MSM377_EINVAL;
+  }
+  return MSM377_OK;
+}
+
+int bmm_check_bases(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k) {
+  for (uint32_t j = 0; j < k; j++)
+    if (!bm_base_canonical(bases_xy + (size_t)j * 96)) {
+      ctx->err = "a base has a coordinate that is not below p";
+      return MSM377_EINVAL;
+    }
+  return MSM377_OK;
+}
+
+// Slots j < k: those whose key is (base j, c) stay; every other one is rebuilt, all of them side by side -- ONE row-base
+// launch (a workgroup per missing base), then the entries of the missing tables as one run of records cut into passes
+// of at most BM_CHUNK, wherever the cut falls.  k_bm_down writes a pass as one run too, so a pass goes through a staging
+// buffer and from there, piece by piece, into the slots it covers (device copies of at most 64 MB beside a 6 ms chain
+// of doublings); the staging is given back at the end of the build.
+int bmm_ensure_tables(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k, int c) {
+  BatchMulMultiState& mm = ctx->bmm;
+  uint32_t missing[MSM377_MUL_MAX_BASES], m = 0;
+  for (uint32_t j = 0; j < k; j++) {
+    const BatchMulMultiState::Slot& sl = mm.slot[j];
+    if (!(sl.valid && sl.width == c && memcmp(sl.base, bases_xy + (size_t)j * 96, 96) == 0)) missing[m++] = j;
+  }
+  if (m == 0) return MSM377_OK;
+  for (uint32_t b = 0; b < m; b++) mm.slot[missing[b]].valid = false;
+  const uint64_t records = bm_table_records((uint32_t)c), rows = (uint64_t)bm_windows(c) + 1, total = records * m;
+  int rc = bm_alloc(ctx, &mm.row_bases, (size_t)MSM377_MUL_MAX_BASES * (bm_windows(BM_MIN_WIDTH) + 1) * BM_REC_WORDS * 4);
+  if (!rc) rc = bm_alloc(ctx, &mm.bases_wire, (size_t)MSM377_MUL_MAX_BASES * 96);
+  for (uint32_t b = 0; b < m && !rc; b++) {
+    BatchMulMultiState::Slot& sl = mm.slot[missing[b]];
+    if (sl.table_cap >= records) continue;
+    ctx->own.release(sl.table);
+    sl.table = nullptr;
+    sl.table_cap = 0;
+    rc = bm_alloc(ctx, &sl.table, (size_t)records * BM_REC_WORDS * 4);
+    if (!rc) sl.table_cap = records;
+  }
+  uint32_t* staging = nullptr;
+  if (!rc) rc = bm_alloc(ctx, &staging, (size_t)std::min<uint64_t>(total, BM_CHUNK) * BM_REC_WORDS * 4);
+  if (rc) return rc;
+  uint8_t wire[MSM377_MUL_MAX_BASES * 96];
+  for (uint32_t b = 0; b < m; b++) memcpy(wire + (size_t)b * 96, bases_xy + (size_t)missing[b] * 96, 96);
+  uint4* stash = reinterpret_cast<uint4*>(ctx->bm.stash);
+  hipError_t e = hipMemcpyAsync(mm.bases_wire, wire, (size_t)m * 96, hipMemcpyHostToDevice, ctx->stream);  // (pageable memory: staged before the call returns)
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_bmm_row_bases, dim3(m), dim3(64), 0, ctx->stream, (const uint32_t*)mm.bases_wire, (uint32_t)c, stash);
+    rc = bm_normalise(ctx, rows * m, BM_FORM_TABLE, mm.row_bases, nullptr);
+  }
+  for (uint64_t first = 0; first < total && !rc && e == hipSuccess; first += BM_CHUNK) {
+    const uint64_t count = std::min<uint64_t>(BM_CHUNK, total - first);
+    hipLaunchKernelGGL(k_bmm_entries, dim3((unsigned)((count + BM_THREADS - 1) / BM_THREADS)), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)mm.row_bases, (uint32_t)c, first,
+                       count, stash);
+    rc = bm_normalise(ctx, count, BM_FORM_TABLE, staging, nullptr);
+    for (uint64_t g = first; g < first + count && !rc && e == hipSuccess;) {  // the pieces of this pass, one per table it covers
+      const uint64_t b = g / records, t = g - b * records, len = std::min<uint64_t>(records - t, first + count - g);
+      e = hipMemcpyAsync(mm.slot[missing[b]].table + t * BM_REC_WORDS, staging + (g - first) * BM_REC_WORDS, (size_t)len * BM_REC_WORDS * 4, hipMemcpyDeviceToDevice, ctx->stream);
+      g += len;
+    }
+  }
+  const hipError_t waited = hipStreamSynchronize(ctx->stream);  // a table is valid only once it is there; and the staging goes back
+  ctx->own.release(staging);
+  if (rc) return rc;
+  HIP_TRY(ctx, e);
+  HIP_TRY(ctx, waited);
+  for (uint32_t b = 0; b < m; b++) {
+    BatchMulMultiState::Slot& sl = mm.slot[missing[b]];
+    memcpy(sl.base, bases_xy + (size_t)missing[b] * 96, 96);
+    sl.width = c;
+    sl.valid = true;
+    mm.builds++;
+  }
+  return MSM377_OK;
+}
+
+}  // namespace
+
+int g1_batch_mul_multi_device(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k, const void* d_scalars, uint64_t n, uint64_t out_stride, uint64_t base_stride, uint32_t out_form,
+                              void* d_out_points, uint8_t* d_out_inf) {
+  int rc = bm_check_form(ctx, out_form);
+  if (!rc) rc = bmm_check_shape(ctx, k, out_stride, base_stride);
+  if (rc) return rc;
+  if (n == 0) return MSM377_OK;
+  if (!bases_xy || !d_scalars || !d_out_points) {
+    ctx->err = "null pointer";
+    return MSM377_EINVAL;
+  }
+  const uintptr_t out_align = out_form == MSM377_POINTS_WIRE ? 15 : 7;
+  if (((uintptr_t)d_scalars & 15) || ((uintptr_t)d_out_points & out_align)) {
+    ctx->err = "device pointers must be 16-byte aligned (8-byte for mont_flag records)";
+    return MSM377_EINVAL;
+  }
+  rc = bmm_check_bases(ctx, bases_xy, k);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const int c = ctx->bm.window ? ctx->bm.window : batch_mul_multi_rule(n, k);
+  rc = bm_ensure_scratch(ctx);
+  if (!rc) rc = bmm_ensure_tables(ctx, bases_xy, k, c);
+  if (rc) {
+    (void)hipStreamSynchronize(ctx->stream);
+    return rc;
+  }
+  ctx->bm.last_window = c;
+  BmmTables tables = {};
+  for (uint32_t j = 0; j < k; j++) tables.t[j] = ctx->bmm.slot[j].table;
+  const size_t stride = out_form == MSM377_POINTS_WIRE ? 96 : 104;
+  for (uint64_t off = 0; off < n && !rc; off += BM_CHUNK) {
+    const uint64_t m = std::min<uint64_t>(BM_CHUNK, n - off);
+    // Row `off` of the CALL's layout: the strides are the call's, whatever the pass's length.
+    hipLaunchKernelGGL(k_bmm_accumulate, dim3((unsigned)((m + BM_THREADS - 1) / BM_THREADS)), dim3(BM_THREADS), 0, ctx->stream, tables, (const uint8_t*)d_scalars + off * out_stride, m, k,
+                       out_stride, base_stride, (uint32_t)c, ctx->scalar_form == MSM377_SCALARS_MONT ? 1u : 0u, reinterpret_cast<uint4*>(ctx->bm.stash));
+    rc = bm_normalise(ctx, m, out_form, (uint8_t*)d_out_points + off * stride, d_out_inf ? d_out_inf + off : nullptr);
+  }
+  const hipError_t e = hipStreamSynchronize(ctx->stream);
+  if (rc) return rc;
+  HIP_TRY(ctx, e);
+  return MSM377_OK;
+}
+
+// Host buffers: each piece of at most 2^20 scalars (2^20 / k outputs) repacked row-major on the host, up, records (and
+// flags) down: the staging of the single-base call.  One width for the whole call, whatever the pieces' sizes.
+int g1_batch_mul_multi(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k, const uint8_t* scalars, uint64_t n, uint64_t out_stride, uint64_t base_stride, uint32_t out_form,
+                       uint8_t* out_points, uint8_t* out_inf) {
+  int rc = bm_check_form(ctx, out_form);
+  if (!rc) rc = bmm_check_shape(ctx, k, out_stride, base_stride);
+  if (rc) return rc;
+  if (n == 0) return MSM377_OK;
+  if (!bases_xy || !scalars || !out_points) {
+    ctx->err = "null pointer";
+    return MSM377_EINVAL;
+  }
+  rc = bmm_check_bases(ctx, bases_xy, k);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t stride = out_form == MSM377_POINTS_WIRE ? 96 : 104;
+  const uint64_t piece = std::min<uint64_t>(n, BM_CHUNK / k);
+  std::vector<uint8_t> rows((size_t)piece * k * 32);
+  uint8_t* d_io = nullptr;  // scalars, records, flags: 16-byte aligned parts
+  const size_t off_out = (size_t)piece * k * 32, off_inf = off_out + (((size_t)piece * stride + 15) & ~(size_t)15);
+  if (hipMalloc((void**)&d_io, off_inf + piece) != hipSuccess) {
+    (void)hipGetLastError();
+    ctx->err = "out of device memory for the batch multiplication staging";
+    return MSM377_ENOMEM;
+  }
+  const int forced = ctx->bm.window;
+  if (!forced) ctx->bm.window = batch_mul_multi_rule(n, k);
+  for (uint64_t off = 0; off < n && !rc; off += piece) {
+    const uint64_t m = std::min<uint64_t>(piece, n - off);
+    for (uint64_t i = 0; i < m; i++)
+      for (uint32_t j = 0; j < k; j++) memcpy(rows.data() + ((size_t)i * k + j) * 32, scalars + (off + i) * out_stride + (uint64_t)j * base_stride, 32);
+    rc = hip_ok(ctx, hipMemcpy(d_io, rows.data(), (size_t)m * k * 32, hipMemcpyHostToDevice), "hipMemcpy(scalars)") ? MSM377_OK : MSM377_EHIP;
+    if (!rc) rc = g1_batch_mul_multi_device(ctx, bases_xy, k, d_io, m, (uint64_t)k * 32, 32, out_form, d_io + off_out, d_io + off_inf);
     if (!rc) rc = hip_ok(ctx, hipMemcpy(out_points + off * stride, d_io + off_out, m * stride, hipMemcpyDeviceToHost), "hipMemcpy(records)") ? MSM377_OK : MSM377_EHIP;
     if (!rc && out_inf) rc = hip_ok(ctx, hipMemcpy(out_inf + off, d_io + off_inf, m, hipMemcpyDeviceToHost), "hipMemcpy(flags)") ? MSM377_OK : MSM377_EHIP;
   }

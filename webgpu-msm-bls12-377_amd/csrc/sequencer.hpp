@@ -41,6 +41,11 @@ int ed_check_points(msm377_ctx* ctx, const uint8_t* points, uint64_t n, uint32_t
 // Fixed-base batch multiplication (kernels/batch_mul.hpp): out[i] = [s_i]B, every output its own affine point.
 int g1_batch_mul_device(msm377_ctx* ctx, const uint8_t base_xy[96], const void* d_scalars, uint64_t n, uint32_t out_form, void* d_out_points, uint8_t* d_out_inf);
 int g1_batch_mul(msm377_ctx* ctx, const uint8_t base_xy[96], const uint8_t* scalars, uint64_t n, uint32_t out_form, uint8_t* out_points, uint8_t* out_inf);
+// Multi-base batch multiplication (kernels/batch_mul_multi.hpp): out[i] = sum_j [s_ij]B_j over k fixed bases.
+int g1_batch_mul_multi_device(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k, const void* d_scalars, uint64_t n, uint64_t out_stride, uint64_t base_stride, uint32_t out_form,
+                              void* d_out_points, uint8_t* d_out_inf);
+int g1_batch_mul_multi(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k, const uint8_t* scalars, uint64_t n, uint64_t out_stride, uint64_t base_stride, uint32_t out_form,
+                       uint8_t* out_points, uint8_t* out_inf);
 // Variable-base batch multiplication (kernels/batch_mul_var.hpp): out[i] = [s_i]P_i.
 int g1_batch_mul_var_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t scalar_stride, uint32_t out_form, void* d_out_points, uint8_t* d_out_inf);
 int g1_batch_mul_var(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint32_t scalar_stride, uint32_t out_form, uint8_t* out_points, uint8_t* out_inf);

@@ -219,6 +219,10 @@ def load_library():
         "msm377_g1_batch_mul_device": (i32, [vp, u8p, vp, u64, u32, vp, vp]),
         "msm377_g1_batch_mul": (i32, [vp, u8p, u8p, u64, u32, vp, vp]),
         "msm377_g1_batch_mul_host": (i32, [u8p, u8p, u64, u32, vp, vp]),
+        "msm377_g1_batch_mul_multi_device": (i32, [vp, u8p, u32, vp, u64, u64, u64, u32, vp, vp]),
+        "msm377_g1_batch_mul_multi": (i32, [vp, u8p, u32, u8p, u64, u64, u64, u32, vp, vp]),
+        "msm377_g1_batch_mul_multi_host": (i32, [u8p, u32, u8p, u64, u64, u64, u32, vp, vp]),
+        "msm377_ctx_get_mul_multi_table_builds": (u64, [vp]),
         "msm377_g1_batch_mul_var_device": (i32, [vp, vp, vp, u64, u32, u32, vp, vp]),
         "msm377_g1_batch_mul_var": (i32, [vp, u8p, u8p, u64, u32, u32, vp, vp]),
         "msm377_g1_batch_mul_var_host": (i32, [u8p, u32, u8p, u32, u64, u32, u32, vp, vp]),
@@ -351,6 +355,40 @@ def batch_mul_host(base: bytes, scalars: bytes, out_form="wire") -> Tuple[bytes,
     rc = load_library().msm377_g1_batch_mul_host(bytes(base), bytes(scalars), n, f, ctypes.addressof(out), ctypes.addressof(inf))
     if rc:
         raise MsmError(rc, "msm377_g1_batch_mul_host")
+    return out.raw[: stride * n], inf.raw[:n]
+
+
+MUL_MAX_BASES = 16  # MSM377_MUL_MAX_BASES
+
+
+def _multi_shape(bases: bytes, scalars: bytes, layout: str) -> Tuple[int, int, int, int]:
+    """(k, n, out_stride, base_stride) of a dense k x n scalar matrix: ``layout`` "rows" (the k scalars of an output side by
+    side) or "columns" (the n scalars of a base side by side)."""
+    if len(bases) % 96 or not 1 <= len(bases) // 96 <= MUL_MAX_BASES:
+        raise ValueError("bases: 1 to %d records of 96 bytes" % MUL_MAX_BASES)
+    k = len(bases) // 96
+    if len(scalars) % (32 * k):
+        raise ValueError("scalars buffer length must be a multiple of 32 k")
+    n = len(scalars) // (32 * k)
+    if layout == "rows":
+        return k, n, 32 * k, 32
+    if layout == "columns":
+        return k, n, 32, 32 * max(n, 1)
+    raise ValueError('layout is "rows" or "columns"')
+
+
+def batch_mul_multi_host(bases: bytes, scalars: bytes, out_form="wire", layout="rows") -> Tuple[bytes, bytes]:
+    """out[i] = sum_j [s_ij]B_j on the calling thread (msm377_g1_batch_mul_multi_host): no context, no device.  ``bases``:
+    k records of 96 wire bytes; ``scalars``: the k x n matrix of 32-byte little-endian integers in ``layout``.  Returns
+    (records, identity flags) as batch_mul_host does."""
+    k, n, out_stride, base_stride = _multi_shape(bases, scalars, layout)
+    f = _batch_mul_out_form(out_form)
+    stride = _POINT_STRIDE.get(f, 96)
+    out = ctypes.create_string_buffer(max(1, stride * n))
+    inf = ctypes.create_string_buffer(max(1, n))
+    rc = load_library().msm377_g1_batch_mul_multi_host(bytes(bases), k, bytes(scalars), n, out_stride, base_stride, f, ctypes.addressof(out), ctypes.addressof(inf))
+    if rc:
+        raise MsmError(rc, "msm377_g1_batch_mul_multi_host")
     return out.raw[: stride * n], inf.raw[:n]
 
 
@@ -718,6 +756,38 @@ class MsmEngine:
         rc = self._lib.msm377_g1_batch_mul(self._ctx, bytes(base), bytes(scalars), n, f, ctypes.addressof(out), ctypes.addressof(inf))
         self._check(rc, "msm377_g1_batch_mul")
         return out.raw[: stride * n], inf.raw[:n]
+
+    # -- multi-base batch multiplication (include/msm377.h): out[i] = sum_j [s_ij]B_j over k fixed bases --
+    def batch_mul_multi_device(self, bases: bytes, d_scalars: int, n: int, d_out: int, d_inf: int = 0, out_form="wire", out_stride=None, base_stride: int = 32):
+        """n rows of k scalars in HBM (in the engine's scalar form) over the k bases ``bases`` (96 wire bytes each, a host
+        buffer): n records at ``d_out`` and, if ``d_inf`` is given, n identity flag bytes there
+        (msm377_g1_batch_mul_multi_device).  s_ij is at ``d_scalars + i * out_stride + j * base_stride``; the default is
+        row-major (``out_stride`` = 32 k).  Any n; every curve point is a legal base, in every relation to the others."""
+        if len(bases) % 96:
+            raise ValueError("a base is 96 bytes")
+        k = len(bases) // 96
+        if out_stride is None:
+            out_stride = 32 * k
+        rc = self._lib.msm377_g1_batch_mul_multi_device(
+            self._ctx, bytes(bases), k, d_scalars or None, int(n), int(out_stride), int(base_stride), _batch_mul_out_form(out_form), d_out or None, d_inf or None
+        )
+        self._check(rc, "msm377_g1_batch_mul_multi_device")
+
+    def batch_mul_multi(self, bases: bytes, scalars: bytes, out_form="wire", layout="rows") -> Tuple[bytes, bytes]:
+        """The same on host buffers, ``scalars`` the dense k x n matrix in ``layout`` ("rows" or "columns"): returns
+        (records, identity flags) (msm377_g1_batch_mul_multi)."""
+        k, n, out_stride, base_stride = _multi_shape(bases, scalars, layout)
+        f = _batch_mul_out_form(out_form)
+        stride = _POINT_STRIDE.get(f, 96)
+        out = ctypes.create_string_buffer(max(1, stride * n))
+        inf = ctypes.create_string_buffer(max(1, n))
+        rc = self._lib.msm377_g1_batch_mul_multi(self._ctx, bytes(bases), k, bytes(scalars), n, out_stride, base_stride, f, ctypes.addressof(out), ctypes.addressof(inf))
+        self._check(rc, "msm377_g1_batch_mul_multi")
+        return out.raw[: stride * n], inf.raw[:n]
+
+    def mul_multi_table_builds(self) -> int:
+        """Table slots batch_mul_multi* built on this engine so far (msm377_ctx_get_mul_multi_table_builds)."""
+        return int(self._lib.msm377_ctx_get_mul_multi_table_builds(self._ctx))
 
     # -- variable-base batch multiplication (include/msm377.h): out[i] = [s_i]P_i --
     def batch_mul_var_device(self, d_points: int, d_scalars: int, n: int, d_out: int, d_inf: int = 0, out_form="wire", scalar_stride: int = 32):

@@ -137,4 +137,16 @@ const batch_lincomb2 = (p, q, a, b, { outForm = 'wire' } = {}) => {
   return addon.batchLincomb2Sync(pointsToBuffer(p), pointsToBuffer(q), scalarsToBuffer(a), scalarsToBuffer(b), BATCH_MUL_FORMS[outForm]);
 };
 
-module.exports = { batch_lincomb2, batch_mul, batch_mul_var, compute_msm, compute_msm_edwards, set_bases, compute_msm_fixed_base, check_points, CHECK_CANONICAL, CHECK_CURVE, CHECK_SUBGROUP, CHECK_ALL, pointsToBuffer, scalarsToBuffer, version: addon.version };
+// Multi-base batch multiplication (msm377_g1_batch_mul_multi): out[i] = sum_j [s_ij]B_j over k <= 16 fixed bases, every output
+// its own point (Pedersen commitments [m_i]G + [r_i]H).  `bases`: k {x, y} points, or a Buffer of 96-byte wire records;
+// `scalars`: the k x n matrix as one flat list or Buffer -- layout 'rows' (default: the k scalars of an output side by side)
+// or 'columns' (the n scalars of a base side by side).  Returns {points, infinity} as batch_mul does.  Any curve point is a
+// legal base, and any relation between the bases.
+const BATCH_MUL_LAYOUTS = { rows: 0, columns: 1 };
+const batch_mul_multi = (bases, scalars, { outForm = 'wire', layout = 'rows' } = {}) => {
+  if (!(outForm in BATCH_MUL_FORMS)) throw new RangeError("outForm: wire | mont_flag (plain mont cannot say 'identity')");
+  if (!(layout in BATCH_MUL_LAYOUTS)) throw new RangeError('layout: rows | columns');
+  return addon.batchMulMultiSync(pointsToBuffer(bases), scalarsToBuffer(scalars), BATCH_MUL_FORMS[outForm], BATCH_MUL_LAYOUTS[layout]);
+};
+
+module.exports = { batch_lincomb2, batch_mul, batch_mul_multi, batch_mul_var, compute_msm, compute_msm_edwards, set_bases, compute_msm_fixed_base, check_points, CHECK_CANONICAL, CHECK_CURVE, CHECK_SUBGROUP, CHECK_ALL, pointsToBuffer, scalarsToBuffer, version: addon.version };

@@ -221,3 +221,21 @@ export const batch_lincomb2 = (
   }
   return addon.batchLincomb2Sync(pointsToBuffer(p), pointsToBuffer(q), scalarsToBuffer(a), scalarsToBuffer(b), BATCH_MUL_FORMS[outForm]);
 };
+
+// Multi-base batch multiplication (msm377_g1_batch_mul_multi): out[i] = sum_j [s_ij]B_j over k <= 16 fixed bases, every output
+// its own point.  `scalars`: the k x n matrix as one flat list or Buffer, layout 'rows' (default: the k scalars of an output
+// side by side) or 'columns' (the n scalars of a base side by side).  Returns what batch_mul returns.
+const BATCH_MUL_LAYOUTS = { rows: 0, columns: 1 } as const;
+export const batch_mul_multi = (
+  bases: BigIntPoint[] | U32ArrayPoint[] | Buffer,
+  scalars: bigint[] | Uint32Array[] | Buffer,
+  { outForm = 'wire', layout = 'rows' }: { outForm?: keyof typeof BATCH_MUL_FORMS; layout?: keyof typeof BATCH_MUL_LAYOUTS } = {},
+): { points: Buffer; infinity: Buffer } => {
+  if (!(outForm in BATCH_MUL_FORMS)) {
+    throw new RangeError("outForm: wire | mont_flag (plain mont cannot say 'identity')");
+  }
+  if (!(layout in BATCH_MUL_LAYOUTS)) {
+    throw new RangeError('layout: rows | columns');
+  }
+  return addon.batchMulMultiSync(pointsToBuffer(bases), scalarsToBuffer(scalars), BATCH_MUL_FORMS[outForm], BATCH_MUL_LAYOUTS[layout]);
+};

@@ -23,6 +23,9 @@
 //                                                                      scalars for n > 1 points: one scalar for all
 //   batchLincomb2Sync(p: Buffer 96n, q: Buffer 96n, a: Buffer 32n | 32, b: Buffer 32n | 32, outForm: number): {points, infinity}
 //                                                                      out[i] = [a_i]P_i + [b_i]Q_i (msm377_g1_batch_lincomb2)
+//   batchMulMultiSync(bases: Buffer 96k, scalars: Buffer 32kn, outForm: number, columns: number): {points, infinity}
+//                                                                      out[i] = sum_j [s_ij]B_j (msm377_g1_batch_mul_multi); the
+//                                                                      k x n scalars row-major, or column-major if columns != 0
 //   version(): string
 // Errors reject / throw a JS Error carrying msm377_strerror + msm377_last_error, matching the
 // reference's behaviour of throwing Error (cuzk/gpu.ts:7-10).
@@ -477,6 +480,53 @@ napi_value BatchLincomb2Sync(napi_env env, napi_callback_info info) {
   return obj;
 }
 
+// batchMulMultiSync(bases, scalars, outForm, columns) -> {points, infinity}: out[i] = sum_j [s_ij]B_j over k = bases / 96 fixed
+// bases; scalars: the dense k x n matrix, row-major (columns = 0) or column-major
+napi_value BatchMulMultiSync(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  bool bb = false, sb = false;
+  uint32_t form = MSM377_POINTS_WIRE, columns = 0;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 4 || napi_is_buffer(env, argv[0], &bb) != napi_ok || !bb ||
+      napi_is_buffer(env, argv[1], &sb) != napi_ok || !sb || napi_get_value_uint32(env, argv[2], &form) != napi_ok || napi_get_value_uint32(env, argv[3], &columns) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "expected (bases: Buffer of 96 bytes per base, scalars: Buffer of 32 bytes per scalar, outForm: number, columns: number)");
+    return nullptr;
+  }
+  uint8_t *b, *s;
+  size_t bl, sl;
+  napi_get_buffer_info(env, argv[0], reinterpret_cast<void**>(&b), &bl);
+  napi_get_buffer_info(env, argv[1], reinterpret_cast<void**>(&s), &sl);
+  const uint32_t k = static_cast<uint32_t>(bl / 96);
+  if (bl % 96 != 0 || k < 1 || k > MSM377_MUL_MAX_BASES || sl % (32 * static_cast<size_t>(k)) != 0 || (form != MSM377_POINTS_WIRE && form != MSM377_POINTS_MONT_FLAG)) {
+    napi_throw_range_error(env, nullptr, "bases must hold 1 to 16 points of 96 bytes, scalars 32 bytes per base and output; outForm is 0 (wire) or 2 (mont_flag)");
+    return nullptr;
+  }
+  const uint64_t n = sl / (32 * static_cast<size_t>(k));
+  const uint64_t out_stride = columns ? 32 : 32 * static_cast<uint64_t>(k), base_stride = columns ? 32 * (n ? n : 1) : 32;
+  const size_t stride = form == MSM377_POINTS_MONT_FLAG ? 104 : 96;
+  napi_value points, infinity, obj;
+  void *pd = nullptr, *id = nullptr;
+  if (napi_create_buffer(env, n * stride, &pd, &points) != napi_ok || napi_create_buffer(env, n, &id, &infinity) != napi_ok) return nullptr;
+  std::string err;
+  int rc;
+  {
+    std::lock_guard<std::mutex> lock(g_mu);
+    rc = ensure_ctx(1, &err);  // any capacity: the call walks n in passes of its own
+    if (!rc) {
+      rc = msm377_g1_batch_mul_multi(g_ctx, b, k, s, n, out_stride, base_stride, form, static_cast<uint8_t*>(pd), static_cast<uint8_t*>(id));
+      if (rc) err = std::string("msm377_g1_batch_mul_multi: ") + msm377_strerror(rc) + ": " + msm377_last_error(g_ctx);
+    }
+  }
+  if (rc) {
+    napi_throw_error(env, nullptr, err.c_str());
+    return nullptr;
+  }
+  napi_create_object(env, &obj);
+  napi_set_named_property(env, obj, "points", points);
+  napi_set_named_property(env, obj, "infinity", infinity);
+  return obj;
+}
+
 struct Job {
   napi_async_work work = nullptr;
   napi_deferred deferred = nullptr;
@@ -552,6 +602,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"batchMulSync", nullptr, BatchMulSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"batchMulVarSync", nullptr, BatchMulVarSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"batchLincomb2Sync", nullptr, BatchLincomb2Sync, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"batchMulMultiSync", nullptr, BatchMulMultiSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"version", nullptr, Version, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
