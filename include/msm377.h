@@ -636,6 +636,60 @@ int msm377_g1_batch_lincomb2(msm377_ctx* ctx, const uint8_t* p, const uint8_t* q
 int msm377_g1_batch_lincomb2_host(const uint8_t* p, const uint8_t* q, uint32_t point_form, const uint8_t* a, const uint8_t* b, uint32_t scalar_form, uint64_t n, uint32_t a_stride,
                                   uint32_t b_stride, uint32_t out_form, uint8_t* out_points, uint8_t* out_inf);
 
+/* ---- row commitments ---------------------------------------------------------------------- */
+
+/* out[i] = sum_{j<k} [s_ij]G_j: n row commitments over a RESIDENT set of up to MSM377_GEN_MAX generators, each returned as
+ * its own affine point (Pedersen vector commitments: the rows of a Hyrax / Spartan-style polynomial commitment, the
+ * per-row commitments of a witness matrix, n ElGamal-style vectors over 32 or 64 generators).  It fills the gap between
+ * msm377_g1_batch_mul_multi* (k <= 16) and one MSM pipeline pass per row.  Wherever the two overlap the contract is that
+ * of msm377_g1_batch_mul_multi* above, word for word -- the meaning of a scalar (every 32-byte value, a wire scalar NOT
+ * reduced mod r, no MSM377_ESCALAR), the context's scalar form (the host twin takes it as an argument), s_ij at
+ * scalars + i * out_stride + j * base_stride with both strides non-zero multiples of 32 (rows may overlap), every curve
+ * point a legal generator and every relation between generators followed through, the two output forms and out_inf, the
+ * alignment of device pointers, any n, synchronous calls, MSM377_EINVAL with the outputs untouched -- and this section
+ * states only what differs (csrc/kernels/commit_rows.hpp, csrc/commit_rows_plan.hpp).
+ *
+ * The set.  msm377_g1_set_generators builds and keeps the window tables of k generators (96 wire bytes each, HOST
+ * memory; a coordinate of p or more is MSM377_EINVAL).  window_bits: 8, 16 (k <= MSM377_GEN_WIDE_MAX only) or 0 = 8; the
+ * width belongs to the set and msm377_ctx_set_mul_window does not apply.  The call follows the rule of the resident base
+ * table: it drops the old set FIRST, whatever its arguments, and installs the new one as its last step; a call that
+ * fails for any reason leaves no set.  gens_xy == NULL or k == 0 drops the set and frees its memory (MSM377_OK).  The
+ * set is ONE allocation of k tables: 0.5 MB per generator at width 8 (2 GB at 4 096), 64 MB per generator at width 16;
+ * msm377_ctx_destroy frees it.  It is independent of the resident MSM bases, the single-base table, the 16 multi-base
+ * slots and both build counters, the variable-base table memory and a check call's state, in both directions.
+ * msm377_ctx_get_generators reports (k, width) of the set, (0, 0) without one.
+ *
+ * The calls.  msm377_g1_commit_rows* run over the FIRST k generators of the set, 1 <= k <= the resident k.  Without a set,
+ * or with k above the resident k (and within MSM377_GEN_MAX), they return MSM377_ESTATE; argument errors are reported
+ * first, and n == 0 is MSM377_OK with or without a set.  With a resident k of 1 the outputs are byte for byte those of
+ * msm377_g1_batch_mul_device at the set's width.  A row's walk is split across ceil(k / 16) threads whose partial sums
+ * are folded by general additions (msm377_commit_rows_plan: segments, generators per segment, rows per pass of the 2^20
+ * partial sums the scratch of the batch calls holds).  msm377_g1_commit_rows accepts the same layouts in host memory,
+ * repacks them row-major and stages them in pieces of at most 2^20 scalars.
+ *
+ * Against one MSM per row (msm377_g1_set_bases once, then msm377_g1_msm_fixed_base_batch_device with n = k and batch =
+ * rows), measured on one MI355X at width 8 (profiles/commit_rows/sweep.txt): the call takes 9.9 / 5.8 / 6.1 / 6.5 / 8.8 ms
+ * for 2^16 x 32 / 2^14 x 64 / 2^12 x 256 / 2^10 x 1 024 / 2^8 x 4 096 full-width scalars where one MSM per row takes
+ * 0.16 to 0.29 ms per ROW (10.5 s .. 72 ms).  The crossover: at k = 4 096 a call costs 8 to 10 ms however few the rows
+ * (one thread walks 16 tables, one thread folds 256 partial sums), so below about 32 rows one MSM per row is the faster
+ * way (16 rows: 4.9 against 9.8 ms; 64 rows: 18.5 against 8.2 ms). */
+#define MSM377_GEN_MAX      4096   /* generators of a resident set */
+#define MSM377_GEN_WIDE_MAX   64   /* ... of a set with 16-bit tables (64 MB each) */
+int msm377_g1_set_generators(msm377_ctx* ctx, const uint8_t* gens_xy /* k x 96, HOST */, uint32_t k, int window_bits);
+int msm377_ctx_get_generators(const msm377_ctx* ctx, uint32_t* k, int* window_bits);
+int msm377_g1_commit_rows_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n, uint32_t k, uint64_t out_stride, uint64_t base_stride, uint32_t out_form, void* d_out_points,
+                                 uint8_t* d_out_inf);
+int msm377_g1_commit_rows(msm377_ctx* ctx, const uint8_t* scalars, uint64_t n, uint32_t k, uint64_t out_stride, uint64_t base_stride, uint32_t out_form, uint8_t* out_points,
+                          uint8_t* out_inf);
+/* The same on ONE CPU thread: no device, no context, the generators an argument (csrc/commit_rows_host.hpp): the terms of
+ * each generator by the single-base twin, then general additions; the yardstick of the device call.  The forms are
+ * arguments as in msm377_g1_batch_mul_var_host. */
+int msm377_g1_commit_rows_host(const uint8_t* gens_xy, uint32_t k, const uint8_t* scalars, uint32_t scalar_form, uint64_t n, uint64_t out_stride, uint64_t base_stride,
+                               uint32_t out_form, uint8_t* out_points, uint8_t* out_inf);
+/* Pure, host-only: how a call over k generators is cut.  0 segments (and zeros) for k outside 1 .. MSM377_GEN_MAX.  Any of
+ * the three pointers may be null. */
+void msm377_commit_rows_plan(uint32_t k, uint32_t* segments, uint32_t* bases_per_segment, uint64_t* rows_per_pass);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 
 #define MSM377_STAGE_CONVERT 0     /* points -> Montgomery records */

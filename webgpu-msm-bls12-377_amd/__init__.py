@@ -34,6 +34,8 @@ from .host.engine import (  # noqa: F401
     batch_mul_multi_host,
     batch_mul_var_host,
     check_points_host,
+    commit_rows_host,
+    commit_rows_plan,
     ed_check_points_host,
     import_points_host,
     import_scalars_host,
@@ -57,6 +59,8 @@ __all__ = [
     "batch_mul_multi_host",
     "batch_mul_var_host",
     "check_points_host",
+    "commit_rows_host",
+    "commit_rows_plan",
     "ed_check_points_host",
     "CHECK_CANONICAL",
     "CHECK_CURVE",

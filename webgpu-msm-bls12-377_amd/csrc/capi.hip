@@ -12,6 +12,8 @@
 #include "sequencer.hpp"
 #include "batch_mul_host.hpp"
 #include "batch_mul_multi_host.hpp"
+#include "commit_rows_host.hpp"
+#include "commit_rows_plan.hpp"
 #include "batch_lincomb2_host.hpp"
 #include "batch_mul_var_host.hpp"
 #include "import_host.hpp"
@@ -270,6 +272,25 @@ int msm377_g1_batch_mul_multi_host(const uint8_t* bases_xy, uint32_t k, const ui
   return batch_mul_multi_host(bases_xy, k, scalars, n, out_stride, base_stride, MSM377_SCALARS_WIRE, out_form, out_points, out_inf);
 }
 
+int msm377_g1_commit_rows_host(const uint8_t* gens_xy, uint32_t k, const uint8_t* scalars, uint32_t scalar_form, uint64_t n, uint64_t out_stride, uint64_t base_stride,
+                               uint32_t out_form, uint8_t* out_points, uint8_t* out_inf) {
+  return commit_rows_host(gens_xy, k, scalars, scalar_form, n, out_stride, base_stride, out_form, out_points, out_inf);
+}
+
+void msm377_commit_rows_plan(uint32_t k, uint32_t* segments, uint32_t* bases_per_segment, uint64_t* rows_per_pass) {
+  const CommitRowsPlan p = commit_rows_plan(k);
+  if (segments) *segments = p.segments;
+  if (bases_per_segment) *bases_per_segment = p.bases_per_segment;
+  if (rows_per_pass) *rows_per_pass = p.rows_per_pass;
+}
+
+int msm377_ctx_get_generators(const msm377_ctx* ctx, uint32_t* k, int* window_bits) {
+  if (!ctx) return MSM377_EINVAL;
+  if (k) *k = ctx->gens.k;
+  if (window_bits) *window_bits = ctx->gens.width;
+  return MSM377_OK;
+}
+
 int msm377_g1_batch_mul_var_host(const uint8_t* points, uint32_t point_form, const uint8_t* scalars, uint32_t scalar_form, uint64_t n, uint32_t scalar_stride, uint32_t out_form,
                                  uint8_t* out_points, uint8_t* out_inf) {
   return batch_mul_var_host(points, point_form, scalars, scalar_form, n, scalar_stride, out_form, out_points, out_inf);
@@ -396,6 +417,15 @@ int msm377_g1_batch_mul_multi_device(msm377_ctx* ctx, const uint8_t* bases_xy, u
 int msm377_g1_batch_mul_multi(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k, const uint8_t* scalars, uint64_t n, uint64_t out_stride, uint64_t base_stride, uint32_t out_form,
                               uint8_t* out_points, uint8_t* out_inf) {
   return eng::g1_batch_mul_multi(ctx, bases_xy, k, scalars, n, out_stride, base_stride, out_form, out_points, out_inf);
+}
+int msm377_g1_set_generators(msm377_ctx* ctx, const uint8_t* gens_xy, uint32_t k, int window_bits) { return eng::g1_set_generators(ctx, gens_xy, k, window_bits); }
+int msm377_g1_commit_rows_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n, uint32_t k, uint64_t out_stride, uint64_t base_stride, uint32_t out_form, void* d_out_points,
+                                 uint8_t* d_out_inf) {
+  return eng::g1_commit_rows_device(ctx, d_scalars, n, k, out_stride, base_stride, out_form, d_out_points, d_out_inf);
+}
+int msm377_g1_commit_rows(msm377_ctx* ctx, const uint8_t* scalars, uint64_t n, uint32_t k, uint64_t out_stride, uint64_t base_stride, uint32_t out_form, uint8_t* out_points,
+                          uint8_t* out_inf) {
+  return eng::g1_commit_rows(ctx, scalars, n, k, out_stride, base_stride, out_form, out_points, out_inf);
 }
 int msm377_g1_batch_mul_var_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t scalar_stride, uint32_t out_form, void* d_out_points, uint8_t* d_out_inf) {
   return eng::g1_batch_mul_var_device(ctx, d_points, d_scalars, n, scalar_stride, out_form, d_out_points, d_out_inf);

@@ -106,6 +106,19 @@ struct BatchMulMultiState {
   uint32_t* bases_wire = nullptr;   // their 96 bytes each on the device
 };
 
+// The resident generator set of the row commitments (msm377_g1_set_generators / msm377_g1_commit_rows*,
+// kernels/commit_rows.hpp): the window tables of k generators at ONE width as ONE allocation, table j at record
+// j * bm_table_records(width).  The rule is ResidentBases': msm377_g1_set_generators drops the set (and gives its
+// memory back) before anything else and sets k as its last step, behind a wait for the build.  The build's own buffers
+// live for the length of the build.  The calls borrow BatchMulState's stash, trees and block products and nothing else:
+// no table, key, width or build count of the batch_mul calls is read or written from here.
+struct GeneratorSet {
+  uint32_t k = 0;             // resident generators (0: no set)
+  int width = 0;              // window width of the tables: 8 or 16
+  uint32_t* tables = nullptr;
+  bool valid() const { return k != 0; }
+};
+
 // Work buffers of the 20-bit-window sort (kernels/wide.hpp) for up to `cap` points.
 struct WideBuffers {
   uint32_t* digits = nullptr;  // 13 x n u32 biased 20-bit digits, the flat list the sort reads
@@ -233,6 +246,7 @@ struct msm377_ctx {
   ResidentBases resident;             // fixed-base mode: the bases of the last successful msm377_g1_set_bases* call
   BatchMulState bm;                   // fixed-base batch multiplication: its table and scratch (allocated on first use)
   BatchMulMultiState bmm;             // multi-base batch multiplication: a table per base position (allocated when built)
+  GeneratorSet gens;                  // row commitments: the resident generator tables (one allocation per set)
   WideBuffers wide;                   // the 20-bit-window sort's buffers (allocated with such a table; the twin's own set)
   AffineConvert aff;
   ZeroCopyOut zc;

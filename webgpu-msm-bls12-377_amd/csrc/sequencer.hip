@@ -51,6 +51,7 @@
 #include "kernels/accumulate.hpp"
 #include "kernels/batch_mul.hpp"
 #include "kernels/batch_mul_multi.hpp"
+#include "kernels/commit_rows.hpp"
 #include "kernels/convert.hpp"
 #include "kernels/decompose.hpp"
 #include "kernels/generate.hpp"
@@ -2214,6 +2215,188 @@ int g1_batch_mul_multi(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k, con
     if (!rc && out_inf) rc = hip_ok(ctx, hipMemcpy(out_inf + off, d_io + off_inf, m, hipMemcpyDeviceToHost), "hipMemcpy(flags)") ? MSM377_OK : MSM377_EHIP;
   }
   ctx->bm.window = forced;
+  (void)hipFree(d_io);
+  return rc;
+}
+
+// ---- row commitments (include/msm377.h "row commitments"; kernels/commit_rows.hpp, commit_rows_plan.hpp) ----
+// The set is built with the build kernels of the multi-base call over buffers sized for k; a call runs on ctx->stream over
+// the scratch of the single-base call, and its one host wait is the synchronisation at its end.
+namespace {
+
+void cr_drop_set(msm377_ctx* ctx) {
+  GeneratorSet& gs = ctx->gens;
+  gs.k = 0;
+  gs.width = 0;
+  ctx->own.release(gs.tables);
+  gs.tables = nullptr;
+}
+
+// k, the strides, the pointers of a device call.  Nothing is allocated, launched or changed before these pass.
+int cr_check_shape(msm377_ctx* ctx, uint32_t k, uint64_t out_stride, uint64_t base_stride) {
+  if (k < 1 || k > MSM377_GEN_MAX) {
+    ctx->err = "k is 1 to MSM377_GEN_MAX generators";
+    return MSM377_EINVAL;
+  }
+  if (!out_stride || !base_stride || (out_stride & 31) || (base_stride & 31)) {
+    ctx->err = "out_stride and base_stride are byte counts: non-zero multiples of 32";
+    return MSM377_EINVAL;
+  }
+  return MSM377_OK;
+}
+
+int cr_check_set(msm377_ctx* ctx, uint32_t k) {
+  if (!ctx->gens.valid()) {
+    ctx->err = "no resident generator set: call msm377_g1_set_generators first";
+    return MSM377_ESTATE;
+  }
+  if (k > ctx->gens.k) {
+    ctx->err = "k is above the resident generator count";
+    return MSM377_ESTATE;
+  }
+  return MSM377_OK;
+}
+
+// The tables of k generators into gs.tables: ONE row-base launch for the whole set, then the concatenated records in
+// passes of at most BM_CHUNK, each normalised straight into its place (the set is one allocation: no staging, no copies).
+int cr_build_tables(msm377_ctx* ctx, const uint8_t* gens_xy, uint32_t k, int c, uint32_t* tables) {
+  const uint64_t records = bm_table_records((uint32_t)c), rows = (uint64_t)bm_windows(c) + 1, total = records * k;
+  static_assert((uint64_t)MSM377_GEN_MAX * (bm_windows(8) + 1) <= BM_CHUNK && (uint64_t)MSM377_GEN_WIDE_MAX * (bm_windows(16) + 1) <= BM_CHUNK, "the row bases of a set are normalised in one chunk");
+  uint32_t *row_bases = nullptr, *gens_wire = nullptr;
+  int rc = bm_alloc(ctx, &row_bases, (size_t)k * rows * BM_REC_WORDS * 4);
+  if (!rc) rc = bm_alloc(ctx, &gens_wire, (size_t)k * 96);
+  hipError_t e = hipSuccess;
+  if (!rc) {
+    uint4* stash = reinterpret_cast<uint4*>(ctx->bm.stash);
+    e = hipMemcpyAsync(gens_wire, gens_xy, (size_t)k * 96, hipMemcpyHostToDevice, ctx->stream);  // (pageable memory: staged before the call returns)
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(k_bmm_row_bases, dim3(k), dim3(64), 0, ctx->stream, (const uint32_t*)gens_wire, (uint32_t)c, stash);
+      rc = bm_normalise(ctx, rows * k, BM_FORM_TABLE, row_bases, nullptr);
+    }
+    for (uint64_t first = 0; first < total && !rc && e == hipSuccess; first += BM_CHUNK) {
+      const uint64_t count = std::min<uint64_t>(BM_CHUNK, total - first);
+      hipLaunchKernelGGL(k_bmm_entries, dim3((unsigned)((count + BM_THREADS - 1) / BM_THREADS)), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)row_bases, (uint32_t)c, first, count,
+                         stash);
+      rc = bm_normalise(ctx, count, BM_FORM_TABLE, tables + first * BM_REC_WORDS, nullptr);
+    }
+  }
+  const hipError_t waited = hipStreamSynchronize(ctx->stream);  // the set is valid only once it is there; and the build's buffers go back
+  ctx->own.release(row_bases);
+  ctx->own.release(gens_wire);
+  if (rc) return rc;
+  HIP_TRY(ctx, e);
+  HIP_TRY(ctx, waited);
+  return MSM377_OK;
+}
+
+}  // namespace
+
+int g1_set_generators(msm377_ctx* ctx, const uint8_t* gens_xy, uint32_t k, int window_bits) {
+  if (!ctx) return MSM377_EINVAL;
+  ctx->err.clear();
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  cr_drop_set(ctx);  // first, whatever follows: a call that fails leaves no set
+  if (!gens_xy || k == 0) return MSM377_OK;
+  const int c = window_bits ? window_bits : BM_NARROW_WIDTH;
+  if (!batch_mul_width_supported(c)) {
+    ctx->err = "window_bits is 8, 16 or 0 (= 8)";
+    return MSM377_EINVAL;
+  }
+  if (k > MSM377_GEN_MAX || (c == BM_WIDE_WIDTH && k > MSM377_GEN_WIDE_MAX)) {
+    ctx->err = "a set holds at most MSM377_GEN_MAX generators, MSM377_GEN_WIDE_MAX with 16-bit tables";
+    return MSM377_EINVAL;
+  }
+  for (uint32_t j = 0; j < k; j++)
+    if (!bm_base_canonical(gens_xy + (size_t)j * 96)) {
+      ctx->err = "a generator has a coordinate that is not below p";
+      return MSM377_EINVAL;
+    }
+  GeneratorSet& gs = ctx->gens;
+  int rc = bm_ensure_scratch(ctx);
+  if (!rc) rc = bm_alloc(ctx, &gs.tables, (size_t)k * bm_table_records((uint32_t)c) * BM_REC_WORDS * 4);
+  if (!rc) rc = cr_build_tables(ctx, gens_xy, k, c, gs.tables);
+  if (rc) {
+    cr_drop_set(ctx);
+    return rc;
+  }
+  gs.width = c;
+  gs.k = k;
+  return MSM377_OK;
+}
+
+int g1_commit_rows_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n, uint32_t k, uint64_t out_stride, uint64_t base_stride, uint32_t out_form, void* d_out_points,
+                          uint8_t* d_out_inf) {
+  int rc = bm_check_form(ctx, out_form);
+  if (!rc) rc = cr_check_shape(ctx, k, out_stride, base_stride);
+  if (rc) return rc;
+  if (n == 0) return MSM377_OK;
+  if (!d_scalars || !d_out_points) {
+    ctx->err = "null pointer";
+    return MSM377_EINVAL;
+  }
+  const uintptr_t out_align = out_form == MSM377_POINTS_WIRE ? 15 : 7;
+  if (((uintptr_t)d_scalars & 15) || ((uintptr_t)d_out_points & out_align)) {
+    ctx->err = "device pointers must be 16-byte aligned (8-byte for mont_flag records)";
+    return MSM377_EINVAL;
+  }
+  rc = cr_check_set(ctx, k);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  rc = bm_ensure_scratch(ctx);
+  if (rc) return rc;
+  const GeneratorSet& gs = ctx->gens;
+  const CommitRowsPlan plan = commit_rows_plan(k);
+  const size_t stride = out_form == MSM377_POINTS_WIRE ? 96 : 104;
+  uint4* stash = reinterpret_cast<uint4*>(ctx->bm.stash);
+  for (uint64_t off = 0; off < n && !rc; off += plan.rows_per_pass) {
+    const uint64_t m = std::min<uint64_t>(plan.rows_per_pass, n - off);
+    const unsigned blocks = (unsigned)((m + BM_THREADS - 1) / BM_THREADS);
+    const uint64_t part_stride = (uint64_t)blocks * BM_THREADS;  // <= rows_per_pass, so segments * part_stride <= BM_CHUNK
+    // Row `off` of the CALL's layout: the strides are the call's, whatever the pass's length.
+    hipLaunchKernelGGL(k_cr_accumulate, dim3(blocks, plan.segments), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)gs.tables, (const uint8_t*)d_scalars + off * out_stride, m, k,
+                       plan.bases_per_segment, out_stride, base_stride, (uint32_t)gs.width, ctx->scalar_form == MSM377_SCALARS_MONT ? 1u : 0u, part_stride, stash);
+    if (plan.segments > 1) hipLaunchKernelGGL(k_cr_fold, dim3(blocks), dim3(BM_THREADS), 0, ctx->stream, stash, m, plan.segments, part_stride);
+    rc = bm_normalise(ctx, m, out_form, (uint8_t*)d_out_points + off * stride, d_out_inf ? d_out_inf + off : nullptr);
+  }
+  const hipError_t e = hipStreamSynchronize(ctx->stream);
+  if (rc) return rc;
+  HIP_TRY(ctx, e);
+  return MSM377_OK;
+}
+
+// Host buffers: each piece of at most 2^20 scalars (2^20 / k rows) repacked row-major on the host, up, records (and
+// flags) down: the staging of the multi-base call.
+int g1_commit_rows(msm377_ctx* ctx, const uint8_t* scalars, uint64_t n, uint32_t k, uint64_t out_stride, uint64_t base_stride, uint32_t out_form, uint8_t* out_points, uint8_t* out_inf) {
+  int rc = bm_check_form(ctx, out_form);
+  if (!rc) rc = cr_check_shape(ctx, k, out_stride, base_stride);
+  if (rc) return rc;
+  if (n == 0) return MSM377_OK;
+  if (!scalars || !out_points) {
+    ctx->err = "null pointer";
+    return MSM377_EINVAL;
+  }
+  rc = cr_check_set(ctx, k);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t stride = out_form == MSM377_POINTS_WIRE ? 96 : 104;
+  const uint64_t piece = std::min<uint64_t>(n, BM_CHUNK / k);
+  std::vector<uint8_t> rows((size_t)piece * k * 32);
+  uint8_t* d_io = nullptr;  // scalars, records, flags: 16-byte aligned parts
+  const size_t off_out = (size_t)piece * k * 32, off_inf = off_out + (((size_t)piece * stride + 15) & ~(size_t)15);
+  if (hipMalloc((void**)&d_io, off_inf + piece) != hipSuccess) {
+    (void)hipGetLastError();
+    ctx->err = "out of device memory for the row commitment staging";
+    return MSM377_ENOMEM;
+  }
+  for (uint64_t off = 0; off < n && !rc; off += piece) {
+    const uint64_t m = std::min<uint64_t>(piece, n - off);
+    for (uint64_t i = 0; i < m; i++)
+      for (uint32_t j = 0; j < k; j++) memcpy(rows.data() + ((size_t)i * k + j) * 32, scalars + (off + i) * out_stride + (uint64_t)j * base_stride, 32);
+    rc = hip_ok(ctx, hipMemcpy(d_io, rows.data(), (size_t)m * k * 32, hipMemcpyHostToDevice), "hipMemcpy(scalars)") ? MSM377_OK : MSM377_EHIP;
+    if (!rc) rc = g1_commit_rows_device(ctx, d_io, m, k, (uint64_t)k * 32, 32, out_form, d_io + off_out, d_io + off_inf);
+    if (!rc) rc = hip_ok(ctx, hipMemcpy(out_points + off * stride, d_io + off_out, m * stride, hipMemcpyDeviceToHost), "hipMemcpy(records)") ? MSM377_OK : MSM377_EHIP;
+    if (!rc && out_inf) rc = hip_ok(ctx, hipMemcpy(out_inf + off, d_io + off_inf, m, hipMemcpyDeviceToHost), "hipMemcpy(flags)") ? MSM377_OK : MSM377_EHIP;
+  }
   (void)hipFree(d_io);
   return rc;
 }

@@ -223,6 +223,12 @@ def load_library():
         "msm377_g1_batch_mul_multi": (i32, [vp, u8p, u32, u8p, u64, u64, u64, u32, vp, vp]),
         "msm377_g1_batch_mul_multi_host": (i32, [u8p, u32, u8p, u64, u64, u64, u32, vp, vp]),
         "msm377_ctx_get_mul_multi_table_builds": (u64, [vp]),
+        "msm377_g1_set_generators": (i32, [vp, u8p, u32, i32]),
+        "msm377_ctx_get_generators": (i32, [vp, vp, vp]),
+        "msm377_g1_commit_rows_device": (i32, [vp, vp, u64, u32, u64, u64, u32, vp, vp]),
+        "msm377_g1_commit_rows": (i32, [vp, u8p, u64, u32, u64, u64, u32, vp, vp]),
+        "msm377_g1_commit_rows_host": (i32, [u8p, u32, u8p, u32, u64, u64, u64, u32, vp, vp]),
+        "msm377_commit_rows_plan": (None, [u32, vp, vp, vp]),
         "msm377_g1_batch_mul_var_device": (i32, [vp, vp, vp, u64, u32, u32, vp, vp]),
         "msm377_g1_batch_mul_var": (i32, [vp, u8p, u8p, u64, u32, u32, vp, vp]),
         "msm377_g1_batch_mul_var_host": (i32, [u8p, u32, u8p, u32, u64, u32, u32, vp, vp]),
@@ -390,6 +396,52 @@ def batch_mul_multi_host(bases: bytes, scalars: bytes, out_form="wire", layout="
     if rc:
         raise MsmError(rc, "msm377_g1_batch_mul_multi_host")
     return out.raw[: stride * n], inf.raw[:n]
+
+
+GEN_MAX = 4096  # MSM377_GEN_MAX
+GEN_WIDE_MAX = 64  # MSM377_GEN_WIDE_MAX
+
+
+def _rows_shape(k: int, scalars: bytes, layout: str) -> Tuple[int, int, int]:
+    """(n, out_stride, base_stride) of a dense k x n scalar matrix in ``layout`` ("rows" or "columns")."""
+    if not 1 <= k <= GEN_MAX:
+        raise ValueError("k: 1 to %d generators" % GEN_MAX)
+    if len(scalars) % (32 * k):
+        raise ValueError("scalars buffer length must be a multiple of 32 k")
+    n = len(scalars) // (32 * k)
+    if layout == "rows":
+        return n, 32 * k, 32
+    if layout == "columns":
+        return n, 32, 32 * max(n, 1)
+    raise ValueError('layout is "rows" or "columns"')
+
+
+def commit_rows_host(gens: bytes, scalars: bytes, out_form="wire", layout="rows", scalar_form="wire") -> Tuple[bytes, bytes]:
+    """out[i] = sum_j [s_ij]G_j on the calling thread (msm377_g1_commit_rows_host): no context, no device.  ``gens``: k
+    records of 96 wire bytes, k up to 4 096; ``scalars``: the k x n matrix of 32-byte values in ``layout`` and
+    ``scalar_form`` ("wire" or "mont").  Returns (records, identity flags) as batch_mul_host does."""
+    if len(gens) % 96:
+        raise ValueError("a generator is 96 bytes")
+    k = len(gens) // 96
+    n, out_stride, base_stride = _rows_shape(k, scalars, layout)
+    f = _batch_mul_out_form(out_form)
+    stride = _POINT_STRIDE.get(f, 96)
+    out = ctypes.create_string_buffer(max(1, stride * n))
+    inf = ctypes.create_string_buffer(max(1, n))
+    rc = load_library().msm377_g1_commit_rows_host(
+        bytes(gens), k, bytes(scalars), _form(_SCALAR_FORMS, scalar_form, "scalar"), n, out_stride, base_stride, f, ctypes.addressof(out), ctypes.addressof(inf)
+    )
+    if rc:
+        raise MsmError(rc, "msm377_g1_commit_rows_host")
+    return out.raw[: stride * n], inf.raw[:n]
+
+
+def commit_rows_plan(k: int) -> Tuple[int, int, int]:
+    """(segments, generators per segment, rows per pass) of a row-commitment call over k generators
+    (msm377_commit_rows_plan); (0, 0, 0) for k outside 1 .. 4 096."""
+    seg, bps, rows = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint64()
+    load_library().msm377_commit_rows_plan(int(k), ctypes.addressof(seg), ctypes.addressof(bps), ctypes.addressof(rows))
+    return seg.value, bps.value, rows.value
 
 
 def _var_scalar_stride(scalars: bytes, n: int) -> int:
@@ -788,6 +840,46 @@ class MsmEngine:
     def mul_multi_table_builds(self) -> int:
         """Table slots batch_mul_multi* built on this engine so far (msm377_ctx_get_mul_multi_table_builds)."""
         return int(self._lib.msm377_ctx_get_mul_multi_table_builds(self._ctx))
+
+    # -- row commitments (include/msm377.h): out[i] = sum_j [s_ij]G_j over a resident generator set --
+    def set_generators(self, gens, window_bits: int = 0):
+        """Build and keep the window tables of the generators ``gens`` (96 wire bytes each, a host buffer, up to 4 096; up
+        to 64 with ``window_bits`` 16).  ``None`` or an empty buffer drops the set and frees its memory.  The old set is
+        dropped first; a call that fails leaves none (msm377_g1_set_generators)."""
+        gens = bytes(gens) if gens else b""
+        if len(gens) % 96:
+            raise ValueError("a generator is 96 bytes")
+        rc = self._lib.msm377_g1_set_generators(self._ctx, gens or None, len(gens) // 96, int(window_bits))
+        self._check(rc, "msm377_g1_set_generators")
+
+    def generators(self) -> Tuple[int, int]:
+        """(k, window width) of the resident generator set, (0, 0) without one (msm377_ctx_get_generators)."""
+        k, c = ctypes.c_uint32(), ctypes.c_int()
+        self._check(self._lib.msm377_ctx_get_generators(self._ctx, ctypes.addressof(k), ctypes.addressof(c)), "msm377_ctx_get_generators")
+        return k.value, c.value
+
+    def commit_rows_device(self, d_scalars: int, n: int, k: int, d_out: int, d_inf: int = 0, out_form="wire", out_stride=None, base_stride: int = 32):
+        """n rows of k scalars in HBM (in the engine's scalar form) over the first k generators of the resident set: n
+        records at ``d_out`` and, if ``d_inf`` is given, n identity flag bytes there (msm377_g1_commit_rows_device).  s_ij
+        is at ``d_scalars + i * out_stride + j * base_stride``; the default is row-major (``out_stride`` = 32 k)."""
+        if out_stride is None:
+            out_stride = 32 * k
+        rc = self._lib.msm377_g1_commit_rows_device(
+            self._ctx, d_scalars or None, int(n), int(k), int(out_stride), int(base_stride), _batch_mul_out_form(out_form), d_out or None, d_inf or None
+        )
+        self._check(rc, "msm377_g1_commit_rows_device")
+
+    def commit_rows(self, scalars: bytes, k: int, out_form="wire", layout="rows") -> Tuple[bytes, bytes]:
+        """The same on host buffers, ``scalars`` the dense k x n matrix in ``layout`` ("rows" or "columns"): returns
+        (records, identity flags) (msm377_g1_commit_rows)."""
+        n, out_stride, base_stride = _rows_shape(k, scalars, layout)
+        f = _batch_mul_out_form(out_form)
+        stride = _POINT_STRIDE.get(f, 96)
+        out = ctypes.create_string_buffer(max(1, stride * n))
+        inf = ctypes.create_string_buffer(max(1, n))
+        rc = self._lib.msm377_g1_commit_rows(self._ctx, bytes(scalars), n, int(k), out_stride, base_stride, f, ctypes.addressof(out), ctypes.addressof(inf))
+        self._check(rc, "msm377_g1_commit_rows")
+        return out.raw[: stride * n], inf.raw[:n]
 
     # -- variable-base batch multiplication (include/msm377.h): out[i] = [s_i]P_i --
     def batch_mul_var_device(self, d_points: int, d_scalars: int, n: int, d_out: int, d_inf: int = 0, out_form="wire", scalar_stride: int = 32):

@@ -149,4 +149,16 @@ const batch_mul_multi = (bases, scalars, { outForm = 'wire', layout = 'rows' } =
   return addon.batchMulMultiSync(pointsToBuffer(bases), scalarsToBuffer(scalars), BATCH_MUL_FORMS[outForm], BATCH_MUL_LAYOUTS[layout]);
 };
 
-module.exports = { batch_lincomb2, batch_mul, batch_mul_multi, batch_mul_var, compute_msm, compute_msm_edwards, set_bases, compute_msm_fixed_base, check_points, CHECK_CANONICAL, CHECK_CURVE, CHECK_SUBGROUP, CHECK_ALL, pointsToBuffer, scalarsToBuffer, version: addon.version };
+// Row commitments (msm377_g1_set_generators / msm377_g1_commit_rows): out[i] = sum_j [s_ij]G_j over a RESIDENT set of up to
+// 4 096 generators (Pedersen vector commitments).  set_generators(gens, {windowBits}) builds and keeps the window tables --
+// `gens`: {x, y} points or a Buffer of 96-byte wire records; windowBits 0 (= 8), 8, or 16 for up to 64 generators; an empty
+// list drops the set.  commit_rows(scalars, k, {outForm, layout}) runs over the first k generators: `scalars` the k x n matrix
+// as one flat list or Buffer, layout 'rows' (default) or 'columns'.  Returns {points, infinity} as batch_mul does.
+const set_generators = (gens, { windowBits = 0 } = {}) => addon.setGeneratorsSync(pointsToBuffer(gens), windowBits);
+const commit_rows = (scalars, k, { outForm = 'wire', layout = 'rows' } = {}) => {
+  if (!(outForm in BATCH_MUL_FORMS)) throw new RangeError("outForm: wire | mont_flag (plain mont cannot say 'identity')");
+  if (!(layout in BATCH_MUL_LAYOUTS)) throw new RangeError('layout: rows | columns');
+  return addon.commitRowsSync(scalarsToBuffer(scalars), k, BATCH_MUL_FORMS[outForm], BATCH_MUL_LAYOUTS[layout]);
+};
+
+module.exports = { batch_lincomb2, batch_mul, batch_mul_multi, commit_rows, set_generators, batch_mul_var, compute_msm, compute_msm_edwards, set_bases, compute_msm_fixed_base, check_points, CHECK_CANONICAL, CHECK_CURVE, CHECK_SUBGROUP, CHECK_ALL, pointsToBuffer, scalarsToBuffer, version: addon.version };

@@ -239,3 +239,25 @@ export const batch_mul_multi = (
   }
   return addon.batchMulMultiSync(pointsToBuffer(bases), scalarsToBuffer(scalars), BATCH_MUL_FORMS[outForm], BATCH_MUL_LAYOUTS[layout]);
 };
+
+// Row commitments (msm377_g1_set_generators / msm377_g1_commit_rows): out[i] = sum_j [s_ij]G_j over a RESIDENT set of up to
+// 4 096 generators.  set_generators builds and keeps the window tables (windowBits 0 = 8, 8, or 16 for up to 64
+// generators; an empty list drops the set); commit_rows runs over the first k generators, `scalars` the k x n matrix as one
+// flat list or Buffer in layout 'rows' (default) or 'columns'.  Returns what batch_mul returns.
+export const set_generators = (gens: BigIntPoint[] | U32ArrayPoint[] | Buffer, { windowBits = 0 }: { windowBits?: number } = {}): void => {
+  addon.setGeneratorsSync(pointsToBuffer(gens), windowBits);
+};
+
+export const commit_rows = (
+  scalars: bigint[] | Uint32Array[] | Buffer,
+  k: number,
+  { outForm = 'wire', layout = 'rows' }: { outForm?: keyof typeof BATCH_MUL_FORMS; layout?: keyof typeof BATCH_MUL_LAYOUTS } = {},
+): { points: Buffer; infinity: Buffer } => {
+  if (!(outForm in BATCH_MUL_FORMS)) {
+    throw new RangeError("outForm: wire | mont_flag (plain mont cannot say 'identity')");
+  }
+  if (!(layout in BATCH_MUL_LAYOUTS)) {
+    throw new RangeError('layout: rows | columns');
+  }
+  return addon.commitRowsSync(scalarsToBuffer(scalars), k, BATCH_MUL_FORMS[outForm], BATCH_MUL_LAYOUTS[layout]);
+};

@@ -26,6 +26,13 @@
 //   batchMulMultiSync(bases: Buffer 96k, scalars: Buffer 32kn, outForm: number, columns: number): {points, infinity}
 //                                                                      out[i] = sum_j [s_ij]B_j (msm377_g1_batch_mul_multi); the
 //                                                                      k x n scalars row-major, or column-major if columns != 0
+//   setGeneratorsSync(gens: Buffer 96k, windowBits: number): void       row commitments: build and keep the window tables of k
+//                                                                      generators (msm377_g1_set_generators); an empty Buffer
+//                                                                      drops the set
+//   commitRowsSync(scalars: Buffer 32kn, k: number, outForm: number, columns: number): {points, infinity}
+//                                                                      out[i] = sum_j [s_ij]G_j over the first k generators of
+//                                                                      the set (msm377_g1_commit_rows); the k x n scalars
+//                                                                      row-major, or column-major if columns != 0
 //   version(): string
 // Errors reject / throw a JS Error carrying msm377_strerror + msm377_last_error, matching the
 // reference's behaviour of throwing Error (cuzk/gpu.ts:7-10).
@@ -527,6 +534,80 @@ napi_value BatchMulMultiSync(napi_env env, napi_callback_info info) {
   return obj;
 }
 
+// setGeneratorsSync(gens, windowBits): the resident generator set of commitRowsSync; an empty Buffer drops it
+napi_value SetGeneratorsSync(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  bool gb = false;
+  int32_t bits = 0;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 2 || napi_is_buffer(env, argv[0], &gb) != napi_ok || !gb ||
+      napi_get_value_int32(env, argv[1], &bits) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "expected (gens: Buffer of 96 bytes per generator, windowBits: number)");
+    return nullptr;
+  }
+  uint8_t* g;
+  size_t gl;
+  napi_get_buffer_info(env, argv[0], reinterpret_cast<void**>(&g), &gl);
+  if (gl % 96 != 0 || gl / 96 > MSM377_GEN_MAX) {
+    napi_throw_range_error(env, nullptr, "gens must hold 0 to 4096 points of 96 bytes");
+    return nullptr;
+  }
+  std::string err;
+  std::lock_guard<std::mutex> lock(g_mu);
+  int rc = ensure_ctx(1, &err);  // any capacity: the set is an allocation of its own
+  if (!rc) {
+    rc = msm377_g1_set_generators(g_ctx, gl ? g : nullptr, static_cast<uint32_t>(gl / 96), bits);
+    if (rc) err = std::string("msm377_g1_set_generators: ") + msm377_strerror(rc) + ": " + msm377_last_error(g_ctx);
+  }
+  if (rc) napi_throw_error(env, nullptr, err.c_str());
+  return nullptr;
+}
+
+// commitRowsSync(scalars, k, outForm, columns) -> {points, infinity}: out[i] = sum_j [s_ij]G_j over the first k generators of
+// the resident set; scalars: the dense k x n matrix, row-major (columns = 0) or column-major
+napi_value CommitRowsSync(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  bool sb = false;
+  uint32_t k = 0, form = MSM377_POINTS_WIRE, columns = 0;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 4 || napi_is_buffer(env, argv[0], &sb) != napi_ok || !sb ||
+      napi_get_value_uint32(env, argv[1], &k) != napi_ok || napi_get_value_uint32(env, argv[2], &form) != napi_ok || napi_get_value_uint32(env, argv[3], &columns) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "expected (scalars: Buffer of 32 bytes per scalar, k: number, outForm: number, columns: number)");
+    return nullptr;
+  }
+  uint8_t* s;
+  size_t sl;
+  napi_get_buffer_info(env, argv[0], reinterpret_cast<void**>(&s), &sl);
+  if (k < 1 || k > MSM377_GEN_MAX || sl % (32 * static_cast<size_t>(k)) != 0 || (form != MSM377_POINTS_WIRE && form != MSM377_POINTS_MONT_FLAG)) {
+    napi_throw_range_error(env, nullptr, "k is 1 to 4096, scalars 32 bytes per generator and output; outForm is 0 (wire) or 2 (mont_flag)");
+    return nullptr;
+  }
+  const uint64_t n = sl / (32 * static_cast<size_t>(k));
+  const uint64_t out_stride = columns ? 32 : 32 * static_cast<uint64_t>(k), base_stride = columns ? 32 * (n ? n : 1) : 32;
+  const size_t stride = form == MSM377_POINTS_MONT_FLAG ? 104 : 96;
+  napi_value points, infinity, obj;
+  void *pd = nullptr, *id = nullptr;
+  if (napi_create_buffer(env, n * stride, &pd, &points) != napi_ok || napi_create_buffer(env, n, &id, &infinity) != napi_ok) return nullptr;
+  std::string err;
+  int rc;
+  {
+    std::lock_guard<std::mutex> lock(g_mu);
+    rc = ensure_ctx(1, &err);  // any capacity; without a set the call itself answers MSM377_ESTATE
+    if (!rc) {
+      rc = msm377_g1_commit_rows(g_ctx, s, n, k, out_stride, base_stride, form, static_cast<uint8_t*>(pd), static_cast<uint8_t*>(id));
+      if (rc) err = std::string("msm377_g1_commit_rows: ") + msm377_strerror(rc) + ": " + msm377_last_error(g_ctx);
+    }
+  }
+  if (rc) {
+    napi_throw_error(env, nullptr, err.c_str());
+    return nullptr;
+  }
+  napi_create_object(env, &obj);
+  napi_set_named_property(env, obj, "points", points);
+  napi_set_named_property(env, obj, "infinity", infinity);
+  return obj;
+}
+
 struct Job {
   napi_async_work work = nullptr;
   napi_deferred deferred = nullptr;
@@ -603,6 +684,8 @@ napi_value Init(napi_env env, napi_value exports) {
       {"batchMulVarSync", nullptr, BatchMulVarSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"batchLincomb2Sync", nullptr, BatchLincomb2Sync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"batchMulMultiSync", nullptr, BatchMulMultiSync, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"setGeneratorsSync", nullptr, SetGeneratorsSync, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"commitRowsSync", nullptr, CommitRowsSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"version", nullptr, Version, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
