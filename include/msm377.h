@@ -428,6 +428,70 @@ typedef struct msm377_stage_info {
  * columns u32, buckets bucket_records x 52 u32 (x 36 for MSM377_STAGE_FORM_ED).  MSM377_ESTATE (and nothing written) unless capture is on and the last call's last
  * pass ran to the end under it on a route the mode describes. */
 int msm377_g1_read_stage_ex(msm377_ctx* ctx, uint32_t slot, msm377_stage_info* info, void* digits, uint32_t* row_ptr, uint32_t* val_idx, uint32_t* buckets);
+
+/* ---- base records and window tables (what the hot kernels gather from) ----
+ *
+ * msm377_g1_read_bases describes and copies the base records the LAST CONVERSION of this context left: any G1 or
+ * Edwards-BLS12 MSM entry point (a chunked host-buffer call: all its chunks), any msm377_g1_set_bases* call, a
+ * window-partials call, and the Weierstrass rerun of any of them (the records then are the rerun's).  The layout is
+ * written down on the host where the conversion is queued, so it holds whatever the capture mode is; a call that does not
+ * use the read-back launches and allocates exactly what it did without it.  MSM377_ESTATE, and nothing written, before
+ * the first conversion and after a converting call that returned an error (its conversion failed, or the records may be
+ * half written: nothing is described until the next conversion succeeds).  `words` = NULL only fills `info`.
+ *
+ *   form           MSM377_BASES_*:
+ *                    TE_PROJECTIVE  64 words: Y - X, Y + X, 2d T, 2 Z of csrc/te377.hpp (13 limbs each, canonical), 12 pad
+ *                    TE_AFFINE      40 words: y - x, y + x (canonical), 2d x y (a lazy product below p + 2^354), 1 pad
+ *                    WEIERSTRASS    32 words: x, y (13 limbs each, canonical), 6 pad
+ *                    ED             32 words: y - x, y + x, 2d x y of Edwards-BLS12 (9 limbs each, canonical), 5 pad
+ *                  every coordinate a Montgomery residue in 29-bit limbs (radix 2^406; 2^261 for ED); pad words are zero
+ *   record_words   words per record
+ *   limbs          limbs per coordinate (13, or 9)
+ *   coords         coordinates per record (4, 3, 2, 3)
+ *   n              points of the conversion
+ *   windows        1, or the windows of a precomputed table (16, or 13 at 20-bit windows)
+ *   window_stride  records per window: record w * window_stride + i is [2^offset_w] P_i, offset_w the sum of window_bits[0 .. w)
+ *   window_bits[w] width of window w (0 beyond `windows`, and where windows == 1)
+ *   glv            1: records n .. 2n - 1 are phi(P_i) = (BETA x_i, y_i)
+ *   records        records the read-back addresses: windows * window_stride, 2 n behind the GLV front end, else n
+ *   flagged        input points that came in with an infinity flag (MSM377_POINTS_MONT_FLAG): their records hold the generator
+ * Records [first, first + count) go to `words`, record_words each; first + count <= records, else MSM377_EINVAL. */
+#define MSM377_BASES_TE_PROJECTIVE 0
+#define MSM377_BASES_TE_AFFINE 1
+#define MSM377_BASES_WEIERSTRASS 2
+#define MSM377_BASES_ED 3
+typedef struct msm377_bases_info {
+  uint32_t form, record_words, limbs, coords;
+  uint64_t n;
+  uint32_t windows, glv;
+  uint64_t window_stride;
+  uint64_t records;
+  uint32_t flagged, reserved;
+  uint32_t window_bits[16];
+} msm377_bases_info;
+int msm377_g1_read_bases(msm377_ctx* ctx, msm377_bases_info* info, uint64_t first, uint64_t count, uint32_t* words);
+
+/* The window table of a batch operation: records of 32 words -- x[13], y[13] (canonical Montgomery limbs), an identity flag
+ * (then x = y = 0) and 5 pad words.  Record w * 2^(c-1) + (d - 1) is [d 2^(c w)]B for w < W = ceil(256 / c), d = 1 .. 2^(c-1);
+ * the last record, W 2^(c-1), is [2^(c W)]B, the carry's entry.
+ *   which  MSM377_MUL_TABLE_SINGLE (msm377_g1_batch_mul*; index 0), _MULTI (slot `index` of msm377_g1_batch_mul_multi*),
+ *          _GENERATOR (generator `index` of the resident set of msm377_g1_set_generators)
+ *   info   width c, rows W + 1, records W 2^(c-1) + 1, and the table's key: the 96 wire bytes of its base (zero for a
+ *          generator table: the set is not keyed)
+ * Records [first, first + count) go to `words`; call with count = 0 and `words` = NULL to fill `info` alone.
+ * MSM377_ESTATE, and nothing written, when that table is not valid (never built, a build that failed, a dropped set, an
+ * index beyond the set).  The per-pass [1..8]P tables of the variable-base and pairwise calls are never valid between calls
+ * and cannot be read. */
+#define MSM377_MUL_TABLE_SINGLE 0
+#define MSM377_MUL_TABLE_MULTI 1
+#define MSM377_MUL_TABLE_GENERATOR 2
+typedef struct msm377_mul_table_info {
+  uint32_t width, rows;
+  uint64_t records;
+  uint8_t key[96];
+} msm377_mul_table_info;
+int msm377_g1_read_mul_table(msm377_ctx* ctx, uint32_t which, uint32_t index, msm377_mul_table_info* info, uint64_t first, uint64_t count, uint32_t* words);
+
 /* Convert one Montgomery XYZZ point (52 words) to the affine wire format (host-only). */
 int msm377_g1_xyzz_to_affine(const uint32_t xyzz[52], uint8_t out_xy[96]);
 

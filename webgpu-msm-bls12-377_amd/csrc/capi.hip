@@ -47,18 +47,24 @@ int msm377_ctx_create(int device, uint64_t max_points, msm377_ctx** out) { retur
 void msm377_ctx_destroy(msm377_ctx* ctx) { eng::ctx_destroy(ctx); }
 int msm377_ctx_set_stage_capture(msm377_ctx* ctx, int enabled) { return eng::set_stage_capture(ctx, enabled); }
 
+// An entry point that converts bases: after an error the base records are not described (msm377_g1_read_bases).
+static int converted(msm377_ctx* ctx, int rc) {
+  if (ctx && rc != MSM377_OK) ctx->last.bases.valid = false;
+  return rc;
+}
+
 const char* msm377_last_error(const msm377_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
 int msm377_g1_window_partials_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t win_begin,
                                      uint32_t win_count, uint8_t* partials_out) {
   if (!partials_out) return MSM377_EINVAL;
-  return eng::window_partials(ctx, d_points, d_scalars, n, win_begin, win_count, partials_out, nullptr);
+  return converted(ctx, eng::window_partials(ctx, d_points, d_scalars, n, win_begin, win_count, partials_out, nullptr));
 }
 
 int msm377_g1_window_partials_resident(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t win_begin,
                                        uint32_t win_count, void* d_partials_out) {
   if (!d_partials_out) return MSM377_EINVAL;
-  return eng::window_partials(ctx, d_points, d_scalars, n, win_begin, win_count, nullptr, d_partials_out);
+  return converted(ctx, eng::window_partials(ctx, d_points, d_scalars, n, win_begin, win_count, nullptr, d_partials_out));
 }
 
 
@@ -187,6 +193,34 @@ int msm377_g1_read_stage_ex(msm377_ctx* ctx, uint32_t slot, msm377_stage_info* i
     HIP_TRY(ctx, e);
   }
   return MSM377_OK;
+}
+
+// The base records of the last conversion: layout and pointer are those note_bases (sequencer.hip) wrote down beside the
+// launch; this is a copy.
+int msm377_g1_read_bases(msm377_ctx* ctx, msm377_bases_info* info, uint64_t first, uint64_t count, uint32_t* words) {
+  if (!ctx) return MSM377_EINVAL;
+  const BasesLayout& bl = ctx->last.bases;
+  if (!bl.valid || !bl.d_records) {
+    ctx->err = "no base records to read: no conversion has run on this context yet, or the last one failed";
+    return MSM377_ESTATE;
+  }
+  if (first > bl.info.records || count > bl.info.records - first || (count && !words && !info)) {
+    ctx->err = "record range outside the base records";
+    return MSM377_EINVAL;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  msm377_bases_info out = bl.info;
+  if (bl.d_flagged) HIP_TRY(ctx, hipMemcpy(&out.flagged, bl.d_flagged, 4, hipMemcpyDeviceToHost));
+  if (info) *info = out;
+  if (words && count) {
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream2));  // (every entry point has waited for its conversion already)
+    HIP_TRY(ctx, hipMemcpy(words, bl.d_records + first * out.record_words, (size_t)count * out.record_words * 4, hipMemcpyDeviceToHost));
+  }
+  return MSM377_OK;
+}
+
+int msm377_g1_read_mul_table(msm377_ctx* ctx, uint32_t which, uint32_t index, msm377_mul_table_info* info, uint64_t first, uint64_t count, uint32_t* words) {
+  return eng::g1_read_mul_table(ctx, which, index, info, first, count, words);
 }
 
 int msm377_ctx_get_stage_form(const msm377_ctx* ctx) { return (ctx && ctx->capture && ctx->last.n && is_g1_form(ctx->last.form)) ? ctx->last.form : -1; }
@@ -390,23 +424,23 @@ static int ed_wire_only(msm377_ctx* ctx) {
   return MSM377_EINVAL;
 }
 int msm377_ctx_reserve_host_staging(msm377_ctx* ctx) { return eng::reserve_host_staging(ctx); }
-int msm377_g1_msm_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint8_t out_xy[96]) { return eng::g1_msm_device(ctx, d_points, d_scalars, n, out_xy); }
-int msm377_g1_msm(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint8_t out_xy[96]) { return eng::g1_msm(ctx, points, scalars, n, out_xy); }
-int msm377_g1_msm_short_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t scalar_bytes, uint32_t scalar_bits, uint8_t out_xy[96]) { return eng::g1_msm_short_device(ctx, d_points, d_scalars, n, scalar_bytes, scalar_bits, out_xy); }
-int msm377_g1_msm_short(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint32_t scalar_bytes, uint32_t scalar_bits, uint8_t out_xy[96]) { return eng::g1_msm_short(ctx, points, scalars, n, scalar_bytes, scalar_bits, out_xy); }
+int msm377_g1_msm_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint8_t out_xy[96]) { return converted(ctx, eng::g1_msm_device(ctx, d_points, d_scalars, n, out_xy)); }
+int msm377_g1_msm(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint8_t out_xy[96]) { return converted(ctx, eng::g1_msm(ctx, points, scalars, n, out_xy)); }
+int msm377_g1_msm_short_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t scalar_bytes, uint32_t scalar_bits, uint8_t out_xy[96]) { return converted(ctx, eng::g1_msm_short_device(ctx, d_points, d_scalars, n, scalar_bytes, scalar_bits, out_xy)); }
+int msm377_g1_msm_short(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint32_t scalar_bytes, uint32_t scalar_bits, uint8_t out_xy[96]) { return converted(ctx, eng::g1_msm_short(ctx, points, scalars, n, scalar_bytes, scalar_bits, out_xy)); }
 int msm377_g1_msm_fixed_base_short_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n, uint32_t scalar_bytes, uint32_t scalar_bits, uint8_t out_xy[96]) { return eng::g1_msm_fixed_base_short_device(ctx, d_scalars, n, scalar_bytes, scalar_bits, out_xy); }
 int msm377_scalars_width_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n, uint32_t scalar_bytes, uint32_t* bits_out) { return eng::scalars_width_device(ctx, d_scalars, n, scalar_bytes, bits_out); }
-int msm377_ed_msm_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint8_t out_xy[64]) { return ed_wire_only(ctx) ? MSM377_EINVAL : eng::ed_msm_device(ctx, d_points, d_scalars, n, out_xy); }
-int msm377_ed_msm(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint8_t out_xy[64]) { return ed_wire_only(ctx) ? MSM377_EINVAL : eng::ed_msm(ctx, points, scalars, n, out_xy); }
+int msm377_ed_msm_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint8_t out_xy[64]) { return converted(ctx, ed_wire_only(ctx) ? MSM377_EINVAL : eng::ed_msm_device(ctx, d_points, d_scalars, n, out_xy)); }
+int msm377_ed_msm(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint8_t out_xy[64]) { return converted(ctx, ed_wire_only(ctx) ? MSM377_EINVAL : eng::ed_msm(ctx, points, scalars, n, out_xy)); }
 int msm377_ed_generate_bases_device(msm377_ctx* ctx, uint64_t seed, uint64_t n, void* d_points_out) { return ed_wire_only(ctx) ? MSM377_EINVAL : eng::ed_generate_bases_device(ctx, seed, n, d_points_out); }
-int msm377_g1_set_bases_device(msm377_ctx* ctx, const void* d_points, uint64_t n) { return eng::g1_set_bases_device(ctx, d_points, n); }
-int msm377_g1_set_bases(msm377_ctx* ctx, const uint8_t* points, uint64_t n) { return eng::g1_set_bases(ctx, points, n); }
-int msm377_g1_set_bases_precomputed_device(msm377_ctx* ctx, const void* d_points, uint64_t n) { return eng::g1_set_bases_precomputed_device(ctx, d_points, n); }
-int msm377_g1_set_bases_precomputed(msm377_ctx* ctx, const uint8_t* points, uint64_t n) { return eng::g1_set_bases_precomputed(ctx, points, n); }
+int msm377_g1_set_bases_device(msm377_ctx* ctx, const void* d_points, uint64_t n) { return converted(ctx, eng::g1_set_bases_device(ctx, d_points, n)); }
+int msm377_g1_set_bases(msm377_ctx* ctx, const uint8_t* points, uint64_t n) { return converted(ctx, eng::g1_set_bases(ctx, points, n)); }
+int msm377_g1_set_bases_precomputed_device(msm377_ctx* ctx, const void* d_points, uint64_t n) { return converted(ctx, eng::g1_set_bases_precomputed_device(ctx, d_points, n)); }
+int msm377_g1_set_bases_precomputed(msm377_ctx* ctx, const uint8_t* points, uint64_t n) { return converted(ctx, eng::g1_set_bases_precomputed(ctx, points, n)); }
 int msm377_g1_msm_fixed_base_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n, uint8_t out_xy[96]) { return eng::g1_msm_fixed_base_device(ctx, d_scalars, n, out_xy); }
 int msm377_g1_msm_fixed_base_batch_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n, uint32_t batch, uint8_t* out_xy) { return eng::g1_msm_fixed_base_batch_device(ctx, d_scalars, n, batch, out_xy); }
 int msm377_g1_msm_fixed_base(msm377_ctx* ctx, const uint8_t* scalars, uint64_t n, uint8_t out_xy[96]) { return eng::g1_msm_fixed_base(ctx, scalars, n, out_xy); }
-int msm377_g1_glv_window_partials_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t win_begin, uint32_t win_count, uint8_t* partials_out) { return eng::g1_glv_window_partials_device(ctx, d_points, d_scalars, n, win_begin, win_count, partials_out); }
+int msm377_g1_glv_window_partials_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t win_begin, uint32_t win_count, uint8_t* partials_out) { return converted(ctx, eng::g1_glv_window_partials_device(ctx, d_points, d_scalars, n, win_begin, win_count, partials_out)); }
 int msm377_g1_generate_bases_device(msm377_ctx* ctx, uint64_t seed, uint64_t n, void* d_points_out) { return eng::g1_generate_bases_device(ctx, seed, n, d_points_out); }
 int msm377_g1_batch_mul_device(msm377_ctx* ctx, const uint8_t base_xy[96], const void* d_scalars, uint64_t n, uint32_t out_form, void* d_out_points, uint8_t* d_out_inf) { return eng::g1_batch_mul_device(ctx, base_xy, d_scalars, n, out_form, d_out_points, d_out_inf); }
 int msm377_g1_batch_mul(msm377_ctx* ctx, const uint8_t base_xy[96], const uint8_t* scalars, uint64_t n, uint32_t out_form, uint8_t* out_points, uint8_t* out_inf) { return eng::g1_batch_mul(ctx, base_xy, scalars, n, out_form, out_points, out_inf); }

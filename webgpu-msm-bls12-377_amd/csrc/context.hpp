@@ -141,6 +141,15 @@ struct StageLayout {
   uint32_t coord_words = 16, limbs = 13;  // a bucket record of the pass: four coordinate slots of coord_words words, `limbs` of them used
 };
 
+// What the last base conversion left, for msm377_g1_read_bases: written on the host where the conversion is queued
+// (sequencer.hip note_bases), never derived afterwards.  valid: the call that queued it came back MSM377_OK.
+struct BasesLayout {
+  bool valid = false;
+  msm377_bases_info info = {};
+  const uint32_t* d_records = nullptr;    // ctx->d_bases, or the precomputed-window table
+  const uint32_t* d_flagged = nullptr;    // per-call imports: the device counter of flagged points (null: info.flagged holds it)
+};
+
 // ---- what belongs together, by the functions that use it ----
 
 // The batched affine conversion (sequencer.hip affine_convert_begin / affine_convert_finish, host_tail.hip
@@ -198,6 +207,7 @@ struct LastCall {
   int products = 0;        // field products per bucket addition of the last accumulation launch (bench.py's int32-mad roof)
   double stage_ms[MSM377_NUM_STAGES] = {};
   StageLayout stage;  // what the last enqueue_decompose launched with; valid is enqueue_windows' (msm377_g1_read_stage_ex)
+  BasesLayout bases;  // what the last base conversion wrote (msm377_g1_read_bases)
 };
 
 struct Fallbacks {

@@ -168,6 +168,32 @@ struct StageTimer {  // HIP events around one stage of a call, on its stream
   }
 };
 
+// The layout of the base records a conversion is about to leave (msm377_g1_read_bases): host bookkeeping next to the
+// launch, nothing is queued or allocated.  first != 0: a later chunk of a chunked upload, behind the records of the chunks
+// before it.  Under MSM377_POINTS_MONT_FLAG the import pass in front of every G1 conversion has counted the flagged points
+// on the device (MASK_BASES); the read-back fetches the count from there.
+void note_bases(msm377_ctx* ctx, uint32_t form, const uint32_t* d_records, uint64_t n, uint64_t first = 0, bool glv = false) {
+  static const uint32_t REC[4] = {64, 40, 32, 32}, LIMBS[4] = {13, 13, 13, 9}, COORDS[4] = {4, 3, 2, 3};
+  BasesLayout b;
+  b.info.form = form;
+  b.info.record_words = REC[form];
+  b.info.limbs = LIMBS[form];
+  b.info.coords = COORDS[form];
+  b.info.n = first + n;
+  b.info.windows = 1;
+  b.info.glv = glv ? 1 : 0;
+  b.info.window_stride = first + n;
+  b.info.records = (glv ? 2 : 1) * (first + n);
+  b.d_records = d_records;
+  if (form != MSM377_BASES_ED && ctx->point_form == MSM377_POINTS_MONT_FLAG && ctx->native.d_inf_mask) b.d_flagged = ctx->native.d_inf_mask + 2 * ctx->native.mask_words();
+  b.valid = true;
+  ctx->last.bases = b;
+}
+template <class CV>
+constexpr uint32_t bases_form_of() {
+  return std::is_same<CV, TeDev>::value ? MSM377_BASES_TE_PROJECTIVE : std::is_same<CV, EdDev>::value ? MSM377_BASES_ED : MSM377_BASES_WEIERSTRASS;
+}
+
 template <class CV>
 int convert_bases(msm377_ctx* ctx, const uint32_t* d_raw, uint64_t n, uint64_t first = 0, bool clear_err = true) {
   // Runs on the side stream: it depends on the points only, while decomposition and the sort
@@ -182,6 +208,7 @@ int convert_bases(msm377_ctx* ctx, const uint32_t* d_raw, uint64_t n, uint64_t f
   hipLaunchKernelGGL(k_convert_bases<CV>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream2, d_raw, ctx->d_bases + first * CV::REC_WORDS, n,
                      ctx->d_err + 2);
   HIP_TRY(ctx, hipGetLastError());
+  note_bases(ctx, bases_form_of<CV>(), ctx->d_bases, n, first);
   if (ctx->timing == 1) (void)hipEventRecord(ctx->ev[MSM377_STAGE_CONVERT][1], ctx->stream2);
   HIP_TRY(ctx, hipEventRecord(ctx->bases_ready, ctx->stream2));
   return MSM377_OK;
@@ -240,6 +267,7 @@ int affine_convert_finish(msm377_ctx* ctx, uint32_t* d_records_out, uint64_t n) 
   // it wait for the sort was measured both ways in round 2: 2^20 2.62 -> 2.59 ms, 2^22 10.39 -> 10.21 without the wait).
   hipLaunchKernelGGL(k_affine_down, dim3(nblk), dim3(AFF_THREADS), 0, ctx->stream2, n, ctx->aff.d_stash, ctx->aff.d_trees, ctx->aff.dm_inv, d_records_out, ctx->knobs.conv_wave_prio);
   HIP_TRY(ctx, hipGetLastError());
+  note_bases(ctx, MSM377_BASES_TE_AFFINE, d_records_out, n);  // (a precomputed table: its last window; the caller describes the whole)
   if (ctx->timing == 1) (void)hipEventRecord(ctx->ev[MSM377_STAGE_CONVERT][1], ctx->stream2);
   HIP_TRY(ctx, hipEventRecord(ctx->bases_ready, ctx->stream2));
   return MSM377_OK;
@@ -743,6 +771,7 @@ int convert_bases_g1(msm377_ctx* ctx, const uint32_t* d_raw, uint64_t n, bool gl
   hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(256), 0, ctx->stream2, (uint32_t*)(ctx->d_err + 2), 1u, (uint32_t*)nullptr, 0u);
   hipLaunchKernelGGL(k_convert_bases_glv, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream2, d_raw, ctx->d_bases, n);
   HIP_TRY(ctx, hipGetLastError());
+  note_bases(ctx, MSM377_BASES_WEIERSTRASS, ctx->d_bases, n, 0, true);
   if (ctx->timing == 1) (void)hipEventRecord(ctx->ev[MSM377_STAGE_CONVERT][1], ctx->stream2);
   HIP_TRY(ctx, hipEventRecord(ctx->bases_ready, ctx->stream2));
   return MSM377_OK;
@@ -900,10 +929,15 @@ int resident_table_to_weierstrass(msm377_ctx* ctx) {
   const uint32_t flagged = ctx->resident.flagged;  // the mask describes the raw copy, whatever form its records take
   const uint32_t* mask = ctx->resident.inf_mask;
   ctx->resident.clear();
+  ctx->last.bases.valid = false;  // the records are being overwritten: described again once the rebuild is through
   int rc = convert_table(ctx, ctx->d_raw_points, n, form);
+  ctx->last.bases.valid = false;
   if (rc) return rc;
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream2));
   ctx->resident.set(ctx->d_bases, n, form, flagged, mask);
+  ctx->last.bases.info.flagged = flagged;  // the set's own count: the input form may have changed since the set was imported
+  ctx->last.bases.d_flagged = nullptr;
+  ctx->last.bases.valid = true;
   return MSM377_OK;
 }
 
@@ -1577,6 +1611,12 @@ int g1_set_bases_precomputed_device(msm377_ctx* ctx, const void* d_points, uint6
   if (d_points != ctx->d_raw_points) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_raw_points, d_points, n * 96, hipMemcpyDeviceToDevice, ctx->stream2));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream2));
   r.set(ctx->d_bases, n, TABLE_TE_PRECOMP, flagged, ctx->native.d_inf_mask);
+  BasesLayout& bl = ctx->last.bases;  // affine_convert_finish described the last window; the table is all of them, n records apart
+  bl.d_records = r.table;
+  bl.info.windows = windows;
+  bl.info.window_stride = n;
+  bl.info.records = (uint64_t)windows * n;
+  for (uint32_t w = 0; w < windows; w++) bl.info.window_bits[w] = wide ? wide_width(w) : (uint32_t)MSM377_WINDOW_BITS;
   return MSM377_OK;
 }
 
@@ -2613,6 +2653,48 @@ int g1_generate_bases_device(msm377_ctx* ctx, uint64_t seed, uint64_t n, void* d
   hipLaunchKernelGGL(k_generate_bases, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, seed, n, (uint32_t*)d_points_out);
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return MSM377_OK;
+}
+
+// msm377_g1_read_mul_table: a copy of records the batch calls keep between calls, and what the host knows about them.
+int g1_read_mul_table(msm377_ctx* ctx, uint32_t which, uint32_t index, msm377_mul_table_info* info, uint64_t first, uint64_t count, uint32_t* words) {
+  if (!ctx) return MSM377_EINVAL;
+  ctx->err.clear();
+  const uint32_t* table = nullptr;
+  const uint8_t* key = nullptr;
+  int c = 0;
+  if (which == MSM377_MUL_TABLE_SINGLE && index == 0 && ctx->bm.valid) {
+    table = ctx->bm.table, key = ctx->bm.base, c = ctx->bm.width;
+  } else if (which == MSM377_MUL_TABLE_MULTI && index < MSM377_MUL_MAX_BASES && ctx->bmm.slot[index].valid) {
+    const BatchMulMultiState::Slot& sl = ctx->bmm.slot[index];
+    table = sl.table, key = sl.base, c = sl.width;
+  } else if (which == MSM377_MUL_TABLE_GENERATOR && index < ctx->gens.k) {
+    c = ctx->gens.width;
+    table = ctx->gens.tables + (size_t)index * bm_table_records((uint32_t)c) * BM_REC_WORDS;
+  } else if (which > MSM377_MUL_TABLE_GENERATOR) {
+    ctx->err = "unknown window table";
+    return MSM377_EINVAL;
+  }
+  if (!table) {
+    ctx->err = "that window table is not valid: never built, dropped, or left by a build that failed";
+    return MSM377_ESTATE;
+  }
+  const uint64_t records = bm_table_records((uint32_t)c);
+  if (first > records || count > records - first || (count && !words)) {
+    ctx->err = "record range outside the table";
+    return MSM377_EINVAL;
+  }
+  if (info) {
+    memset(info, 0, sizeof *info);
+    info->width = (uint32_t)c;
+    info->rows = (uint32_t)bm_windows(c) + 1;
+    info->records = records;
+    if (key) memcpy(info->key, key, 96);
+  }
+  if (words && count) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpy(words, table + first * BM_REC_WORDS, (size_t)count * BM_REC_WORDS * 4, hipMemcpyDeviceToHost));
+  }
   return MSM377_OK;
 }
 

@@ -60,6 +60,9 @@ int g1_batch_lincomb2_device(msm377_ctx* ctx, const void* d_p, const void* d_q, 
 int g1_batch_lincomb2(msm377_ctx* ctx, const uint8_t* p, const uint8_t* q, const uint8_t* a, const uint8_t* b, uint64_t n, uint32_t a_stride, uint32_t b_stride, uint32_t out_form,
                       uint8_t* out_points, uint8_t* out_inf);
 
+// The window table of a batch operation as it stands (no launch): msm377_g1_read_mul_table.
+int g1_read_mul_table(msm377_ctx* ctx, uint32_t which, uint32_t index, msm377_mul_table_info* info, uint64_t first, uint64_t count, uint32_t* words);
+
 void twin_return(msm377_ctx* ctx);  // takes back the resident bases a batch call lent to the twin of ctx
 
 // Shared with capi.hip (argument checks of the host-only entry points, the stage read-back).

@@ -88,6 +88,59 @@ class StageInfo(NamedTuple):
     key_max: Tuple[int, ...]
 
 
+BASES_TE_PROJECTIVE, BASES_TE_AFFINE, BASES_WEIERSTRASS, BASES_ED = 0, 1, 2, 3  # MSM377_BASES_*: BasesInfo.form
+MUL_TABLE_SINGLE, MUL_TABLE_MULTI, MUL_TABLE_GENERATOR = 0, 1, 2  # MSM377_MUL_TABLE_*
+_MUL_TABLES = {"single": MUL_TABLE_SINGLE, "multi": MUL_TABLE_MULTI, "generator": MUL_TABLE_GENERATOR}
+MUL_TABLE_RECORD_WORDS = 32
+
+
+class _BasesInfoStruct(ctypes.Structure):  # msm377_bases_info
+    _fields_ = [
+        ("form", ctypes.c_uint32),
+        ("record_words", ctypes.c_uint32),
+        ("limbs", ctypes.c_uint32),
+        ("coords", ctypes.c_uint32),
+        ("n", ctypes.c_uint64),
+        ("windows", ctypes.c_uint32),
+        ("glv", ctypes.c_uint32),
+        ("window_stride", ctypes.c_uint64),
+        ("records", ctypes.c_uint64),
+        ("flagged", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("window_bits", ctypes.c_uint32 * 16),
+    ]
+
+
+class BasesInfo(NamedTuple):
+    """msm377_bases_info: the base records the last conversion left (include/msm377.h); ``window_bits`` holds one entry
+    per window of a precomputed table and is empty otherwise."""
+
+    form: int
+    record_words: int
+    limbs: int
+    coords: int
+    n: int
+    windows: int
+    glv: int
+    window_stride: int
+    records: int
+    flagged: int
+    window_bits: Tuple[int, ...]
+
+
+class _MulTableInfoStruct(ctypes.Structure):  # msm377_mul_table_info
+    _fields_ = [("width", ctypes.c_uint32), ("rows", ctypes.c_uint32), ("records", ctypes.c_uint64), ("key", ctypes.c_uint8 * 96)]
+
+
+class MulTableInfo(NamedTuple):
+    """msm377_mul_table_info: width c, rows W + 1, records W 2^(c-1) + 1 and the 96 key bytes of a window table."""
+
+    width: int
+    rows: int
+    records: int
+    key: bytes
+
+
 class CheckReport(NamedTuple):
     """msm377_check_report: a point is counted once, in the first class it fails; ``first_bad`` is the lowest failing
     index (None if every point passed) and ``first_bad_reason`` the CHECK_* bit it failed (0 if none)."""
@@ -183,6 +236,8 @@ def load_library():
         "msm377_ctx_set_stage_capture": (i32, [vp, i32]),
         "msm377_g1_read_stage": (i32, [vp, u32, vp, vp, vp, vp]),
         "msm377_g1_read_stage_ex": (i32, [vp, u32, vp, vp, vp, vp, vp]),
+        "msm377_g1_read_bases": (i32, [vp, vp, u64, u64, vp]),
+        "msm377_g1_read_mul_table": (i32, [vp, u32, u32, vp, u64, u64, vp]),
         "msm377_g1_xyzz_to_affine": (i32, [vp, vp]),
         "msm377_g1_fold_window_partials": (i32, [vp, ctypes.c_uint32]),
         "msm377_ctx_set_glv": (i32, [vp, i32]),
@@ -1039,6 +1094,43 @@ class MsmEngine:
             if v is not None:
                 res[k] = v
         return res
+
+    def read_bases(self, first: int = 0, count=None, info_only: bool = False):
+        """(BasesInfo, records) of the base records the last conversion of this engine left (msm377_g1_read_bases): a
+        numpy array of ``count`` x record_words u32 starting at record ``first`` (default: all of them), or None with
+        ``info_only``.  Records of a precomputed table are window-major, w * window_stride + i.  MsmError(ESTATE) before
+        the first conversion and after one that failed."""
+        import numpy as np
+
+        raw = _BasesInfoStruct()
+        self._check(self._lib.msm377_g1_read_bases(self._ctx, ctypes.addressof(raw), 0, 0, None), "msm377_g1_read_bases")
+        bits = tuple(raw.window_bits[: raw.windows]) if raw.windows > 1 else ()
+        info = BasesInfo(int(raw.form), int(raw.record_words), int(raw.limbs), int(raw.coords), int(raw.n), int(raw.windows), int(raw.glv), int(raw.window_stride),
+                         int(raw.records), int(raw.flagged), bits)
+        if info_only:
+            return info, None
+        count = info.records - int(first) if count is None else int(count)
+        words = np.empty((count, info.record_words), dtype=np.uint32)
+        self._check(self._lib.msm377_g1_read_bases(self._ctx, None, int(first), count, words.ctypes.data if count else None), "msm377_g1_read_bases")
+        return info, words
+
+    def read_mul_table(self, which="single", index: int = 0, first: int = 0, count=None, info_only: bool = False):
+        """(MulTableInfo, records) of a window table of the batch operations (msm377_g1_read_mul_table): ``which`` is
+        "single" (batch_mul*), "multi" (slot ``index`` of batch_mul_multi*) or "generator" (generator ``index`` of the
+        resident set); records are 32 u32 each -- x[13], y[13], identity flag, 5 pad.  MsmError(ESTATE) when that table is
+        not valid."""
+        import numpy as np
+
+        w = _MUL_TABLES.get(which, which)
+        raw = _MulTableInfoStruct()
+        self._check(self._lib.msm377_g1_read_mul_table(self._ctx, int(w), int(index), ctypes.addressof(raw), 0, 0, None), "msm377_g1_read_mul_table")
+        info = MulTableInfo(int(raw.width), int(raw.rows), int(raw.records), bytes(raw.key))
+        if info_only:
+            return info, None
+        count = info.records - int(first) if count is None else int(count)
+        words = np.empty((count, MUL_TABLE_RECORD_WORDS), dtype=np.uint32)
+        self._check(self._lib.msm377_g1_read_mul_table(self._ctx, int(w), int(index), None, int(first), count, words.ctypes.data if count else None), "msm377_g1_read_mul_table")
+        return info, words
 
     def stage_form(self) -> int:
         """Coordinate system of the captured buckets: 0 = Weierstrass XYZZ, 1 = twisted Edwards (X, Y, T, Z), -1 = none."""
