@@ -626,6 +626,52 @@ int msm377_g1_batch_mul_multi_host(const uint8_t* bases_xy, uint32_t k, const ui
                                    uint8_t* out_points, uint8_t* out_inf);
 uint64_t msm377_ctx_get_mul_multi_table_builds(const msm377_ctx* ctx);
 
+/* ---- Edwards-BLS12 batch multiplication --------------------------------------------------- */
+
+/* out[i] = sum_{j<k} [s_ij]B_j on Edwards-BLS12 (a = -1, d = 3021 over Fq, cofactor 4), k = 1 .. MSM377_MUL_MAX_BASES, every
+ * output its own 64-byte wire point x || y: account addresses and view keys [sk_i]G, Pedersen-style record and value
+ * commitments [m_i]G + [r_i]H, ElGamal halves, Schnorr nonces, batches of public keys.  k = 1 is the single-base call.
+ * Wherever the two overlap the contract is that of msm377_g1_batch_mul_multi* above -- s_ij at
+ * scalars + i * out_stride + j * base_stride with both strides non-zero multiples of 32, rows that may overlap, any n in
+ * passes of 2^20 over the same scratch, 16-byte aligned device pointers, synchronous calls, MSM377_EINVAL with the outputs
+ * untouched, n = 0 MSM377_OK without a launch, msm377_ctx_set_mul_window / msm377_ctx_get_last_mul_window -- and this
+ * section states only what differs (csrc/kernels/ed_batch_mul.hpp).
+ *
+ * Scalars.  Every 32-byte value is a legal scalar, read as an integer and NOT reduced: no MSM377_ESCALAR, no rerun.  The
+ * context's scalar form MSM377_SCALARS_MONT is defined for Fr, not for this curve: while any non-wire input form is set the
+ * calls return MSM377_EINVAL, like every msm377_ed_* call.
+ *
+ * Bases.  bases_xy holds k records of 64 wire bytes in HOST memory.  Every curve point is a legal base and every relation
+ * between bases is followed through: the identity (0, 1), the point of order 2, both points of order 4, P + T,
+ * B_1 = +-B_0, B_1 = [m]B_0.  The addition law is complete ON THE CURVE, and the batched inversion relies on it, so the
+ * bases are verified on the host before anything is launched: a coordinate of q or more, or a point off the curve, is
+ * MSM377_EINVAL.
+ *
+ * Output.  64-byte wire records; the identity is (0, 1), an ordinary record.  There is no out_form and no flag bytes.
+ *
+ * State.  MSM377_MUL_MAX_BASES table slots of their own on the context, beside the G1 tables and independent of them: slot
+ * j is keyed by (the 64 bytes of the base at position j, the width).  A call rebuilds, in ONE build, only the slots among
+ * j < k whose key changed (msm377_ed_ctx_get_mul_table_builds counts the slots built); slots at k and above are left as
+ * they are; a failed build leaves the slots it touched invalid; a slot's memory (0.5 MB at c = 8, 64 MB at c = 16) is
+ * allocated at its first build and freed by msm377_ctx_destroy.  The resident MSM bases, every G1 table and build counter,
+ * the generator set and a check call's state are untouched by these calls, and the other way round.  The width rule is
+ * the G1 call's (csrc/batch_mul_recode.hpp batch_mul_multi_rule): inherited, not measured for this curve.
+ *
+ * msm377_ed_read_mul_table: slot `index` as msm377_g1_read_mul_table reads a G1 table, with records in the
+ * MSM377_BASES_ED layout -- (y - x)[9], (y + x)[9], (2d x y)[9] canonical limbs in the Montgomery radix 2^261, then 5 zero
+ * words; the identity is the ordinary record (1, 1, 0).  Record w * 2^(c-1) + (d - 1) is [d 2^(c w)]B, the last record
+ * [2^(c W)]B.  info->key holds the 64 base bytes, then zeros.  MSM377_ESTATE when the slot is not valid, MSM377_EINVAL for
+ * an index of MSM377_MUL_MAX_BASES or more. */
+int msm377_ed_batch_mul_multi_device(msm377_ctx* ctx, const uint8_t* bases_xy /* k x 64, HOST */, uint32_t k, const void* d_scalars, uint64_t n, uint64_t out_stride,
+                                     uint64_t base_stride, void* d_out_points);
+int msm377_ed_batch_mul_multi(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k, const uint8_t* scalars, uint64_t n, uint64_t out_stride, uint64_t base_stride,
+                              uint8_t* out_points);
+/* The same on ONE CPU thread: no device, no context (csrc/ed_batch_mul_host.hpp): plain double-and-add per term, general
+ * additions, one inversion per output; the yardstick of the device call. */
+int msm377_ed_batch_mul_multi_host(const uint8_t* bases_xy, uint32_t k, const uint8_t* scalars, uint64_t n, uint64_t out_stride, uint64_t base_stride, uint8_t* out_points);
+uint64_t msm377_ed_ctx_get_mul_table_builds(const msm377_ctx* ctx);
+int msm377_ed_read_mul_table(msm377_ctx* ctx, uint32_t index, msm377_mul_table_info* info, uint64_t first, uint64_t count, uint32_t* words);
+
 /* ---- variable-base batch multiplication --------------------------------------------------- */
 
 /* out[i] = [s_i]P_i: n scalar multiples of n points, each returned as its own affine point (an SRS or powers-of-tau

@@ -12,6 +12,7 @@
 #include "sequencer.hpp"
 #include "batch_mul_host.hpp"
 #include "batch_mul_multi_host.hpp"
+#include "ed_batch_mul_host.hpp"
 #include "commit_rows_host.hpp"
 #include "commit_rows_plan.hpp"
 #include "batch_lincomb2_host.hpp"
@@ -347,6 +348,13 @@ uint64_t msm377_ctx_get_mul_table_builds(const msm377_ctx* ctx) { return ctx ? c
 
 uint64_t msm377_ctx_get_mul_multi_table_builds(const msm377_ctx* ctx) { return ctx ? ctx->bmm.builds : 0; }
 
+// ---- Edwards-BLS12 batch multiplication: the host-only parts (ed_batch_mul_host.hpp) ----
+int msm377_ed_batch_mul_multi_host(const uint8_t* bases_xy, uint32_t k, const uint8_t* scalars, uint64_t n, uint64_t out_stride, uint64_t base_stride, uint8_t* out_points) {
+  return ed_batch_mul_multi_host(bases_xy, k, scalars, n, out_stride, base_stride, out_points);
+}
+
+uint64_t msm377_ed_ctx_get_mul_table_builds(const msm377_ctx* ctx) { return ctx ? ctx->edbm.builds : 0; }
+
 int msm377_ctx_get_last_check(const msm377_ctx* ctx, msm377_check_report* out) {
   if (!ctx || !out) return MSM377_EINVAL;
   *out = ctx->last_check;
@@ -433,6 +441,16 @@ int msm377_scalars_width_device(msm377_ctx* ctx, const void* d_scalars, uint64_t
 int msm377_ed_msm_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint8_t out_xy[64]) { return converted(ctx, ed_wire_only(ctx) ? MSM377_EINVAL : eng::ed_msm_device(ctx, d_points, d_scalars, n, out_xy)); }
 int msm377_ed_msm(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint8_t out_xy[64]) { return converted(ctx, ed_wire_only(ctx) ? MSM377_EINVAL : eng::ed_msm(ctx, points, scalars, n, out_xy)); }
 int msm377_ed_generate_bases_device(msm377_ctx* ctx, uint64_t seed, uint64_t n, void* d_points_out) { return ed_wire_only(ctx) ? MSM377_EINVAL : eng::ed_generate_bases_device(ctx, seed, n, d_points_out); }
+int msm377_ed_batch_mul_multi_device(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k, const void* d_scalars, uint64_t n, uint64_t out_stride, uint64_t base_stride,
+                                     void* d_out_points) {
+  return ed_wire_only(ctx) ? MSM377_EINVAL : eng::ed_batch_mul_multi_device(ctx, bases_xy, k, d_scalars, n, out_stride, base_stride, d_out_points);
+}
+int msm377_ed_batch_mul_multi(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k, const uint8_t* scalars, uint64_t n, uint64_t out_stride, uint64_t base_stride, uint8_t* out_points) {
+  return ed_wire_only(ctx) ? MSM377_EINVAL : eng::ed_batch_mul_multi(ctx, bases_xy, k, scalars, n, out_stride, base_stride, out_points);
+}
+int msm377_ed_read_mul_table(msm377_ctx* ctx, uint32_t index, msm377_mul_table_info* info, uint64_t first, uint64_t count, uint32_t* words) {
+  return eng::ed_read_mul_table(ctx, index, info, first, count, words);
+}
 int msm377_g1_set_bases_device(msm377_ctx* ctx, const void* d_points, uint64_t n) { return converted(ctx, eng::g1_set_bases_device(ctx, d_points, n)); }
 int msm377_g1_set_bases(msm377_ctx* ctx, const uint8_t* points, uint64_t n) { return converted(ctx, eng::g1_set_bases(ctx, points, n)); }
 int msm377_g1_set_bases_precomputed_device(msm377_ctx* ctx, const void* d_points, uint64_t n) { return converted(ctx, eng::g1_set_bases_precomputed_device(ctx, d_points, n)); }

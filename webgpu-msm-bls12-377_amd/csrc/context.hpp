@@ -106,6 +106,23 @@ struct BatchMulMultiState {
   uint32_t* bases_wire = nullptr;   // their 96 bytes each on the device
 };
 
+// Edwards-BLS12 batch multiplication (msm377_ed_batch_mul_multi*, kernels/ed_batch_mul.hpp): one window table per base
+// POSITION, keyed by the base's 64 wire bytes and the width, each its own allocation made when the slot is first built.
+// The rule is BatchMulMultiState's: a build clears `valid` of every slot it rebuilds first and sets it as its last step.
+// The stash, the trees, the block products, the build's row-base scratch and the forced / last width are the G1 batch
+// calls'; no G1 table, key or build count is read or written from here.
+struct EdBatchMulState {
+  struct Slot {
+    bool valid = false;
+    uint8_t base[64] = {};
+    int width = 0;
+    uint32_t* table = nullptr;
+    uint64_t table_cap = 0;  // records allocated
+  };
+  Slot slot[MSM377_MUL_MAX_BASES];
+  uint64_t builds = 0;  // slots built so far (msm377_ed_ctx_get_mul_table_builds)
+};
+
 // The resident generator set of the row commitments (msm377_g1_set_generators / msm377_g1_commit_rows*,
 // kernels/commit_rows.hpp): the window tables of k generators at ONE width as ONE allocation, table j at record
 // j * bm_table_records(width).  The rule is ResidentBases': msm377_g1_set_generators drops the set (and gives its
@@ -256,6 +273,7 @@ struct msm377_ctx {
   ResidentBases resident;             // fixed-base mode: the bases of the last successful msm377_g1_set_bases* call
   BatchMulState bm;                   // fixed-base batch multiplication: its table and scratch (allocated on first use)
   BatchMulMultiState bmm;             // multi-base batch multiplication: a table per base position (allocated when built)
+  EdBatchMulState edbm;               // Edwards-BLS12 batch multiplication: a table per base position (allocated when built)
   GeneratorSet gens;                  // row commitments: the resident generator tables (one allocation per set)
   WideBuffers wide;                   // the 20-bit-window sort's buffers (allocated with such a table; the twin's own set)
   AffineConvert aff;

@@ -47,10 +47,12 @@
 
 #include "context.hpp"
 #include "host_tail.hpp"
+#include "ed_batch_mul_host.hpp"
 #include "validate_host.hpp"
 #include "kernels/accumulate.hpp"
 #include "kernels/batch_mul.hpp"
 #include "kernels/batch_mul_multi.hpp"
+#include "kernels/ed_batch_mul.hpp"
 #include "kernels/commit_rows.hpp"
 #include "kernels/convert.hpp"
 #include "kernels/decompose.hpp"
@@ -2257,6 +2259,208 @@ int g1_batch_mul_multi(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k, con
   ctx->bm.window = forced;
   (void)hipFree(d_io);
   return rc;
+}
+
+// ---- Edwards-BLS12 batch multiplication (include/msm377.h "Edwards-BLS12 batch multiplication"; kernels/ed_batch_mul.hpp) ----
+// The flow of the multi-base G1 call on ctx->stream over the same scratch; the tables are ctx->edbm's.
+namespace {
+
+int edbm_check_args(msm377_ctx* ctx, uint32_t k, uint64_t out_stride, uint64_t base_stride) {
+  if (!ctx) return MSM377_EINVAL;
+  ctx->err.clear();
+  return bmm_check_shape(ctx, k, out_stride, base_stride);
+}
+
+int edbm_check_bases(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k) {
+  if (ed_batch_mul_bases_ok(bases_xy, k)) return MSM377_OK;
+  ctx->err = "a base has a coordinate that is not below q or is not on the curve";
+  return MSM377_EINVAL;
+}
+
+// The m <= BM_CHUNK points the stash holds -> wire records or table records at d_out: three launches.
+int edbm_normalise(msm377_ctx* ctx, uint64_t m, uint32_t form, void* d_out) {
+  BatchMulState& bm = ctx->bm;
+  const uint32_t blocks = (uint32_t)((m + BM_BLOCK - 1) / BM_BLOCK);
+  uint4* stash = reinterpret_cast<uint4*>(bm.stash);
+  hipLaunchKernelGGL(k_edbm_up, dim3(blocks), dim3(BM_THREADS), 0, ctx->stream, stash, m, bm.trees, bm.block_prod);
+  hipLaunchKernelGGL(k_edbm_across, dim3(1), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)bm.block_prod, blocks, bm.block_inv);
+  const dim3 grid(blocks), block(BM_THREADS);
+  if (form == EDBM_FORM_WIRE)
+    hipLaunchKernelGGL(k_edbm_down<EDBM_FORM_WIRE>, grid, block, 0, ctx->stream, (const uint4*)stash, m, (const uint32_t*)bm.trees, (const uint32_t*)bm.block_inv, (uint8_t*)d_out);
+  else
+    hipLaunchKernelGGL(k_edbm_down<EDBM_FORM_TABLE>, grid, block, 0, ctx->stream, (const uint4*)stash, m, (const uint32_t*)bm.trees, (const uint32_t*)bm.block_inv, (uint8_t*)d_out);
+  HIP_TRY(ctx, hipGetLastError());
+  return MSM377_OK;
+}
+
+// bmm_ensure_tables on ctx->edbm: slots j < k whose key is (base j, c) stay, every other one is rebuilt in ONE build.  The
+// row-base scratch is the G1 multi-base build's (used and waited for inside a build only).
+int edbm_ensure_tables(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k, int c) {
+  EdBatchMulState& em = ctx->edbm;
+  uint32_t missing[MSM377_MUL_MAX_BASES], m = 0;
+  for (uint32_t j = 0; j < k; j++) {
+    const EdBatchMulState::Slot& sl = em.slot[j];
+    if (!(sl.valid && sl.width == c && memcmp(sl.base, bases_xy + (size_t)j * 64, 64) == 0)) missing[m++] = j;
+  }
+  if (m == 0) return MSM377_OK;
+  for (uint32_t b = 0; b < m; b++) em.slot[missing[b]].valid = false;
+  const uint64_t records = bm_table_records((uint32_t)c), rows = (uint64_t)bm_windows(c) + 1, total = records * m;
+  int rc = bm_alloc(ctx, &ctx->bmm.row_bases, (size_t)MSM377_MUL_MAX_BASES * (bm_windows(BM_MIN_WIDTH) + 1) * BM_REC_WORDS * 4);
+  if (!rc) rc = bm_alloc(ctx, &ctx->bmm.bases_wire, (size_t)MSM377_MUL_MAX_BASES * 96);
+  for (uint32_t b = 0; b < m && !rc; b++) {
+    EdBatchMulState::Slot& sl = em.slot[missing[b]];
+    if (sl.table_cap >= records) continue;
+    ctx->own.release(sl.table);
+    sl.table = nullptr;
+    sl.table_cap = 0;
+    rc = bm_alloc(ctx, &sl.table, (size_t)records * BM_REC_WORDS * 4);
+    if (!rc) sl.table_cap = records;
+  }
+  uint32_t* staging = nullptr;
+  if (!rc) rc = bm_alloc(ctx, &staging, (size_t)std::min<uint64_t>(total, BM_CHUNK) * BM_REC_WORDS * 4);
+  if (rc) return rc;
+  uint8_t wire[MSM377_MUL_MAX_BASES * 64];
+  for (uint32_t b = 0; b < m; b++) memcpy(wire + (size_t)b * 64, bases_xy + (size_t)missing[b] * 64, 64);
+  uint4* stash = reinterpret_cast<uint4*>(ctx->bm.stash);
+  uint32_t* row_bases = ctx->bmm.row_bases;
+  hipError_t e = hipMemcpyAsync(ctx->bmm.bases_wire, wire, (size_t)m * 64, hipMemcpyHostToDevice, ctx->stream);  // (pageable memory: staged before the call returns)
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_edbm_row_bases, dim3(m), dim3(64), 0, ctx->stream, (const uint32_t*)ctx->bmm.bases_wire, (uint32_t)c, stash);
+    rc = edbm_normalise(ctx, rows * m, EDBM_FORM_TABLE, row_bases);
+  }
+  for (uint64_t first = 0; first < total && !rc && e == hipSuccess; first += BM_CHUNK) {
+    const uint64_t count = std::min<uint64_t>(BM_CHUNK, total - first);
+    hipLaunchKernelGGL(k_edbm_entries, dim3((unsigned)((count + BM_THREADS - 1) / BM_THREADS)), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)row_bases, (uint32_t)c, first, count,
+                       stash);
+    rc = edbm_normalise(ctx, count, EDBM_FORM_TABLE, staging);
+    for (uint64_t g = first; g < first + count && !rc && e == hipSuccess;) {  // the pieces of this pass, one per table it covers
+      const uint64_t b = g / records, t = g - b * records, len = std::min<uint64_t>(records - t, first + count - g);
+      e = hipMemcpyAsync(em.slot[missing[b]].table + t * BM_REC_WORDS, staging + (g - first) * BM_REC_WORDS, (size_t)len * BM_REC_WORDS * 4, hipMemcpyDeviceToDevice, ctx->stream);
+      g += len;
+    }
+  }
+  const hipError_t waited = hipStreamSynchronize(ctx->stream);  // a table is valid only once it is there; and the staging goes back
+  ctx->own.release(staging);
+  if (rc) return rc;
+  HIP_TRY(ctx, e);
+  HIP_TRY(ctx, waited);
+  for (uint32_t b = 0; b < m; b++) {
+    EdBatchMulState::Slot& sl = em.slot[missing[b]];
+    memcpy(sl.base, bases_xy + (size_t)missing[b] * 64, 64);
+    sl.width = c;
+    sl.valid = true;
+    em.builds++;
+  }
+  return MSM377_OK;
+}
+
+}  // namespace
+
+int ed_batch_mul_multi_device(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k, const void* d_scalars, uint64_t n, uint64_t out_stride, uint64_t base_stride, void* d_out_points) {
+  int rc = edbm_check_args(ctx, k, out_stride, base_stride);
+  if (rc) return rc;
+  if (n == 0) return MSM377_OK;
+  if (!bases_xy || !d_scalars || !d_out_points) {
+    ctx->err = "null pointer";
+    return MSM377_EINVAL;
+  }
+  if (((uintptr_t)d_scalars & 15) || ((uintptr_t)d_out_points & 15)) {
+    ctx->err = "device pointers must be 16-byte aligned";
+    return MSM377_EINVAL;
+  }
+  rc = edbm_check_bases(ctx, bases_xy, k);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const int c = ctx->bm.window ? ctx->bm.window : batch_mul_multi_rule(n, k);
+  rc = bm_ensure_scratch(ctx);
+  if (!rc) rc = edbm_ensure_tables(ctx, bases_xy, k, c);
+  if (rc) {
+    (void)hipStreamSynchronize(ctx->stream);
+    return rc;
+  }
+  ctx->bm.last_window = c;
+  EdbmTables tables = {};
+  for (uint32_t j = 0; j < k; j++) tables.t[j] = ctx->edbm.slot[j].table;
+  for (uint64_t off = 0; off < n && !rc; off += BM_CHUNK) {
+    const uint64_t m = std::min<uint64_t>(BM_CHUNK, n - off);
+    // Row `off` of the CALL's layout: the strides are the call's, whatever the pass's length.
+    hipLaunchKernelGGL(k_edbm_accumulate, dim3((unsigned)((m + BM_THREADS - 1) / BM_THREADS)), dim3(BM_THREADS), 0, ctx->stream, tables, (const uint8_t*)d_scalars + off * out_stride, m, k,
+                       out_stride, base_stride, (uint32_t)c, reinterpret_cast<uint4*>(ctx->bm.stash));
+    rc = edbm_normalise(ctx, m, EDBM_FORM_WIRE, (uint8_t*)d_out_points + off * 64);
+  }
+  const hipError_t e = hipStreamSynchronize(ctx->stream);
+  if (rc) return rc;
+  HIP_TRY(ctx, e);
+  return MSM377_OK;
+}
+
+// Host buffers: each piece of at most 2^20 scalars repacked row-major on the host, up, records down.  One width for the
+// whole call, whatever the pieces' sizes.
+int ed_batch_mul_multi(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k, const uint8_t* scalars, uint64_t n, uint64_t out_stride, uint64_t base_stride, uint8_t* out_points) {
+  int rc = edbm_check_args(ctx, k, out_stride, base_stride);
+  if (rc) return rc;
+  if (n == 0) return MSM377_OK;
+  if (!bases_xy || !scalars || !out_points) {
+    ctx->err = "null pointer";
+    return MSM377_EINVAL;
+  }
+  rc = edbm_check_bases(ctx, bases_xy, k);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const uint64_t piece = std::min<uint64_t>(n, BM_CHUNK / k);
+  std::vector<uint8_t> rows((size_t)piece * k * 32);
+  uint8_t* d_io = nullptr;  // scalars, then records: 16-byte aligned parts
+  const size_t off_out = (size_t)piece * k * 32;
+  if (hipMalloc((void**)&d_io, off_out + (size_t)piece * 64) != hipSuccess) {
+    (void)hipGetLastError();
+    ctx->err = "out of device memory for the batch multiplication staging";
+    return MSM377_ENOMEM;
+  }
+  const int forced = ctx->bm.window;
+  if (!forced) ctx->bm.window = batch_mul_multi_rule(n, k);
+  for (uint64_t off = 0; off < n && !rc; off += piece) {
+    const uint64_t m = std::min<uint64_t>(piece, n - off);
+    for (uint64_t i = 0; i < m; i++)
+      for (uint32_t j = 0; j < k; j++) memcpy(rows.data() + ((size_t)i * k + j) * 32, scalars + (off + i) * out_stride + (uint64_t)j * base_stride, 32);
+    rc = hip_ok(ctx, hipMemcpy(d_io, rows.data(), (size_t)m * k * 32, hipMemcpyHostToDevice), "hipMemcpy(scalars)") ? MSM377_OK : MSM377_EHIP;
+    if (!rc) rc = ed_batch_mul_multi_device(ctx, bases_xy, k, d_io, m, (uint64_t)k * 32, 32, d_io + off_out);
+    if (!rc) rc = hip_ok(ctx, hipMemcpy(out_points + off * 64, d_io + off_out, m * 64, hipMemcpyDeviceToHost), "hipMemcpy(records)") ? MSM377_OK : MSM377_EHIP;
+  }
+  ctx->bm.window = forced;
+  (void)hipFree(d_io);
+  return rc;
+}
+
+// msm377_ed_read_mul_table: slot `index` of ctx->edbm as it stands; the key is the 64 base bytes, then zeros.
+int ed_read_mul_table(msm377_ctx* ctx, uint32_t index, msm377_mul_table_info* info, uint64_t first, uint64_t count, uint32_t* words) {
+  if (!ctx) return MSM377_EINVAL;
+  ctx->err.clear();
+  if (index >= MSM377_MUL_MAX_BASES) {
+    ctx->err = "unknown window table";
+    return MSM377_EINVAL;
+  }
+  const EdBatchMulState::Slot& sl = ctx->edbm.slot[index];
+  if (!sl.valid) {
+    ctx->err = "that window table is not valid: never built, or left by a build that failed";
+    return MSM377_ESTATE;
+  }
+  const uint64_t records = bm_table_records((uint32_t)sl.width);
+  if (first > records || count > records - first || (count && !words)) {
+    ctx->err = "record range outside the table";
+    return MSM377_EINVAL;
+  }
+  if (info) {
+    memset(info, 0, sizeof *info);
+    info->width = (uint32_t)sl.width;
+    info->rows = (uint32_t)bm_windows(sl.width) + 1;
+    info->records = records;
+    memcpy(info->key, sl.base, 64);
+  }
+  if (words && count) {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpy(words, sl.table + first * BM_REC_WORDS, (size_t)count * BM_REC_WORDS * 4, hipMemcpyDeviceToHost));
+  }
+  return MSM377_OK;
 }
 
 // ---- row commitments (include/msm377.h "row commitments"; kernels/commit_rows.hpp, commit_rows_plan.hpp) ----

@@ -290,6 +290,11 @@ def load_library():
         "msm377_g1_batch_lincomb2_device": (i32, [vp, vp, vp, vp, vp, u64, u32, u32, u32, vp, vp]),
         "msm377_g1_batch_lincomb2": (i32, [vp, u8p, u8p, u8p, u8p, u64, u32, u32, u32, vp, vp]),
         "msm377_g1_batch_lincomb2_host": (i32, [u8p, u8p, u32, u8p, u8p, u32, u64, u32, u32, u32, vp, vp]),
+        "msm377_ed_batch_mul_multi_device": (i32, [vp, u8p, u32, vp, u64, u64, u64, vp]),
+        "msm377_ed_batch_mul_multi": (i32, [vp, u8p, u32, u8p, u64, u64, u64, vp]),
+        "msm377_ed_batch_mul_multi_host": (i32, [u8p, u32, u8p, u64, u64, u64, vp]),
+        "msm377_ed_ctx_get_mul_table_builds": (u64, [vp]),
+        "msm377_ed_read_mul_table": (i32, [vp, u32, vp, u64, u64, vp]),
         "msm377_ctx_set_mul_window": (i32, [vp, i32]),
         "msm377_ctx_get_last_mul_window": (i32, [vp]),
         "msm377_ctx_get_mul_table_builds": (u64, [vp]),
@@ -451,6 +456,25 @@ def batch_mul_multi_host(bases: bytes, scalars: bytes, out_form="wire", layout="
     if rc:
         raise MsmError(rc, "msm377_g1_batch_mul_multi_host")
     return out.raw[: stride * n], inf.raw[:n]
+
+
+def _ed_multi_shape(bases: bytes, scalars: bytes, layout: str) -> Tuple[int, int, int, int]:
+    """_multi_shape for Edwards-BLS12 bases, 64 wire bytes each."""
+    if len(bases) % 64 or not 1 <= len(bases) // 64 <= MUL_MAX_BASES:
+        raise ValueError("bases: 1 to %d records of 64 bytes" % MUL_MAX_BASES)
+    return _multi_shape(b"\0" * (96 * (len(bases) // 64)), scalars, layout)
+
+
+def ed_batch_mul_multi_host(bases: bytes, scalars: bytes, layout="rows") -> bytes:
+    """out[i] = sum_j [s_ij]B_j on Edwards-BLS12 on the calling thread (msm377_ed_batch_mul_multi_host): no context, no
+    device.  ``bases``: k records of 64 wire bytes, every one a curve point; ``scalars``: the k x n matrix of 32-byte
+    little-endian integers in ``layout``, any value below 2^256.  Returns n 64-byte wire records; the identity is (0, 1)."""
+    k, n, out_stride, base_stride = _ed_multi_shape(bases, scalars, layout)
+    out = ctypes.create_string_buffer(max(1, 64 * n))
+    rc = load_library().msm377_ed_batch_mul_multi_host(bytes(bases), k, bytes(scalars), n, out_stride, base_stride, ctypes.addressof(out))
+    if rc:
+        raise MsmError(rc, "msm377_ed_batch_mul_multi_host")
+    return out.raw[: 64 * n]
 
 
 GEN_MAX = 4096  # MSM377_GEN_MAX
@@ -1046,6 +1070,52 @@ class MsmEngine:
 
     def ed_generate_bases_device(self, seed: int, n: int, d_points_out: int):
         self._check(self._lib.msm377_ed_generate_bases_device(self._ctx, int(seed) & (2**64 - 1), int(n), d_points_out), "msm377_ed_generate_bases_device")
+
+    # -- Edwards-BLS12 batch multiplication (include/msm377.h): out[i] = sum_j [s_ij]B_j, 64-byte wire outputs --
+    def ed_batch_mul_multi_device(self, bases: bytes, d_scalars: int, n: int, d_out: int, out_stride=None, base_stride: int = 32):
+        """n rows of k scalars in HBM over the k Edwards-BLS12 bases ``bases`` (64 wire bytes each, a host buffer): n
+        64-byte wire records at ``d_out`` (msm377_ed_batch_mul_multi_device).  s_ij is at ``d_scalars + i * out_stride + j *
+        base_stride``; the default is row-major.  Any n; every curve point is a legal base, in every relation to the others."""
+        if len(bases) % 64:
+            raise ValueError("an Edwards base is 64 bytes")
+        k = len(bases) // 64
+        if out_stride is None:
+            out_stride = 32 * k
+        rc = self._lib.msm377_ed_batch_mul_multi_device(self._ctx, bytes(bases), k, d_scalars or None, int(n), int(out_stride), int(base_stride), d_out or None)
+        self._check(rc, "msm377_ed_batch_mul_multi_device")
+
+    def ed_batch_mul_multi(self, bases: bytes, scalars: bytes, layout="rows") -> bytes:
+        """The same on host buffers, ``scalars`` the dense k x n matrix in ``layout`` ("rows" or "columns"): returns the n
+        records (msm377_ed_batch_mul_multi)."""
+        k, n, out_stride, base_stride = _ed_multi_shape(bases, scalars, layout)
+        out = ctypes.create_string_buffer(max(1, 64 * n))
+        rc = self._lib.msm377_ed_batch_mul_multi(self._ctx, bytes(bases), k, bytes(scalars), n, out_stride, base_stride, ctypes.addressof(out))
+        self._check(rc, "msm377_ed_batch_mul_multi")
+        return out.raw[: 64 * n]
+
+    def ed_batch_mul(self, base: bytes, scalars: bytes) -> bytes:
+        """out[i] = [s_i]B for one Edwards-BLS12 base: ed_batch_mul_multi with k = 1."""
+        return self.ed_batch_mul_multi(base, scalars)
+
+    def ed_mul_table_builds(self) -> int:
+        """Table slots the Edwards-BLS12 batch calls built on this engine so far (msm377_ed_ctx_get_mul_table_builds)."""
+        return int(self._lib.msm377_ed_ctx_get_mul_table_builds(self._ctx))
+
+    def ed_read_mul_table(self, index: int = 0, first: int = 0, count=None, info_only: bool = False):
+        """(MulTableInfo, records) of slot ``index`` of the Edwards-BLS12 batch calls (msm377_ed_read_mul_table): records
+        are 32 u32 each -- (y - x)[9], (y + x)[9], (2dxy)[9], 5 pad; the key is the 64 base bytes, then zeros.
+        MsmError(ESTATE) when the slot is not valid."""
+        import numpy as np
+
+        raw = _MulTableInfoStruct()
+        self._check(self._lib.msm377_ed_read_mul_table(self._ctx, int(index), ctypes.addressof(raw), 0, 0, None), "msm377_ed_read_mul_table")
+        info = MulTableInfo(int(raw.width), int(raw.rows), int(raw.records), bytes(raw.key))
+        if info_only:
+            return info, None
+        count = info.records - int(first) if count is None else int(count)
+        words = np.empty((count, MUL_TABLE_RECORD_WORDS), dtype=np.uint32)
+        self._check(self._lib.msm377_ed_read_mul_table(self._ctx, int(index), None, int(first), count, words.ctypes.data if count else None), "msm377_ed_read_mul_table")
+        return info, words
 
     # -- stage access (the reference's debug=true read-backs) --
     def set_stage_capture(self, mode=True):

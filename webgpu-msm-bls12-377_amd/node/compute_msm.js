@@ -149,6 +149,17 @@ const batch_mul_multi = (bases, scalars, { outForm = 'wire', layout = 'rows' } =
   return addon.batchMulMultiSync(pointsToBuffer(bases), scalarsToBuffer(scalars), BATCH_MUL_FORMS[outForm], BATCH_MUL_LAYOUTS[layout]);
 };
 
+// Edwards-BLS12 batch multiplication (msm377_ed_batch_mul_multi): out[i] = sum_j [s_ij]B_j over k <= 16 fixed bases of the
+// Edwards curve, every output its own point (addresses [sk_i]G, commitments [m_i]G + [r_i]H).  `bases`: a Buffer of 64-byte
+// wire records x || y; `scalars`: the k x n matrix as one flat list or Buffer in layout 'rows' (default) or 'columns'.
+// Returns a Buffer of n 64-byte records; the identity is (0, 1).  Every curve point is a legal base; a base off the curve
+// is refused.  ed_batch_mul is the k = 1 call.
+const ed_batch_mul_multi = (bases, scalars, { layout = 'rows' } = {}) => {
+  if (!(layout in BATCH_MUL_LAYOUTS)) throw new RangeError('layout: rows | columns');
+  return addon.edBatchMulMultiSync(bases, scalarsToBuffer(scalars), BATCH_MUL_LAYOUTS[layout]);
+};
+const ed_batch_mul = (base, scalars) => ed_batch_mul_multi(base, scalars);
+
 // Row commitments (msm377_g1_set_generators / msm377_g1_commit_rows): out[i] = sum_j [s_ij]G_j over a RESIDENT set of up to
 // 4 096 generators (Pedersen vector commitments).  set_generators(gens, {windowBits}) builds and keeps the window tables --
 // `gens`: {x, y} points or a Buffer of 96-byte wire records; windowBits 0 (= 8), 8, or 16 for up to 64 generators; an empty
@@ -161,4 +172,4 @@ const commit_rows = (scalars, k, { outForm = 'wire', layout = 'rows' } = {}) => 
   return addon.commitRowsSync(scalarsToBuffer(scalars), k, BATCH_MUL_FORMS[outForm], BATCH_MUL_LAYOUTS[layout]);
 };
 
-module.exports = { batch_lincomb2, batch_mul, batch_mul_multi, commit_rows, set_generators, batch_mul_var, compute_msm, compute_msm_edwards, set_bases, compute_msm_fixed_base, check_points, CHECK_CANONICAL, CHECK_CURVE, CHECK_SUBGROUP, CHECK_ALL, pointsToBuffer, scalarsToBuffer, version: addon.version };
+module.exports = { batch_lincomb2, batch_mul, batch_mul_multi, ed_batch_mul, ed_batch_mul_multi, commit_rows, set_generators, batch_mul_var, compute_msm, compute_msm_edwards, set_bases, compute_msm_fixed_base, check_points, CHECK_CANONICAL, CHECK_CURVE, CHECK_SUBGROUP, CHECK_ALL, pointsToBuffer, scalarsToBuffer, version: addon.version };

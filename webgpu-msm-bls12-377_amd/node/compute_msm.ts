@@ -240,6 +240,23 @@ export const batch_mul_multi = (
   return addon.batchMulMultiSync(pointsToBuffer(bases), scalarsToBuffer(scalars), BATCH_MUL_FORMS[outForm], BATCH_MUL_LAYOUTS[layout]);
 };
 
+// Edwards-BLS12 batch multiplication (msm377_ed_batch_mul_multi): out[i] = sum_j [s_ij]B_j over k <= 16 fixed bases of the
+// Edwards curve, every output its own 64-byte wire point x || y (the identity is (0, 1)).  `bases`: a Buffer of 64-byte wire
+// records; `scalars`: the k x n matrix as one flat list or Buffer in layout 'rows' (default) or 'columns'.  ed_batch_mul is
+// the k = 1 call.
+export const ed_batch_mul_multi = (
+  bases: Buffer,
+  scalars: bigint[] | Uint32Array[] | Buffer,
+  { layout = 'rows' }: { layout?: keyof typeof BATCH_MUL_LAYOUTS } = {},
+): Buffer => {
+  if (!(layout in BATCH_MUL_LAYOUTS)) {
+    throw new RangeError('layout: rows | columns');
+  }
+  return addon.edBatchMulMultiSync(bases, scalarsToBuffer(scalars), BATCH_MUL_LAYOUTS[layout]);
+};
+
+export const ed_batch_mul = (base: Buffer, scalars: bigint[] | Uint32Array[] | Buffer): Buffer => ed_batch_mul_multi(base, scalars);
+
 // Row commitments (msm377_g1_set_generators / msm377_g1_commit_rows): out[i] = sum_j [s_ij]G_j over a RESIDENT set of up to
 // 4 096 generators.  set_generators builds and keeps the window tables (windowBits 0 = 8, 8, or 16 for up to 64
 // generators; an empty list drops the set); commit_rows runs over the first k generators, `scalars` the k x n matrix as one

@@ -26,6 +26,9 @@
 //   batchMulMultiSync(bases: Buffer 96k, scalars: Buffer 32kn, outForm: number, columns: number): {points, infinity}
 //                                                                      out[i] = sum_j [s_ij]B_j (msm377_g1_batch_mul_multi); the
 //                                                                      k x n scalars row-major, or column-major if columns != 0
+//   edBatchMulMultiSync(bases: Buffer 64k, scalars: Buffer 32kn, columns: number): Buffer 64n
+//                                                                      out[i] = sum_j [s_ij]B_j on Edwards-BLS12
+//                                                                      (msm377_ed_batch_mul_multi), 64-byte records x || y
 //   setGeneratorsSync(gens: Buffer 96k, windowBits: number): void       row commitments: build and keep the window tables of k
 //                                                                      generators (msm377_g1_set_generators); an empty Buffer
 //                                                                      drops the set
@@ -534,6 +537,50 @@ napi_value BatchMulMultiSync(napi_env env, napi_callback_info info) {
   return obj;
 }
 
+// edBatchMulMultiSync(bases, scalars, columns) -> Buffer: out[i] = sum_j [s_ij]B_j on Edwards-BLS12 over k = bases / 64 fixed
+// bases (msm377_ed_batch_mul_multi); scalars: the dense k x n matrix, row-major (columns = 0) or column-major; n records of
+// 64 bytes x || y, the identity as (0, 1)
+napi_value EdBatchMulMultiSync(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  bool bb = false, sb = false;
+  uint32_t columns = 0;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 3 || napi_is_buffer(env, argv[0], &bb) != napi_ok || !bb ||
+      napi_is_buffer(env, argv[1], &sb) != napi_ok || !sb || napi_get_value_uint32(env, argv[2], &columns) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "expected (bases: Buffer of 64 bytes per base, scalars: Buffer of 32 bytes per scalar, columns: number)");
+    return nullptr;
+  }
+  uint8_t *b, *s;
+  size_t bl, sl;
+  napi_get_buffer_info(env, argv[0], reinterpret_cast<void**>(&b), &bl);
+  napi_get_buffer_info(env, argv[1], reinterpret_cast<void**>(&s), &sl);
+  const uint32_t k = static_cast<uint32_t>(bl / 64);
+  if (bl % 64 != 0 || k < 1 || k > MSM377_MUL_MAX_BASES || sl % (32 * static_cast<size_t>(k)) != 0) {
+    napi_throw_range_error(env, nullptr, "bases must hold 1 to 16 points of 64 bytes, scalars 32 bytes per base and output");
+    return nullptr;
+  }
+  const uint64_t n = sl / (32 * static_cast<size_t>(k));
+  const uint64_t out_stride = columns ? 32 : 32 * static_cast<uint64_t>(k), base_stride = columns ? 32 * (n ? n : 1) : 32;
+  napi_value points;
+  void* pd = nullptr;
+  if (napi_create_buffer(env, n * 64, &pd, &points) != napi_ok) return nullptr;
+  std::string err;
+  int rc;
+  {
+    std::lock_guard<std::mutex> lock(g_mu);
+    rc = ensure_ctx(1, &err);  // any capacity: the call walks n in passes of its own
+    if (!rc) {
+      rc = msm377_ed_batch_mul_multi(g_ctx, b, k, s, n, out_stride, base_stride, static_cast<uint8_t*>(pd));
+      if (rc) err = std::string("msm377_ed_batch_mul_multi: ") + msm377_strerror(rc) + ": " + msm377_last_error(g_ctx);
+    }
+  }
+  if (rc) {
+    napi_throw_error(env, nullptr, err.c_str());
+    return nullptr;
+  }
+  return points;
+}
+
 // setGeneratorsSync(gens, windowBits): the resident generator set of commitRowsSync; an empty Buffer drops it
 napi_value SetGeneratorsSync(napi_env env, napi_callback_info info) {
   size_t argc = 2;
@@ -684,6 +731,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"batchMulVarSync", nullptr, BatchMulVarSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"batchLincomb2Sync", nullptr, BatchLincomb2Sync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"batchMulMultiSync", nullptr, BatchMulMultiSync, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"edBatchMulMultiSync", nullptr, EdBatchMulMultiSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"setGeneratorsSync", nullptr, SetGeneratorsSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"commitRowsSync", nullptr, CommitRowsSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"version", nullptr, Version, nullptr, nullptr, nullptr, napi_default, nullptr},
