@@ -107,6 +107,33 @@ def test_host_buffer_call(engine, bulk, out_form):
     assert engine.batch_lincomb2(b"", b"", b"", b"", out_form) == (b"", b"")
 
 
+@pytest.mark.parametrize("a_stride,b_stride", [(32, 0), (0, 32)])
+def test_host_buffer_call_past_one_piece(engine, a_stride, b_stride):
+    """n = 2^20 + 1: the host-buffer call works in pieces of 2^20 pairs, so its loop runs twice and the second piece is
+    ONE pair.  Records and flags are the device call's on the same inputs, byte for byte (the tests above pin the device
+    call to the oracle), on poisoned buffers: a piece that is not uploaded or downloaded shows.  One scalar array has a
+    scalar per pair, uploaded piece by piece; the other is the stride-0 scalar, uploaded once before the loop."""
+    import ctypes
+
+    import torch
+
+    n = (1 << 20) + 1
+    d_pq = torch.empty(96 * 2 * n, dtype=torch.uint8, device="cuda")
+    engine.generate_bases_device(0x1C0B2, 2 * n, d_pq.data_ptr())
+    pq = bytes(d_pq.cpu().numpy())
+    del d_pq
+    p, q = pq[: 96 * n], pq[96 * n :]
+    rng = np.random.default_rng(0x1C0B3)
+    a = rng.integers(0, 256, size=(n if a_stride else 1, 32), dtype=np.uint8).tobytes()
+    b = rng.integers(0, 256, size=(n if b_stride else 1, 32), dtype=np.uint8).tobytes()
+    out, inf = ctypes.create_string_buffer(b"\xee" * (96 * n), 96 * n), ctypes.create_string_buffer(b"\xee" * n, n)
+    rc = msm.load_library().msm377_g1_batch_lincomb2(engine._ctx, p, q, a, b, n, a_stride, b_stride, V.WIRE, ctypes.addressof(out), ctypes.addressof(inf))
+    assert rc == 0
+    wire, flags = run_device(engine, p, q, a, b, a_stride=a_stride, b_stride=b_stride)
+    assert inf.raw == flags == bytes(n)
+    assert out.raw == wire
+
+
 # ---- 2. a pass boundary, past the context's capacity: every output enters one MSM with a random weight ----
 def test_pass_boundary_past_the_context_capacity(engine, oracle):
     """n = 2^16 + 3 on an engine created for 2^12 points: two passes, the second of three outputs."""

@@ -107,6 +107,34 @@ def test_host_buffer_call(engine, g_reference, out_form, width):
         assert engine.batch_mul(G_BYTES, b"", out_form) == (b"", b"")
 
 
+def test_host_buffer_call_past_one_piece():
+    """n = 2^20 + 1: the host-buffer call works in pieces of 2^20 outputs, so its loop runs twice and the second piece is
+    ONE output.  Records and flags are the device call's on the same inputs, byte for byte (the tests above pin the device
+    call to the oracle), on poisoned buffers: a piece that is not downloaded shows.  One width for the whole call: the
+    rule gives n the wide table where a piece of one output alone would take the narrow one, and a fresh engine builds
+    ONE table.  Then mont_flag records with no flag array."""
+    n = (1 << 20) + 1
+    s = np.random.default_rng(0x9BEC3).integers(0, 256, size=(n, 32), dtype=np.uint8)
+    s[3] = 0
+    s[(1 << 20) - 1] = 0  # identity outputs: one early, one at the end of the first piece
+    sb = s.tobytes()
+    base = V.base_bytes(R.mul(R.G, 0x9BEC3))
+    lib = msm.load_library()
+    with msm.MsmEngine(1 << 10) as fresh:
+        out, inf = ctypes.create_string_buffer(b"\xee" * (96 * n), 96 * n), ctypes.create_string_buffer(b"\xee" * n, n)
+        assert lib.msm377_g1_batch_mul(fresh._ctx, base, sb, n, V.WIRE, ctypes.addressof(out), ctypes.addressof(inf)) == 0
+        assert fresh.last_mul_window() == 16 and fresh.mul_table_builds() == 1
+        wire, flags = run_device(fresh, base, sb)
+        assert fresh.last_mul_window() == 16 and fresh.mul_table_builds() == 1
+        assert inf.raw == flags and flags[3] == 1 and flags[(1 << 20) - 1] == 1 and flags[n - 1] == 0
+        assert out.raw == wire
+        del out, wire
+        out = ctypes.create_string_buffer(b"\xee" * (104 * n), 104 * n)
+        assert lib.msm377_g1_batch_mul(fresh._ctx, base, sb, n, V.MONT_FLAG, ctypes.addressof(out), None) == 0
+        assert fresh.mul_table_builds() == 1
+        assert out.raw == run_device(fresh, base, sb, "mont_flag", flags=False)[0]
+
+
 # ---- identity outputs: a zero in a product tree would wipe a block ----
 @pytest.mark.parametrize("width", V.WIDTHS)
 def test_identity_outputs_leave_their_neighbours_exact(engine, oracle, width):

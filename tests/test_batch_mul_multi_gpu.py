@@ -389,6 +389,35 @@ def test_host_buffer_call(engine, size_reference, layout, width):
         assert engine.last_mul_window() == width
 
 
+@pytest.mark.parametrize("layout", ["rows", "columns"])
+def test_host_buffer_call_past_one_piece(layout):
+    """k = 16, n = 65 537: the host-buffer call works in pieces of 2^20 / k = 65 536 rows, so its loop runs twice and the
+    second piece is ONE row.  Records and flags are the device call's on the same inputs, byte for byte (the tests above
+    pin the device call), on poisoned buffers: a piece that is not repacked, uploaded or downloaded shows.  One width
+    for the whole call: the width a device call of n rows picks, and 16 builds on a fresh engine -- a second width for the
+    second piece would build 16 more."""
+    k, n = 16, 65537
+    bases = MV.bases_bytes([R.mul(R.G, 0xB16B00 + j) for j in range(k)])
+    s = np.random.default_rng(0x16B45E5).integers(0, 256, size=(n, k, 32), dtype=np.uint8)
+    s[7] = 0
+    s[65535] = 0  # identity outputs: one early, one in the last row of the first piece
+    if layout == "rows":
+        buf, out_stride, base_stride = s.tobytes(), 32 * k, 32
+    else:
+        buf, out_stride, base_stride = np.ascontiguousarray(s.transpose(1, 0, 2)).tobytes(), 32, 32 * n
+    out, inf = ctypes.create_string_buffer(b"\xee" * (96 * n), 96 * n), ctypes.create_string_buffer(b"\xee" * n, n)
+    with msm.MsmEngine(1 << 10) as fresh:
+        rc = msm.load_library().msm377_g1_batch_mul_multi(fresh._ctx, bases, k, buf, n, out_stride, base_stride, V.WIRE, ctypes.addressof(out), ctypes.addressof(inf))
+        assert rc == 0
+        host_width = fresh.last_mul_window()
+        assert fresh.mul_multi_table_builds() == 16 and fresh.mul_table_builds() == 0
+        wire, flags = run_device(fresh, bases, buf, n, out_stride, base_stride)
+        assert fresh.last_mul_window() == host_width
+        assert fresh.mul_multi_table_builds() == 16
+    assert inf.raw == flags and flags[7] == 1 and flags[65535] == 1 and flags[n - 1] == 0
+    assert out.raw == wire
+
+
 # ---- arguments ----
 def test_arguments(engine):
     import torch

@@ -101,6 +101,34 @@ def test_host_buffer_call(engine, bulk, out_form):
     assert engine.batch_mul_var(b"", b"", out_form) == (b"", b"")
 
 
+@pytest.mark.parametrize("scalar_stride", [32, 0])
+def test_host_buffer_call_past_one_piece(engine, scalar_stride):
+    """n = 2^20 + 1: the host-buffer call works in pieces of 2^20 points, so its loop runs twice and the second piece is
+    ONE point.  Records and flags are the device call's on the same inputs, byte for byte (the tests above pin the device
+    call to the oracle), on poisoned buffers: a piece that is not uploaded or downloaded shows.  With stride 0 the one
+    scalar is uploaded once, before the loop, and serves both pieces."""
+    import torch
+
+    n = (1 << 20) + 1
+    d_p = torch.empty(96 * n, dtype=torch.uint8, device="cuda")
+    engine.generate_bases_device(0x9A5507, n, d_p.data_ptr())
+    points = bytes(d_p.cpu().numpy())
+    del d_p
+    s = np.random.default_rng(0x9A5508).integers(0, 256, size=(n if scalar_stride else 1, 32), dtype=np.uint8)
+    if scalar_stride:
+        s[3] = 0
+        s[(1 << 20) - 1] = 0  # identity outputs: one early, one at the end of the first piece
+    sb = s.tobytes()
+    out, inf = ctypes.create_string_buffer(b"\xee" * (96 * n), 96 * n), ctypes.create_string_buffer(b"\xee" * n, n)
+    rc = msm.load_library().msm377_g1_batch_mul_var(engine._ctx, points, sb, n, scalar_stride, V.WIRE, ctypes.addressof(out), ctypes.addressof(inf))
+    assert rc == 0
+    wire, flags = run_device(engine, points, sb, stride=scalar_stride)
+    assert inf.raw == flags and flags[n - 1] == 0
+    if scalar_stride:
+        assert flags[3] == 1 and flags[(1 << 20) - 1] == 1
+    assert out.raw == wire
+
+
 # ---- exceptional points, mixed within waves ----
 @pytest.fixture(scope="module")
 def exceptional():

@@ -406,3 +406,29 @@ def test_host_buffer_call(engine):
             assert lib.msm377_g1_commit_rows(engine._ctx, data, n, k, out_stride, base_stride, V.WIRE, ctypes.addressof(out), ctypes.addressof(inf)) == 0
             assert (out.raw, inf.raw) == exp, layout
         assert engine.commit_rows(b"", k) == (b"", b"")
+
+
+@pytest.mark.parametrize("layout", ["rows", "columns"])
+def test_host_buffer_call_past_one_piece(engine, layout):
+    """k = 4 096 (the set of test_4096_generators), n = 257: the host-buffer call works in pieces of 2^20 / k = 256 rows, so
+    its loop runs twice and the second piece is ONE row.  Records and flags are the device call's on the same inputs,
+    byte for byte (the tests above pin the device call), on poisoned buffers: a piece that is not repacked, uploaded or
+    downloaded shows.  Dense full-width scalars; two all-zero rows."""
+    import ctypes
+
+    k, n = CR.GEN_MAX, 257
+    _, gens = CR.known_logs(k)
+    s = np.random.default_rng(0xC0441715).integers(0, 256, size=(n, k, 32), dtype=np.uint8)
+    s[7] = 0
+    s[255] = 0  # identity outputs: one early, one in the last row of the first piece
+    if layout == "rows":
+        buf, out_stride, base_stride = s.tobytes(), 32 * k, 32
+    else:
+        buf, out_stride, base_stride = np.ascontiguousarray(s.transpose(1, 0, 2)).tobytes(), 32, 32 * n
+    out, inf = ctypes.create_string_buffer(b"\xee" * (96 * n), 96 * n), ctypes.create_string_buffer(b"\xee" * n, n)
+    with generators(engine, gens):
+        rc = msm.load_library().msm377_g1_commit_rows(engine._ctx, buf, n, k, out_stride, base_stride, V.WIRE, ctypes.addressof(out), ctypes.addressof(inf))
+        assert rc == 0
+        wire, flags = run_device(engine, buf, n, k, out_stride, base_stride)
+    assert inf.raw == flags and flags[7] == 1 and flags[255] == 1 and flags[n - 1] == 0
+    assert out.raw == wire

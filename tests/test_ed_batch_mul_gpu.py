@@ -425,6 +425,34 @@ def test_host_buffer_call(engine, size_reference, layout, width):
         assert engine.ed_batch_mul(bases[:64], EV.pack(one[:65])[0]) == wire1[: 64 * 65]
 
 
+@pytest.mark.parametrize("layout", ["rows", "columns"])
+def test_host_buffer_call_past_one_piece(layout):
+    """k = 16, n = 65 537: the host-buffer call works in pieces of 2^20 / k = 65 536 rows, so its loop runs twice and the
+    second piece is ONE row.  The records are the device call's on the same inputs, byte for byte (the tests above pin the
+    device call), on a poisoned buffer: a piece that is not repacked, uploaded or downloaded shows.  One width for the
+    whole call: the width a device call of n rows picks, and 16 builds on a fresh engine -- a second width for the second
+    piece would build 16 more."""
+    k, n = 16, 65537
+    bases = EV.bases_bytes([R.ed_mul(R.ED_G, 0xEDB16B00 + j) for j in range(k)])
+    s = np.random.default_rng(0xED16B45).integers(0, 256, size=(n, k, 32), dtype=np.uint8)
+    s[7] = 0
+    s[65535] = 0  # identity outputs: one early, one in the last row of the first piece
+    if layout == "rows":
+        buf, out_stride, base_stride = s.tobytes(), 32 * k, 32
+    else:
+        buf, out_stride, base_stride = np.ascontiguousarray(s.transpose(1, 0, 2)).tobytes(), 32, 32 * n
+    out = ctypes.create_string_buffer(b"\xee" * (64 * n), 64 * n)
+    with msm.MsmEngine(1 << 10) as fresh:
+        assert msm.load_library().msm377_ed_batch_mul_multi(fresh._ctx, bases, k, buf, n, out_stride, base_stride, ctypes.addressof(out)) == 0
+        host_width = fresh.last_mul_window()
+        assert fresh.ed_mul_table_builds() == 16 and fresh.mul_multi_table_builds() == 0 and fresh.mul_table_builds() == 0
+        wire = run_device(fresh, bases, buf, n, out_stride, base_stride)
+        assert fresh.last_mul_window() == host_width
+        assert fresh.ed_mul_table_builds() == 16
+    assert out.raw == wire
+    assert wire[64 * 7 : 64 * 8] == wire[64 * 65535 : 64 * 65536] == EV.IDENTITY_WIRE
+
+
 # ---- arguments ----
 def test_arguments(engine):
     import torch

@@ -34,9 +34,9 @@ def run():
 
 def report(folder):
     files = glob.glob(os.path.join(folder, "**", "*kernel_trace.csv"), recursive=True)
-    rows = [r for f in files for r in csv.DictReader(open(f)) if "k_bm_" in r["Kernel_Name"]]
+    rows = [r for f in files for r in csv.DictReader(open(f)) if "k_bm_" in r["Kernel_Name"] or "k_bmm_" in r["Kernel_Name"]]  # the build kernels are the multi-base call's
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    starts = [i for i, r in enumerate(rows) if "k_bm_row_bases" in r["Kernel_Name"]]
+    starts = [i for i, r in enumerate(rows) if "k_bmm_row_bases" in r["Kernel_Name"]]
     print("# one cold n = 1 call per width: the build's launches, then the call's own four; us under rocprofv3 --kernel-trace")
     for width, i in zip((8, 16), starts[1:]):
         j = starts[starts.index(i) + 1] if starts.index(i) + 1 < len(starts) else len(rows)

@@ -60,19 +60,27 @@ struct ResidentBases {
   }
 };
 
-// Fixed-base batch multiplication (msm377_g1_batch_mul*, kernels/batch_mul.hpp): the window table of ONE base, keyed by
-// the base's 96 wire bytes and the window width, and the fixed-size scratch a chunk of outputs passes through.  Like the
-// resident base table the window table is valid only from the successful end of a build: a build clears `valid` first
-// and sets it as its last step.  Nothing here is shared with the MSM paths or the check calls.
+// One window table the batch calls keep between calls: the records, and the (base, width) they were built for.  The rule
+// is the resident base table's and it is written once, in the table builder (sequencer.hip build_mul_tables): a build
+// clears `valid` of every slot it rebuilds FIRST and sets it as its last step, behind a wait for its launches, so a
+// failed build leaves no table behind.  Each slot is its own allocation, made when it is first built and regrown for a
+// wider table.
+struct MulTableSlot {
+  bool valid = false;
+  uint8_t key[96] = {};    // the base's wire bytes: 96 on G1; 64 on Edwards-BLS12, the rest zero
+  int width = 0;           // window width of the table in `table`
+  uint32_t* table = nullptr;
+  uint64_t table_cap = 0;  // records allocated
+};
+
+// Fixed-base batch multiplication (msm377_g1_batch_mul*, kernels/batch_mul.hpp): the window table of ONE base and the
+// fixed-size scratch a chunk of outputs passes through, which every other batch call borrows.  Nothing here is shared
+// with the MSM paths or the check calls.
 struct BatchMulState {
   int window = 0;          // msm377_ctx_set_mul_window: 0 = the rule by n, else the forced width
   int last_window = 0;     // width the last call ran (msm377_ctx_get_last_mul_window)
   uint64_t builds = 0;     // table builds so far (msm377_ctx_get_mul_table_builds)
-  bool valid = false;
-  uint8_t base[96] = {};   // key: the base ...
-  int width = 0;           // ... and the width of the table in `table`
-  uint32_t* table = nullptr;        // records of the current table
-  uint64_t table_cap = 0;           // records allocated
+  MulTableSlot single;     // the table of the single-base call
   uint32_t* stash = nullptr;        // BM_PIECES x BM_CHUNK 16-byte pieces
   uint32_t* trees = nullptr;        // one product tree per workgroup of a chunk
   uint32_t* block_prod = nullptr;   // 13 limbs per workgroup: its product, then (block_inv) the inverse
@@ -87,39 +95,22 @@ struct BatchMulState {
 };
 
 // Multi-base batch multiplication (msm377_g1_batch_mul_multi*, kernels/batch_mul_multi.hpp): one window table per base
-// POSITION, each keyed like BatchMulState's by the base's 96 wire bytes and the width, each its own allocation (made when
-// the slot is first built, regrown for a wider table).  A build clears `valid` of every slot it rebuilds first and sets
-// it as its last step.  The stash, the trees and the block products are BatchMulState's; the forced width and the last
-// width are too (msm377_ctx_set_mul_window speaks for every batch_mul call).  Nothing else is shared with it: the
-// single-base table, its key and its build count are not touched from here.
+// POSITION.  The stash, the trees and the block products are BatchMulState's; the forced width and the last width are
+// too (msm377_ctx_set_mul_window speaks for every batch_mul call).  Nothing else is shared with it: the single-base
+// table, its key and its build count are not touched from here.
 struct BatchMulMultiState {
-  struct Slot {
-    bool valid = false;
-    uint8_t base[96] = {};
-    int width = 0;
-    uint32_t* table = nullptr;
-    uint64_t table_cap = 0;  // records allocated
-  };
-  Slot slot[MSM377_MUL_MAX_BASES];
+  MulTableSlot slot[MSM377_MUL_MAX_BASES];
   uint64_t builds = 0;              // slots built so far (msm377_ctx_get_mul_multi_table_builds)
   uint32_t* row_bases = nullptr;    // MSM377_MUL_MAX_BASES x (W + 1) table records: [2^(c w)]B_b of the slots being built
   uint32_t* bases_wire = nullptr;   // their 96 bytes each on the device
 };
 
 // Edwards-BLS12 batch multiplication (msm377_ed_batch_mul_multi*, kernels/ed_batch_mul.hpp): one window table per base
-// POSITION, keyed by the base's 64 wire bytes and the width, each its own allocation made when the slot is first built.
-// The rule is BatchMulMultiState's: a build clears `valid` of every slot it rebuilds first and sets it as its last step.
-// The stash, the trees, the block products, the build's row-base scratch and the forced / last width are the G1 batch
-// calls'; no G1 table, key or build count is read or written from here.
+// POSITION.  The stash, the trees, the block products, the build's row-base scratch (BatchMulMultiState's, used and
+// waited for inside a build only) and the forced / last width are the G1 batch calls'; no G1 table, key or build count
+// is read or written from here.
 struct EdBatchMulState {
-  struct Slot {
-    bool valid = false;
-    uint8_t base[64] = {};
-    int width = 0;
-    uint32_t* table = nullptr;
-    uint64_t table_cap = 0;  // records allocated
-  };
-  Slot slot[MSM377_MUL_MAX_BASES];
+  MulTableSlot slot[MSM377_MUL_MAX_BASES];
   uint64_t builds = 0;  // slots built so far (msm377_ed_ctx_get_mul_table_builds)
 };
 
@@ -127,7 +118,7 @@ struct EdBatchMulState {
 // kernels/commit_rows.hpp): the window tables of k generators at ONE width as ONE allocation, table j at record
 // j * bm_table_records(width).  The rule is ResidentBases': msm377_g1_set_generators drops the set (and gives its
 // memory back) before anything else and sets k as its last step, behind a wait for the build.  The build's own buffers
-// live for the length of the build.  The calls borrow BatchMulState's stash, trees and block products and nothing else:
+// (row bases and wire bytes sized for k) live for the length of the build.  The calls borrow BatchMulState's stash, trees and block products and nothing else:
 // no table, key, width or build count of the batch_mul calls is read or written from here.
 struct GeneratorSet {
   uint32_t k = 0;             // resident generators (0: no set)

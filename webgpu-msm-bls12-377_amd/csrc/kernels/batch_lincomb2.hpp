@@ -5,7 +5,7 @@
 // normalisation and table record.
 //
 //   k_bmv_table       launched twice per pass: [1..8]P_i into the stash at (e - 1) m + i, [1..8]Q_i at (8 + e - 1) m + i
-//                     (the second launch's stash pointer is 8 m pieces further on); ONE bm_normalise(BM_FORM_TABLE) over
+//                     (the second launch's stash pointer is 8 m pieces further on); ONE normalise<G1Mul>(BM_FORM_TABLE) over
 //                     the 16 m entries makes 128-byte affine records of both halves
 //   k_bl2_accumulate  THE HOT KERNEL: a thread per output walks the signed 4-bit digits of BOTH scalars from the top
 //                     (batch_mul_var_recode.hpp) and shares the doublings: acc = 16 acc + da_w P + db_w Q -- four doublings

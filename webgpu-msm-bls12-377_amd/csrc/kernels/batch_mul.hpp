@@ -2,15 +2,16 @@
 // its own affine point.  Nothing in the reference corresponds to this (it computes sums only); the counterpart in the
 // prover stacks is arkworks' FixedBase::msm / batch_mul.
 //
-//   k_bm_row_bases   thread w: [2^(c w)]B by c w doublings, w = 0 .. W (W = ceil(256 / c); row W is the carry's entry)
-//   k_bm_entries     thread (w, d): [d] of row base w by double-and-add, d = 1 .. 2^(c-1); plus the one entry of row W
+//   (the table)      row w, w = 0 .. W (W = ceil(256 / c); row W is the carry's entry), holds [d 2^(c w)]B, d = 1 .. 2^(c-1);
+//                    built by the one table builder of the batch calls (sequencer.hip build_mul_tables) with the build
+//                    kernels of kernels/batch_mul_multi.hpp, for one base
 //   k_bm_accumulate  THE HOT KERNEL: a thread per output walks the signed digits of its scalar (batch_mul_recode.hpp) from
 //                    the low end and adds one table record per non-zero digit
 //   k_bm_up / k_bm_across / k_bm_down   Montgomery's trick across the outputs of a chunk, entirely on the device: running
 //                    products per thread and a product tree per workgroup on the way up, ONE inversion per chunk in a
 //                    single-workgroup launch (a binary Euclid walk on one lane, fp_inverse.hpp), the trees walked down
 //                    and the affine records written on the way down
-// The two table kernels leave XYZZ points in the same stash the hot kernel writes, and the same three launches normalise
+// The build kernels leave XYZZ points in the same stash the hot kernel writes, and the same three launches normalise
 // them into table records: the table is built with the machinery it serves.  Grid-wide dependencies are launch
 // boundaries on one stream; no kernel waits for another workgroup.
 //
@@ -87,41 +88,7 @@ __device__ __forceinline__ G1XYZZ bm_tidy(const G1XYZZ& p) {
 }
 
 // ---- table build ----
-// Thread w <= W: [2^(c w)]B.  256 dependent doublings for the last row, on one wave, once per (base, width): the longest
-// launch of a build (profiles/batch_mul/build_trace.txt).
-__global__ void __launch_bounds__(64) k_bm_row_bases(const uint32_t* __restrict__ base_wire, uint32_t c, uint4* __restrict__ stash) {
-  const uint32_t w = threadIdx.x, W = (uint32_t)bm_windows((int)c);
-  if (w > W) return;
-  uint32_t raw[24];
-  load_words16(base_wire, raw, 6);
-  G1Affine b;
-  b.x = Fp::to_mont(Fp::from_words<12>(raw));
-  b.y = Fp::to_mont(Fp::from_words<12>(raw + 12));
-  G1XYZZ acc = G1::from_affine(b);
-#pragma unroll 1
-  for (uint32_t k = 0; k < c * w; k++) acc = G1::dbl(acc);  // O stays O; Y = 0 (order 2) gives ZZ = 0
-  bm_store_point(stash, w, bm_tidy(acc));
-}
-
-// Thread t < W 2^(c-1) + 1: entry d = (t mod 2^(c-1)) + 1 of row w = t / 2^(c-1); t = W 2^(c-1) is entry 1 of row W.
-// One workgroup per CU: G1::dbl and G1::madd side by side in one loop want more than the 256 registers that two would leave
-// (182 of them spilled); the kernel runs once per build.
-__global__ void __launch_bounds__(BM_THREADS) k_bm_entries(const uint32_t* __restrict__ row_bases, uint32_t c, uint4* __restrict__ stash) {
-  const uint64_t t = (uint64_t)blockIdx.x * BM_THREADS + threadIdx.x;
-  if (t >= bm_table_records(c)) return;
-  const uint32_t w = (uint32_t)(t >> (c - 1)), d = ((uint32_t)t & ((1u << (c - 1)) - 1u)) + 1u;
-  G1Affine q;
-  const bool finite = bm_load_record(row_bases, w, q);
-  G1XYZZ acc = G1::identity();
-  if (finite) {
-#pragma unroll 1
-    for (int bit = 31 - __clz((int)d); bit >= 0; bit--) {
-      acc = G1::dbl(acc);
-      if ((d >> bit) & 1u) acc = G1::madd(acc, q);  // identity, equal and opposite points handled inside
-    }
-  }
-  bm_store_point(stash, t, bm_tidy(acc));
-}
+// k_bmm_row_bases and k_bmm_entries (kernels/batch_mul_multi.hpp): the one table of this call is a build of one base.
 
 // ---- the hot kernel ----
 // 4 x 13 accumulator limbs, the 2 x 13 of a record and madd's temporaries in registers, two workgroups per CU: the

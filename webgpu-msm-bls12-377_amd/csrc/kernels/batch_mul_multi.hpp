@@ -3,6 +3,8 @@
 // ElGamal ciphertext, a hiding SRS).  The window tables, the signed recode, the mixed addition and the normalisation are
 // those of kernels/batch_mul.hpp; new here:
 //
+// These two are the build kernels of EVERY G1 window table -- the single-base table (one base), these slots, the generator
+// set of the row commitments -- under the one table builder of sequencer.hip (build_mul_tables):
 //   k_bmm_row_bases   workgroup b, thread w: [2^(c w)]B_b for every base a build is missing, ONE launch -- the 256
 //                     dependent doublings of the last row are paid once per build, not once per base
 //   k_bmm_entries     thread (b, w, d) over the concatenated records of the missing tables, cut into passes of at most
@@ -27,7 +29,9 @@ struct BmmTables {
 };
 
 // ---- table build, every missing slot at once ----
-// bases_wire: 96 bytes per missing base; row base w of base b goes to stash index b (W + 1) + w.
+// bases_wire: 96 bytes per missing base; row base w of base b goes to stash index b (W + 1) + w.  Thread w <= W: 256
+// dependent doublings for the last row, on one wave, once per build: the longest launch of a build
+// (profiles/batch_mul/build_trace.txt).
 __global__ void __launch_bounds__(64) k_bmm_row_bases(const uint32_t* __restrict__ bases_wire, uint32_t c, uint4* __restrict__ stash) {
   const uint32_t w = threadIdx.x, W = (uint32_t)bm_windows((int)c), b = blockIdx.x;
   if (w > W) return;
@@ -43,8 +47,9 @@ __global__ void __launch_bounds__(64) k_bmm_row_bases(const uint32_t* __restrict
 }
 
 // Record g = first + u of the concatenation, u < count <= BM_CHUNK: table b = g / records, entry t = g mod records of it
-// (t as in k_bm_entries), from the row bases of base b; the point goes to stash index u.  One workgroup per CU, as
-// k_bm_entries and for its reason.
+// (thread t < W 2^(c-1) + 1: entry d = (t mod 2^(c-1)) + 1 of row w = t / 2^(c-1); t = W 2^(c-1) is entry 1 of row W),
+// from the row bases of base b; the point goes to stash index u.  One workgroup per CU: G1::dbl and G1::madd side by side
+// in one loop want more than the 256 registers that two would leave (182 of them spilled); the kernel runs once per build.
 __global__ void __launch_bounds__(BM_THREADS) k_bmm_entries(const uint32_t* __restrict__ row_bases, uint32_t c, uint64_t first, uint64_t count, uint4* __restrict__ stash) {
   const uint64_t u = (uint64_t)blockIdx.x * BM_THREADS + threadIdx.x;
   if (u >= count) return;

@@ -4,7 +4,7 @@
 // normalisation (k_bm_up / k_bm_across / k_bm_down) and the table record.
 //
 //   k_bmv_table       a thread per point: the point from the context's point form, then [e]P_i, e = 1 .. 8, as XYZZ into
-//                     the stash at (e - 1) m + i (m: the points of this pass); bm_normalise(BM_FORM_TABLE) makes
+//                     the stash at (e - 1) m + i (m: the points of this pass); normalise<G1Mul>(BM_FORM_TABLE) makes
 //                     128-byte affine records of them
 //   k_bmv_accumulate  THE HOT KERNEL: a thread per output walks the 64 signed 4-bit digits of its scalar from the top
 //                     (batch_mul_var_recode.hpp): acc = carry ? P : O, then 64 steps acc = 16 acc + d_w P -- four
@@ -34,7 +34,7 @@ static_assert(BMV_PASS * BMV_ENTRIES == BM_CHUNK && BMV_PASS % BM_THREADS == 0, 
 // 8-byte loads; a flagged record's coordinate bytes are never interpreted).  The conversions are those of
 // kernels/import.hpp (one product with 2^22 takes v = x 2^384 to x) and kernels/convert.hpp (x -> the 2^406 limbs).
 // Runs once per point beside the 2 944 products of the walk: one doubling and six madd's.  Code object: 256 VGPRs, no
-// scratch, one workgroup per CU (dbl_affine and madd side by side, as in k_bm_entries); 0.17 ms per 2^17 points.
+// scratch, one workgroup per CU (dbl_affine and madd side by side, as in k_bmm_entries); 0.17 ms per 2^17 points.
 template <uint32_t POINT_FORM>
 __global__ void __launch_bounds__(BM_THREADS) k_bmv_table(const uint8_t* __restrict__ points, uint64_t m, uint4* __restrict__ stash) {
   const uint64_t i = (uint64_t)blockIdx.x * BM_THREADS + threadIdx.x;
@@ -86,7 +86,7 @@ __global__ void __launch_bounds__(BM_THREADS) k_bmv_table(const uint8_t* __restr
 // Code object (-Rpass-analysis=kernel-resource-usage, gfx950): 205 VGPRs, no VGPR spill, 2 waves per SIMD (two workgroups
 // per CU); 100 bytes of scratch per lane, the 25 accumulator limbs that k_bm_accumulate also keeps there across madd's four
 // exits -- the same figures as that kernel: G1::dbl in a rolled inner loop of four beside G1::madd did not overflow the
-// way k_bm_entries' pair did.
+// way k_bmm_entries' pair did.
 // Measured (profiles/batch_mul_var/sweep.txt): 5.90 ms per 2^17 outputs against 5.78 ms for k_check_subgroup's chain of
 // 2 948 products.
 __global__ void __launch_bounds__(BM_THREADS, 2) k_bmv_accumulate(const uint32_t* __restrict__ table, const uint32_t* __restrict__ scalars, uint64_t m, uint32_t stride_words,

@@ -1,7 +1,8 @@
 // Row commitments (msm377_g1_commit_rows*): out[i] = sum_{j<k} [s_ij]G_j over a resident set of up to MSM377_GEN_MAX
 // generators, every output its own affine point (Pedersen vector commitments).  The window tables, their two build
 // kernels, the signed recode, the mixed addition, the stash and the normalisation are those of kernels/batch_mul.hpp and
-// kernels/batch_mul_multi.hpp; the set is ONE allocation, table j at record j * bm_table_records(c).  New here:
+// kernels/batch_mul_multi.hpp; the set is ONE allocation, table j at record j * bm_table_records(c), which the one table
+// builder (sequencer.hip build_mul_tables) fills pass by pass, in place.  New here:
 //
 //   k_cr_accumulate   THE HOT KERNEL: grid (row blocks, S).  Thread (i, g) walks the tables of segment g of the plan
 //                     (commit_rows_plan.hpp: at most 16 generators) with the scalars of row i into one accumulator and

@@ -15,7 +15,8 @@
 //                      product tree per workgroup, ONE inversion per pass on one lane (fq_inverse.hpp), the trees walked
 //                      down, x = X / Z and y = Y / Z written as wire records or as table records
 // The two table kernels use the canonical Ed:: formulas (they run once per build) and leave extended points in the stash
-// the hot kernel writes; the same three launches normalise them into table records.  The completeness of the law on the
+// the hot kernel writes; the same three launches normalise them into table records.  The build itself is the one table
+// builder of the batch calls (sequencer.hip build_mul_tables) under this curve's policy, the slots the one slot type.  The completeness of the law on the
 // curve is what keeps every Z non-zero: the host verifies the bases (EdHostCheck) before anything is launched.
 // Stash, trees and block products are the G1 batch calls' (ctx->bm): 9 point pieces and 3 running-product pieces of their
 // 17, 9-limb nodes in their 13-limb trees.  Device code; included by sequencer.hip only, after kernels/batch_mul_multi.hpp.

@@ -31,6 +31,10 @@
 // every G1 MSM on base records that are in place, at full width or over short scalars, and the entry points are thin wrappers over one
 // flow per kind of input (g1_device_flow, g1_host_flow, g1_fixed_base_flow, ed_device_flow); the chunked uploads, the
 // batches and the window shards keep schedules of their own over the same steps.
+// The batch calls (every output its own point: fixed-base, multi-base, Edwards-BLS12, row commitments, variable-base,
+// pairwise) are not MSM paths and sit behind all of that, over one machinery of their own: one table builder, one
+// normalisation, one flow of a device call, one staging of a host-buffer call; an entry point supplies its checks, its
+// pass length and the launch of its hot kernel.
 #include "sequencer.hpp"
 
 #include <hip/hip_runtime.h>
@@ -1933,8 +1937,14 @@ int g1_glv_window_partials_device(msm377_ctx* ctx, const void* d_points, const v
   return MSM377_OK;
 }
 
-// ---- fixed-base batch multiplication (include/msm377.h "fixed-base batch multiplication"; kernels/batch_mul.hpp) ----
-// Everything runs on ctx->stream, launch after launch; the one host wait is the synchronisation at the end of the call.
+// ---- the batch calls (include/msm377.h: fixed-base, multi-base, Edwards-BLS12, row commitments, variable-base, pairwise) ----
+// Six entry points over one machinery:
+//   normalise          the stash -> affine records of a form, three launches, on either curve
+//   build_mul_tables   ONE table builder: row bases, then the concatenated records in passes of at most BM_CHUNK
+//   ensure_mul_tables  ONE keeper of the table slots: which (base, width) keys are missing, and when a slot is valid
+//   batch_device_call  ONE flow of a device call: the checks in their order, the scratch, the passes, the one host wait
+//   HostStage          ONE staging of a host-buffer call: the parts of a piece in one device allocation
+// Everything runs on ctx->stream, launch after launch; the one host wait of a warm call is the synchronisation at its end.
 namespace {
 
 // The scratch of one chunk: fixed sizes, whatever n and the context's capacity are.
@@ -1949,61 +1959,134 @@ int bm_ensure_scratch(msm377_ctx* ctx) {
   return rc;
 }
 
-// The m <= BM_CHUNK points the stash holds -> records of `form` at d_out: three launches.
-int bm_normalise(msm377_ctx* ctx, uint64_t m, uint32_t form, void* d_out, uint8_t* d_out_inf) {
+// What the normalisation, the builder and the pointer check need to know of a curve: the bytes of a base on the wire, the
+// build kernels, the normalisation kernels and the form of a table record.  The hot kernels are each call's own.
+struct G1Mul {
+  static constexpr size_t WIRE = 96;
+  static constexpr uint32_t FORM_TABLE = BM_FORM_TABLE;
+  static constexpr const char* MISALIGNED = "device pointers must be 16-byte aligned (8-byte for mont_flag records)";
+  static constexpr auto row_bases = k_bmm_row_bases;
+  static constexpr auto entries = k_bmm_entries;
+  static constexpr auto up = k_bm_up;
+  static constexpr auto across = k_bm_across;
+  static void down(hipStream_t s, uint32_t blocks, uint32_t form, const uint4* stash, uint64_t m, const uint32_t* trees, const uint32_t* inv, uint8_t* out, uint8_t* out_inf) {
+    const auto k = form == MSM377_POINTS_WIRE ? k_bm_down<MSM377_POINTS_WIRE> : form == MSM377_POINTS_MONT_FLAG ? k_bm_down<MSM377_POINTS_MONT_FLAG> : k_bm_down<BM_FORM_TABLE>;
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(BM_THREADS), 0, s, stash, m, trees, inv, out, out_inf);
+  }
+};
+struct EdMul {
+  static constexpr size_t WIRE = 64;
+  static constexpr uint32_t FORM_TABLE = EDBM_FORM_TABLE;
+  static constexpr const char* MISALIGNED = "device pointers must be 16-byte aligned";
+  static constexpr auto row_bases = k_edbm_row_bases;
+  static constexpr auto entries = k_edbm_entries;
+  static constexpr auto up = k_edbm_up;
+  static constexpr auto across = k_edbm_across;
+  static void down(hipStream_t s, uint32_t blocks, uint32_t form, const uint4* stash, uint64_t m, const uint32_t* trees, const uint32_t* inv, uint8_t* out, uint8_t*) {
+    const auto k = form == EDBM_FORM_WIRE ? k_edbm_down<EDBM_FORM_WIRE> : k_edbm_down<EDBM_FORM_TABLE>;  // no flag array: the identity is the record (0, 1)
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(BM_THREADS), 0, s, stash, m, trees, inv, out);
+  }
+};
+
+// The m <= BM_CHUNK points the stash holds -> records of `form` at d_out (G1: and their flags at d_out_inf): three launches.
+template <class MC>
+int normalise(msm377_ctx* ctx, uint64_t m, uint32_t form, void* d_out, uint8_t* d_out_inf) {
   BatchMulState& bm = ctx->bm;
   const uint32_t blocks = (uint32_t)((m + BM_BLOCK - 1) / BM_BLOCK);
   uint4* stash = reinterpret_cast<uint4*>(bm.stash);
-  hipLaunchKernelGGL(k_bm_up, dim3(blocks), dim3(BM_THREADS), 0, ctx->stream, stash, m, bm.trees, bm.block_prod);
-  hipLaunchKernelGGL(k_bm_across, dim3(1), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)bm.block_prod, blocks, bm.block_inv);
-  const dim3 grid(blocks), block(BM_THREADS);
-  if (form == MSM377_POINTS_WIRE)
-    hipLaunchKernelGGL(k_bm_down<MSM377_POINTS_WIRE>, grid, block, 0, ctx->stream, (const uint4*)stash, m, (const uint32_t*)bm.trees, (const uint32_t*)bm.block_inv, (uint8_t*)d_out, d_out_inf);
-  else if (form == MSM377_POINTS_MONT_FLAG)
-    hipLaunchKernelGGL(k_bm_down<MSM377_POINTS_MONT_FLAG>, grid, block, 0, ctx->stream, (const uint4*)stash, m, (const uint32_t*)bm.trees, (const uint32_t*)bm.block_inv, (uint8_t*)d_out, d_out_inf);
-  else
-    hipLaunchKernelGGL(k_bm_down<BM_FORM_TABLE>, grid, block, 0, ctx->stream, (const uint4*)stash, m, (const uint32_t*)bm.trees, (const uint32_t*)bm.block_inv, (uint8_t*)d_out, d_out_inf);
+  hipLaunchKernelGGL(MC::up, dim3(blocks), dim3(BM_THREADS), 0, ctx->stream, stash, m, bm.trees, bm.block_prod);
+  hipLaunchKernelGGL(MC::across, dim3(1), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)bm.block_prod, blocks, bm.block_inv);
+  MC::down(ctx->stream, blocks, form, stash, m, bm.trees, bm.block_inv, (uint8_t*)d_out, d_out_inf);
   HIP_TRY(ctx, hipGetLastError());
   return MSM377_OK;
 }
 
-// The window table of (base, c): kept until either key changes.  A build drops the old table FIRST and marks the new one
-// valid as its last step, behind a wait for its launches: a failed build leaves no table behind.
-int bm_ensure_table(msm377_ctx* ctx, const uint8_t base_xy[96], int c) {
-  BatchMulState& bm = ctx->bm;
-  if (bm.valid && bm.width == c && memcmp(bm.base, base_xy, 96) == 0) return MSM377_OK;
-  bm.valid = false;
-  const uint64_t records = bm_table_records((uint32_t)c);
-  if (bm.table_cap < records) {
-    ctx->own.release(bm.table);
-    bm.table = nullptr;
-    bm.table_cap = 0;
-    const int rc = bm_alloc(ctx, &bm.table, (size_t)records * BM_REC_WORDS * 4);
-    if (rc) return rc;
-    bm.table_cap = records;
+// A whole build of the window tables of m bases at width c, all of them side by side: the bases' wire bytes up, ONE
+// row-base launch (a workgroup per base: the 256 dependent doublings of the last row are paid once per build), then the
+// entries of the m tables as one run of records cut into passes of at most BM_CHUNK, wherever the cut falls.  A pass's
+// records go straight to their place in `into` where the tables are one allocation; else (`slots`: table b is
+// slots[b]->table, its own allocation) through a staging buffer -- the down kernel writes a pass as one run -- and from
+// there, piece by piece, into the tables the pass covers (device copies of at most 64 MB beside a 6 ms chain of
+// doublings).  row_bases and d_wire: device scratch for m x (W + 1) records and m bases.  Returns behind ONE wait for
+// all of it, the staging given back: the tables are there, or the call failed (rc, then the copy, then the wait).
+template <class MC>
+int build_mul_tables(msm377_ctx* ctx, const uint8_t* wire, uint32_t m, int c, uint32_t* row_bases, uint32_t* d_wire, uint32_t* into, MulTableSlot* const* slots) {
+  const uint64_t records = bm_table_records((uint32_t)c), rows = (uint64_t)bm_windows(c) + 1, total = records * m;
+  uint32_t* staging = nullptr;
+  int rc = into ? MSM377_OK : bm_alloc(ctx, &staging, (size_t)std::min<uint64_t>(total, BM_CHUNK) * BM_REC_WORDS * 4);
+  if (rc) return rc;
+  uint4* stash = reinterpret_cast<uint4*>(ctx->bm.stash);
+  hipError_t e = hipMemcpyAsync(d_wire, wire, (size_t)m * MC::WIRE, hipMemcpyHostToDevice, ctx->stream);  // (pageable memory: staged before the call returns)
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(MC::row_bases, dim3(m), dim3(64), 0, ctx->stream, (const uint32_t*)d_wire, (uint32_t)c, stash);
+    rc = normalise<MC>(ctx, rows * m, MC::FORM_TABLE, row_bases, nullptr);
   }
-  HIP_TRY(ctx, hipMemcpyAsync(bm.base_wire, base_xy, 96, hipMemcpyHostToDevice, ctx->stream));
-  uint4* stash = reinterpret_cast<uint4*>(bm.stash);
-  hipLaunchKernelGGL(k_bm_row_bases, dim3(1), dim3(64), 0, ctx->stream, (const uint32_t*)bm.base_wire, (uint32_t)c, stash);
-  int rc = bm_normalise(ctx, (uint64_t)bm_windows(c) + 1, BM_FORM_TABLE, bm.row_bases, nullptr);
+  for (uint64_t first = 0; first < total && !rc && e == hipSuccess; first += BM_CHUNK) {
+    const uint64_t count = std::min<uint64_t>(BM_CHUNK, total - first);
+    hipLaunchKernelGGL(MC::entries, dim3((unsigned)((count + BM_THREADS - 1) / BM_THREADS)), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)row_bases, (uint32_t)c, first, count, stash);
+    rc = normalise<MC>(ctx, count, MC::FORM_TABLE, into ? into + first * BM_REC_WORDS : staging, nullptr);
+    for (uint64_t g = first; !into && g < first + count && !rc && e == hipSuccess;) {  // the pieces of this pass, one per table it covers
+      const uint64_t b = g / records, t = g - b * records, len = std::min<uint64_t>(records - t, first + count - g);
+      e = hipMemcpyAsync(slots[b]->table + t * BM_REC_WORDS, staging + (g - first) * BM_REC_WORDS, (size_t)len * BM_REC_WORDS * 4, hipMemcpyDeviceToDevice, ctx->stream);
+      g += len;
+    }
+  }
+  const hipError_t waited = hipStreamSynchronize(ctx->stream);  // the wire bytes are the caller's; and the staging goes back
+  ctx->own.release(staging);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_bm_entries, dim3((unsigned)((records + BM_THREADS - 1) / BM_THREADS)), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)bm.row_bases, (uint32_t)c, stash);
-  rc = bm_normalise(ctx, records, BM_FORM_TABLE, bm.table, nullptr);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // the base bytes are the caller's; and a table is valid only once it is there
-  memcpy(bm.base, base_xy, 96);
-  bm.width = c;
-  bm.builds++;
-  bm.valid = true;
+  HIP_TRY(ctx, e);
+  HIP_TRY(ctx, waited);
   return MSM377_OK;
 }
 
-bool bm_base_canonical(const uint8_t base_xy[96]) {
-  uint64_t lim[2][6];
-  memcpy(lim, base_xy, 96);
-  return !Fp64::geq_p(lim[0]) && !Fp64::geq_p(lim[1]);
+// The window tables of (base j, c) in slot[j], j < k: a slot whose key is that stays; every other one is rebuilt, all of
+// them in ONE build.  A build drops the old tables FIRST and marks the new ones valid as its last step, behind the
+// build's wait: a failed build leaves no table behind.  contiguous: the one slot (k = 1) takes its records directly.
+template <class MC>
+int ensure_mul_tables(msm377_ctx* ctx, MulTableSlot* slot, const uint8_t* bases_xy, uint32_t k, int c, uint32_t* row_bases, uint32_t* d_wire, bool contiguous, uint64_t* builds) {
+  MulTableSlot* missing[MSM377_MUL_MAX_BASES];
+  uint8_t wire[MSM377_MUL_MAX_BASES * 96];
+  uint32_t m = 0;
+  for (uint32_t j = 0; j < k; j++) {
+    const uint8_t* base = bases_xy + (size_t)j * MC::WIRE;
+    if (slot[j].valid && slot[j].width == c && memcmp(slot[j].key, base, MC::WIRE) == 0) continue;
+    memcpy(wire + (size_t)m * MC::WIRE, base, MC::WIRE);
+    missing[m++] = &slot[j];
+  }
+  if (m == 0) return MSM377_OK;
+  for (uint32_t b = 0; b < m; b++) missing[b]->valid = false;
+  const uint64_t records = bm_table_records((uint32_t)c);
+  int rc = MSM377_OK;
+  for (uint32_t b = 0; b < m && !rc; b++) {
+    MulTableSlot& sl = *missing[b];
+    if (sl.table_cap >= records) continue;
+    ctx->own.release(sl.table);
+    sl.table = nullptr;
+    sl.table_cap = 0;
+    rc = bm_alloc(ctx, &sl.table, (size_t)records * BM_REC_WORDS * 4);
+    if (!rc) sl.table_cap = records;
+  }
+  if (!rc) rc = build_mul_tables<MC>(ctx, wire, m, c, row_bases, d_wire, contiguous ? missing[0]->table : nullptr, missing);
+  if (rc) return rc;
+  for (uint32_t b = 0; b < m; b++) {
+    memcpy(missing[b]->key, wire + (size_t)b * MC::WIRE, MC::WIRE);  // (the rest of a 64-byte key stays zero)
+    missing[b]->width = c;
+    missing[b]->valid = true;
+    ++*builds;
+  }
+  return MSM377_OK;
 }
 
+// The slots of the multi-base calls, G1 or Edwards-BLS12, over the row-base scratch the two share.
+template <class MC>
+int ensure_multi_tables(msm377_ctx* ctx, MulTableSlot* slot, const uint8_t* bases_xy, uint32_t k, int c, uint64_t* builds) {
+  BatchMulMultiState& mm = ctx->bmm;
+  int rc = bm_alloc(ctx, &mm.row_bases, (size_t)MSM377_MUL_MAX_BASES * (bm_windows(BM_MIN_WIDTH) + 1) * BM_REC_WORDS * 4);
+  if (!rc) rc = bm_alloc(ctx, &mm.bases_wire, (size_t)MSM377_MUL_MAX_BASES * 96);
+  return rc ? rc : ensure_mul_tables<MC>(ctx, slot, bases_xy, k, c, mm.row_bases, mm.bases_wire, false, builds);
+}
+
+// ---- argument checks: nothing is allocated, launched or changed before they pass ----
 int bm_check_form(msm377_ctx* ctx, uint32_t out_form) {
   if (!ctx) return MSM377_EINVAL;
   ctx->err.clear();
@@ -2012,89 +2095,10 @@ int bm_check_form(msm377_ctx* ctx, uint32_t out_form) {
   return MSM377_EINVAL;
 }
 
-}  // namespace
-
-int g1_batch_mul_device(msm377_ctx* ctx, const uint8_t base_xy[96], const void* d_scalars, uint64_t n, uint32_t out_form, void* d_out_points, uint8_t* d_out_inf) {
-  int rc = bm_check_form(ctx, out_form);
-  if (rc) return rc;
-  if (n == 0) return MSM377_OK;
-  if (!base_xy || !d_scalars || !d_out_points) {
-    ctx->err = "null pointer";
-    return MSM377_EINVAL;
-  }
-  const uintptr_t out_align = out_form == MSM377_POINTS_WIRE ? 15 : 7;
-  if (((uintptr_t)d_scalars & 15) || ((uintptr_t)d_out_points & out_align)) {
-    ctx->err = "device pointers must be 16-byte aligned (8-byte for mont_flag records)";
-    return MSM377_EINVAL;
-  }
-  if (!bm_base_canonical(base_xy)) {
-    ctx->err = "the base has a coordinate that is not below p";
-    return MSM377_EINVAL;
-  }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const int c = ctx->bm.window ? ctx->bm.window : batch_mul_rule(n);
-  rc = bm_ensure_scratch(ctx);
-  if (!rc) rc = bm_ensure_table(ctx, base_xy, c);
-  if (rc) {
-    (void)hipStreamSynchronize(ctx->stream);
-    return rc;
-  }
-  ctx->bm.last_window = c;
-  const size_t stride = out_form == MSM377_POINTS_WIRE ? 96 : 104;
-  for (uint64_t off = 0; off < n && !rc; off += BM_CHUNK) {
-    const uint64_t m = std::min<uint64_t>(BM_CHUNK, n - off);
-    hipLaunchKernelGGL(k_bm_accumulate, dim3((unsigned)((m + BM_THREADS - 1) / BM_THREADS)), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)ctx->bm.table,
-                       (const uint32_t*)d_scalars + off * 8, m, (uint32_t)c, ctx->scalar_form == MSM377_SCALARS_MONT ? 1u : 0u, reinterpret_cast<uint4*>(ctx->bm.stash));
-    rc = bm_normalise(ctx, m, out_form, (uint8_t*)d_out_points + off * stride, d_out_inf ? d_out_inf + off : nullptr);
-  }
-  const hipError_t e = hipStreamSynchronize(ctx->stream);
-  if (rc) return rc;
-  HIP_TRY(ctx, e);
-  return MSM377_OK;
-}
-
-// Host buffers: scalars up, records (and flags) down, a chunk's worth of device staging for the length of the call.
-int g1_batch_mul(msm377_ctx* ctx, const uint8_t base_xy[96], const uint8_t* scalars, uint64_t n, uint32_t out_form, uint8_t* out_points, uint8_t* out_inf) {
-  int rc = bm_check_form(ctx, out_form);
-  if (rc) return rc;
-  if (n == 0) return MSM377_OK;
-  if (!base_xy || !scalars || !out_points) {
-    ctx->err = "null pointer";
-    return MSM377_EINVAL;
-  }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t stride = out_form == MSM377_POINTS_WIRE ? 96 : 104;
-  const uint64_t piece = std::min<uint64_t>(n, BM_CHUNK);
-  uint8_t* d_io = nullptr;  // scalars, records, flags: 16-byte aligned parts
-  const size_t off_out = (size_t)piece * 32, off_inf = off_out + (((size_t)piece * stride + 15) & ~(size_t)15);
-  if (hipMalloc((void**)&d_io, off_inf + piece) != hipSuccess) {
-    (void)hipGetLastError();
-    ctx->err = "out of device memory for the batch multiplication staging";
-    return MSM377_ENOMEM;
-  }
-  const int forced = ctx->bm.window;
-  if (!forced) ctx->bm.window = batch_mul_rule(n);  // one width for the whole call, whatever the pieces' sizes
-  for (uint64_t off = 0; off < n && !rc; off += piece) {
-    const uint64_t m = std::min<uint64_t>(piece, n - off);
-    rc = hip_ok(ctx, hipMemcpy(d_io, scalars + off * 32, m * 32, hipMemcpyHostToDevice), "hipMemcpy(scalars)") ? MSM377_OK : MSM377_EHIP;
-    if (!rc) rc = g1_batch_mul_device(ctx, base_xy, d_io, m, out_form, d_io + off_out, d_io + off_inf);
-    if (!rc) rc = hip_ok(ctx, hipMemcpy(out_points + off * stride, d_io + off_out, m * stride, hipMemcpyDeviceToHost), "hipMemcpy(records)") ? MSM377_OK : MSM377_EHIP;
-    if (!rc && out_inf) rc = hip_ok(ctx, hipMemcpy(out_inf + off, d_io + off_inf, m, hipMemcpyDeviceToHost), "hipMemcpy(flags)") ? MSM377_OK : MSM377_EHIP;
-  }
-  ctx->bm.window = forced;
-  (void)hipFree(d_io);
-  return rc;
-}
-
-// ---- multi-base batch multiplication (include/msm377.h "multi-base batch multiplication"; kernels/batch_mul_multi.hpp) ----
-// Everything runs on ctx->stream, launch after launch, over the scratch of the single-base call; the one host wait of a
-// warm call is the synchronisation at its end.
-namespace {
-
-// Strides and k; a coordinate of p or more in any base.  Nothing is allocated, launched or changed before these pass.
-int bmm_check_shape(msm377_ctx* ctx, uint32_t k, uint64_t out_stride, uint64_t base_stride) {
-  if (k < 1 || k > MSM377_MUL_MAX_BASES) {
-    ctx->err = "k is 1 to MSM377_MUL_MAX_BASES bases";
+// k and the strides of a k x n scalar matrix.
+int check_shape(msm377_ctx* ctx, uint32_t k, uint32_t k_max, const char* message, uint64_t out_stride, uint64_t base_stride) {
+  if (k < 1 || k > k_max) {
+    ctx->err = message;
     return MSM377_EINVAL;
   }
   if (!out_stride || !base_stride || (out_stride & 31) || (base_stride & 31)) {
@@ -2102,6 +2106,35 @@ int bmm_check_shape(msm377_ctx* ctx, uint32_t k, uint64_t out_stride, uint64_t b
     return MSM377_EINVAL;
   }
   return MSM377_OK;
+}
+
+int null_pointer(msm377_ctx* ctx) {
+  ctx->err = "null pointer";
+  return MSM377_EINVAL;
+}
+
+// The pointers of a device call: none null (host: the bases, which live in host memory); scalars and records of 64 or 96
+// bytes 16-byte aligned, 104-byte records 8-byte aligned.
+template <class MC>
+int check_pointers(msm377_ctx* ctx, std::initializer_list<const void*> host, std::initializer_list<const void*> scalars, std::initializer_list<const void*> points, size_t in_stride,
+                   const void* out, size_t out_stride) {
+  const auto mask = [](size_t stride) { return (uintptr_t)(stride == 104 ? 7 : 15); };
+  bool null = !out, misaligned = ((uintptr_t)out & mask(out_stride)) != 0;
+  for (const void* h : host) null |= !h;
+  for (const void* s : scalars) null |= !s, misaligned |= ((uintptr_t)s & 15) != 0;
+  for (const void* p : points) null |= !p, misaligned |= ((uintptr_t)p & mask(in_stride)) != 0;
+  if (null) return null_pointer(ctx);
+  if (misaligned) {
+    ctx->err = MC::MISALIGNED;
+    return MSM377_EINVAL;
+  }
+  return MSM377_OK;
+}
+
+bool bm_base_canonical(const uint8_t base_xy[96]) {
+  uint64_t lim[2][6];
+  memcpy(lim, base_xy, 96);
+  return !Fp64::geq_p(lim[0]) && !Fp64::geq_p(lim[1]);
 }
 
 int bmm_check_bases(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k) {
@@ -2113,162 +2146,205 @@ int bmm_check_bases(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k) {
   return MSM377_OK;
 }
 
-// Slots j < k: those whose key is (base j, c) stay; every other one is rebuilt, all of them side by side -- ONE row-base
-// launch (a workgroup per missing base), then the entries of the missing tables as one run of records cut into passes
-// of at most BM_CHUNK, wherever the cut falls.  k_bm_down writes a pass as one run too, so a pass goes through a staging
-// buffer and from there, piece by piece, into the slots it covers (device copies of at most 64 MB beside a 6 ms chain
-// of doublings); the staging is given back at the end of the build.
-int bmm_ensure_tables(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k, int c) {
-  BatchMulMultiState& mm = ctx->bmm;
-  uint32_t missing[MSM377_MUL_MAX_BASES], m = 0;
-  for (uint32_t j = 0; j < k; j++) {
-    const BatchMulMultiState::Slot& sl = mm.slot[j];
-    if (!(sl.valid && sl.width == c && memcmp(sl.base, bases_xy + (size_t)j * 96, 96) == 0)) missing[m++] = j;
-  }
-  if (m == 0) return MSM377_OK;
-  for (uint32_t b = 0; b < m; b++) mm.slot[missing[b]].valid = false;
-  const uint64_t records = bm_table_records((uint32_t)c), rows = (uint64_t)bm_windows(c) + 1, total = records * m;
-  int rc = bm_alloc(ctx, &mm.row_bases, (size_t)MSM377_MUL_MAX_BASES * (bm_windows(BM_MIN_WIDTH) + 1) * BM_REC_WORDS * 4);
-  if (!rc) rc = bm_alloc(ctx, &mm.bases_wire, (size_t)MSM377_MUL_MAX_BASES * 96);
-  for (uint32_t b = 0; b < m && !rc; b++) {
-    BatchMulMultiState::Slot& sl = mm.slot[missing[b]];
-    if (sl.table_cap >= records) continue;
-    ctx->own.release(sl.table);
-    sl.table = nullptr;
-    sl.table_cap = 0;
-    rc = bm_alloc(ctx, &sl.table, (size_t)records * BM_REC_WORDS * 4);
-    if (!rc) sl.table_cap = records;
-  }
-  uint32_t* staging = nullptr;
-  if (!rc) rc = bm_alloc(ctx, &staging, (size_t)std::min<uint64_t>(total, BM_CHUNK) * BM_REC_WORDS * 4);
-  if (rc) return rc;
-  uint8_t wire[MSM377_MUL_MAX_BASES * 96];
-  for (uint32_t b = 0; b < m; b++) memcpy(wire + (size_t)b * 96, bases_xy + (size_t)missing[b] * 96, 96);
-  uint4* stash = reinterpret_cast<uint4*>(ctx->bm.stash);
-  hipError_t e = hipMemcpyAsync(mm.bases_wire, wire, (size_t)m * 96, hipMemcpyHostToDevice, ctx->stream);  // (pageable memory: staged before the call returns)
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_bmm_row_bases, dim3(m), dim3(64), 0, ctx->stream, (const uint32_t*)mm.bases_wire, (uint32_t)c, stash);
-    rc = bm_normalise(ctx, rows * m, BM_FORM_TABLE, mm.row_bases, nullptr);
-  }
-  for (uint64_t first = 0; first < total && !rc && e == hipSuccess; first += BM_CHUNK) {
-    const uint64_t count = std::min<uint64_t>(BM_CHUNK, total - first);
-    hipLaunchKernelGGL(k_bmm_entries, dim3((unsigned)((count + BM_THREADS - 1) / BM_THREADS)), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)mm.row_bases, (uint32_t)c, first,
-                       count, stash);
-    rc = bm_normalise(ctx, count, BM_FORM_TABLE, staging, nullptr);
-    for (uint64_t g = first; g < first + count && !rc && e == hipSuccess;) {  // the pieces of this pass, one per table it covers
-      const uint64_t b = g / records, t = g - b * records, len = std::min<uint64_t>(records - t, first + count - g);
-      e = hipMemcpyAsync(mm.slot[missing[b]].table + t * BM_REC_WORDS, staging + (g - first) * BM_REC_WORDS, (size_t)len * BM_REC_WORDS * 4, hipMemcpyDeviceToDevice, ctx->stream);
-      g += len;
-    }
-  }
-  const hipError_t waited = hipStreamSynchronize(ctx->stream);  // a table is valid only once it is there; and the staging goes back
-  ctx->own.release(staging);
-  if (rc) return rc;
-  HIP_TRY(ctx, e);
-  HIP_TRY(ctx, waited);
-  for (uint32_t b = 0; b < m; b++) {
-    BatchMulMultiState::Slot& sl = mm.slot[missing[b]];
-    memcpy(sl.base, bases_xy + (size_t)missing[b] * 96, 96);
-    sl.width = c;
-    sl.valid = true;
-    mm.builds++;
-  }
-  return MSM377_OK;
-}
+size_t point_stride(uint32_t form) { return form == MSM377_POINTS_MONT_FLAG ? 104 : 96; }
+uint32_t scalars_mont(const msm377_ctx* ctx) { return ctx->scalar_form == MSM377_SCALARS_MONT ? 1u : 0u; }
+dim3 bm_grid(uint64_t m) { return dim3((unsigned)((m + BM_THREADS - 1) / BM_THREADS)); }
 
-}  // namespace
-
-int g1_batch_mul_multi_device(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k, const void* d_scalars, uint64_t n, uint64_t out_stride, uint64_t base_stride, uint32_t out_form,
-                              void* d_out_points, uint8_t* d_out_inf) {
-  int rc = bm_check_form(ctx, out_form);
-  if (!rc) rc = bmm_check_shape(ctx, k, out_stride, base_stride);
-  if (rc) return rc;
-  if (n == 0) return MSM377_OK;
-  if (!bases_xy || !d_scalars || !d_out_points) {
-    ctx->err = "null pointer";
-    return MSM377_EINVAL;
-  }
-  const uintptr_t out_align = out_form == MSM377_POINTS_WIRE ? 15 : 7;
-  if (((uintptr_t)d_scalars & 15) || ((uintptr_t)d_out_points & out_align)) {
-    ctx->err = "device pointers must be 16-byte aligned (8-byte for mont_flag records)";
-    return MSM377_EINVAL;
-  }
-  rc = bmm_check_bases(ctx, bases_xy, k);
+// ---- the flow of a device call ----
+// early: the verdict of the form and shape checks, which come first and hold for n == 0 too; then n == 0 (nothing to do,
+// whatever the pointers); then check(): the pointers, and what is checked behind them (bases below p, a resident set).
+// Only then the device: the scratch, prepare() (the call's tables, its width), and the passes of at most pass_len outputs
+// -- pass(off, m) queues what leaves m points in the stash, the normalisation writes them as out_form records of
+// out_stride bytes (and flags) at output `off`.  ONE host wait at the end; a failure in the flow is reported before what
+// the wait says.
+template <class MC, class Check, class Prepare, class Pass>
+int batch_device_call(msm377_ctx* ctx, int early, uint64_t n, uint64_t pass_len, uint32_t out_form, void* d_out, size_t out_stride, uint8_t* d_out_inf, Check&& check, Prepare&& prepare,
+                      Pass&& pass) {
+  if (early || n == 0) return early;
+  int rc = check();
   if (rc) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const int c = ctx->bm.window ? ctx->bm.window : batch_mul_multi_rule(n, k);
   rc = bm_ensure_scratch(ctx);
-  if (!rc) rc = bmm_ensure_tables(ctx, bases_xy, k, c);
+  if (!rc) rc = prepare();
   if (rc) {
     (void)hipStreamSynchronize(ctx->stream);
     return rc;
   }
-  ctx->bm.last_window = c;
-  BmmTables tables = {};
-  for (uint32_t j = 0; j < k; j++) tables.t[j] = ctx->bmm.slot[j].table;
-  const size_t stride = out_form == MSM377_POINTS_WIRE ? 96 : 104;
-  for (uint64_t off = 0; off < n && !rc; off += BM_CHUNK) {
-    const uint64_t m = std::min<uint64_t>(BM_CHUNK, n - off);
-    // Row `off` of the CALL's layout: the strides are the call's, whatever the pass's length.
-    hipLaunchKernelGGL(k_bmm_accumulate, dim3((unsigned)((m + BM_THREADS - 1) / BM_THREADS)), dim3(BM_THREADS), 0, ctx->stream, tables, (const uint8_t*)d_scalars + off * out_stride, m, k,
-                       out_stride, base_stride, (uint32_t)c, ctx->scalar_form == MSM377_SCALARS_MONT ? 1u : 0u, reinterpret_cast<uint4*>(ctx->bm.stash));
-    rc = bm_normalise(ctx, m, out_form, (uint8_t*)d_out_points + off * stride, d_out_inf ? d_out_inf + off : nullptr);
+  for (uint64_t off = 0; off < n && !rc; off += pass_len) {
+    const uint64_t m = std::min<uint64_t>(pass_len, n - off);
+    rc = pass(off, m);
+    if (!rc) rc = normalise<MC>(ctx, m, out_form, (uint8_t*)d_out + off * out_stride, d_out_inf ? d_out_inf + off : nullptr);
   }
   const hipError_t e = hipStreamSynchronize(ctx->stream);
   if (rc) return rc;
   HIP_TRY(ctx, e);
   return MSM377_OK;
 }
+const auto nothing_to_prepare = [] { return MSM377_OK; };
+
+// ---- the staging of a host-buffer call ----
+// The parts of one piece -- the inputs in the caller's order, then the records, then the flags -- at 16-byte aligned
+// offsets of ONE device allocation that lives as long as this object.  rc: MSM377_ENOMEM (and ctx->err = oom) if there
+// is no memory for it.
+struct HostStage {
+  msm377_ctx* ctx;
+  uint8_t* d_io = nullptr;
+  std::vector<size_t> offset;
+  std::vector<uint8_t> rows;  // repack_rows' row-major copy of a piece
+  int rc = MSM377_OK;
+  HostStage(msm377_ctx* c, std::initializer_list<size_t> inputs, size_t record_bytes, size_t flag_bytes, const char* oom) : ctx(c) {
+    size_t total = 0;
+    const auto add = [&](size_t bytes) { offset.push_back(total), total += (bytes + 15) & ~(size_t)15; };
+    for (size_t bytes : inputs) add(bytes);
+    add(record_bytes), add(flag_bytes);
+    if (hipMalloc((void**)&d_io, total) == hipSuccess) return;
+    (void)hipGetLastError();
+    d_io = nullptr;
+    ctx->err = oom;
+    rc = MSM377_ENOMEM;
+  }
+  ~HostStage() { (void)hipFree(d_io); }
+  HostStage(const HostStage&) = delete;
+  uint8_t* part(size_t i) const { return d_io + offset[i]; }
+  uint8_t* records() const { return part(offset.size() - 2); }
+  uint8_t* flags() const { return part(offset.size() - 1); }
+  int copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, const char* what) const { return hip_ok(ctx, hipMemcpy(dst, src, bytes, kind), what) ? MSM377_OK : MSM377_EHIP; }
+  int up(size_t i, const uint8_t* src, size_t bytes, const char* what) const { return copy(part(i), src, bytes, hipMemcpyHostToDevice, what); }
+  int down_records(uint8_t* dst, size_t bytes) const { return copy(dst, records(), bytes, hipMemcpyDeviceToHost, "hipMemcpy(records)"); }
+  int down_flags(uint8_t* dst, size_t bytes) const { return copy(dst, flags(), bytes, hipMemcpyDeviceToHost, "hipMemcpy(flags)"); }
+  // The loop over pieces of at most `piece` outputs: load(off, m) uploads the inputs of outputs off .. off + m and runs the
+  // device call on them; their records of `stride` bytes and, where the caller wants them, their flags come down.
+  template <class Load>
+  int run(uint64_t n, uint64_t piece, uint8_t* out_points, size_t stride, uint8_t* out_inf, Load&& load) const {
+    int rc = MSM377_OK;
+    for (uint64_t off = 0; off < n && !rc; off += piece) {
+      const uint64_t m = std::min<uint64_t>(piece, n - off);
+      rc = load(off, m);
+      if (!rc) rc = down_records(out_points + off * stride, m * stride);
+      if (!rc && out_inf) rc = down_flags(out_inf + off, m);
+    }
+    return rc;
+  }
+  // Rows off .. off + m of the caller's k x n matrix (s_ij at scalars + i out_stride + j base_stride), row-major, into part i.
+  int repack_rows(size_t i, const uint8_t* scalars, uint64_t off, uint64_t m, uint32_t k, uint64_t out_stride, uint64_t base_stride) {
+    rows.resize((size_t)m * k * 32);
+    for (uint64_t r = 0; r < m; r++)
+      for (uint32_t j = 0; j < k; j++) memcpy(rows.data() + ((size_t)r * k + j) * 32, scalars + (off + r) * out_stride + (uint64_t)j * base_stride, 32);
+    return up(i, rows.data(), rows.size(), "hipMemcpy(scalars)");
+  }
+};
+
+// One width for the whole host-buffer call, whatever its pieces' sizes: the rule's value for the CALL's n stands in for a
+// width that nobody forced, and what was there comes back on every way out.
+struct OneWidth {
+  int& window;
+  const int forced;
+  OneWidth(msm377_ctx* ctx, int by_rule) : window(ctx->bm.window), forced(window) {
+    if (!forced) window = by_rule;
+  }
+  ~OneWidth() { window = forced; }
+};
+
+}  // namespace
+
+// ---- fixed-base batch multiplication (include/msm377.h "fixed-base batch multiplication"; kernels/batch_mul.hpp) ----
+int g1_batch_mul_device(msm377_ctx* ctx, const uint8_t base_xy[96], const void* d_scalars, uint64_t n, uint32_t out_form, void* d_out_points, uint8_t* d_out_inf) {
+  int c = 0;
+  const size_t stride = point_stride(out_form);
+  const auto check = [&]() -> int {
+    const int rc = check_pointers<G1Mul>(ctx, {base_xy}, {d_scalars}, {}, 96, d_out_points, stride);
+    if (rc || bm_base_canonical(base_xy)) return rc;
+    ctx->err = "the base has a coordinate that is not below p";
+    return MSM377_EINVAL;
+  };
+  const auto prepare = [&]() -> int {  // the table of (base, c): kept until either key changes
+    BatchMulState& bm = ctx->bm;
+    c = bm.window ? bm.window : batch_mul_rule(n);
+    const int rc = ensure_mul_tables<G1Mul>(ctx, &bm.single, base_xy, 1, c, bm.row_bases, bm.base_wire, true, &bm.builds);
+    if (!rc) bm.last_window = c;
+    return rc;
+  };
+  const auto pass = [&](uint64_t off, uint64_t m) -> int {
+    hipLaunchKernelGGL(k_bm_accumulate, bm_grid(m), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)ctx->bm.single.table, (const uint32_t*)d_scalars + off * 8, m, (uint32_t)c, scalars_mont(ctx),
+                       reinterpret_cast<uint4*>(ctx->bm.stash));
+    return MSM377_OK;
+  };
+  return batch_device_call<G1Mul>(ctx, bm_check_form(ctx, out_form), n, BM_CHUNK, out_form, d_out_points, stride, d_out_inf, check, prepare, pass);
+}
+
+// Host buffers: scalars up, records (and flags) down, in pieces of at most a chunk.
+int g1_batch_mul(msm377_ctx* ctx, const uint8_t base_xy[96], const uint8_t* scalars, uint64_t n, uint32_t out_form, uint8_t* out_points, uint8_t* out_inf) {
+  int rc = bm_check_form(ctx, out_form);
+  if (rc || n == 0) return rc;
+  if (!base_xy || !scalars || !out_points) return null_pointer(ctx);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t stride = point_stride(out_form);
+  const uint64_t piece = std::min<uint64_t>(n, BM_CHUNK);
+  HostStage io(ctx, {(size_t)piece * 32}, (size_t)piece * stride, piece, "out of device memory for the batch multiplication staging");
+  if (io.rc) return io.rc;
+  OneWidth width(ctx, batch_mul_rule(n));
+  return io.run(n, piece, out_points, stride, out_inf, [&](uint64_t off, uint64_t m) -> int {
+    const int up = io.up(0, scalars + off * 32, m * 32, "hipMemcpy(scalars)");
+    return up ? up : g1_batch_mul_device(ctx, base_xy, io.part(0), m, out_form, io.records(), io.flags());
+  });
+}
+
+// ---- multi-base batch multiplication (include/msm377.h "multi-base batch multiplication"; kernels/batch_mul_multi.hpp) ----
+int g1_batch_mul_multi_device(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k, const void* d_scalars, uint64_t n, uint64_t out_stride, uint64_t base_stride, uint32_t out_form,
+                              void* d_out_points, uint8_t* d_out_inf) {
+  int early = bm_check_form(ctx, out_form), c = 0;
+  if (!early) early = check_shape(ctx, k, MSM377_MUL_MAX_BASES, "k is 1 to MSM377_MUL_MAX_BASES bases", out_stride, base_stride);
+  BmmTables tables = {};
+  const size_t stride = point_stride(out_form);
+  const auto check = [&]() -> int {
+    const int rc = check_pointers<G1Mul>(ctx, {bases_xy}, {d_scalars}, {}, 96, d_out_points, stride);
+    return rc ? rc : bmm_check_bases(ctx, bases_xy, k);
+  };
+  const auto prepare = [&]() -> int {
+    c = ctx->bm.window ? ctx->bm.window : batch_mul_multi_rule(n, k);
+    const int rc = ensure_multi_tables<G1Mul>(ctx, ctx->bmm.slot, bases_xy, k, c, &ctx->bmm.builds);
+    if (rc) return rc;
+    ctx->bm.last_window = c;
+    for (uint32_t j = 0; j < k; j++) tables.t[j] = ctx->bmm.slot[j].table;
+    return MSM377_OK;
+  };
+  const auto pass = [&](uint64_t off, uint64_t m) -> int {  // row `off` of the CALL's layout: the strides are the call's, whatever the pass's length
+    hipLaunchKernelGGL(k_bmm_accumulate, bm_grid(m), dim3(BM_THREADS), 0, ctx->stream, tables, (const uint8_t*)d_scalars + off * out_stride, m, k, out_stride, base_stride, (uint32_t)c,
+                       scalars_mont(ctx), reinterpret_cast<uint4*>(ctx->bm.stash));
+    return MSM377_OK;
+  };
+  return batch_device_call<G1Mul>(ctx, early, n, BM_CHUNK, out_form, d_out_points, stride, d_out_inf, check, prepare, pass);
+}
 
 // Host buffers: each piece of at most 2^20 scalars (2^20 / k outputs) repacked row-major on the host, up, records (and
-// flags) down: the staging of the single-base call.  One width for the whole call, whatever the pieces' sizes.
+// flags) down.
 int g1_batch_mul_multi(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k, const uint8_t* scalars, uint64_t n, uint64_t out_stride, uint64_t base_stride, uint32_t out_form,
                        uint8_t* out_points, uint8_t* out_inf) {
   int rc = bm_check_form(ctx, out_form);
-  if (!rc) rc = bmm_check_shape(ctx, k, out_stride, base_stride);
-  if (rc) return rc;
-  if (n == 0) return MSM377_OK;
-  if (!bases_xy || !scalars || !out_points) {
-    ctx->err = "null pointer";
-    return MSM377_EINVAL;
-  }
+  if (!rc) rc = check_shape(ctx, k, MSM377_MUL_MAX_BASES, "k is 1 to MSM377_MUL_MAX_BASES bases", out_stride, base_stride);
+  if (rc || n == 0) return rc;
+  if (!bases_xy || !scalars || !out_points) return null_pointer(ctx);
   rc = bmm_check_bases(ctx, bases_xy, k);
   if (rc) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t stride = out_form == MSM377_POINTS_WIRE ? 96 : 104;
+  const size_t stride = point_stride(out_form);
   const uint64_t piece = std::min<uint64_t>(n, BM_CHUNK / k);
-  std::vector<uint8_t> rows((size_t)piece * k * 32);
-  uint8_t* d_io = nullptr;  // scalars, records, flags: 16-byte aligned parts
-  const size_t off_out = (size_t)piece * k * 32, off_inf = off_out + (((size_t)piece * stride + 15) & ~(size_t)15);
-  if (hipMalloc((void**)&d_io, off_inf + piece) != hipSuccess) {
-    (void)hipGetLastError();
-    ctx->err = "out of device memory for the batch multiplication staging";
-    return MSM377_ENOMEM;
-  }
-  const int forced = ctx->bm.window;
-  if (!forced) ctx->bm.window = batch_mul_multi_rule(n, k);
-  for (uint64_t off = 0; off < n && !rc; off += piece) {
-    const uint64_t m = std::min<uint64_t>(piece, n - off);
-    for (uint64_t i = 0; i < m; i++)
-      for (uint32_t j = 0; j < k; j++) memcpy(rows.data() + ((size_t)i * k + j) * 32, scalars + (off + i) * out_stride + (uint64_t)j * base_stride, 32);
-    rc = hip_ok(ctx, hipMemcpy(d_io, rows.data(), (size_t)m * k * 32, hipMemcpyHostToDevice), "hipMemcpy(scalars)") ? MSM377_OK : MSM377_EHIP;
-    if (!rc) rc = g1_batch_mul_multi_device(ctx, bases_xy, k, d_io, m, (uint64_t)k * 32, 32, out_form, d_io + off_out, d_io + off_inf);
-    if (!rc) rc = hip_ok(ctx, hipMemcpy(out_points + off * stride, d_io + off_out, m * stride, hipMemcpyDeviceToHost), "hipMemcpy(records)") ? MSM377_OK : MSM377_EHIP;
-    if (!rc && out_inf) rc = hip_ok(ctx, hipMemcpy(out_inf + off, d_io + off_inf, m, hipMemcpyDeviceToHost), "hipMemcpy(flags)") ? MSM377_OK : MSM377_EHIP;
-  }
-  ctx->bm.window = forced;
-  (void)hipFree(d_io);
-  return rc;
+  HostStage io(ctx, {(size_t)piece * k * 32}, (size_t)piece * stride, piece, "out of device memory for the batch multiplication staging");
+  if (io.rc) return io.rc;
+  OneWidth width(ctx, batch_mul_multi_rule(n, k));
+  return io.run(n, piece, out_points, stride, out_inf, [&](uint64_t off, uint64_t m) -> int {
+    const int up = io.repack_rows(0, scalars, off, m, k, out_stride, base_stride);
+    return up ? up : g1_batch_mul_multi_device(ctx, bases_xy, k, io.part(0), m, (uint64_t)k * 32, 32, out_form, io.records(), io.flags());
+  });
 }
 
 // ---- Edwards-BLS12 batch multiplication (include/msm377.h "Edwards-BLS12 batch multiplication"; kernels/ed_batch_mul.hpp) ----
-// The flow of the multi-base G1 call on ctx->stream over the same scratch; the tables are ctx->edbm's.
 namespace {
 
 int edbm_check_args(msm377_ctx* ctx, uint32_t k, uint64_t out_stride, uint64_t base_stride) {
   if (!ctx) return MSM377_EINVAL;
   ctx->err.clear();
-  return bmm_check_shape(ctx, k, out_stride, base_stride);
+  return check_shape(ctx, k, MSM377_MUL_MAX_BASES, "k is 1 to MSM377_MUL_MAX_BASES bases", out_stride, base_stride);
 }
 
 int edbm_check_bases(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k) {
@@ -2277,195 +2353,50 @@ int edbm_check_bases(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k) {
   return MSM377_EINVAL;
 }
 
-// The m <= BM_CHUNK points the stash holds -> wire records or table records at d_out: three launches.
-int edbm_normalise(msm377_ctx* ctx, uint64_t m, uint32_t form, void* d_out) {
-  BatchMulState& bm = ctx->bm;
-  const uint32_t blocks = (uint32_t)((m + BM_BLOCK - 1) / BM_BLOCK);
-  uint4* stash = reinterpret_cast<uint4*>(bm.stash);
-  hipLaunchKernelGGL(k_edbm_up, dim3(blocks), dim3(BM_THREADS), 0, ctx->stream, stash, m, bm.trees, bm.block_prod);
-  hipLaunchKernelGGL(k_edbm_across, dim3(1), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)bm.block_prod, blocks, bm.block_inv);
-  const dim3 grid(blocks), block(BM_THREADS);
-  if (form == EDBM_FORM_WIRE)
-    hipLaunchKernelGGL(k_edbm_down<EDBM_FORM_WIRE>, grid, block, 0, ctx->stream, (const uint4*)stash, m, (const uint32_t*)bm.trees, (const uint32_t*)bm.block_inv, (uint8_t*)d_out);
-  else
-    hipLaunchKernelGGL(k_edbm_down<EDBM_FORM_TABLE>, grid, block, 0, ctx->stream, (const uint4*)stash, m, (const uint32_t*)bm.trees, (const uint32_t*)bm.block_inv, (uint8_t*)d_out);
-  HIP_TRY(ctx, hipGetLastError());
-  return MSM377_OK;
-}
-
-// bmm_ensure_tables on ctx->edbm: slots j < k whose key is (base j, c) stay, every other one is rebuilt in ONE build.  The
-// row-base scratch is the G1 multi-base build's (used and waited for inside a build only).
-int edbm_ensure_tables(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k, int c) {
-  EdBatchMulState& em = ctx->edbm;
-  uint32_t missing[MSM377_MUL_MAX_BASES], m = 0;
-  for (uint32_t j = 0; j < k; j++) {
-    const EdBatchMulState::Slot& sl = em.slot[j];
-    if (!(sl.valid && sl.width == c && memcmp(sl.base, bases_xy + (size_t)j * 64, 64) == 0)) missing[m++] = j;
-  }
-  if (m == 0) return MSM377_OK;
-  for (uint32_t b = 0; b < m; b++) em.slot[missing[b]].valid = false;
-  const uint64_t records = bm_table_records((uint32_t)c), rows = (uint64_t)bm_windows(c) + 1, total = records * m;
-  int rc = bm_alloc(ctx, &ctx->bmm.row_bases, (size_t)MSM377_MUL_MAX_BASES * (bm_windows(BM_MIN_WIDTH) + 1) * BM_REC_WORDS * 4);
-  if (!rc) rc = bm_alloc(ctx, &ctx->bmm.bases_wire, (size_t)MSM377_MUL_MAX_BASES * 96);
-  for (uint32_t b = 0; b < m && !rc; b++) {
-    EdBatchMulState::Slot& sl = em.slot[missing[b]];
-    if (sl.table_cap >= records) continue;
-    ctx->own.release(sl.table);
-    sl.table = nullptr;
-    sl.table_cap = 0;
-    rc = bm_alloc(ctx, &sl.table, (size_t)records * BM_REC_WORDS * 4);
-    if (!rc) sl.table_cap = records;
-  }
-  uint32_t* staging = nullptr;
-  if (!rc) rc = bm_alloc(ctx, &staging, (size_t)std::min<uint64_t>(total, BM_CHUNK) * BM_REC_WORDS * 4);
-  if (rc) return rc;
-  uint8_t wire[MSM377_MUL_MAX_BASES * 64];
-  for (uint32_t b = 0; b < m; b++) memcpy(wire + (size_t)b * 64, bases_xy + (size_t)missing[b] * 64, 64);
-  uint4* stash = reinterpret_cast<uint4*>(ctx->bm.stash);
-  uint32_t* row_bases = ctx->bmm.row_bases;
-  hipError_t e = hipMemcpyAsync(ctx->bmm.bases_wire, wire, (size_t)m * 64, hipMemcpyHostToDevice, ctx->stream);  // (pageable memory: staged before the call returns)
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_edbm_row_bases, dim3(m), dim3(64), 0, ctx->stream, (const uint32_t*)ctx->bmm.bases_wire, (uint32_t)c, stash);
-    rc = edbm_normalise(ctx, rows * m, EDBM_FORM_TABLE, row_bases);
-  }
-  for (uint64_t first = 0; first < total && !rc && e == hipSuccess; first += BM_CHUNK) {
-    const uint64_t count = std::min<uint64_t>(BM_CHUNK, total - first);
-    hipLaunchKernelGGL(k_edbm_entries, dim3((unsigned)((count + BM_THREADS - 1) / BM_THREADS)), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)row_bases, (uint32_t)c, first, count,
-                       stash);
-    rc = edbm_normalise(ctx, count, EDBM_FORM_TABLE, staging);
-    for (uint64_t g = first; g < first + count && !rc && e == hipSuccess;) {  // the pieces of this pass, one per table it covers
-      const uint64_t b = g / records, t = g - b * records, len = std::min<uint64_t>(records - t, first + count - g);
-      e = hipMemcpyAsync(em.slot[missing[b]].table + t * BM_REC_WORDS, staging + (g - first) * BM_REC_WORDS, (size_t)len * BM_REC_WORDS * 4, hipMemcpyDeviceToDevice, ctx->stream);
-      g += len;
-    }
-  }
-  const hipError_t waited = hipStreamSynchronize(ctx->stream);  // a table is valid only once it is there; and the staging goes back
-  ctx->own.release(staging);
-  if (rc) return rc;
-  HIP_TRY(ctx, e);
-  HIP_TRY(ctx, waited);
-  for (uint32_t b = 0; b < m; b++) {
-    EdBatchMulState::Slot& sl = em.slot[missing[b]];
-    memcpy(sl.base, bases_xy + (size_t)missing[b] * 64, 64);
-    sl.width = c;
-    sl.valid = true;
-    em.builds++;
-  }
-  return MSM377_OK;
-}
-
 }  // namespace
 
 int ed_batch_mul_multi_device(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k, const void* d_scalars, uint64_t n, uint64_t out_stride, uint64_t base_stride, void* d_out_points) {
-  int rc = edbm_check_args(ctx, k, out_stride, base_stride);
-  if (rc) return rc;
-  if (n == 0) return MSM377_OK;
-  if (!bases_xy || !d_scalars || !d_out_points) {
-    ctx->err = "null pointer";
-    return MSM377_EINVAL;
-  }
-  if (((uintptr_t)d_scalars & 15) || ((uintptr_t)d_out_points & 15)) {
-    ctx->err = "device pointers must be 16-byte aligned";
-    return MSM377_EINVAL;
-  }
-  rc = edbm_check_bases(ctx, bases_xy, k);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const int c = ctx->bm.window ? ctx->bm.window : batch_mul_multi_rule(n, k);
-  rc = bm_ensure_scratch(ctx);
-  if (!rc) rc = edbm_ensure_tables(ctx, bases_xy, k, c);
-  if (rc) {
-    (void)hipStreamSynchronize(ctx->stream);
-    return rc;
-  }
-  ctx->bm.last_window = c;
+  int c = 0;
   EdbmTables tables = {};
-  for (uint32_t j = 0; j < k; j++) tables.t[j] = ctx->edbm.slot[j].table;
-  for (uint64_t off = 0; off < n && !rc; off += BM_CHUNK) {
-    const uint64_t m = std::min<uint64_t>(BM_CHUNK, n - off);
-    // Row `off` of the CALL's layout: the strides are the call's, whatever the pass's length.
-    hipLaunchKernelGGL(k_edbm_accumulate, dim3((unsigned)((m + BM_THREADS - 1) / BM_THREADS)), dim3(BM_THREADS), 0, ctx->stream, tables, (const uint8_t*)d_scalars + off * out_stride, m, k,
-                       out_stride, base_stride, (uint32_t)c, reinterpret_cast<uint4*>(ctx->bm.stash));
-    rc = edbm_normalise(ctx, m, EDBM_FORM_WIRE, (uint8_t*)d_out_points + off * 64);
-  }
-  const hipError_t e = hipStreamSynchronize(ctx->stream);
-  if (rc) return rc;
-  HIP_TRY(ctx, e);
-  return MSM377_OK;
+  const auto check = [&]() -> int {
+    const int rc = check_pointers<EdMul>(ctx, {bases_xy}, {d_scalars}, {}, 64, d_out_points, 64);
+    return rc ? rc : edbm_check_bases(ctx, bases_xy, k);
+  };
+  const auto prepare = [&]() -> int {
+    c = ctx->bm.window ? ctx->bm.window : batch_mul_multi_rule(n, k);
+    const int rc = ensure_multi_tables<EdMul>(ctx, ctx->edbm.slot, bases_xy, k, c, &ctx->edbm.builds);
+    if (rc) return rc;
+    ctx->bm.last_window = c;
+    for (uint32_t j = 0; j < k; j++) tables.t[j] = ctx->edbm.slot[j].table;
+    return MSM377_OK;
+  };
+  const auto pass = [&](uint64_t off, uint64_t m) -> int {  // row `off` of the CALL's layout, as on G1
+    hipLaunchKernelGGL(k_edbm_accumulate, bm_grid(m), dim3(BM_THREADS), 0, ctx->stream, tables, (const uint8_t*)d_scalars + off * out_stride, m, k, out_stride, base_stride, (uint32_t)c,
+                       reinterpret_cast<uint4*>(ctx->bm.stash));
+    return MSM377_OK;
+  };
+  return batch_device_call<EdMul>(ctx, edbm_check_args(ctx, k, out_stride, base_stride), n, BM_CHUNK, EDBM_FORM_WIRE, d_out_points, 64, nullptr, check, prepare, pass);
 }
 
-// Host buffers: each piece of at most 2^20 scalars repacked row-major on the host, up, records down.  One width for the
-// whole call, whatever the pieces' sizes.
+// Host buffers: each piece of at most 2^20 scalars repacked row-major on the host, up, records down.
 int ed_batch_mul_multi(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k, const uint8_t* scalars, uint64_t n, uint64_t out_stride, uint64_t base_stride, uint8_t* out_points) {
   int rc = edbm_check_args(ctx, k, out_stride, base_stride);
-  if (rc) return rc;
-  if (n == 0) return MSM377_OK;
-  if (!bases_xy || !scalars || !out_points) {
-    ctx->err = "null pointer";
-    return MSM377_EINVAL;
-  }
+  if (rc || n == 0) return rc;
+  if (!bases_xy || !scalars || !out_points) return null_pointer(ctx);
   rc = edbm_check_bases(ctx, bases_xy, k);
   if (rc) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const uint64_t piece = std::min<uint64_t>(n, BM_CHUNK / k);
-  std::vector<uint8_t> rows((size_t)piece * k * 32);
-  uint8_t* d_io = nullptr;  // scalars, then records: 16-byte aligned parts
-  const size_t off_out = (size_t)piece * k * 32;
-  if (hipMalloc((void**)&d_io, off_out + (size_t)piece * 64) != hipSuccess) {
-    (void)hipGetLastError();
-    ctx->err = "out of device memory for the batch multiplication staging";
-    return MSM377_ENOMEM;
-  }
-  const int forced = ctx->bm.window;
-  if (!forced) ctx->bm.window = batch_mul_multi_rule(n, k);
-  for (uint64_t off = 0; off < n && !rc; off += piece) {
-    const uint64_t m = std::min<uint64_t>(piece, n - off);
-    for (uint64_t i = 0; i < m; i++)
-      for (uint32_t j = 0; j < k; j++) memcpy(rows.data() + ((size_t)i * k + j) * 32, scalars + (off + i) * out_stride + (uint64_t)j * base_stride, 32);
-    rc = hip_ok(ctx, hipMemcpy(d_io, rows.data(), (size_t)m * k * 32, hipMemcpyHostToDevice), "hipMemcpy(scalars)") ? MSM377_OK : MSM377_EHIP;
-    if (!rc) rc = ed_batch_mul_multi_device(ctx, bases_xy, k, d_io, m, (uint64_t)k * 32, 32, d_io + off_out);
-    if (!rc) rc = hip_ok(ctx, hipMemcpy(out_points + off * 64, d_io + off_out, m * 64, hipMemcpyDeviceToHost), "hipMemcpy(records)") ? MSM377_OK : MSM377_EHIP;
-  }
-  ctx->bm.window = forced;
-  (void)hipFree(d_io);
-  return rc;
-}
-
-// msm377_ed_read_mul_table: slot `index` of ctx->edbm as it stands; the key is the 64 base bytes, then zeros.
-int ed_read_mul_table(msm377_ctx* ctx, uint32_t index, msm377_mul_table_info* info, uint64_t first, uint64_t count, uint32_t* words) {
-  if (!ctx) return MSM377_EINVAL;
-  ctx->err.clear();
-  if (index >= MSM377_MUL_MAX_BASES) {
-    ctx->err = "unknown window table";
-    return MSM377_EINVAL;
-  }
-  const EdBatchMulState::Slot& sl = ctx->edbm.slot[index];
-  if (!sl.valid) {
-    ctx->err = "that window table is not valid: never built, or left by a build that failed";
-    return MSM377_ESTATE;
-  }
-  const uint64_t records = bm_table_records((uint32_t)sl.width);
-  if (first > records || count > records - first || (count && !words)) {
-    ctx->err = "record range outside the table";
-    return MSM377_EINVAL;
-  }
-  if (info) {
-    memset(info, 0, sizeof *info);
-    info->width = (uint32_t)sl.width;
-    info->rows = (uint32_t)bm_windows(sl.width) + 1;
-    info->records = records;
-    memcpy(info->key, sl.base, 64);
-  }
-  if (words && count) {
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemcpy(words, sl.table + first * BM_REC_WORDS, (size_t)count * BM_REC_WORDS * 4, hipMemcpyDeviceToHost));
-  }
-  return MSM377_OK;
+  HostStage io(ctx, {(size_t)piece * k * 32}, (size_t)piece * 64, 0, "out of device memory for the batch multiplication staging");
+  if (io.rc) return io.rc;
+  OneWidth width(ctx, batch_mul_multi_rule(n, k));
+  return io.run(n, piece, out_points, 64, nullptr, [&](uint64_t off, uint64_t m) -> int {
+    const int up = io.repack_rows(0, scalars, off, m, k, out_stride, base_stride);
+    return up ? up : ed_batch_mul_multi_device(ctx, bases_xy, k, io.part(0), m, (uint64_t)k * 32, 32, io.records());
+  });
 }
 
 // ---- row commitments (include/msm377.h "row commitments"; kernels/commit_rows.hpp, commit_rows_plan.hpp) ----
-// The set is built with the build kernels of the multi-base call over buffers sized for k; a call runs on ctx->stream over
-// the scratch of the single-base call, and its one host wait is the synchronisation at its end.
 namespace {
 
 void cr_drop_set(msm377_ctx* ctx) {
@@ -2474,19 +2405,6 @@ void cr_drop_set(msm377_ctx* ctx) {
   gs.width = 0;
   ctx->own.release(gs.tables);
   gs.tables = nullptr;
-}
-
-// k, the strides, the pointers of a device call.  Nothing is allocated, launched or changed before these pass.
-int cr_check_shape(msm377_ctx* ctx, uint32_t k, uint64_t out_stride, uint64_t base_stride) {
-  if (k < 1 || k > MSM377_GEN_MAX) {
-    ctx->err = "k is 1 to MSM377_GEN_MAX generators";
-    return MSM377_EINVAL;
-  }
-  if (!out_stride || !base_stride || (out_stride & 31) || (base_stride & 31)) {
-    ctx->err = "out_stride and base_stride are byte counts: non-zero multiples of 32";
-    return MSM377_EINVAL;
-  }
-  return MSM377_OK;
 }
 
 int cr_check_set(msm377_ctx* ctx, uint32_t k) {
@@ -2501,40 +2419,10 @@ int cr_check_set(msm377_ctx* ctx, uint32_t k) {
   return MSM377_OK;
 }
 
-// The tables of k generators into gs.tables: ONE row-base launch for the whole set, then the concatenated records in
-// passes of at most BM_CHUNK, each normalised straight into its place (the set is one allocation: no staging, no copies).
-int cr_build_tables(msm377_ctx* ctx, const uint8_t* gens_xy, uint32_t k, int c, uint32_t* tables) {
-  const uint64_t records = bm_table_records((uint32_t)c), rows = (uint64_t)bm_windows(c) + 1, total = records * k;
-  static_assert((uint64_t)MSM377_GEN_MAX * (bm_windows(8) + 1) <= BM_CHUNK && (uint64_t)MSM377_GEN_WIDE_MAX * (bm_windows(16) + 1) <= BM_CHUNK, "the row bases of a set are normalised in one chunk");
-  uint32_t *row_bases = nullptr, *gens_wire = nullptr;
-  int rc = bm_alloc(ctx, &row_bases, (size_t)k * rows * BM_REC_WORDS * 4);
-  if (!rc) rc = bm_alloc(ctx, &gens_wire, (size_t)k * 96);
-  hipError_t e = hipSuccess;
-  if (!rc) {
-    uint4* stash = reinterpret_cast<uint4*>(ctx->bm.stash);
-    e = hipMemcpyAsync(gens_wire, gens_xy, (size_t)k * 96, hipMemcpyHostToDevice, ctx->stream);  // (pageable memory: staged before the call returns)
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(k_bmm_row_bases, dim3(k), dim3(64), 0, ctx->stream, (const uint32_t*)gens_wire, (uint32_t)c, stash);
-      rc = bm_normalise(ctx, rows * k, BM_FORM_TABLE, row_bases, nullptr);
-    }
-    for (uint64_t first = 0; first < total && !rc && e == hipSuccess; first += BM_CHUNK) {
-      const uint64_t count = std::min<uint64_t>(BM_CHUNK, total - first);
-      hipLaunchKernelGGL(k_bmm_entries, dim3((unsigned)((count + BM_THREADS - 1) / BM_THREADS)), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)row_bases, (uint32_t)c, first, count,
-                         stash);
-      rc = bm_normalise(ctx, count, BM_FORM_TABLE, tables + first * BM_REC_WORDS, nullptr);
-    }
-  }
-  const hipError_t waited = hipStreamSynchronize(ctx->stream);  // the set is valid only once it is there; and the build's buffers go back
-  ctx->own.release(row_bases);
-  ctx->own.release(gens_wire);
-  if (rc) return rc;
-  HIP_TRY(ctx, e);
-  HIP_TRY(ctx, waited);
-  return MSM377_OK;
-}
-
 }  // namespace
 
+// The set is ONE allocation, table j at record j * bm_table_records(c): the builder writes every pass straight to its
+// place, over row bases and wire bytes sized for k that live for the length of the build.
 int g1_set_generators(msm377_ctx* ctx, const uint8_t* gens_xy, uint32_t k, int window_bits) {
   if (!ctx) return MSM377_EINVAL;
   ctx->err.clear();
@@ -2555,10 +2443,16 @@ int g1_set_generators(msm377_ctx* ctx, const uint8_t* gens_xy, uint32_t k, int w
       ctx->err = "a generator has a coordinate that is not below p";
       return MSM377_EINVAL;
     }
+  static_assert((uint64_t)MSM377_GEN_MAX * (bm_windows(8) + 1) <= BM_CHUNK && (uint64_t)MSM377_GEN_WIDE_MAX * (bm_windows(16) + 1) <= BM_CHUNK, "the row bases of a set are normalised in one chunk");
   GeneratorSet& gs = ctx->gens;
+  uint32_t *row_bases = nullptr, *gens_wire = nullptr;
   int rc = bm_ensure_scratch(ctx);
   if (!rc) rc = bm_alloc(ctx, &gs.tables, (size_t)k * bm_table_records((uint32_t)c) * BM_REC_WORDS * 4);
-  if (!rc) rc = cr_build_tables(ctx, gens_xy, k, c, gs.tables);
+  if (!rc) rc = bm_alloc(ctx, &row_bases, (size_t)k * (bm_windows(c) + 1) * BM_REC_WORDS * 4);
+  if (!rc) rc = bm_alloc(ctx, &gens_wire, (size_t)k * 96);
+  if (!rc) rc = build_mul_tables<G1Mul>(ctx, gens_xy, k, c, row_bases, gens_wire, gs.tables, nullptr);
+  ctx->own.release(row_bases);  // (the build has waited for its launches)
+  ctx->own.release(gens_wire);
   if (rc) {
     cr_drop_set(ctx);
     return rc;
@@ -2570,89 +2464,52 @@ int g1_set_generators(msm377_ctx* ctx, const uint8_t* gens_xy, uint32_t k, int w
 
 int g1_commit_rows_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n, uint32_t k, uint64_t out_stride, uint64_t base_stride, uint32_t out_form, void* d_out_points,
                           uint8_t* d_out_inf) {
-  int rc = bm_check_form(ctx, out_form);
-  if (!rc) rc = cr_check_shape(ctx, k, out_stride, base_stride);
-  if (rc) return rc;
-  if (n == 0) return MSM377_OK;
-  if (!d_scalars || !d_out_points) {
-    ctx->err = "null pointer";
-    return MSM377_EINVAL;
-  }
-  const uintptr_t out_align = out_form == MSM377_POINTS_WIRE ? 15 : 7;
-  if (((uintptr_t)d_scalars & 15) || ((uintptr_t)d_out_points & out_align)) {
-    ctx->err = "device pointers must be 16-byte aligned (8-byte for mont_flag records)";
-    return MSM377_EINVAL;
-  }
-  rc = cr_check_set(ctx, k);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  rc = bm_ensure_scratch(ctx);
-  if (rc) return rc;
-  const GeneratorSet& gs = ctx->gens;
-  const CommitRowsPlan plan = commit_rows_plan(k);
-  const size_t stride = out_form == MSM377_POINTS_WIRE ? 96 : 104;
-  uint4* stash = reinterpret_cast<uint4*>(ctx->bm.stash);
-  for (uint64_t off = 0; off < n && !rc; off += plan.rows_per_pass) {
-    const uint64_t m = std::min<uint64_t>(plan.rows_per_pass, n - off);
-    const unsigned blocks = (unsigned)((m + BM_THREADS - 1) / BM_THREADS);
-    const uint64_t part_stride = (uint64_t)blocks * BM_THREADS;  // <= rows_per_pass, so segments * part_stride <= BM_CHUNK
-    // Row `off` of the CALL's layout: the strides are the call's, whatever the pass's length.
-    hipLaunchKernelGGL(k_cr_accumulate, dim3(blocks, plan.segments), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)gs.tables, (const uint8_t*)d_scalars + off * out_stride, m, k,
-                       plan.bases_per_segment, out_stride, base_stride, (uint32_t)gs.width, ctx->scalar_form == MSM377_SCALARS_MONT ? 1u : 0u, part_stride, stash);
-    if (plan.segments > 1) hipLaunchKernelGGL(k_cr_fold, dim3(blocks), dim3(BM_THREADS), 0, ctx->stream, stash, m, plan.segments, part_stride);
-    rc = bm_normalise(ctx, m, out_form, (uint8_t*)d_out_points + off * stride, d_out_inf ? d_out_inf + off : nullptr);
-  }
-  const hipError_t e = hipStreamSynchronize(ctx->stream);
-  if (rc) return rc;
-  HIP_TRY(ctx, e);
-  return MSM377_OK;
+  int early = bm_check_form(ctx, out_form);
+  if (!early) early = check_shape(ctx, k, MSM377_GEN_MAX, "k is 1 to MSM377_GEN_MAX generators", out_stride, base_stride);
+  const CommitRowsPlan plan = commit_rows_plan(early ? 1 : k);  // (a k that was refused is not planned for)
+  const size_t stride = point_stride(out_form);
+  const auto check = [&]() -> int {
+    const int rc = check_pointers<G1Mul>(ctx, {}, {d_scalars}, {}, 96, d_out_points, stride);
+    return rc ? rc : cr_check_set(ctx, k);
+  };
+  const auto pass = [&](uint64_t off, uint64_t m) -> int {  // row `off` of the CALL's layout: the strides are the call's, whatever the pass's length
+    const GeneratorSet& gs = ctx->gens;
+    uint4* stash = reinterpret_cast<uint4*>(ctx->bm.stash);
+    const dim3 grid = bm_grid(m);
+    const uint64_t part_stride = (uint64_t)grid.x * BM_THREADS;  // <= rows_per_pass, so segments * part_stride <= BM_CHUNK
+    hipLaunchKernelGGL(k_cr_accumulate, dim3(grid.x, plan.segments), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)gs.tables, (const uint8_t*)d_scalars + off * out_stride, m, k,
+                       plan.bases_per_segment, out_stride, base_stride, (uint32_t)gs.width, scalars_mont(ctx), part_stride, stash);
+    if (plan.segments > 1) hipLaunchKernelGGL(k_cr_fold, grid, dim3(BM_THREADS), 0, ctx->stream, stash, m, plan.segments, part_stride);
+    return MSM377_OK;
+  };
+  return batch_device_call<G1Mul>(ctx, early, n, plan.rows_per_pass, out_form, d_out_points, stride, d_out_inf, check, nothing_to_prepare, pass);
 }
 
 // Host buffers: each piece of at most 2^20 scalars (2^20 / k rows) repacked row-major on the host, up, records (and
-// flags) down: the staging of the multi-base call.
+// flags) down.
 int g1_commit_rows(msm377_ctx* ctx, const uint8_t* scalars, uint64_t n, uint32_t k, uint64_t out_stride, uint64_t base_stride, uint32_t out_form, uint8_t* out_points, uint8_t* out_inf) {
   int rc = bm_check_form(ctx, out_form);
-  if (!rc) rc = cr_check_shape(ctx, k, out_stride, base_stride);
-  if (rc) return rc;
-  if (n == 0) return MSM377_OK;
-  if (!scalars || !out_points) {
-    ctx->err = "null pointer";
-    return MSM377_EINVAL;
-  }
+  if (!rc) rc = check_shape(ctx, k, MSM377_GEN_MAX, "k is 1 to MSM377_GEN_MAX generators", out_stride, base_stride);
+  if (rc || n == 0) return rc;
+  if (!scalars || !out_points) return null_pointer(ctx);
   rc = cr_check_set(ctx, k);
   if (rc) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t stride = out_form == MSM377_POINTS_WIRE ? 96 : 104;
+  const size_t stride = point_stride(out_form);
   const uint64_t piece = std::min<uint64_t>(n, BM_CHUNK / k);
-  std::vector<uint8_t> rows((size_t)piece * k * 32);
-  uint8_t* d_io = nullptr;  // scalars, records, flags: 16-byte aligned parts
-  const size_t off_out = (size_t)piece * k * 32, off_inf = off_out + (((size_t)piece * stride + 15) & ~(size_t)15);
-  if (hipMalloc((void**)&d_io, off_inf + piece) != hipSuccess) {
-    (void)hipGetLastError();
-    ctx->err = "out of device memory for the row commitment staging";
-    return MSM377_ENOMEM;
-  }
-  for (uint64_t off = 0; off < n && !rc; off += piece) {
-    const uint64_t m = std::min<uint64_t>(piece, n - off);
-    for (uint64_t i = 0; i < m; i++)
-      for (uint32_t j = 0; j < k; j++) memcpy(rows.data() + ((size_t)i * k + j) * 32, scalars + (off + i) * out_stride + (uint64_t)j * base_stride, 32);
-    rc = hip_ok(ctx, hipMemcpy(d_io, rows.data(), (size_t)m * k * 32, hipMemcpyHostToDevice), "hipMemcpy(scalars)") ? MSM377_OK : MSM377_EHIP;
-    if (!rc) rc = g1_commit_rows_device(ctx, d_io, m, k, (uint64_t)k * 32, 32, out_form, d_io + off_out, d_io + off_inf);
-    if (!rc) rc = hip_ok(ctx, hipMemcpy(out_points + off * stride, d_io + off_out, m * stride, hipMemcpyDeviceToHost), "hipMemcpy(records)") ? MSM377_OK : MSM377_EHIP;
-    if (!rc && out_inf) rc = hip_ok(ctx, hipMemcpy(out_inf + off, d_io + off_inf, m, hipMemcpyDeviceToHost), "hipMemcpy(flags)") ? MSM377_OK : MSM377_EHIP;
-  }
-  (void)hipFree(d_io);
-  return rc;
+  HostStage io(ctx, {(size_t)piece * k * 32}, (size_t)piece * stride, piece, "out of device memory for the row commitment staging");
+  if (io.rc) return io.rc;
+  return io.run(n, piece, out_points, stride, out_inf, [&](uint64_t off, uint64_t m) -> int {
+    const int up = io.repack_rows(0, scalars, off, m, k, out_stride, base_stride);
+    return up ? up : g1_commit_rows_device(ctx, io.part(0), m, k, (uint64_t)k * 32, 32, out_form, io.records(), io.flags());
+  });
 }
 
 // ---- variable-base batch multiplication (include/msm377.h "variable-base batch multiplication"; kernels/batch_mul_var.hpp) ----
-// Per pass of BMV_PASS points: the per-point tables through the stash and the normalisation, then the walk and the
-// normalisation again, all on ctx->stream; the one host wait is the synchronisation at the end of the call.  A pass reads
-// its points before it writes its outputs, and passes cover disjoint index ranges: d_out_points == d_points is safe for
-// records of equal size.
+// Per pass of BMV_PASS points: the per-point tables through the stash and the normalisation, then the walk; the flow
+// normalises again.  A pass reads its points before it writes its outputs, and passes cover disjoint index ranges:
+// d_out_points == d_points is safe for records of equal size.
 namespace {
-
-size_t bmv_point_stride(uint32_t form) { return form == MSM377_POINTS_MONT_FLAG ? 104 : 96; }
 
 bool bmv_stride_ok(uint32_t scalar_stride) { return scalar_stride == 0 || scalar_stride == 32; }
 
@@ -2666,104 +2523,59 @@ int bmv_check_args(msm377_ctx* ctx, uint32_t scalar_stride, uint32_t out_form) {
   return MSM377_OK;
 }
 
-// The device pointers of a call: none null, scalars and 96-byte records 16-byte aligned, 104-byte records 8-byte aligned.
-int bmv_check_pointers(msm377_ctx* ctx, std::initializer_list<const void*> scalars, std::initializer_list<const void*> points, size_t in_stride, const void* out, size_t out_stride) {
-  bool null = !out, misaligned = ((uintptr_t)out & (out_stride == 96 ? 15 : 7)) != 0;
-  for (const void* s : scalars) null |= !s, misaligned |= ((uintptr_t)s & 15) != 0;
-  for (const void* p : points) null |= !p, misaligned |= ((uintptr_t)p & (in_stride == 96 ? 15 : 7)) != 0;
-  if (null) {
-    ctx->err = "null pointer";
-    return MSM377_EINVAL;
-  }
-  if (misaligned) {
-    ctx->err = "device pointers must be 16-byte aligned (8-byte for mont_flag records)";
-    return MSM377_EINVAL;
-  }
-  return MSM377_OK;
-}
+int bmv_ensure_table(msm377_ctx* ctx) { return bm_alloc(ctx, &ctx->bm.var_table, (size_t)BM_CHUNK * BM_REC_WORDS * 4); }
 
 // [1..8] of m points of `form` into the stash at (e - 1) m + i.
 void bmv_launch_table(msm377_ctx* ctx, uint32_t form, const uint8_t* pts, uint64_t m, uint4* stash) {
-  const dim3 grid((unsigned)((m + BM_THREADS - 1) / BM_THREADS)), block(BM_THREADS);
-  if (form == MSM377_POINTS_WIRE)
-    hipLaunchKernelGGL(k_bmv_table<MSM377_POINTS_WIRE>, grid, block, 0, ctx->stream, pts, m, stash);
-  else if (form == MSM377_POINTS_MONT)
-    hipLaunchKernelGGL(k_bmv_table<MSM377_POINTS_MONT>, grid, block, 0, ctx->stream, pts, m, stash);
-  else
-    hipLaunchKernelGGL(k_bmv_table<MSM377_POINTS_MONT_FLAG>, grid, block, 0, ctx->stream, pts, m, stash);
+  const auto k = form == MSM377_POINTS_WIRE ? k_bmv_table<MSM377_POINTS_WIRE> : form == MSM377_POINTS_MONT ? k_bmv_table<MSM377_POINTS_MONT> : k_bmv_table<MSM377_POINTS_MONT_FLAG>;
+  hipLaunchKernelGGL(k, bm_grid(m), dim3(BM_THREADS), 0, ctx->stream, pts, m, stash);
 }
 
 }  // namespace
 
 int g1_batch_mul_var_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t scalar_stride, uint32_t out_form, void* d_out_points,
                             uint8_t* d_out_inf) {
-  int rc = bmv_check_args(ctx, scalar_stride, out_form);
-  if (rc) return rc;
-  if (n == 0) return MSM377_OK;
-  const uint32_t form = ctx->point_form;
-  const size_t in_stride = bmv_point_stride(form), out_stride = bmv_point_stride(out_form);
-  rc = bmv_check_pointers(ctx, {d_scalars}, {d_points}, in_stride, d_out_points, out_stride);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  rc = bm_ensure_scratch(ctx);
-  if (!rc) rc = bm_alloc(ctx, &ctx->bm.var_table, (size_t)BM_CHUNK * BM_REC_WORDS * 4);
-  if (rc) return rc;
-  uint4* stash = reinterpret_cast<uint4*>(ctx->bm.stash);
-  const uint32_t* table = ctx->bm.var_table;
-  const uint32_t stride_words = scalar_stride / 4, scalars_mont = ctx->scalar_form == MSM377_SCALARS_MONT ? 1u : 0u;
-  for (uint64_t off = 0; off < n && !rc; off += BMV_PASS) {
-    const uint64_t m = std::min<uint64_t>(BMV_PASS, n - off);
-    const dim3 grid((unsigned)((m + BM_THREADS - 1) / BM_THREADS)), block(BM_THREADS);
+  const int early = bmv_check_args(ctx, scalar_stride, out_form);
+  const uint32_t form = early ? 0 : ctx->point_form, stride_words = scalar_stride / 4;
+  const size_t in_stride = point_stride(form), out_stride = point_stride(out_form);
+  const auto check = [&] { return check_pointers<G1Mul>(ctx, {}, {d_scalars}, {d_points}, in_stride, d_out_points, out_stride); };
+  const auto pass = [&](uint64_t off, uint64_t m) -> int {
+    uint4* stash = reinterpret_cast<uint4*>(ctx->bm.stash);
     bmv_launch_table(ctx, form, (const uint8_t*)d_points + off * in_stride, m, stash);
-    rc = bm_normalise(ctx, m * BMV_ENTRIES, BM_FORM_TABLE, ctx->bm.var_table, nullptr);
-    if (rc) break;
-    hipLaunchKernelGGL(k_bmv_accumulate, grid, block, 0, ctx->stream, table, (const uint32_t*)d_scalars + off * stride_words, m, stride_words, scalars_mont, stash);
-    rc = bm_normalise(ctx, m, out_form, (uint8_t*)d_out_points + off * out_stride, d_out_inf ? d_out_inf + off : nullptr);
-  }
-  const hipError_t e = hipStreamSynchronize(ctx->stream);
-  if (rc) return rc;
-  HIP_TRY(ctx, e);
-  return MSM377_OK;
+    const int rc = normalise<G1Mul>(ctx, m * BMV_ENTRIES, BM_FORM_TABLE, ctx->bm.var_table, nullptr);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_bmv_accumulate, bm_grid(m), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)ctx->bm.var_table, (const uint32_t*)d_scalars + off * stride_words, m, stride_words,
+                       scalars_mont(ctx), stash);
+    return MSM377_OK;
+  };
+  return batch_device_call<G1Mul>(ctx, early, n, BMV_PASS, out_form, d_out_points, out_stride, d_out_inf, check, [&] { return bmv_ensure_table(ctx); }, pass);
 }
 
-// Host buffers: points and scalars up, records (and flags) down, a chunk's worth of device staging for the length of the call.
+// Host buffers: points and scalars up, records (and flags) down, in pieces of at most a chunk.  A stride-0 scalar is
+// uploaded once.
 int g1_batch_mul_var(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint32_t scalar_stride, uint32_t out_form, uint8_t* out_points, uint8_t* out_inf) {
   int rc = bmv_check_args(ctx, scalar_stride, out_form);
-  if (rc) return rc;
-  if (n == 0) return MSM377_OK;
-  if (!points || !scalars || !out_points) {
-    ctx->err = "null pointer";
-    return MSM377_EINVAL;
-  }
+  if (rc || n == 0) return rc;
+  if (!points || !scalars || !out_points) return null_pointer(ctx);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t in_stride = bmv_point_stride(ctx->point_form), out_stride = bmv_point_stride(out_form);
+  const size_t in_stride = point_stride(ctx->point_form), out_stride = point_stride(out_form);
   const uint64_t piece = std::min<uint64_t>(n, BM_CHUNK);
-  const auto round16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-  uint8_t* d_io = nullptr;  // scalars, points, records, flags: 16-byte aligned parts
-  const size_t off_pts = (size_t)piece * 32, off_out = off_pts + round16((size_t)piece * in_stride), off_inf = off_out + round16((size_t)piece * out_stride);
-  if (hipMalloc((void**)&d_io, off_inf + piece) != hipSuccess) {
-    (void)hipGetLastError();
-    ctx->err = "out of device memory for the batch multiplication staging";
-    return MSM377_ENOMEM;
-  }
-  if (scalar_stride == 0) rc = hip_ok(ctx, hipMemcpy(d_io, scalars, 32, hipMemcpyHostToDevice), "hipMemcpy(scalar)") ? MSM377_OK : MSM377_EHIP;
-  for (uint64_t off = 0; off < n && !rc; off += piece) {
-    const uint64_t m = std::min<uint64_t>(piece, n - off);
-    if (scalar_stride) rc = hip_ok(ctx, hipMemcpy(d_io, scalars + off * 32, m * 32, hipMemcpyHostToDevice), "hipMemcpy(scalars)") ? MSM377_OK : MSM377_EHIP;
-    if (!rc) rc = hip_ok(ctx, hipMemcpy(d_io + off_pts, points + off * in_stride, m * in_stride, hipMemcpyHostToDevice), "hipMemcpy(points)") ? MSM377_OK : MSM377_EHIP;
-    if (!rc) rc = g1_batch_mul_var_device(ctx, d_io + off_pts, d_io, m, scalar_stride, out_form, d_io + off_out, d_io + off_inf);
-    if (!rc) rc = hip_ok(ctx, hipMemcpy(out_points + off * out_stride, d_io + off_out, m * out_stride, hipMemcpyDeviceToHost), "hipMemcpy(records)") ? MSM377_OK : MSM377_EHIP;
-    if (!rc && out_inf) rc = hip_ok(ctx, hipMemcpy(out_inf + off, d_io + off_inf, m, hipMemcpyDeviceToHost), "hipMemcpy(flags)") ? MSM377_OK : MSM377_EHIP;
-  }
-  (void)hipFree(d_io);
-  return rc;
+  HostStage io(ctx, {(size_t)piece * 32, (size_t)piece * in_stride}, (size_t)piece * out_stride, piece, "out of device memory for the batch multiplication staging");
+  if (io.rc) return io.rc;
+  if (scalar_stride == 0) rc = io.up(0, scalars, 32, "hipMemcpy(scalar)");
+  if (rc) return rc;
+  return io.run(n, piece, out_points, out_stride, out_inf, [&](uint64_t off, uint64_t m) -> int {
+    int up = scalar_stride ? io.up(0, scalars + off * 32, m * 32, "hipMemcpy(scalars)") : MSM377_OK;
+    if (!up) up = io.up(1, points + off * in_stride, m * in_stride, "hipMemcpy(points)");
+    return up ? up : g1_batch_mul_var_device(ctx, io.part(1), io.part(0), m, scalar_stride, out_form, io.records(), io.flags());
+  });
 }
 
 // ---- pairwise linear combination (include/msm377.h "pairwise linear combination"; kernels/batch_lincomb2.hpp) ----
-// Per pass of BL2_PASS pairs: both tables through the stash and ONE normalisation, then the joint walk and the
-// normalisation again, all on ctx->stream; the one host wait is the synchronisation at the end of the call.  A pass reads
-// all of its inputs before it writes its outputs, and passes cover disjoint index ranges: d_out_points == d_p or == d_q
-// is safe for records of equal size, and so is the fold in place (q = p + h records, out = p, n = h).
+// Per pass of BL2_PASS pairs: both tables through the stash and ONE normalisation, then the joint walk; the flow
+// normalises again.  A pass reads all of its inputs before it writes its outputs, and passes cover disjoint index
+// ranges: d_out_points == d_p or == d_q is safe for records of equal size, and so is the fold in place (q = p + h
+// records, out = p, n = h).
 namespace {
 
 int bl2_check_args(msm377_ctx* ctx, uint32_t a_stride, uint32_t b_stride, uint32_t out_form) {
@@ -2780,74 +2592,46 @@ int bl2_check_args(msm377_ctx* ctx, uint32_t a_stride, uint32_t b_stride, uint32
 
 int g1_batch_lincomb2_device(msm377_ctx* ctx, const void* d_p, const void* d_q, const void* d_a, const void* d_b, uint64_t n, uint32_t a_stride, uint32_t b_stride,
                              uint32_t out_form, void* d_out_points, uint8_t* d_out_inf) {
-  int rc = bl2_check_args(ctx, a_stride, b_stride, out_form);
-  if (rc) return rc;
-  if (n == 0) return MSM377_OK;
-  const uint32_t form = ctx->point_form;
-  const size_t in_stride = bmv_point_stride(form), out_stride = bmv_point_stride(out_form);
-  rc = bmv_check_pointers(ctx, {d_a, d_b}, {d_p, d_q}, in_stride, d_out_points, out_stride);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  rc = bm_ensure_scratch(ctx);
-  if (!rc) rc = bm_alloc(ctx, &ctx->bm.var_table, (size_t)BM_CHUNK * BM_REC_WORDS * 4);
-  if (rc) return rc;
-  uint4* stash = reinterpret_cast<uint4*>(ctx->bm.stash);
-  const uint32_t* table = ctx->bm.var_table;
-  const uint32_t a_words = a_stride / 4, b_words = b_stride / 4, scalars_mont = ctx->scalar_form == MSM377_SCALARS_MONT ? 1u : 0u;
-  for (uint64_t off = 0; off < n && !rc; off += BL2_PASS) {
-    const uint64_t m = std::min<uint64_t>(BL2_PASS, n - off);
+  const int early = bl2_check_args(ctx, a_stride, b_stride, out_form);
+  const uint32_t form = early ? 0 : ctx->point_form, a_words = a_stride / 4, b_words = b_stride / 4;
+  const size_t in_stride = point_stride(form), out_stride = point_stride(out_form);
+  const auto check = [&] { return check_pointers<G1Mul>(ctx, {}, {d_a, d_b}, {d_p, d_q}, in_stride, d_out_points, out_stride); };
+  const auto pass = [&](uint64_t off, uint64_t m) -> int {
+    uint4* stash = reinterpret_cast<uint4*>(ctx->bm.stash);
     bmv_launch_table(ctx, form, (const uint8_t*)d_p + off * in_stride, m, stash);
     bmv_launch_table(ctx, form, (const uint8_t*)d_q + off * in_stride, m, stash + BMV_ENTRIES * m);
-    rc = bm_normalise(ctx, m * BL2_TERMS * BMV_ENTRIES, BM_FORM_TABLE, ctx->bm.var_table, nullptr);
-    if (rc) break;
-    hipLaunchKernelGGL(k_bl2_accumulate, dim3((unsigned)((m + BM_THREADS - 1) / BM_THREADS)), dim3(BM_THREADS), 0, ctx->stream, table, (const uint32_t*)d_a + off * a_words,
-                       (const uint32_t*)d_b + off * b_words, m, a_words, b_words, scalars_mont, stash);
-    rc = bm_normalise(ctx, m, out_form, (uint8_t*)d_out_points + off * out_stride, d_out_inf ? d_out_inf + off : nullptr);
-  }
-  const hipError_t e = hipStreamSynchronize(ctx->stream);
-  if (rc) return rc;
-  HIP_TRY(ctx, e);
-  return MSM377_OK;
+    const int rc = normalise<G1Mul>(ctx, m * BL2_TERMS * BMV_ENTRIES, BM_FORM_TABLE, ctx->bm.var_table, nullptr);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_bl2_accumulate, bm_grid(m), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)ctx->bm.var_table, (const uint32_t*)d_a + off * a_words,
+                       (const uint32_t*)d_b + off * b_words, m, a_words, b_words, scalars_mont(ctx), stash);
+    return MSM377_OK;
+  };
+  return batch_device_call<G1Mul>(ctx, early, n, BL2_PASS, out_form, d_out_points, out_stride, d_out_inf, check, [&] { return bmv_ensure_table(ctx); }, pass);
 }
 
-// Host buffers: both scalar arrays and both point arrays up, records (and flags) down, a chunk's worth of device staging
-// for the length of the call.  A stride-0 scalar is uploaded once.
+// Host buffers: both scalar arrays and both point arrays up, records (and flags) down, in pieces of at most a chunk.  A
+// stride-0 scalar is uploaded once.
 int g1_batch_lincomb2(msm377_ctx* ctx, const uint8_t* p, const uint8_t* q, const uint8_t* a, const uint8_t* b, uint64_t n, uint32_t a_stride, uint32_t b_stride, uint32_t out_form,
                       uint8_t* out_points, uint8_t* out_inf) {
   int rc = bl2_check_args(ctx, a_stride, b_stride, out_form);
-  if (rc) return rc;
-  if (n == 0) return MSM377_OK;
-  if (!p || !q || !a || !b || !out_points) {
-    ctx->err = "null pointer";
-    return MSM377_EINVAL;
-  }
+  if (rc || n == 0) return rc;
+  if (!p || !q || !a || !b || !out_points) return null_pointer(ctx);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t in_stride = bmv_point_stride(ctx->point_form), out_stride = bmv_point_stride(out_form);
+  const size_t in_stride = point_stride(ctx->point_form), out_stride = point_stride(out_form);
   const uint64_t piece = std::min<uint64_t>(n, BM_CHUNK);
-  const auto round16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-  uint8_t* d_io = nullptr;  // a, b, p, q, records, flags: 16-byte aligned parts
-  const size_t off_b = (size_t)piece * 32, off_p = 2 * off_b, off_q = off_p + round16((size_t)piece * in_stride), off_out = off_q + round16((size_t)piece * in_stride),
-               off_inf = off_out + round16((size_t)piece * out_stride);
-  if (hipMalloc((void**)&d_io, off_inf + piece) != hipSuccess) {
-    (void)hipGetLastError();
-    ctx->err = "out of device memory for the linear combination staging";
-    return MSM377_ENOMEM;
-  }
-  const auto up = [&](size_t dst, const uint8_t* src, size_t bytes, const char* what) { return hip_ok(ctx, hipMemcpy(d_io + dst, src, bytes, hipMemcpyHostToDevice), what) ? MSM377_OK : MSM377_EHIP; };
-  if (a_stride == 0) rc = up(0, a, 32, "hipMemcpy(scalar a)");
-  if (!rc && b_stride == 0) rc = up(off_b, b, 32, "hipMemcpy(scalar b)");
-  for (uint64_t off = 0; off < n && !rc; off += piece) {
-    const uint64_t m = std::min<uint64_t>(piece, n - off);
-    if (a_stride) rc = up(0, a + off * 32, m * 32, "hipMemcpy(scalars a)");
-    if (!rc && b_stride) rc = up(off_b, b + off * 32, m * 32, "hipMemcpy(scalars b)");
-    if (!rc) rc = up(off_p, p + off * in_stride, m * in_stride, "hipMemcpy(points p)");
-    if (!rc) rc = up(off_q, q + off * in_stride, m * in_stride, "hipMemcpy(points q)");
-    if (!rc) rc = g1_batch_lincomb2_device(ctx, d_io + off_p, d_io + off_q, d_io, d_io + off_b, m, a_stride, b_stride, out_form, d_io + off_out, d_io + off_inf);
-    if (!rc) rc = hip_ok(ctx, hipMemcpy(out_points + off * out_stride, d_io + off_out, m * out_stride, hipMemcpyDeviceToHost), "hipMemcpy(records)") ? MSM377_OK : MSM377_EHIP;
-    if (!rc && out_inf) rc = hip_ok(ctx, hipMemcpy(out_inf + off, d_io + off_inf, m, hipMemcpyDeviceToHost), "hipMemcpy(flags)") ? MSM377_OK : MSM377_EHIP;
-  }
-  (void)hipFree(d_io);
-  return rc;
+  HostStage io(ctx, {(size_t)piece * 32, (size_t)piece * 32, (size_t)piece * in_stride, (size_t)piece * in_stride}, (size_t)piece * out_stride, piece,
+               "out of device memory for the linear combination staging");  // a, b, p, q
+  if (io.rc) return io.rc;
+  if (a_stride == 0) rc = io.up(0, a, 32, "hipMemcpy(scalar a)");
+  if (!rc && b_stride == 0) rc = io.up(1, b, 32, "hipMemcpy(scalar b)");
+  if (rc) return rc;
+  return io.run(n, piece, out_points, out_stride, out_inf, [&](uint64_t off, uint64_t m) -> int {
+    int up = a_stride ? io.up(0, a + off * 32, m * 32, "hipMemcpy(scalars a)") : MSM377_OK;
+    if (!up && b_stride) up = io.up(1, b + off * 32, m * 32, "hipMemcpy(scalars b)");
+    if (!up) up = io.up(2, p + off * in_stride, m * in_stride, "hipMemcpy(points p)");
+    if (!up) up = io.up(3, q + off * in_stride, m * in_stride, "hipMemcpy(points q)");
+    return up ? up : g1_batch_lincomb2_device(ctx, io.part(2), io.part(3), io.part(0), io.part(1), m, a_stride, b_stride, out_form, io.records(), io.flags());
+  });
 }
 
 int g1_generate_bases_device(msm377_ctx* ctx, uint64_t seed, uint64_t n, void* d_points_out) {
@@ -2860,27 +2644,12 @@ int g1_generate_bases_device(msm377_ctx* ctx, uint64_t seed, uint64_t n, void* d
   return MSM377_OK;
 }
 
-// msm377_g1_read_mul_table: a copy of records the batch calls keep between calls, and what the host knows about them.
-int g1_read_mul_table(msm377_ctx* ctx, uint32_t which, uint32_t index, msm377_mul_table_info* info, uint64_t first, uint64_t count, uint32_t* words) {
-  if (!ctx) return MSM377_EINVAL;
-  ctx->err.clear();
-  const uint32_t* table = nullptr;
-  const uint8_t* key = nullptr;
-  int c = 0;
-  if (which == MSM377_MUL_TABLE_SINGLE && index == 0 && ctx->bm.valid) {
-    table = ctx->bm.table, key = ctx->bm.base, c = ctx->bm.width;
-  } else if (which == MSM377_MUL_TABLE_MULTI && index < MSM377_MUL_MAX_BASES && ctx->bmm.slot[index].valid) {
-    const BatchMulMultiState::Slot& sl = ctx->bmm.slot[index];
-    table = sl.table, key = sl.base, c = sl.width;
-  } else if (which == MSM377_MUL_TABLE_GENERATOR && index < ctx->gens.k) {
-    c = ctx->gens.width;
-    table = ctx->gens.tables + (size_t)index * bm_table_records((uint32_t)c) * BM_REC_WORDS;
-  } else if (which > MSM377_MUL_TABLE_GENERATOR) {
-    ctx->err = "unknown window table";
-    return MSM377_EINVAL;
-  }
+// ---- table read-backs (msm377_g1_read_mul_table, msm377_ed_read_mul_table) ----
+// A copy of records the batch calls keep between calls, and what the host knows about them.  table: null if there is no
+// valid table at that place; key: the slot's 96 bytes (Edwards-BLS12: 64 base bytes, then zeros), null for a generator's.
+static int read_mul_table(msm377_ctx* ctx, const uint32_t* table, int c, const uint8_t* key, const char* not_valid, msm377_mul_table_info* info, uint64_t first, uint64_t count, uint32_t* words) {
   if (!table) {
-    ctx->err = "that window table is not valid: never built, dropped, or left by a build that failed";
+    ctx->err = not_valid;
     return MSM377_ESTATE;
   }
   const uint64_t records = bm_table_records((uint32_t)c);
@@ -2900,6 +2669,35 @@ int g1_read_mul_table(msm377_ctx* ctx, uint32_t which, uint32_t index, msm377_mu
     HIP_TRY(ctx, hipMemcpy(words, table + first * BM_REC_WORDS, (size_t)count * BM_REC_WORDS * 4, hipMemcpyDeviceToHost));
   }
   return MSM377_OK;
+}
+static int read_mul_slot(msm377_ctx* ctx, const MulTableSlot& sl, const char* not_valid, msm377_mul_table_info* info, uint64_t first, uint64_t count, uint32_t* words) {
+  return read_mul_table(ctx, sl.valid ? sl.table : nullptr, sl.width, sl.key, not_valid, info, first, count, words);
+}
+
+int g1_read_mul_table(msm377_ctx* ctx, uint32_t which, uint32_t index, msm377_mul_table_info* info, uint64_t first, uint64_t count, uint32_t* words) {
+  if (!ctx) return MSM377_EINVAL;
+  ctx->err.clear();
+  const char* not_valid = "that window table is not valid: never built, dropped, or left by a build that failed";
+  if (which == MSM377_MUL_TABLE_SINGLE && index == 0) return read_mul_slot(ctx, ctx->bm.single, not_valid, info, first, count, words);
+  if (which == MSM377_MUL_TABLE_MULTI && index < MSM377_MUL_MAX_BASES) return read_mul_slot(ctx, ctx->bmm.slot[index], not_valid, info, first, count, words);
+  if (which > MSM377_MUL_TABLE_GENERATOR) {
+    ctx->err = "unknown window table";
+    return MSM377_EINVAL;
+  }
+  const GeneratorSet& gs = ctx->gens;
+  const bool there = which == MSM377_MUL_TABLE_GENERATOR && index < gs.k;
+  return read_mul_table(ctx, there ? gs.tables + (size_t)index * bm_table_records((uint32_t)gs.width) * BM_REC_WORDS : nullptr, gs.width, nullptr, not_valid, info, first, count, words);
+}
+
+// Slot `index` of ctx->edbm as it stands.
+int ed_read_mul_table(msm377_ctx* ctx, uint32_t index, msm377_mul_table_info* info, uint64_t first, uint64_t count, uint32_t* words) {
+  if (!ctx) return MSM377_EINVAL;
+  ctx->err.clear();
+  if (index >= MSM377_MUL_MAX_BASES) {
+    ctx->err = "unknown window table";
+    return MSM377_EINVAL;
+  }
+  return read_mul_slot(ctx, ctx->edbm.slot[index], "that window table is not valid: never built, or left by a build that failed", info, first, count, words);
 }
 
 }  // namespace eng

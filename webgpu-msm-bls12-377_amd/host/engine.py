@@ -863,6 +863,16 @@ class MsmEngine:
     def generate_bases_device(self, seed: int, n: int, d_points_out: int):
         self._check(self._lib.msm377_g1_generate_bases_device(self._ctx, int(seed) & (2**64 - 1), int(n), d_points_out), "msm377_g1_generate_bases_device")
 
+    def _batch_host_call(self, fn: str, n: int, out_form, *args) -> Tuple[bytes, bytes]:
+        """One G1 batch call on host buffers: ``fn(ctx, *args, out form, records, flags)`` for n outputs; returns
+        (records, identity flags), one flag byte per output."""
+        f = _batch_mul_out_form(out_form)
+        stride = _POINT_STRIDE.get(f, 96)
+        out = ctypes.create_string_buffer(max(1, stride * n))
+        inf = ctypes.create_string_buffer(max(1, n))
+        self._check(getattr(self._lib, fn)(self._ctx, *args, f, ctypes.addressof(out), ctypes.addressof(inf)), fn)
+        return out.raw[: stride * n], inf.raw[:n]
+
     # -- fixed-base batch multiplication (include/msm377.h): out[i] = [s_i]B, every output its own point --
     def batch_mul_device(self, base: bytes, d_scalars: int, n: int, d_out: int, d_inf: int = 0, out_form="wire"):
         """n scalars in HBM (in the engine's scalar form) times the base ``base`` (96 wire bytes, a host buffer): n
@@ -879,14 +889,8 @@ class MsmEngine:
             raise ValueError("a base is 96 bytes")
         if len(scalars) % 32:
             raise ValueError("scalars buffer length must be a multiple of 32")
-        f = _batch_mul_out_form(out_form)
         n = len(scalars) // 32
-        stride = _POINT_STRIDE.get(f, 96)
-        out = ctypes.create_string_buffer(max(1, stride * n))
-        inf = ctypes.create_string_buffer(max(1, n))
-        rc = self._lib.msm377_g1_batch_mul(self._ctx, bytes(base), bytes(scalars), n, f, ctypes.addressof(out), ctypes.addressof(inf))
-        self._check(rc, "msm377_g1_batch_mul")
-        return out.raw[: stride * n], inf.raw[:n]
+        return self._batch_host_call("msm377_g1_batch_mul", n, out_form, bytes(base), bytes(scalars), n)
 
     # -- multi-base batch multiplication (include/msm377.h): out[i] = sum_j [s_ij]B_j over k fixed bases --
     def batch_mul_multi_device(self, bases: bytes, d_scalars: int, n: int, d_out: int, d_inf: int = 0, out_form="wire", out_stride=None, base_stride: int = 32):
@@ -908,13 +912,7 @@ class MsmEngine:
         """The same on host buffers, ``scalars`` the dense k x n matrix in ``layout`` ("rows" or "columns"): returns
         (records, identity flags) (msm377_g1_batch_mul_multi)."""
         k, n, out_stride, base_stride = _multi_shape(bases, scalars, layout)
-        f = _batch_mul_out_form(out_form)
-        stride = _POINT_STRIDE.get(f, 96)
-        out = ctypes.create_string_buffer(max(1, stride * n))
-        inf = ctypes.create_string_buffer(max(1, n))
-        rc = self._lib.msm377_g1_batch_mul_multi(self._ctx, bytes(bases), k, bytes(scalars), n, out_stride, base_stride, f, ctypes.addressof(out), ctypes.addressof(inf))
-        self._check(rc, "msm377_g1_batch_mul_multi")
-        return out.raw[: stride * n], inf.raw[:n]
+        return self._batch_host_call("msm377_g1_batch_mul_multi", n, out_form, bytes(bases), k, bytes(scalars), n, out_stride, base_stride)
 
     def mul_multi_table_builds(self) -> int:
         """Table slots batch_mul_multi* built on this engine so far (msm377_ctx_get_mul_multi_table_builds)."""
@@ -952,13 +950,7 @@ class MsmEngine:
         """The same on host buffers, ``scalars`` the dense k x n matrix in ``layout`` ("rows" or "columns"): returns
         (records, identity flags) (msm377_g1_commit_rows)."""
         n, out_stride, base_stride = _rows_shape(k, scalars, layout)
-        f = _batch_mul_out_form(out_form)
-        stride = _POINT_STRIDE.get(f, 96)
-        out = ctypes.create_string_buffer(max(1, stride * n))
-        inf = ctypes.create_string_buffer(max(1, n))
-        rc = self._lib.msm377_g1_commit_rows(self._ctx, bytes(scalars), n, int(k), out_stride, base_stride, f, ctypes.addressof(out), ctypes.addressof(inf))
-        self._check(rc, "msm377_g1_commit_rows")
-        return out.raw[: stride * n], inf.raw[:n]
+        return self._batch_host_call("msm377_g1_commit_rows", n, out_form, bytes(scalars), n, int(k), out_stride, base_stride)
 
     # -- variable-base batch multiplication (include/msm377.h): out[i] = [s_i]P_i --
     def batch_mul_var_device(self, d_points: int, d_scalars: int, n: int, d_out: int, d_inf: int = 0, out_form="wire", scalar_stride: int = 32):
@@ -973,13 +965,7 @@ class MsmEngine:
         """The same on host buffers: returns (records, identity flags).  A 32-byte ``scalars`` with more than one point
         is the one scalar of all points (msm377_g1_batch_mul_var)."""
         n = self._count_points(points)
-        f = _batch_mul_out_form(out_form)
-        stride = _POINT_STRIDE.get(f, 96)
-        out = ctypes.create_string_buffer(max(1, stride * n))
-        inf = ctypes.create_string_buffer(max(1, n))
-        rc = self._lib.msm377_g1_batch_mul_var(self._ctx, bytes(points), bytes(scalars), n, _var_scalar_stride(scalars, n), f, ctypes.addressof(out), ctypes.addressof(inf))
-        self._check(rc, "msm377_g1_batch_mul_var")
-        return out.raw[: stride * n], inf.raw[:n]
+        return self._batch_host_call("msm377_g1_batch_mul_var", n, out_form, bytes(points), bytes(scalars), n, _var_scalar_stride(scalars, n))
 
     # -- pairwise linear combination (include/msm377.h): out[i] = [a_i]P_i + [b_i]Q_i --
     def batch_lincomb2_device(self, d_p: int, d_q: int, d_a: int, d_b: int, n: int, d_out: int, d_inf: int = 0, out_form="wire", a_stride: int = 32, b_stride: int = 32):
@@ -998,15 +984,7 @@ class MsmEngine:
         n = self._count_points(p)
         if len(q) != len(p):
             raise ValueError("p and q: the same number of records")
-        f = _batch_mul_out_form(out_form)
-        stride = _POINT_STRIDE.get(f, 96)
-        out = ctypes.create_string_buffer(max(1, stride * n))
-        inf = ctypes.create_string_buffer(max(1, n))
-        rc = self._lib.msm377_g1_batch_lincomb2(
-            self._ctx, bytes(p), bytes(q), bytes(a), bytes(b), n, _var_scalar_stride(a, n), _var_scalar_stride(b, n), f, ctypes.addressof(out), ctypes.addressof(inf)
-        )
-        self._check(rc, "msm377_g1_batch_lincomb2")
-        return out.raw[: stride * n], inf.raw[:n]
+        return self._batch_host_call("msm377_g1_batch_lincomb2", n, out_form, bytes(p), bytes(q), bytes(a), bytes(b), n, _var_scalar_stride(a, n), _var_scalar_stride(b, n))
 
     def set_mul_window(self, bits: int = 0):
         """Window width of the batch_mul calls' table: 8 or 16, 0 = by the number of outputs (the default;
