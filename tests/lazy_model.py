@@ -32,9 +32,10 @@ N_RANDOM_POLY = 600  # per polynomial-map case of the curve formulas (their shap
 
 # op numbers of tests/native/primitives_ops.hpp
 FIELD_OPS = ["mul_lz", "sqr_lz", "mul_add_mul_lz", "mul", "sqr", "mul_sub_mul", "add", "sub", "neg", "reduce_once", "norm", "csub_mod", "csub_mod2",
-             "csub_mod4", "canon", "add_kp2_sub", "add_kp6_sub", "add_kp4w3_sub_sub2", "kp2_sub", "add_lz"]
+             "csub_mod4", "canon", "add_kp2_sub", "add_kp6_sub", "add_kp4w3_sub_sub2", "kp2_sub", "add_lz", "inverse_mont"]
 TE_OPS = ["madd", "madd_affine", "add", "finish", "from_base", "from_base_affine", "is_zero"]
-G1_OPS = ["madd_lz", "add_lz", "canon_pt"]
+G1_OPS = ["madd_lz", "add_lz", "canon_pt", "dbl", "dbl_affine"]
+ED_OPS = ["madd", "add", "dbl", "dbl_nt", "make_base", "cneg"]
 
 
 def value(limbs):
@@ -236,6 +237,7 @@ def field_cases(fm, n_random=None):
     add_case("kp2_sub", "stored", vec("stored", 36))
     add_case("add_lz", "stored + stored", vec("stored", 37), vec("stored", 38))
     add_case("add_lz", "lazy + canonical", vec("lazy", 39), vec("canonical", 40))
+    add_case("inverse_mont", "edges, both arms, extreme k, random", [nform_limbs(a, n) for a, _, _ in inverse_cases(fm)])
     return cases
 
 
@@ -259,6 +261,8 @@ def check_field_case(fm, op, label, ins, out):
             exp = {"mul": va * vb * Ri, "sqr": va * va * Ri, "mul_sub_mul": (va * vb - vc * vd) * Ri, "add": va + vb, "sub": va - vb, "neg": -va,
                    "reduce_once": va, "canon": va}[op] % P
             assert o == nform_limbs(exp, N), (what, hex(vo), hex(exp))  # THE canonical residue, carry-normalised
+        elif op == "inverse_mont":  # a = x R -> x^-1 R = a^-1 R^2, THE canonical residue
+            assert o == nform_limbs(pow(va, -1, P) * fm.R * fm.R % P, N), (what, hex(va), hex(vo))
         elif op == "norm":
             assert vo == va and all(x <= MASK for x in o[:-1]), what
         elif op in ("csub_mod", "csub_mod2", "csub_mod4"):
@@ -277,6 +281,120 @@ def check_field_case(fm, op, label, ins, out):
             assert o == exp, (what, [hex(x) for x in o], [hex(x) for x in exp])  # limb by limb, unmasked: nothing wrapped
         else:
             raise AssertionError("no contract for " + op)
+
+
+# ------------------------------------------------------------------ the inversion walk ----
+
+# fp_inverse.hpp / fq_inverse.hpp: the word count of the walk (its cap is 2 * 32 NW steps), and the k below which the
+# conversion takes its two-factor arm: j1 = 2 * 29 RS - k > 376 (Fp: k < 436), > 252 (Fq: 522 - k > 252, k < 270).
+INVERSE_WALK = {"Fp": {"cap": 2 * 384, "short_below": 812 - 376}, "Fq": {"cap": 2 * 256, "short_below": 522 - 252}}
+INVERSE_SCAN = 100000  # seeded random residues searched for the extreme k
+INVERSE_RANDOM = 256  # of them in the case list
+INVERSE_EXTREMES = os.path.join(ROOT, "tests", "golden", "inverse_k_extremes.json")
+
+
+def kaliski_k(fm, a):
+    """k of Kaliski's phase 1 as the headers walk it: u = p, v = a mod p; one step per pass, the branches in their order
+    (u even; v even; u > v; else), until v = 0 or the cap."""
+    u, v, k, cap = fm.P, a % fm.P, 0, INVERSE_WALK[fm.name]["cap"]
+    while v and k < cap:
+        if not u & 1:
+            u >>= 1
+        elif not v & 1:
+            v >>= 1
+        elif u > v:
+            u = (u - v) >> 1
+        else:
+            v = (v - u) >> 1
+        k += 1
+    return k
+
+
+def kaliski_k_fast(fm, a):
+    """The same k, a run of halvings at a time: a subtraction step halves once, and the even-operand steps that follow it
+    each halve once more.  (The host test holds it against kaliski_k.)"""
+    u, v, k = fm.P, a % fm.P, 0
+    assert v
+    tz = (v & -v).bit_length() - 1
+    v >>= tz
+    k += tz
+    while True:
+        if u > v:
+            u -= v
+            tz = (u & -u).bit_length() - 1
+            u >>= tz
+        else:
+            v -= u
+            if v == 0:
+                return k + 1
+            tz = (v & -v).bit_length() - 1
+            v >>= tz
+        k += tz
+
+
+def inverse_random_residue(fm, i):
+    """Seeded random residue number i in [1, p - 1]: addressable by index, so the scan's extremes can be named."""
+    import hashlib
+
+    return int.from_bytes(hashlib.sha512(b"inverse/%s/%d" % (fm.name.encode(), i)).digest(), "little") % (fm.P - 1) + 1
+
+
+def inverse_edge_values(fm):
+    """Montgomery 1, 2, p - 1, (p - 1) / 2 and the plain ones, every power of two below p plain and a few in Montgomery
+    form, and the non-canonical a + p the stored box admits (the walk starts with a canonical product that reduces it)."""
+    p, Rm = fm.P, fm.R
+    vals = []
+    for x in (1, 2, p - 1, (p - 1) // 2):
+        vals += [(x * Rm % p, "%#x R" % x), (x, "%#x" % x)]
+    j = 0
+    while (1 << j) < p:
+        vals.append((1 << j, "2^%d" % j))
+        j += 1
+    for j in (1, 29, 376 if fm.name == "Fp" else 252):
+        vals.append(((1 << j) * Rm % p, "2^%d R" % j))
+    rnd = random.Random("inverse-edges-" + fm.name)
+    for a in (1, 2, 3, 1 << 29, rnd.randrange(1, fm.E), fm.E - 1 - (fm.P & MASK)):
+        assert fm.shapes["stored"].holds(nform_limbs(a + p, fm.N)), hex(a)
+        vals.append((a + p, "%#x + p" % a))
+    return vals
+
+
+def inverse_scan(fm, count=INVERSE_SCAN):
+    """-> ((index, k) of the smallest k, (index, k) of the largest) over the first `count` seeded random residues; ties go
+    to the lower index.  Seconds of pure Python: the host test runs it and pins tests/golden/inverse_k_extremes.json."""
+    lo = hi = None
+    for i in range(count):
+        k = kaliski_k_fast(fm, inverse_random_residue(fm, i))
+        if lo is None or k < lo[1]:
+            lo = (i, k)
+        if hi is None or k > hi[1]:
+            hi = (i, k)
+    return lo, hi
+
+
+_INVERSE_CACHE = {}
+
+
+def inverse_cases(fm):
+    """[(a, k, label)]: the edge list, the scan's two extremes (from the pinned file, their k recomputed here) and
+    INVERSE_RANDOM random residues."""
+    import json
+
+    if fm.name in _INVERSE_CACHE:
+        return _INVERSE_CACHE[fm.name]
+    with open(INVERSE_EXTREMES) as f:
+        pinned = json.load(f)[fm.name]
+    assert pinned["scanned"] == INVERSE_SCAN
+    out = [(a, kaliski_k(fm, a), label) for a, label in inverse_edge_values(fm)]
+    for which in ("min", "max"):
+        i, k = pinned[which]
+        a = inverse_random_residue(fm, i)
+        assert kaliski_k(fm, a) == k, (fm.name, which)
+        out.append((a, k, "%s k of the scan, residue %d" % (which, i)))
+    out += [(inverse_random_residue(fm, i), None, "random %d" % i) for i in range(INVERSE_RANDOM)]
+    out = [(a, kaliski_k(fm, a) if k is None else k, label) for a, k, label in out]
+    _INVERSE_CACHE[fm.name] = out
+    return out
 
 
 # ------------------------------------------------------------------ twisted Edwards formulas ----
@@ -510,6 +628,25 @@ def xyzz_values(pt, z):
     return [pt[0] * zz * Rm % p, pt[1] * zzz * Rm % p, zz * Rm % p, zzz * Rm % p]
 
 
+def steer_xyzz(pt, which, target):
+    """z with coordinate `which` (X = x z^2, Y = y z^3, ZZ = z^2, ZZZ = z^3) stored as a value at or just above
+    target: the target moves up until target / (x R), / (y R) or / R is a square (X, ZZ) or a cube (Y, ZZZ)."""
+    p, Rm = R.P, 1 << (LB * 14)
+    assert (p - 1) % 3 == 0 and (p - 1) // 3 % 3 != 0  # 3 divides p - 1 exactly once: a cubic residue has the root c^(1/3 mod (p-1)/3)
+    cube_exp = pow(3, -1, (p - 1) // 3)
+    t = target
+    while True:
+        c = t * pow((Rm, pt[0] * Rm, pt[1] * Rm)[(2, 0, 1).index(which) if which != 3 else 0], -1, p) % p
+        if which in (0, 2):
+            z = _sqrt_p(c) if pow(c, (p - 1) // 2, p) == 1 else None
+        else:
+            z = pow(c, cube_exp, p) if pow(c, (p - 1) // 3, p) == 1 else None
+            assert z is None or pow(z, 3, p) == c
+        if z:
+            return z, t
+        t += 1
+
+
 def g1_point_cases(fm):
     """Real points in edge representations for G1::madd_lz / add_lz: X as x + k p for k = 0..4 (the stored X may be anything
     below 5p + e), each of X, Y, ZZ, ZZZ in turn steered to 1, to all-low-limbs-max, to values below e (stored as v and
@@ -534,24 +671,7 @@ def g1_point_cases(fm):
             emit("add_lz", av, qv, 0, exp, label)
             emit("add_lz", qv, av, 0, exp, label + " swapped")
 
-    assert (p - 1) % 3 == 0 and (p - 1) // 3 % 3 != 0  # 3 divides p - 1 exactly once: a cubic residue has the root c^(1/3 mod (p-1)/3)
-    cube_exp = pow(3, -1, (p - 1) // 3)
-
-    def steer(pt, which, target):
-        """z with coordinate `which` (X = x z^2, Y = y z^3, ZZ = z^2, ZZZ = z^3) stored as a value at or just above
-        target: the target moves up until target / (x R), / (y R) or / R is a square (X, ZZ) or a cube (Y, ZZZ)."""
-        t = target
-        while True:
-            c = t * pow((Rm, pt[0] * Rm, pt[1] * Rm)[(2, 0, 1).index(which) if which != 3 else 0], -1, p) % p
-            if which in (0, 2):
-                z = _sqrt_p(c) if pow(c, (p - 1) // 2, p) == 1 else None
-            else:
-                z = pow(c, cube_exp, p) if pow(c, (p - 1) // 3, p) == 1 else None
-                assert z is None or pow(z, 3, p) == c
-            if z:
-                return z, t
-            t += 1
-
+    steer = steer_xyzz
     lowmax = ((fm.MOD[-1] - 1) << (LB * 12)) | ((1 << (LB * 12)) - 1 - 64)
     A, Q = pts[3], pts[4]
     for rel, (apt, qpt) in (("generic", (A, Q)), ("P = Q", (A, A)), ("P = -Q", (A, R.neg(A)))):
@@ -591,6 +711,146 @@ def check_g1_words(fm, words, exp, what):
     for c in co[1:]:
         assert fm.is_stored(c), ("storage invariant", what)
     assert util.affine_from_xyzz_words(words) == exp, ("wrong point", what)
+
+
+def g1_two_torsion():
+    """The three points (x, 0) of y^2 = x^3 + 1: x^3 = -1."""
+    import util
+
+    p = R.P
+    tp = util.t_prime()
+    xs = [p - 1, tp[0], (1 - tp[0]) % p]
+    for x in xs:
+        assert R.on_curve((x, 0))
+    return xs
+
+
+def g1_dbl_cases(fm):
+    """Every stored representation of a real point for the strict G1::dbl (the one place where a non-canonical stored point
+    meets strict arithmetic, through canon_pt): X as x + k p while below 5p + e, each of X, Y, ZZ, ZZZ steered below e and
+    stored as v and as v + p, the 2-torsion points with Y = 0 and with Y = p (the double is the identity and ZZ must come
+    back zero limb by limb), an identity operand.  -> (a rows, [expected affine or None], [label])"""
+    p, n = R.P, 13
+    rnd = random.Random("g1-dbl")
+    pts = [R.mul(R.G, k) for k in (1, 2, 3, 12345, R.R_ORDER - 7)]
+    rows, exps, labels = [], [], []
+    xmax, omax = fm.shapes["stored_x"].hi, fm.shapes["stored"].hi
+
+    def emit(av, exp, label):
+        assert av[0] < xmax and all(v < omax for v in av[1:]), label
+        rows.append([x for v in av for x in nform_limbs(v, n)])
+        exps.append(exp), labels.append(label)
+
+    for i, pt in enumerate(pts):
+        av = xyzz_values(pt, rnd.randrange(1, p))
+        for k in range(5):
+            emit([av[0] + k * p] + av[1:], R.add(pt, pt), "point %d X + %d p" % (i, k))
+    A = pts[3]
+    for which, cname in ((0, "X"), (1, "Y"), (2, "ZZ"), (3, "ZZZ")):
+        for target in (1, rnd.randrange(1, fm.E >> 1), fm.E - 1000):
+            z, t = steer_xyzz(A, which, target)
+            av = xyzz_values(A, z)
+            assert av[which] == t
+            for k in range(6 if which == 0 else 2):
+                av2 = list(av)
+                av2[which] += k * p
+                emit(av2, R.add(A, A), "%s -> %#x + %d p" % (cname, t, k))
+    for x in g1_two_torsion():
+        for z in (1, rnd.randrange(1, p)):
+            av = xyzz_values((x, 0), z)
+            for y in (0, p):
+                for k in range(5):
+                    emit([av[0] + k * p, y] + av[2:], None, "2-torsion x = %#x.. Y = %s X + %d p" % (x >> 340, "p" if y else "0", k))
+    emit([rnd.randrange(p), rnd.randrange(p), 0, rnd.randrange(p)], None, "identity operand (x, y, 0, zzz)")
+    emit([0, fm.R % p, 0, 0], None, "identity()")
+    return arr(rows), exps, labels
+
+
+def g1_dbl_affine_cases(fm):
+    """Canonical affine points for G1::dbl_affine, the 2-torsion points among them.  -> (q rows, [expected], [label])"""
+    p, Rm = R.P, fm.R
+    pts = [R.mul(R.G, k) for k in (1, 2, 3, 5, 12345, R.R_ORDER - 7, R.R_ORDER - 1)] + [(x, 0) for x in g1_two_torsion()]
+    rows = [[x for v in (pt[0] * Rm % p, pt[1] * Rm % p, 0, 0) for x in nform_limbs(v, 13)] for pt in pts]
+    return arr(rows), [R.add(pt, pt) for pt in pts], ["point %d" % i for i in range(len(pts))]
+
+
+def check_g1_doubles(fm, out, exps, labels, op):
+    for i, o in enumerate(out.tolist()):
+        check_g1_words(fm, o, exps[i], (op, labels[i]))
+        if exps[i] is None:
+            assert o[26:39] == [0] * 13, ("the identity is ZZ = 0 limb by limb", op, labels[i])
+
+
+def ed_strict_cases(cm):
+    """The strict Edwards-BLS12 formulas (ed_ext.hpp EdT: canonical in, canonical out) on real points: one coordinate of
+    the first operand steered to 1, q - 1, all-low-limbs-max and a small value, generic / equal / opposite pairs, identity
+    and order-2 operands, random representations.
+    -> dict op -> (p rows, q rows, neg, [expected], [label]); expected is an affine point, or for make_base / cneg the three
+    exact record values."""
+    fm, p, n = cm.fm, cm.p, cm.fm.N
+    assert fm.name == "Fq"
+    rnd = random.Random("ed-strict")
+    out = {op: ([], [], [], [], []) for op in ED_OPS}
+
+    def emit(op, pv, qv, neg, exp, label):
+        assert all(0 <= v < p for v in pv + qv), label  # canonical operands only
+        o = out[op]
+        o[0].append([x for v in pv for x in nform_limbs(v, n)]), o[1].append([x for v in qv for x in nform_limbs(v, n)])
+        o[2].append(neg), o[3].append(exp), o[4].append(label)
+
+    def all_ops(pv, ppt, qpt, label):
+        emit("madd", pv, cm.base_values(qpt, 1)[:3] + [0], 0, cm.add(ppt, qpt), label)
+        qv = cm.ext_values(qpt, rnd.randrange(1, p))
+        emit("add", pv, qv, 0, cm.add(ppt, qpt), label)
+        emit("add", qv, pv, 0, cm.add(ppt, qpt), label + " swapped")
+        for op in ("dbl", "dbl_nt"):
+            emit(op, pv, [0] * 4, 0, cm.add(ppt, ppt), label)
+
+    P0, Q0 = cm.points[4], cm.points[5]
+    order2 = (0, p - 1)
+    assert cm.on_curve(order2)
+    for rel, (ppt, qpt) in (("generic", (P0, Q0)), ("P = Q", (P0, P0)), ("P = -Q", (P0, cm.neg(P0))), ("P + order 2", (P0, order2)), ("order 2 + Q", (order2, Q0))):
+        for c, cname in enumerate("XYTZ"):
+            coord = [ppt[0], ppt[1], ppt[0] * ppt[1] % p, 1][c]
+            if coord == 0:
+                continue
+            for tv, _ in edge_targets(fm, rnd):
+                lam = tv * pow(coord * fm.R, -1, p) % p
+                pv = cm.ext_values(ppt, lam)
+                assert pv[c] == tv % p
+                all_ops(pv, ppt, qpt, "%s %s -> %#x" % (rel, cname, tv))
+    one = fm.R % p
+    for qpt in cm.points[:3] + [(0, 1), order2]:
+        all_ops([0, one, 0, one], (0, 1), qpt, "identity() + Q")
+        cst = rnd.randrange(1, p)
+        all_ops([0, cst, 0, cst], (0, 1), qpt, "(0, c, 0, c) + Q")
+    for i in range(40):
+        ppt, qpt = rnd.choice(cm.points), rnd.choice(cm.points)
+        all_ops(cm.ext_values(ppt, rnd.randrange(1, p)), ppt, qpt, "random")
+    for pt in cm.points + [(0, 1), order2]:
+        rec = cm.base_values(pt, 1)[:3]
+        emit("make_base", [pt[0] * fm.R % p, pt[1] * fm.R % p, 0, 0], [0] * 4, 0, rec, "make_base")
+        for neg in (0, 1):
+            emit("cneg", [0] * 4, rec + [0], neg, cm.base_values(cm.neg(pt), 1)[:3] if neg else rec, "cneg neg=%d" % neg)
+    return {op: (arr(o[0]), arr(o[1]), np.array(o[2], dtype=np.uint32), o[3], o[4]) for op, o in out.items()}
+
+
+def check_ed_strict_case(cm, op, case, out):
+    fm, p, n = cm.fm, cm.p, cm.fm.N
+    for i, (o, exp, label) in enumerate(zip(out.tolist(), case[3], case[4])):
+        what = ("Ed", op, label, i)
+        co = [o[n * c : n * c + n] for c in range(4)]
+        for c in co:
+            assert c == nform_limbs(value(c) % p, n) and value(c) < p, ("not canonical", what)
+        if op in ("make_base", "cneg"):
+            assert [value(c) for c in co] == list(exp) + [0], ("wrong record", what)
+            continue
+        X, Y, T, Z = (value(c) for c in co)
+        assert Z != 0 and (X - exp[0] * Z) % p == 0 and (Y - exp[1] * Z) % p == 0, ("wrong point", what)
+        if op == "dbl_nt":
+            assert T == 0, what
+        else:  # T Z = X Y up to the Montgomery factor both sides carry once: stored values s = v R
+            assert (T * Z - X * Y) % p == 0, ("T Z = X Y", what)
 
 
 _GUARD_CACHE = {}
@@ -751,7 +1011,8 @@ NATIVE = os.path.join(ROOT, "tests", "native")
 SHIM_SO = os.path.join(NATIVE, "_build", "libfield29_shim.so")
 # (MSM377_PRIMTEST_SO: a build of the test library against a copy of csrc/ with a seeded fault, tests/PRIMITIVES.md)
 PRIMTEST_SO = os.environ.get("MSM377_PRIMTEST_SO") or os.path.join(CSRC, "libmsm377_primtest.so")
-PRIMTEST_ENTRY_POINTS = ["primtest_field", "primtest_te", "primtest_g1", "primtest_add_quad", "primtest_madd_quad", "primtest_aff_wire", "primtest_records"]
+PRIMTEST_ENTRY_POINTS = ["primtest_field", "primtest_te", "primtest_g1", "primtest_ed", "primtest_add_quad", "primtest_madd_quad", "primtest_aff_wire", "primtest_records",
+                         "primtest_normalise_g1", "primtest_normalise_ed", "primtest_normalise_guard"]
 
 
 def build_shim(csrc=CSRC, so=SHIM_SO):
@@ -810,7 +1071,34 @@ class Backend:
         self._call("g1", G1_OPS.index(op), _p(a), _p(q), _p(neg), _p(out), len(a))
         return out
 
+    def ed(self, op, p, q, neg):
+        p, q, neg = np.ascontiguousarray(p), np.ascontiguousarray(q), np.ascontiguousarray(neg)
+        assert p.shape == q.shape == (len(neg), 36)
+        out = np.zeros_like(p)
+        self._call("ed", ED_OPS.index(op), _p(p), _p(q), _p(neg), _p(out), len(p))
+        return out
+
     # ---- device only ----
+    def normalise(self, curve, form, pts, with_inf=True):
+        """k_bm_up / k_bm_across / k_bm_down<form> (curve "g1": form 0 wire, 1 mont_flag, 2 table) or the k_edbm_* three
+        (curve "ed": form 0 wire, 1 table) on the stash rows pts.  -> (records (n, record bytes) uint8, the guard band behind
+        them, flag bytes (n,) or None, their guard band or None); with_inf=False hands the kernel a null out_inf."""
+        import ctypes
+
+        pts = np.ascontiguousarray(pts)
+        n, w = pts.shape
+        rec = {"g1": (96, 104, 128), "ed": (64, 128)}[curve][form]
+        assert w == {"g1": 52, "ed": 36}[curve] and n >= 1
+        guard = self.lib.primtest_normalise_guard()
+        out = np.zeros(n * rec + guard, dtype=np.uint8)
+        u8 = ctypes.POINTER(ctypes.c_uint8)
+        if curve == "ed":
+            self._call("normalise_ed", form, _p(pts), n, out.ctypes.data_as(u8))
+            return out[: n * rec].reshape(n, rec), out[n * rec :], None, None
+        inf = np.zeros(n + guard, dtype=np.uint8) if with_inf else None
+        self._call("normalise_g1", form, _p(pts), n, out.ctypes.data_as(u8), inf.ctypes.data_as(u8) if with_inf else None)
+        return out[: n * rec].reshape(n, rec), out[n * rec :], (inf[:n] if with_inf else None), (inf[n:] if with_inf else None)
+
     def add_quad(self, kind, a, b):
         a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
         n, w = a.shape

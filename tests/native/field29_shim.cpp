@@ -52,9 +52,13 @@ void shim_raw_te(int field, int op, const uint32_t* p, const uint32_t* q, const 
       flags[i] = primtest::te_op<EdLazy>(op, p + 36 * i, q + 36 * i, neg[i], out + 36 * i);
   }
 }
-// G1::madd_lz / add_lz / canon_pt on raw XYZZ limbs (52 per operand and result)
+// G1::madd_lz / add_lz / canon_pt / dbl / dbl_affine on raw XYZZ limbs (52 per operand and result)
 void shim_raw_g1(int op, const uint32_t* a, const uint32_t* q, const uint32_t* neg, uint32_t* out, uint32_t n) {
   for (uint32_t i = 0; i < n; i++) primtest::g1_op(op, a + 52 * i, q + 52 * i, neg[i], out + 52 * i);
+}
+// the strict Edwards-BLS12 formulas (Ed = EdT<Fq, EdK29>) on raw limbs: 36 per operand and result
+void shim_raw_ed(int op, const uint32_t* p, const uint32_t* q, const uint32_t* neg, uint32_t* out, uint32_t n) {
+  for (uint32_t i = 0; i < n; i++) primtest::ed_op(op, p + 36 * i, q + 36 * i, neg[i], out + 36 * i);
 }
 
 // canonical 12-word little-endian operands -> canonical results

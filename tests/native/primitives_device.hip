@@ -2,7 +2,8 @@
 // headers (te_add_quad, g1_add_quad, te_madd_quad, AffWireSource::load, the bucket-record loads and stores), run one case
 // per lane -- or per lane quad -- on gfx950.  Built as libmsm377_primtest.so by csrc/Makefile, loaded by
 // tests/test_primitives_gpu.py; never linked into libmsm377.so.  Every launcher takes host arrays, copies them in,
-// launches 256-thread blocks over n cases, copies the results out and returns the HIP status.
+// launches 256-thread blocks over n cases, copies the results out and returns the HIP status.  The two normalise
+// launchers (tests/test_normalise_gpu.py) run the batch calls' own k_bm_* / k_edbm_* kernels on a stash the caller writes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -13,7 +14,9 @@
 #include "field29.hpp"
 #include "g1_xyzz.hpp"
 #include "kernels/accumulate.hpp"
+#include "kernels/batch_mul.hpp"
 #include "kernels/convert.hpp"
+#include "kernels/ed_batch_mul.hpp"
 #include "kernels/reduce.hpp"
 #include "primitives_ops.hpp"
 #include "te377.hpp"
@@ -76,6 +79,11 @@ __global__ void __launch_bounds__(256) k_g1(int op, const uint32_t* a, const uin
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   primtest::g1_op(op, a + 52 * i, q + 52 * i, neg[i], out + 52 * i);
+}
+__global__ void __launch_bounds__(256) k_ed(int op, const uint32_t* p, const uint32_t* q, const uint32_t* neg, uint32_t* out, uint32_t n) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  primtest::ed_op(op, p + 36 * i, q + 36 * i, neg[i], out + 36 * i);
 }
 // AffWireSource::load: raw = n x 24 wire words; out = n x 39 limbs (n1, n2, z); flags = its return value
 __global__ void __launch_bounds__(256) k_aff_wire(const uint32_t* raw, uint32_t* out, uint32_t* flags, uint32_t n) {
@@ -230,6 +238,69 @@ int run_records(const uint32_t* in, uint32_t* rec, uint32_t* out_thread, uint32_
   return (int)fetch(out_quad, dq, 4 * w);
 }
 
+
+// ---- the batch calls' normalisation (k_bm_up / k_bm_across / k_bm_down, k_edbm_*) on a stash the CALLER writes ----
+// The product's own kernels at the product's own launch geometry (sequencer.hip normalise()); nothing is re-implemented.
+// The stash has the size the kernels' indexing needs (piece stride BM_CHUNK: BM_PIECES x 16 MiB); only the n rows of the
+// point pieces are written.  The output and flag buffers are filled with 0xEE and end in a guard band that comes back too.
+constexpr size_t NORM_GUARD = 256;
+constexpr uint32_t NORM_MAX_N = 1u << 16;
+struct NormG1 {
+  static constexpr uint32_t PT_WORDS = 52, PIECES = BM_POINT_PIECES;
+  static constexpr auto up = k_bm_up;
+  static constexpr auto across = k_bm_across;
+  static size_t record(int form) { return form == 0 ? 96 : form == 1 ? 104 : form == 2 ? 128 : 0; }
+  static void down(int form, uint32_t blocks, const uint4* stash, uint64_t n, const uint32_t* trees, const uint32_t* inv, uint8_t* out, uint8_t* inf) {
+    const auto k = form == 0 ? k_bm_down<MSM377_POINTS_WIRE> : form == 1 ? k_bm_down<MSM377_POINTS_MONT_FLAG> : k_bm_down<BM_FORM_TABLE>;
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(BM_THREADS), 0, 0, stash, n, trees, inv, out, inf);
+  }
+};
+struct NormEd {
+  static constexpr uint32_t PT_WORDS = 36, PIECES = EDBM_POINT_PIECES;
+  static constexpr auto up = k_edbm_up;
+  static constexpr auto across = k_edbm_across;
+  static size_t record(int form) { return form == 0 ? 64 : form == 1 ? 128 : 0; }
+  static void down(int form, uint32_t blocks, const uint4* stash, uint64_t n, const uint32_t* trees, const uint32_t* inv, uint8_t* out, uint8_t*) {
+    const auto k = form == 0 ? k_edbm_down<EDBM_FORM_WIRE> : k_edbm_down<EDBM_FORM_TABLE>;
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(BM_THREADS), 0, 0, stash, n, trees, inv, out);
+  }
+};
+static_assert(4 * NormG1::PIECES == NormG1::PT_WORDS && 4 * NormEd::PIECES == NormEd::PT_WORDS, "a point is whole pieces");
+// pts: n points of PT_WORDS raw words.  out: n records + NORM_GUARD bytes.  inf: n + NORM_GUARD bytes, or null (the kernel
+// then gets a null out_inf).
+template <class C>
+int run_normalise(int form, const uint32_t* pts, uint32_t n, uint8_t* out, uint8_t* inf) {
+  const size_t rec = C::record(form);
+  if (!rec || n == 0 || n > NORM_MAX_N) return -1;
+  const uint32_t blocks = (n + BM_BLOCK - 1) / BM_BLOCK;
+  Bufs m;
+  uint32_t *stash_w, *trees, *prod, *inv, *dout, *dinf = nullptr;
+  void* raw = nullptr;
+  PT_TRY(hipMalloc(&raw, (size_t)BM_PIECES * BM_CHUNK * sizeof(uint4)));
+  m.all.push_back(raw);
+  stash_w = static_cast<uint32_t*>(raw);
+  uint4* stash = reinterpret_cast<uint4*>(stash_w);
+  std::vector<uint32_t> piece((size_t)4 * n);
+  for (uint32_t k = 0; k < C::PIECES; k++) {
+    for (uint32_t i = 0; i < n; i++)
+      for (uint32_t j = 0; j < 4; j++) piece[(size_t)4 * i + j] = pts[(size_t)C::PT_WORDS * i + 4 * k + j];
+    PT_TRY(hipMemcpy(stash + (size_t)k * BM_CHUNK, piece.data(), (size_t)n * sizeof(uint4), hipMemcpyHostToDevice));
+  }
+  PT_TRY(m.get(&trees, nullptr, (size_t)blocks * BM_TREE_WORDS));
+  PT_TRY(m.get(&prod, nullptr, (size_t)blocks * 13));
+  PT_TRY(m.get(&inv, nullptr, (size_t)blocks * 13));
+  const size_t out_bytes = (size_t)n * rec + NORM_GUARD, inf_bytes = (size_t)n + NORM_GUARD;
+  PT_TRY(m.get(&dout, nullptr, (out_bytes + 3) / 4, 0xEE));
+  if (inf) PT_TRY(m.get(&dinf, nullptr, (inf_bytes + 3) / 4, 0xEE));
+  hipLaunchKernelGGL(C::up, dim3(blocks), dim3(BM_THREADS), 0, 0, stash, (uint64_t)n, trees, prod);
+  hipLaunchKernelGGL(C::across, dim3(1), dim3(BM_THREADS), 0, 0, (const uint32_t*)prod, blocks, inv);
+  C::down(form, blocks, stash, n, trees, inv, reinterpret_cast<uint8_t*>(dout), reinterpret_cast<uint8_t*>(dinf));
+  PT_TRY(finish_launch());
+  PT_TRY(hipMemcpy(out, dout, out_bytes, hipMemcpyDeviceToHost));
+  if (inf) PT_TRY(hipMemcpy(inf, dinf, inf_bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -258,6 +329,28 @@ int primtest_g1(int op, const uint32_t* a, const uint32_t* q, const uint32_t* ne
   PT_TRY(finish_launch());
   return (int)fetch(out, dout, w);
 }
+// op = primtest::EdOp, the strict Edwards-BLS12 formulas.  Same arguments as shim_raw_ed.
+int primtest_ed(int op, const uint32_t* p, const uint32_t* q, const uint32_t* neg, uint32_t* out, uint32_t n) {
+  if (op < 0 || op >= primtest::E_NUM_OPS) return -1;
+  Bufs m;
+  uint32_t *dp, *dq, *dn, *dout;
+  const size_t w = (size_t)36 * n;
+  PT_TRY(m.get(&dp, p, w));
+  PT_TRY(m.get(&dq, q, w));
+  PT_TRY(m.get(&dn, neg, n));
+  PT_TRY(m.get(&dout, nullptr, w));
+  if (n) k_ed<<<blocks_for(n), 256>>>(op, dp, dq, dn, dout, n);
+  PT_TRY(finish_launch());
+  return (int)fetch(out, dout, w);
+}
+// k_bm_up / k_bm_across / k_bm_down<form> over n XYZZ points (52 raw words each) placed at the kernels' own stash indices.
+// form 0 = MSM377_POINTS_WIRE (96-byte records), 1 = MSM377_POINTS_MONT_FLAG (104), 2 = BM_FORM_TABLE (128).  out: n records
+// and the 256-byte guard band behind them; inf: n flag bytes and their guard band, or null for a null out_inf.
+int primtest_normalise_g1(int form, const uint32_t* pts, uint32_t n, uint8_t* out, uint8_t* inf) { return run_normalise<NormG1>(form, pts, n, out, inf); }
+// k_edbm_up / k_edbm_across / k_edbm_down<form> over n extended points (36 raw words).  form 0 = EDBM_FORM_WIRE (64-byte
+// records), 1 = EDBM_FORM_TABLE (128).
+int primtest_normalise_ed(int form, const uint32_t* pts, uint32_t n, uint8_t* out) { return run_normalise<NormEd>(form, pts, n, out, nullptr); }
+int primtest_normalise_guard() { return (int)NORM_GUARD; }
 // kind 0 = te_add_quad<Fp>, 1 = te_add_quad<Fq>, 2 = g1_add_quad.  a, b: n packed points (4 N limbs); out: 4 n points (one per
 // lane of every quad); flags: 4 n words, is_bad of each lane's sum.
 int primtest_add_quad(int kind, const uint32_t* a, const uint32_t* b, uint32_t* out, uint32_t* flags, uint32_t n) {

@@ -7,6 +7,9 @@
 
 #include <type_traits>
 
+#include "ed_ext.hpp"
+#include "fp_inverse.hpp"
+#include "fq_inverse.hpp"
 #include "g1_xyzz.hpp"
 #include "te377.hpp"
 
@@ -34,10 +37,12 @@ enum FieldOp {
   F_ADD_KP4W3_SUB_SUB2,
   F_KP2_SUB,
   F_ADD_LZ,
+  F_INVERSE_MONT,  // FpInverse / FqInverse::inverse_mont: a data-dependent walk, one branch sequence per case
   F_NUM_OPS
 };
 enum TeOp { T_MADD = 0, T_MADD_AFFINE, T_ADD, T_FINISH, T_FROM_BASE, T_FROM_BASE_AFFINE, T_IS_ZERO, T_NUM_OPS };
-enum G1Op { G_MADD_LZ = 0, G_ADD_LZ, G_CANON_PT, G_NUM_OPS };
+enum G1Op { G_MADD_LZ = 0, G_ADD_LZ, G_CANON_PT, G_DBL, G_DBL_AFFINE, G_NUM_OPS };
+enum EdOp { E_MADD = 0, E_ADD, E_DBL, E_DBL_NT, E_MAKE_BASE, E_CNEG, E_NUM_OPS };  // the strict EdT<Fq, EdK29> (ed_ext.hpp)
 
 template <class F>
 MSM_HD typename F::El ld(const uint32_t* w) {
@@ -80,6 +85,10 @@ MSM_HD void field_op(int op, const uint32_t* pa, const uint32_t* pb, const uint3
     case F_ADD_KP4W3_SUB_SUB2: r = F::add_kp_sub_sub2(a, K::KP4W3, b, c); break;
     case F_KP2_SUB: r = F::kp_sub(K::KP2, a); break;
     case F_ADD_LZ: r = F::add_lz(a, b); break;
+    case F_INVERSE_MONT:
+      if constexpr (std::is_same<F, Fp>::value) r = FpInverse::inverse_mont(a);
+      else r = FqInverse::inverse_mont(a);
+      break;
     default: break;
   }
   st<F>(out, r);
@@ -134,9 +143,35 @@ MSM_HD void g1_op(int op, const uint32_t* pa, const uint32_t* pq, uint32_t neg, 
     case G_MADD_LZ: o = G1::madd_lz(a, q, neg != 0); break;
     case G_ADD_LZ: o = G1::add_lz(a, b); break;
     case G_CANON_PT: o = G1::canon_pt(a); break;
+    case G_DBL: o = G1::dbl(a); break;
+    case G_DBL_AFFINE: o = G1::dbl_affine(q); break;
     default: break;
   }
   st<Fp>(out, o.x), st<Fp>(out + 13, o.y), st<Fp>(out + 26, o.zz), st<Fp>(out + 39, o.zzz);
+}
+
+// The strict (canonical in, canonical out) Edwards-BLS12 formulas the batch kernels build their tables with.  p: an Ext
+// (X, Y, T, Z), 36 limbs.  q: a Base (ymx, ypx, kt: 27 limbs used) or a second Ext.  out: 36 limbs -- an Ext, or for
+// E_MAKE_BASE (from p.x, p.y) and E_CNEG (of q) a Base in the first 27 and zeros behind it.
+MSM_HD void ed_op(int op, const uint32_t* pp, const uint32_t* pq, uint32_t neg, uint32_t* out) {
+  Ed::Ext p, q, o;
+  p.x = ld<Fq>(pp), p.y = ld<Fq>(pp + 9), p.t = ld<Fq>(pp + 18), p.z = ld<Fq>(pp + 27);
+  q.x = ld<Fq>(pq), q.y = ld<Fq>(pq + 9), q.t = ld<Fq>(pq + 18), q.z = ld<Fq>(pq + 27);
+  Ed::Base b, ob;
+  b.ymx = q.x, b.ypx = q.y, b.kt = q.t;
+  o.x = o.y = o.t = o.z = Fq::zero();
+  bool base_out = false;
+  switch (op) {
+    case E_MADD: o = Ed::madd(p, b); break;
+    case E_ADD: o = Ed::add(p, q); break;
+    case E_DBL: o = Ed::dbl(p); break;
+    case E_DBL_NT: o = Ed::dbl_nt(p); break;
+    case E_MAKE_BASE: ob = Ed::make_base(p.x, p.y), base_out = true; break;
+    case E_CNEG: ob = Ed::cneg(b, neg != 0), base_out = true; break;
+    default: break;
+  }
+  if (base_out) o.x = ob.ymx, o.y = ob.ypx, o.t = ob.kt;
+  st<Fq>(out, o.x), st<Fq>(out + 9, o.y), st<Fq>(out + 18, o.t), st<Fq>(out + 27, o.z);
 }
 
 }  // namespace primtest

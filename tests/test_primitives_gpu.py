@@ -109,6 +109,50 @@ def test_xyzz_formulas_device_equals_host_and_contract(dev, host):
             assert o[13 * c : 13 * c + 13] == M.nform_limbs(M.value(a[13 * c : 13 * c + 13]) % fm.P, 13)
 
 
+def test_strict_g1_doublings_device_equals_host_and_contract(dev, host):
+    """G1::dbl (through canon_pt, on every stored representation; 2-torsion with Y = 0 and Y = p -> ZZ limb-zero) and
+    G1::dbl_affine, the strict formulas the batch kernels call."""
+    fm = M.FieldModel("Fp")
+    rows, exps, labels = M.g1_dbl_cases(fm)
+    zero = np.zeros(len(rows), dtype=np.uint32)
+    out = dev.g1("dbl", rows, np.zeros_like(rows), zero)
+    same(out, host.g1("dbl", rows, np.zeros_like(rows), zero), "dbl")
+    M.check_g1_doubles(fm, out, exps, labels, "dbl")
+    rows, exps, labels = M.g1_dbl_affine_cases(fm)
+    zero = np.zeros(len(rows), dtype=np.uint32)
+    out = dev.g1("dbl_affine", np.zeros_like(rows), rows, zero)
+    same(out, host.g1("dbl_affine", np.zeros_like(rows), rows, zero), "dbl_affine")
+    M.check_g1_doubles(fm, out, exps, labels, "dbl_affine")
+
+
+def test_strict_edwards_formulas_device_equals_host_and_contract(dev, host):
+    """EdT<Fq, EdK29> madd, add, dbl, dbl_nt, make_base, cneg: the formulas of k_edbm_row_bases, k_edbm_entries and
+    k_edbm_down<table>."""
+    cm = M.CurveModel(M.FieldModel("Fq"))
+    cases = M.ed_strict_cases(cm)
+    assert set(cases) == set(M.ED_OPS)
+    for op, case in cases.items():
+        out = dev.ed(op, case[0], case[1], case[2])
+        same(out, host.ed(op, case[0], case[1], case[2]), ("Ed", op))
+        M.check_ed_strict_case(cm, op, case, out)
+
+
+def test_inversion_walks_take_both_arms_on_the_device(dev, host, fm):
+    """FpInverse / FqInverse::inverse_mont, one case per lane, each lane its own branch sequence: device == host bit for
+    bit and == pow(a, -1, p) in Montgomery form, with the arm counts of the case list stated (the floors themselves are
+    asserted from the k-model in tests/test_primitives_host.py)."""
+    cases = M.inverse_cases(fm)
+    short = sum(1 for _, k, _ in cases if k < M.INVERSE_WALK[fm.name]["short_below"])
+    assert short >= 8 and len(cases) - short >= 8
+    a = M.arr([M.nform_limbs(v, fm.N) for v, _, _ in cases])
+    ins = [a] + [np.zeros_like(a)] * 3
+    got = dev.field(fm, "inverse_mont", ins)
+    same(got, host.field(fm, "inverse_mont", ins), (fm.name, "inverse_mont"))
+    M.check_field_case(fm, "inverse_mont", "both arms", ins, got)
+    for n in (1, 67):  # a ragged launch: idle lanes beside walking ones
+        same(dev.field(fm, "inverse_mont", [x[:n] for x in ins]), got[:n], (fm.name, "inverse_mont ragged", n))
+
+
 def test_te_add_quad_is_the_thread_level_addition(dev, fm):
     """te_add_quad<Fp> / te_add_quad<Fq>: the same products as TeLazy::add, spread over four lanes -- bit-identical to it,
     every lane holding the whole sum, adjacent quads carrying different operands; and the contract on top."""

@@ -54,6 +54,45 @@ def test_shape_table_is_the_proofs():
     subprocess.check_call(["python3", os.path.join(util.ROOT, "tools", "check_lazy_bounds.py")], stdout=subprocess.DEVNULL)
 
 
+def test_normalisation_replay_and_the_gpu_tests_operands():
+    """tools/check_lazy_bounds.py normalisation_formulas() -- the interval replay of k_bm_up / k_bm_across / k_bm_down and
+    the k_edbm_* three -- runs for both fields, and the corner operands tests/test_normalise_gpu.py writes into the stash
+    ARE the boxes that replay starts from: same table, same limb maxima, same value bounds."""
+    import normalise_model as NM
+
+    B = M.B
+    for name in FIELDS:
+        B.use_field(name)
+        B.normalisation_formulas()
+        fm = M.FieldModel(name)
+        table = B.shapes()
+        ops = B.NORMALISATION_OPERANDS[name]
+        got = NM.stash_shapes(fm)
+        assert [c for c, _ in got] == list(ops) == (["X", "Y", "ZZ", "ZZZ"] if name == "Fp" else ["X", "Y", "T", "Z"])
+        for c, sh in got:
+            assert sh.hi == table[ops[c]].hi, (name, c)
+            if ops[c] != "canonical":
+                assert sh.box == table[ops[c]].limbs, (name, c)
+    assert B.NORMALISATION_OPERANDS["Fp"] == {"X": "stored_x", "Y": "stored", "ZZ": "stored", "ZZZ": "stored"}
+    fm = M.FieldModel("Fp")
+    B.use_field("Fp")
+    corners = dict(NM.g1_corner_rows(fm))
+    assert corners["all corners"] == B.shapes()["stored_x"].limbs + 3 * B.shapes()["stored"].limbs
+    assert corners["all value maxima"] == [x for h in (5 * fm.P + fm.E, fm.P + fm.E, fm.P + fm.E, fm.P + fm.E) for x in M.nform_limbs(h - 1, 13)]
+    for c, name in enumerate(("X", "Y", "ZZ", "ZZZ")):
+        assert corners[name + " corner"][13 * c : 13 * c + 13] == B.shapes()[ops_name(name)].limbs
+    # the steered residues cover both arms of both walks
+    for name in FIELDS:
+        f = M.FieldModel(name)
+        ks = [M.kaliski_k(f, a) for _, a in NM.steered_values(f)]
+        cut = M.INVERSE_WALK[name]["short_below"]
+        assert sum(k < cut for k in ks) >= 3 and sum(k >= cut for k in ks) >= 3, (name, ks)
+
+
+def ops_name(coordinate):
+    return M.B.NORMALISATION_OPERANDS["Fp"][coordinate]
+
+
 def test_generator_emits_only_in_contract_vectors(fm):
     """Every shape: its fixed edge set plus at least 2 000 random vectors, all inside the shape (asserted by the generator
     itself, never filtered), deterministic, and the corner of the box really is there."""
@@ -161,6 +200,63 @@ def test_xyzz_formulas_on_real_points_in_edge_representations(host):
     for i, (o, a) in enumerate(zip(out.tolist(), pts.tolist())):
         for c in range(4):
             assert o[13 * c : 13 * c + 13] == M.nform_limbs(M.value(a[13 * c : 13 * c + 13]) % fm.P, 13), i
+
+
+def test_inversion_walk_cases_cover_both_arms(fm):
+    """FpInverse / FqInverse::inverse_mont, from the k-model ALONE (nothing native runs here): the case list of
+    field_cases holds at least 8 inputs in the two-factor arm of the conversion (Fp: k < 436, Fq: k < 270, read from the
+    headers' j1 > 376 / j1 > 252) and 8 in the other, the edge list, 256 random residues, and the smallest and the
+    largest k among 10^5 seeded random residues -- which the pinned file names and this test finds again."""
+    import json
+
+    walk = M.INVERSE_WALK[fm.name]
+    hdr = open(os.path.join(M.CSRC, "fp_inverse.hpp" if fm.name == "Fp" else "fq_inverse.hpp")).read()
+    total, cut = (812, 376) if fm.name == "Fp" else (522, 252)
+    assert "int j1 = %d - k" % total in hdr and "if (j1 > %d)" % cut in hdr and "k < 2 * %d" % (walk["cap"] // 2) in hdr
+    assert walk["short_below"] == total - cut and total == 2 * 29 * fm.RS
+    cases = M.inverse_cases(fm)
+    ks = [k for _, k, _ in cases]
+    short, long_ = [k for k in ks if k < walk["short_below"]], [k for k in ks if k >= walk["short_below"]]
+    print("%s inverse_mont: %d cases, %d in the short-k arm, %d in the other, k in [%d, %d]" % (fm.name, len(cases), len(short), len(long_), min(ks), max(ks)))
+    assert len(short) >= 8 and len(long_) >= 8
+    assert sum(1 for _, _, l in cases if l.startswith("random")) == M.INVERSE_RANDOM == 256
+    assert sum(1 for _, _, l in cases if l.endswith("+ p")) >= 4  # non-canonical representatives
+    bits = fm.P.bit_length()
+    assert all(bits <= k <= 2 * bits for k in ks)  # Kaliski's range; the cap of the loop is never what ends a walk
+    for a, k, label in cases:
+        assert M.kaliski_k(fm, a) == k == M.kaliski_k_fast(fm, a), label
+        assert M.value(M.nform_limbs(a, fm.N)) == a and a % fm.P
+    lo, hi = M.inverse_scan(fm)
+    with open(M.INVERSE_EXTREMES) as f:
+        pinned = json.load(f)[fm.name]
+    assert pinned == {"scanned": M.INVERSE_SCAN, "min": list(lo), "max": list(hi)} and M.INVERSE_SCAN == 100000
+    assert lo[1] in ks and hi[1] in ks and lo[1] >= walk["short_below"]  # a random residue does not reach the short arm: the edges do
+
+
+def test_strict_g1_doublings(host):
+    """G1::dbl on every stored representation (X = x + k p up to the box, Y, ZZ, ZZZ with + p where the box allows), the
+    2-torsion points with Y = 0 and Y = p -> ZZ limb-zero, outputs inside the stored boxes; G1::dbl_affine."""
+    fm = M.FieldModel("Fp")
+    rows, exps, labels = M.g1_dbl_cases(fm)
+    zero = np.zeros(len(rows), dtype=np.uint32)
+    M.check_g1_doubles(fm, host.g1("dbl", rows, np.zeros_like(rows), zero), exps, labels, "dbl")
+    assert sum(1 for l in labels if "Y = p" in l) >= 15 and sum(1 for l in labels if "+ 5 p" in l) >= 3 and len(rows) > 100
+    for c in ("Y", "ZZ", "ZZZ"):
+        assert sum(1 for l in labels if l.startswith(c + " ->") and l.endswith("+ 1 p")) == 3
+    rows, exps, labels = M.g1_dbl_affine_cases(fm)
+    zero = np.zeros(len(rows), dtype=np.uint32)
+    M.check_g1_doubles(fm, host.g1("dbl_affine", np.zeros_like(rows), rows, zero), exps, labels, "dbl_affine")
+    assert exps.count(None) == 3
+
+
+def test_strict_edwards_formulas(host):
+    """EdT<Fq, EdK29> madd, add, dbl, dbl_nt, make_base, cneg against pyref's group law on real points."""
+    cm = M.CurveModel(M.FieldModel("Fq"))
+    cases = M.ed_strict_cases(cm)
+    assert set(cases) == set(M.ED_OPS)
+    for op, case in cases.items():
+        assert len(case[3]) >= (8 if op == "make_base" else 16), op  # make_base: six points, the identity, the point of order 2
+        M.check_ed_strict_case(cm, op, case, host.ed(op, case[0], case[1], case[2]))
 
 
 def test_device_test_library_is_built_for_gfx950_and_kept_apart():

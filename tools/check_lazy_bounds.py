@@ -8,6 +8,10 @@ and that the results satisfy the storage invariant the next addition assumes:
 
     X: N-form, value < 5p + 2^354        Y, ZZ, ZZZ: N-form, value < p + 2^354
 
+normalisation_formulas() replays the batch calls' normalisation (kernels/batch_mul.hpp k_bm_up / k_bm_across / k_bm_down,
+kernels/ed_batch_mul.hpp k_edbm_*) the same way, from the stash shapes of NORMALISATION_OPERANDS;
+tests/test_normalise_gpu.py puts exactly those operands into the stash on the GPU.
+
 The operand shapes live in ONE table, shapes(): main() reads the ones it starts from (canonical, stored, stored_x) from there, and so do the
 primitive tests (tests/lazy_model.py), which feed the real field29.hpp / te377.hpp / g1_xyzz.hpp code operands at exactly
 these bounds on the host and on the GPU -- tests/test_primitives_host.py::test_shape_table_is_the_proofs pins the two together.
@@ -80,7 +84,7 @@ LAZY_TOP = 1 << 31
 
 def shapes():
     """The operand shapes of the field in use, name -> V, and what the primitive tests generate.  canonical, stored and
-    stored_x are what the replays below START from (main(), te_formulas, conversion_formulas).  The others are not inputs
+    stored_x are what the replays below START from (main(), te_formulas, conversion_formulas, normalisation_formulas).  The others are not inputs
     of a replay: wide / narrow / lazy restate field29.hpp's comment, diff3 / diff7 / kp2_sub name intermediate values, and
     they are tied to the replay only where it asserts that its own values fit them (point_formula, conversion_formulas --
     Fp; the Fq pass consumes none of them) and where a caller runs check_columns on them (tests/lazy_model.py
@@ -291,9 +295,94 @@ def conversion_formulas():
     mul_lz(kt, canonical, "conv-rec first: kt / d")  # from_base_affine: mul(kt, TE_INV_D), reduce_once needs < 2p
 
 
+# The stash rows the batch calls' normalisation starts from (g1_xyzz.hpp's storage invariant; ed_batch_mul.hpp "Canonical
+# coordinates in"): coordinate -> name in shapes().  tests/normalise_model.py builds its corner operands from this table.
+NORMALISATION_OPERANDS = {
+    "Fp": {"X": "stored_x", "Y": "stored", "ZZ": "stored", "ZZZ": "stored"},
+    "Fq": {"X": "canonical", "Y": "canonical", "T": "canonical", "Z": "canonical"},
+}
+
+
+def reduce_once_ok(a, name):
+    """field29.hpp reduce_once: limbs below 2^29 except the top one (< 2^31), value < 2p."""
+    assert a.normalised and a.limbs[-1] < (1 << 31) and a.hi <= 2 * P, (name, a.hi / P)
+
+
+def normalisation_formulas():
+    """kernels/batch_mul.hpp k_bm_up / k_bm_across / k_bm_down (Fp) and kernels/ed_batch_mul.hpp k_edbm_* (Fq) from the
+    stash shapes of NORMALISATION_OPERANDS: the per-thread running product, both product trees, the inversion's first
+    product, the trees walked down, the unfolding, zi, tt, x, y and the last product into each output form.  Every product
+    goes through check_columns (mul_lz / sqr_lz above); the value assertions are the ones the source comments make."""
+    sh = shapes()
+    canonical = sh["canonical"]
+    ops = {k: sh[v] for k, v in NORMALISATION_OPERANDS["Fp" if N == 13 else "Fq"].items()}
+
+    def closed(v, name):  # "M1 is closed under mul_lz": the product is again a stored value, limb box and value bound
+        assert v.limbs == sh["stored"].limbs and v.hi == sh["stored"].hi and v.normalised, name
+        return v
+
+    def tree(leaf, tag):  # eight levels of pairwise products of nodes of one shape; the root
+        node = leaf
+        for level in range(8):
+            node = closed(mul_lz(node, node, "%s tree level %d" % (tag, level)), tag)
+        return node
+
+    def tree_down(root_inv, node, tag):  # inv_k * sibling: the first level takes the kernel's input, the others a product
+        inv = closed(mul_lz(root_inv, node, tag + " down from the root"), tag)
+        for level in range(1, 8):
+            inv = closed(mul_lz(inv, node, "%s down level %d" % (tag, level)), tag)
+        return inv
+
+    if N == 13:
+        one = canonical  # Fp::one(), and the 1 an identity contributes in place of its ZZZ = 0
+        # k_bm_up: c = 1, then c = c * z four times, z a stored ZZZ or 1
+        c = closed(mul_lz(one, ops["ZZZ"], "up c0*z"), "up")
+        mul_lz(one, one, "up c0*1")
+        c = closed(mul_lz(c, ops["ZZZ"], "up c*z"), "up")
+        mul_lz(c, one, "up c*1")
+        block = tree(c, "up")
+        # k_bm_across: the same one level up, the factors now workgroup products
+        c = closed(mul_lz(one, block, "across c0*prod"), "across")
+        c = closed(mul_lz(c, block, "across c*prod"), "across")
+        root = tree(c, "across")
+        reduce_once_ok(mul_lz(root, one, "inverse a*1"), "inverse a*1")  # FpInverse::inverse_mont: Fp::mul(a, one())
+        inv_root = canonical  # ... and its result is a canonical product
+        inv = tree_down(inv_root, c, "across")
+        closed(mul_lz(inv, one, "across inv*c0"), "across")  # the unfolding: 1 / product_b = (1 / C_(b+1)) C_b
+        closed(mul_lz(inv, c, "across inv*c"), "across")
+        binv = closed(mul_lz(inv, block, "across inv*prod"), "across")
+        # k_bm_down: the workgroup tree from block_inv, then per output
+        inv = tree_down(binv, block, "down")
+        zi = closed(mul_lz(inv, one, "down zi, first output"), "down")
+        zi = closed(mul_lz(inv, c, "down zi"), "down")
+        inv = closed(mul_lz(inv, ops["ZZZ"], "down inv*ZZZ"), "down")
+        tt = closed(mul_lz(zi, ops["ZZ"], "down tt"), "down")
+        sq = closed(sqr_lz(tt, "down tt^2"), "down")  # sqr_lz asserts its operand carry-normalised
+        x = closed(mul_lz(ops["X"], sq, "down x"), "down")  # X: N-form below 5p + e, the square below p + e
+        y = closed(mul_lz(ops["Y"], zi, "down y"), "down")
+        for v, nm in ((x, "x"), (y, "y")):
+            reduce_once_ok(v, "table record " + nm)  # BM_FORM_TABLE: reduce_once of the lazy product itself
+            reduce_once_ok(mul_lz(v, canonical, "wire / mont_flag " + nm), "wire / mont_flag " + nm)  # Fp::mul with the raw 1 or TO64
+    else:
+        # Edwards-BLS12: canonical coordinates in, the canonical Fq::mul = reduce_once(mul_lz) throughout
+        def mul(a, b, name):
+            reduce_once_ok(mul_lz(a, b, "ed " + name), "ed " + name)
+            return canonical
+
+        c = mul(mul(canonical, ops["Z"], "up c0*Z"), ops["Z"], "up c*Z")
+        root = mul(mul(c, c, "trees"), canonical, "inverse a*1")
+        inv = mul(mul(root, c, "trees down"), c, "unfold")
+        zi = mul(inv, c, "zi")
+        mul(inv, ops["Z"], "inv*Z")
+        x, y = mul(ops["X"], zi, "x"), mul(ops["Y"], zi, "y")
+        mul(x, canonical, "from_mont")
+        mul(mul(x, y, "make_base x*y"), canonical, "make_base 2d")
+
+
 def main():
     use_field("Fq")  # Edwards-BLS12 buckets (EdDev): same law over the 9-limb field
     te_formulas(shapes()["canonical"])
+    normalisation_formulas()
     use_field("Fp")
     canonical = shapes()["canonical"]
     X1 = shapes()["stored_x"]
@@ -326,6 +415,7 @@ def main():
 
     te_formulas(canonical)
     conversion_formulas()
+    normalisation_formulas()
 
     # canonical operations on stored (lazy) coordinates: mul() = reduce_once(mul_lz()) needs mul_lz < 2p
     mul_lz(X1, canonical, "gather X*TO64")
