@@ -429,6 +429,57 @@ typedef struct msm377_stage_info {
  * pass ran to the end under it on a route the mode describes. */
 int msm377_g1_read_stage_ex(msm377_ctx* ctx, uint32_t slot, msm377_stage_info* info, void* digits, uint32_t* row_ptr, uint32_t* val_idx, uint32_t* buckets);
 
+/* ---- window records (what the bucket reduction hands to the host tail) ----
+ *
+ * msm377_g1_read_partials describes and copies the window records of the LAST PASS of the last call: what
+ * k_gather_partials (csrc/kernels/reduce.hpp) wrote after the bucket reduction, before the host tail combined them.  It
+ * answers exactly where msm377_g1_read_stage_ex answers (capture mode 1 or 2, a whole G1 or -- mode 2 -- Edwards-BLS12
+ * call from window 0; after a rerun the pass that produced the result) and returns MSM377_ESTATE, writing nothing,
+ * everywhere else.  It waits for the context's stream first: a call returns to its caller while the gather kernel is
+ * still finishing.  `info` is written down on the host beside the launches it describes; with capture off a call launches
+ * and allocates exactly what it did without the read-back.  `words` = NULL only fills `info` (sizes the buffer:
+ * records * points * 4 * coord_words u32).
+ *
+ *   records        window records (wc_out): one per window slot; ONE behind a precomputed table (the wide table's single
+ *                  slot, or the sixteen slots of the 16-bit table folded into slot 0 by k_fold_windows)
+ *   points         points per record (pp): 16, or 20 in the one record of the wide table
+ *   planes         L, the bucket_log of the pass: point 0 is the sum of all 2^L buckets, point 1 + b (b < L) the sum of the
+ *                  buckets whose index has bit b set (bucket index t holds key t + 1).  Points beyond index `planes` are
+ *                  UNSPECIFIED: the gather kernel does not write them and the host tail does not read them
+ *   coord_words    u32 words per coordinate: 12, or 8 for MSM377_STAGE_FORM_ED; a point is four coordinates
+ *   form           MSM377_STAGE_FORM_* of the records
+ *   folded_slots   window slots added into each record before the reduction (16 behind the 16-bit table, else 1)
+ *   tail_kind      the host tail the records went to: 0 twisted Edwards, 1 Weierstrass (XYZZ), 2 Edwards-BLS12
+ *   tail_windows, tail_cbits, tail_planes, tail_short_from
+ *                  the geometry that tail was called with: window count, bits between two windows, bit planes per window,
+ *                  and the first window that is one bit narrower (0: none)
+ *   coop_from, tail_from, columns, tail_lds
+ *                  the reduction schedule of the pass.  Levels [0, tail_from) ran as column launches of up to four levels
+ *                  (k_tree_columns; columns = 1) or one launch per level (columns = 0: k_tree_step below coop_from,
+ *                  k_tree_step_quad from there on); levels [tail_from, planes) in one launch, k_reduce_tail_lds (tail_lds
+ *                  = 1) or k_reduce_tail.  Below coop_from an empty bucket is skipped, from there on it is added
+ *
+ * The record contract (pack_partial in csrc/kernels/reduce.hpp; readers in csrc/fp64_host.hpp):
+ *   - point p of record w starts at word ((w * points + p) * 4) * coord_words; its coordinates are X, Y, T, Z (twisted
+ *     Edwards forms) or X, Y, ZZ, ZZZ (Weierstrass), coord_words little-endian u32 each;
+ *   - EVERY coordinate of every point up to `planes` is CANONICAL: the Montgomery residue v * 2^(32 coord_words) mod p
+ *     (mod q for Edwards-BLS12), below the modulus -- whatever lazy form the bucket held;
+ *   - the tag: bit 31 of the last word of coordinate 0 of POINT 0 of every record of form MSM377_STAGE_FORM_TE is set
+ *     (values are below 2^377, the bit is free) and must be cleared before the coordinate is used.  It is set in no other
+ *     word: not in another coordinate, not in another point, and in no word of a Weierstrass or Edwards-BLS12 record;
+ *   - the identity is (0 : c : 0 : c), c != 0, in both Edwards forms -- any c: from level coop_from on empty buckets are
+ *     added like any other, and a sum that cancels leaves whatever Z it came to -- and ZZ = ZZZ = 0 in the Weierstrass form;
+ *   - every point satisfies its form's invariant: T Z = X Y and the curve equation; ZZ^3 = ZZZ^2. */
+typedef struct msm377_partials_info {
+  uint32_t records, points, planes, coord_words;
+  int32_t form;
+  uint32_t folded_slots;
+  uint32_t tail_kind, tail_windows, tail_cbits, tail_planes, tail_short_from;
+  uint32_t coop_from, tail_from, columns, tail_lds;
+  uint32_t reserved;
+} msm377_partials_info;
+int msm377_g1_read_partials(msm377_ctx* ctx, msm377_partials_info* info, uint32_t* words);
+
 /* ---- base records and window tables (what the hot kernels gather from) ----
  *
  * msm377_g1_read_bases describes and copies the base records the LAST CONVERSION of this context left: any G1 or

@@ -206,8 +206,13 @@ int shim_fp64_inv(int which, const uint64_t* a, uint64_t* plain_inv, uint64_t* m
 // The host tail's Horner chain over window records in a given window geometry (fp64_host.hpp teh_combine / g1h_combine /
 // tail_position): num_windows records of 16 points x 48 words, windows of cbits bits with `planes` bit-plane sums each,
 // the windows from short_from on one bit shorter (0: all alike).  form 0: Edwards records (returns 1 on an exceptional
-// case), 1: Weierstrass records (16-bit windows only).  pieces > 1: the chain cut the way the threaded tail cuts it.
+// case), 1: Weierstrass records (16-bit windows only), 2: Edwards-BLS12 records (16 points x 32 words, sixteen 16-bit
+// windows, 64 bytes out).
 int shim_tail_combine_geom(const uint32_t* partials, int num_windows, int cbits, int planes, int short_from, int form, uint8_t* out96) {
+  if (form == 2) {
+    edh_combine(partials, out96, short_from);
+    return 0;
+  }
   if (form == 1) {
     g1h_combine(partials, num_windows, out96, short_from);
     return 0;

@@ -293,3 +293,194 @@ def ed_record_affine(words):
     pt = (X * zi % fq.P, Y * zi % fq.P)
     assert R.ed_on_curve(pt), "not on the Edwards-BLS12 curve"
     return pt
+
+
+# ---- the window records (msm377_g1_read_partials): what the bucket reduction must hand to the host tail ----
+# csrc/kernels/reduce.hpp lines 10-22: per record, point 0 = the sum of all 2^L buckets and point 1 + b = the sum of the
+# buckets whose INDEX has bit b set, b < L; bucket index t holds key t + 1.  Written from that definition, not from the tree.
+FORM_XYZZ, FORM_TE, FORM_ED = 0, 1, 2  # MSM377_STAGE_FORM_*
+RECORD_TAG = 0x80000000  # TE_RECORD_TAG: bit 31 of the last word of coordinate 0 of point 0 of a FORM_TE record
+
+
+def group(ed=False):
+    """(add, neg, mul, identity, generator, order of the generator) of the curve of a call."""
+    if ed:
+        return R.ed_add, R.ed_neg, R.ed_mul, R.ED_ID, R.ED_G, R.ED_SUBGROUP
+    return R.add, R.neg, R.mul, None, R.G, R.R_ORDER
+
+
+def record_slots(g: Geometry, fold=False):
+    """Window slots that go into each record: one each, or all of them into ONE record behind the 16-bit table (fold)."""
+    count = 1 if g.name == "wide13" else len(g.slots)
+    return [list(range(count))] if fold else [[s] for s in range(count)]
+
+
+def entry_weight(entry, slot, g: Geometry, n: int, fold=False):
+    """(index of the point, factor) of an entry of a slot: the base it adds is [factor] points[index].  lambda behind the
+    GLV front end for entry n + i; 2^wide_offset(w) on the wide table; 2^(16 slot) on the folded 16-bit table, whose window
+    `slot` holds [2^(16 slot)] P_i."""
+    if g.name == "glv8":
+        return (entry, 1) if entry < n else (entry - n, glv_consts()[0])
+    if g.name == "wide13":
+        w, i = divmod(entry, n)
+        return i, 1 << wide_offset(w)
+    return entry, (1 << g.slots[slot].offset) if fold else 1
+
+
+def partial_points(points, cols, g: Geometry, n: int, logs=None, ed=False, fold=False):
+    """For every record of a call (one per slot; ONE with fold, the sixteen slots of the 16-bit table added together; one on
+    the wide table, whose 13 digit columns share a bucket set): [total, plane_0, .., plane_(L-1)] as affine points (the
+    identity: None on G1, (0, 1) on Edwards-BLS12).  total = the sum of all buckets, plane_b = the sum of the buckets whose
+    index t = key - 1 has bit b set.
+    logs[i]: the discrete logarithm of points[i] to the curve's generator, or None where it is not known (low-order points,
+    points outside the subgroup): entries with a known logarithm are summed as integers and cost ONE scalar multiplication
+    per point of a record; the others are added one by one with the group law."""
+    add, neg, mul, ident, gen, order = group(ed)
+    L = g.bucket_log
+    out = []
+    for slots in record_slots(g, fold):
+        log_sum = [0] * (L + 1)
+        rest = [ident] * (L + 1)
+        for slot in slots:
+            s = g.slots[-1] if g.name == "wide13" else g.slots[slot]
+            key, sign = keys_and_signs(cols[slot], s.bias, s.key_unsigned)
+            for entry in np.nonzero(key)[0]:
+                t = int(key[entry]) - 1
+                i, factor = entry_weight(int(entry), slot, g, n, fold)
+                where = [0] + [1 + b for b in range(L) if (t >> b) & 1]
+                if logs is not None and logs[i] is not None:
+                    v = -factor * logs[i] if sign[entry] else factor * logs[i]
+                    for p in where:
+                        log_sum[p] += v
+                else:
+                    assert not ed or factor == 1
+                    pt = mul(points[i], factor) if factor != 1 else points[i]
+                    pt = neg(pt) if sign[entry] else pt
+                    for p in where:
+                        rest[p] = add(rest[p], pt)
+        out.append([add(mul(gen, v % order) if v % order else ident, q) for v, q in zip(log_sum, rest)])
+    return out
+
+
+def record_weights(g: Geometry, fold=False):
+    """Bit offset of every record in the result: the slot's; 0 for the one record behind a table."""
+    return [0 if (fold or g.name == "wide13") else g.slots[slots[0]].offset for slots in record_slots(g, fold)]
+
+
+def weighted_sum(records, g: Geometry, ed=False, fold=False):
+    """sum_records 2^offset (total + sum_b 2^b plane_b) = sum_t (t + 1) B[t] over every window: the call's result."""
+    add, _, mul, ident, _, _ = group(ed)
+    acc = ident
+    for rec, off in zip(records, record_weights(g, fold)):
+        w = rec[0]
+        for b, pl in enumerate(rec[1:]):
+            w = add(w, mul(pl, 1 << b))
+        acc = add(acc, mul(w, 1 << off))
+    return acc
+
+
+def meetings(x, y, L):
+    """Where the reduction tree first adds what started in bucket x to what started in bucket y: a list of (level r, array)
+    with array 0 = the running block, 1 + r' = the list that level r' left behind.  reduce.hpp: level r folds
+    B[lo + k + half] onto B[lo + k] for k < half = 2^L >> (r + 1), in the running block (lo = 0) and in the list of every
+    earlier level r' (lo = 2^L >> (r' + 1)); the upper half is only read, so the block's upper half stays behind as the
+    list of level r.  Replayed on the occupied bucket indices alone; two buckets can meet in more than one array (a pair in
+    the block's upper half meets again in the list that half becomes)."""
+    NB = 1 << L
+    held = {x: {"x"}, y: {"y"}} if x != y else {x: {"x", "y"}}
+    out = []
+    for r in range(L):
+        half = NB >> (r + 1)
+        step = {}
+        for arr in range(r + 1):
+            lo = 0 if arr == 0 else NB >> arr
+            for at, labels in held.items():
+                if lo + half <= at < lo + 2 * half:
+                    step[at - half] = (set(labels), arr)
+        for to, (labels, arr) in sorted(step.items()):
+            have = held.setdefault(to, set())
+            if have and labels and len(have) == 1 and len(labels) == 1 and have != labels:
+                out.append((r, arr))
+            have |= labels
+    return sorted(out)
+
+
+def record_point_contract(words, form, first_point):
+    """The contract of one point of a window record (include/msm377.h): four coordinates of 12 (8: Edwards-BLS12) u32
+    words, each CANONICAL -- below the modulus -- once the tag is taken off; the tag (bit 31 of the last word of
+    coordinate 0) set on point 0 of a FORM_TE record and nowhere else.  Returns the four coordinates as Montgomery
+    residues (radix 2^(32 words))."""
+    cw = 8 if form == FORM_ED else 12
+    mod = R.Q if form == FORM_ED else R.P
+    w = [int(x) for x in words]
+    assert len(w) == 4 * cw
+    tagged = form == FORM_TE and first_point
+    assert bool(w[cw - 1] & RECORD_TAG) == tagged, "the tag bit of coordinate 0 is %s" % ("missing" if tagged else "set where it must not be")
+    w[cw - 1] &= ~RECORD_TAG
+    vals = [sum(w[cw * c + i] << (32 * i) for i in range(cw)) for c in range(4)]
+    for c, v in enumerate(vals):
+        assert v < mod, "coordinate %d is not canonical (at or above the modulus%s)" % (c, "; bit 31 of its last word set" if w[cw * c + cw - 1] >> 31 else "")
+    return vals
+
+
+def record_point_affine(words, form, first_point=False):
+    """Contract, invariant and value of one point of a window record: ZZ^3 = ZZZ^2 (FORM_XYZZ; the identity is ZZ = ZZZ =
+    0), T Z = X Y and the curve equation (both Edwards forms; the identity is (0 : c : 0 : c), c != 0).  FORM_XYZZ and
+    FORM_TE give the Weierstrass affine point or None, FORM_ED the Edwards-BLS12 affine point ((0, 1): the identity)."""
+    import util
+
+    vals = record_point_contract(words, form, first_point)
+    if form == FORM_ED:
+        ri = pow(1 << 256, -1, R.Q)
+        X, Y, T, Z = (v * ri % R.Q for v in vals)
+        assert Z != 0 and (X * Y - T * Z) % R.Q == 0, "extended-coordinate invariant T Z = X Y violated"
+        zi = pow(Z, -1, R.Q)
+        pt = (X * zi % R.Q, Y * zi % R.Q)
+        assert R.ed_on_curve(pt), "not on the Edwards-BLS12 curve"
+        return pt
+    plain = [x for v in vals for x in util._words12(v)]
+    if form == FORM_TE:
+        return util.affine_from_te_record_words(plain)
+    ri = pow(util.R64, -1, R.P)
+    if vals[2] == 0:
+        assert vals[3] == 0, "the Weierstrass identity stores ZZ = ZZZ = 0"
+    else:
+        assert vals[3] * ri % R.P != 0
+    return util.affine_from_record_words(plain)
+
+
+def is_stored_identity(words, form):
+    """The identity AS STORED: (0 : c : 0 : c) with c != 0 in the Edwards forms, ZZ = ZZZ = 0 in the Weierstrass form."""
+    cw = 8 if form == FORM_ED else 12
+    w = [int(x) for x in words]
+    w[cw - 1] &= ~RECORD_TAG
+    c = [w[cw * k : cw * k + cw] for k in range(4)]
+    if form == FORM_XYZZ:
+        return not any(c[2]) and not any(c[3])
+    return not any(c[0]) and not any(c[2]) and c[1] == c[3] and any(c[1])
+
+
+def ed_record_point_words(pt, z=1):
+    """An Edwards-BLS12 affine point -> one point of a window record: X, Y, T, Z as 8 u32 words each, radix 2^256."""
+    X, Y, T, Z = pt[0] * z % R.Q, pt[1] * z % R.Q, pt[0] * pt[1] * z % R.Q, z % R.Q
+    return [((v << 256) % R.Q >> (32 * i)) & 0xFFFFFFFF for v in (X, Y, T, Z) for i in range(8)]
+
+
+def encode_records(records, form, points_per_record=16, z=lambda: 1, filler=None):
+    """The model's points as the window records the host tail reads: `points_per_record` points each, the model's
+    L + 1 first, then `filler` words (points beyond `planes` are unspecified: a tail that read them would show)."""
+    import util
+
+    out = []
+    for rec in records:
+        for i in range(points_per_record):
+            if i < len(rec):
+                if form == FORM_ED:
+                    out += ed_record_point_words(rec[i], z())
+                elif form == FORM_TE:
+                    out += util.te_record_point_words(rec[i], z(), tag=(i == 0))
+                else:
+                    out += util.record_point_words(rec[i], z())
+            else:
+                out += list(filler) if filler is not None else [0xFFFFFFFF] * (32 if form == FORM_ED else 48)
+    return np.array(out, dtype=np.uint32)

@@ -156,6 +156,49 @@ def check_slot(engine, slot, g, cols, c, points, n, form, small=False, key_max=N
     return info
 
 
+def short_point(pt):
+    """A point in a failure message: the identity, or the head of its x."""
+    return "the identity" if pt in (None, R.ED_ID) else "x = %s..." % hex(pt[0])[:20]
+
+
+TAIL_SHORT_FROM = {"even16": 13, "narrow22": 11}  # the first window that is one bit narrower (WindowPlan::short_from)
+
+
+def check_records(engine, g, model, form, fold=False, label="", schedule=None):
+    """The window records of the last call (msm377_g1_read_partials) against stage_model.partial_points: `info` against the
+    geometry, then EVERY point of EVERY record up to `planes` -- its words against the record contract of include/msm377.h
+    (canonical coordinates, the tag on coordinate 0 of point 0 of a twisted Edwards record and nowhere else), its invariant
+    and its value; where the model says identity, the identity as stored.  Points beyond `planes` are not read.
+    schedule: what `info` must report of the reduction schedule (a dict over coop_from, tail_from, columns, tail_lds)."""
+    info, words = engine.read_partials()
+    L, one = g.bucket_log, g.name == "wide13" or fold
+    tag = (label, g.name)
+    assert info.records == len(model) == (1 if one else len(g.slots)), (tag, info)
+    assert (info.points, info.planes, info.coord_words, info.form) == (20 if g.name == "wide13" else 16, L, 8 if form == FORM_ED else 12, form), (tag, info)
+    assert info.folded_slots == (len(g.slots) if fold else 1), (tag, info)
+    assert info.tail_kind == {FORM_TE: 0, FORM_XYZZ: 1, FORM_ED: 2}[form], (tag, info)
+    assert (info.tail_windows, info.tail_cbits, info.tail_planes, info.tail_short_from) == (info.records, L + 1, L, TAIL_SHORT_FROM.get(g.name, 0)), (tag, info)
+    assert info.coop_from <= L and info.tail_from <= L and info.columns in (0, 1) and info.tail_lds in (0, 1), (tag, info)
+    if info.tail_from == L:
+        assert info.tail_lds == 0, (tag, "no single-launch tail ran")
+    for key, want in (schedule or {}).items():
+        assert getattr(info, key) == want, (tag, "schedule", key, getattr(info, key), want)
+    assert words.shape == (info.records, info.points, 4, info.coord_words) and info.planes + 1 <= info.points, tag
+    ident = model_identity(form)
+    for w in range(info.records):
+        for p in range(L + 1):
+            where = (label, g.name, "record %d" % w, "the total" if p == 0 else "plane %d" % (p - 1))
+            flat = words[w, p].ravel()
+            try:
+                got = M.record_point_affine(flat, form, first_point=p == 0)
+            except AssertionError as e:
+                raise AssertionError("%s: %s" % (where, e)) from e
+            assert got == model[w][p], "%s: value: the record holds %s, the model %s" % (where, short_point(got), short_point(model[w][p]))
+            if model[w][p] == ident:
+                assert M.is_stored_identity(flat, form), (where, "the identity is not stored as the form writes it")
+    return info
+
+
 def tracked_key_max(g, cols):
     """The slots whose largest key the decomposition measures, and the word it must publish: window 15 of sixteen equal
     windows; the unsigned top slot of a short call on 2^15 buckets.  Every other slot's word stays untracked."""
@@ -167,8 +210,10 @@ def tracked_key_max(g, cols):
     return {}
 
 
-def run_case(engine, call, g, scalars, points_wire, form, slots, other_scalars, expected, small=(), label="", reruns=0):
-    """call(scalars) runs the MSM under test; first once with other_scalars (same size, same context)."""
+def run_case(engine, call, g, scalars, points_wire, form, slots, other_scalars, expected, small=(), label="", reruns=0, records=None, schedule=None):
+    """call(scalars) runs the MSM under test; first once with other_scalars (same size, same context).
+    records: the model's window records (stage_model.partial_points) -- compared as the LAST stage, after the buckets and
+    before the result (check_records; schedule: what the read-back must report of the reduction schedule)."""
     n = len(scalars)
     points = wire_points(points_wire, form)
     cols, flags = M.digit_matrix(scalars, g)
@@ -194,6 +239,8 @@ def run_case(engine, call, g, scalars, points_wire, form, slots, other_scalars, 
             for slot in slots:
                 info = check_slot(engine, slot, g, cols, csrs[slot], points, n, form, small=slot in small, key_max=key_max.get(slot), label=label)
             assert info.geometry_reruns == reruns_before + reruns, (label, "reruns on another window geometry", info.geometry_reruns - reruns_before)
+            if records is not None:
+                check_records(engine, g, records, form, label=label, schedule=schedule)
         except AssertionError as e:
             raise AssertionError("%s [the call's result is %s]" % (e, "right" if got == expected else "WRONG")) from e
         assert got == expected, (label, "every stage read agrees with the model, the result does not")

@@ -311,3 +311,251 @@ def test_ed_stage_cases_meet_the_decode_floors():
     for ks in (V.few_distinct_scalars(3000, 5, 8), V.one_long_row_scalars(1100, 600, 10), V.every_curve_point(600, 1)[1]):
         assert M.digit_matrix(ks, M.even16())[1] == 0
     assert len([k for k in V.even_edge_scalars() if M.recode(k, M.even16()).flags == 0]) == 13  # the others rerun
+
+
+# ---- the window records: stage_model.partial_points, the record decode, and the inputs of tests/test_partial_records_gpu.py ----
+import ctypes
+
+import partial_cases as C
+from test_field29_host import shim  # noqa: F401  (the fixture: the product's host tail behind ctypes)
+
+# (name, geometry, Edwards-BLS12, folded table): every way a call lays out its records
+RECORD_GEOMETRIES = [
+    ("even16", M.even16(), False, False), ("equal16", M.equal16(), False, False), ("narrow22", M.narrow22(), False, False),
+    ("short 64/15", M.short(64, 15), False, False), ("short 64/11", M.short(64, 11), False, False), ("short 200/15", M.short(200, 15), False, False),
+    ("wide13", M.wide13(), False, False), ("glv8", M.glv8(), False, False), ("table16", M.equal16(), False, True),
+    ("ed even16", M.even16(), True, False), ("ed equal16", M.equal16(), True, False),
+]
+RECORD_IDS = [x[0] for x in RECORD_GEOMETRIES]
+
+
+def naive(points, scalars, ed):
+    return R.ed_msm_naive(points, scalars) if ed else R.msm_naive(points, scalars)
+
+
+def small_inputs(g, ed, seed):
+    """A dozen points -- random ones, one twice, one with its negative, low-order ones on Edwards-BLS12 -- under random
+    scalars and the geometry's edge scalars that fit it."""
+    rnd = random.Random("record model/%s/%s" % (g.name, seed))
+    _, neg, mul, _, gen, order = M.group(ed)
+    logs = [rnd.randrange(1, order) for _ in range(8)]
+    logs += [logs[0], order - logs[1]]
+    points = [mul(gen, a) for a in logs]
+    if ed:
+        from check_vectors import ed_low_order_points
+
+        low = ed_low_order_points()
+        points += low
+        logs += [None] * len(low)
+    top = g.bits if g.name == "short" else 253
+    pool = [k for k in planted(g, top) if M.recode(k, g).flags == 0 and k < order]
+    ks = [rnd.choice(pool) if i % 3 == 0 else rnd.randrange(min(order, 1 << top)) for i in range(len(points))]
+    ks = [k if M.recode(k, g).flags == 0 else 1 for k in ks]
+    return points, logs, ks
+
+
+@pytest.mark.parametrize("name,g,ed,fold", RECORD_GEOMETRIES, ids=RECORD_IDS)
+def test_partial_points_weigh_up_to_the_naive_msm(name, g, ed, fold):
+    """(a) sum_records 2^offset (total + sum_b 2^b plane_b) = msm_naive, with the logarithms and with the group law alone;
+    both give the same points."""
+    for seed in range(1 if ed else 2):  # (pyref.ed_mul takes 20 ms)
+        points, logs, ks = small_inputs(g, ed, seed)
+        n = len(ks)
+        cols, flags = M.digit_matrix(ks, g)
+        assert flags == 0
+        by_law = M.partial_points(points, cols, g, n, ed=ed, fold=fold)
+        by_log = M.partial_points(points, cols, g, n, logs=logs, ed=ed, fold=fold)
+        assert by_law == by_log, name
+        assert len(by_law) == (1 if fold or g.name == "wide13" else len(g.slots)) and all(len(rec) == g.bucket_log + 1 for rec in by_law)
+        assert M.weighted_sum(by_law, g, ed=ed, fold=fold) == naive(points, ks, ed), name
+
+
+def tail_args(g, ed, fold, form):
+    """(windows, cbits, planes, short_from, shim form) the product calls its host tail with at this geometry."""
+    L = g.bucket_log
+    records = 1 if fold or g.name == "wide13" else len(g.slots)
+    short_from = {"even16": 13, "narrow22": 11}.get(g.name, 0)
+    return records, L + 1, L, short_from, {M.FORM_TE: 0, M.FORM_XYZZ: 1, M.FORM_ED: 2}[form]
+
+
+def through_the_host_tail(shim, model, g, ed, fold, form, rnd):
+    words = M.encode_records(model, form, 20 if g.name == "wide13" else 16, z=lambda: rnd.randrange(1, R.Q if ed else R.P))
+    arr = (ctypes.c_uint32 * len(words))(*[int(x) for x in words])
+    out = ctypes.create_string_buffer(64 if ed else 96)
+    assert shim.shim_tail_combine_geom(arr, *tail_args(g, ed, fold, form), out) == 0
+    return out.raw
+
+
+@pytest.mark.parametrize("name,g,ed,fold", RECORD_GEOMETRIES, ids=RECORD_IDS)
+def test_partial_points_through_the_products_host_tail(shim, name, g, ed, fold):
+    """(b) The model's points, encoded as records under random projective factors with 0xFFFFFFFF words beyond `planes`, give
+    the call's 96 (64) bytes through teh_combine / g1h_combine / edh_combine at the geometry the product passes.  The
+    Weierstrass tail takes 16-bit windows only: equal16 and glv8."""
+    rnd = random.Random("tail/" + name)
+    points, logs, ks = small_inputs(g, ed, 7)
+    cols, _ = M.digit_matrix(ks, g)
+    model = M.partial_points(points, cols, g, len(ks), logs=logs, ed=ed, fold=fold)
+    exp = R.ed_encode_result(naive(points, ks, ed)) if ed else R.encode_result(naive(points, ks, ed))
+    forms = [M.FORM_ED] if ed else [M.FORM_XYZZ] if g.name == "glv8" else [M.FORM_TE, M.FORM_XYZZ] if name == "equal16" else [M.FORM_TE]
+    for form in forms:
+        assert through_the_host_tail(shim, model, g, ed, fold, form, rnd) == exp, (name, form)
+
+
+def test_record_point_decode_and_contract():
+    """record_point_affine inverts the encoders in each form and refuses what the contract forbids: a coordinate at or
+    above the modulus, a tag in the wrong place or missing, a broken invariant; is_stored_identity tells the identity as
+    stored from a point that merely decodes to it."""
+    rnd = random.Random("record decode")
+    p = R.mul(R.G, 0xDEC0DE)
+    e = R.ed_mul(R.ED_G, 0xDEC0DE)
+    for form, pt, ident in ((M.FORM_TE, p, None), (M.FORM_XYZZ, p, None), (M.FORM_ED, e, R.ED_ID)):
+        cw, mod = (8, R.Q) if form == M.FORM_ED else (12, R.P)
+        for first in (True, False):
+            for value in (pt, ident):
+                words = list(M.encode_records([[value] if first else [ident, value]], form, 2, z=lambda: rnd.randrange(2, mod))[(0 if first else 4 * cw) : (4 * cw if first else 8 * cw)])
+                assert M.record_point_affine(words, form, first_point=first) == value
+                assert M.is_stored_identity(words, form) == (value == ident)
+                bad = list(words)  # + modulus on coordinate 1: the same point, not canonical
+                v = sum(int(x) << (32 * i) for i, x in enumerate(bad[cw : 2 * cw])) + mod
+                bad[cw : 2 * cw] = [(v >> (32 * i)) & 0xFFFFFFFF for i in range(cw)]
+                with pytest.raises(AssertionError, match="not canonical"):
+                    M.record_point_affine(bad, form, first_point=first)
+                bad = list(words)  # the tag where it must not be / missing where it must be
+                bad[cw - 1] ^= M.RECORD_TAG
+                with pytest.raises(AssertionError, match="tag"):
+                    M.record_point_affine(bad, form, first_point=first)
+                bad = list(words)  # the tag bit on another coordinate: at or above the modulus
+                bad[3 * cw - 1] |= M.RECORD_TAG
+                with pytest.raises(AssertionError, match="not canonical"):
+                    M.record_point_affine(bad, form, first_point=first)
+                if value != ident:
+                    bad = list(words)
+                    bad[2 * cw] ^= 1  # T / ZZ off by one
+                    with pytest.raises(AssertionError, match="invariant"):
+                        M.record_point_affine(bad, form, first_point=first)
+
+
+def test_meetings_of_the_reduction_tree_against_a_replay_of_all_buckets():
+    """stage_model.meetings follows two occupied buckets; here the whole array of 2^L sets is folded level by level as
+    reduce.hpp defines it, for L = 6, and every pair must meet where meetings says (and end in the same record points)."""
+    L = 6
+    NB = 1 << L
+    for x in range(NB):
+        for y in range(x + 1, NB):
+            B = [set() for _ in range(NB)]
+            B[x], B[y] = {"x"}, {"y"}
+            met = []
+            for r in range(L):
+                half = NB >> (r + 1)
+                for arr in range(r + 1):
+                    lo = 0 if arr == 0 else NB >> arr
+                    for k in range(half):
+                        a, b = B[lo + k], B[lo + k + half]
+                        if len(a) == 1 and len(b) == 1 and a != b:
+                            met.append((r, arr))
+                        B[lo + k] = a | b
+            assert met == M.meetings(x, y, L), (x, y)
+            assert B[0] == {"x", "y"}
+            for b in range(L):
+                assert B[1 << b] == ({"x"} if (x >> b) & 1 else set()) | ({"y"} if (y >> b) & 1 else set()), (x, y, b)
+
+
+LADDER_GEOMETRIES = [x for x in RECORD_GEOMETRIES if x[0] in ("even16", "equal16", "narrow22", "glv8", "ed even16", "wide13", "table16")]
+
+
+def occupied_by_the_model(case):
+    """record -> bucket indices that hold entries, from the model's digit matrix alone."""
+    cols, flags = M.digit_matrix(case.scalars, case.g)
+    assert flags == 0
+    out = {}
+    for rec, slots in enumerate(M.record_slots(case.g, case.fold)):
+        for slot in slots:
+            s = case.g.slots[-1] if case.g.name == "wide13" else case.g.slots[slot]
+            key, _ = M.keys_and_signs(cols[slot], s.bias, s.key_unsigned)
+            for k in key[key > 0]:
+                out.setdefault(rec, set()).add(int(k) - 1)
+    return out
+
+
+def check_preconditions(case):
+    """(c) What a case promises, from the model alone: which buckets are occupied, where its pair meets, which planes are
+    empty -- and that its records weigh up to its expected result."""
+    L = case.g.bucket_log
+    assert occupied_by_the_model(case) == {r: s for r, s in case.occupied.items() if s}, case.name
+    for rec, where in case.meet.items():
+        x, y = sorted(case.occupied[rec])
+        assert M.meetings(x, y, L) == where, (case.name, rec)
+    model = C.model_records(case)
+    ident = R.ED_ID if case.ed else None
+    for rec, points in enumerate(model):
+        held = case.occupied.get(rec, set())
+        for b in range(L):
+            if not any((t >> b) & 1 for t in held):
+                assert points[1 + b] == ident, (case.name, rec, b, "a plane no occupied bucket feeds")
+        if not held:
+            assert points[0] == ident
+    got = M.weighted_sum(model, case.g, ed=case.ed, fold=case.fold)
+    assert (R.ed_encode_result(got) if case.ed else R.encode_result(got)) == C.expected_result(case), case.name
+    return model
+
+
+@pytest.mark.parametrize("name,g,ed,fold", RECORD_GEOMETRIES, ids=RECORD_IDS)
+def test_planted_planes_hold_what_they_promise(name, g, ed, fold):
+    """One point alone in bucket 2^b: plane b and the total ARE that point, every other plane is the identity.  Coverage:
+    every plane of the geometry in some window; every window of a full-width geometry used."""
+    ident = R.ED_ID if ed else None
+    seen_planes = set()
+    uses = [range(8), range(8, 16)] if g.name == "glv8" else [None]
+    for use in uses:
+        for case in C.planted(g, ed=ed, fold=fold, use=use):
+            model = check_preconditions(case)
+            for rec, held in case.occupied.items():
+                if len(held) != 1:
+                    continue
+                (t,) = held
+                b = t.bit_length() - 1
+                assert t == 1 << b
+                pts = [pt for pt, k in zip(case.points, case.scalars) if k]  # (single-record cases: one scalar)
+                assert model[rec][0] == model[rec][1 + b] != ident
+                assert all(model[rec][1 + c] == ident for c in range(g.bucket_log) if c != b)
+                assert model[rec][0] in pts or fold or g.name in ("wide13", "glv8")  # (a table window / phi(P) carries a factor)
+                seen_planes.add(b)
+    if g.name != "short":
+        assert seen_planes == set(range(g.bucket_log)), (name, seen_planes)
+    for case in C.extras(g, ed=ed, fold=fold):
+        model = check_preconditions(case)
+        if case.name in ("extras", "P and -P"):
+            rec = 0 if (fold or g.name == "wide13") else 3
+            assert model[rec][0] == ident and model[rec][1 + g.bucket_log - 1] != ident and model[rec][1] != ident, name
+        if case.name == "extras":
+            assert all(pt == ident for pt in model[2]) and all(pt != ident for pt in model[0]), name  # an empty window; index 2^L - 1: every plane set
+
+
+@pytest.mark.parametrize("name,g,ed,fold", LADDER_GEOMETRIES, ids=[x[0] for x in LADDER_GEOMETRIES])
+def test_the_ladder_meets_where_it_promises(name, g, ed, fold):
+    """Indices 0 and 2^L >> (r + 1) first meet at level r in the running block; lo + k and lo + k + half meet at level r in
+    the block and in the list of level r - age.  A doubling doubles, a cancellation leaves total O and plane -P."""
+    ident = R.ED_ID if ed else None
+    single = fold or g.name == "wide13"
+    kinds = C.SECOND + (("order2", "order4") if ed else ())
+    for kind in kinds:
+        for age in (0, 1, 2, 3) if kind in C.SECOND else (0,):  # the ages the GPU cases run
+            levels = [lv for lv in range(g.bucket_log) if lv >= age]
+            todo, done_all = ([levels[0]], [levels[-1]]) if single else (levels,), []
+            for lv_list in todo:
+                use = range(8, 16) if g.name == "glv8" and age % 2 else None
+                left = list(lv_list)
+                while left:
+                    case = C.ladder(g, kind, ed=ed, age=age, use=use, levels=left, fold=fold)
+                    model = check_preconditions(case)
+                    done = C.levels_in(case)
+                    done_all += done
+                    left = [lv for lv in left if lv not in done]
+                    for rec, where in case.meet.items():
+                        assert where[0][1] == 0 and (len(where) == 1) == (age == 0)
+                        if kind == "negative":
+                            assert model[rec][0] == ident and sum(pt != ident for pt in model[rec][1:]) >= 1
+                        if kind == "same" and age == 0 and not single and g.name != "glv8":
+                            assert model[rec][0] == M.group(ed)[0](case.points[0], case.points[0])
+            if not single:
+                assert sorted(done_all) == levels, (name, kind, age)

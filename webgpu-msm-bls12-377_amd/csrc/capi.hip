@@ -196,6 +196,25 @@ int msm377_g1_read_stage_ex(msm377_ctx* ctx, uint32_t slot, msm377_stage_info* i
   return MSM377_OK;
 }
 
+// The window records of the last pass: layout and pointer are those enqueue_reduce wrote down beside the gather launch.
+int msm377_g1_read_partials(msm377_ctx* ctx, msm377_partials_info* info, uint32_t* words) {
+  if (!ctx) return MSM377_EINVAL;
+  const StageLayout& sl = ctx->last.stage;
+  if (!ctx->capture || !sl.valid || !ctx->d_buckets_snap || !sl.d_partials) {
+    ctx->err = "no captured window records: stage capture is off, or the last call is not one the capture mode describes";
+    return MSM377_ESTATE;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // a zero-copy call returns while k_gather_partials is still finishing (kernels/reduce.hpp publish_to_host, INVARIANT)
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (info) *info = sl.partials;
+  if (words) {
+    const size_t count = (size_t)sl.partials.records * sl.partials.points * 4 * sl.partials.coord_words;
+    HIP_TRY(ctx, hipMemcpy(words, sl.d_partials, count * 4, hipMemcpyDeviceToHost));
+  }
+  return MSM377_OK;
+}
+
 // The base records of the last conversion: layout and pointer are those note_bases (sequencer.hip) wrote down beside the
 // launch; this is a copy.
 int msm377_g1_read_bases(msm377_ctx* ctx, msm377_bases_info* info, uint64_t first, uint64_t count, uint32_t* words) {

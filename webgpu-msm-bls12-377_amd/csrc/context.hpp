@@ -147,6 +147,10 @@ struct StageLayout {
   const void* d_digits = nullptr;       // the digit matrix the decomposition wrote: ctx->d_digits (u16) or ctx->wide.digits (u32)
   const uint32_t* d_key_max = nullptr;  // the call's key_max words, or null where the sort reads none
   uint32_t coord_words = 16, limbs = 13;  // a bucket record of the pass: four coordinate slots of coord_words words, `limbs` of them used
+  // The window records of the pass, for msm377_g1_read_partials: written in enqueue_reduce beside the k_gather_partials
+  // launch, from the launch's own arguments and the plan the host tail is then called with.
+  msm377_partials_info partials = {};
+  const uint32_t* d_partials = nullptr;  // what k_gather_partials wrote to (slot 0 of ctx->d_partials for every call the capture modes describe)
 };
 
 // What the last base conversion left, for msm377_g1_read_bases: written on the host where the conversion is queued

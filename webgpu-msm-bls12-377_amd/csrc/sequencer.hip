@@ -641,8 +641,10 @@ int enqueue_reduce(msm377_ctx* ctx, const LaunchRecord& k) {
     HIP_TRY(ctx, hipGetLastError());
     m = half;
   }
+  const bool columns = ctx->knobs.reduce_columns != 0;
+  bool tail_in_lds = false;
   uint32_t r = 0;
-  while (ctx->knobs.reduce_columns && r < k.tail_from) {
+  while (columns && r < k.tail_from) {
     const uint32_t levels = std::min(k.tail_from - r, COLUMN_LEVELS_MAX);
     const uint32_t threads = (r + 1) * (k.buckets >> (r + 1));  // per window: (r + 1) arrays x (buckets >> (r + levels)) columns x 2^(levels-1) lanes
     hipLaunchKernelGGL(k_tree_columns<CV>, dim3((threads + 255) / 256, k.wc_out), dim3(256), 0, st, ctx->d_buckets, k.L, r, levels, k.coop_from, threads, k.d_err);
@@ -658,7 +660,7 @@ int enqueue_reduce(msm377_ctx* ctx, const LaunchRecord& k) {
     HIP_TRY(ctx, hipGetLastError());
   }
   if (k.tail_from < k.L) {
-    const bool in_lds = ctx->knobs.tail_lds && k.tail_lds_bytes <= TAIL_LDS_BYTES_MAX;
+    const bool in_lds = tail_in_lds = ctx->knobs.tail_lds && k.tail_lds_bytes <= TAIL_LDS_BYTES_MAX;
     if (in_lds && k.tail_lds_bytes > 64 * 1024)  // (only with MSM377_TAIL_FROM below its default; per device, so every time)
       HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_reduce_tail_lds<CV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TAIL_LDS_BYTES_MAX));
     if (in_lds)
@@ -672,6 +674,14 @@ int enqueue_reduce(msm377_ctx* ctx, const LaunchRecord& k) {
   hipLaunchKernelGGL(k_gather_partials<CV>, dim3((k.wc_out * k.pp * 4 + 63) / 64), dim3(64), 0, st, ctx->d_buckets, k.d_partials, k.wc_out, k.L, zc ? ctx->zc.dm_partials : nullptr,
                      zc ? ctx->zc.dm_flag : nullptr, zc ? ctx->zc.d_count : nullptr, zc ? (const int*)k.d_err : nullptr, zc ? ctx->zc.out_seq : 0u, k.pp);
   HIP_TRY(ctx, hipGetLastError());
+  // The records of the pass (msm377_g1_read_partials), from the arguments of the launches above and the plan run_tail takes.
+  msm377_partials_info& pi = ctx->last.stage.partials = msm377_partials_info{};
+  pi.records = k.wc_out, pi.points = k.pp, pi.planes = k.L, pi.coord_words = k.cv.out_words / 4, pi.form = k.cv.form;
+  pi.folded_slots = k.plan.table ? k.slots : 1u;
+  pi.tail_kind = (uint32_t)k.plan.tail, pi.tail_windows = (uint32_t)k.plan.records, pi.tail_cbits = (uint32_t)k.plan.cbits(), pi.tail_planes = (uint32_t)k.plan.planes();
+  pi.tail_short_from = (uint32_t)k.plan.short_from;
+  pi.coop_from = k.coop_from, pi.tail_from = k.tail_from, pi.columns = columns ? 1u : 0u, pi.tail_lds = tail_in_lds ? 1u : 0u;
+  ctx->last.stage.d_partials = k.d_partials;
   return MSM377_OK;
 }
 

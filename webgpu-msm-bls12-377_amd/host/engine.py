@@ -88,6 +88,34 @@ class StageInfo(NamedTuple):
     key_max: Tuple[int, ...]
 
 
+class _PartialsInfoStruct(ctypes.Structure):  # msm377_partials_info
+    _fields_ = [(name, ctypes.c_int32 if name == "form" else ctypes.c_uint32) for name in (
+        "records", "points", "planes", "coord_words", "form", "folded_slots", "tail_kind", "tail_windows", "tail_cbits", "tail_planes", "tail_short_from",
+        "coop_from", "tail_from", "columns", "tail_lds", "reserved")]
+
+
+class PartialsInfo(NamedTuple):
+    """msm377_partials_info: the window records of the last call's last pass, the geometry the host tail combined them
+    with and the schedule the bucket reduction ran (include/msm377.h)."""
+
+    records: int
+    points: int
+    planes: int
+    coord_words: int
+    form: int
+    folded_slots: int
+    tail_kind: int
+    tail_windows: int
+    tail_cbits: int
+    tail_planes: int
+    tail_short_from: int
+    coop_from: int
+    tail_from: int
+    columns: int
+    tail_lds: int
+
+
+TAIL_TE, TAIL_XYZZ, TAIL_ED = 0, 1, 2  # PartialsInfo.tail_kind
 BASES_TE_PROJECTIVE, BASES_TE_AFFINE, BASES_WEIERSTRASS, BASES_ED = 0, 1, 2, 3  # MSM377_BASES_*: BasesInfo.form
 MUL_TABLE_SINGLE, MUL_TABLE_MULTI, MUL_TABLE_GENERATOR = 0, 1, 2  # MSM377_MUL_TABLE_*
 _MUL_TABLES = {"single": MUL_TABLE_SINGLE, "multi": MUL_TABLE_MULTI, "generator": MUL_TABLE_GENERATOR}
@@ -237,6 +265,7 @@ def load_library():
         "msm377_g1_read_stage": (i32, [vp, u32, vp, vp, vp, vp]),
         "msm377_g1_read_stage_ex": (i32, [vp, u32, vp, vp, vp, vp, vp]),
         "msm377_g1_read_bases": (i32, [vp, vp, u64, u64, vp]),
+        "msm377_g1_read_partials": (i32, [vp, vp, vp]),
         "msm377_g1_read_mul_table": (i32, [vp, u32, u32, vp, u64, u64, vp]),
         "msm377_g1_xyzz_to_affine": (i32, [vp, vp]),
         "msm377_g1_fold_window_partials": (i32, [vp, ctypes.c_uint32]),
@@ -1123,6 +1152,21 @@ class MsmEngine:
             ptr = [res[k].ctypes.data if k in res else None for k in ("digits", "row_ptr", "val_idx", "buckets")]
             self._check(self._lib.msm377_g1_read_stage_ex(self._ctx, int(slot), None, *ptr), "msm377_g1_read_stage_ex")
         return info, res
+
+    def read_partials(self, info_only: bool = False):
+        """(PartialsInfo, records) of the window records the last call's last pass handed to the host tail
+        (msm377_g1_read_partials): a numpy array of shape (records, points, 4, coord_words) u32, or None with
+        ``info_only``.  Points beyond ``planes`` are unspecified.  MsmError(ESTATE) wherever read_stage_ex refuses."""
+        import numpy as np
+
+        raw = _PartialsInfoStruct()
+        self._check(self._lib.msm377_g1_read_partials(self._ctx, ctypes.addressof(raw), None), "msm377_g1_read_partials")
+        info = PartialsInfo(*(int(getattr(raw, f)) for f in PartialsInfo._fields))
+        if info_only:
+            return info, None
+        words = np.empty((info.records, info.points, 4, info.coord_words), dtype=np.uint32)
+        self._check(self._lib.msm377_g1_read_partials(self._ctx, None, words.ctypes.data), "msm377_g1_read_partials")
+        return info, words
 
     def read_stage(self, slot: int, n: int, want=("digits", "row_ptr", "val_idx", "buckets")):
         """Returns a dict of numpy arrays for window slot ``slot`` of the last call."""
