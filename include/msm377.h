@@ -531,8 +531,8 @@ int msm377_g1_read_bases(msm377_ctx* ctx, msm377_bases_info* info, uint64_t firs
  *          generator table: the set is not keyed)
  * Records [first, first + count) go to `words`; call with count = 0 and `words` = NULL to fill `info` alone.
  * MSM377_ESTATE, and nothing written, when that table is not valid (never built, a build that failed, a dropped set, an
- * index beyond the set).  The per-pass [1..8]P tables of the variable-base and pairwise calls are never valid between calls
- * and cannot be read. */
+ * index beyond the set).  The per-pass [1..8]P tables of the variable-base and pairwise calls are not window tables and are
+ * not read from here: msm377_g1_read_walk_tables (below) copies the tables of the last pass. */
 #define MSM377_MUL_TABLE_SINGLE 0
 #define MSM377_MUL_TABLE_MULTI 1
 #define MSM377_MUL_TABLE_GENERATOR 2
@@ -542,6 +542,75 @@ typedef struct msm377_mul_table_info {
   uint8_t key[96];
 } msm377_mul_table_info;
 int msm377_g1_read_mul_table(msm377_ctx* ctx, uint32_t which, uint32_t index, msm377_mul_table_info* info, uint64_t first, uint64_t count, uint32_t* words);
+
+/* ---- the stash of a batch call (what the walk kernels hand to the normalisation) ----
+ *
+ * msm377_read_walk_stash describes and copies what the LAST PASS of the last batch DEVICE call left in the stash: the
+ * projective point of every output as its walk kernel stored it (k_bm_accumulate, k_bmm_accumulate, k_cr_accumulate and
+ * k_cr_fold, k_bmv_accumulate, k_bl2_accumulate, k_edbm_accumulate) and the exclusive running products the up-sweep of the
+ * normalisation (k_bm_up, k_edbm_up) put beside them.  It covers msm377_g1_batch_mul*, _batch_mul_multi*, _commit_rows*,
+ * _batch_mul_var*, _batch_lincomb2* and msm377_ed_batch_mul_multi*; a host-buffer call is one device call per piece of at
+ * most 2^20 scalars, and the description is that of its last piece.  `info` is written down on the host beside the
+ * launches it describes; a call that does not use the read-back launches and allocates exactly what it did without it.
+ *
+ *   kind           MSM377_WALK_*: the call
+ *   form           MSM377_WALK_FORM_XYZZ: 52 point words X, Y, ZZ, ZZZ (13 limbs each) and 13 running-product words
+ *                  MSM377_WALK_FORM_ED:   36 point words X, Y, T, Z (9 limbs each) and 9 running-product words
+ *   point_words, product_words   52 and 13, or 36 and 9
+ *   product_pad    3: the words the last 16-byte piece of a running product holds behind its limbs; they are zero
+ *   n              outputs of the device call
+ *   pass_offset, m the last pass: outputs pass_offset .. pass_offset + m - 1 of the call; stash point i is output pass_offset + i
+ *   width          window width the pass walked: 8 or 16; 4 for the variable-base and the pairwise call
+ *   k              bases, generators or terms per output: 1 (batch_mul, batch_mul_var), 2 (batch_lincomb2), else the call's k
+ *   segments, stride   row commitments: the plan's segments and the stride the launches were given -- the partial sum of
+ *                  segment g of row i is stash point g * stride + i.  Segment 0 holds the fold (k_cr_fold's sum over all
+ *                  segments; the walk's own sum where segments == 1), segments 1 and up the partial sums the fold read and
+ *                  left.  Every other call: segments 1, stride 0
+ *
+ * The stash contract (csrc/kernels/batch_mul.hpp, ed_batch_mul.hpp; tools/check_lazy_bounds.py NORMALISATION_OPERANDS):
+ *   - XYZZ: limbs 0..11 of every coordinate below 2^29; X below 5p + 2^354, Y, ZZ, ZZZ below p + 2^354; ZZ^3 = ZZZ^2; a live
+ *     point has ZZ and ZZZ non-zero mod p; the identity is X = 0, Y = the Montgomery 1, ZZ = ZZZ = 0, word for word;
+ *   - ED: every coordinate canonical (below q), Z non-zero, T Z = X Y; the identity is any (0 : c : 0 : c);
+ *   - running products: for thread tid of workgroup blk, whose outputs are blk * 1024 + j * 256 + tid, j < 4, the words of
+ *     output j = 0 are the Montgomery 1, those of output j + 1 the lazy (XYZZ) or canonical (ED) Montgomery product of the
+ *     words of output j with its ZZZ (Z), an identity counting as 1.
+ *
+ * Points [first, first + count) of segment `segment` go to `point_words` (count x point_words u32) and, where
+ * `product_words` is not NULL, their running products to `product_words` (count x (product_words + product_pad) u32: the
+ * limbs, then the pad words; segment 0 only: the up-sweep runs over the m outputs).  first + count <= m and segment < segments, else MSM377_EINVAL.  count = 0 with
+ * NULL buffers fills `info` alone.
+ *
+ * MSM377_ESTATE, and nothing written: before the first batch call; after a batch call that returned an error or had
+ * n = 0 (it ran no pass); after msm377_g1_set_generators (a table build goes through the stash).  A batch call forgets
+ * the description when it starts and writes a new one when its last pass is through.  MSM, check and set-bases calls do
+ * not touch the stash and leave the description valid.
+ *
+ * msm377_g1_read_walk_tables copies the per-point tables [1..8]P_i the last pass of a variable-base call (tables = 1) or of
+ * a pairwise call (tables = 2: table 0 of the P_i, table 1 of the Q_i) walked: window-table records of 32 words (above;
+ * a flagged input or an entry that is the identity: x = y = 0, flag 1).  In the engine entry e of point i of table t is
+ * record ((t * 8) + e - 1) * m + i; the read-back writes entry e of point first + j at record (e - 1) * count + j of
+ * `words` (entries * count * 32 u32).  MSM377_ESTATE as above, and after any batch call of another kind. */
+#define MSM377_WALK_BATCH_MUL 1
+#define MSM377_WALK_BATCH_MUL_MULTI 2
+#define MSM377_WALK_COMMIT_ROWS 3
+#define MSM377_WALK_BATCH_MUL_VAR 4
+#define MSM377_WALK_BATCH_LINCOMB2 5
+#define MSM377_WALK_ED_BATCH_MUL_MULTI 6
+#define MSM377_WALK_FORM_XYZZ 0
+#define MSM377_WALK_FORM_ED 1
+typedef struct msm377_walk_stash_info {
+  uint32_t kind, form, point_words, product_words;
+  uint64_t n, pass_offset, m;
+  uint32_t width, k;
+  uint32_t segments, product_pad;
+  uint64_t stride;
+} msm377_walk_stash_info;
+int msm377_read_walk_stash(msm377_ctx* ctx, msm377_walk_stash_info* info, uint32_t segment, uint64_t first, uint64_t count, uint32_t* point_words, uint32_t* product_words);
+typedef struct msm377_walk_tables_info {
+  uint64_t m;
+  uint32_t tables, entries;
+} msm377_walk_tables_info;
+int msm377_g1_read_walk_tables(msm377_ctx* ctx, msm377_walk_tables_info* info, uint32_t table, uint64_t first, uint64_t count, uint32_t* words);
 
 /* Convert one Montgomery XYZZ point (52 words) to the affine wire format (host-only). */
 int msm377_g1_xyzz_to_affine(const uint32_t xyzz[52], uint8_t out_xy[96]);

@@ -243,6 +243,14 @@ int msm377_g1_read_mul_table(msm377_ctx* ctx, uint32_t which, uint32_t index, ms
   return eng::g1_read_mul_table(ctx, which, index, info, first, count, words);
 }
 
+int msm377_read_walk_stash(msm377_ctx* ctx, msm377_walk_stash_info* info, uint32_t segment, uint64_t first, uint64_t count, uint32_t* point_words, uint32_t* product_words) {
+  return eng::read_walk_stash(ctx, info, segment, first, count, point_words, product_words);
+}
+
+int msm377_g1_read_walk_tables(msm377_ctx* ctx, msm377_walk_tables_info* info, uint32_t table, uint64_t first, uint64_t count, uint32_t* words) {
+  return eng::g1_read_walk_tables(ctx, info, table, first, count, words);
+}
+
 int msm377_ctx_get_stage_form(const msm377_ctx* ctx) { return (ctx && ctx->capture && ctx->last.n && is_g1_form(ctx->last.form)) ? ctx->last.form : -1; }
 
 int msm377_g1_xyzz_to_affine(const uint32_t xyzz[52], uint8_t out_xy[96]) {

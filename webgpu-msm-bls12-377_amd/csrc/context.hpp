@@ -162,6 +162,16 @@ struct BasesLayout {
   const uint32_t* d_flagged = nullptr;    // per-call imports: the device counter of flagged points (null: info.flagged holds it)
 };
 
+// What the last pass of the last batch call left in BatchMulState's stash, for msm377_read_walk_stash and
+// msm377_g1_read_walk_tables: written on the host beside the launches (sequencer.hip note_walk, batch_device_call) from the
+// values they were given.  valid: from the successful end of a batch call that ran a pass until the next batch call or
+// msm377_g1_set_generators starts (sequencer.hip forget_walk): whatever writes the stash goes through one of the two.
+struct WalkLayout {
+  bool valid = false;
+  msm377_walk_stash_info info = {};
+  msm377_walk_tables_info tables = {};  // tables == 0: the pass walked no per-point tables
+};
+
 // ---- what belongs together, by the functions that use it ----
 
 // The batched affine conversion (sequencer.hip affine_convert_begin / affine_convert_finish, host_tail.hip
@@ -220,6 +230,7 @@ struct LastCall {
   double stage_ms[MSM377_NUM_STAGES] = {};
   StageLayout stage;  // what the last enqueue_decompose launched with; valid is enqueue_windows' (msm377_g1_read_stage_ex)
   BasesLayout bases;  // what the last base conversion wrote (msm377_g1_read_bases)
+  WalkLayout walk;    // what the last batch call's last pass left in the stash (msm377_read_walk_stash)
 };
 
 struct Fallbacks {

@@ -1969,6 +1969,30 @@ int bm_ensure_scratch(msm377_ctx* ctx) {
   return rc;
 }
 
+// ---- what the stash holds, for msm377_read_walk_stash / msm377_g1_read_walk_tables (context.hpp WalkLayout) ----
+// forget_walk: every batch call starts with it (the two argument checks that open each of them) and so does
+// msm377_g1_set_generators: from here on the stash is no longer what the last description said.  note_walk: beside a
+// pass's walk launch, from the launch's own arguments.  batch_device_call adds the pass (n, offset, length) and marks the
+// description valid behind the call's one wait.
+void forget_walk(msm377_ctx* ctx) { ctx->last.walk.valid = false; }
+
+void note_walk(msm377_ctx* ctx, uint32_t kind, uint32_t form, uint32_t width, uint32_t k, uint32_t segments = 1, uint64_t stride = 0, uint32_t tables = 0) {
+  WalkLayout& wl = ctx->last.walk;
+  wl.info = msm377_walk_stash_info{};
+  wl.info.kind = kind;
+  wl.info.form = form;
+  wl.info.point_words = form == MSM377_WALK_FORM_ED ? EDBM_POINT_PIECES * 4 : BM_POINT_PIECES * 4;
+  wl.info.product_words = form == MSM377_WALK_FORM_ED ? 9 : 13;
+  wl.info.product_pad = (form == MSM377_WALK_FORM_ED ? (EDBM_PIECES - EDBM_POINT_PIECES) * 4 : (BM_PIECES - BM_POINT_PIECES) * 4) - wl.info.product_words;
+  wl.info.width = width;
+  wl.info.k = k;
+  wl.info.segments = segments;
+  wl.info.stride = stride;
+  wl.tables = msm377_walk_tables_info{};
+  wl.tables.tables = tables;
+  wl.tables.entries = tables ? (uint32_t)BMV_ENTRIES : 0;
+}
+
 // What the normalisation, the builder and the pointer check need to know of a curve: the bytes of a base on the wire, the
 // build kernels, the normalisation kernels and the form of a table record.  The hot kernels are each call's own.
 struct G1Mul {
@@ -2100,6 +2124,7 @@ int ensure_multi_tables(msm377_ctx* ctx, MulTableSlot* slot, const uint8_t* base
 int bm_check_form(msm377_ctx* ctx, uint32_t out_form) {
   if (!ctx) return MSM377_EINVAL;
   ctx->err.clear();
+  forget_walk(ctx);  // every G1 batch call, device or host buffers, opens with this check
   if (out_form == MSM377_POINTS_WIRE || out_form == MSM377_POINTS_MONT_FLAG) return MSM377_OK;
   ctx->err = out_form == MSM377_POINTS_MONT ? "batch_mul outputs need a form that can say \"identity\": MSM377_POINTS_WIRE or MSM377_POINTS_MONT_FLAG" : "unknown output form";
   return MSM377_EINVAL;
@@ -2182,12 +2207,18 @@ int batch_device_call(msm377_ctx* ctx, int early, uint64_t n, uint64_t pass_len,
   }
   for (uint64_t off = 0; off < n && !rc; off += pass_len) {
     const uint64_t m = std::min<uint64_t>(pass_len, n - off);
-    rc = pass(off, m);
+    rc = pass(off, m);  // (notes what it launched: note_walk)
     if (!rc) rc = normalise<MC>(ctx, m, out_form, (uint8_t*)d_out + off * out_stride, d_out_inf ? d_out_inf + off : nullptr);
+    WalkLayout& wl = ctx->last.walk;  // the pass just queued: the last one is what the stash holds at the end
+    wl.info.n = n;
+    wl.info.pass_offset = off;
+    wl.info.m = m;
+    wl.tables.m = m;
   }
   const hipError_t e = hipStreamSynchronize(ctx->stream);
   if (rc) return rc;
   HIP_TRY(ctx, e);
+  ctx->last.walk.valid = true;
   return MSM377_OK;
 }
 const auto nothing_to_prepare = [] { return MSM377_OK; };
@@ -2233,6 +2264,7 @@ struct HostStage {
       if (!rc) rc = down_records(out_points + off * stride, m * stride);
       if (!rc && out_inf) rc = down_flags(out_inf + off, m);
     }
+    if (rc) forget_walk(ctx);  // (a download that failed behind a device call that did not)
     return rc;
   }
   // Rows off .. off + m of the caller's k x n matrix (s_ij at scalars + i out_stride + j base_stride), row-major, into part i.
@@ -2277,6 +2309,7 @@ int g1_batch_mul_device(msm377_ctx* ctx, const uint8_t base_xy[96], const void* 
   const auto pass = [&](uint64_t off, uint64_t m) -> int {
     hipLaunchKernelGGL(k_bm_accumulate, bm_grid(m), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)ctx->bm.single.table, (const uint32_t*)d_scalars + off * 8, m, (uint32_t)c, scalars_mont(ctx),
                        reinterpret_cast<uint4*>(ctx->bm.stash));
+    note_walk(ctx, MSM377_WALK_BATCH_MUL, MSM377_WALK_FORM_XYZZ, (uint32_t)c, 1);
     return MSM377_OK;
   };
   return batch_device_call<G1Mul>(ctx, bm_check_form(ctx, out_form), n, BM_CHUNK, out_form, d_out_points, stride, d_out_inf, check, prepare, pass);
@@ -2321,6 +2354,7 @@ int g1_batch_mul_multi_device(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t
   const auto pass = [&](uint64_t off, uint64_t m) -> int {  // row `off` of the CALL's layout: the strides are the call's, whatever the pass's length
     hipLaunchKernelGGL(k_bmm_accumulate, bm_grid(m), dim3(BM_THREADS), 0, ctx->stream, tables, (const uint8_t*)d_scalars + off * out_stride, m, k, out_stride, base_stride, (uint32_t)c,
                        scalars_mont(ctx), reinterpret_cast<uint4*>(ctx->bm.stash));
+    note_walk(ctx, MSM377_WALK_BATCH_MUL_MULTI, MSM377_WALK_FORM_XYZZ, (uint32_t)c, k);
     return MSM377_OK;
   };
   return batch_device_call<G1Mul>(ctx, early, n, BM_CHUNK, out_form, d_out_points, stride, d_out_inf, check, prepare, pass);
@@ -2354,6 +2388,7 @@ namespace {
 int edbm_check_args(msm377_ctx* ctx, uint32_t k, uint64_t out_stride, uint64_t base_stride) {
   if (!ctx) return MSM377_EINVAL;
   ctx->err.clear();
+  forget_walk(ctx);  // as bm_check_form: both Edwards-BLS12 batch calls open here
   return check_shape(ctx, k, MSM377_MUL_MAX_BASES, "k is 1 to MSM377_MUL_MAX_BASES bases", out_stride, base_stride);
 }
 
@@ -2383,6 +2418,7 @@ int ed_batch_mul_multi_device(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t
   const auto pass = [&](uint64_t off, uint64_t m) -> int {  // row `off` of the CALL's layout, as on G1
     hipLaunchKernelGGL(k_edbm_accumulate, bm_grid(m), dim3(BM_THREADS), 0, ctx->stream, tables, (const uint8_t*)d_scalars + off * out_stride, m, k, out_stride, base_stride, (uint32_t)c,
                        reinterpret_cast<uint4*>(ctx->bm.stash));
+    note_walk(ctx, MSM377_WALK_ED_BATCH_MUL_MULTI, MSM377_WALK_FORM_ED, (uint32_t)c, k);
     return MSM377_OK;
   };
   return batch_device_call<EdMul>(ctx, edbm_check_args(ctx, k, out_stride, base_stride), n, BM_CHUNK, EDBM_FORM_WIRE, d_out_points, 64, nullptr, check, prepare, pass);
@@ -2436,6 +2472,7 @@ int cr_check_set(msm377_ctx* ctx, uint32_t k) {
 int g1_set_generators(msm377_ctx* ctx, const uint8_t* gens_xy, uint32_t k, int window_bits) {
   if (!ctx) return MSM377_EINVAL;
   ctx->err.clear();
+  forget_walk(ctx);  // the build below goes through the stash
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   cr_drop_set(ctx);  // first, whatever follows: a call that fails leaves no set
   if (!gens_xy || k == 0) return MSM377_OK;
@@ -2490,6 +2527,7 @@ int g1_commit_rows_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n, ui
     hipLaunchKernelGGL(k_cr_accumulate, dim3(grid.x, plan.segments), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)gs.tables, (const uint8_t*)d_scalars + off * out_stride, m, k,
                        plan.bases_per_segment, out_stride, base_stride, (uint32_t)gs.width, scalars_mont(ctx), part_stride, stash);
     if (plan.segments > 1) hipLaunchKernelGGL(k_cr_fold, grid, dim3(BM_THREADS), 0, ctx->stream, stash, m, plan.segments, part_stride);
+    note_walk(ctx, MSM377_WALK_COMMIT_ROWS, MSM377_WALK_FORM_XYZZ, (uint32_t)gs.width, k, plan.segments, part_stride);
     return MSM377_OK;
   };
   return batch_device_call<G1Mul>(ctx, early, n, plan.rows_per_pass, out_form, d_out_points, stride, d_out_inf, check, nothing_to_prepare, pass);
@@ -2556,6 +2594,7 @@ int g1_batch_mul_var_device(msm377_ctx* ctx, const void* d_points, const void* d
     if (rc) return rc;
     hipLaunchKernelGGL(k_bmv_accumulate, bm_grid(m), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)ctx->bm.var_table, (const uint32_t*)d_scalars + off * stride_words, m, stride_words,
                        scalars_mont(ctx), stash);
+    note_walk(ctx, MSM377_WALK_BATCH_MUL_VAR, MSM377_WALK_FORM_XYZZ, (uint32_t)BMV_WIDTH, 1, 1, 0, 1);
     return MSM377_OK;
   };
   return batch_device_call<G1Mul>(ctx, early, n, BMV_PASS, out_form, d_out_points, out_stride, d_out_inf, check, [&] { return bmv_ensure_table(ctx); }, pass);
@@ -2614,6 +2653,7 @@ int g1_batch_lincomb2_device(msm377_ctx* ctx, const void* d_p, const void* d_q, 
     if (rc) return rc;
     hipLaunchKernelGGL(k_bl2_accumulate, bm_grid(m), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)ctx->bm.var_table, (const uint32_t*)d_a + off * a_words,
                        (const uint32_t*)d_b + off * b_words, m, a_words, b_words, scalars_mont(ctx), stash);
+    note_walk(ctx, MSM377_WALK_BATCH_LINCOMB2, MSM377_WALK_FORM_XYZZ, (uint32_t)BMV_WIDTH, BL2_TERMS, 1, 0, BL2_TERMS);
     return MSM377_OK;
   };
   return batch_device_call<G1Mul>(ctx, early, n, BL2_PASS, out_form, d_out_points, out_stride, d_out_inf, check, [&] { return bmv_ensure_table(ctx); }, pass);
@@ -2708,6 +2748,68 @@ int ed_read_mul_table(msm377_ctx* ctx, uint32_t index, msm377_mul_table_info* in
     return MSM377_EINVAL;
   }
   return read_mul_slot(ctx, ctx->edbm.slot[index], "that window table is not valid: never built, or left by a build that failed", info, first, count, words);
+}
+
+// ---- stash read-backs (msm377_read_walk_stash, msm377_g1_read_walk_tables) ----
+// Copies of what the last pass of the last batch call left (context.hpp WalkLayout), gathered from the piece-major stash
+// into point-major words: piece k of stash point j is at piece index k * BM_CHUNK + j.  No launch; every batch call has
+// waited for its stream before it returned.
+static int walk_not_valid(msm377_ctx* ctx) {
+  ctx->err = "no batch pass to read: no batch call has completed a pass on this context, the last one failed, or the stash was written since";
+  return MSM377_ESTATE;
+}
+
+// `pieces` 16-byte pieces from piece `first_piece` on, of stash points [at, at + count), into `words` (count x take u32,
+// take <= 4 pieces: the words of a point that are wanted).
+static int gather_pieces(msm377_ctx* ctx, uint32_t first_piece, uint32_t pieces, uint64_t at, uint64_t count, uint32_t take, uint32_t* words) {
+  std::vector<uint32_t> piece((size_t)count * 4);
+  for (uint32_t k = 0; k < pieces; k++) {
+    HIP_TRY(ctx, hipMemcpy(piece.data(), ctx->bm.stash + ((size_t)(first_piece + k) * BM_CHUNK + at) * 4, (size_t)count * 16, hipMemcpyDeviceToHost));
+    for (uint64_t j = 0; j < count; j++)
+      for (uint32_t q = 0; q < 4 && 4 * k + q < take; q++) words[(size_t)j * take + 4 * k + q] = piece[(size_t)j * 4 + q];
+  }
+  return MSM377_OK;
+}
+
+int read_walk_stash(msm377_ctx* ctx, msm377_walk_stash_info* info, uint32_t segment, uint64_t first, uint64_t count, uint32_t* point_words, uint32_t* product_words) {
+  if (!ctx) return MSM377_EINVAL;
+  ctx->err.clear();
+  const WalkLayout& wl = ctx->last.walk;
+  if (!wl.valid || !ctx->bm.stash) return walk_not_valid(ctx);
+  const msm377_walk_stash_info& wi = wl.info;
+  if (segment >= wi.segments || first > wi.m || count > wi.m - first || (count && !point_words && !product_words) || (product_words && segment != 0)) {
+    ctx->err = "point range or segment outside the pass (running products: segment 0 only)";
+    return MSM377_EINVAL;
+  }
+  if (info) *info = wi;
+  if (!count) return MSM377_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const bool ed = wi.form == MSM377_WALK_FORM_ED;
+  const uint32_t point_pieces = ed ? EDBM_POINT_PIECES : BM_POINT_PIECES, all_pieces = ed ? EDBM_PIECES : BM_PIECES;
+  const uint64_t at = (uint64_t)segment * wi.stride + first;  // < segments * stride <= BM_CHUNK by the plan; first + count <= m <= stride
+  int rc = MSM377_OK;
+  if (point_words) rc = gather_pieces(ctx, 0, point_pieces, at, count, wi.point_words, point_words);
+  if (!rc && product_words) rc = gather_pieces(ctx, point_pieces, all_pieces - point_pieces, at, count, wi.product_words + wi.product_pad, product_words);
+  return rc;
+}
+
+int g1_read_walk_tables(msm377_ctx* ctx, msm377_walk_tables_info* info, uint32_t table, uint64_t first, uint64_t count, uint32_t* words) {
+  if (!ctx) return MSM377_EINVAL;
+  ctx->err.clear();
+  const WalkLayout& wl = ctx->last.walk;
+  if (!wl.valid || !wl.tables.tables || !ctx->bm.var_table) return walk_not_valid(ctx);
+  const msm377_walk_tables_info& ti = wl.tables;
+  if (table >= ti.tables || first > ti.m || count > ti.m - first || (count && !words)) {
+    ctx->err = "point range or table outside the pass";
+    return MSM377_EINVAL;
+  }
+  if (info) *info = ti;
+  if (!count) return MSM377_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  for (uint32_t e = 0; e < ti.entries; e++)  // entry e + 1 of point i of table t: record ((t * entries) + e) * m + i
+    HIP_TRY(ctx, hipMemcpy(words + ((size_t)e * count) * BM_REC_WORDS, ctx->bm.var_table + (((size_t)table * ti.entries + e) * ti.m + first) * BM_REC_WORDS,
+                           (size_t)count * BM_REC_WORDS * 4, hipMemcpyDeviceToHost));
+  return MSM377_OK;
 }
 
 }  // namespace eng

@@ -169,6 +169,46 @@ class MulTableInfo(NamedTuple):
     key: bytes
 
 
+class _WalkStashInfoStruct(ctypes.Structure):  # msm377_walk_stash_info
+    _fields_ = [(f, ctypes.c_uint32) for f in ("kind", "form", "point_words", "product_words")] + [(f, ctypes.c_uint64) for f in ("n", "pass_offset", "m")] + [
+        (f, ctypes.c_uint32) for f in ("width", "k", "segments", "product_pad")] + [("stride", ctypes.c_uint64)]
+
+
+class WalkStashInfo(NamedTuple):
+    """msm377_walk_stash_info: the last pass of the last batch call -- the call (WALK_*), the record form (WALK_FORM_*) and
+    its word counts, the call's n, the pass (pass_offset, m), the width it walked, k, and the row commitments' segments
+    and stride."""
+
+    kind: int
+    form: int
+    point_words: int
+    product_words: int
+    n: int
+    pass_offset: int
+    m: int
+    width: int
+    k: int
+    segments: int
+    product_pad: int
+    stride: int
+
+
+class _WalkTablesInfoStruct(ctypes.Structure):  # msm377_walk_tables_info
+    _fields_ = [("m", ctypes.c_uint64), ("tables", ctypes.c_uint32), ("entries", ctypes.c_uint32)]
+
+
+class WalkTablesInfo(NamedTuple):
+    """msm377_walk_tables_info: points of the pass, tables (1: variable-base, 2: pairwise), entries per point (8)."""
+
+    m: int
+    tables: int
+    entries: int
+
+
+WALK_BATCH_MUL, WALK_BATCH_MUL_MULTI, WALK_COMMIT_ROWS, WALK_BATCH_MUL_VAR, WALK_BATCH_LINCOMB2, WALK_ED_BATCH_MUL_MULTI = 1, 2, 3, 4, 5, 6
+WALK_FORM_XYZZ, WALK_FORM_ED = 0, 1
+
+
 class CheckReport(NamedTuple):
     """msm377_check_report: a point is counted once, in the first class it fails; ``first_bad`` is the lowest failing
     index (None if every point passed) and ``first_bad_reason`` the CHECK_* bit it failed (0 if none)."""
@@ -267,6 +307,8 @@ def load_library():
         "msm377_g1_read_bases": (i32, [vp, vp, u64, u64, vp]),
         "msm377_g1_read_partials": (i32, [vp, vp, vp]),
         "msm377_g1_read_mul_table": (i32, [vp, u32, u32, vp, u64, u64, vp]),
+        "msm377_read_walk_stash": (i32, [vp, vp, u32, u64, u64, vp, vp]),
+        "msm377_g1_read_walk_tables": (i32, [vp, vp, u32, u64, u64, vp]),
         "msm377_g1_xyzz_to_affine": (i32, [vp, vp]),
         "msm377_g1_fold_window_partials": (i32, [vp, ctypes.c_uint32]),
         "msm377_ctx_set_glv": (i32, [vp, i32]),
@@ -1222,6 +1264,42 @@ class MsmEngine:
         count = info.records - int(first) if count is None else int(count)
         words = np.empty((count, MUL_TABLE_RECORD_WORDS), dtype=np.uint32)
         self._check(self._lib.msm377_g1_read_mul_table(self._ctx, int(w), int(index), None, int(first), count, words.ctypes.data if count else None), "msm377_g1_read_mul_table")
+        return info, words
+
+    def read_walk_stash(self, segment: int = 0, first: int = 0, count=None, products: bool = True, info_only: bool = False):
+        """(WalkStashInfo, points, running products) of what the last pass of the last batch call left in the stash
+        (msm377_read_walk_stash): ``points`` is count x point_words u32 (X, Y, ZZ, ZZZ of 13 limbs, or X, Y, T, Z of 9),
+        ``products`` count x (product_words + product_pad) u32 (the limbs, then the zero pad words of the last piece), or
+        None without ``products`` and for a segment above 0 of a row commitment.  Default: all m points of the pass.  MsmError(ESTATE) when no completed pass is described."""
+        import numpy as np
+
+        raw = _WalkStashInfoStruct()
+        self._check(self._lib.msm377_read_walk_stash(self._ctx, ctypes.addressof(raw), 0, 0, 0, None, None), "msm377_read_walk_stash")
+        info = WalkStashInfo(*(int(getattr(raw, f)) for f in WalkStashInfo._fields))
+        if info_only:
+            return info, None, None
+        count = info.m - int(first) if count is None else int(count)
+        pts = np.empty((count, info.point_words), dtype=np.uint32)
+        prod = np.empty((count, info.product_words + info.product_pad), dtype=np.uint32) if products and int(segment) == 0 else None
+        rc = self._lib.msm377_read_walk_stash(self._ctx, None, int(segment), int(first), count, pts.ctypes.data if count else None,
+                                              prod.ctypes.data if prod is not None and count else None)
+        self._check(rc, "msm377_read_walk_stash")
+        return info, pts, prod
+
+    def read_walk_tables(self, table: int = 0, first: int = 0, count=None, info_only: bool = False):
+        """(WalkTablesInfo, records) of the per-point tables [1..8]P_i the last pass of a variable-base or pairwise call
+        walked (msm377_g1_read_walk_tables): ``records`` has shape (entries, count, 32) u32, entry e of point first + j at
+        [e - 1, j].  MsmError(ESTATE) unless the last batch call was one of the two and completed."""
+        import numpy as np
+
+        raw = _WalkTablesInfoStruct()
+        self._check(self._lib.msm377_g1_read_walk_tables(self._ctx, ctypes.addressof(raw), 0, 0, 0, None), "msm377_g1_read_walk_tables")
+        info = WalkTablesInfo(int(raw.m), int(raw.tables), int(raw.entries))
+        if info_only:
+            return info, None
+        count = info.m - int(first) if count is None else int(count)
+        words = np.empty((info.entries, count, MUL_TABLE_RECORD_WORDS), dtype=np.uint32)
+        self._check(self._lib.msm377_g1_read_walk_tables(self._ctx, None, int(table), int(first), count, words.ctypes.data if count else None), "msm377_g1_read_walk_tables")
         return info, words
 
     def stage_form(self) -> int:
