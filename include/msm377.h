@@ -42,7 +42,8 @@ extern "C" {
                                     case of their (incomplete) addition law -- possible only with input points outside the
                                     prime-order subgroup; recompute the windows in form 0 (msm377_ctx_set_g1_form) and combine
                                     again.  The full-MSM entry points handle this themselves and never return it. */
-#define MSM377_EPOINT (-8)    /* an input point failed a check the caller asked for (msm377_ctx_set_base_checks) */
+#define MSM377_EPOINT (-8)    /* an input point failed a check the caller asked for (msm377_ctx_set_base_checks), or the canonical /
+                                    on-curve check msm377_ed_batch_mul_var* always run; msm377_last_error names index and reason */
 
 #define MSM377_NUM_WINDOWS 16          /* ceil(256 / 16): submission.ts:108-109 */
 #define MSM377_WINDOW_BITS 16          /* chunk_size for n >= 2^16: submission.ts:97 */
@@ -596,6 +597,7 @@ int msm377_g1_read_mul_table(msm377_ctx* ctx, uint32_t which, uint32_t index, ms
 #define MSM377_WALK_BATCH_MUL_VAR 4
 #define MSM377_WALK_BATCH_LINCOMB2 5
 #define MSM377_WALK_ED_BATCH_MUL_MULTI 6
+#define MSM377_WALK_ED_BATCH_MUL_VAR 7 /* k_edbmv_accumulate; its tables: msm377_ed_read_walk_tables */
 #define MSM377_WALK_FORM_XYZZ 0
 #define MSM377_WALK_FORM_ED 1
 typedef struct msm377_walk_stash_info {
@@ -791,6 +793,48 @@ int msm377_ed_batch_mul_multi(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t
 int msm377_ed_batch_mul_multi_host(const uint8_t* bases_xy, uint32_t k, const uint8_t* scalars, uint64_t n, uint64_t out_stride, uint64_t base_stride, uint8_t* out_points);
 uint64_t msm377_ed_ctx_get_mul_table_builds(const msm377_ctx* ctx);
 int msm377_ed_read_mul_table(msm377_ctx* ctx, uint32_t index, msm377_mul_table_info* info, uint64_t first, uint64_t count, uint32_t* words);
+
+/* ---- Edwards-BLS12 variable-base batch multiplication -------------------------------------- */
+
+/* out[i] = [s_i]P_i on Edwards-BLS12: n scalar multiples of n points, every output its own 64-byte wire point, with n
+ * scalars or ONE scalar for all points (record scanning [view_key] nonce_i; the ElGamal / ECDH halves [r_i]PK_i).  Wherever
+ * they overlap the contract is word for word that of msm377_ed_batch_mul_multi* above and of msm377_g1_batch_mul_var*
+ * below -- 64-byte wire records x || y in and out, the identity the ordinary record (0, 1), no out_form and no flag bytes;
+ * every 32-byte value a legal scalar, read as an integer and NOT reduced, no MSM377_ESCALAR, no rerun; scalar_stride 32, or
+ * 0 for ONE 32-byte scalar for all points; any n, in passes of 2^17 over a fixed scratch, n = 0 MSM377_OK without a
+ * launch; 16-byte aligned device pointers; synchronous calls; MSM377_EINVAL while a non-wire input form is set, for a
+ * misaligned pointer, a null pointer with n > 0 or another stride, with the outputs untouched -- and this section states
+ * only what differs (csrc/kernels/ed_batch_mul_var.hpp).
+ *
+ * Points.  Every curve point is a legal input, mixed freely within one array: the identity, the point of order 2, both
+ * points of order 4, P + T for a subgroup point P and each torsion point T, P_i = +-P_j.  No subgroup test is run.  A point
+ * that is NOT on the curve is refused: the addition law is complete on the curve only, and the one batched inversion of a
+ * pass needs every Z non-zero, so a single bad point would corrupt every output of its pass.  Before anything is written
+ * the device call runs the canonical + on-curve check over all n points (the kernel of msm377_ed_check_points*, into
+ * counters of the call's own: the state of a check call is not touched); a finding is MSM377_EPOINT with the outputs
+ * untouched, and msm377_last_error names the lowest failing index and the reason (a coordinate that is not below q / not
+ * on the curve).  The host-buffer call works in pieces of 2^20 points: a call of several pieces runs the same check over
+ * all of them first (its points go up twice), so that no piece has come down when a later one is refused.
+ *
+ * In place.  d_out_points == d_points is allowed: a pass reads its points before it writes its outputs, and passes cover
+ * disjoint index ranges.  Any other overlap is the caller's bug.
+ *
+ * State.  The per-point tables [1..8]P_i of a pass live in the table memory of msm377_g1_batch_mul_var* (128 MB, allocated
+ * by the first call of either, never valid between calls).  The resident MSM bases, every G1 table, slot and build counter,
+ * the 16 Edwards-BLS12 table slots and msm377_ed_ctx_get_mul_table_builds, the generator set and a check call's state are
+ * untouched, and the other way round.
+ *
+ * msm377_ed_read_walk_tables copies the per-point tables of the last pass as msm377_g1_read_walk_tables does for G1
+ * (there is one table): entry e of point first + j at record (e - 1) * count + j of `words`, 32 words each in the
+ * MSM377_BASES_ED layout of msm377_ed_read_mul_table.  MSM377_ESTATE after any batch call of another kind. */
+int msm377_ed_batch_mul_var_device(msm377_ctx* ctx, const void* d_points /* n x 64 */, const void* d_scalars, uint64_t n, uint32_t scalar_stride /* 32 or 0 */,
+                                   void* d_out_points /* n x 64 */);
+int msm377_ed_batch_mul_var(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint32_t scalar_stride, uint8_t* out_points);
+/* The same on ONE CPU thread: no device, no context (csrc/ed_batch_mul_var_host.hpp): the same checks and codes, plain
+ * double-and-add on the canonical formulas, one inversion per output; the yardstick of the device call.  There is no
+ * context to carry the text of a refusal: msm377_ed_check_points_host names the index and the reason. */
+int msm377_ed_batch_mul_var_host(const uint8_t* points, const uint8_t* scalars, uint64_t n, uint32_t scalar_stride, uint8_t* out_points);
+int msm377_ed_read_walk_tables(msm377_ctx* ctx, msm377_walk_tables_info* info, uint64_t first, uint64_t count, uint32_t* words);
 
 /* ---- variable-base batch multiplication --------------------------------------------------- */
 

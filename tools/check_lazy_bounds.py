@@ -232,8 +232,7 @@ def te_formulas(canonical):
         f = norm(add_kp_sub(d, "KP2", 2, c, tag + " F"), tag + " F")
         g = norm(add_lz(d, c, tag + " G"), tag + " G")
         h = add_lz(b, a, tag + " H")
-        for nm, (x, y) in (("X3", (e, f)), ("Y3", (h, g)), ("T3", (h, e)), ("Z3", (f, g))):
-            mul_lz(x, y, "%s %s" % (tag, nm))
+        return [mul_lz(x, y, "%s %s" % (tag, nm)) for nm, (x, y) in (("X3", (e, f)), ("Y3", (h, g)), ("T3", (h, e)), ("Z3", (f, g)))]
 
     PX, PY, PT, PZ = m1("PX"), m1("PY"), m1("PT"), m1("PZ")
     a = mul_lz(add_kp_sub(PY, "KP2", 2, PX, "te madd Y-X"), canonical, "te madd A")
@@ -251,6 +250,33 @@ def te_formulas(canonical):
     b = mul_lz(add_lz(PY, PX, "te amadd Y+X"), canonical, "te amadd B")
     c = mul_lz(kp_sub("KP2", 2, canonical, "te amadd -kt"), PT, "te amadd C")
     te_finish(a, b, c, add_lz(PZ, PZ, "te amadd 2Z"), "te amadd")
+    # dbl / dbl_nt (dbl_any): four lazy squares, then the four products on factors of the opposite sign.  What it reads
+    # and what it returns are stored coordinates, so the walk of kernels/ed_batch_mul_var.hpp is replayed as a chain:
+    # the start values, dbl after madd_affine, dbl after dbl, madd_affine after dbl.
+    def te_dbl(x, y, z, tag):
+        a, b, zz = sqr_lz(x, tag + " A"), sqr_lz(y, tag + " B"), sqr_lz(z, tag + " ZZ")
+        s = sqr_lz(norm(add_lz(x, y, tag + " X+Y"), tag + " X+Y"), tag + " S")
+        h = add_lz(a, b, tag + " H")
+        g = norm(add_kp_sub(a, "KP2", 2, b, tag + " G"), tag + " G")
+        e = norm(add_kp_sub(h, "KP2", 2, s, tag + " E"), tag + " E")
+        f = norm(add_lz(add_lz(zz, zz, tag + " 2ZZ"), g, tag + " F"), tag + " F")
+        assert g.lo > 0 and e.lo > 0 and f.hi <= 5 * P + 3 * E and e.hi <= 4 * P + 2 * E, (tag, f.hi / P, e.hi / P)
+        return [mul_lz(u, v, "%s %s" % (tag, nm)) for nm, (u, v) in (("X3", (e, f)), ("Y3", (h, g)), ("T3", (h, e)), ("Z3", (f, g)))]
+
+    def te_amadd(x, y, t, z, tag):
+        a = mul_lz(add_kp_sub(y, "KP2", 2, x, tag + " Y-X"), canonical, tag + " A")
+        b = mul_lz(add_lz(y, x, tag + " Y+X"), canonical, tag + " B")
+        mul_lz(canonical, t, tag + " C")
+        c = mul_lz(kp_sub("KP2", 2, canonical, tag + " -kt"), t, tag + " C neg")
+        return te_finish(a, b, c, add_lz(z, z, tag + " 2Z"), tag)
+
+    zero, one = V([0] * N, 1, 0, "0"), canonical  # identity(): (0, 1, 0, 1)
+    acc = te_amadd(zero, one, zero, one, "te start amadd")  # acc = carry ? P : O
+    x, y, t, z = te_dbl(zero, one, one, "te dbl of the start value")
+    for pt, tag in ((acc, "te dbl after amadd"), ((x, y, t, z), "te dbl after dbl")):
+        x, y, t, z = te_dbl(pt[0], pt[1], pt[3], tag)
+    te_amadd(x, y, t, z, "te amadd after dbl")
+
     # canonical operations on stored (lazy) coordinates: mul() = reduce_once(mul_lz()) needs mul_lz < 2p
     mul_lz(PX, canonical, "gather X*TO64")
 

@@ -13,6 +13,7 @@
 #include "batch_mul_host.hpp"
 #include "batch_mul_multi_host.hpp"
 #include "ed_batch_mul_host.hpp"
+#include "ed_batch_mul_var_host.hpp"
 #include "commit_rows_host.hpp"
 #include "commit_rows_plan.hpp"
 #include "batch_lincomb2_host.hpp"
@@ -379,6 +380,9 @@ uint64_t msm377_ctx_get_mul_multi_table_builds(const msm377_ctx* ctx) { return c
 int msm377_ed_batch_mul_multi_host(const uint8_t* bases_xy, uint32_t k, const uint8_t* scalars, uint64_t n, uint64_t out_stride, uint64_t base_stride, uint8_t* out_points) {
   return ed_batch_mul_multi_host(bases_xy, k, scalars, n, out_stride, base_stride, out_points);
 }
+int msm377_ed_batch_mul_var_host(const uint8_t* points, const uint8_t* scalars, uint64_t n, uint32_t scalar_stride, uint8_t* out_points) {
+  return ed_batch_mul_var_host(points, scalars, n, scalar_stride, out_points);
+}
 
 uint64_t msm377_ed_ctx_get_mul_table_builds(const msm377_ctx* ctx) { return ctx ? ctx->edbm.builds : 0; }
 
@@ -474,6 +478,15 @@ int msm377_ed_batch_mul_multi_device(msm377_ctx* ctx, const uint8_t* bases_xy, u
 }
 int msm377_ed_batch_mul_multi(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k, const uint8_t* scalars, uint64_t n, uint64_t out_stride, uint64_t base_stride, uint8_t* out_points) {
   return ed_wire_only(ctx) ? MSM377_EINVAL : eng::ed_batch_mul_multi(ctx, bases_xy, k, scalars, n, out_stride, base_stride, out_points);
+}
+int msm377_ed_batch_mul_var_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t scalar_stride, void* d_out_points) {
+  return ed_wire_only(ctx) ? MSM377_EINVAL : eng::ed_batch_mul_var_device(ctx, d_points, d_scalars, n, scalar_stride, d_out_points);
+}
+int msm377_ed_batch_mul_var(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint32_t scalar_stride, uint8_t* out_points) {
+  return ed_wire_only(ctx) ? MSM377_EINVAL : eng::ed_batch_mul_var(ctx, points, scalars, n, scalar_stride, out_points);
+}
+int msm377_ed_read_walk_tables(msm377_ctx* ctx, msm377_walk_tables_info* info, uint64_t first, uint64_t count, uint32_t* words) {
+  return eng::ed_read_walk_tables(ctx, info, first, count, words);
 }
 int msm377_ed_read_mul_table(msm377_ctx* ctx, uint32_t index, msm377_mul_table_info* info, uint64_t first, uint64_t count, uint32_t* words) {
   return eng::ed_read_mul_table(ctx, index, info, first, count, words);

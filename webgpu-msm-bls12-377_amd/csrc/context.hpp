@@ -112,6 +112,9 @@ struct BatchMulMultiState {
 struct EdBatchMulState {
   MulTableSlot slot[MSM377_MUL_MAX_BASES];
   uint64_t builds = 0;  // slots built so far (msm377_ed_ctx_get_mul_table_builds)
+  // The variable-base call (msm377_ed_batch_mul_var*, kernels/ed_batch_mul_var.hpp): the counters of ITS point check
+  // (CHK_WORDS words, allocated on first use).  Its per-point tables are BatchMulState::var_table.
+  uint32_t* point_check = nullptr;
 };
 
 // The resident generator set of the row commitments (msm377_g1_set_generators / msm377_g1_commit_rows*,

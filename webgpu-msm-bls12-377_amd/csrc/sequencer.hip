@@ -52,6 +52,7 @@
 #include "context.hpp"
 #include "host_tail.hpp"
 #include "ed_batch_mul_host.hpp"
+#include "ed_batch_mul_var_host.hpp"
 #include "validate_host.hpp"
 #include "kernels/accumulate.hpp"
 #include "kernels/batch_mul.hpp"
@@ -66,6 +67,7 @@
 #include "kernels/validate.hpp"
 #include "kernels/import.hpp"
 #include "kernels/batch_mul_var.hpp"
+#include "kernels/ed_batch_mul_var.hpp"
 #include "kernels/batch_lincomb2.hpp"
 #include "kernels/wide.hpp"
 
@@ -2620,6 +2622,95 @@ int g1_batch_mul_var(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scal
   });
 }
 
+// ---- Edwards-BLS12 variable-base batch multiplication (include/msm377.h; kernels/ed_batch_mul_var.hpp) ----
+// The flow of the G1 call above on the Edwards kernels, behind ONE more step: the canonical + on-curve check of all n
+// points, before anything is written.  The per-point tables are the G1 call's allocation (ctx->bm.var_table, never valid
+// between calls); no slot, key or build count of any table is read or written from here.
+namespace {
+
+int edbmv_check_args(msm377_ctx* ctx, uint32_t scalar_stride) {
+  if (!ctx) return MSM377_EINVAL;
+  ctx->err.clear();
+  forget_walk(ctx);  // as edbm_check_args
+  if (bmv_stride_ok(scalar_stride)) return MSM377_OK;
+  ctx->err = "scalar_stride is 32 (a scalar per point) or 0 (one scalar for all points)";
+  return MSM377_EINVAL;
+}
+
+int edbmv_refuse(msm377_ctx* ctx, uint64_t index, uint32_t reason) {
+  ctx->err = ed_batch_mul_var_refusal(index, reason);
+  return MSM377_EPOINT;
+}
+
+// k_check_curve<EdCheck> over the caller's points into counters of this call's own (ctx->edbm.point_check): no check
+// call's scratch, report or list is touched.  One tiny clear, one launch, one wait.  first: the index of d_points[0] in the
+// caller's array (a piece of a host-buffer call).
+int edbmv_check_points(msm377_ctx* ctx, const void* d_points, uint64_t n, uint64_t first = 0) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const int rc = bm_alloc(ctx, &ctx->edbm.point_check, CHK_WORDS * 4);
+  if (rc) return rc;
+  uint32_t* scratch = ctx->edbm.point_check;
+  hipLaunchKernelGGL(k_check_clear, dim3(1), dim3(64), 0, ctx->stream, scratch);
+  hipLaunchKernelGGL(k_check_curve<EdCheck>, dim3((unsigned)((n + CHK_THREADS - 1) / CHK_THREADS)), dim3(CHK_THREADS), 0, ctx->stream, (const uint32_t*)d_points, n, 1u, scratch,
+                     (uint32_t*)nullptr);
+  HIP_TRY(ctx, hipGetLastError());
+  uint32_t h[CHK_WORDS];
+  HIP_TRY(ctx, hipMemcpyAsync(h, scratch, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  const uint64_t key = (uint64_t)h[CHK_FIRST] | ((uint64_t)h[CHK_FIRST + 1] << 32);
+  if (key == UINT64_MAX) return MSM377_OK;
+  return edbmv_refuse(ctx, first + (key >> 2), (uint32_t)(key & 3) == CHK_CLASS_NONCANON ? MSM377_CHECK_CANONICAL : MSM377_CHECK_CURVE);
+}
+
+}  // namespace
+
+int ed_batch_mul_var_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t scalar_stride, void* d_out_points) {
+  const uint32_t stride_words = scalar_stride / 4;
+  const auto check = [&]() -> int {
+    const int rc = check_pointers<EdMul>(ctx, {}, {d_scalars}, {d_points}, 64, d_out_points, 64);
+    return rc ? rc : edbmv_check_points(ctx, d_points, n);
+  };
+  const auto pass = [&](uint64_t off, uint64_t m) -> int {
+    uint4* stash = reinterpret_cast<uint4*>(ctx->bm.stash);
+    hipLaunchKernelGGL(k_edbmv_table, bm_grid(m), dim3(BM_THREADS), 0, ctx->stream, (const uint8_t*)d_points + off * 64, m, stash);
+    const int rc = normalise<EdMul>(ctx, m * BMV_ENTRIES, EDBM_FORM_TABLE, ctx->bm.var_table, nullptr);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_edbmv_accumulate, bm_grid(m), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)ctx->bm.var_table, (const uint32_t*)d_scalars + off * stride_words, m, stride_words,
+                       stash);
+    note_walk(ctx, MSM377_WALK_ED_BATCH_MUL_VAR, MSM377_WALK_FORM_ED, (uint32_t)BMV_WIDTH, 1, 1, 0, 1);
+    return MSM377_OK;
+  };
+  return batch_device_call<EdMul>(ctx, edbmv_check_args(ctx, scalar_stride), n, BMV_PASS, EDBM_FORM_WIRE, d_out_points, 64, nullptr, check, [&] { return bmv_ensure_table(ctx); }, pass);
+}
+
+// Host buffers: points and scalars up, records down, in pieces of at most a chunk; a stride-0 scalar is uploaded once.  A
+// call of ONE piece leaves the check to its device call, which runs it before anything is written.  A call of several
+// pieces checks all of them first, on the device, piece by piece through the staging -- a piece that has come down is not
+// taken back -- and then uploads the points a second time (the host's own check, EdHostCheck, takes 11 us per point on
+// one thread against 6 ms per 2^20 points of upload).
+int ed_batch_mul_var(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint32_t scalar_stride, uint8_t* out_points) {
+  int rc = edbmv_check_args(ctx, scalar_stride);
+  if (rc || n == 0) return rc;
+  if (!points || !scalars || !out_points) return null_pointer(ctx);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const uint64_t piece = std::min<uint64_t>(n, BM_CHUNK);
+  HostStage io(ctx, {(size_t)piece * 32, (size_t)piece * 64}, (size_t)piece * 64, 0, "out of device memory for the batch multiplication staging");
+  if (io.rc) return io.rc;
+  for (uint64_t off = 0; n > piece && off < n && !rc; off += piece) {
+    const uint64_t m = std::min<uint64_t>(piece, n - off);
+    rc = io.up(1, points + off * 64, m * 64, "hipMemcpy(points)");
+    if (!rc) rc = edbmv_check_points(ctx, io.part(1), m, off);
+  }
+  if (rc) return rc;
+  if (scalar_stride == 0) rc = io.up(0, scalars, 32, "hipMemcpy(scalar)");
+  if (rc) return rc;
+  return io.run(n, piece, out_points, 64, nullptr, [&](uint64_t off, uint64_t m) -> int {
+    int up = scalar_stride ? io.up(0, scalars + off * 32, m * 32, "hipMemcpy(scalars)") : MSM377_OK;
+    if (!up) up = io.up(1, points + off * 64, m * 64, "hipMemcpy(points)");
+    return up ? up : ed_batch_mul_var_device(ctx, io.part(1), io.part(0), m, scalar_stride, io.records());
+  });
+}
+
 // ---- pairwise linear combination (include/msm377.h "pairwise linear combination"; kernels/batch_lincomb2.hpp) ----
 // Per pass of BL2_PASS pairs: both tables through the stash and ONE normalisation, then the joint walk; the flow
 // normalises again.  A pass reads all of its inputs before it writes its outputs, and passes cover disjoint index
@@ -2750,7 +2841,7 @@ int ed_read_mul_table(msm377_ctx* ctx, uint32_t index, msm377_mul_table_info* in
   return read_mul_slot(ctx, ctx->edbm.slot[index], "that window table is not valid: never built, or left by a build that failed", info, first, count, words);
 }
 
-// ---- stash read-backs (msm377_read_walk_stash, msm377_g1_read_walk_tables) ----
+// ---- stash read-backs (msm377_read_walk_stash, msm377_g1_read_walk_tables, msm377_ed_read_walk_tables) ----
 // Copies of what the last pass of the last batch call left (context.hpp WalkLayout), gathered from the piece-major stash
 // into point-major words: piece k of stash point j is at piece index k * BM_CHUNK + j.  No launch; every batch call has
 // waited for its stream before it returned.
@@ -2793,11 +2884,12 @@ int read_walk_stash(msm377_ctx* ctx, msm377_walk_stash_info* info, uint32_t segm
   return rc;
 }
 
-int g1_read_walk_tables(msm377_ctx* ctx, msm377_walk_tables_info* info, uint32_t table, uint64_t first, uint64_t count, uint32_t* words) {
+// form: the curve whose call asks; the tables of the other curve's pass are not its to read.
+static int read_walk_tables(msm377_ctx* ctx, uint32_t form, msm377_walk_tables_info* info, uint32_t table, uint64_t first, uint64_t count, uint32_t* words) {
   if (!ctx) return MSM377_EINVAL;
   ctx->err.clear();
   const WalkLayout& wl = ctx->last.walk;
-  if (!wl.valid || !wl.tables.tables || !ctx->bm.var_table) return walk_not_valid(ctx);
+  if (!wl.valid || !wl.tables.tables || wl.info.form != form || !ctx->bm.var_table) return walk_not_valid(ctx);
   const msm377_walk_tables_info& ti = wl.tables;
   if (table >= ti.tables || first > ti.m || count > ti.m - first || (count && !words)) {
     ctx->err = "point range or table outside the pass";
@@ -2810,6 +2902,13 @@ int g1_read_walk_tables(msm377_ctx* ctx, msm377_walk_tables_info* info, uint32_t
     HIP_TRY(ctx, hipMemcpy(words + ((size_t)e * count) * BM_REC_WORDS, ctx->bm.var_table + (((size_t)table * ti.entries + e) * ti.m + first) * BM_REC_WORDS,
                            (size_t)count * BM_REC_WORDS * 4, hipMemcpyDeviceToHost));
   return MSM377_OK;
+}
+
+int g1_read_walk_tables(msm377_ctx* ctx, msm377_walk_tables_info* info, uint32_t table, uint64_t first, uint64_t count, uint32_t* words) {
+  return read_walk_tables(ctx, MSM377_WALK_FORM_XYZZ, info, table, first, count, words);
+}
+int ed_read_walk_tables(msm377_ctx* ctx, msm377_walk_tables_info* info, uint64_t first, uint64_t count, uint32_t* words) {
+  return read_walk_tables(ctx, MSM377_WALK_FORM_ED, info, 0, first, count, words);
 }
 
 }  // namespace eng

@@ -125,6 +125,45 @@ struct TeLazy {
     const El d = F::mul_lz(p.z, q.z);
     return finish(a, b, c, F::add_lz(d, d));
   }
+  // A scheduling barrier between the squares of a doubling: each square holds 2 x 18 column registers, and the scheduler,
+  // left alone, ran them side by side -- 128 VGPRs and 9 spilled in k_edbmv_accumulate against 102 and none with it.
+  static MSM_HD void fence() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_sched_barrier(0);
+#endif
+  }
+  // 2p: dbl-2008-hwcd with a = -1, four lazy squares and four lazy products (dbl_nt: three, T3 is not formed -- for a
+  // doubling that is followed by another doubling, which never reads T).  All four factors are taken with the opposite
+  // sign, which the four products do not see and which leaves sums where the textbook lines negate:
+  //   A = X^2, B = Y^2, ZZ = Z^2, S = (X + Y)^2 lazy squares (< p + e);
+  //   H = A + B < 2p + 2e, limb-wise like finish()'s H;  G = A - B + 2p in (p - e, 3p + e);
+  //   E = H - S + 2p in (p - e, 4p + 2e);  F = 2 ZZ + G < 5p + 3e;  G, E, F and X + Y carry-normalised.
+  //   X3 = E F, Y3 = G H, T3 = E H, Z3 = F G: every coordinate the output of a lazy product, the stored form of an
+  //   addition's result, so doublings and madd_affine chain in any order with no canon between them.  The order below
+  //   lets X, Y and then Z die as early as they can.
+  template <bool WITH_T>
+  static MSM_HD Ext dbl_any(const Ext& p) {
+    const El s = F::sqr_lz(F::norm(F::add_lz(p.x, p.y)));
+    fence();
+    const El a = F::sqr_lz(p.x);
+    fence();
+    const El b = F::sqr_lz(p.y);
+    fence();
+    const El h = F::add_lz(a, b);
+    const El g = F::norm(F::add_kp_sub(a, K::KP2, b));
+    const El e = F::norm(F::add_kp_sub(h, K::KP2, s));
+    const El zz = F::sqr_lz(p.z);
+    fence();
+    const El f = F::norm(F::add_lz(F::add_lz(zz, zz), g));
+    Ext r;
+    r.x = F::mul_lz(e, f);
+    r.y = F::mul_lz(h, g);
+    r.t = WITH_T ? F::mul_lz(h, e) : F::zero();
+    r.z = F::mul_lz(f, g);
+    return r;
+  }
+  static MSM_HD Ext dbl(const Ext& p) { return dbl_any<true>(p); }
+  static MSM_HD Ext dbl_nt(const Ext& p) { return dbl_any<false>(p); }
   // E = B - A, F = D - C, G = D + C, H = B + A;  X3 = E F, Y3 = G H, T3 = E H, Z3 = F G.
   // d may be limb-wise doubled (limbs < 2^30, value < 2p + 2e): F < 5p, G < 4p, still N-form after norm().
   static MSM_HD Ext finish(const El& a, const El& b, const El& c, const El& d) {

@@ -8,6 +8,7 @@ MsmError(MSM377_EHIP) at context creation.
 """
 import ctypes
 import os
+import re
 import sys
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
@@ -206,6 +207,7 @@ class WalkTablesInfo(NamedTuple):
 
 
 WALK_BATCH_MUL, WALK_BATCH_MUL_MULTI, WALK_COMMIT_ROWS, WALK_BATCH_MUL_VAR, WALK_BATCH_LINCOMB2, WALK_ED_BATCH_MUL_MULTI = 1, 2, 3, 4, 5, 6
+WALK_ED_BATCH_MUL_VAR = 7
 WALK_FORM_XYZZ, WALK_FORM_ED = 0, 1
 
 
@@ -234,8 +236,11 @@ class MsmError(RuntimeError):
     """Raised for any non-zero return of the C ABI (the reference throws Error /
     AssertionError, src/submission/implementation/cuzk/gpu.ts:7-10, submission.ts:405)."""
 
-    def __init__(self, code: int, what: str, detail: str = ""):
+    def __init__(self, code: int, what: str, detail: str = "", index=None):
         self.code = code
+        # EPOINT: the lowest failing index -- given by the caller, or the "point <i>" of msm377_last_error's text
+        found = re.search(r"\bpoint (\d+)\b", detail) if code == EPOINT and index is None else None
+        self.index = int(found.group(1)) if found else index
         msg = "%s failed: %s (%d)" % (what, _strerror(code), code)
         if detail:
             msg += ": " + detail
@@ -364,6 +369,10 @@ def load_library():
         "msm377_ed_batch_mul_multi_device": (i32, [vp, u8p, u32, vp, u64, u64, u64, vp]),
         "msm377_ed_batch_mul_multi": (i32, [vp, u8p, u32, u8p, u64, u64, u64, vp]),
         "msm377_ed_batch_mul_multi_host": (i32, [u8p, u32, u8p, u64, u64, u64, vp]),
+        "msm377_ed_batch_mul_var_device": (i32, [vp, vp, vp, u64, u32, vp]),
+        "msm377_ed_batch_mul_var": (i32, [vp, u8p, u8p, u64, u32, vp]),
+        "msm377_ed_batch_mul_var_host": (i32, [u8p, u8p, u64, u32, vp]),
+        "msm377_ed_read_walk_tables": (i32, [vp, vp, u64, u64, vp]),
         "msm377_ed_ctx_get_mul_table_builds": (u64, [vp]),
         "msm377_ed_read_mul_table": (i32, [vp, u32, vp, u64, u64, vp]),
         "msm377_ctx_set_mul_window": (i32, [vp, i32]),
@@ -545,6 +554,31 @@ def ed_batch_mul_multi_host(bases: bytes, scalars: bytes, layout="rows") -> byte
     rc = load_library().msm377_ed_batch_mul_multi_host(bytes(bases), k, bytes(scalars), n, out_stride, base_stride, ctypes.addressof(out))
     if rc:
         raise MsmError(rc, "msm377_ed_batch_mul_multi_host")
+    return out.raw[: 64 * n]
+
+
+def _ed_var_shape(points: bytes, scalars: bytes) -> Tuple[int, int]:
+    """(n, scalar_stride) of n 64-byte Edwards-BLS12 points and their scalars."""
+    if len(points) % 64:
+        raise ValueError("an Edwards-BLS12 point is 64 bytes")
+    n = len(points) // 64
+    return n, _var_scalar_stride(scalars, n)
+
+
+def ed_batch_mul_var_host(points: bytes, scalars: bytes) -> bytes:
+    """out[i] = [s_i]P_i on Edwards-BLS12 on the calling thread (msm377_ed_batch_mul_var_host): no context, no device.
+    ``points``: n records of 64 wire bytes, every one a curve point; ``scalars``: 32 bytes per point, or 32 bytes for all of
+    them, any value below 2^256.  Returns n 64-byte wire records; the identity is (0, 1).  A point that is not on the
+    curve raises MsmError(EPOINT) whose ``index`` is the lowest failing one (msm377_ed_check_points_host names it)."""
+    n, stride = _ed_var_shape(points, scalars)
+    out = ctypes.create_string_buffer(max(1, 64 * n))
+    rc = load_library().msm377_ed_batch_mul_var_host(bytes(points), bytes(scalars), n, stride, ctypes.addressof(out))
+    if rc == EPOINT:
+        rep = ed_check_points_host(points, CHECK_CANONICAL | CHECK_CURVE)
+        why = "has a coordinate that is not below q" if rep.first_bad_reason == CHECK_CANONICAL else "is not on the curve"
+        raise MsmError(rc, "msm377_ed_batch_mul_var_host", "point %d %s" % (rep.first_bad, why), index=rep.first_bad)
+    if rc:
+        raise MsmError(rc, "msm377_ed_batch_mul_var_host")
     return out.raw[: 64 * n]
 
 
@@ -1142,6 +1176,23 @@ class MsmEngine:
         self._check(rc, "msm377_ed_batch_mul_multi")
         return out.raw[: 64 * n]
 
+    def ed_batch_mul_var_device(self, d_points: int, d_scalars: int, n: int, d_out: int, scalar_stride: int = 32):
+        """out[i] = [s_i]P_i on Edwards-BLS12 for n 64-byte wire points at ``d_points`` and their scalars at ``d_scalars``
+        (``scalar_stride`` 0: ONE 32-byte scalar for all), as 64-byte wire records at ``d_out``
+        (msm377_ed_batch_mul_var_device).  Any n; every curve point is a legal input; ``d_out`` may be ``d_points``.  A
+        point that is not on the curve raises MsmError(EPOINT) with its ``index``, the outputs untouched."""
+        rc = self._lib.msm377_ed_batch_mul_var_device(self._ctx, d_points or None, d_scalars or None, int(n), int(scalar_stride), d_out or None)
+        self._check(rc, "msm377_ed_batch_mul_var_device")
+
+    def ed_batch_mul_var(self, points: bytes, scalars: bytes) -> bytes:
+        """Host-buffer form: returns n 64-byte wire records.  A 32-byte ``scalars`` with n > 1 points is the one scalar of
+        all points (msm377_ed_batch_mul_var)."""
+        n, stride = _ed_var_shape(points, scalars)
+        out = ctypes.create_string_buffer(max(1, 64 * n))
+        rc = self._lib.msm377_ed_batch_mul_var(self._ctx, bytes(points), bytes(scalars), n, stride, ctypes.addressof(out))
+        self._check(rc, "msm377_ed_batch_mul_var")
+        return out.raw[: 64 * n]
+
     def ed_batch_mul(self, base: bytes, scalars: bytes) -> bytes:
         """out[i] = [s_i]B for one Edwards-BLS12 base: ed_batch_mul_multi with k = 1."""
         return self.ed_batch_mul_multi(base, scalars)
@@ -1300,6 +1351,22 @@ class MsmEngine:
         count = info.m - int(first) if count is None else int(count)
         words = np.empty((info.entries, count, MUL_TABLE_RECORD_WORDS), dtype=np.uint32)
         self._check(self._lib.msm377_g1_read_walk_tables(self._ctx, None, int(table), int(first), count, words.ctypes.data if count else None), "msm377_g1_read_walk_tables")
+        return info, words
+
+    def ed_read_walk_tables(self, first: int = 0, count=None, info_only: bool = False):
+        """(WalkTablesInfo, records) of the per-point tables [1..8]P_i the last pass of ed_batch_mul_var* walked
+        (msm377_ed_read_walk_tables): ``records`` has shape (entries, count, 32) u32 in the MSM377_BASES_ED layout, entry e
+        of point first + j at [e - 1, j].  MsmError(ESTATE) unless the last batch call was that one and completed."""
+        import numpy as np
+
+        raw = _WalkTablesInfoStruct()
+        self._check(self._lib.msm377_ed_read_walk_tables(self._ctx, ctypes.addressof(raw), 0, 0, None), "msm377_ed_read_walk_tables")
+        info = WalkTablesInfo(int(raw.m), int(raw.tables), int(raw.entries))
+        if info_only:
+            return info, None
+        count = info.m - int(first) if count is None else int(count)
+        words = np.empty((info.entries, count, MUL_TABLE_RECORD_WORDS), dtype=np.uint32)
+        self._check(self._lib.msm377_ed_read_walk_tables(self._ctx, None, int(first), count, words.ctypes.data if count else None), "msm377_ed_read_walk_tables")
         return info, words
 
     def stage_form(self) -> int:

@@ -160,6 +160,13 @@ const ed_batch_mul_multi = (bases, scalars, { layout = 'rows' } = {}) => {
 };
 const ed_batch_mul = (base, scalars) => ed_batch_mul_multi(base, scalars);
 
+// Edwards-BLS12 variable-base batch multiplication (msm377_ed_batch_mul_var): out[i] = [s_i]P_i, every output its own point
+// (record scanning [view_key] nonce_i, the ElGamal / ECDH halves [r_i]PK_i).  `points`: a Buffer of 64-byte wire records
+// x || y; `scalars`: one per point, or ONE scalar (a 32-byte Buffer, a one-element array) for all points.  Returns a Buffer
+// of n 64-byte records; the identity is (0, 1).  Every curve point is a legal input; a point off the curve throws, and the
+// text names its index.
+const ed_batch_mul_var = (points, scalars) => addon.edBatchMulVarSync(points, scalarsToBuffer(scalars));
+
 // Row commitments (msm377_g1_set_generators / msm377_g1_commit_rows): out[i] = sum_j [s_ij]G_j over a RESIDENT set of up to
 // 4 096 generators (Pedersen vector commitments).  set_generators(gens, {windowBits}) builds and keeps the window tables --
 // `gens`: {x, y} points or a Buffer of 96-byte wire records; windowBits 0 (= 8), 8, or 16 for up to 64 generators; an empty
@@ -172,4 +179,4 @@ const commit_rows = (scalars, k, { outForm = 'wire', layout = 'rows' } = {}) => 
   return addon.commitRowsSync(scalarsToBuffer(scalars), k, BATCH_MUL_FORMS[outForm], BATCH_MUL_LAYOUTS[layout]);
 };
 
-module.exports = { batch_lincomb2, batch_mul, batch_mul_multi, ed_batch_mul, ed_batch_mul_multi, commit_rows, set_generators, batch_mul_var, compute_msm, compute_msm_edwards, set_bases, compute_msm_fixed_base, check_points, CHECK_CANONICAL, CHECK_CURVE, CHECK_SUBGROUP, CHECK_ALL, pointsToBuffer, scalarsToBuffer, version: addon.version };
+module.exports = { batch_lincomb2, batch_mul, batch_mul_multi, ed_batch_mul, ed_batch_mul_multi, ed_batch_mul_var, commit_rows, set_generators, batch_mul_var, compute_msm, compute_msm_edwards, set_bases, compute_msm_fixed_base, check_points, CHECK_CANONICAL, CHECK_CURVE, CHECK_SUBGROUP, CHECK_ALL, pointsToBuffer, scalarsToBuffer, version: addon.version };

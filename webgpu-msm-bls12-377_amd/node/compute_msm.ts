@@ -257,6 +257,13 @@ export const ed_batch_mul_multi = (
 
 export const ed_batch_mul = (base: Buffer, scalars: bigint[] | Uint32Array[] | Buffer): Buffer => ed_batch_mul_multi(base, scalars);
 
+// Edwards-BLS12 variable-base batch multiplication (msm377_ed_batch_mul_var): out[i] = [s_i]P_i, every output its own 64-byte
+// wire point.  `points`: a Buffer of 64-byte wire records; `scalars`: one per point, or ONE scalar (a 32-byte Buffer, a
+// one-element array) for all points.  Every curve point is a legal input; a point off the curve throws, and the text names
+// its index.
+export const ed_batch_mul_var = (points: Buffer, scalars: bigint[] | Uint32Array[] | Buffer): Buffer =>
+  addon.edBatchMulVarSync(points, scalarsToBuffer(scalars));
+
 // Row commitments (msm377_g1_set_generators / msm377_g1_commit_rows): out[i] = sum_j [s_ij]G_j over a RESIDENT set of up to
 // 4 096 generators.  set_generators builds and keeps the window tables (windowBits 0 = 8, 8, or 16 for up to 64
 // generators; an empty list drops the set); commit_rows runs over the first k generators, `scalars` the k x n matrix as one

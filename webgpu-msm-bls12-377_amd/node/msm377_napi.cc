@@ -29,6 +29,7 @@
 //   edBatchMulMultiSync(bases: Buffer 64k, scalars: Buffer 32kn, columns: number): Buffer 64n
 //                                                                      out[i] = sum_j [s_ij]B_j on Edwards-BLS12
 //                                                                      (msm377_ed_batch_mul_multi), 64-byte records x || y
+//   edBatchMulVarSync(points: Buffer, scalars: Buffer) -> Buffer     out[i] = [s_i]P_i on Edwards-BLS12 (msm377_ed_batch_mul_var)
 //   setGeneratorsSync(gens: Buffer 96k, windowBits: number): void       row commitments: build and keep the window tables of k
 //                                                                      generators (msm377_g1_set_generators); an empty Buffer
 //                                                                      drops the set
@@ -581,6 +582,48 @@ napi_value EdBatchMulMultiSync(napi_env env, napi_callback_info info) {
   return points;
 }
 
+// edBatchMulVarSync(points, scalars) -> Buffer: out[i] = [s_i]P_i on Edwards-BLS12 (msm377_ed_batch_mul_var); points: 64 bytes
+// x || y each, scalars: 32 bytes per point, or 32 bytes of ONE scalar for all; n records of 64 bytes, the identity as (0, 1).
+// A point that is not on the curve throws, with the index in the text
+napi_value EdBatchMulVarSync(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  bool pb = false, sb = false;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 2 || napi_is_buffer(env, argv[0], &pb) != napi_ok || !pb ||
+      napi_is_buffer(env, argv[1], &sb) != napi_ok || !sb) {
+    napi_throw_type_error(env, nullptr, "expected (points: Buffer of 64 bytes per point, scalars: Buffer of 32 bytes per point or 32 bytes)");
+    return nullptr;
+  }
+  uint8_t *p, *s;
+  size_t pl, sl;
+  napi_get_buffer_info(env, argv[0], reinterpret_cast<void**>(&p), &pl);
+  napi_get_buffer_info(env, argv[1], reinterpret_cast<void**>(&s), &sl);
+  const uint64_t n = pl / 64;
+  const uint32_t scalar_stride = (sl == 32 && n > 1) ? 0 : 32;
+  if (pl % 64 != 0 || (scalar_stride && sl != n * 32)) {
+    napi_throw_range_error(env, nullptr, "points must hold 64 bytes each, scalars 32 bytes per point or 32 bytes for all");
+    return nullptr;
+  }
+  napi_value points;
+  void* pd = nullptr;
+  if (napi_create_buffer(env, n * 64, &pd, &points) != napi_ok) return nullptr;
+  std::string err;
+  int rc;
+  {
+    std::lock_guard<std::mutex> lock(g_mu);
+    rc = ensure_ctx(1, &err);  // any capacity: the call walks n in passes of its own
+    if (!rc) {
+      rc = msm377_ed_batch_mul_var(g_ctx, p, s, n, scalar_stride, static_cast<uint8_t*>(pd));
+      if (rc) err = std::string("msm377_ed_batch_mul_var: ") + msm377_strerror(rc) + ": " + msm377_last_error(g_ctx);
+    }
+  }
+  if (rc) {
+    napi_throw_error(env, nullptr, err.c_str());
+    return nullptr;
+  }
+  return points;
+}
+
 // setGeneratorsSync(gens, windowBits): the resident generator set of commitRowsSync; an empty Buffer drops it
 napi_value SetGeneratorsSync(napi_env env, napi_callback_info info) {
   size_t argc = 2;
@@ -732,6 +775,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"batchLincomb2Sync", nullptr, BatchLincomb2Sync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"batchMulMultiSync", nullptr, BatchMulMultiSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"edBatchMulMultiSync", nullptr, EdBatchMulMultiSync, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"edBatchMulVarSync", nullptr, EdBatchMulVarSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"setGeneratorsSync", nullptr, SetGeneratorsSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"commitRowsSync", nullptr, CommitRowsSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"version", nullptr, Version, nullptr, nullptr, nullptr, napi_default, nullptr},
