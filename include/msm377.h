@@ -598,6 +598,7 @@ int msm377_g1_read_mul_table(msm377_ctx* ctx, uint32_t which, uint32_t index, ms
 #define MSM377_WALK_BATCH_LINCOMB2 5
 #define MSM377_WALK_ED_BATCH_MUL_MULTI 6
 #define MSM377_WALK_ED_BATCH_MUL_VAR 7 /* k_edbmv_accumulate; its tables: msm377_ed_read_walk_tables */
+#define MSM377_WALK_ED_BATCH_LINCOMB2 8 /* k_edbl2_accumulate: form ED, width 4, k 2; its two tables: msm377_ed_read_walk_table */
 #define MSM377_WALK_FORM_XYZZ 0
 #define MSM377_WALK_FORM_ED 1
 typedef struct msm377_walk_stash_info {
@@ -835,6 +836,56 @@ int msm377_ed_batch_mul_var(msm377_ctx* ctx, const uint8_t* points, const uint8_
  * context to carry the text of a refusal: msm377_ed_check_points_host names the index and the reason. */
 int msm377_ed_batch_mul_var_host(const uint8_t* points, const uint8_t* scalars, uint64_t n, uint32_t scalar_stride, uint8_t* out_points);
 int msm377_ed_read_walk_tables(msm377_ctx* ctx, msm377_walk_tables_info* info, uint64_t first, uint64_t count, uint32_t* words);
+
+/* ---- Edwards-BLS12 pairwise linear combination --------------------------------------------- */
+
+/* out[i] = [a_i]P_i + [b_i]Q_i on Edwards-BLS12: n pairs of points, two scalars each, every output its own 64-byte wire
+ * point (Schnorr verification R_i = [s_i]G + [c_i]PK_i; ElGamal decryption C2_i - [sk]C1_i and re-randomisation
+ * [r_i]G + [r_i']PK_i; plain P_i + Q_i with a = b = 1).  Wherever they overlap the contract is word for word that of
+ * msm377_ed_batch_mul_var* above and of msm377_g1_batch_lincomb2* below -- 64-byte wire records in and out, the identity
+ * the record (0, 1), no out_form and no flag bytes; every 32-byte value a legal scalar, not reduced, no MSM377_ESCALAR, no
+ * rerun; any n, n = 0 MSM377_OK without a launch; 16-byte aligned device pointers; synchronous calls; MSM377_EINVAL while
+ * a non-wire input form is set, for a misaligned pointer, a null pointer with n > 0 or a stride outside its set, with the
+ * outputs untouched -- and this section states only what differs (csrc/kernels/ed_batch_lincomb2.hpp).
+ *
+ * Strides.  a_stride and b_stride are each 32 or 0, p_stride and q_stride each 64 or 0; 0 means ONE scalar or ONE point
+ * for all n pairs, and only its 32 or 64 bytes are read.  The four are independent: p_stride = 0 with q_stride = 64 is the
+ * Schnorr shape.  (The G1 call has no point strides: the one deliberate difference in shape.)
+ *
+ * Points and relations.  Every curve point is a legal input in either array, mixed freely, and every relation between the
+ * two is followed through by the complete law itself: Q_i = P_i, Q_i = -P_i, Q_i = [m]P_i, a sum of O from two terms that
+ * are not O, both terms O.  No subgroup test is run.
+ *
+ * Refusal.  Before anything is written the device call runs the canonical + on-curve check over BOTH arrays (a stride-0
+ * array is ONE point), into counters of the call's own; a finding is MSM377_EPOINT with the outputs untouched, and
+ * msm377_last_error reads "point <i> of p ..." or "point <i> of q ...": the array, the lowest failing index in it, and the
+ * reason.  Of a finding in each array the one with the lower index is reported; p where they are equal.  The host-buffer
+ * call works in pieces of 2^20 pairs; a call of several pieces checks every piece of both arrays first, on the device.
+ *
+ * Overlap.  d_p and d_q are only read and may overlap or be the same pointer.  d_out_points may equal d_p or d_q where
+ * that array's stride is 64, and the fold in place works (d_q = d_p + h records, d_out_points = d_p, n = h): a pass reads
+ * all of its inputs before it writes its outputs, and passes cover disjoint index ranges.  d_out_points equal to the
+ * pointer of a stride-0 array is MSM377_EINVAL.  Any other overlap is the caller's bug.
+ *
+ * State.  Passes are 2^16 pairs: both per-point tables [1..8]P_i and [1..8]Q_i of a pass, 16 x 2^16 records, are exactly
+ * the table memory of msm377_g1_batch_mul_var* (128 MB, never valid between calls) and one normalisation chunk.  The
+ * resident MSM bases, every G1 table, slot and build counter, the 16 Edwards-BLS12 table slots and
+ * msm377_ed_ctx_get_mul_table_builds, the generator set and a check call's state are untouched, and the other way round.
+ *
+ * msm377_ed_read_walk_table copies table `table` of the last pass (0: of the P_i, 1: of the Q_i; info.tables = 2), records
+ * as msm377_ed_read_walk_tables above, which is table 0 of it and stays valid after a variable-base call (tables = 1).  A
+ * stride-0 array's table holds the same eight records for every i.  msm377_g1_read_walk_tables is MSM377_ESTATE after
+ * this call. */
+int msm377_ed_batch_lincomb2_device(msm377_ctx* ctx, const void* d_p, const void* d_q, const void* d_a, const void* d_b, uint64_t n, uint32_t p_stride /* 64 or 0 */,
+                                    uint32_t q_stride /* 64 or 0 */, uint32_t a_stride /* 32 or 0 */, uint32_t b_stride /* 32 or 0 */, void* d_out_points /* n x 64 */);
+int msm377_ed_batch_lincomb2(msm377_ctx* ctx, const uint8_t* p, const uint8_t* q, const uint8_t* a, const uint8_t* b, uint64_t n, uint32_t p_stride, uint32_t q_stride, uint32_t a_stride,
+                             uint32_t b_stride, uint8_t* out_points);
+/* The same on ONE CPU thread: no device, no context (csrc/ed_batch_lincomb2_host.hpp): the same checks and codes, each term
+ * by plain double-and-add on the canonical formulas, then one addition and one inversion per output; the yardstick of the
+ * device call.  There is no context to carry the text of a refusal: msm377_ed_check_points_host names index and reason. */
+int msm377_ed_batch_lincomb2_host(const uint8_t* p, const uint8_t* q, const uint8_t* a, const uint8_t* b, uint64_t n, uint32_t p_stride, uint32_t q_stride, uint32_t a_stride,
+                                  uint32_t b_stride, uint8_t* out_points);
+int msm377_ed_read_walk_table(msm377_ctx* ctx, msm377_walk_tables_info* info, uint32_t table, uint64_t first, uint64_t count, uint32_t* words);
 
 /* ---- variable-base batch multiplication --------------------------------------------------- */
 

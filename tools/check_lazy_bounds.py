@@ -276,6 +276,15 @@ def te_formulas(canonical):
     for pt, tag in ((acc, "te dbl after amadd"), ((x, y, t, z), "te dbl after dbl")):
         x, y, t, z = te_dbl(pt[0], pt[1], pt[3], tag)
     te_amadd(x, y, t, z, "te amadd after dbl")
+    # The joint walk of kernels/ed_batch_lincomb2.hpp: two additions per step.  New against the chain above: madd_affine
+    # directly after madd_affine (the second term reads what the first returned, T included), dbl_nt after two additions,
+    # and both of step 64, the carries': an addition to O and one to what that returned.
+    first = te_amadd(zero, one, zero, one, "te l2 carry amadd")
+    second = te_amadd(*first, "te l2 carry amadd after amadd")
+    first = te_amadd(x, y, t, z, "te l2 amadd after dbl")
+    second = te_amadd(*first, "te l2 amadd after amadd")
+    for pt, tag in ((second, "te l2 dbl after two amadd"), (first, "te l2 dbl after one amadd")):
+        te_amadd(*te_dbl(pt[0], pt[1], pt[3], tag), tag + ", amadd")
 
     # canonical operations on stored (lazy) coordinates: mul() = reduce_once(mul_lz()) needs mul_lz < 2p
     mul_lz(PX, canonical, "gather X*TO64")

@@ -14,6 +14,7 @@
 #include "batch_mul_multi_host.hpp"
 #include "ed_batch_mul_host.hpp"
 #include "ed_batch_mul_var_host.hpp"
+#include "ed_batch_lincomb2_host.hpp"
 #include "commit_rows_host.hpp"
 #include "commit_rows_plan.hpp"
 #include "batch_lincomb2_host.hpp"
@@ -383,6 +384,10 @@ int msm377_ed_batch_mul_multi_host(const uint8_t* bases_xy, uint32_t k, const ui
 int msm377_ed_batch_mul_var_host(const uint8_t* points, const uint8_t* scalars, uint64_t n, uint32_t scalar_stride, uint8_t* out_points) {
   return ed_batch_mul_var_host(points, scalars, n, scalar_stride, out_points);
 }
+int msm377_ed_batch_lincomb2_host(const uint8_t* p, const uint8_t* q, const uint8_t* a, const uint8_t* b, uint64_t n, uint32_t p_stride, uint32_t q_stride, uint32_t a_stride,
+                                  uint32_t b_stride, uint8_t* out_points) {
+  return ed_batch_lincomb2_host(p, q, a, b, n, p_stride, q_stride, a_stride, b_stride, out_points);
+}
 
 uint64_t msm377_ed_ctx_get_mul_table_builds(const msm377_ctx* ctx) { return ctx ? ctx->edbm.builds : 0; }
 
@@ -487,6 +492,17 @@ int msm377_ed_batch_mul_var(msm377_ctx* ctx, const uint8_t* points, const uint8_
 }
 int msm377_ed_read_walk_tables(msm377_ctx* ctx, msm377_walk_tables_info* info, uint64_t first, uint64_t count, uint32_t* words) {
   return eng::ed_read_walk_tables(ctx, info, first, count, words);
+}
+int msm377_ed_batch_lincomb2_device(msm377_ctx* ctx, const void* d_p, const void* d_q, const void* d_a, const void* d_b, uint64_t n, uint32_t p_stride, uint32_t q_stride,
+                                    uint32_t a_stride, uint32_t b_stride, void* d_out_points) {
+  return ed_wire_only(ctx) ? MSM377_EINVAL : eng::ed_batch_lincomb2_device(ctx, d_p, d_q, d_a, d_b, n, p_stride, q_stride, a_stride, b_stride, d_out_points);
+}
+int msm377_ed_batch_lincomb2(msm377_ctx* ctx, const uint8_t* p, const uint8_t* q, const uint8_t* a, const uint8_t* b, uint64_t n, uint32_t p_stride, uint32_t q_stride, uint32_t a_stride,
+                             uint32_t b_stride, uint8_t* out_points) {
+  return ed_wire_only(ctx) ? MSM377_EINVAL : eng::ed_batch_lincomb2(ctx, p, q, a, b, n, p_stride, q_stride, a_stride, b_stride, out_points);
+}
+int msm377_ed_read_walk_table(msm377_ctx* ctx, msm377_walk_tables_info* info, uint32_t table, uint64_t first, uint64_t count, uint32_t* words) {
+  return eng::ed_read_walk_table(ctx, info, table, first, count, words);
 }
 int msm377_ed_read_mul_table(msm377_ctx* ctx, uint32_t index, msm377_mul_table_info* info, uint64_t first, uint64_t count, uint32_t* words) {
   return eng::ed_read_mul_table(ctx, index, info, first, count, words);

@@ -115,6 +115,9 @@ struct EdBatchMulState {
   // The variable-base call (msm377_ed_batch_mul_var*, kernels/ed_batch_mul_var.hpp): the counters of ITS point check
   // (CHK_WORDS words, allocated on first use).  Its per-point tables are BatchMulState::var_table.
   uint32_t* point_check = nullptr;
+  // The pairwise linear combination (msm377_ed_batch_lincomb2*, kernels/ed_batch_lincomb2.hpp): the counters of ITS two
+  // point checks, p's then q's (2 x CHK_WORDS words, allocated on first use).
+  uint32_t* pair_check = nullptr;
 };
 
 // The resident generator set of the row commitments (msm377_g1_set_generators / msm377_g1_commit_rows*,

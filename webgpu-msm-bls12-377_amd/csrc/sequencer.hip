@@ -53,6 +53,7 @@
 #include "host_tail.hpp"
 #include "ed_batch_mul_host.hpp"
 #include "ed_batch_mul_var_host.hpp"
+#include "ed_batch_lincomb2_host.hpp"
 #include "validate_host.hpp"
 #include "kernels/accumulate.hpp"
 #include "kernels/batch_mul.hpp"
@@ -68,6 +69,7 @@
 #include "kernels/import.hpp"
 #include "kernels/batch_mul_var.hpp"
 #include "kernels/ed_batch_mul_var.hpp"
+#include "kernels/ed_batch_lincomb2.hpp"
 #include "kernels/batch_lincomb2.hpp"
 #include "kernels/wide.hpp"
 
@@ -2711,6 +2713,123 @@ int ed_batch_mul_var(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scal
   });
 }
 
+// ---- Edwards-BLS12 pairwise linear combination (include/msm377.h; kernels/ed_batch_lincomb2.hpp) ----
+// The flow of the G1 call below on the Edwards kernels, behind the step of the Edwards variable-base call above: the
+// canonical + on-curve check of BOTH arrays before anything is written.  Per pass of EDBL2_PASS pairs: both tables through
+// the stash and ONE normalisation, then the joint walk; the flow normalises again.  A pass reads all of its inputs before it
+// writes its outputs, and passes cover disjoint index ranges: d_out_points == d_p or == d_q is safe where that array has a
+// record per pair, and so is the fold in place (q = p + h records, out = p, n = h).  The tables are ctx->bm.var_table, never
+// valid between calls; no slot, key or build count of any table is read or written from here.
+namespace {
+
+int edbl2_check_args(msm377_ctx* ctx, uint32_t p_stride, uint32_t q_stride, uint32_t a_stride, uint32_t b_stride) {
+  if (!ctx) return MSM377_EINVAL;
+  ctx->err.clear();
+  forget_walk(ctx);  // as edbm_check_args
+  if (ed_batch_lincomb2_strides_ok(p_stride, q_stride, a_stride, b_stride)) return MSM377_OK;
+  ctx->err = "a_stride and b_stride are each 32 or 0 (one scalar for all pairs), p_stride and q_stride each 64 or 0 (one point for all pairs)";
+  return MSM377_EINVAL;
+}
+
+int edbl2_check_overlap(msm377_ctx* ctx, const void* p, const void* q, uint32_t p_stride, uint32_t q_stride, const void* out) {
+  if ((p_stride || out != p) && (q_stride || out != q)) return MSM377_OK;
+  ctx->err = "the outputs would overwrite the one point of a stride-0 array";
+  return MSM377_EINVAL;
+}
+
+// k_check_curve<EdCheck> over np points of p and nq of q (a stride-0 array: ONE point) into two sets of counters of this
+// call's own (ctx->edbm.pair_check): no check call's scratch, report or list is touched, nor the variable-base call's.  Two
+// tiny clears, two launches, one wait.  first_p, first_q: the index of d_p[0] / d_q[0] in the caller's array (a piece of a
+// host-buffer call; 0 for the one point of a stride-0 array).
+int edbl2_check_points(msm377_ctx* ctx, const void* d_p, uint64_t np, const void* d_q, uint64_t nq, uint64_t first_p = 0, uint64_t first_q = 0) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const int rc = bm_alloc(ctx, &ctx->edbm.pair_check, 2 * CHK_WORDS * 4);
+  if (rc) return rc;
+  const void* pts[2] = {d_p, d_q};
+  const uint64_t cnt[2] = {np, nq}, first[2] = {first_p, first_q};
+  for (uint32_t t = 0; t < 2; t++) {
+    uint32_t* scratch = ctx->edbm.pair_check + t * CHK_WORDS;
+    hipLaunchKernelGGL(k_check_clear, dim3(1), dim3(64), 0, ctx->stream, scratch);
+    if (cnt[t])
+      hipLaunchKernelGGL(k_check_curve<EdCheck>, dim3((unsigned)((cnt[t] + CHK_THREADS - 1) / CHK_THREADS)), dim3(CHK_THREADS), 0, ctx->stream, (const uint32_t*)pts[t], cnt[t], 1u, scratch,
+                         (uint32_t*)nullptr);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  uint32_t h[2 * CHK_WORDS];
+  HIP_TRY(ctx, hipMemcpyAsync(h, ctx->edbm.pair_check, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  uint64_t key[2], bad[2];
+  for (uint32_t t = 0; t < 2; t++) {
+    key[t] = (uint64_t)h[t * CHK_WORDS + CHK_FIRST] | ((uint64_t)h[t * CHK_WORDS + CHK_FIRST + 1] << 32);
+    bad[t] = key[t] == UINT64_MAX ? UINT64_MAX : first[t] + (key[t] >> 2);
+  }
+  if (bad[0] == UINT64_MAX && bad[1] == UINT64_MAX) return MSM377_OK;
+  const uint32_t t = ed_batch_lincomb2_q_first(bad[0], bad[1]) ? 1u : 0u;
+  ctx->err = ed_batch_lincomb2_refusal(t, bad[t], (uint32_t)(key[t] & 3) == CHK_CLASS_NONCANON ? MSM377_CHECK_CANONICAL : MSM377_CHECK_CURVE);
+  return MSM377_EPOINT;
+}
+
+}  // namespace
+
+int ed_batch_lincomb2_device(msm377_ctx* ctx, const void* d_p, const void* d_q, const void* d_a, const void* d_b, uint64_t n, uint32_t p_stride, uint32_t q_stride, uint32_t a_stride,
+                             uint32_t b_stride, void* d_out_points) {
+  const uint32_t a_words = a_stride / 4, b_words = b_stride / 4;
+  const auto check = [&]() -> int {
+    int rc = check_pointers<EdMul>(ctx, {}, {d_a, d_b}, {d_p, d_q}, 64, d_out_points, 64);
+    if (!rc) rc = edbl2_check_overlap(ctx, d_p, d_q, p_stride, q_stride, d_out_points);
+    return rc ? rc : edbl2_check_points(ctx, d_p, p_stride ? n : 1, d_q, q_stride ? n : 1);
+  };
+  const auto pass = [&](uint64_t off, uint64_t m) -> int {
+    uint4* stash = reinterpret_cast<uint4*>(ctx->bm.stash);
+    hipLaunchKernelGGL(k_edbl2_table, dim3(bm_grid(m).x, EDBL2_TERMS), dim3(BM_THREADS), 0, ctx->stream, (const uint8_t*)d_p + off * p_stride, (const uint8_t*)d_q + off * q_stride, p_stride,
+                       q_stride, m, stash);
+    const int rc = normalise<EdMul>(ctx, m * EDBL2_TERMS * BMV_ENTRIES, EDBM_FORM_TABLE, ctx->bm.var_table, nullptr);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_edbl2_accumulate, bm_grid(m), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)ctx->bm.var_table, (const uint32_t*)d_a + off * a_words,
+                       (const uint32_t*)d_b + off * b_words, m, a_words, b_words, stash);
+    note_walk(ctx, MSM377_WALK_ED_BATCH_LINCOMB2, MSM377_WALK_FORM_ED, (uint32_t)BMV_WIDTH, EDBL2_TERMS, 1, 0, EDBL2_TERMS);
+    return MSM377_OK;
+  };
+  return batch_device_call<EdMul>(ctx, edbl2_check_args(ctx, p_stride, q_stride, a_stride, b_stride), n, EDBL2_PASS, EDBM_FORM_WIRE, d_out_points, 64, nullptr, check,
+                                  [&] { return bmv_ensure_table(ctx); }, pass);
+}
+
+// Host buffers: both scalar arrays and both point arrays up, records down, in pieces of at most a chunk; a stride-0 scalar
+// or point is uploaded once.  A call of ONE piece leaves the check to its device call; a call of several pieces checks all
+// pieces of both arrays first, on the device, piece by piece through the staging, as ed_batch_mul_var does, and then uploads
+// the points a second time.  Pieces come in rising order, so the first piece with a finding holds the lowest index.
+int ed_batch_lincomb2(msm377_ctx* ctx, const uint8_t* p, const uint8_t* q, const uint8_t* a, const uint8_t* b, uint64_t n, uint32_t p_stride, uint32_t q_stride, uint32_t a_stride,
+                      uint32_t b_stride, uint8_t* out_points) {
+  int rc = edbl2_check_args(ctx, p_stride, q_stride, a_stride, b_stride);
+  if (rc || n == 0) return rc;
+  if (!p || !q || !a || !b || !out_points) return null_pointer(ctx);
+  rc = edbl2_check_overlap(ctx, p, q, p_stride, q_stride, out_points);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const uint64_t piece = std::min<uint64_t>(n, BM_CHUNK);
+  HostStage io(ctx, {(size_t)piece * 32, (size_t)piece * 32, (size_t)piece * 64, (size_t)piece * 64}, (size_t)piece * 64, 0,
+               "out of device memory for the linear combination staging");  // a, b, p, q
+  if (io.rc) return io.rc;
+  if (a_stride == 0) rc = io.up(0, a, 32, "hipMemcpy(scalar a)");
+  if (!rc && b_stride == 0) rc = io.up(1, b, 32, "hipMemcpy(scalar b)");
+  if (!rc && p_stride == 0) rc = io.up(2, p, 64, "hipMemcpy(point p)");
+  if (!rc && q_stride == 0) rc = io.up(3, q, 64, "hipMemcpy(point q)");
+  for (uint64_t off = 0; n > piece && off < n && !rc; off += piece) {
+    const uint64_t m = std::min<uint64_t>(piece, n - off);
+    if (p_stride) rc = io.up(2, p + off * 64, m * 64, "hipMemcpy(points p)");
+    if (!rc && q_stride) rc = io.up(3, q + off * 64, m * 64, "hipMemcpy(points q)");
+    if (!rc) rc = edbl2_check_points(ctx, io.part(2), p_stride ? m : (off ? 0 : 1), io.part(3), q_stride ? m : (off ? 0 : 1), p_stride ? off : 0, q_stride ? off : 0);
+  }
+  if (rc) return rc;
+  return io.run(n, piece, out_points, 64, nullptr, [&](uint64_t off, uint64_t m) -> int {
+    int up = a_stride ? io.up(0, a + off * 32, m * 32, "hipMemcpy(scalars a)") : MSM377_OK;
+    if (!up && b_stride) up = io.up(1, b + off * 32, m * 32, "hipMemcpy(scalars b)");
+    if (!up && p_stride) up = io.up(2, p + off * 64, m * 64, "hipMemcpy(points p)");
+    if (!up && q_stride) up = io.up(3, q + off * 64, m * 64, "hipMemcpy(points q)");
+    return up ? up : ed_batch_lincomb2_device(ctx, io.part(2), io.part(3), io.part(0), io.part(1), m, p_stride, q_stride, a_stride, b_stride, io.records());
+  });
+}
+
 // ---- pairwise linear combination (include/msm377.h "pairwise linear combination"; kernels/batch_lincomb2.hpp) ----
 // Per pass of BL2_PASS pairs: both tables through the stash and ONE normalisation, then the joint walk; the flow
 // normalises again.  A pass reads all of its inputs before it writes its outputs, and passes cover disjoint index
@@ -2841,7 +2960,7 @@ int ed_read_mul_table(msm377_ctx* ctx, uint32_t index, msm377_mul_table_info* in
   return read_mul_slot(ctx, ctx->edbm.slot[index], "that window table is not valid: never built, or left by a build that failed", info, first, count, words);
 }
 
-// ---- stash read-backs (msm377_read_walk_stash, msm377_g1_read_walk_tables, msm377_ed_read_walk_tables) ----
+// ---- stash read-backs (msm377_read_walk_stash, msm377_g1_read_walk_tables, msm377_ed_read_walk_table[s]) ----
 // Copies of what the last pass of the last batch call left (context.hpp WalkLayout), gathered from the piece-major stash
 // into point-major words: piece k of stash point j is at piece index k * BM_CHUNK + j.  No launch; every batch call has
 // waited for its stream before it returned.
@@ -2907,8 +3026,11 @@ static int read_walk_tables(msm377_ctx* ctx, uint32_t form, msm377_walk_tables_i
 int g1_read_walk_tables(msm377_ctx* ctx, msm377_walk_tables_info* info, uint32_t table, uint64_t first, uint64_t count, uint32_t* words) {
   return read_walk_tables(ctx, MSM377_WALK_FORM_XYZZ, info, table, first, count, words);
 }
+int ed_read_walk_table(msm377_ctx* ctx, msm377_walk_tables_info* info, uint32_t table, uint64_t first, uint64_t count, uint32_t* words) {
+  return read_walk_tables(ctx, MSM377_WALK_FORM_ED, info, table, first, count, words);
+}
 int ed_read_walk_tables(msm377_ctx* ctx, msm377_walk_tables_info* info, uint64_t first, uint64_t count, uint32_t* words) {
-  return read_walk_tables(ctx, MSM377_WALK_FORM_ED, info, 0, first, count, words);
+  return ed_read_walk_table(ctx, info, 0, first, count, words);
 }
 
 }  // namespace eng

@@ -66,16 +66,22 @@ int ed_batch_mul_multi(msm377_ctx* ctx, const uint8_t* bases_xy, uint32_t k, con
 // Edwards-BLS12 variable-base batch multiplication (kernels/ed_batch_mul_var.hpp): out[i] = [s_i]P_i.
 int ed_batch_mul_var_device(msm377_ctx* ctx, const void* d_points, const void* d_scalars, uint64_t n, uint32_t scalar_stride, void* d_out_points);
 int ed_batch_mul_var(msm377_ctx* ctx, const uint8_t* points, const uint8_t* scalars, uint64_t n, uint32_t scalar_stride, uint8_t* out_points);
+// Edwards-BLS12 pairwise linear combination (kernels/ed_batch_lincomb2.hpp): out[i] = [a_i]P_i + [b_i]Q_i.
+int ed_batch_lincomb2_device(msm377_ctx* ctx, const void* d_p, const void* d_q, const void* d_a, const void* d_b, uint64_t n, uint32_t p_stride, uint32_t q_stride, uint32_t a_stride,
+                             uint32_t b_stride, void* d_out_points);
+int ed_batch_lincomb2(msm377_ctx* ctx, const uint8_t* p, const uint8_t* q, const uint8_t* a, const uint8_t* b, uint64_t n, uint32_t p_stride, uint32_t q_stride, uint32_t a_stride,
+                      uint32_t b_stride, uint8_t* out_points);
 
 // The window table of a batch operation as it stands (no launch): msm377_g1_read_mul_table, msm377_ed_read_mul_table.
 int g1_read_mul_table(msm377_ctx* ctx, uint32_t which, uint32_t index, msm377_mul_table_info* info, uint64_t first, uint64_t count, uint32_t* words);
 int ed_read_mul_table(msm377_ctx* ctx, uint32_t index, msm377_mul_table_info* info, uint64_t first, uint64_t count, uint32_t* words);
 
 // What the last pass of the last batch call left in the stash, and the per-point tables it walked (no launch):
-// msm377_read_walk_stash, msm377_g1_read_walk_tables, msm377_ed_read_walk_tables.
+// msm377_read_walk_stash, msm377_g1_read_walk_tables, msm377_ed_read_walk_tables, msm377_ed_read_walk_table.
 int read_walk_stash(msm377_ctx* ctx, msm377_walk_stash_info* info, uint32_t segment, uint64_t first, uint64_t count, uint32_t* point_words, uint32_t* product_words);
 int g1_read_walk_tables(msm377_ctx* ctx, msm377_walk_tables_info* info, uint32_t table, uint64_t first, uint64_t count, uint32_t* words);
 int ed_read_walk_tables(msm377_ctx* ctx, msm377_walk_tables_info* info, uint64_t first, uint64_t count, uint32_t* words);
+int ed_read_walk_table(msm377_ctx* ctx, msm377_walk_tables_info* info, uint32_t table, uint64_t first, uint64_t count, uint32_t* words);
 
 void twin_return(msm377_ctx* ctx);  // takes back the resident bases a batch call lent to the twin of ctx
 

@@ -208,6 +208,7 @@ class WalkTablesInfo(NamedTuple):
 
 WALK_BATCH_MUL, WALK_BATCH_MUL_MULTI, WALK_COMMIT_ROWS, WALK_BATCH_MUL_VAR, WALK_BATCH_LINCOMB2, WALK_ED_BATCH_MUL_MULTI = 1, 2, 3, 4, 5, 6
 WALK_ED_BATCH_MUL_VAR = 7
+WALK_ED_BATCH_LINCOMB2 = 8
 WALK_FORM_XYZZ, WALK_FORM_ED = 0, 1
 
 
@@ -241,6 +242,9 @@ class MsmError(RuntimeError):
         # EPOINT: the lowest failing index -- given by the caller, or the "point <i>" of msm377_last_error's text
         found = re.search(r"\bpoint (\d+)\b", detail) if code == EPOINT and index is None else None
         self.index = int(found.group(1)) if found else index
+        # ed_batch_lincomb2*: the array that index counts in, "p" or "q" ("point <i> of q ..."); None for every other call
+        of = re.search(r"\bpoint \d+ of ([pq])\b", detail) if code == EPOINT else None
+        self.array = of.group(1) if of else None
         msg = "%s failed: %s (%d)" % (what, _strerror(code), code)
         if detail:
             msg += ": " + detail
@@ -373,6 +377,10 @@ def load_library():
         "msm377_ed_batch_mul_var": (i32, [vp, u8p, u8p, u64, u32, vp]),
         "msm377_ed_batch_mul_var_host": (i32, [u8p, u8p, u64, u32, vp]),
         "msm377_ed_read_walk_tables": (i32, [vp, vp, u64, u64, vp]),
+        "msm377_ed_batch_lincomb2_device": (i32, [vp, vp, vp, vp, vp, u64, u32, u32, u32, u32, vp]),
+        "msm377_ed_batch_lincomb2": (i32, [vp, u8p, u8p, u8p, u8p, u64, u32, u32, u32, u32, vp]),
+        "msm377_ed_batch_lincomb2_host": (i32, [u8p, u8p, u8p, u8p, u64, u32, u32, u32, u32, vp]),
+        "msm377_ed_read_walk_table": (i32, [vp, vp, u32, u64, u64, vp]),
         "msm377_ed_ctx_get_mul_table_builds": (u64, [vp]),
         "msm377_ed_read_mul_table": (i32, [vp, u32, vp, u64, u64, vp]),
         "msm377_ctx_set_mul_window": (i32, [vp, i32]),
@@ -579,6 +587,41 @@ def ed_batch_mul_var_host(points: bytes, scalars: bytes) -> bytes:
         raise MsmError(rc, "msm377_ed_batch_mul_var_host", "point %d %s" % (rep.first_bad, why), index=rep.first_bad)
     if rc:
         raise MsmError(rc, "msm377_ed_batch_mul_var_host")
+    return out.raw[: 64 * n]
+
+
+def _ed_lincomb2_shape(p: bytes, q: bytes, a: bytes, b: bytes) -> Tuple[int, int, int, int, int]:
+    """(n, p_stride, q_stride, a_stride, b_stride) of the four arrays of an Edwards-BLS12 linear combination: n is the
+    largest element count; an argument of exactly one element, with n > 1, is the stride-0 form (one for all pairs)."""
+    if len(p) % 64 or len(q) % 64 or len(a) % 32 or len(b) % 32:
+        raise ValueError("an Edwards-BLS12 point is 64 bytes, a scalar 32")
+    counts = (len(p) // 64, len(q) // 64, len(a) // 32, len(b) // 32)
+    n = max(counts)
+    strides = []
+    for count, size in zip(counts, (64, 64, 32, 32)):
+        if count != n and not (count == 1 and n > 1):
+            raise ValueError("p, q, a and b: one element per pair, or exactly one element for all pairs")
+        strides.append(size if count == n else 0)
+    return (n, *strides)
+
+
+def ed_batch_lincomb2_host(p: bytes, q: bytes, a: bytes, b: bytes) -> bytes:
+    """out[i] = [a_i]P_i + [b_i]Q_i on Edwards-BLS12 on the calling thread (msm377_ed_batch_lincomb2_host): no context, no
+    device.  ``p``, ``q``: 64-byte wire records, every one a curve point; ``a``, ``b``: 32-byte scalars, any value below
+    2^256.  n is the largest element count; an argument of exactly one element with n > 1 stands for all pairs.  Returns n
+    64-byte wire records; the identity is (0, 1).  A point that is not on the curve raises MsmError(EPOINT) with its
+    ``array`` ("p" or "q") and ``index``: the lower index of the two arrays' findings, p where they are equal."""
+    n, ps, qs, sa, sb = _ed_lincomb2_shape(p, q, a, b)
+    out = ctypes.create_string_buffer(max(1, 64 * n))
+    rc = load_library().msm377_ed_batch_lincomb2_host(bytes(p), bytes(q), bytes(a), bytes(b), n, ps, qs, sa, sb, ctypes.addressof(out))
+    if rc == EPOINT:
+        reps = [ed_check_points_host(pts, CHECK_CANONICAL | CHECK_CURVE) for pts in (p, q)]
+        bad = [n if r.first_bad is None else r.first_bad for r in reps]
+        t = 1 if bad[1] < bad[0] else 0
+        why = "has a coordinate that is not below q" if reps[t].first_bad_reason == CHECK_CANONICAL else "is not on the curve"
+        raise MsmError(rc, "msm377_ed_batch_lincomb2_host", "point %d of %s %s" % (bad[t], "pq"[t], why), index=bad[t])
+    if rc:
+        raise MsmError(rc, "msm377_ed_batch_lincomb2_host")
     return out.raw[: 64 * n]
 
 
@@ -1193,6 +1236,26 @@ class MsmEngine:
         self._check(rc, "msm377_ed_batch_mul_var")
         return out.raw[: 64 * n]
 
+    def ed_batch_lincomb2_device(self, d_p: int, d_q: int, d_a: int, d_b: int, n: int, d_out: int, p_stride: int = 64, q_stride: int = 64, a_stride: int = 32, b_stride: int = 32):
+        """out[i] = [a_i]P_i + [b_i]Q_i on Edwards-BLS12 for n pairs of 64-byte wire points at ``d_p`` / ``d_q`` and their
+        scalars at ``d_a`` / ``d_b``, as 64-byte wire records at ``d_out`` (msm377_ed_batch_lincomb2_device).  A stride of 0
+        is ONE point or ONE scalar for all pairs (``p_stride`` 0: the Schnorr shape [s_i]G + [c_i]PK_i).  Every curve point
+        is a legal input; ``d_out`` may be ``d_p`` or ``d_q`` where that array's stride is 64.  A point that is not on the
+        curve raises MsmError(EPOINT) with its ``array`` and ``index``, the outputs untouched."""
+        rc = self._lib.msm377_ed_batch_lincomb2_device(
+            self._ctx, d_p or None, d_q or None, d_a or None, d_b or None, int(n), int(p_stride), int(q_stride), int(a_stride), int(b_stride), d_out or None
+        )
+        self._check(rc, "msm377_ed_batch_lincomb2_device")
+
+    def ed_batch_lincomb2(self, p: bytes, q: bytes, a: bytes, b: bytes) -> bytes:
+        """Host-buffer form: returns n 64-byte wire records, n the largest element count of the four arguments.  An
+        argument of exactly one element with n > 1 is the one point or scalar of all pairs (msm377_ed_batch_lincomb2)."""
+        n, ps, qs, sa, sb = _ed_lincomb2_shape(p, q, a, b)
+        out = ctypes.create_string_buffer(max(1, 64 * n))
+        rc = self._lib.msm377_ed_batch_lincomb2(self._ctx, bytes(p), bytes(q), bytes(a), bytes(b), n, ps, qs, sa, sb, ctypes.addressof(out))
+        self._check(rc, "msm377_ed_batch_lincomb2")
+        return out.raw[: 64 * n]
+
     def ed_batch_mul(self, base: bytes, scalars: bytes) -> bytes:
         """out[i] = [s_i]B for one Edwards-BLS12 base: ed_batch_mul_multi with k = 1."""
         return self.ed_batch_mul_multi(base, scalars)
@@ -1367,6 +1430,22 @@ class MsmEngine:
         count = info.m - int(first) if count is None else int(count)
         words = np.empty((info.entries, count, MUL_TABLE_RECORD_WORDS), dtype=np.uint32)
         self._check(self._lib.msm377_ed_read_walk_tables(self._ctx, None, int(first), count, words.ctypes.data if count else None), "msm377_ed_read_walk_tables")
+        return info, words
+
+    def ed_read_walk_table(self, table: int = 0, first: int = 0, count=None, info_only: bool = False):
+        """(WalkTablesInfo, records) of table ``table`` of the last pass of ed_batch_lincomb2* (0: [1..8]P_i, 1: [1..8]Q_i;
+        info.tables = 2) or of ed_batch_mul_var* (table 0 only), records as ed_read_walk_tables returns them
+        (msm377_ed_read_walk_table).  MsmError(ESTATE) unless the last batch call was one of the two and completed."""
+        import numpy as np
+
+        raw = _WalkTablesInfoStruct()
+        self._check(self._lib.msm377_ed_read_walk_table(self._ctx, ctypes.addressof(raw), 0, 0, 0, None), "msm377_ed_read_walk_table")
+        info = WalkTablesInfo(int(raw.m), int(raw.tables), int(raw.entries))
+        if info_only:
+            return info, None
+        count = info.m - int(first) if count is None else int(count)
+        words = np.empty((info.entries, count, MUL_TABLE_RECORD_WORDS), dtype=np.uint32)
+        self._check(self._lib.msm377_ed_read_walk_table(self._ctx, None, int(table), int(first), count, words.ctypes.data if count else None), "msm377_ed_read_walk_table")
         return info, words
 
     def stage_form(self) -> int:

@@ -167,6 +167,14 @@ const ed_batch_mul = (base, scalars) => ed_batch_mul_multi(base, scalars);
 // text names its index.
 const ed_batch_mul_var = (points, scalars) => addon.edBatchMulVarSync(points, scalarsToBuffer(scalars));
 
+// Edwards-BLS12 pairwise linear combination (msm377_ed_batch_lincomb2): out[i] = [a_i]P_i + [b_i]Q_i, every output its own
+// point (Schnorr verification [s_i]G + [c_i]PK_i, ElGamal decryption and re-randomisation, plain P_i + Q_i).  `p`, `q`:
+// Buffers of 64-byte wire records x || y; `a`, `b`: scalars (bigint[], Uint32Array[] or a Buffer of 32 bytes each).  n is
+// the largest element count; an argument of exactly ONE element with n > 1 stands for all pairs.  Returns a Buffer of n
+// 64-byte records; the identity is (0, 1).  Every curve point is a legal input; a point off the curve throws, and the text
+// names its array and index.
+const ed_batch_lincomb2 = (p, q, a, b) => addon.edBatchLincomb2Sync(p, q, scalarsToBuffer(a), scalarsToBuffer(b));
+
 // Row commitments (msm377_g1_set_generators / msm377_g1_commit_rows): out[i] = sum_j [s_ij]G_j over a RESIDENT set of up to
 // 4 096 generators (Pedersen vector commitments).  set_generators(gens, {windowBits}) builds and keeps the window tables --
 // `gens`: {x, y} points or a Buffer of 96-byte wire records; windowBits 0 (= 8), 8, or 16 for up to 64 generators; an empty
@@ -179,4 +187,4 @@ const commit_rows = (scalars, k, { outForm = 'wire', layout = 'rows' } = {}) => 
   return addon.commitRowsSync(scalarsToBuffer(scalars), k, BATCH_MUL_FORMS[outForm], BATCH_MUL_LAYOUTS[layout]);
 };
 
-module.exports = { batch_lincomb2, batch_mul, batch_mul_multi, ed_batch_mul, ed_batch_mul_multi, ed_batch_mul_var, commit_rows, set_generators, batch_mul_var, compute_msm, compute_msm_edwards, set_bases, compute_msm_fixed_base, check_points, CHECK_CANONICAL, CHECK_CURVE, CHECK_SUBGROUP, CHECK_ALL, pointsToBuffer, scalarsToBuffer, version: addon.version };
+module.exports = { batch_lincomb2, batch_mul, batch_mul_multi, ed_batch_mul, ed_batch_mul_multi, ed_batch_mul_var, ed_batch_lincomb2, commit_rows, set_generators, batch_mul_var, compute_msm, compute_msm_edwards, set_bases, compute_msm_fixed_base, check_points, CHECK_CANONICAL, CHECK_CURVE, CHECK_SUBGROUP, CHECK_ALL, pointsToBuffer, scalarsToBuffer, version: addon.version };

@@ -264,6 +264,13 @@ export const ed_batch_mul = (base: Buffer, scalars: bigint[] | Uint32Array[] | B
 export const ed_batch_mul_var = (points: Buffer, scalars: bigint[] | Uint32Array[] | Buffer): Buffer =>
   addon.edBatchMulVarSync(points, scalarsToBuffer(scalars));
 
+// Edwards-BLS12 pairwise linear combination (msm377_ed_batch_lincomb2): out[i] = [a_i]P_i + [b_i]Q_i, every output its own
+// 64-byte wire point.  `p`, `q`: Buffers of 64-byte wire records; `a`, `b`: scalars.  n is the largest element count; an
+// argument of exactly ONE element with n > 1 stands for all pairs.  Every curve point is a legal input; a point off the
+// curve throws, and the text names its array and index.
+export const ed_batch_lincomb2 = (p: Buffer, q: Buffer, a: bigint[] | Uint32Array[] | Buffer, b: bigint[] | Uint32Array[] | Buffer): Buffer =>
+  addon.edBatchLincomb2Sync(p, q, scalarsToBuffer(a), scalarsToBuffer(b));
+
 // Row commitments (msm377_g1_set_generators / msm377_g1_commit_rows): out[i] = sum_j [s_ij]G_j over a RESIDENT set of up to
 // 4 096 generators.  set_generators builds and keeps the window tables (windowBits 0 = 8, 8, or 16 for up to 64
 // generators; an empty list drops the set); commit_rows runs over the first k generators, `scalars` the k x n matrix as one

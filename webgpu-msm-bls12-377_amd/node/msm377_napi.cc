@@ -30,6 +30,9 @@
 //                                                                      out[i] = sum_j [s_ij]B_j on Edwards-BLS12
 //                                                                      (msm377_ed_batch_mul_multi), 64-byte records x || y
 //   edBatchMulVarSync(points: Buffer, scalars: Buffer) -> Buffer     out[i] = [s_i]P_i on Edwards-BLS12 (msm377_ed_batch_mul_var)
+//   edBatchLincomb2Sync(p: Buffer 64n | 64, q: Buffer 64n | 64, a: Buffer 32n | 32, b: Buffer 32n | 32) -> Buffer 64n
+//                                                                      out[i] = [a_i]P_i + [b_i]Q_i on Edwards-BLS12
+//                                                                      (msm377_ed_batch_lincomb2)
 //   setGeneratorsSync(gens: Buffer 96k, windowBits: number): void       row commitments: build and keep the window tables of k
 //                                                                      generators (msm377_g1_set_generators); an empty Buffer
 //                                                                      drops the set
@@ -624,6 +627,61 @@ napi_value EdBatchMulVarSync(napi_env env, napi_callback_info info) {
   return points;
 }
 
+// edBatchLincomb2Sync(p, q, a, b) -> Buffer: out[i] = [a_i]P_i + [b_i]Q_i on Edwards-BLS12 (msm377_ed_batch_lincomb2); p, q:
+// 64 bytes x || y each, a, b: 32 bytes each; n is the largest element count, an argument of exactly ONE element with n > 1
+// stands for all pairs (stride 0); n records of 64 bytes, the identity as (0, 1).  A point that is not on the curve throws,
+// with the array and the index in the text
+napi_value EdBatchLincomb2Sync(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  bool ok = napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) == napi_ok && argc >= 4;
+  for (int i = 0; ok && i < 4; i++) {
+    bool is = false;
+    ok = napi_is_buffer(env, argv[i], &is) == napi_ok && is;
+  }
+  if (!ok) {
+    napi_throw_type_error(env, nullptr, "expected (p: Buffer, q: Buffer, a: Buffer, b: Buffer): 64 bytes per point, 32 per scalar");
+    return nullptr;
+  }
+  uint8_t* in[4];
+  size_t len[4];
+  const size_t size[4] = {64, 64, 32, 32};
+  uint64_t n = 0;
+  for (int i = 0; i < 4; i++) {
+    napi_get_buffer_info(env, argv[i], reinterpret_cast<void**>(&in[i]), &len[i]);
+    ok = ok && len[i] % size[i] == 0;
+    if (len[i] / size[i] > n) n = len[i] / size[i];
+  }
+  uint32_t stride[4];
+  for (int i = 0; i < 4; i++) {
+    const uint64_t count = len[i] / size[i];
+    stride[i] = count == n ? (uint32_t)size[i] : 0;
+    ok = ok && (count == n || (count == 1 && n > 1));
+  }
+  if (!ok) {
+    napi_throw_range_error(env, nullptr, "p, q hold 64 bytes per point, a, b 32 per scalar: one element per pair, or exactly one element for all pairs");
+    return nullptr;
+  }
+  napi_value points;
+  void* pd = nullptr;
+  if (napi_create_buffer(env, n * 64, &pd, &points) != napi_ok) return nullptr;
+  std::string err;
+  int rc;
+  {
+    std::lock_guard<std::mutex> lock(g_mu);
+    rc = ensure_ctx(1, &err);  // any capacity: the call walks n in passes of its own
+    if (!rc) {
+      rc = msm377_ed_batch_lincomb2(g_ctx, in[0], in[1], in[2], in[3], n, stride[0], stride[1], stride[2], stride[3], static_cast<uint8_t*>(pd));
+      if (rc) err = std::string("msm377_ed_batch_lincomb2: ") + msm377_strerror(rc) + ": " + msm377_last_error(g_ctx);
+    }
+  }
+  if (rc) {
+    napi_throw_error(env, nullptr, err.c_str());
+    return nullptr;
+  }
+  return points;
+}
+
 // setGeneratorsSync(gens, windowBits): the resident generator set of commitRowsSync; an empty Buffer drops it
 napi_value SetGeneratorsSync(napi_env env, napi_callback_info info) {
   size_t argc = 2;
@@ -776,6 +834,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"batchMulMultiSync", nullptr, BatchMulMultiSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"edBatchMulMultiSync", nullptr, EdBatchMulMultiSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"edBatchMulVarSync", nullptr, EdBatchMulVarSync, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"edBatchLincomb2Sync", nullptr, EdBatchLincomb2Sync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"setGeneratorsSync", nullptr, SetGeneratorsSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"commitRowsSync", nullptr, CommitRowsSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"version", nullptr, Version, nullptr, nullptr, nullptr, napi_default, nullptr},
