@@ -548,9 +548,10 @@ int msm377_g1_read_mul_table(msm377_ctx* ctx, uint32_t which, uint32_t index, ms
  *
  * msm377_read_walk_stash describes and copies what the LAST PASS of the last batch DEVICE call left in the stash: the
  * projective point of every output as its walk kernel stored it (k_bm_accumulate, k_bmm_accumulate, k_cr_accumulate and
- * k_cr_fold, k_bmv_accumulate, k_bl2_accumulate, k_edbm_accumulate) and the exclusive running products the up-sweep of the
+ * k_cr_fold, k_bmv_accumulate, k_bl2_accumulate, k_edbm_accumulate, k_edbmv_accumulate, k_edbl2_accumulate, k_edcr_accumulate and
+ * k_edcr_fold) and the exclusive running products the up-sweep of the
  * normalisation (k_bm_up, k_edbm_up) put beside them.  It covers msm377_g1_batch_mul*, _batch_mul_multi*, _commit_rows*,
- * _batch_mul_var*, _batch_lincomb2* and msm377_ed_batch_mul_multi*; a host-buffer call is one device call per piece of at
+ * _batch_mul_var*, _batch_lincomb2* and msm377_ed_batch_mul_multi*, _batch_mul_var*, _batch_lincomb2*, _commit_rows*; a host-buffer call is one device call per piece of at
  * most 2^20 scalars, and the description is that of its last piece.  `info` is written down on the host beside the
  * launches it describes; a call that does not use the read-back launches and allocates exactly what it did without it.
  *
@@ -566,7 +567,10 @@ int msm377_g1_read_mul_table(msm377_ctx* ctx, uint32_t which, uint32_t index, ms
  *   segments, stride   row commitments: the plan's segments and the stride the launches were given -- the partial sum of
  *                  segment g of row i is stash point g * stride + i.  Segment 0 holds the fold (k_cr_fold's sum over all
  *                  segments; the walk's own sum where segments == 1), segments 1 and up the partial sums the fold read and
- *                  left.  Every other call: segments 1, stride 0
+ *                  left.  Edwards-BLS12 row commitments (k_edcr_fold, in groups of 16): segment 0 holds the row's sum;
+ *                  when segments > 16, a segment g > 0 with g % 16 == 0 holds the sum of segments g .. min(segments, g + 16) - 1;
+ *                  every other segment holds its own partial sum.  Running products exist for segment 0 only.
+ *                  Every other call: segments 1, stride 0
  *
  * The stash contract (csrc/kernels/batch_mul.hpp, ed_batch_mul.hpp; tools/check_lazy_bounds.py NORMALISATION_OPERANDS):
  *   - XYZZ: limbs 0..11 of every coordinate below 2^29; X below 5p + 2^354, Y, ZZ, ZZZ below p + 2^354; ZZ^3 = ZZZ^2; a live
@@ -582,7 +586,7 @@ int msm377_g1_read_mul_table(msm377_ctx* ctx, uint32_t which, uint32_t index, ms
  * NULL buffers fills `info` alone.
  *
  * MSM377_ESTATE, and nothing written: before the first batch call; after a batch call that returned an error or had
- * n = 0 (it ran no pass); after msm377_g1_set_generators (a table build goes through the stash).  A batch call forgets
+ * n = 0 (it ran no pass); after msm377_g1_set_generators or msm377_ed_set_generators (a table build goes through the stash).  A batch call forgets
  * the description when it starts and writes a new one when its last pass is through.  MSM, check and set-bases calls do
  * not touch the stash and leave the description valid.
  *
@@ -599,6 +603,7 @@ int msm377_g1_read_mul_table(msm377_ctx* ctx, uint32_t which, uint32_t index, ms
 #define MSM377_WALK_ED_BATCH_MUL_MULTI 6
 #define MSM377_WALK_ED_BATCH_MUL_VAR 7 /* k_edbmv_accumulate; its tables: msm377_ed_read_walk_tables */
 #define MSM377_WALK_ED_BATCH_LINCOMB2 8 /* k_edbl2_accumulate: form ED, width 4, k 2; its two tables: msm377_ed_read_walk_table */
+#define MSM377_WALK_ED_COMMIT_ROWS 9 /* k_edcr_accumulate and k_edcr_fold: form ED, the set's width, the call's k, the plan's segments */
 #define MSM377_WALK_FORM_XYZZ 0
 #define MSM377_WALK_FORM_ED 1
 typedef struct msm377_walk_stash_info {
@@ -1014,6 +1019,63 @@ int msm377_g1_commit_rows_host(const uint8_t* gens_xy, uint32_t k, const uint8_t
 /* Pure, host-only: how a call over k generators is cut.  0 segments (and zeros) for k outside 1 .. MSM377_GEN_MAX.  Any of
  * the three pointers may be null. */
 void msm377_commit_rows_plan(uint32_t k, uint32_t* segments, uint32_t* bases_per_segment, uint64_t* rows_per_pass);
+
+/* ---- Edwards-BLS12 row commitments -------------------------------------------------------- */
+
+/* out[i] = sum_{j<k} [s_ij]G_j over the FIRST k generators of a resident Edwards-BLS12 set of up to MSM377_GEN_MAX
+ * generators, every output its own 64-byte wire record x || y (Pedersen and BHP-style hashes, vector commitments: sums
+ * over hundreds to thousands of fixed generators, one per record, Merkle node or witness row).  The contract is that of
+ * msm377_g1_commit_rows* above wherever that applies to this curve, and that of msm377_ed_batch_mul_multi* for everything
+ * about the curve; this section states the two lists and what differs (csrc/kernels/ed_commit_rows.hpp).
+ *
+ * From msm377_g1_commit_rows*.  The set is resident: msm377_ed_set_generators drops the old set FIRST and installs the new
+ * one as its last step, behind the wait for the build; a call that fails leaves none; gens_xy == NULL or k == 0 drops the
+ * set and frees it (MSM377_OK).  window_bits is 8, 16 (k <= MSM377_GEN_WIDE_MAX only) or 0 = 8; another width, or a k
+ * above the limits, is MSM377_EINVAL.  The set is ONE allocation, table j at record j * (records of a table), 128-byte
+ * records in the MSM377_BASES_ED layout msm377_ed_read_mul_table documents.  The calls return MSM377_ESTATE without a
+ * set or with k above the resident k; the shape (k, both strides: non-zero multiples of 32) is checked first, also for
+ * n = 0, and n = 0 is MSM377_OK with nothing launched.  s_ij is the 32 bytes at scalars + i * out_stride + j *
+ * base_stride: rows, columns, padded and sliding layouts all work.  A pass is msm377_commit_rows_plan(k)'s rows_per_pass
+ * rows long -- the one plan of both curves -- and the host-buffer call works in pieces of 2^20 / k rows, repacked
+ * row-major.  The width belongs to the set: msm377_ctx_set_mul_window does not apply and
+ * msm377_ctx_get_last_mul_window is unchanged by these calls.  With a resident k of 1 the outputs are byte for byte those
+ * of msm377_ed_batch_mul_multi_device with k = 1 at the set's width.
+ *
+ * From msm377_ed_batch_mul_multi*.  Every 32-byte value is a legal scalar, read as an integer and NOT reduced: no
+ * MSM377_ESCALAR, no rerun.  No out_form, no flag bytes: the identity is the record (0, 1).  Device pointers are 16-byte
+ * aligned.  msm377_ed_set_generators, msm377_ed_commit_rows_device and msm377_ed_commit_rows return MSM377_EINVAL while
+ * a non-wire input form is set, and change nothing.  Every curve point is a legal generator -- the identity, the point of
+ * order 2, both points of order 4, P + T, G_j = +-G_i, G_j = [m]G_i -- and every relation is followed through by the
+ * complete addition law: a row sum of O from partial sums that are not O, relations across the threads that share a row.
+ *
+ * Generators that are not on the curve.  msm377_ed_set_generators uploads the k generators and runs the canonical +
+ * on-curve check over them on the DEVICE (no subgroup test).  A finding is MSM377_EPOINT with no set afterwards;
+ * msm377_last_error names the lowest failing index ("point <i> of the generators ...") and the reason.  This differs on
+ * purpose from msm377_ed_batch_mul_multi*, which checks its at most 16 bases on the host and returns MSM377_EINVAL: the
+ * host check takes 11 us per point, about 45 ms at 4 096 generators.  The host twin checks on the host and returns
+ * MSM377_EPOINT too.
+ *
+ * State.  The set is a second one on the context, independent of G1's: both may be resident at once, and setting,
+ * dropping or failing one leaves the other alone.  The set, the resident MSM bases, every G1 table, slot and counter, the
+ * 16 Edwards-BLS12 slots with msm377_ed_ctx_get_mul_table_builds, and a check call's state are mutually untouched.
+ * msm377_ed_ctx_get_generators reports (k, width), (0, 0) without a set.  msm377_ed_read_generator_table reads generator
+ * `index`'s table as msm377_ed_read_mul_table reads a slot, with a zero key; MSM377_ESTATE without a set or for an index
+ * beyond it.
+ *
+ * The fold.  A row's walk is split across S = ceil(k / 16) threads as on G1; their partial sums are folded in groups of 16:
+ * one launch adds segments 16 h .. 16 h + 15 into segment 16 h, and for S > 16 a second one adds segments 0, 16, 32, ..
+ * into segment 0 (30 dependent additions at k = 4 096 where G1's chain has 255).  Addition is associative and the outputs
+ * are normalised, so the order does not show in the bytes.  What msm377_read_walk_stash finds after a pass: above.
+ *
+ * The same on ONE CPU thread (csrc/ed_commit_rows_host.hpp): every term by plain double-and-add on the canonical
+ * formulas, added in the order j = 0 .. k - 1, one inversion per output; k = 1 .. MSM377_GEN_MAX; refusals leave the
+ * outputs untouched. */
+int msm377_ed_set_generators(msm377_ctx* ctx, const uint8_t* gens_xy /* k x 64, HOST */, uint32_t k, int window_bits);
+int msm377_ed_ctx_get_generators(const msm377_ctx* ctx, uint32_t* k, int* window_bits);
+int msm377_ed_commit_rows_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n, uint32_t k, uint64_t out_stride, uint64_t base_stride, void* d_out_points);
+int msm377_ed_commit_rows(msm377_ctx* ctx, const uint8_t* scalars, uint64_t n, uint32_t k, uint64_t out_stride, uint64_t base_stride, uint8_t* out_points);
+int msm377_ed_commit_rows_host(const uint8_t* gens_xy, uint32_t k, const uint8_t* scalars, uint64_t n, uint64_t out_stride, uint64_t base_stride, uint8_t* out_points);
+int msm377_ed_read_generator_table(msm377_ctx* ctx, uint32_t index, msm377_mul_table_info* info, uint64_t first, uint64_t count, uint32_t* words);
 
 /* ---- measurement ------------------------------------------------------------------------ */
 

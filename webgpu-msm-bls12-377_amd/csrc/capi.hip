@@ -15,6 +15,7 @@
 #include "ed_batch_mul_host.hpp"
 #include "ed_batch_mul_var_host.hpp"
 #include "ed_batch_lincomb2_host.hpp"
+#include "ed_commit_rows_host.hpp"
 #include "commit_rows_host.hpp"
 #include "commit_rows_plan.hpp"
 #include "batch_lincomb2_host.hpp"
@@ -384,6 +385,15 @@ int msm377_ed_batch_mul_multi_host(const uint8_t* bases_xy, uint32_t k, const ui
 int msm377_ed_batch_mul_var_host(const uint8_t* points, const uint8_t* scalars, uint64_t n, uint32_t scalar_stride, uint8_t* out_points) {
   return ed_batch_mul_var_host(points, scalars, n, scalar_stride, out_points);
 }
+int msm377_ed_commit_rows_host(const uint8_t* gens_xy, uint32_t k, const uint8_t* scalars, uint64_t n, uint64_t out_stride, uint64_t base_stride, uint8_t* out_points) {
+  return ed_commit_rows_host(gens_xy, k, scalars, n, out_stride, base_stride, out_points);
+}
+int msm377_ed_ctx_get_generators(const msm377_ctx* ctx, uint32_t* k, int* window_bits) {
+  if (!ctx) return MSM377_EINVAL;
+  if (k) *k = ctx->ed_gens.k;
+  if (window_bits) *window_bits = ctx->ed_gens.width;
+  return MSM377_OK;
+}
 int msm377_ed_batch_lincomb2_host(const uint8_t* p, const uint8_t* q, const uint8_t* a, const uint8_t* b, uint64_t n, uint32_t p_stride, uint32_t q_stride, uint32_t a_stride,
                                   uint32_t b_stride, uint8_t* out_points) {
   return ed_batch_lincomb2_host(p, q, a, b, n, p_stride, q_stride, a_stride, b_stride, out_points);
@@ -506,6 +516,16 @@ int msm377_ed_read_walk_table(msm377_ctx* ctx, msm377_walk_tables_info* info, ui
 }
 int msm377_ed_read_mul_table(msm377_ctx* ctx, uint32_t index, msm377_mul_table_info* info, uint64_t first, uint64_t count, uint32_t* words) {
   return eng::ed_read_mul_table(ctx, index, info, first, count, words);
+}
+int msm377_ed_set_generators(msm377_ctx* ctx, const uint8_t* gens_xy, uint32_t k, int window_bits) { return ed_wire_only(ctx) ? MSM377_EINVAL : eng::ed_set_generators(ctx, gens_xy, k, window_bits); }
+int msm377_ed_commit_rows_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n, uint32_t k, uint64_t out_stride, uint64_t base_stride, void* d_out_points) {
+  return ed_wire_only(ctx) ? MSM377_EINVAL : eng::ed_commit_rows_device(ctx, d_scalars, n, k, out_stride, base_stride, d_out_points);
+}
+int msm377_ed_commit_rows(msm377_ctx* ctx, const uint8_t* scalars, uint64_t n, uint32_t k, uint64_t out_stride, uint64_t base_stride, uint8_t* out_points) {
+  return ed_wire_only(ctx) ? MSM377_EINVAL : eng::ed_commit_rows(ctx, scalars, n, k, out_stride, base_stride, out_points);
+}
+int msm377_ed_read_generator_table(msm377_ctx* ctx, uint32_t index, msm377_mul_table_info* info, uint64_t first, uint64_t count, uint32_t* words) {
+  return eng::ed_read_generator_table(ctx, index, info, first, count, words);
 }
 int msm377_g1_set_bases_device(msm377_ctx* ctx, const void* d_points, uint64_t n) { return converted(ctx, eng::g1_set_bases_device(ctx, d_points, n)); }
 int msm377_g1_set_bases(msm377_ctx* ctx, const uint8_t* points, uint64_t n) { return converted(ctx, eng::g1_set_bases(ctx, points, n)); }

@@ -126,10 +126,13 @@ struct EdBatchMulState {
 // memory back) before anything else and sets k as its last step, behind a wait for the build.  The build's own buffers
 // (row bases and wire bytes sized for k) live for the length of the build.  The calls borrow BatchMulState's stash, trees and block products and nothing else:
 // no table, key, width or build count of the batch_mul calls is read or written from here.
+// The Edwards-BLS12 calls (msm377_ed_set_generators / msm377_ed_commit_rows*, kernels/ed_commit_rows.hpp) keep a second
+// set of the same shape, ed_gens, under the same rule: either set is set, dropped or failed without a look at the other.
 struct GeneratorSet {
   uint32_t k = 0;             // resident generators (0: no set)
   int width = 0;              // window width of the tables: 8 or 16
   uint32_t* tables = nullptr;
+  uint32_t* check = nullptr;  // Edwards-BLS12: the counters of the set's own generator check (CHK_WORDS words, allocated on first use, kept across sets)
   bool valid() const { return k != 0; }
 };
 
@@ -171,7 +174,7 @@ struct BasesLayout {
 // What the last pass of the last batch call left in BatchMulState's stash, for msm377_read_walk_stash and
 // msm377_g1_read_walk_tables: written on the host beside the launches (sequencer.hip note_walk, batch_device_call) from the
 // values they were given.  valid: from the successful end of a batch call that ran a pass until the next batch call or
-// msm377_g1_set_generators starts (sequencer.hip forget_walk): whatever writes the stash goes through one of the two.
+// msm377_g1_set_generators / msm377_ed_set_generators starts (sequencer.hip forget_walk): whatever writes the stash goes through one of the two.
 struct WalkLayout {
   bool valid = false;
   msm377_walk_stash_info info = {};
@@ -287,6 +290,7 @@ struct msm377_ctx {
   BatchMulMultiState bmm;             // multi-base batch multiplication: a table per base position (allocated when built)
   EdBatchMulState edbm;               // Edwards-BLS12 batch multiplication: a table per base position (allocated when built)
   GeneratorSet gens;                  // row commitments: the resident generator tables (one allocation per set)
+  GeneratorSet ed_gens;               // Edwards-BLS12 row commitments: that curve's resident generator tables, independent of gens
   WideBuffers wide;                   // the 20-bit-window sort's buffers (allocated with such a table; the twin's own set)
   AffineConvert aff;
   ZeroCopyOut zc;

@@ -54,11 +54,13 @@
 #include "ed_batch_mul_host.hpp"
 #include "ed_batch_mul_var_host.hpp"
 #include "ed_batch_lincomb2_host.hpp"
+#include "ed_commit_rows_host.hpp"
 #include "validate_host.hpp"
 #include "kernels/accumulate.hpp"
 #include "kernels/batch_mul.hpp"
 #include "kernels/batch_mul_multi.hpp"
 #include "kernels/ed_batch_mul.hpp"
+#include "kernels/ed_commit_rows.hpp"
 #include "kernels/commit_rows.hpp"
 #include "kernels/convert.hpp"
 #include "kernels/decompose.hpp"
@@ -1951,8 +1953,8 @@ int g1_glv_window_partials_device(msm377_ctx* ctx, const void* d_points, const v
   return MSM377_OK;
 }
 
-// ---- the batch calls (include/msm377.h: fixed-base, multi-base, Edwards-BLS12, row commitments, variable-base, pairwise) ----
-// Six entry points over one machinery:
+// ---- the batch calls (include/msm377.h: fixed-base, multi-base, Edwards-BLS12, row commitments on both curves, variable-base, pairwise) ----
+// Their entry points over one machinery:
 //   normalise          the stash -> affine records of a form, three launches, on either curve
 //   build_mul_tables   ONE table builder: row bases, then the concatenated records in passes of at most BM_CHUNK
 //   ensure_mul_tables  ONE keeper of the table slots: which (base, width) keys are missing, and when a slot is valid
@@ -1974,8 +1976,8 @@ int bm_ensure_scratch(msm377_ctx* ctx) {
 }
 
 // ---- what the stash holds, for msm377_read_walk_stash / msm377_g1_read_walk_tables (context.hpp WalkLayout) ----
-// forget_walk: every batch call starts with it (the two argument checks that open each of them) and so does
-// msm377_g1_set_generators: from here on the stash is no longer what the last description said.  note_walk: beside a
+// forget_walk: every batch call starts with it (the two argument checks that open each of them) and so do
+// msm377_g1_set_generators and msm377_ed_set_generators: from here on the stash is no longer what the last description said.  note_walk: beside a
 // pass's walk launch, from the launch's own arguments.  batch_device_call adds the pass (n, offset, length) and marks the
 // description valid behind the call's one wait.
 void forget_walk(msm377_ctx* ctx) { ctx->last.walk.valid = false; }
@@ -2830,6 +2832,139 @@ int ed_batch_lincomb2(msm377_ctx* ctx, const uint8_t* p, const uint8_t* q, const
   });
 }
 
+// ---- Edwards-BLS12 row commitments (include/msm377.h "Edwards-BLS12 row commitments"; kernels/ed_commit_rows.hpp) ----
+// The G1 flow above on this curve's kernels, over a set of its own (ctx->ed_gens): the plan, the ONE allocation, the
+// drop-first / install-last rule and the host staging are G1's.  What differs: the generators are checked on the DEVICE
+// before anything is built (k_check_curve<EdCheck> into counters of the set's own: EdHostCheck takes 11 us per point on
+// one thread, 45 ms at 4 096 generators), and the fold is grouped (k_edcr_fold, two levels at most).
+namespace {
+
+void edcr_drop_set(msm377_ctx* ctx) {
+  GeneratorSet& gs = ctx->ed_gens;
+  gs.k = 0;
+  gs.width = 0;
+  ctx->own.release(gs.tables);
+  gs.tables = nullptr;
+}
+
+int edcr_check_args(msm377_ctx* ctx, uint32_t k, uint64_t out_stride, uint64_t base_stride) {
+  if (!ctx) return MSM377_EINVAL;
+  ctx->err.clear();
+  forget_walk(ctx);  // as edbm_check_args
+  return check_shape(ctx, k, MSM377_GEN_MAX, "k is 1 to MSM377_GEN_MAX generators", out_stride, base_stride);
+}
+
+int edcr_check_set(msm377_ctx* ctx, uint32_t k) {
+  if (!ctx->ed_gens.valid()) {
+    ctx->err = "no resident Edwards-BLS12 generator set: call msm377_ed_set_generators first";
+    return MSM377_ESTATE;
+  }
+  if (k > ctx->ed_gens.k) {
+    ctx->err = "k is above the resident generator count";
+    return MSM377_ESTATE;
+  }
+  return MSM377_OK;
+}
+
+// edbmv_check_points over the k generators at d_gens, into ctx->ed_gens.check: no check call's scratch, report or list
+// and no other batch call's counters are touched.
+int edcr_check_generators(msm377_ctx* ctx, const uint32_t* d_gens, uint32_t k) {
+  const int rc = bm_alloc(ctx, &ctx->ed_gens.check, CHK_WORDS * 4);
+  if (rc) return rc;
+  uint32_t* scratch = ctx->ed_gens.check;
+  hipLaunchKernelGGL(k_check_clear, dim3(1), dim3(64), 0, ctx->stream, scratch);
+  hipLaunchKernelGGL(k_check_curve<EdCheck>, dim3((unsigned)((k + CHK_THREADS - 1) / CHK_THREADS)), dim3(CHK_THREADS), 0, ctx->stream, d_gens, (uint64_t)k, 1u, scratch, (uint32_t*)nullptr);
+  HIP_TRY(ctx, hipGetLastError());
+  uint32_t h[CHK_WORDS];
+  HIP_TRY(ctx, hipMemcpyAsync(h, scratch, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  const uint64_t key = (uint64_t)h[CHK_FIRST] | ((uint64_t)h[CHK_FIRST + 1] << 32);
+  if (key == UINT64_MAX) return MSM377_OK;
+  ctx->err = ed_commit_rows_refusal(key >> 2, (uint32_t)(key & 3) == CHK_CLASS_NONCANON ? MSM377_CHECK_CANONICAL : MSM377_CHECK_CURVE);
+  return MSM377_EPOINT;
+}
+
+}  // namespace
+
+// As g1_set_generators; the wire bytes go up once, are checked where they lie, and the builder reads them from there
+// (its own upload writes the same bytes to the same place).
+int ed_set_generators(msm377_ctx* ctx, const uint8_t* gens_xy, uint32_t k, int window_bits) {
+  if (!ctx) return MSM377_EINVAL;
+  ctx->err.clear();
+  forget_walk(ctx);  // the build below goes through the stash
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  edcr_drop_set(ctx);  // first, whatever follows: a call that fails leaves no set
+  if (!gens_xy || k == 0) return MSM377_OK;
+  const int c = window_bits ? window_bits : BM_NARROW_WIDTH;
+  if (!batch_mul_width_supported(c)) {
+    ctx->err = "window_bits is 8, 16 or 0 (= 8)";
+    return MSM377_EINVAL;
+  }
+  if (k > MSM377_GEN_MAX || (c == BM_WIDE_WIDTH && k > MSM377_GEN_WIDE_MAX)) {
+    ctx->err = "a set holds at most MSM377_GEN_MAX generators, MSM377_GEN_WIDE_MAX with 16-bit tables";
+    return MSM377_EINVAL;
+  }
+  GeneratorSet& gs = ctx->ed_gens;
+  uint32_t *row_bases = nullptr, *gens_wire = nullptr;
+  int rc = bm_ensure_scratch(ctx);
+  if (!rc) rc = bm_alloc(ctx, &gens_wire, (size_t)k * 64);
+  if (!rc && !hip_ok(ctx, hipMemcpyAsync(gens_wire, gens_xy, (size_t)k * 64, hipMemcpyHostToDevice, ctx->stream), "hipMemcpy(generators)")) rc = MSM377_EHIP;
+  if (!rc) rc = edcr_check_generators(ctx, gens_wire, k);
+  if (!rc) rc = bm_alloc(ctx, &gs.tables, (size_t)k * bm_table_records((uint32_t)c) * BM_REC_WORDS * 4);
+  if (!rc) rc = bm_alloc(ctx, &row_bases, (size_t)k * (bm_windows(c) + 1) * BM_REC_WORDS * 4);
+  if (!rc) rc = build_mul_tables<EdMul>(ctx, gens_xy, k, c, row_bases, gens_wire, gs.tables, nullptr);
+  if (rc) (void)hipStreamSynchronize(ctx->stream);  // (nothing in flight reads what goes back below)
+  ctx->own.release(row_bases);  // (the build has waited for its launches)
+  ctx->own.release(gens_wire);
+  if (rc) {
+    edcr_drop_set(ctx);
+    return rc;
+  }
+  gs.width = c;
+  gs.k = k;
+  return MSM377_OK;
+}
+
+int ed_commit_rows_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n, uint32_t k, uint64_t out_stride, uint64_t base_stride, void* d_out_points) {
+  const int early = edcr_check_args(ctx, k, out_stride, base_stride);
+  const CommitRowsPlan plan = commit_rows_plan(early ? 1 : k);  // (a k that was refused is not planned for)
+  const auto check = [&]() -> int {
+    const int rc = check_pointers<EdMul>(ctx, {}, {d_scalars}, {}, 64, d_out_points, 64);
+    return rc ? rc : edcr_check_set(ctx, k);
+  };
+  const auto pass = [&](uint64_t off, uint64_t m) -> int {  // row `off` of the CALL's layout, as on G1
+    const GeneratorSet& gs = ctx->ed_gens;
+    uint4* stash = reinterpret_cast<uint4*>(ctx->bm.stash);
+    const dim3 grid = bm_grid(m);
+    const uint64_t part_stride = (uint64_t)grid.x * BM_THREADS;  // <= rows_per_pass, so segments * part_stride <= BM_CHUNK
+    const uint32_t S = plan.segments, groups = (S + CR_FOLD_GROUP - 1) / CR_FOLD_GROUP;
+    hipLaunchKernelGGL(k_edcr_accumulate, dim3(grid.x, S), dim3(BM_THREADS), 0, ctx->stream, (const uint32_t*)gs.tables, (const uint8_t*)d_scalars + off * out_stride, m, k, plan.bases_per_segment,
+                       out_stride, base_stride, (uint32_t)gs.width, part_stride, stash);
+    if (S > 1) hipLaunchKernelGGL(k_edcr_fold, dim3(grid.x, groups), dim3(BM_THREADS), 0, ctx->stream, stash, m, S, 1u, part_stride);
+    if (groups > 1) hipLaunchKernelGGL(k_edcr_fold, dim3(grid.x, 1), dim3(BM_THREADS), 0, ctx->stream, stash, m, S, CR_FOLD_GROUP, part_stride);
+    note_walk(ctx, MSM377_WALK_ED_COMMIT_ROWS, MSM377_WALK_FORM_ED, (uint32_t)gs.width, k, S, part_stride);
+    return MSM377_OK;
+  };
+  return batch_device_call<EdMul>(ctx, early, n, plan.rows_per_pass, EDBM_FORM_WIRE, d_out_points, 64, nullptr, check, nothing_to_prepare, pass);
+}
+
+// Host buffers: each piece of at most 2^20 scalars (2^20 / k rows) repacked row-major on the host, up, records down.
+int ed_commit_rows(msm377_ctx* ctx, const uint8_t* scalars, uint64_t n, uint32_t k, uint64_t out_stride, uint64_t base_stride, uint8_t* out_points) {
+  int rc = edcr_check_args(ctx, k, out_stride, base_stride);
+  if (rc || n == 0) return rc;
+  if (!scalars || !out_points) return null_pointer(ctx);
+  rc = edcr_check_set(ctx, k);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const uint64_t piece = std::min<uint64_t>(n, BM_CHUNK / k);
+  HostStage io(ctx, {(size_t)piece * k * 32}, (size_t)piece * 64, 0, "out of device memory for the row commitment staging");
+  if (io.rc) return io.rc;
+  return io.run(n, piece, out_points, 64, nullptr, [&](uint64_t off, uint64_t m) -> int {
+    const int up = io.repack_rows(0, scalars, off, m, k, out_stride, base_stride);
+    return up ? up : ed_commit_rows_device(ctx, io.part(0), m, k, (uint64_t)k * 32, 32, io.records());
+  });
+}
+
 // ---- pairwise linear combination (include/msm377.h "pairwise linear combination"; kernels/batch_lincomb2.hpp) ----
 // Per pass of BL2_PASS pairs: both tables through the stash and ONE normalisation, then the joint walk; the flow
 // normalises again.  A pass reads all of its inputs before it writes its outputs, and passes cover disjoint index
@@ -2958,6 +3093,15 @@ int ed_read_mul_table(msm377_ctx* ctx, uint32_t index, msm377_mul_table_info* in
     return MSM377_EINVAL;
   }
   return read_mul_slot(ctx, ctx->edbm.slot[index], "that window table is not valid: never built, or left by a build that failed", info, first, count, words);
+}
+
+// Generator `index` of ctx->ed_gens as it stands: as ed_read_mul_table reads a slot, with a zero key.
+int ed_read_generator_table(msm377_ctx* ctx, uint32_t index, msm377_mul_table_info* info, uint64_t first, uint64_t count, uint32_t* words) {
+  if (!ctx) return MSM377_EINVAL;
+  ctx->err.clear();
+  const GeneratorSet& gs = ctx->ed_gens;
+  const uint32_t* table = index < gs.k ? gs.tables + (size_t)index * bm_table_records((uint32_t)gs.width) * BM_REC_WORDS : nullptr;
+  return read_mul_table(ctx, table, gs.width, nullptr, "no resident Edwards-BLS12 generator set, or the index is beyond it", info, first, count, words);
 }
 
 // ---- stash read-backs (msm377_read_walk_stash, msm377_g1_read_walk_tables, msm377_ed_read_walk_table[s]) ----

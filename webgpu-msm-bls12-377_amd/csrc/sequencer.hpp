@@ -72,7 +72,14 @@ int ed_batch_lincomb2_device(msm377_ctx* ctx, const void* d_p, const void* d_q, 
 int ed_batch_lincomb2(msm377_ctx* ctx, const uint8_t* p, const uint8_t* q, const uint8_t* a, const uint8_t* b, uint64_t n, uint32_t p_stride, uint32_t q_stride, uint32_t a_stride,
                       uint32_t b_stride, uint8_t* out_points);
 
-// The window table of a batch operation as it stands (no launch): msm377_g1_read_mul_table, msm377_ed_read_mul_table.
+// Edwards-BLS12 row commitments (kernels/ed_commit_rows.hpp): out[i] = sum_j [s_ij]G_j over the first k generators of that curve's resident set.
+int ed_set_generators(msm377_ctx* ctx, const uint8_t* gens_xy, uint32_t k, int window_bits);
+int ed_commit_rows_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n, uint32_t k, uint64_t out_stride, uint64_t base_stride, void* d_out_points);
+int ed_commit_rows(msm377_ctx* ctx, const uint8_t* scalars, uint64_t n, uint32_t k, uint64_t out_stride, uint64_t base_stride, uint8_t* out_points);
+
+// The window table of a batch operation as it stands (no launch): msm377_g1_read_mul_table, msm377_ed_read_mul_table,
+// msm377_ed_read_generator_table.
+int ed_read_generator_table(msm377_ctx* ctx, uint32_t index, msm377_mul_table_info* info, uint64_t first, uint64_t count, uint32_t* words);
 int g1_read_mul_table(msm377_ctx* ctx, uint32_t which, uint32_t index, msm377_mul_table_info* info, uint64_t first, uint64_t count, uint32_t* words);
 int ed_read_mul_table(msm377_ctx* ctx, uint32_t index, msm377_mul_table_info* info, uint64_t first, uint64_t count, uint32_t* words);
 

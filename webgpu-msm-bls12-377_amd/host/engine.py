@@ -209,6 +209,7 @@ class WalkTablesInfo(NamedTuple):
 WALK_BATCH_MUL, WALK_BATCH_MUL_MULTI, WALK_COMMIT_ROWS, WALK_BATCH_MUL_VAR, WALK_BATCH_LINCOMB2, WALK_ED_BATCH_MUL_MULTI = 1, 2, 3, 4, 5, 6
 WALK_ED_BATCH_MUL_VAR = 7
 WALK_ED_BATCH_LINCOMB2 = 8
+WALK_ED_COMMIT_ROWS = 9
 WALK_FORM_XYZZ, WALK_FORM_ED = 0, 1
 
 
@@ -383,6 +384,12 @@ def load_library():
         "msm377_ed_read_walk_table": (i32, [vp, vp, u32, u64, u64, vp]),
         "msm377_ed_ctx_get_mul_table_builds": (u64, [vp]),
         "msm377_ed_read_mul_table": (i32, [vp, u32, vp, u64, u64, vp]),
+        "msm377_ed_set_generators": (i32, [vp, u8p, u32, i32]),
+        "msm377_ed_ctx_get_generators": (i32, [vp, vp, vp]),
+        "msm377_ed_commit_rows_device": (i32, [vp, vp, u64, u32, u64, u64, vp]),
+        "msm377_ed_commit_rows": (i32, [vp, u8p, u64, u32, u64, u64, vp]),
+        "msm377_ed_commit_rows_host": (i32, [u8p, u32, u8p, u64, u64, u64, vp]),
+        "msm377_ed_read_generator_table": (i32, [vp, u32, vp, u64, u64, vp]),
         "msm377_ctx_set_mul_window": (i32, [vp, i32]),
         "msm377_ctx_get_last_mul_window": (i32, [vp]),
         "msm377_ctx_get_mul_table_builds": (u64, [vp]),
@@ -661,6 +668,27 @@ def commit_rows_host(gens: bytes, scalars: bytes, out_form="wire", layout="rows"
     if rc:
         raise MsmError(rc, "msm377_g1_commit_rows_host")
     return out.raw[: stride * n], inf.raw[:n]
+
+
+def ed_commit_rows_host(gens: bytes, scalars: bytes, layout="rows") -> bytes:
+    """out[i] = sum_j [s_ij]G_j on Edwards-BLS12 on the calling thread (msm377_ed_commit_rows_host): no context, no device.
+    ``gens``: k records of 64 wire bytes, k up to 4 096, every one a curve point; ``scalars``: the k x n matrix of 32-byte
+    little-endian integers in ``layout``, any value below 2^256.  Returns n 64-byte wire records; the identity is (0, 1).
+    A generator that is not on the curve raises MsmError(EPOINT) whose ``index`` is the lowest failing one
+    (msm377_ed_check_points_host names it)."""
+    if len(gens) % 64:
+        raise ValueError("an Edwards-BLS12 generator is 64 bytes")
+    k = len(gens) // 64
+    n, out_stride, base_stride = _rows_shape(k, scalars, layout)
+    out = ctypes.create_string_buffer(max(1, 64 * n))
+    rc = load_library().msm377_ed_commit_rows_host(bytes(gens), k, bytes(scalars), n, out_stride, base_stride, ctypes.addressof(out))
+    if rc == EPOINT:
+        rep = ed_check_points_host(gens, CHECK_CANONICAL | CHECK_CURVE)
+        why = "has a coordinate that is not below q" if rep.first_bad_reason == CHECK_CANONICAL else "is not on the curve"
+        raise MsmError(rc, "msm377_ed_commit_rows_host", "point %d of the generators %s" % (rep.first_bad, why), index=rep.first_bad)
+    if rc:
+        raise MsmError(rc, "msm377_ed_commit_rows_host")
+    return out.raw[: 64 * n]
 
 
 def commit_rows_plan(k: int) -> Tuple[int, int, int]:
@@ -1255,6 +1283,58 @@ class MsmEngine:
         rc = self._lib.msm377_ed_batch_lincomb2(self._ctx, bytes(p), bytes(q), bytes(a), bytes(b), n, ps, qs, sa, sb, ctypes.addressof(out))
         self._check(rc, "msm377_ed_batch_lincomb2")
         return out.raw[: 64 * n]
+
+    # -- Edwards-BLS12 row commitments (include/msm377.h): out[i] = sum_j [s_ij]G_j over that curve's resident set --
+    def ed_set_generators(self, gens, window_bits: int = 0):
+        """Build and keep the window tables of the Edwards-BLS12 generators ``gens`` (64 wire bytes each, a host buffer, up
+        to 4 096; up to 64 with ``window_bits`` 16).  ``None`` or an empty buffer drops the set and frees its memory.  The
+        old set is dropped first; a call that fails leaves none.  A generator that is not on the curve raises
+        MsmError(EPOINT) with its ``index`` (msm377_ed_set_generators).  Independent of the G1 set."""
+        gens = bytes(gens) if gens else b""
+        if len(gens) % 64:
+            raise ValueError("an Edwards-BLS12 generator is 64 bytes")
+        rc = self._lib.msm377_ed_set_generators(self._ctx, gens or None, len(gens) // 64, int(window_bits))
+        self._check(rc, "msm377_ed_set_generators")
+
+    def ed_generators(self) -> Tuple[int, int]:
+        """(k, window width) of the resident Edwards-BLS12 generator set, (0, 0) without one (msm377_ed_ctx_get_generators)."""
+        k, c = ctypes.c_uint32(), ctypes.c_int()
+        self._check(self._lib.msm377_ed_ctx_get_generators(self._ctx, ctypes.addressof(k), ctypes.addressof(c)), "msm377_ed_ctx_get_generators")
+        return k.value, c.value
+
+    def ed_commit_rows_device(self, d_scalars: int, n: int, k: int, d_out: int, out_stride=None, base_stride: int = 32):
+        """n rows of k scalars in HBM over the first k generators of the resident Edwards-BLS12 set: n 64-byte wire records
+        at ``d_out`` (msm377_ed_commit_rows_device).  s_ij is at ``d_scalars + i * out_stride + j * base_stride``; the
+        default is row-major (``out_stride`` = 32 k)."""
+        if out_stride is None:
+            out_stride = 32 * k
+        rc = self._lib.msm377_ed_commit_rows_device(self._ctx, d_scalars or None, int(n), int(k), int(out_stride), int(base_stride), d_out or None)
+        self._check(rc, "msm377_ed_commit_rows_device")
+
+    def ed_commit_rows(self, scalars: bytes, k: int, layout="rows") -> bytes:
+        """The same on host buffers, ``scalars`` the dense k x n matrix in ``layout`` ("rows" or "columns"): returns the n
+        records (msm377_ed_commit_rows)."""
+        n, out_stride, base_stride = _rows_shape(k, scalars, layout)
+        out = ctypes.create_string_buffer(max(1, 64 * n))
+        rc = self._lib.msm377_ed_commit_rows(self._ctx, bytes(scalars), n, int(k), out_stride, base_stride, ctypes.addressof(out))
+        self._check(rc, "msm377_ed_commit_rows")
+        return out.raw[: 64 * n]
+
+    def ed_read_generator_table(self, index: int = 0, first: int = 0, count=None, info_only: bool = False):
+        """(MulTableInfo, records) of generator ``index`` of the resident Edwards-BLS12 set (msm377_ed_read_generator_table):
+        records as ed_read_mul_table's, the key zero.  MsmError(ESTATE) without a set or for an index beyond it."""
+        import numpy as np
+
+        fn = self._lib.msm377_ed_read_generator_table
+        raw = _MulTableInfoStruct()
+        self._check(fn(self._ctx, int(index), ctypes.addressof(raw), 0, 0, None), "msm377_ed_read_generator_table")
+        info = MulTableInfo(int(raw.width), int(raw.rows), int(raw.records), bytes(raw.key))
+        if info_only:
+            return info, None
+        count = info.records - int(first) if count is None else int(count)
+        words = np.empty((count, MUL_TABLE_RECORD_WORDS), dtype=np.uint32)
+        self._check(fn(self._ctx, int(index), None, int(first), count, words.ctypes.data if count else None), "msm377_ed_read_generator_table")
+        return info, words
 
     def ed_batch_mul(self, base: bytes, scalars: bytes) -> bytes:
         """out[i] = [s_i]B for one Edwards-BLS12 base: ed_batch_mul_multi with k = 1."""

@@ -187,4 +187,17 @@ const commit_rows = (scalars, k, { outForm = 'wire', layout = 'rows' } = {}) => 
   return addon.commitRowsSync(scalarsToBuffer(scalars), k, BATCH_MUL_FORMS[outForm], BATCH_MUL_LAYOUTS[layout]);
 };
 
-module.exports = { batch_lincomb2, batch_mul, batch_mul_multi, ed_batch_mul, ed_batch_mul_multi, ed_batch_mul_var, ed_batch_lincomb2, commit_rows, set_generators, batch_mul_var, compute_msm, compute_msm_edwards, set_bases, compute_msm_fixed_base, check_points, CHECK_CANONICAL, CHECK_CURVE, CHECK_SUBGROUP, CHECK_ALL, pointsToBuffer, scalarsToBuffer, version: addon.version };
+// Edwards-BLS12 row commitments (msm377_ed_set_generators / msm377_ed_commit_rows): out[i] = sum_j [s_ij]G_j over a RESIDENT
+// set of up to 4 096 Edwards-BLS12 generators (Pedersen and BHP-style hashes, vector commitments), independent of the G1 set.
+// ed_set_generators(gens, {windowBits}) builds and keeps the window tables -- `gens`: a Buffer of 64-byte wire records
+// x || y; windowBits 0 (= 8), 8, or 16 for up to 64 generators; an empty Buffer drops the set; a generator off the curve
+// throws, and the text names its index.  ed_commit_rows(scalars, k, {layout}) runs over the first k generators: `scalars`
+// the k x n matrix as one flat list or Buffer, layout 'rows' (default) or 'columns'.  Returns a Buffer of n 64-byte records;
+// the identity is (0, 1).
+const ed_set_generators = (gens, { windowBits = 0 } = {}) => addon.edSetGeneratorsSync(gens, windowBits);
+const ed_commit_rows = (scalars, k, { layout = 'rows' } = {}) => {
+  if (!(layout in BATCH_MUL_LAYOUTS)) throw new RangeError('layout: rows | columns');
+  return addon.edCommitRowsSync(scalarsToBuffer(scalars), k, BATCH_MUL_LAYOUTS[layout]);
+};
+
+module.exports = { batch_lincomb2, batch_mul, batch_mul_multi, ed_batch_mul, ed_batch_mul_multi, ed_batch_mul_var, ed_batch_lincomb2, ed_commit_rows, ed_set_generators, commit_rows, set_generators, batch_mul_var, compute_msm, compute_msm_edwards, set_bases, compute_msm_fixed_base, check_points, CHECK_CANONICAL, CHECK_CURVE, CHECK_SUBGROUP, CHECK_ALL, pointsToBuffer, scalarsToBuffer, version: addon.version };

@@ -292,3 +292,24 @@ export const commit_rows = (
   }
   return addon.commitRowsSync(scalarsToBuffer(scalars), k, BATCH_MUL_FORMS[outForm], BATCH_MUL_LAYOUTS[layout]);
 };
+
+// Edwards-BLS12 row commitments (msm377_ed_set_generators / msm377_ed_commit_rows): out[i] = sum_j [s_ij]G_j over a RESIDENT
+// set of up to 4 096 Edwards-BLS12 generators, independent of the G1 set.  ed_set_generators builds and keeps the window
+// tables (`gens`: a Buffer of 64-byte wire records; windowBits 0 = 8, 8, or 16 for up to 64 generators; an empty Buffer
+// drops the set; a generator off the curve throws, and the text names its index); ed_commit_rows runs over the first k
+// generators, `scalars` the k x n matrix as one flat list or Buffer in layout 'rows' (default) or 'columns', and returns n
+// 64-byte wire records (the identity is (0, 1)).
+export const ed_set_generators = (gens: Buffer, { windowBits = 0 }: { windowBits?: number } = {}): void => {
+  addon.edSetGeneratorsSync(gens, windowBits);
+};
+
+export const ed_commit_rows = (
+  scalars: bigint[] | Uint32Array[] | Buffer,
+  k: number,
+  { layout = 'rows' }: { layout?: keyof typeof BATCH_MUL_LAYOUTS } = {},
+): Buffer => {
+  if (!(layout in BATCH_MUL_LAYOUTS)) {
+    throw new RangeError('layout: rows | columns');
+  }
+  return addon.edCommitRowsSync(scalarsToBuffer(scalars), k, BATCH_MUL_LAYOUTS[layout]);
+};

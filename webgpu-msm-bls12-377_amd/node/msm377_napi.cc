@@ -40,6 +40,12 @@
 //                                                                      out[i] = sum_j [s_ij]G_j over the first k generators of
 //                                                                      the set (msm377_g1_commit_rows); the k x n scalars
 //                                                                      row-major, or column-major if columns != 0
+//   edSetGeneratorsSync(gens: Buffer 64k, windowBits: number): void     Edwards-BLS12 row commitments: build and keep the
+//                                                                      window tables of k generators (msm377_ed_set_generators);
+//                                                                      an empty Buffer drops the set
+//   edCommitRowsSync(scalars: Buffer 32kn, k: number, columns: number): Buffer 64n
+//                                                                      out[i] = sum_j [s_ij]G_j over the first k generators of
+//                                                                      that set (msm377_ed_commit_rows), 64-byte records x || y
 //   version(): string
 // Errors reject / throw a JS Error carrying msm377_strerror + msm377_last_error, matching the
 // reference's behaviour of throwing Error (cuzk/gpu.ts:7-10).
@@ -756,6 +762,78 @@ napi_value CommitRowsSync(napi_env env, napi_callback_info info) {
   return obj;
 }
 
+// edSetGeneratorsSync(gens, windowBits): the resident Edwards-BLS12 generator set of edCommitRowsSync; an empty Buffer drops
+// it.  A generator that is not on the curve throws, with the index in the text
+napi_value EdSetGeneratorsSync(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  bool gb = false;
+  int32_t bits = 0;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 2 || napi_is_buffer(env, argv[0], &gb) != napi_ok || !gb ||
+      napi_get_value_int32(env, argv[1], &bits) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "expected (gens: Buffer of 64 bytes per generator, windowBits: number)");
+    return nullptr;
+  }
+  uint8_t* g;
+  size_t gl;
+  napi_get_buffer_info(env, argv[0], reinterpret_cast<void**>(&g), &gl);
+  if (gl % 64 != 0 || gl / 64 > MSM377_GEN_MAX) {
+    napi_throw_range_error(env, nullptr, "gens must hold 0 to 4096 points of 64 bytes");
+    return nullptr;
+  }
+  std::string err;
+  std::lock_guard<std::mutex> lock(g_mu);
+  int rc = ensure_ctx(1, &err);  // any capacity: the set is an allocation of its own
+  if (!rc) {
+    rc = msm377_ed_set_generators(g_ctx, gl ? g : nullptr, static_cast<uint32_t>(gl / 64), bits);
+    if (rc) err = std::string("msm377_ed_set_generators: ") + msm377_strerror(rc) + ": " + msm377_last_error(g_ctx);
+  }
+  if (rc) napi_throw_error(env, nullptr, err.c_str());
+  return nullptr;
+}
+
+// edCommitRowsSync(scalars, k, columns) -> Buffer: out[i] = sum_j [s_ij]G_j over the first k generators of the resident
+// Edwards-BLS12 set; scalars: the dense k x n matrix, row-major (columns = 0) or column-major; n records of 64 bytes, the
+// identity as (0, 1)
+napi_value EdCommitRowsSync(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  bool sb = false;
+  uint32_t k = 0, columns = 0;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 3 || napi_is_buffer(env, argv[0], &sb) != napi_ok || !sb ||
+      napi_get_value_uint32(env, argv[1], &k) != napi_ok || napi_get_value_uint32(env, argv[2], &columns) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "expected (scalars: Buffer of 32 bytes per scalar, k: number, columns: number)");
+    return nullptr;
+  }
+  uint8_t* s;
+  size_t sl;
+  napi_get_buffer_info(env, argv[0], reinterpret_cast<void**>(&s), &sl);
+  if (k < 1 || k > MSM377_GEN_MAX || sl % (32 * static_cast<size_t>(k)) != 0) {
+    napi_throw_range_error(env, nullptr, "k is 1 to 4096, scalars 32 bytes per generator and output");
+    return nullptr;
+  }
+  const uint64_t n = sl / (32 * static_cast<size_t>(k));
+  const uint64_t out_stride = columns ? 32 : 32 * static_cast<uint64_t>(k), base_stride = columns ? 32 * (n ? n : 1) : 32;
+  napi_value points;
+  void* pd = nullptr;
+  if (napi_create_buffer(env, n * 64, &pd, &points) != napi_ok) return nullptr;
+  std::string err;
+  int rc;
+  {
+    std::lock_guard<std::mutex> lock(g_mu);
+    rc = ensure_ctx(1, &err);  // any capacity; without a set the call itself answers MSM377_ESTATE
+    if (!rc) {
+      rc = msm377_ed_commit_rows(g_ctx, s, n, k, out_stride, base_stride, static_cast<uint8_t*>(pd));
+      if (rc) err = std::string("msm377_ed_commit_rows: ") + msm377_strerror(rc) + ": " + msm377_last_error(g_ctx);
+    }
+  }
+  if (rc) {
+    napi_throw_error(env, nullptr, err.c_str());
+    return nullptr;
+  }
+  return points;
+}
+
 struct Job {
   napi_async_work work = nullptr;
   napi_deferred deferred = nullptr;
@@ -837,6 +915,8 @@ napi_value Init(napi_env env, napi_value exports) {
       {"edBatchLincomb2Sync", nullptr, EdBatchLincomb2Sync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"setGeneratorsSync", nullptr, SetGeneratorsSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"commitRowsSync", nullptr, CommitRowsSync, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"edSetGeneratorsSync", nullptr, EdSetGeneratorsSync, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"edCommitRowsSync", nullptr, EdCommitRowsSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"version", nullptr, Version, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
