@@ -481,6 +481,63 @@ typedef struct msm377_partials_info {
 } msm377_partials_info;
 int msm377_g1_read_partials(msm377_ctx* ctx, msm377_partials_info* info, uint32_t* words);
 
+/* ---- the accumulation work list (what the dominant kernel is handed, and the overflow partials of split rows) ----
+ *
+ * The accumulation stage cuts every bucket row into work items of at most `seg` entries (csrc/row_split.hpp), sorts
+ * them by length, longest first, across all window slots (k_work_hist / k_work_scatter), runs one thread or lane quad
+ * per item (k_accumulate / k_accumulate_quad: item 0 of a row writes the bucket, item s >= 1 the overflow record
+ * row_ovf_base[row] + s - 1) and adds the overflow records back (k_fold_long_rows for the long rows of the top slot of
+ * a short-scalar call, then k_merge_split_rows_quad).  msm377_g1_read_work_list describes and copies what the LAST PASS
+ * of the last call left of all that.  It answers exactly where msm377_g1_read_stage_ex answers (capture mode 1 or 2, a
+ * whole G1 or -- mode 2 -- Edwards-BLS12 call from window 0; after a rerun the pass that produced the result) and
+ * returns MSM377_ESTATE, writing nothing, everywhere else.  It STOPS ANSWERING (MSM377_ESTATE) once a later call has
+ * used the front of the work-list block as scratch -- msm377_g1_check_points*, msm377_ed_check_points*,
+ * msm377_scalars_width_device -- until the next describable MSM call: the counters are read where the kernels left
+ * them and are not copied aside under capture.  It waits for the context's stream first.  With capture off a call
+ * launches and allocates exactly what it did without the read-back.
+ *
+ * Written on the host beside the launches, from the values they were given:
+ *   seg             entries per work item (SEG) of the pass
+ *   rows            window slots x 2^L: row = slot 2^L + t is bucket t (key t + 1) of the slot
+ *   max_items       the bound the accumulation grid was sized for: rows + entries / seg
+ *   quad            1: k_accumulate_quad ran (a lane quad per item), 0: k_accumulate
+ *   fold_slot       the window slot k_fold_long_rows was launched on (the top one), -1: not launched
+ *   record_words    u32 words per overflow record as copied out: 52, or 36 for MSM377_STAGE_FORM_ED -- the layout of a
+ *                   bucket record of msm377_g1_read_stage_ex
+ *   form            MSM377_STAGE_FORM_* of the records
+ *   bucket_log      L
+ * Read from the device once the stream is idle:
+ *   items           work items in the list (what the accumulation kernel read as its count)
+ *   split_rows      rows of more than one item
+ *   overflow_slots  overflow records reserved: the sum of nseg - 1 over the split rows
+ *   hist[b]         work items of b entries, b = 0 .. 128 (rows without entries are items of length 0)
+ *
+ * Buffers, any of which may be NULL (call once with `info` alone to size them):
+ *   items_out         items x 2 u32: (row, seg) in list order, longest first
+ *   split_rows_out    split_rows u32: the rows of the split-row list, in the order the merge walks them
+ *   row_ovf_base_out  rows u32: the first overflow slot of a split row; bit 31 (the fold mark) set on the rows
+ *                     k_fold_long_rows added up into their first record.  Words of rows that are not split are
+ *                     UNSPECIFIED (nothing writes them)
+ *   ovf_out           ovf_count x record_words u32: overflow records [ovf_first, ovf_first + ovf_count), which must lie
+ *                     inside [0, overflow_slots) (MSM377_EINVAL otherwise).  The records of a row with the fold mark
+ *                     hold the fold's intermediate sums; its first record is the sum of all its partials */
+#define MSM377_WORK_HIST_BINS 129
+#define MSM377_WORK_ROW_FOLDED 0x80000000u
+typedef struct msm377_work_list_info {
+  uint32_t seg, rows;
+  uint64_t max_items;
+  uint32_t quad;
+  int32_t fold_slot;
+  uint32_t record_words;
+  int32_t form;
+  uint32_t bucket_log;
+  uint32_t items, split_rows, overflow_slots;
+  uint32_t hist[MSM377_WORK_HIST_BINS];
+  uint32_t reserved;
+} msm377_work_list_info;
+int msm377_g1_read_work_list(msm377_ctx* ctx, msm377_work_list_info* info, uint32_t* items_out, uint32_t* split_rows_out, uint32_t* row_ovf_base_out, uint64_t ovf_first,
+                             uint64_t ovf_count, uint32_t* ovf_out);
+
 /* ---- base records and window tables (what the hot kernels gather from) ----
  *
  * msm377_g1_read_bases describes and copies the base records the LAST CONVERSION of this context left: any G1 or

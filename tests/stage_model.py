@@ -268,6 +268,73 @@ def key_max_word(stored: np.ndarray, bias: int, key_unsigned: bool) -> int:
     return int(key.max(initial=0)) | KEY_TRACKED | (KEY_UNSIGNED if key_unsigned else 0)
 
 
+# ---- the accumulation work list (msm377_g1_read_work_list) ----
+# Written from the comments of csrc/kernels/accumulate.hpp and the contract in include/msm377.h: a row of more than SEG
+# entries is cut into the fewest equal parts of at most SEG entries.  ceil() is spelled -(-a // b) here, not as the
+# kernel spells it.
+SEG_BINS = 129            # work items are counted by length 0 .. 128
+LONG_ROW_PARTIALS = 32    # k_fold_long_rows folds the rows of its slot with MORE work items than this
+
+
+class RowSplit(NamedTuple):
+    nseg: int
+    seglen: int
+    lastlen: int
+
+
+def row_split(length: int, seg: int) -> RowSplit:
+    """(work items, entries per item, entries of the last item) of a row: one item up to `seg` entries (also for an empty
+    row: an item of length 0); beyond that parts = ceil(len / seg) equal parts of ceil(len / parts) entries -- as many
+    of those as the row fills, the last one holding the rest."""
+    if length <= seg:
+        return RowSplit(1, length, length)
+    parts = -(-length // seg)
+    seglen = -(-length // parts)
+    nseg = -(-length // seglen)
+    return RowSplit(nseg, seglen, length - (nseg - 1) * seglen)
+
+
+def item_range(length: int, seg: int, s: int):
+    """Entries [lo, hi) of a row of `length` entries that its work item s adds."""
+    sp = row_split(length, seg)
+    assert 0 <= s < sp.nseg
+    return s * sp.seglen, min((s + 1) * sp.seglen, length)
+
+
+class WorkList(NamedTuple):
+    hist: List[int]            # hist[b]: work items of b entries
+    items: int                 # work items in all
+    split_rows: List[int]      # rows of more than one item, ascending
+    overflow_slots: int        # sum of nseg - 1 over the split rows
+    item_set: np.ndarray       # the set of (row, seg, entries) items: an (items, 3) int64 array sorted by (row, seg)
+    folded: List[int]          # rows of the fold slot with more than LONG_ROW_PARTIALS items (empty without a fold slot)
+
+
+def work_list(row_lens, seg: int, fold_slot: int = -1, bucket_log: int = 15) -> WorkList:
+    """The work list of a pass from the lengths of its rows (row = slot 2^L + t, in that order).  fold_slot: the window
+    slot k_fold_long_rows is launched on, -1: none.  (Rows of one item -- nearly all of half a million -- are listed
+    with NumPy, the split rows one by one.)"""
+    lens = np.asarray(row_lens, dtype=np.int64)
+    one = np.nonzero(lens <= seg)[0]
+    items = [np.stack([one, np.zeros_like(one), lens[one]], axis=1)]
+    split, folded, ovf = [], [], 0
+    for row in np.nonzero(lens > seg)[0]:
+        row, length = int(row), int(lens[row])
+        sp = row_split(length, seg)
+        assert sp.nseg > 1
+        ranges = [item_range(length, seg, s) for s in range(sp.nseg)]
+        items.append(np.array([(row, s, hi - lo) for s, (lo, hi) in enumerate(ranges)], dtype=np.int64))
+        split.append(row)
+        ovf += sp.nseg - 1
+        if fold_slot >= 0 and row >> bucket_log == fold_slot and sp.nseg > LONG_ROW_PARTIALS:
+            folded.append(row)
+    item_set = np.concatenate(items)
+    item_set = item_set[np.lexsort((item_set[:, 1], item_set[:, 0]))]
+    hist = [int(x) for x in np.bincount(item_set[:, 2], minlength=SEG_BINS)]
+    assert len(hist) == SEG_BINS, "a work item of more than 128 entries"
+    return WorkList(hist, len(item_set), split, ovf, item_set, folded)
+
+
 _FQ = None
 
 

@@ -22,7 +22,7 @@ def test_header_declares_the_boundary():
     names = declared_functions()
     for must in ("msm377_g1_msm", "msm377_g1_msm_device", "msm377_ctx_create", "msm377_ctx_destroy", "msm377_g1_combine_partials",
                  "msm377_g1_read_stage_ex", "msm377_g1_read_bases", "msm377_g1_read_mul_table", "msm377_g1_read_partials",
-                 "msm377_read_walk_stash", "msm377_g1_read_walk_tables"):
+                 "msm377_read_walk_stash", "msm377_g1_read_walk_tables", "msm377_g1_read_work_list"):
         assert must in names
 
 

@@ -559,3 +559,94 @@ def test_the_ladder_meets_where_it_promises(name, g, ed, fold):
                             assert model[rec][0] == M.group(ed)[0](case.points[0], case.points[0])
             if not single:
                 assert sorted(done_all) == levels, (name, kind, age)
+
+
+# ---- the accumulation work list: row_split of the product against the model, the model on hand-worked rows ----
+import os  # noqa: E402
+import subprocess  # noqa: E402
+
+import work_list_cases as W  # noqa: E402
+
+ROW_SPLIT_SRC = os.path.join(util.ROOT, "tests", "native", "row_split_shim.cpp")
+ROW_SPLIT_SO = os.path.join(util.ROOT, "tests", "native", "_build", "librow_split_shim.so")
+
+
+@pytest.fixture(scope="module")
+def row_split_shim():
+    csrc = os.path.join(util.ROOT, "webgpu-msm-bls12-377_amd", "csrc")
+    deps = [ROW_SPLIT_SRC, os.path.join(csrc, "row_split.hpp")]
+    if not os.path.exists(ROW_SPLIT_SO) or any(os.path.getmtime(d) > os.path.getmtime(ROW_SPLIT_SO) for d in deps):
+        os.makedirs(os.path.dirname(ROW_SPLIT_SO), exist_ok=True)
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Werror", "-I", csrc, "-o", ROW_SPLIT_SO, ROW_SPLIT_SRC])
+    return ctypes.CDLL(ROW_SPLIT_SO)
+
+
+def test_row_split_of_the_product_is_the_models_and_keeps_its_contract(row_split_shim):
+    """csrc/row_split.hpp (the function every accumulation kernel cuts its rows with, compiled for the host) against
+    stage_model.row_split for every SEG in 8..128 and every length in 0..34 SEG + 8, and the contract of a split."""
+    for seg in range(8, 129):
+        count = 34 * seg + 9
+        out = (ctypes.c_uint32 * (3 * count))()
+        row_split_shim.row_split_table(ctypes.c_uint32(seg), ctypes.c_uint32(0), ctypes.c_uint32(count), out)
+        got = np.frombuffer(out, dtype=np.uint32).reshape(count, 3)
+        for length in range(count):
+            nseg, seglen, lastlen = (int(x) for x in got[length])
+            assert (nseg, seglen, lastlen) == tuple(M.row_split(length, seg)), (seg, length)
+            if length == 0:
+                assert (nseg, seglen, lastlen) == (1, 0, 0)
+                continue
+            assert seglen <= seg and 1 <= lastlen <= seglen, (seg, length)
+            assert (nseg - 1) * seglen + lastlen == length, (seg, length)
+            assert nseg <= -(-length // seg), (seg, length)
+            assert (nseg == 1) == (length <= seg), (seg, length)
+
+
+def test_work_list_model_on_hand_worked_rows():
+    """Rows of 0, 1, SEG, SEG + 1, 2 SEG + 1, 32 SEG and 32 SEG + 1 entries at SEG = 24, worked by hand."""
+    seg = 24
+    assert M.row_split(0, seg) == (1, 0, 0) and M.row_split(1, seg) == (1, 1, 1) and M.row_split(24, seg) == (1, 24, 24)
+    assert M.row_split(25, seg) == (2, 13, 12)      # two parts: 13 + 12
+    assert M.row_split(49, seg) == (3, 17, 15)      # three parts: 17 + 17 + 15
+    assert M.row_split(768, seg) == (32, 24, 24)    # 32 full parts
+    assert M.row_split(769, seg) == (33, 24, 1)     # 33 parts of ceil(769 / 33) = 24: 32 x 24 + 1
+    assert M.item_range(49, seg, 2) == (34, 49) and M.item_range(769, seg, 32) == (768, 769)
+    lens = [0, 1, 24, 25, 49, 768, 769]
+    # two slots of 2^3 rows; the same lengths in both, the second slot is the fold slot
+    L = 3
+    rows = lens + [0] + lens + [0]
+    wl = M.work_list(rows, seg, fold_slot=1, bucket_log=L)
+    hist = [0] * M.SEG_BINS
+    for b, c in ((0, 2), (1, 1 + 1), (24, 1 + 32 + 32), (13, 1), (12, 1), (17, 2), (15, 1)):
+        hist[b] += 2 * c
+    assert wl.hist == hist
+    assert wl.items == 2 * (2 + 1 + 1 + 2 + 3 + 32 + 33) == sum(hist)
+    assert wl.split_rows == [3, 4, 5, 6, 11, 12, 13, 14]
+    assert wl.overflow_slots == 2 * (1 + 2 + 31 + 32)
+    assert wl.folded == [14]  # 33 items: more than 32, in the fold slot; the 32-item row 13 is not, nor is row 6 of slot 0
+    assert M.work_list(rows, seg, bucket_log=L).folded == []
+    assert wl.item_set.shape == (wl.items, 3)
+    as_set = {tuple(int(x) for x in it) for it in wl.item_set}
+    assert len(as_set) == wl.items
+    assert {(0, 0, 0), (1, 0, 1), (3, 0, 13), (3, 1, 12), (4, 2, 15), (6, 32, 1), (14, 31, 24), (15, 0, 0)} <= as_set
+    assert (6, 33, 1) not in as_set and (5, 32, 0) not in as_set
+
+
+@pytest.mark.parametrize("S", [16, 24, 64, 120, 128])
+def test_work_list_cases_hold_what_they_promise(S):
+    """The skewed inputs of tests/test_work_list_gpu.py in every geometry they are run in: every slot holds rows of exactly
+    the case's lengths, among them rows of 32 and of 33 work items; three histogram bins above 16 are occupied."""
+    geoms = [M.even16()] if S not in (24, 64) else [M.even16(), M.equal16(), M.short(72, 15)] + ([M.glv8(), M.wide13(), M.narrow22()] if S == 64 else [])
+    for g in geoms + ([M.equal16()] if S == 128 else []):
+        case = W.skewed(g, S, bound=(1 << 72) if g.name == "short" else R.R_ORDER)
+        assert len(case.scalars) == len(case.other) == 138 * S + 8 and sorted(case.scalars) != sorted(case.other)
+        cols, flags = M.digit_matrix(case.scalars, g)
+        assert flags == 0 and M.digit_matrix(case.other, g)[1] == 0
+        lens = W.row_lengths(g, cols)
+        slots = 1 if g.name == "wide13" else len(g.slots)
+        assert len(lens) == slots << g.bucket_log
+        wl = M.work_list(lens, S, fold_slot=slots - 1 if g.name == "short" else -1, bucket_log=g.bucket_log)
+        W.check_promises(case, lens, wl, range(slots))
+        per = {"glv8": 2, "wide13": 13}.get(g.name, 1)
+        assert len(wl.split_rows) == 8 * per * slots  # the rows longer than S: eight of the eleven lengths
+        if g.name == "short":
+            assert len(wl.folded) == 2  # 32 S + 1 and 33 S + 5 in the top slot: 33 and 34 items; 31 S + 1 and 32 S (32 items) stay

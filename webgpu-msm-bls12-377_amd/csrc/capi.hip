@@ -218,6 +218,54 @@ int msm377_g1_read_partials(msm377_ctx* ctx, msm377_partials_info* info, uint32_
   return MSM377_OK;
 }
 
+// The accumulation work list of the last pass: the host's half of `info` and the pointers are those enqueue_accumulate
+// wrote down beside its launches (WorkListLayout); the counters are read where the kernels left them.
+int msm377_g1_read_work_list(msm377_ctx* ctx, msm377_work_list_info* info, uint32_t* items_out, uint32_t* split_rows_out, uint32_t* row_ovf_base_out, uint64_t ovf_first,
+                             uint64_t ovf_count, uint32_t* ovf_out) {
+  if (!ctx) return MSM377_EINVAL;
+  const WorkListLayout& wl = ctx->last.work;
+  if (!ctx->capture || !ctx->last.stage.valid || !ctx->d_buckets_snap || !wl.valid) {
+    ctx->err = "no captured work list: stage capture is off, the last call is not one the capture mode describes, or a check call has used the work-list counters since";
+    return MSM377_ESTATE;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  msm377_work_list_info out = wl.info;
+  static_assert(MSM377_WORK_HIST_BINS == SEG_BINS, "the histogram of the ABI is the kernels'");
+  uint32_t counters[2] = {};
+  HIP_TRY(ctx, hipMemcpy(out.hist, wl.d_hist, sizeof out.hist, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(&out.items, wl.d_total, 4, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(counters, wl.d_counters, sizeof counters, hipMemcpyDeviceToHost));
+  out.split_rows = counters[0], out.overflow_slots = counters[1];
+  // what the kernels counted must fit what the launches were sized for before anything is copied by those counts
+  if (out.items > out.max_items || out.split_rows > out.rows || out.overflow_slots > out.max_items - out.rows) {
+    ctx->err = "the work-list counters exceed the bounds of their launches";
+    return MSM377_ESTATE;
+  }
+  if (ovf_out && (ovf_first > out.overflow_slots || ovf_count > out.overflow_slots - ovf_first)) {
+    ctx->err = "record range outside the overflow records";
+    return MSM377_EINVAL;
+  }
+  if (info) *info = out;
+  if (items_out && out.items) HIP_TRY(ctx, hipMemcpy(items_out, ctx->d_work, (size_t)out.items * sizeof(WorkItem), hipMemcpyDeviceToHost));
+  if (split_rows_out && out.split_rows) HIP_TRY(ctx, hipMemcpy(split_rows_out, ctx->d_split_rows, (size_t)out.split_rows * 4, hipMemcpyDeviceToHost));
+  if (row_ovf_base_out) HIP_TRY(ctx, hipMemcpy(row_ovf_base_out, ctx->d_row_ovf_base, (size_t)out.rows * 4, hipMemcpyDeviceToHost));
+  if (ovf_out && ovf_count) {
+    // records as the pass stored them (four coordinate slots of coord_words words) -> 4 x limbs packed words, as msm377_g1_read_stage_ex packs a bucket
+    const size_t cw = wl.coord_words, nl = wl.limbs, bw = wl.bkt_words;
+    uint32_t* tmp = (uint32_t*)malloc((size_t)ovf_count * bw * 4);
+    if (!tmp) return MSM377_ENOMEM;
+    hipError_t e = hipMemcpy(tmp, ctx->d_ovf + (size_t)ovf_first * bw, (size_t)ovf_count * bw * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess)
+      for (size_t t = 0; t < ovf_count; t++)
+        for (size_t c = 0; c < 4; c++)
+          for (size_t j = 0; j < nl; j++) ovf_out[(t * 4 + c) * nl + j] = tmp[t * bw + c * cw + j];
+    free(tmp);
+    HIP_TRY(ctx, e);
+  }
+  return MSM377_OK;
+}
+
 // The base records of the last conversion: layout and pointer are those note_bases (sequencer.hip) wrote down beside the
 // launch; this is a copy.
 int msm377_g1_read_bases(msm377_ctx* ctx, msm377_bases_info* info, uint64_t first, uint64_t count, uint32_t* words) {

@@ -162,6 +162,16 @@ struct StageLayout {
   const uint32_t* d_partials = nullptr;  // what k_gather_partials wrote to (slot 0 of ctx->d_partials for every call the capture modes describe)
 };
 
+// What the last enqueue_accumulate launched with, for msm377_g1_read_work_list: written beside its launches (sequencer.hip)
+// under stage capture, from the LaunchRecord they were given.  valid: from there until something else writes the front of
+// d_work_meta (the check calls, msm377_scalars_width_device: they clear it); the read-back also asks for StageLayout::valid.
+struct WorkListLayout {
+  bool valid = false;
+  msm377_work_list_info info = {};      // the host's half; items, the counters and the histogram are read from the device
+  uint32_t bkt_words = 64, coord_words = 16, limbs = 13;  // an overflow record: the bucket record of the pass
+  const uint32_t *d_hist = nullptr, *d_total = nullptr, *d_counters = nullptr;  // LaunchRecord::work_hist / total / counters
+};
+
 // What the last base conversion left, for msm377_g1_read_bases: written on the host where the conversion is queued
 // (sequencer.hip note_bases), never derived afterwards.  valid: the call that queued it came back MSM377_OK.
 struct BasesLayout {
@@ -238,6 +248,7 @@ struct LastCall {
   int products = 0;        // field products per bucket addition of the last accumulation launch (bench.py's int32-mad roof)
   double stage_ms[MSM377_NUM_STAGES] = {};
   StageLayout stage;  // what the last enqueue_decompose launched with; valid is enqueue_windows' (msm377_g1_read_stage_ex)
+  WorkListLayout work;  // what the last enqueue_accumulate launched with (msm377_g1_read_work_list)
   BasesLayout bases;  // what the last base conversion wrote (msm377_g1_read_bases)
   WalkLayout walk;    // what the last batch call's last pass left in the stash (msm377_read_walk_stash)
 };

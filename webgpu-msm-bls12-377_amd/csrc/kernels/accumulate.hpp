@@ -3,6 +3,7 @@
 // Device code; included by sequencer.hip only.
 #pragma once
 #include "../curves.hpp"
+#include "../row_split.hpp"
 #include "reduce.hpp"  // quad_bcast, sel4, add_quad, coord4
 
 namespace msm377 {
@@ -31,24 +32,8 @@ __device__ __forceinline__ uint32_t row_len(const uint32_t* __restrict__ row_ptr
   return row_ptr[at + 1] - row_ptr[at];
 }
 
-// A row of `len` entries becomes `nseg` work items of `seglen` entries (the last one `lastlen`): equal parts of at
-// most SEG entries, so a row just over a multiple of SEG does not leave one full-length chain beside a stub.
-struct RowSplit {
-  uint32_t nseg, seglen, lastlen;
-};
-__device__ __forceinline__ RowSplit row_split(uint32_t len, uint32_t SEG) {
-  RowSplit r;
-  if (len <= SEG) {
-    r.nseg = 1;
-    r.seglen = r.lastlen = len;
-    return r;
-  }
-  const uint32_t parts = (len + SEG - 1) / SEG;
-  r.seglen = (len + parts - 1) / parts;
-  r.nseg = (len + r.seglen - 1) / r.seglen;  // <= parts
-  r.lastlen = len - (r.nseg - 1) * r.seglen;  // 1..seglen
-  return r;
-}
+// RowSplit / row_split (row_split.hpp, a host-and-device function): a row of `len` entries becomes `nseg` work items of
+// `seglen` entries, the last one `lastlen`.
 
 // Thread per row, 1024 rows per block: length histogram of its work items (LDS, then one global
 // atomic per bin and block -- the ~60 hot counters serialise, hence the large blocks); rows with more than one item reserve overflow slots and join the split-row list.

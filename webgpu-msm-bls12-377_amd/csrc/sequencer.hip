@@ -611,15 +611,27 @@ int enqueue_accumulate(msm377_ctx* ctx, const LaunchRecord& k) {
   launch_accumulate<CV, BP>(ctx, k);
   HIP_TRY(ctx, hipGetLastError());
   ctx->zc.acc_seq++;
+  int32_t fold_slot = -1;  // the slot k_fold_long_rows is launched on (msm377_g1_read_work_list)
   if (k.is_short) {  // the top window of a short call: few rows, thousands of partials each -- folded before the merge
     hipLaunchKernelGGL(k_fold_long_rows<CV>, dim3(FOLD_BLOCKS), dim3(FOLD_THREADS), 0, st, ctx->d_row_ptr, ctx->d_row_ovf_base, ctx->d_ovf, k.SEG, k.d_err, k.L, k.slots - 1);
     HIP_TRY(ctx, hipGetLastError());
+    fold_slot = (int32_t)(k.slots - 1);
   }
   // (grid-stride over the split-row list: with the even windows few rows split, and 8192 workgroups that only read the
   // count cost 11 us at 2^20)
   hipLaunchKernelGGL(k_merge_split_rows_quad<CV>, dim3(std::min<uint32_t>((k.rows + 63) / 64, 1024u)), dim3(256), 0, st, ctx->d_row_ptr, ctx->d_buckets, k.counters,
                      ctx->d_split_rows, ctx->d_row_ovf_base, ctx->d_ovf, k.SEG, k.d_err, k.L, ctx->zc.dm_flag + ACC_FLAG_WORD, ctx->zc.acc_seq);
   HIP_TRY(ctx, hipGetLastError());
+  if (ctx->capture) {  // the work list of the pass (msm377_g1_read_work_list), from the arguments of the launches above
+    WorkListLayout& wl = ctx->last.work;
+    msm377_work_list_info& wi = wl.info = msm377_work_list_info{};
+    wi.seg = k.SEG, wi.rows = k.rows, wi.max_items = k.max_items, wi.quad = k.quad_acc ? 1u : 0u;
+    wi.fold_slot = fold_slot;
+    wi.record_words = 4 * k.cv.limbs, wi.form = k.cv.form, wi.bucket_log = k.L;
+    wl.bkt_words = k.cv.bkt_words, wl.coord_words = k.cv.coord_words, wl.limbs = k.cv.limbs;
+    wl.d_hist = k.work_hist, wl.d_total = k.total, wl.d_counters = k.counters;
+    wl.valid = true;
+  }
   return MSM377_OK;
 }
 
@@ -1072,6 +1084,7 @@ int check_points_device(msm377_ctx* ctx, const void* d_points, uint64_t n, uint3
   if (n == 0) return MSM377_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   uint32_t* scratch = ctx->d_work_meta;
+  ctx->last.work.valid = false;  // msm377_g1_read_work_list reads its counters from these words
   static_assert(CHK_WORDS <= META_BLOCK_WORDS, "the check's counters fit the work-list block");
   uint32_t* list = (flags & MSM377_CHECK_SUBGROUP) ? ctx->d_val_idx : nullptr;  // cap entries at least (capi.hip: wcap >= 16 cap)
   const dim3 grid((unsigned)((n + CHK_THREADS - 1) / CHK_THREADS));
@@ -1433,6 +1446,7 @@ int scalars_width_device(msm377_ctx* ctx, const void* d_scalars, uint64_t n, uin
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   // the result word: the front of the work-list block, which every MSM clears for itself and no resident form reads
   uint32_t* d_out = ctx->d_work_meta;
+  ctx->last.work.valid = false;  // msm377_g1_read_work_list reads its histogram from these words
   const uint64_t nwords = n * (sbytes / 4);
   const unsigned blocks = (unsigned)std::min<uint64_t>((nwords / 4 + 255) / 256 + 1, 2048);
   hipLaunchKernelGGL(k_clear_words, dim3(1), dim3(256), 0, ctx->stream, d_out, 1u, (uint32_t*)nullptr, 0u);

@@ -117,6 +117,45 @@ class PartialsInfo(NamedTuple):
 
 
 TAIL_TE, TAIL_XYZZ, TAIL_ED = 0, 1, 2  # PartialsInfo.tail_kind
+
+WORK_HIST_BINS = 129           # MSM377_WORK_HIST_BINS
+WORK_ROW_FOLDED = 0x80000000   # MSM377_WORK_ROW_FOLDED: the fold mark in a word of row_ovf_base
+
+
+class _WorkListInfoStruct(ctypes.Structure):  # msm377_work_list_info
+    _fields_ = [
+        ("seg", ctypes.c_uint32),
+        ("rows", ctypes.c_uint32),
+        ("max_items", ctypes.c_uint64),
+        ("quad", ctypes.c_uint32),
+        ("fold_slot", ctypes.c_int32),
+        ("record_words", ctypes.c_uint32),
+        ("form", ctypes.c_int32),
+        ("bucket_log", ctypes.c_uint32),
+        ("items", ctypes.c_uint32),
+        ("split_rows", ctypes.c_uint32),
+        ("overflow_slots", ctypes.c_uint32),
+        ("hist", ctypes.c_uint32 * WORK_HIST_BINS),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
+class WorkListInfo(NamedTuple):
+    """msm377_work_list_info: the accumulation work list of the last call's last pass (include/msm377.h); ``hist[b]`` is
+    the number of work items of b entries."""
+
+    seg: int
+    rows: int
+    max_items: int
+    quad: int
+    fold_slot: int
+    record_words: int
+    form: int
+    bucket_log: int
+    items: int
+    split_rows: int
+    overflow_slots: int
+    hist: Tuple[int, ...]
 BASES_TE_PROJECTIVE, BASES_TE_AFFINE, BASES_WEIERSTRASS, BASES_ED = 0, 1, 2, 3  # MSM377_BASES_*: BasesInfo.form
 MUL_TABLE_SINGLE, MUL_TABLE_MULTI, MUL_TABLE_GENERATOR = 0, 1, 2  # MSM377_MUL_TABLE_*
 _MUL_TABLES = {"single": MUL_TABLE_SINGLE, "multi": MUL_TABLE_MULTI, "generator": MUL_TABLE_GENERATOR}
@@ -316,6 +355,7 @@ def load_library():
         "msm377_g1_read_stage_ex": (i32, [vp, u32, vp, vp, vp, vp, vp]),
         "msm377_g1_read_bases": (i32, [vp, vp, u64, u64, vp]),
         "msm377_g1_read_partials": (i32, [vp, vp, vp]),
+        "msm377_g1_read_work_list": (i32, [vp, vp, vp, vp, vp, u64, u64, vp]),
         "msm377_g1_read_mul_table": (i32, [vp, u32, u32, vp, u64, u64, vp]),
         "msm377_read_walk_stash": (i32, [vp, vp, u32, u64, u64, vp, vp]),
         "msm377_g1_read_walk_tables": (i32, [vp, vp, u32, u64, u64, vp]),
@@ -1403,6 +1443,32 @@ class MsmEngine:
         words = np.empty((info.records, info.points, 4, info.coord_words), dtype=np.uint32)
         self._check(self._lib.msm377_g1_read_partials(self._ctx, None, words.ctypes.data), "msm377_g1_read_partials")
         return info, words
+
+    def read_work_list(self, want=("items", "split_rows", "row_ovf_base"), ovf_first: int = 0, ovf_count: int = 0):
+        """(WorkListInfo, dict of numpy arrays) of the accumulation work list the last call's last pass left
+        (msm377_g1_read_work_list): ``items`` (info.items, 2) u32 (row, seg) in list order, ``split_rows``
+        (info.split_rows,), ``row_ovf_base`` (info.rows,) with WORK_ROW_FOLDED on folded rows, and -- with ``ovf_count``
+        -- ``ovf``: overflow records [ovf_first, ovf_first + ovf_count) of info.record_words words in the layout of a
+        bucket of read_stage_ex.  MsmError(ESTATE) wherever read_stage_ex refuses, and after a check call."""
+        import numpy as np
+
+        raw = _WorkListInfoStruct()
+        self._check(self._lib.msm377_g1_read_work_list(self._ctx, ctypes.addressof(raw), None, None, None, 0, 0, None), "msm377_g1_read_work_list")
+        info = WorkListInfo(*(int(getattr(raw, f)) for f in WorkListInfo._fields[:-1]), tuple(raw.hist))
+        bufs = {
+            "items": np.empty((info.items, 2), dtype=np.uint32),
+            "split_rows": np.empty(info.split_rows, dtype=np.uint32),
+            "row_ovf_base": np.empty(info.rows, dtype=np.uint32),
+        }
+        res = {k: v for k, v in bufs.items() if k in want}
+        ovf = np.empty((int(ovf_count), info.record_words), dtype=np.uint32) if ovf_count else None
+        if res or ovf is not None:
+            ptr = [res[k].ctypes.data if k in res and res[k].size else None for k in ("items", "split_rows", "row_ovf_base")]
+            self._check(self._lib.msm377_g1_read_work_list(self._ctx, None, *ptr, int(ovf_first), int(ovf_count), ovf.ctypes.data if ovf is not None else None),
+                        "msm377_g1_read_work_list")
+        if ovf is not None:
+            res["ovf"] = ovf
+        return info, res
 
     def read_stage(self, slot: int, n: int, want=("digits", "row_ptr", "val_idx", "buckets")):
         """Returns a dict of numpy arrays for window slot ``slot`` of the last call."""
