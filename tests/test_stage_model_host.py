@@ -650,3 +650,77 @@ def test_work_list_cases_hold_what_they_promise(S):
         assert len(wl.split_rows) == 8 * per * slots  # the rows longer than S: eight of the eleven lengths
         if g.name == "short":
             assert len(wl.folded) == 2  # 32 S + 1 and 33 S + 5 in the top slot: 33 and 34 items; 31 S + 1 and 32 S (32 items) stay
+
+
+# ---- the GLV front end: csrc/glv_split.hpp (the arithmetic of k_decompose_glv, compiled for the host) against the model ----
+import glv_cases as GC  # noqa: E402
+
+GLV_SPLIT_SRC = os.path.join(util.ROOT, "tests", "native", "glv_split_shim.cpp")
+GLV_SPLIT_SO = os.path.join(util.ROOT, "tests", "native", "_build", "libglv_split_shim.so")
+
+
+@pytest.fixture(scope="module")
+def glv_split_shim():
+    csrc = os.path.join(util.ROOT, "webgpu-msm-bls12-377_amd", "csrc")
+    deps = [GLV_SPLIT_SRC, os.path.join(csrc, "glv_split.hpp"), os.path.join(csrc, "consts_gen.hpp")]
+    if not os.path.exists(GLV_SPLIT_SO) or any(os.path.getmtime(d) > os.path.getmtime(GLV_SPLIT_SO) for d in deps):
+        os.makedirs(os.path.dirname(GLV_SPLIT_SO), exist_ok=True)
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Werror", "-Wno-unknown-pragmas", "-I", csrc, "-o", GLV_SPLIT_SO, GLV_SPLIT_SRC])
+    return ctypes.CDLL(GLV_SPLIT_SO)
+
+
+def glv_split_table(lib, ks):
+    """(rem0, k1, k2, digits, bad, corrected) per scalar, as the product's arithmetic computes them."""
+    n = len(ks)
+    words = np.frombuffer(b"".join(k.to_bytes(32, "little") for k in ks), dtype=np.uint32)
+    rem0, k1, k2 = (np.zeros(5 * n, dtype=np.uint32) for _ in range(3))
+    digits, bad, corrected = np.zeros(16 * n, dtype=np.uint16), np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+    ptr = lambda a: ctypes.c_void_p(a.ctypes.data)  # noqa: E731
+    lib.glv_split_table(ptr(words), ctypes.c_uint64(n), ptr(rem0), ptr(k1), ptr(k2), ptr(digits), ptr(bad), ptr(corrected))
+    def ints(a):
+        raw = a.tobytes()
+        return [int.from_bytes(raw[20 * i : 20 * i + 20], "little") for i in range(n)]
+
+    return ints(rem0), ints(k1), ints(k2), digits.reshape(n, 16).tolist(), bad.tolist(), corrected.tolist()
+
+
+def test_glv_split_of_the_product_is_divmod_and_the_models_digits(glv_split_shim):
+    """csrc/glv_split.hpp -- Barrett quotient, its one correction, the digit chains of both halves -- against Python's
+    divmod and stage_model.recode(k, glv8()): k1, k2, the sixteen stored digits, the range flag, and WHETHER THE CORRECTION
+    WAS TAKEN: for every k = m lambda with m >= 1 and for no other input (so the test cannot pass without reaching the
+    arm); the remainder before it is below 2 lambda, as the kernel's comment says.  Inputs: m lambda + t, t in -2 .. 2,
+    for the factors of glv_cases.lambda_factors (10^5 random ones); 10^6 random k below 2^256 and 10^5 below r; every
+    boundary word in every window of k2 and of k1; the edge of the range."""
+    lam, g = GC.LAM, M.glv8()
+    rnd = GC.rng("host")
+    groups = {
+        "multiples": GC.around_multiples(GC.lambda_factors(rnd, 100000)),
+        "random256": [rnd.getrandbits(256) for _ in range(1000000)],
+        "random_r": [rnd.randrange(r) for _ in range(100000)],
+        "boundaries": GC.boundary_halves(rnd, 25),
+        "edge": [GC.EDGE - 1, GC.EDGE, GC.BEYOND, GC.BEYOND + 1, GC.EDGE_CARRIED, GC.EDGE_CARRIED + 1, (1 << 256) - 1],
+    }
+    taken = {}
+    for name, ks in groups.items():
+        rem0, k1, k2, digits, bad, corrected = glv_split_table(glv_split_shim, ks)
+        flagged = 0
+        for i, k in enumerate(ks):
+            q, t = divmod(k, lam)
+            rec = M.recode(k, g)
+            assert (k1[i], k2[i]) == (t, q), (name, hex(k))
+            assert digits[i] == rec.stored, (name, hex(k))
+            assert bool(bad[i]) == bool(rec.flags & M.ERR_GLV_RANGE) and rec.flags & ~M.ERR_GLV_RANGE == 0, (name, hex(k))
+            assert bool(corrected[i]) == (t == 0 and q >= 1), (name, hex(k), "the correction arm")
+            assert rem0[i] < 2 * lam and rem0[i] == t + lam * corrected[i], (name, hex(k))
+            flagged += bad[i]
+        taken[name] = (sum(corrected), len(ks), flagged)
+    print("correction arm taken / inputs / out of range:", taken)
+    assert taken["multiples"][0] == sum(k % lam == 0 and k > 0 for k in groups["multiples"]) > 100000
+    assert taken["random256"][0] == taken["random_r"][0] == 0  # no random scalar reaches it
+    assert taken["edge"][0] == 2  # BEYOND = lambda (HALF_MAX + 1) and EDGE_CARRIED + 1 = lambda (HALF_MAX_CARRIED + 1)
+    assert taken["boundaries"][2] > 0 and taken["random_r"][2] == 0 and taken["random256"][2] > 0
+    # the edge of the range, from the model: EDGE is the largest scalar without the flag
+    assert M.recode(GC.EDGE, g).flags == 0 and M.recode(GC.EDGE_CARRIED, g).flags == 0 and M.recode(GC.BEYOND, g).flags == M.ERR_GLV_RANGE
+    assert M.recode(GC.EDGE, g).digits == M.recode(lam - 1, g).digits[:8] + [0x7FFF] * 8
+    assert M.recode(GC.EDGE_CARRIED, g).digits[8:] == [-1] + [0] * 6 + [0x7FFF]  # top limb 0x7FFE + the carry
+    assert all(M.recode(GC.EDGE + 1 + lam * j, g).flags for j in range(0, 70000, 7))  # (no gap right above it)

@@ -4,6 +4,7 @@
 // Device code; included by sequencer.hip only.
 #pragma once
 #include "../curves.hpp"
+#include "../glv_split.hpp"
 
 namespace msm377 {
 namespace {
@@ -272,89 +273,35 @@ __global__ void __launch_bounds__(256) k_scalars_width(const uint32_t* __restric
   }
 }
 
-// out[0..NA+NB) = a * b on 32-bit words (schoolbook, carries resolved per row).
-template <int NA, int NB_>
-__device__ __forceinline__ void mul_words(const uint32_t* a, const uint32_t* b, uint32_t* out) {
-#pragma unroll
-  for (int k = 0; k < NA + NB_; k++) out[k] = 0;
-#pragma unroll
-  for (int i = 0; i < NA; i++) {
-    uint32_t carry = 0;
-#pragma unroll
-    for (int j = 0; j < NB_; j++) {
-      const uint64_t t = (uint64_t)a[i] * b[j] + out[i + j] + carry;
-      out[i + j] = (uint32_t)t;
-      carry = (uint32_t)(t >> 32);
-    }
-    out[i + NB_] = carry;
-  }
-}
-
-// Eight signed 16-bit digits of a 128-bit value v < 2^127 (top digit stays non-negative); windows
-// [wb, wb + wc) are written to slots 0..wc-1.  Returns non-zero if the value does not fit (top window
-// reaches 2^15).
+// Eight signed 16-bit digits of a 128-bit value v < 2^127 (top digit stays non-negative; the chain is recode128_step of
+// glv_split.hpp); windows [wb, wb + wc) are written to slots 0..wc-1.  Returns non-zero if the value does not fit (top
+// window reaches 2^15).
 __device__ __forceinline__ uint32_t recode128(const uint32_t* v, uint16_t* __restrict__ digits, size_t stride, size_t col, uint32_t wb,
                                               uint32_t wc) {
   uint32_t carry = 0, bad = 0;
 #pragma unroll
   for (uint32_t win = 0; win < 8; win++) {
-    const uint32_t limb = (v[win >> 1] >> (16 * (win & 1))) & 0xffffu;
-    const uint32_t t = limb + carry;
-    carry = (win < 7 && t >= 32768u) ? 1u : 0u;
-    if (win >= wb && win < wb + wc) digits[(size_t)(win - wb) * stride + col] = (uint16_t)((t + 32768u) & 0xffffu);
-    if (win == 7 && t >= 32768u) bad = 1u;
+    const uint32_t stored = recode128_step(v, win, carry, bad);
+    if (win >= wb && win < wb + wc) digits[(size_t)(win - wb) * stride + col] = (uint16_t)stored;
   }
   return bad;
 }
 
 // One thread per scalar: k -> (k1, k2) by a Barrett quotient (MU = floor(2^384 / LAMBDA), at
-// most one correction), then the signed digits of k1 into column i and of k2 into column n + i of
-// the 8 x 2n digit matrix.  Scalars outside the GLV range (k2 >= 2^127, i.e. k >~ 2^254) set bit 1
-// of *err: the host then reruns the call on the plain 16-window path.
+// most one correction: glv_split.hpp, shared with the host), then the signed digits of k1 into
+// column i and of k2 into column n + i of the 8 x 2n digit matrix.  Scalars outside the GLV range
+// (k2 >= 2^127, i.e. k >~ 2^254) set bit 1 of *err: the host then reruns the call on the plain
+// 16-window path.
 __global__ void __launch_bounds__(256) k_decompose_glv(const uint32_t* __restrict__ scalars, uint16_t* __restrict__ digits, uint64_t n,
                                                        uint32_t wb, uint32_t wc, int* __restrict__ err) {
   uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   uint32_t k[8];
   load_words16(scalars + i * 8, k, 2);
-  uint32_t prod[17];
-  mul_words<8, 9>(k, GlvConsts::MU, prod);
-  uint32_t q[5];
-#pragma unroll
-  for (int j = 0; j < 5; j++) q[j] = prod[12 + j];  // floor(k MU / 2^384): the quotient or one less
-  uint32_t ql[9];
-  mul_words<5, 4>(q, GlvConsts::LAMBDA, ql);
-  uint32_t rem[5];
-  {
-    uint32_t borrow = 0;
-#pragma unroll
-    for (int j = 0; j < 5; j++) {
-      const uint64_t d = (uint64_t)k[j] - ql[j] - borrow;
-      rem[j] = (uint32_t)d;
-      borrow = (uint32_t)(d >> 32) & 1u;
-    }
-  }
-  // rem in [0, 2 LAMBDA): one conditional correction
-  uint32_t sub[5];
-  uint32_t borrow = 0;
-#pragma unroll
-  for (int j = 0; j < 5; j++) {
-    const uint64_t d = (uint64_t)rem[j] - (j < 4 ? GlvConsts::LAMBDA[j] : 0u) - borrow;
-    sub[j] = (uint32_t)d;
-    borrow = (uint32_t)(d >> 32) & 1u;
-  }
-  if (!borrow) {
-#pragma unroll
-    for (int j = 0; j < 5; j++) rem[j] = sub[j];
-    uint32_t c = 1;
-#pragma unroll
-    for (int j = 0; j < 5; j++) {
-      const uint64_t t = (uint64_t)q[j] + c;
-      q[j] = (uint32_t)t;
-      c = (uint32_t)(t >> 32);
-    }
-  }
-  uint32_t bad = q[4] | rem[4];
+  uint32_t q[5], rem[5];
+  glv_quotient(k, q, rem);
+  glv_correct(q, rem);  // rem in [0, 2 LAMBDA): one conditional correction
+  uint32_t bad = glv_fifth_words(q, rem);
   bad |= recode128(rem, digits, (size_t)2 * n, (size_t)i, wb, wc);
   bad |= recode128(q, digits, (size_t)2 * n, (size_t)(n + i), wb, wc);
   if (bad) atomicOr(err, 2);
