@@ -605,10 +605,10 @@ int msm377_g1_read_mul_table(msm377_ctx* ctx, uint32_t which, uint32_t index, ms
  *
  * msm377_read_walk_stash describes and copies what the LAST PASS of the last batch DEVICE call left in the stash: the
  * projective point of every output as its walk kernel stored it (k_bm_accumulate, k_bmm_accumulate, k_cr_accumulate and
- * k_cr_fold, k_bmv_accumulate, k_bl2_accumulate, k_edbm_accumulate, k_edbmv_accumulate, k_edbl2_accumulate, k_edcr_accumulate and
- * k_edcr_fold) and the exclusive running products the up-sweep of the
+ * k_cr_fold, k_bmv_accumulate, k_bl2_accumulate, k_edbm_accumulate, k_edbmv_accumulate, k_edbl2_accumulate, k_edbl_accumulate,
+ * k_edcr_accumulate and k_edcr_fold) and the exclusive running products the up-sweep of the
  * normalisation (k_bm_up, k_edbm_up) put beside them.  It covers msm377_g1_batch_mul*, _batch_mul_multi*, _commit_rows*,
- * _batch_mul_var*, _batch_lincomb2* and msm377_ed_batch_mul_multi*, _batch_mul_var*, _batch_lincomb2*, _commit_rows*; a host-buffer call is one device call per piece of at
+ * _batch_mul_var*, _batch_lincomb2* and msm377_ed_batch_mul_multi*, _batch_mul_var*, _batch_lincomb2*, _batch_lincomb*, _commit_rows*; a host-buffer call is one device call per piece of at
  * most 2^20 scalars, and the description is that of its last piece.  `info` is written down on the host beside the
  * launches it describes; a call that does not use the read-back launches and allocates exactly what it did without it.
  *
@@ -661,6 +661,7 @@ int msm377_g1_read_mul_table(msm377_ctx* ctx, uint32_t which, uint32_t index, ms
 #define MSM377_WALK_ED_BATCH_MUL_VAR 7 /* k_edbmv_accumulate; its tables: msm377_ed_read_walk_tables */
 #define MSM377_WALK_ED_BATCH_LINCOMB2 8 /* k_edbl2_accumulate: form ED, width 4, k 2; its two tables: msm377_ed_read_walk_table */
 #define MSM377_WALK_ED_COMMIT_ROWS 9 /* k_edcr_accumulate and k_edcr_fold: form ED, the set's width, the call's k, the plan's segments */
+#define MSM377_WALK_ED_BATCH_LINCOMB 10 /* k_edbl_accumulate: form ED, width 4, the call's k; its k tables: msm377_ed_read_walk_table */
 #define MSM377_WALK_FORM_XYZZ 0
 #define MSM377_WALK_FORM_ED 1
 typedef struct msm377_walk_stash_info {
@@ -937,7 +938,7 @@ int msm377_ed_read_walk_tables(msm377_ctx* ctx, msm377_walk_tables_info* info, u
  * msm377_ed_read_walk_table copies table `table` of the last pass (0: of the P_i, 1: of the Q_i; info.tables = 2), records
  * as msm377_ed_read_walk_tables above, which is table 0 of it and stays valid after a variable-base call (tables = 1).  A
  * stride-0 array's table holds the same eight records for every i.  msm377_g1_read_walk_tables is MSM377_ESTATE after
- * this call. */
+ * this call.  After msm377_ed_batch_lincomb* it answers with info.tables = k, the call's terms (below). */
 int msm377_ed_batch_lincomb2_device(msm377_ctx* ctx, const void* d_p, const void* d_q, const void* d_a, const void* d_b, uint64_t n, uint32_t p_stride /* 64 or 0 */,
                                     uint32_t q_stride /* 64 or 0 */, uint32_t a_stride /* 32 or 0 */, uint32_t b_stride /* 32 or 0 */, void* d_out_points /* n x 64 */);
 int msm377_ed_batch_lincomb2(msm377_ctx* ctx, const uint8_t* p, const uint8_t* q, const uint8_t* a, const uint8_t* b, uint64_t n, uint32_t p_stride, uint32_t q_stride, uint32_t a_stride,
@@ -948,6 +949,68 @@ int msm377_ed_batch_lincomb2(msm377_ctx* ctx, const uint8_t* p, const uint8_t* q
 int msm377_ed_batch_lincomb2_host(const uint8_t* p, const uint8_t* q, const uint8_t* a, const uint8_t* b, uint64_t n, uint32_t p_stride, uint32_t q_stride, uint32_t a_stride,
                                   uint32_t b_stride, uint8_t* out_points);
 int msm377_ed_read_walk_table(msm377_ctx* ctx, msm377_walk_tables_info* info, uint32_t table, uint64_t first, uint64_t count, uint32_t* words);
+
+/* ---- Edwards-BLS12 k-term linear combination ----------------------------------------------- */
+
+/* out[i] = sum_{j<k} [s_ij]P_ij on Edwards-BLS12, 1 <= k <= MSM377_LINCOMB_MAX_TERMS: n outputs, every one its own 64-byte
+ * wire point, every term its own array of points and of scalars (a Schnorr check as one sum [s_i]G - [c_i]PK_i - R_i
+ * compared with O; both halves of a Chaum-Pedersen / DLEQ proof; address derivation pk_sig_i + pr_sig_i + [sk_prf_i]G;
+ * ElGamal re-encryption [r_i]G + [r_i']PK_i + C_i; a random linear combination of a few key vectors).  Per term the
+ * contract is word for word that of msm377_ed_batch_lincomb2* above -- 64-byte wire records in and out, the identity the
+ * record (0, 1); every 32-byte value a legal scalar, not reduced; any n, n = 0 MSM377_OK without a launch once the shape
+ * has been checked; 16-byte aligned device pointers; synchronous calls; MSM377_EINVAL while a non-wire input form is set,
+ * for a misaligned pointer, a null pointer with n > 0 or a stride outside its set, with the outputs untouched -- and this
+ * section states only what differs (csrc/kernels/ed_batch_lincomb.hpp).
+ *
+ * Terms.  `terms` points to k descriptors in HOST memory; the pointers inside are device pointers (_device) or host
+ * pointers (the other two).  point_stride is 64 or 0, scalar_stride 32 or 0; 0 means ONE point or ONE scalar for all n
+ * outputs, and only its 64 or 32 bytes are read.  All strides are independent: term 0 a stride-0 point and term 2 a
+ * stride-0 scalar is the Schnorr check as one sum.  k = 0, k above MSM377_LINCOMB_MAX_TERMS and a null `terms` are
+ * MSM377_EINVAL, whatever n.
+ *
+ * Points and relations.  Every curve point is a legal input in every term, mixed freely, and every relation among the k
+ * points of one output is followed through by the complete law itself: P_ij = +-P_ij', one term a multiple of another, a
+ * sum of O from terms none of which is O, every term O.  No subgroup test is run.
+ *
+ * Refusal.  Before anything is written the device call runs the canonical + on-curve check over the points of every term
+ * (a stride-0 term is ONE point), into k sets of counters of the call's own; a finding is MSM377_EPOINT with the outputs
+ * untouched, and msm377_last_error reads "point <i> of term <j> ...": the lowest failing index, the term, and the reason.
+ * Of several findings the one with the lowest index is reported; among equal indices the lowest term.  The host-buffer
+ * call works in pieces of 2^20 outputs; a call of several pieces checks every piece of every term first, on the device.
+ *
+ * Overlap.  Point arrays are only read and may overlap or be the same pointer.  d_out_points may equal any term's points
+ * where that term's point_stride is 64, and the fold in place works: a pass reads all of its inputs before it writes its
+ * outputs, and passes cover disjoint index ranges.  d_out_points equal to the pointer of a stride-0 point is
+ * MSM377_EINVAL.  Any other overlap is the caller's bug.
+ *
+ * State.  A pass is 2^16 outputs whatever k.  The per-point tables [1..8]P_ij of a pass, k x 2^19 records of 128 bytes
+ * (k x 64 MB), are ONE allocation of this call's own: it grows when a call brings a larger k, never shrinks, is released
+ * by msm377_ctx_destroy and is never valid between calls.  The table memory of msm377_g1_batch_mul_var*, the resident MSM
+ * bases, every G1 table, slot and build counter, the 16 Edwards-BLS12 table slots and msm377_ed_ctx_get_mul_table_builds,
+ * both generator sets and a check call's state are untouched, and the other way round.
+ *
+ * k = 1 and k = 2 run this call's own kernels; their outputs are byte for byte those of msm377_ed_batch_mul_var_device and
+ * msm377_ed_batch_lincomb2_device, which remain the calls to use for one and two terms.
+ *
+ * msm377_read_walk_stash answers with kind MSM377_WALK_ED_BATCH_LINCOMB (form ED, width 4, k the call's k): stash point i
+ * is the sum of output pass_offset + i.  msm377_ed_read_walk_table answers with info.tables = k and copies table t < k,
+ * records as after the pairwise call: entry e of term t of output i is record ((t * 8) + e - 1) * m + i of the engine's
+ * tables, m the outputs of the pass.  msm377_ed_read_walk_tables is table 0 of it; msm377_g1_read_walk_tables is
+ * MSM377_ESTATE after this call. */
+#define MSM377_LINCOMB_MAX_TERMS 8
+typedef struct msm377_lincomb_term {
+  const void* points;      /* n x 64-byte wire records, or ONE record (point_stride 0) */
+  const void* scalars;     /* n x 32 bytes, or ONE scalar (scalar_stride 0)           */
+  uint32_t point_stride;   /* 64 or 0 */
+  uint32_t scalar_stride;  /* 32 or 0 */
+} msm377_lincomb_term;
+/* out[i] = sum_{j<k} [s_ij]P_ij.  terms: k descriptors in HOST memory; the pointers inside are device pointers */
+int msm377_ed_batch_lincomb_device(msm377_ctx* ctx, const msm377_lincomb_term* terms, uint32_t k, uint64_t n, void* d_out_points);
+int msm377_ed_batch_lincomb(msm377_ctx* ctx, const msm377_lincomb_term* terms /* host pointers */, uint32_t k, uint64_t n, uint8_t* out_points);
+/* The same on ONE CPU thread: no device, no context (csrc/ed_batch_lincomb_host.hpp): the same checks and codes, each term
+ * by plain double-and-add on the canonical formulas, the terms added in order, one inversion per output; the yardstick of
+ * the device call.  There is no context to carry the text of a refusal: msm377_ed_check_points_host names index and reason. */
+int msm377_ed_batch_lincomb_host(const msm377_lincomb_term* terms, uint32_t k, uint64_t n, uint8_t* out_points);
 
 /* ---- variable-base batch multiplication --------------------------------------------------- */
 

@@ -25,6 +25,7 @@ import sys
 P_FP = 0x01AE3A4617C510EAC63B05C06CA1493B1A22D9F300F5138F1EF3622FBA094800170B5D44300000008508C00000000001
 Q_FQ = 8444461749428370424248824938781546531375899335154063827935233455917409239041
 LB = 29
+LINCOMB_MAX_TERMS = 8  # MSM377_LINCOMB_MAX_TERMS: consecutive additions of one step of kernels/ed_batch_lincomb.hpp
 BETA = 1 << LB
 MASK = BETA - 1
 # the field under test (use_field): modulus, limbs, reduction steps, slack of a lazy product above the modulus
@@ -285,6 +286,14 @@ def te_formulas(canonical):
     second = te_amadd(*first, "te l2 amadd after amadd")
     for pt, tag in ((second, "te l2 dbl after two amadd"), (first, "te l2 dbl after one amadd")):
         te_amadd(*te_dbl(pt[0], pt[1], pt[3], tag), tag + ", amadd")
+    # The k-term walk of kernels/ed_batch_lincomb.hpp: up to LINCOMB_MAX_TERMS additions per step, each reading what the one
+    # before returned with no normalisation between them -- after a doubling, and after the start value O (step 64, the
+    # carries') -- and the next step's first dbl_nt on what ANY number of them returned (zero digits sit their addition out).
+    for start, tag in (((x, y, t, z), "te lk after dbl"), ((zero, one, zero, one), "te lk carries")):
+        pt = start
+        for j in range(1, LINCOMB_MAX_TERMS + 1):
+            pt = te_amadd(*pt, "%s, amadd %d" % (tag, j))
+            te_amadd(*te_dbl(pt[0], pt[1], pt[3], "%s, dbl after %d amadd" % (tag, j)), "%s, dbl after %d amadd, amadd" % (tag, j))
 
     # canonical operations on stored (lazy) coordinates: mul() = reduce_once(mul_lz()) needs mul_lz < 2p
     mul_lz(PX, canonical, "gather X*TO64")

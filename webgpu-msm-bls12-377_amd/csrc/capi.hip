@@ -15,6 +15,7 @@
 #include "ed_batch_mul_host.hpp"
 #include "ed_batch_mul_var_host.hpp"
 #include "ed_batch_lincomb2_host.hpp"
+#include "ed_batch_lincomb_host.hpp"
 #include "ed_commit_rows_host.hpp"
 #include "commit_rows_host.hpp"
 #include "commit_rows_plan.hpp"
@@ -447,6 +448,8 @@ int msm377_ed_batch_lincomb2_host(const uint8_t* p, const uint8_t* q, const uint
   return ed_batch_lincomb2_host(p, q, a, b, n, p_stride, q_stride, a_stride, b_stride, out_points);
 }
 
+int msm377_ed_batch_lincomb_host(const msm377_lincomb_term* terms, uint32_t k, uint64_t n, uint8_t* out_points) { return ed_batch_lincomb_host(terms, k, n, out_points); }
+
 uint64_t msm377_ed_ctx_get_mul_table_builds(const msm377_ctx* ctx) { return ctx ? ctx->edbm.builds : 0; }
 
 int msm377_ctx_get_last_check(const msm377_ctx* ctx, msm377_check_report* out) {
@@ -558,6 +561,12 @@ int msm377_ed_batch_lincomb2_device(msm377_ctx* ctx, const void* d_p, const void
 int msm377_ed_batch_lincomb2(msm377_ctx* ctx, const uint8_t* p, const uint8_t* q, const uint8_t* a, const uint8_t* b, uint64_t n, uint32_t p_stride, uint32_t q_stride, uint32_t a_stride,
                              uint32_t b_stride, uint8_t* out_points) {
   return ed_wire_only(ctx) ? MSM377_EINVAL : eng::ed_batch_lincomb2(ctx, p, q, a, b, n, p_stride, q_stride, a_stride, b_stride, out_points);
+}
+int msm377_ed_batch_lincomb_device(msm377_ctx* ctx, const msm377_lincomb_term* terms, uint32_t k, uint64_t n, void* d_out_points) {
+  return ed_wire_only(ctx) ? MSM377_EINVAL : eng::ed_batch_lincomb_device(ctx, terms, k, n, d_out_points);
+}
+int msm377_ed_batch_lincomb(msm377_ctx* ctx, const msm377_lincomb_term* terms, uint32_t k, uint64_t n, uint8_t* out_points) {
+  return ed_wire_only(ctx) ? MSM377_EINVAL : eng::ed_batch_lincomb(ctx, terms, k, n, out_points);
 }
 int msm377_ed_read_walk_table(msm377_ctx* ctx, msm377_walk_tables_info* info, uint32_t table, uint64_t first, uint64_t count, uint32_t* words) {
   return eng::ed_read_walk_table(ctx, info, table, first, count, words);

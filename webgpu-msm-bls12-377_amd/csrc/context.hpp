@@ -118,6 +118,13 @@ struct EdBatchMulState {
   // The pairwise linear combination (msm377_ed_batch_lincomb2*, kernels/ed_batch_lincomb2.hpp): the counters of ITS two
   // point checks, p's then q's (2 x CHK_WORDS words, allocated on first use).
   uint32_t* pair_check = nullptr;
+  // The k-term linear combination (msm377_ed_batch_lincomb*, kernels/ed_batch_lincomb.hpp): the counters of ITS point checks,
+  // a set per term (MSM377_LINCOMB_MAX_TERMS x CHK_WORDS words, allocated on first use), and the per-point tables of ONE
+  // pass of 2^16 outputs, [1..8]P_ij for lincomb_terms terms (64 MB each) as ONE allocation of the call's own: regrown when a
+  // call brings more terms, never shrunk, never valid between calls.  BatchMulState::var_table is not used.
+  uint32_t* lincomb_check = nullptr;
+  uint32_t* lincomb_table = nullptr;
+  uint32_t lincomb_terms = 0;
 };
 
 // The resident generator set of the row commitments (msm377_g1_set_generators / msm377_g1_commit_rows*,
@@ -189,6 +196,7 @@ struct WalkLayout {
   bool valid = false;
   msm377_walk_stash_info info = {};
   msm377_walk_tables_info tables = {};  // tables == 0: the pass walked no per-point tables
+  const uint32_t* d_tables = nullptr;   // where they are: BatchMulState::var_table, or the k-term call's own (EdBatchMulState::lincomb_table)
 };
 
 // ---- what belongs together, by the functions that use it ----

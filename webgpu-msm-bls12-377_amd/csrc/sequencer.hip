@@ -54,6 +54,7 @@
 #include "ed_batch_mul_host.hpp"
 #include "ed_batch_mul_var_host.hpp"
 #include "ed_batch_lincomb2_host.hpp"
+#include "ed_batch_lincomb_host.hpp"
 #include "ed_commit_rows_host.hpp"
 #include "validate_host.hpp"
 #include "kernels/accumulate.hpp"
@@ -72,6 +73,7 @@
 #include "kernels/batch_mul_var.hpp"
 #include "kernels/ed_batch_mul_var.hpp"
 #include "kernels/ed_batch_lincomb2.hpp"
+#include "kernels/ed_batch_lincomb.hpp"
 #include "kernels/batch_lincomb2.hpp"
 #include "kernels/wide.hpp"
 
@@ -2011,6 +2013,7 @@ void note_walk(msm377_ctx* ctx, uint32_t kind, uint32_t form, uint32_t width, ui
   wl.tables = msm377_walk_tables_info{};
   wl.tables.tables = tables;
   wl.tables.entries = tables ? (uint32_t)BMV_ENTRIES : 0;
+  wl.d_tables = tables ? ctx->bm.var_table : nullptr;  // (the k-term call names its own behind this)
 }
 
 // What the normalisation, the builder and the pointer check need to know of a curve: the bytes of a base on the wire, the
@@ -2846,6 +2849,173 @@ int ed_batch_lincomb2(msm377_ctx* ctx, const uint8_t* p, const uint8_t* q, const
   });
 }
 
+// ---- Edwards-BLS12 k-term linear combination (include/msm377.h; kernels/ed_batch_lincomb.hpp) ----
+// The flow of the pairwise call above with the number of terms a run-time value: the canonical + on-curve check of EVERY
+// term's points before anything is written; per pass of EDBL_PASS outputs the k tables through the stash in ceil(k / 2)
+// rounds of one table launch and ONE normalisation each (a chunk of the stash holds two tables of a full pass), round r
+// into the records from r * 16 m on, then the joint walk; the flow normalises again.  A pass reads all of its inputs
+// before it writes its outputs, and passes cover disjoint index ranges: d_out_points equal to the points of a term with a
+// record per output is safe, and so is the fold in place.  The tables are the call's own allocation
+// (ctx->edbm.lincomb_table), never valid between calls; ctx->bm.var_table and every slot, key and build count are left alone.
+namespace {
+
+int edbl_check_args(msm377_ctx* ctx, const msm377_lincomb_term* terms, uint32_t k) {
+  if (!ctx) return MSM377_EINVAL;
+  ctx->err.clear();
+  forget_walk(ctx);  // as edbm_check_args
+  if (ed_batch_lincomb_shape_ok(terms, k)) return MSM377_OK;
+  ctx->err = !terms ? "null pointer" : k < 1 || k > MSM377_LINCOMB_MAX_TERMS ? "k is 1 to MSM377_LINCOMB_MAX_TERMS terms"
+                                      : "in every term scalar_stride is 32 or 0 (one scalar for all outputs) and point_stride 64 or 0 (one point for all outputs)";
+  return MSM377_EINVAL;
+}
+
+// The pointers of the k terms and of the outputs: none null, all 16-byte aligned, the outputs not over a stride-0 point.
+int edbl_check_pointers(msm377_ctx* ctx, const msm377_lincomb_term* terms, uint32_t k, const void* out, bool device) {
+  bool null = !out, misaligned = device && ((uintptr_t)out & 15) != 0, over = false;
+  for (uint32_t j = 0; j < k; j++) {
+    null |= !terms[j].points || !terms[j].scalars;
+    misaligned |= device && ((((uintptr_t)terms[j].points) | ((uintptr_t)terms[j].scalars)) & 15) != 0;
+    over |= terms[j].point_stride == 0 && terms[j].points == out;
+  }
+  if (null) return null_pointer(ctx);
+  if (misaligned) {
+    ctx->err = EdMul::MISALIGNED;
+    return MSM377_EINVAL;
+  }
+  if (over) {
+    ctx->err = "the outputs would overwrite the one point of a stride-0 term";
+    return MSM377_EINVAL;
+  }
+  return MSM377_OK;
+}
+
+// k_check_curve<EdCheck> over cnt[j] points of term j (a stride-0 term: ONE point; 0: nothing of it in this piece) into k
+// sets of counters of this call's own (ctx->edbm.lincomb_check): no check call's scratch, report or list is touched, nor
+// the other batch calls'.  k tiny clears, up to k launches, one wait.  first[j]: the index of d_points[j][0] in the
+// caller's array (a piece of a host-buffer call; 0 for the one point of a stride-0 term).
+int edbl_check_points(msm377_ctx* ctx, uint32_t k, const void* const* d_points, const uint64_t* cnt, const uint64_t* first) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const int rc = bm_alloc(ctx, &ctx->edbm.lincomb_check, (size_t)MSM377_LINCOMB_MAX_TERMS * CHK_WORDS * 4);
+  if (rc) return rc;
+  for (uint32_t j = 0; j < k; j++) {
+    uint32_t* scratch = ctx->edbm.lincomb_check + j * CHK_WORDS;
+    hipLaunchKernelGGL(k_check_clear, dim3(1), dim3(64), 0, ctx->stream, scratch);
+    if (cnt[j])
+      hipLaunchKernelGGL(k_check_curve<EdCheck>, dim3((unsigned)((cnt[j] + CHK_THREADS - 1) / CHK_THREADS)), dim3(CHK_THREADS), 0, ctx->stream, (const uint32_t*)d_points[j], cnt[j], 1u,
+                         scratch, (uint32_t*)nullptr);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  uint32_t h[MSM377_LINCOMB_MAX_TERMS * CHK_WORDS];
+  HIP_TRY(ctx, hipMemcpyAsync(h, ctx->edbm.lincomb_check, (size_t)k * CHK_WORDS * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  uint64_t key[MSM377_LINCOMB_MAX_TERMS], bad[MSM377_LINCOMB_MAX_TERMS];
+  for (uint32_t j = 0; j < k; j++) {
+    key[j] = (uint64_t)h[j * CHK_WORDS + CHK_FIRST] | ((uint64_t)h[j * CHK_WORDS + CHK_FIRST + 1] << 32);
+    bad[j] = key[j] == UINT64_MAX ? UINT64_MAX : first[j] + (key[j] >> 2);
+  }
+  const uint32_t t = ed_batch_lincomb_first_term(bad, k);
+  if (t == k) return MSM377_OK;
+  ctx->err = ed_batch_lincomb_refusal(t, bad[t], (uint32_t)(key[t] & 3) == CHK_CLASS_NONCANON ? MSM377_CHECK_CANONICAL : MSM377_CHECK_CURVE);
+  return MSM377_EPOINT;
+}
+
+// The tables of a pass for k terms: ONE allocation, regrown for a larger k (the old one goes back first) and kept otherwise.
+int edbl_ensure_table(msm377_ctx* ctx, uint32_t k) {
+  EdBatchMulState& st = ctx->edbm;
+  if (st.lincomb_table && st.lincomb_terms >= k) return MSM377_OK;
+  ctx->own.release(st.lincomb_table);
+  st.lincomb_table = nullptr;
+  st.lincomb_terms = 0;
+  const int rc = bm_alloc(ctx, &st.lincomb_table, (size_t)k * BMV_ENTRIES * EDBL_PASS * BM_REC_WORDS * 4);
+  if (!rc) st.lincomb_terms = k;
+  return rc;
+}
+
+}  // namespace
+
+int ed_batch_lincomb_device(msm377_ctx* ctx, const msm377_lincomb_term* terms, uint32_t k, uint64_t n, void* d_out_points) {
+  const int early = edbl_check_args(ctx, terms, k);
+  const auto check = [&]() -> int {
+    const int rc = edbl_check_pointers(ctx, terms, k, d_out_points, true);
+    if (rc) return rc;
+    const void* pts[MSM377_LINCOMB_MAX_TERMS];
+    uint64_t cnt[MSM377_LINCOMB_MAX_TERMS], first[MSM377_LINCOMB_MAX_TERMS];
+    for (uint32_t j = 0; j < k; j++) pts[j] = terms[j].points, cnt[j] = terms[j].point_stride ? n : 1, first[j] = 0;
+    return edbl_check_points(ctx, k, pts, cnt, first);
+  };
+  const auto pass = [&](uint64_t off, uint64_t m) -> int {
+    uint4* stash = reinterpret_cast<uint4*>(ctx->bm.stash);
+    uint32_t* table = ctx->edbm.lincomb_table;
+    EdblTerms of_pass = {};
+    for (uint32_t j = 0; j < k; j++) {
+      of_pass.points[j] = (const uint8_t*)terms[j].points + off * terms[j].point_stride;
+      of_pass.scalars[j] = (const uint32_t*)terms[j].scalars + off * (terms[j].scalar_stride / 4);
+      of_pass.point_stride[j] = terms[j].point_stride;
+      of_pass.scalar_words[j] = terms[j].scalar_stride / 4;
+    }
+    for (uint32_t first = 0; first < k; first += EDBL_ROUND_TERMS) {  // (two tables of a full pass are one chunk of the stash)
+      const uint32_t round_terms = std::min<uint32_t>(EDBL_ROUND_TERMS, k - first);
+      hipLaunchKernelGGL(k_edbl_table, dim3(bm_grid(m).x, round_terms), dim3(BM_THREADS), 0, ctx->stream, of_pass, first, m, stash);
+      const int rc = normalise<EdMul>(ctx, m * round_terms * BMV_ENTRIES, EDBM_FORM_TABLE, table + (size_t)first * BMV_ENTRIES * m * BM_REC_WORDS, nullptr);
+      if (rc) return rc;
+    }
+    hipLaunchKernelGGL(k_edbl_accumulate, bm_grid(m), dim3(BM_THREADS), (size_t)k * EDBL_TERM_LDS_WORDS * 4, ctx->stream, (const uint32_t*)table, of_pass, k, m, stash);
+    note_walk(ctx, MSM377_WALK_ED_BATCH_LINCOMB, MSM377_WALK_FORM_ED, (uint32_t)BMV_WIDTH, k, 1, 0, k);
+    ctx->last.walk.d_tables = table;
+    return MSM377_OK;
+  };
+  return batch_device_call<EdMul>(ctx, early, n, EDBL_PASS, EDBM_FORM_WIRE, d_out_points, 64, nullptr, check, [&] { return edbl_ensure_table(ctx, k); }, pass);
+}
+
+// Host buffers: every term's scalars and points up, records down, in pieces of at most a chunk; a stride-0 scalar or point
+// is uploaded once.  Parts 2j and 2j + 1 of the staging are term j's scalars and points.  A call of ONE piece leaves the
+// check to its device call; a call of several pieces checks all pieces of all terms first, on the device, piece by piece
+// through the staging, as ed_batch_lincomb2 does, and then uploads the points a second time.  Pieces come in rising
+// order, so the first piece with a finding holds the lowest index.
+int ed_batch_lincomb(msm377_ctx* ctx, const msm377_lincomb_term* terms, uint32_t k, uint64_t n, uint8_t* out_points) {
+  int rc = edbl_check_args(ctx, terms, k);
+  if (rc || n == 0) return rc;
+  rc = edbl_check_pointers(ctx, terms, k, out_points, false);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const uint64_t piece = std::min<uint64_t>(n, BM_CHUNK);
+  const auto s = [&](uint32_t j) { return j < k ? (size_t)piece * 32 : (size_t)0; };  // parts 2j, 2j + 1: the scalars and the points of term j
+  const auto p = [&](uint32_t j) { return j < k ? (size_t)piece * 64 : (size_t)0; };
+  HostStage io(ctx, {s(0), p(0), s(1), p(1), s(2), p(2), s(3), p(3), s(4), p(4), s(5), p(5), s(6), p(6), s(7), p(7)}, (size_t)piece * 64, 0,
+               "out of device memory for the linear combination staging");
+  static_assert(MSM377_LINCOMB_MAX_TERMS == 8, "the staging above lists eight terms");
+  if (io.rc) return io.rc;
+  const auto points_of = [&](uint32_t j) { return (const uint8_t*)terms[j].points; };
+  const auto scalars_of = [&](uint32_t j) { return (const uint8_t*)terms[j].scalars; };
+  for (uint32_t j = 0; j < k && !rc; j++) {
+    if (terms[j].scalar_stride == 0) rc = io.up(2 * j, scalars_of(j), 32, "hipMemcpy(scalar)");
+    if (!rc && terms[j].point_stride == 0) rc = io.up(2 * j + 1, points_of(j), 64, "hipMemcpy(point)");
+  }
+  const void* pts[MSM377_LINCOMB_MAX_TERMS];
+  for (uint32_t j = 0; j < k; j++) pts[j] = io.part(2 * j + 1);
+  for (uint64_t off = 0; n > piece && off < n && !rc; off += piece) {
+    const uint64_t m = std::min<uint64_t>(piece, n - off);
+    uint64_t cnt[MSM377_LINCOMB_MAX_TERMS], first[MSM377_LINCOMB_MAX_TERMS];
+    for (uint32_t j = 0; j < k && !rc; j++) {
+      if (terms[j].point_stride) rc = io.up(2 * j + 1, points_of(j) + off * 64, m * 64, "hipMemcpy(points)");
+      cnt[j] = terms[j].point_stride ? m : (off ? 0 : 1);
+      first[j] = terms[j].point_stride ? off : 0;
+    }
+    if (!rc) rc = edbl_check_points(ctx, k, pts, cnt, first);
+  }
+  if (rc) return rc;
+  return io.run(n, piece, out_points, 64, nullptr, [&](uint64_t off, uint64_t m) -> int {
+    int up = MSM377_OK;
+    msm377_lincomb_term d_terms[MSM377_LINCOMB_MAX_TERMS];
+    for (uint32_t j = 0; j < k && !up; j++) {
+      if (terms[j].scalar_stride) up = io.up(2 * j, scalars_of(j) + off * 32, m * 32, "hipMemcpy(scalars)");
+      if (!up && terms[j].point_stride) up = io.up(2 * j + 1, points_of(j) + off * 64, m * 64, "hipMemcpy(points)");
+      d_terms[j] = msm377_lincomb_term{io.part(2 * j + 1), io.part(2 * j), terms[j].point_stride, terms[j].scalar_stride};
+    }
+    return up ? up : ed_batch_lincomb_device(ctx, d_terms, k, m, io.records());
+  });
+}
+
 // ---- Edwards-BLS12 row commitments (include/msm377.h "Edwards-BLS12 row commitments"; kernels/ed_commit_rows.hpp) ----
 // The G1 flow above on this curve's kernels, over a set of its own (ctx->ed_gens): the plan, the ONE allocation, the
 // drop-first / install-last rule and the host staging are G1's.  What differs: the generators are checked on the DEVICE
@@ -3166,7 +3336,7 @@ static int read_walk_tables(msm377_ctx* ctx, uint32_t form, msm377_walk_tables_i
   if (!ctx) return MSM377_EINVAL;
   ctx->err.clear();
   const WalkLayout& wl = ctx->last.walk;
-  if (!wl.valid || !wl.tables.tables || wl.info.form != form || !ctx->bm.var_table) return walk_not_valid(ctx);
+  if (!wl.valid || !wl.tables.tables || wl.info.form != form || !wl.d_tables) return walk_not_valid(ctx);
   const msm377_walk_tables_info& ti = wl.tables;
   if (table >= ti.tables || first > ti.m || count > ti.m - first || (count && !words)) {
     ctx->err = "point range or table outside the pass";
@@ -3176,7 +3346,7 @@ static int read_walk_tables(msm377_ctx* ctx, uint32_t form, msm377_walk_tables_i
   if (!count) return MSM377_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   for (uint32_t e = 0; e < ti.entries; e++)  // entry e + 1 of point i of table t: record ((t * entries) + e) * m + i
-    HIP_TRY(ctx, hipMemcpy(words + ((size_t)e * count) * BM_REC_WORDS, ctx->bm.var_table + (((size_t)table * ti.entries + e) * ti.m + first) * BM_REC_WORDS,
+    HIP_TRY(ctx, hipMemcpy(words + ((size_t)e * count) * BM_REC_WORDS, wl.d_tables + (((size_t)table * ti.entries + e) * ti.m + first) * BM_REC_WORDS,
                            (size_t)count * BM_REC_WORDS * 4, hipMemcpyDeviceToHost));
   return MSM377_OK;
 }

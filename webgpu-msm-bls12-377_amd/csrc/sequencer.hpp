@@ -71,6 +71,9 @@ int ed_batch_lincomb2_device(msm377_ctx* ctx, const void* d_p, const void* d_q, 
                              uint32_t b_stride, void* d_out_points);
 int ed_batch_lincomb2(msm377_ctx* ctx, const uint8_t* p, const uint8_t* q, const uint8_t* a, const uint8_t* b, uint64_t n, uint32_t p_stride, uint32_t q_stride, uint32_t a_stride,
                       uint32_t b_stride, uint8_t* out_points);
+// Edwards-BLS12 k-term linear combination (kernels/ed_batch_lincomb.hpp): out[i] = sum_j [s_ij]P_ij, 1 <= k <= 8 terms.
+int ed_batch_lincomb_device(msm377_ctx* ctx, const msm377_lincomb_term* terms, uint32_t k, uint64_t n, void* d_out_points);
+int ed_batch_lincomb(msm377_ctx* ctx, const msm377_lincomb_term* terms, uint32_t k, uint64_t n, uint8_t* out_points);
 
 // Edwards-BLS12 row commitments (kernels/ed_commit_rows.hpp): out[i] = sum_j [s_ij]G_j over the first k generators of that curve's resident set.
 int ed_set_generators(msm377_ctx* ctx, const uint8_t* gens_xy, uint32_t k, int window_bits);

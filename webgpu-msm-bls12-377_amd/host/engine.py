@@ -249,6 +249,7 @@ WALK_BATCH_MUL, WALK_BATCH_MUL_MULTI, WALK_COMMIT_ROWS, WALK_BATCH_MUL_VAR, WALK
 WALK_ED_BATCH_MUL_VAR = 7
 WALK_ED_BATCH_LINCOMB2 = 8
 WALK_ED_COMMIT_ROWS = 9
+WALK_ED_BATCH_LINCOMB = 10
 WALK_FORM_XYZZ, WALK_FORM_ED = 0, 1
 
 
@@ -285,6 +286,9 @@ class MsmError(RuntimeError):
         # ed_batch_lincomb2*: the array that index counts in, "p" or "q" ("point <i> of q ..."); None for every other call
         of = re.search(r"\bpoint \d+ of ([pq])\b", detail) if code == EPOINT else None
         self.array = of.group(1) if of else None
+        # ed_batch_lincomb*: the term that index counts in ("point <i> of term <j> ..."); None for every other call
+        term = re.search(r"\bof term (\d+)\b", detail) if code == EPOINT else None
+        self.term = int(term.group(1)) if term else None
         msg = "%s failed: %s (%d)" % (what, _strerror(code), code)
         if detail:
             msg += ": " + detail
@@ -422,6 +426,9 @@ def load_library():
         "msm377_ed_batch_lincomb2": (i32, [vp, u8p, u8p, u8p, u8p, u64, u32, u32, u32, u32, vp]),
         "msm377_ed_batch_lincomb2_host": (i32, [u8p, u8p, u8p, u8p, u64, u32, u32, u32, u32, vp]),
         "msm377_ed_read_walk_table": (i32, [vp, vp, u32, u64, u64, vp]),
+        "msm377_ed_batch_lincomb_device": (i32, [vp, vp, u32, u64, vp]),
+        "msm377_ed_batch_lincomb": (i32, [vp, vp, u32, u64, vp]),
+        "msm377_ed_batch_lincomb_host": (i32, [vp, u32, u64, vp]),
         "msm377_ed_ctx_get_mul_table_builds": (u64, [vp]),
         "msm377_ed_read_mul_table": (i32, [vp, u32, vp, u64, u64, vp]),
         "msm377_ed_set_generators": (i32, [vp, u8p, u32, i32]),
@@ -669,6 +676,69 @@ def ed_batch_lincomb2_host(p: bytes, q: bytes, a: bytes, b: bytes) -> bytes:
         raise MsmError(rc, "msm377_ed_batch_lincomb2_host", "point %d of %s %s" % (bad[t], "pq"[t], why), index=bad[t])
     if rc:
         raise MsmError(rc, "msm377_ed_batch_lincomb2_host")
+    return out.raw[: 64 * n]
+
+
+LINCOMB_MAX_TERMS = 8  # MSM377_LINCOMB_MAX_TERMS
+
+
+class _LincombTermStruct(ctypes.Structure):
+    """msm377_lincomb_term"""
+
+    _fields_ = [("points", ctypes.c_void_p), ("scalars", ctypes.c_void_p), ("point_stride", ctypes.c_uint32), ("scalar_stride", ctypes.c_uint32)]
+
+
+def _lincomb_terms(terms):
+    """The C array of msm377_lincomb_term for ``terms``, a sequence of (points, scalars, point_stride, scalar_stride) with the
+    two pointers as integers (0: NULL); None for an empty sequence (the NULL ``terms`` of the C call)."""
+    if not terms:
+        return None
+    arr = (_LincombTermStruct * len(terms))()
+    for slot, (pts, scs, ps, ss) in zip(arr, terms):
+        slot.points, slot.scalars, slot.point_stride, slot.scalar_stride = pts or None, scs or None, int(ps), int(ss)
+    return arr
+
+
+def _ed_lincomb_shape(points_list, scalars_list) -> Tuple[int, list]:
+    """(n, [(point_stride, scalar_stride)] per term) of the k terms of an Edwards-BLS12 linear combination: n is the largest
+    element count; an argument of exactly one element, with n > 1, is the stride-0 form (one for all outputs)."""
+    if len(points_list) != len(scalars_list):
+        raise ValueError("one array of scalars per array of points")
+    if any(len(p) % 64 for p in points_list) or any(len(s) % 32 for s in scalars_list):
+        raise ValueError("an Edwards-BLS12 point is 64 bytes, a scalar 32")
+    counts = [(len(p) // 64, len(s) // 32) for p, s in zip(points_list, scalars_list)]
+    n = max((c for pair in counts for c in pair), default=0)
+    if any(c != n and not (c == 1 and n > 1) for pair in counts for c in pair):
+        raise ValueError("every term: one element per output, or exactly one element for all outputs")
+    return n, [(64 if cp == n else 0, 32 if cs == n else 0) for cp, cs in counts]
+
+
+def _lincomb_host_terms(points_list, scalars_list, strides):
+    """(C array, the buffers it points into) for host-buffer terms."""
+    keep = [(ctypes.create_string_buffer(bytes(p), max(1, len(p))), ctypes.create_string_buffer(bytes(s), max(1, len(s)))) for p, s in zip(points_list, scalars_list)]
+    return _lincomb_terms([(ctypes.addressof(p), ctypes.addressof(s), ps, ss) for (p, s), (ps, ss) in zip(keep, strides)]), keep
+
+
+def ed_batch_lincomb_host(points_list, scalars_list) -> bytes:
+    """out[i] = sum_j [s_ij]P_ij on Edwards-BLS12 on the calling thread (msm377_ed_batch_lincomb_host): no context, no
+    device.  ``points_list``: k buffers of 64-byte wire records, every one a curve point; ``scalars_list``: k buffers of
+    32-byte scalars, any value below 2^256; 1 <= k <= 8.  n is the largest element count; a buffer of exactly one element
+    with n > 1 stands for all outputs.  Returns n 64-byte wire records; the identity is (0, 1).  A point that is not on the
+    curve raises MsmError(EPOINT) with its ``term`` and ``index``: the lowest index of all findings, the lowest term where
+    indices are equal."""
+    n, strides = _ed_lincomb_shape(points_list, scalars_list)
+    terms, keep = _lincomb_host_terms(points_list, scalars_list, strides)
+    out = ctypes.create_string_buffer(max(1, 64 * n))
+    rc = load_library().msm377_ed_batch_lincomb_host(terms, len(points_list), n, ctypes.addressof(out))
+    if rc == EPOINT:
+        reps = [ed_check_points_host(bytes(p), CHECK_CANONICAL | CHECK_CURVE) for p in points_list]
+        bad = [n if r.first_bad is None else r.first_bad for r in reps]
+        t = bad.index(min(bad))
+        why = "has a coordinate that is not below q" if reps[t].first_bad_reason == CHECK_CANONICAL else "is not on the curve"
+        raise MsmError(rc, "msm377_ed_batch_lincomb_host", "point %d of term %d %s" % (bad[t], t, why), index=bad[t])
+    if rc:
+        raise MsmError(rc, "msm377_ed_batch_lincomb_host")
+    del keep
     return out.raw[: 64 * n]
 
 
@@ -1324,6 +1394,26 @@ class MsmEngine:
         self._check(rc, "msm377_ed_batch_lincomb2")
         return out.raw[: 64 * n]
 
+    def ed_batch_lincomb_device(self, terms, n: int, d_out: int):
+        """out[i] = sum_j [s_ij]P_ij on Edwards-BLS12 for n outputs, as 64-byte wire records at ``d_out``
+        (msm377_ed_batch_lincomb_device).  ``terms``: 1 to 8 tuples ``(d_points, d_scalars, point_stride, scalar_stride)`` of
+        device pointers, ``point_stride`` 64 or 0 (ONE point for all outputs), ``scalar_stride`` 32 or 0 (ONE scalar).  Every
+        curve point is a legal input in every term; ``d_out`` may be the points of any term of stride 64.  A point that is
+        not on the curve raises MsmError(EPOINT) with its ``term`` and ``index``, the outputs untouched."""
+        rc = self._lib.msm377_ed_batch_lincomb_device(self._ctx, _lincomb_terms(terms), len(terms), int(n), d_out or None)
+        self._check(rc, "msm377_ed_batch_lincomb_device")
+
+    def ed_batch_lincomb(self, points_list, scalars_list) -> bytes:
+        """Host-buffer form: returns n 64-byte wire records, n the largest element count of all buffers.  A buffer of
+        exactly one element with n > 1 is the one point or scalar of all outputs (msm377_ed_batch_lincomb)."""
+        n, strides = _ed_lincomb_shape(points_list, scalars_list)
+        terms, keep = _lincomb_host_terms(points_list, scalars_list, strides)
+        out = ctypes.create_string_buffer(max(1, 64 * n))
+        rc = self._lib.msm377_ed_batch_lincomb(self._ctx, terms, len(points_list), n, ctypes.addressof(out))
+        del keep
+        self._check(rc, "msm377_ed_batch_lincomb")
+        return out.raw[: 64 * n]
+
     # -- Edwards-BLS12 row commitments (include/msm377.h): out[i] = sum_j [s_ij]G_j over that curve's resident set --
     def ed_set_generators(self, gens, window_bits: int = 0):
         """Build and keep the window tables of the Edwards-BLS12 generators ``gens`` (64 wire bytes each, a host buffer, up
@@ -1580,8 +1670,9 @@ class MsmEngine:
 
     def ed_read_walk_table(self, table: int = 0, first: int = 0, count=None, info_only: bool = False):
         """(WalkTablesInfo, records) of table ``table`` of the last pass of ed_batch_lincomb2* (0: [1..8]P_i, 1: [1..8]Q_i;
-        info.tables = 2) or of ed_batch_mul_var* (table 0 only), records as ed_read_walk_tables returns them
-        (msm377_ed_read_walk_table).  MsmError(ESTATE) unless the last batch call was one of the two and completed."""
+        info.tables = 2), of ed_batch_lincomb* (table t of term t; info.tables = k) or of ed_batch_mul_var* (table 0 only),
+        records as ed_read_walk_tables returns them (msm377_ed_read_walk_table).  MsmError(ESTATE) unless the last batch
+        call was one of the three and completed."""
         import numpy as np
 
         raw = _WalkTablesInfoStruct()

@@ -175,6 +175,18 @@ const ed_batch_mul_var = (points, scalars) => addon.edBatchMulVarSync(points, sc
 // names its array and index.
 const ed_batch_lincomb2 = (p, q, a, b) => addon.edBatchLincomb2Sync(p, q, scalarsToBuffer(a), scalarsToBuffer(b));
 
+// Edwards-BLS12 k-term linear combination (msm377_ed_batch_lincomb): out[i] = sum_j [s_ij]P_ij, 1 to 8 terms, every output
+// its own point (a Schnorr check as one sum [s_i]G - [c_i]PK_i - R_i, both halves of a DLEQ proof, ElGamal re-encryption).
+// `terms`: one {points, scalars} per term -- a Buffer of 64-byte wire records x || y, and scalars (bigint[], Uint32Array[]
+// or a Buffer of 32 bytes each).  n is the largest element count; an argument of exactly ONE element with n > 1 stands for
+// all outputs.  Returns a Buffer of n 64-byte records; the identity is (0, 1).  Every curve point is a legal input; a point
+// off the curve throws, and the text names its index and its term.
+const ed_batch_lincomb = (terms) =>
+  addon.edBatchLincombSync(
+    terms.map((t) => t.points),
+    terms.map((t) => scalarsToBuffer(t.scalars)),
+  );
+
 // Row commitments (msm377_g1_set_generators / msm377_g1_commit_rows): out[i] = sum_j [s_ij]G_j over a RESIDENT set of up to
 // 4 096 generators (Pedersen vector commitments).  set_generators(gens, {windowBits}) builds and keeps the window tables --
 // `gens`: {x, y} points or a Buffer of 96-byte wire records; windowBits 0 (= 8), 8, or 16 for up to 64 generators; an empty
@@ -200,4 +212,4 @@ const ed_commit_rows = (scalars, k, { layout = 'rows' } = {}) => {
   return addon.edCommitRowsSync(scalarsToBuffer(scalars), k, BATCH_MUL_LAYOUTS[layout]);
 };
 
-module.exports = { batch_lincomb2, batch_mul, batch_mul_multi, ed_batch_mul, ed_batch_mul_multi, ed_batch_mul_var, ed_batch_lincomb2, ed_commit_rows, ed_set_generators, commit_rows, set_generators, batch_mul_var, compute_msm, compute_msm_edwards, set_bases, compute_msm_fixed_base, check_points, CHECK_CANONICAL, CHECK_CURVE, CHECK_SUBGROUP, CHECK_ALL, pointsToBuffer, scalarsToBuffer, version: addon.version };
+module.exports = { batch_lincomb2, batch_mul, batch_mul_multi, ed_batch_mul, ed_batch_mul_multi, ed_batch_mul_var, ed_batch_lincomb2, ed_batch_lincomb, ed_commit_rows, ed_set_generators, commit_rows, set_generators, batch_mul_var, compute_msm, compute_msm_edwards, set_bases, compute_msm_fixed_base, check_points, CHECK_CANONICAL, CHECK_CURVE, CHECK_SUBGROUP, CHECK_ALL, pointsToBuffer, scalarsToBuffer, version: addon.version };

@@ -271,6 +271,16 @@ export const ed_batch_mul_var = (points: Buffer, scalars: bigint[] | Uint32Array
 export const ed_batch_lincomb2 = (p: Buffer, q: Buffer, a: bigint[] | Uint32Array[] | Buffer, b: bigint[] | Uint32Array[] | Buffer): Buffer =>
   addon.edBatchLincomb2Sync(p, q, scalarsToBuffer(a), scalarsToBuffer(b));
 
+// Edwards-BLS12 k-term linear combination (msm377_ed_batch_lincomb): out[i] = sum_j [s_ij]P_ij, 1 to 8 terms, every output
+// its own 64-byte wire point.  `terms`: one {points, scalars} per term -- a Buffer of 64-byte wire records and the scalars.
+// n is the largest element count; an argument of exactly ONE element with n > 1 stands for all outputs.  Every curve point
+// is a legal input; a point off the curve throws, and the text names its index and its term.
+export const ed_batch_lincomb = (terms: { points: Buffer; scalars: bigint[] | Uint32Array[] | Buffer }[]): Buffer =>
+  addon.edBatchLincombSync(
+    terms.map((t) => t.points),
+    terms.map((t) => scalarsToBuffer(t.scalars)),
+  );
+
 // Row commitments (msm377_g1_set_generators / msm377_g1_commit_rows): out[i] = sum_j [s_ij]G_j over a RESIDENT set of up to
 // 4 096 generators.  set_generators builds and keeps the window tables (windowBits 0 = 8, 8, or 16 for up to 64
 // generators; an empty list drops the set); commit_rows runs over the first k generators, `scalars` the k x n matrix as one

@@ -33,6 +33,9 @@
 //   edBatchLincomb2Sync(p: Buffer 64n | 64, q: Buffer 64n | 64, a: Buffer 32n | 32, b: Buffer 32n | 32) -> Buffer 64n
 //                                                                      out[i] = [a_i]P_i + [b_i]Q_i on Edwards-BLS12
 //                                                                      (msm377_ed_batch_lincomb2)
+//   edBatchLincombSync(points: Buffer[k], scalars: Buffer[k]) -> Buffer 64n
+//                                                                      out[i] = sum_j [s_ij]P_ij on Edwards-BLS12, 1 <= k <= 8
+//                                                                      (msm377_ed_batch_lincomb); each Buffer n elements or ONE
 //   setGeneratorsSync(gens: Buffer 96k, windowBits: number): void       row commitments: build and keep the window tables of k
 //                                                                      generators (msm377_g1_set_generators); an empty Buffer
 //                                                                      drops the set
@@ -688,6 +691,70 @@ napi_value EdBatchLincomb2Sync(napi_env env, napi_callback_info info) {
   return points;
 }
 
+// edBatchLincombSync(points, scalars) -> Buffer: out[i] = sum_j [s_ij]P_ij on Edwards-BLS12 (msm377_ed_batch_lincomb); points,
+// scalars: arrays of k Buffers, 64 bytes per point and 32 per scalar; n is the largest element count, a Buffer of exactly ONE
+// element with n > 1 stands for all outputs (stride 0); n records of 64 bytes, the identity as (0, 1).  A point that is not
+// on the curve throws, with the index and the term in the text
+napi_value EdBatchLincombSync(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  uint32_t k = 0, ks = 0;
+  bool ok = napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) == napi_ok && argc >= 2;
+  for (int i = 0; ok && i < 2; i++) {
+    bool is = false;
+    ok = napi_is_array(env, argv[i], &is) == napi_ok && is;
+  }
+  ok = ok && napi_get_array_length(env, argv[0], &k) == napi_ok && napi_get_array_length(env, argv[1], &ks) == napi_ok && k == ks && k <= MSM377_LINCOMB_MAX_TERMS;
+  uint8_t* in[2][MSM377_LINCOMB_MAX_TERMS];
+  size_t len[2][MSM377_LINCOMB_MAX_TERMS];
+  for (int i = 0; ok && i < 2; i++)
+    for (uint32_t j = 0; ok && j < k; j++) {
+      napi_value el;
+      bool is = false;
+      ok = napi_get_element(env, argv[i], j, &el) == napi_ok && napi_is_buffer(env, el, &is) == napi_ok && is &&
+           napi_get_buffer_info(env, el, reinterpret_cast<void**>(&in[i][j]), &len[i][j]) == napi_ok;
+    }
+  if (!ok) {
+    napi_throw_type_error(env, nullptr, "expected (points: Buffer[], scalars: Buffer[]): at most 8 terms, one Buffer of points and one of scalars each");
+    return nullptr;
+  }
+  const size_t size[2] = {64, 32};
+  uint64_t n = 0;
+  for (int i = 0; i < 2; i++)
+    for (uint32_t j = 0; j < k; j++) {
+      ok = ok && len[i][j] % size[i] == 0;
+      if (len[i][j] / size[i] > n) n = len[i][j] / size[i];
+    }
+  msm377_lincomb_term terms[MSM377_LINCOMB_MAX_TERMS];
+  for (uint32_t j = 0; j < k; j++) {
+    const uint64_t cp = len[0][j] / 64, cs = len[1][j] / 32;
+    ok = ok && (cp == n || (cp == 1 && n > 1)) && (cs == n || (cs == 1 && n > 1));
+    terms[j] = msm377_lincomb_term{in[0][j], in[1][j], cp == n ? 64u : 0u, cs == n ? 32u : 0u};
+  }
+  if (!ok) {
+    napi_throw_range_error(env, nullptr, "64 bytes per point, 32 per scalar: in every term one element per output, or exactly one element for all outputs");
+    return nullptr;
+  }
+  napi_value points;
+  void* pd = nullptr;
+  if (napi_create_buffer(env, n * 64, &pd, &points) != napi_ok) return nullptr;
+  std::string err;
+  int rc;
+  {
+    std::lock_guard<std::mutex> lock(g_mu);
+    rc = ensure_ctx(1, &err);  // any capacity: the call walks n in passes of its own
+    if (!rc) {
+      rc = msm377_ed_batch_lincomb(g_ctx, terms, k, n, static_cast<uint8_t*>(pd));
+      if (rc) err = std::string("msm377_ed_batch_lincomb: ") + msm377_strerror(rc) + ": " + msm377_last_error(g_ctx);
+    }
+  }
+  if (rc) {
+    napi_throw_error(env, nullptr, err.c_str());
+    return nullptr;
+  }
+  return points;
+}
+
 // setGeneratorsSync(gens, windowBits): the resident generator set of commitRowsSync; an empty Buffer drops it
 napi_value SetGeneratorsSync(napi_env env, napi_callback_info info) {
   size_t argc = 2;
@@ -913,6 +980,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"edBatchMulMultiSync", nullptr, EdBatchMulMultiSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"edBatchMulVarSync", nullptr, EdBatchMulVarSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"edBatchLincomb2Sync", nullptr, EdBatchLincomb2Sync, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"edBatchLincombSync", nullptr, EdBatchLincombSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"setGeneratorsSync", nullptr, SetGeneratorsSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"commitRowsSync", nullptr, CommitRowsSync, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"edSetGeneratorsSync", nullptr, EdSetGeneratorsSync, nullptr, nullptr, nullptr, napi_default, nullptr},
